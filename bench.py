@@ -18,6 +18,11 @@ used for the barriers and the MAX / SUM of (time, units) only.
 Prints ONE JSON line (contract in the task statement).  `roofline` is computed for the dominant kernel from HIP-event durations
 taken inside the timed region on the stream the kernels run on; `cpu_baseline` times the CPU oracle (port of the reference
 algorithm, test infrastructure) on a bounded sample of the same workload on rank 0 at N=1, with 1 thread and with all cores.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K headline steps and prints their line (`value`,
+`ms_per_step`, the per-kernel times and roofline of those steps).  `--full` adds everything else: the popcount search, the sparse /
+VGA / PCIe-inclusive legs, C3, local BA (C4), the greedy matchers, C5 and the CPU baselines.  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds can be compared array by array.
 """
 import argparse
 import json
@@ -67,8 +72,14 @@ def parse_args(argv=None):
     ap.add_argument("--plumbing-fail-rank", type=int, default=-1, help="with --plumbing: this rank exits with code 3 (launcher test)")
     ap.add_argument("--master-port", type=int, default=0)
     ap.add_argument("--launcher-timeout", type=int, default=1500, help="wall-clock limit of the N-rank launcher in seconds: past it every rank is stopped")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: the popcount search, the sparse / VGA / PCIe-inclusive legs, C3, local BA, the greedy matchers, C5 and the "
+                         "CPU baselines (without it, and without an --only-* selection, the run times the headline steps and prints their line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed headline steps: what their last step computed (rank 0's 256 frames: keypoints, descriptors, matches) as DIR/<name>.npy, float32 / float64")
     a = ap.parse_args(argv)
-    if a.only_headline:
+    a.lean = not (a.full or a.only_headline or a.only_ba or a.only_greedy or a.only_c5)
+    if a.only_headline or a.lean:
         a.no_ba = a.no_c5 = a.no_extra = a.no_cpu_baseline = a.no_greedy = True
     a.no_ba_leg = a.no_ba
     if a.only_c5:
@@ -340,7 +351,7 @@ def run_plumbing(R, args):
     def fake_baseline():
         time.sleep(0.3)                                   # the other ranks are gone by now; nothing may wait for them
         return {"value": 0.0, "unit": "frames/s", "cores": 1, "kind": "port", "sample": "none (plumbing run)"}
-    finish(R, args, out, [(out, fake_baseline)])
+    finish(R, args, out, [(out, fake_baseline)] if not args.no_cpu_baseline else [])
 
 
 class Headline:
@@ -440,6 +451,32 @@ def kernel_table(avg_ms, n_kp, w=W, h=H):
     return kernels, alg, P, K
 
 
+def dump_outputs(hl, n_kp, out_dir):
+    """What the last timed step handed its caller, as float32 / float64 .npy files: every frame's keypoints and descriptors and the best / second-best /
+    ratio-tested match of each of its keypoints against the previous frame's.  Rows are the frames' keypoints in order, frame 0 first (keypoint_count
+    gives each frame's share); descriptors are their 8 uint32 words, exact in float64.  About 50 MB for the 256 frames."""
+    import numpy as np
+    ctx, v, cap, n = hl.ctx, hl.view, hl.cap, n_kp.astype(np.int64)
+    ctx.sync()
+    keep = (np.arange(cap)[None, :] < n[:, None]).reshape(-1)           # rows 0 .. count - 1 of every frame's slot of `cap` rows
+
+    def rows(ptr, dtype, width=1):
+        a = np.frombuffer(ctx_download(ctx, ptr, np.dtype(dtype).itemsize * width * BATCH * cap), dtype).reshape(BATCH * cap, width)
+        return a[keep].squeeze(1) if width == 1 else a[keep]
+    t = lambda x: x.cpu().numpy().reshape(-1)[keep]
+    out = {"keypoint_count": n.astype(np.float64), "keypoint_x": rows(v.x, np.float32), "keypoint_y": rows(v.y, np.float32),
+           "keypoint_angle": rows(v.angle, np.float32), "keypoint_octave": rows(v.octave, np.int32).astype(np.float32),
+           "descriptor_words": rows(v.desc, np.uint32, 8).astype(np.float64),
+           "best_index": t(hl.best_idx).astype(np.float32), "best_distance": t(hl.best_dist).astype(np.float32),
+           "second_distance": t(hl.second_dist).astype(np.float32), "match": t(hl.match).astype(np.float32)}
+    total = sum(a.nbytes for a in out.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the 64 MB a dump may hold" % total)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def pmc_of(kernel):
     """HBM bytes and instruction counts per launch from the committed PMC passes (tools/profile_set.sh), or None: absent, or taken on OTHER kernel
     sources than the ones in this tree (the summary carries the SHA-256 of slam-module_amd/csrc + include/; tools/build_id.py)."""
@@ -480,17 +517,20 @@ def run_gpu(R, args):
     frames_total, dt = R.aggregate(BATCH * args.steps, dt)
     value = frames_total / dt
     n_kp, n_match = hl.counts()
+    if args.dump_outputs and R.rank == 0:
+        dump_outputs(hl, n_kp, args.dump_outputs)
     kernels, alg, P, K = kernel_table(avg_ms, n_kp)
 
-    # outside the timed region: the same 256 searches on the popcount kernel (v_xor / v_bcnt), for comparison with the matrix-core one
-    ctx.set_hamming_path(1)
-    for rep in range(3):
-        if rep == 1:
-            ctx.event_mark(2)
-        hl.search()
-    ctx.event_mark(3)
-    kernels["hamming"]["popcount_kernel_ms"] = round(ctx.event_elapsed_ms(2, 3) / 2, 4)
-    ctx.set_hamming_path(0)
+    if not args.lean:
+        # outside the timed region: the same 256 searches on the popcount kernel (v_xor / v_bcnt), for comparison with the matrix-core one
+        ctx.set_hamming_path(1)
+        for rep in range(3):
+            if rep == 1:
+                ctx.event_mark(2)
+            hl.search()
+        ctx.event_mark(3)
+        kernels["hamming"]["popcount_kernel_ms"] = round(ctx.event_elapsed_ms(2, 3) / 2, 4)
+        ctx.set_hamming_path(0)
     # the unmasked search is an i8 matrix product (1 multiply-add per descriptor bit and pair): its own roofline is the dense i8 MFMA peak
     pair_ops = 2.0 * 256 * float((n_kp.astype(np.float64) * np.roll(n_kp, 1).astype(np.float64)).sum())
     kernels["hamming"]["mfma"] = {"bound": "mfma", "achieved": round(pair_ops / (avg_ms["hamming"] * 1e-3) / 1e12, 1), "peak": 5000.0, "unit": "Top/s (i8)",

@@ -20,7 +20,7 @@ def _run(*extra, env=None):
 
 
 def test_launcher_starts_two_ranks_and_reports_the_whole_job():
-    r = _run("--gpus", "2")
+    r = _run("--gpus", "2", "--full")
     assert r.returncode == 0, r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                           # ONE JSON line, printed by the parent
@@ -41,6 +41,19 @@ def test_single_rank_needs_no_launcher():
     assert r.returncode == 0, r.stderr
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 1 and out["units_total"] == 1024.0
+
+
+def test_a_plain_run_leaves_every_other_leg_to_full():
+    """Without --full (or an --only-* selection) the run times the headline steps and prints their line: no CPU baseline, no secondary leg."""
+    out = json.loads(_run().stdout.strip().splitlines()[-1])
+    assert "cpu_baseline" not in out and out["steps"] == 4 and out["warmup"] == 1
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.lean and (a.steps, a.warmup) == (7, 2) and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_ba_leg and a.no_c5 and a.no_extra and a.no_greedy
+    f = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert not f.lean and f.dump_outputs == "d" and not (f.no_cpu_baseline or f.no_ba_leg or f.no_c5 or f.no_extra or f.no_greedy)
+    assert not bench.parse_args(["--only-c5"]).no_c5                     # the profiling selections keep working without --full
 
 
 def test_a_failing_rank_fails_the_run():

@@ -100,3 +100,36 @@ def test_c3_thousand_pairs_of_2000_by_2000(oracle, ctx):
         found += int((BI[p, perms[p]] == np.arange(len(perms[p]))).sum())
         assert (m[p, perms[p]] >= 0).mean() > 0.95
     assert found >= 0.999 * P * 1400
+
+
+def test_bench_dump_outputs_are_what_the_timed_step_computed(oracle, tmp_path):
+    """`bench.py --dump-outputs DIR` after a plain run: the line is the headline's, the arrays are float32 / float64 and within 64 MB, and
+    frame 0's keypoints, descriptors and matches against frame 255 (the pairing bench.py times) are the oracle's, bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    import synth
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"),
+                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert all(k in line for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")) and line["steps"] == 3
+    assert not any(k in line for k in ("cpu_baseline", "local_ba", "c5", "vga"))                    # the other legs come with --full
+    d = {fn[:-4]: np.load(os.path.join(tmp_path, fn)) for fn in os.listdir(tmp_path)}
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20 and all(a.dtype in (np.float32, np.float64) for a in d.values())
+    n = d["keypoint_count"].astype(np.int64)
+    assert len(n) == bench.BATCH and all(len(a) == n.sum() for k, a in d.items() if k != "keypoint_count")
+    frames = synth.synth_sequences(bench.BATCH, bench.W, bench.H, 1000)
+    ocfg = oracle.cfg(levels=bench.LEVELS, scale_factor=bench.SCALE, max_kpts=bench.MAX_KPTS, fast_threshold=bench.FAST_THR)
+    want = {f: oracle.orb_extract(ocfg, frames[f]) for f in (0, bench.BATCH - 1)}
+    s = slice(0, int(n[0]))
+    assert n[0] == len(want[0]["x"])
+    for k in ("x", "y", "angle"):
+        assert np.array_equal(d["keypoint_" + k][s].view(np.uint32), want[0][k].view(np.uint32)), k
+    assert np.array_equal(d["keypoint_octave"][s], want[0]["octave"]) and np.array_equal(d["descriptor_words"][s], want[0]["desc"].astype(np.float64))
+    wi, wd, ws = oracle.hamming_best2(want[0]["desc"], want[bench.BATCH - 1]["desc"])
+    assert np.array_equal(d["best_index"][s], wi) and np.array_equal(d["best_distance"][s], wd) and np.array_equal(d["second_distance"][s], ws)
+    ok = (wd <= 50) & (np.float32(bench.LOWE_RATIO) * ws.astype(np.float32) >= wd.astype(np.float32))
+    assert np.array_equal(d["match"][s], np.where(ok, wi, -1))

@@ -41,7 +41,7 @@ def test_two_ranks_on_one_gpu_check_their_own_outputs_against_the_oracle():
 
 def test_bench_launcher_runs_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2 --ranks-share-gpu` as the driver would start it (small legs): one line, n_gpus 2, both ranks' rates, BA and C5 on both ranks."""
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--ranks-share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-greedy",
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--ranks-share-gpu", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-greedy",
            "--ba-batch", "4", "--ba-steps", "1", "--c5-frames", "10", "--c5-distinct", "5", "--launcher-timeout", "400"]
     env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=480, env=env)

@@ -13,9 +13,9 @@ cd /tmp && export TMPDIR=/tmp
 # unprofiled bench line gets from the library (two per context: 16 for the 8 sequences of its C5 leg), and the bench line says which applied (c5.hw_queues)
 export GPU_MAX_HW_QUEUES=16
 if [ -z "$SKIP_HEAD" ]; then      # SKIP_HEAD=1: the bench line, the kernel stats and the front-end counter passes are already in $O; do the calibration and the BA passes
-python3 "$R/bench.py" > "$O/bench_default.json" 2> "$O/bench_default.err"
+python3 "$R/bench.py" --full > "$O/bench_default.json" 2> "$O/bench_default.err"
 echo "bench done"
-rocprofv3 --kernel-trace --stats -d "$O/stats" -o p --output-format csv -- python3 "$R/bench.py" --no-cpu-baseline > "$O/bench_under_rocprof.json" 2> "$O/rocprof.err"
+rocprofv3 --kernel-trace --stats -d "$O/stats" -o p --output-format csv -- python3 "$R/bench.py" --full --no-cpu-baseline > "$O/bench_under_rocprof.json" 2> "$O/rocprof.err"
 echo "stats done"
 # the same headline region alone (23 launches of every front-end kernel, all of them 256-frame batches): per-kernel averages that can be held
 # against the bench line's HIP-event times (the full command above also launches the kernels once per frame in its C5 leg)
@@ -88,5 +88,5 @@ PY
 # the bench line once more, now that the counters of THESE sources exist: the line of the set quotes them (roofline.traffic, valu_issue_frac) instead of withholding
 # the numbers of an older tree (bench.py compares src_sha256); the snapshot's own copy of the summary is replaced, nothing outside the scratch tree is touched
 cp "$O/pmc_traffic.json" "$R/$(grep -o '"profiles", "r[0-9]*_pmc_traffic.json"' "$R/bench.py" | head -1 | sed 's/"profiles", "/profiles\//; s/"$//')"      # (the file bench.py's PMC_FILE names)
-python3 "$R/bench.py" > "$O/bench_default.json" 2> "$O/bench_default.err"
+python3 "$R/bench.py" --full > "$O/bench_default.json" 2> "$O/bench_default.err"
 echo "bench line with this set's counters done"
