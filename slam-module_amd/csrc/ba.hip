@@ -49,10 +49,7 @@ constexpr int kMaxFreePosesTeam = 2048;   // ... and the factorisation is spread
 constexpr int kMaxTeam = 64;         // workgroups that may share one problem
 constexpr size_t kBaCacheSlack = 8;  // a kept device block serves a request of at least 1/8 of its size
 constexpr size_t kBaCacheMaxBytes = (size_t)1 << 30;   // blocks kept per context for the next ms_ba_create: 1 GiB in total, larger ones are freed at destroy
-#ifndef MS_BA_LDS_KB
-#define MS_BA_LDS_KB 150                  // -DMS_BA_LDS_KB=78 -DMS_FS_OB=32 -DMS_BA_WAVES_PER_EU=4: the two-windows-per-CU build of tools/ba_occupancy_probe.py
-#endif
-constexpr size_t kLdsBytes = (size_t)MS_BA_LDS_KB * 1024;  // max(Schur staging 8 x 9 KB, Cholesky panel (n+1) x 16 doubles + x (n doubles))
+constexpr size_t kLdsBytes = (size_t)150 * 1024;  // max(Schur staging 8 x 9 KB, Cholesky panel (n+1) x 16 doubles + x (n doubles))
 
 // One set of passes of the fused Schur phase.  A pass owns the free-pose rows [row0, row1) of S: their envelope part lives in an
 // LDS tile while every point that observes one of these poses adds its block products; points are packed into batches of
@@ -429,10 +426,7 @@ __device__ __forceinline__ void group_sync(const BaProb &P, uint32_t *counter, u
     }
     __syncthreads();
 }
-#ifndef MS_TEAM_NO_FENCE
-#define MS_TEAM_NO_FENCE 0          /* -DMS_TEAM_NO_FENCE=1: k_ba_lm's team barriers without the agent-scope write-back / invalidate (WRONG results; timing A/B of tools/beside_probe.py) */
-#endif
-__device__ __noinline__ void team_sync(const BaProb &P) { group_sync<!MS_TEAM_NO_FENCE>(P, P.bar, (uint32_t)P.team); }
+__device__ __noinline__ void team_sync(const BaProb &P) { group_sync(P, P.bar, (uint32_t)P.team); }
 __device__ __noinline__ void team_sync_light(const BaProb &P, int team) { group_sync<false>(P, P.bar, (uint32_t)team); }
 // barrier of the first P.chol_team workgroups only (the distributed factorisation), on a counter of its own (P.bar + 32: another 128-byte line)
 __device__ __noinline__ void chol_sync(const BaProb &P) { group_sync(P, P.bar + 32, (uint32_t)P.chol_team); }
@@ -563,12 +557,6 @@ __device__ __noinline__ double linearise_stream(const BaProb &P_, double *lds_v)
 #pragma unroll
         for (int a = 0; a < 6; ++a) Jw[a] = wi * Jl[a];
         MS_LDS double *t = ptab + 9 * l;
-#if MS_LIN_ABL == 1           /* timing ablation (wrong results): plain stores instead of LDS atomics */
-        t[0] = fma(Jw[0], Jl[0], Jw[3] * Jl[3]); t[1] = fma(Jw[0], Jl[1], Jw[3] * Jl[4]); t[2] = fma(Jw[0], Jl[2], Jw[3] * Jl[5]);
-        t[3] = fma(Jw[1], Jl[1], Jw[4] * Jl[4]); t[4] = fma(Jw[1], Jl[2], Jw[4] * Jl[5]); t[5] = fma(Jw[2], Jl[2], Jw[5] * Jl[5]);
-        for (int a = 0; a < 3; ++a) t[6 + a] = -fma(Jw[a], e[0], Jw[3 + a] * e[1]);
-        return;
-#endif
         lds_addd(t + 0, fma(Jw[0], Jl[0], Jw[3] * Jl[3])); lds_addd(t + 1, fma(Jw[0], Jl[1], Jw[3] * Jl[4])); lds_addd(t + 2, fma(Jw[0], Jl[2], Jw[3] * Jl[5]));
         lds_addd(t + 3, fma(Jw[1], Jl[1], Jw[4] * Jl[4])); lds_addd(t + 4, fma(Jw[1], Jl[2], Jw[4] * Jl[5])); lds_addd(t + 5, fma(Jw[2], Jl[2], Jw[5] * Jl[5]));
 #pragma unroll
@@ -828,34 +816,15 @@ __device__ __noinline__ void backsub_stream(const BaProb &P_, double lambda_, do
 }
 
 // ---------------------------------------------------------------- linearisation
-#ifndef MS_LIN_ABL
-#define MS_LIN_ABL 0
-#endif
-#ifndef MS_BA_NO_FUSED_TRIAL
-#define MS_BA_NO_FUSED_TRIAL 0  // 1: k_ba_lm never fuses a trial's chi2 with the next linearisation (A/B builds)
-#endif
-#ifndef MS_LIN_NO_STREAM
-#define MS_LIN_NO_STREAM 0          /* -DMS_LIN_NO_STREAM=1: round 3's per-pose pass over index chains (A/B runs) */
-#endif
-#ifdef MS_LIN_PROF
-__device__ long long g_lin[32 * 8 * 6];
-extern "C" int ms_debug_linprof(long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lin), sizeof(g_lin)); }
-#define LINP(i) do { if (lane == 0 && rank_ < 32) g_lin[(rank_ * 8 + wave) * 6 + i] = clock64() - lin_t0; } while (0)
-#else
-#define LINP(i) do { } while (0)
-#endif
 // chi2_share (optional): the linearisation visits every edge at the current state anyway -- when the caller wants the robust chi2 of that state (a trial of the fused
 // schedule in k_ba_lm), every thread's share of it is added here (streamed, one-workgroup path only: the caller checks lin_streams())
 __device__ __forceinline__ bool lin_streams(const BaProb &P) {      // build_system takes the streamed path (linearise_stream) for this problem on ONE workgroup
-    return P.fused && 9 * (size_t)P.n_point + 64 <= kLdsBytes / 8 && P.fo_lo != nullptr && !MS_LIN_NO_STREAM;
+    return P.fused && 9 * (size_t)P.n_point + 64 <= kLdsBytes / 8 && P.fo_lo != nullptr;
 }
 __device__ __noinline__ void build_system(const BaProb &P_, double *lds_, double *chi2_share = nullptr) {
     const BaProb &P = P_;
     BA_IDS
     const int n6 = P.n6;
-#ifdef MS_LIN_PROF
-    const long long lin_t0 = clock64();
-#endif
     if (P.fused) {
         // Hpp is its diagonal blocks and the lower blocks of the pose-pose edges: only those row pieces are written below, read by the Schur pass and cleared here (the
         // rest of the n6 x n6 array keeps the zeros it was created with; round 3 cleared all of it, 720 KB per window and iteration)
@@ -868,9 +837,7 @@ __device__ __noinline__ void build_system(const BaProb &P_, double *lds_, double
     } else
     for (size_t i = gt; i < (size_t)n6 * n6; i += GT) P.Hpp[i] = 0;
     for (int i = gt; i < n6; i += GT) P.bp[i] = 0;
-    LINP(0);
     team_sync(P);
-    LINP(1);
     // A team on a window whose sums fit the LDS: a THREAD PER OBSERVATION, once.  Workgroup r takes the points [n r / T, n (r+1) / T) and with them a
     // contiguous run of the point-major observation list; each thread evaluates its observation (error, both Jacobians) and adds the point's
     // Hll / bl terms and the pose's diagonal-block / gradient terms into two LDS tables with ds_add_f64.  The point table goes out with plain
@@ -962,7 +929,7 @@ __device__ __noinline__ void build_system(const BaProb &P_, double *lds_, double
     // every observation twice: 260 k + 340 k cycles of a 760 k-cycle linearisation.
     const bool one_pass = T_ == 1 && !obs_par && P.fused && 9 * (size_t)P.n_point + 64 <= kLdsBytes / 8;
     MS_LDS double *ptab1 = (MS_LDS double *)lds_;
-    const bool stream = one_pass && P.fo_lo != nullptr && !MS_LIN_NO_STREAM;
+    const bool stream = one_pass && P.fo_lo != nullptr;
     if (stream) { const double share = linearise_stream(P, lds_); if (chi2_share) *chi2_share += share; }
     if (one_pass && !stream) {
         for (int i = tid; i < 9 * P.n_point; i += NT) ptab1[i] = 0;
@@ -1030,7 +997,6 @@ __device__ __noinline__ void build_system(const BaProb &P_, double *lds_, double
 #pragma unroll
         for (int a = 0; a < 3; ++a) P.bl[3 * (size_t)l + a] = b[a];
     }
-    LINP(2);
     // per free pose: Hpp diagonal block + bp (a wave per pose, lanes over its observations).  A team cuts every pose's observations into
     // slices so that all its waves have work, adds the slices' sums with fp64 atomics, and lets the first waves take the SE3 edges at the
     // same time (one wave per edge, ~27 k cycles each): both only ADD into Hpp / bp, so no barrier is needed between them.
@@ -1096,7 +1062,6 @@ __device__ __noinline__ void build_system(const BaProb &P_, double *lds_, double
             }
         }
     }
-    LINP(3);
     if (one_pass && !stream) {                                     // the point table leaves the LDS before the SE3 edges take it over
         __syncthreads();
         for (int i = tid; i < 9 * P.n_point; i += NT) {
@@ -1223,9 +1188,7 @@ __device__ __noinline__ void build_system(const BaProb &P_, double *lds_, double
             __syncthreads();
         }
     }
-    LINP(4);
     team_sync(P);
-    LINP(5);
 }
 
 // The (observation a, observation b) pairs of a chunk, one per record piece this lane moves (9 pieces per lane) ...
@@ -1392,10 +1355,7 @@ __device__ __noinline__ void schur_segments(const BaProb &P_, double *lds_) {
 // slab, then the lanes take the batch's (a, b) pairs and subtract Z_a Z_b^T (= W_a (Hll + lambda I)^-1 W_b^T) from block
 // (pose a, pose b) of the tile with LDS atomics.  Per damped solve the pass reads the 32 bytes of every observation (once per
 // pass its point touches) instead of 288 bytes per PAIR.  The sums are no longer in a fixed order (LDS atomics), like the SE3-edge sums.
-#ifndef MS_FS_OB
-#define MS_FS_OB 64
-#endif
-constexpr int FS_OB = MS_FS_OB;                                  // observations (lanes) per batch
+constexpr int FS_OB = 64;                                        // observations (lanes) per batch
 constexpr int FS_ZD = 14;                                        // doubles per slab entry: Z_a = Jp_a^T G_a is kept as its factors, G (2 x 3) and the 8 entries of Jp that are neither zero nor repeated
 constexpr int kFsStageDoubles = NW * FS_OB * FS_ZD;              // slabs of the 8 waves: 57,344 B
 constexpr int kFsMetaDoubles = NW * FS_OB / 2;                   // free-pose index per lane: 2,048 B
@@ -1408,32 +1368,6 @@ __device__ __forceinline__ void lds_sub(MS_LDS double *p, double v) {
     (void)__hip_atomic_fetch_add(p, -v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);       // ds_add_f64
 }
 
-// Stamps inside schur_fused (build with BA_EXTRA=-DMS_FS_PROF, read with tools/ba_schur_prof.py): per-wave cycle sums of workgroup 0, kept in registers and written once per call:
-// 0 hand-out, 1 top of the batch (index loads issued), 2 Jacobians + slab stores, 3 pair products, 4 last flush, 5 batches, 6 next batch's lane values requested, 7 single pairs / enumerated pairs
-#ifdef MS_FS_PROF
-__device__ long long g_fsprof[NW * 8];
-extern "C" int ms_debug_fsprof(long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fsprof), sizeof(g_fsprof)); }
-#define FSP_DECL long long fst = clock64(), fsacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define FSP(i) do { const long long _t = clock64(); fsacc[i] += _t - fst; fst = _t; } while (0)
-#if MS_FS_PROF > 1
-#define FSP_WAIT_VM asm volatile("s_waitcnt vmcnt(0)" ::: "memory")      /* -DMS_FS_PROF=2: the wait for the batch's loads gets a stamp of its own (and is forced to sit there) */
-#else
-#define FSP_WAIT_VM do { } while (0)
-#endif
-#define FSP_FLUSH do { if (blockIdx.x == 0 && lane == 0) { for (int i = 0; i < 8; ++i) g_fsprof[wave * 8 + i] += fsacc[i]; } } while (0)
-#else
-#define FSP_DECL
-#define FSP(i) do { } while (0)
-#define FSP_WAIT_VM do { } while (0)
-#define FSP_FLUSH do { } while (0)
-#endif
-#ifndef MS_FS_PROCEDURAL
-#define MS_FS_PROCEDURAL 1
-#endif
-#ifndef MS_FS_ABL
-#define MS_FS_ABL 0
-#endif
-constexpr bool kProceduralPairs = MS_FS_PROCEDURAL != 0;         // batches of equal pose sets carry no pair list (-DMS_FS_PROCEDURAL=0: lists for every batch, for A/B runs)
 template <bool PROCEDURAL, bool POSE_LDS>    // PROCEDURAL: the pass set has batches without pair lists (fmt < 0).  Two copies of the function: the enumeration code in the pair loop cost the
                               // list-only launches (256 windows, one workgroup each) 5 % through register allocation alone, whether or not it ever ran
                               // POSE_LDS: every pose vertex of the window fits the LDS table (n_pose <= kFsPoseTab).  A template parameter, not a branch: where a value may come from
@@ -1546,7 +1480,6 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
         int ykey = -1;
         // runs per hand-out: a row pass of a team has ~75 batches per workgroup (runs of 1 / 2 / 3 / 4 / 5 / 7 gave 2.22 / 2.08 / 2.00 / 1.99 / 1.96 / 1.98 ms per C4 window:
         // fewer block flushes against a longer tail); a pass that owns points has ~10, one at a time
-        FSP_DECL
         // One stream of batches per wave, every batch's operands requested while the batch before it is worked on (round 4: with everything fetched at the top of
         // a batch a wave of the 256-window launch waited 5.2 k cycles per batch for memory -- 270 MB of windows stream from HBM in every pass --, 29 % of the pass):
         // the next batch's lane records and run table entry go out before the Jacobians, its point and observation values (15 doubles per lane) before the pair
@@ -1586,7 +1519,6 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
         if (b < pb1) { rec = pobs4[FS_OB * b + lane]; fmt = b_fmt[b]; run0 = b_run[b]; run1 = b_run[b + 1]; fetch_lane(rec, FS_OB * b + lane, cur); }
         __builtin_amdgcn_s_waitcnt(0x0F70);                         // vmcnt(0), as an instruction the compiler's counter tracking sees: otherwise the loop's first use of run0 waits for "everything" in EVERY
                                                                    // iteration (the first batch's lane values are younger than it), and with it for the loads the loop has just issued
-        FSP(0);
         while (b < pb1) {
             // this batch's lane values were requested before the previous batch's pair products: they are here.  Saying so BEFORE the next loads go out keeps the compiler's
             // wait in front of the Jacobians from covering those as well (the loads below sit in branches, so it would wait for "all of them")
@@ -1611,7 +1543,6 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
             i4_t rec_n = pobs4[FS_OB * bc + lane];
             const int fmt_n = b_fmt[bc], run0_n = b_run[bc], run1_n = b_run[bc + 1];
             if (bn >= pb1) rec_n.x = -1;
-            FSP_WAIT_VM; FSP(1);
             const double (&X)[3] = cur.X, (&blv)[3] = cur.bl, (&H)[6] = cur.H, (&uv)[2] = cur.uv;
             const double info = cur.info;
             if (act) {
@@ -1664,10 +1595,8 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            FSP(2);
             LaneData nxt;
             fetch_lane(rec_n, FS_OB * bc + lane, nxt);
-            FSP(6);
             auto take_block = [&](unsigned ab) {                      // the block of pair ab becomes the lane's current one: the old sum goes out first
                 const int k2 = (meta[ab & 255u] << 16) | meta[ab >> 8];
                 if (k2 != key) {
@@ -1679,7 +1608,7 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
 #pragma unroll
                         for (int i = 0; i < 6; ++i)
 #pragma unroll
-                            for (int j = 0; j < 6; ++j) { if (!(MS_FS_ABL & 8)) lds_sub(blk + i * len + j, acc[6 * i + j]); acc[6 * i + j] = 0; }
+                            for (int j = 0; j < 6; ++j) { lds_sub(blk + i * len + j, acc[6 * i + j]); acc[6 * i + j] = 0; }
                     }
                     key = k2;
                 }
@@ -1687,19 +1616,8 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
             auto add_pair = [&](unsigned ab) {
                 const MS_LDS d2_t *za = (const MS_LDS d2_t *)(stage + (ab & 255u) * FS_ZD), *zb = (const MS_LDS d2_t *)(stage + (ab >> 8) * FS_ZD);
                 double A[FS_ZD], B[FS_ZD];
-#if (MS_FS_ABL & 3) == 2          /* timing ablation (wrong results): no slab reads */
-#pragma unroll
-                for (int q = 0; q < FS_ZD; ++q) { A[q] = acc[q] * 1e-300; B[q] = acc[q + 14] * 1e-300; }
-                (void)za; (void)zb;
-#else
 #pragma unroll
                 for (int q = 0; q < FS_ZD / 2; ++q) { const d2_t u = za[q], v = zb[q]; A[2 * q] = u.x; A[2 * q + 1] = u.y; B[2 * q] = v.x; B[2 * q + 1] = v.y; }
-#endif
-#if (MS_FS_ABL & 3) == 1          /* timing ablation (wrong results): slab reads, no products */
-#pragma unroll
-                for (int q = 0; q < FS_ZD; ++q) acc[q] += A[q] + B[q];
-                return;
-#endif
                 double M[4], T0[6], T1[6];                                 // M = G_a G_b^T, T = M Jp_b
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
@@ -1736,7 +1654,6 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
                 }
             }
             if (single != 0xFFFFu) { take_block(single); add_pair(single); }
-            FSP(7);
             for (int run = run_lo + lane; run < run_hi; run += 64) {
                 u4_t nx = chunks[min(run + 64, run_hi - 1)];
                 if (!(run + 64 < run_hi)) nx = u4_t{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
@@ -1752,10 +1669,6 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            FSP(3);
-#ifdef MS_FS_PROF
-            fsacc[5] += 1;
-#endif
             rec = rec_n; cur = nxt; fmt = fmt_n; run0 = run0_n; run1 = run1_n; b = bn;
         }
         if (key >= 0) {
@@ -1772,7 +1685,6 @@ __device__ __noinline__ void schur_fused(const BaProb &P_, double lambda_, doubl
 #pragma unroll
             for (int r = 0; r < 6; ++r) lds_sub(tile + yoff + 6 * (ykey - r0) + r, yacc[r]);
         }
-        FSP(4); FSP_FLUSH;
         const long long tp2 = clock64();
         __syncthreads();
         cyc[6] += clock64() - tp2;
@@ -2172,18 +2084,6 @@ __device__ __noinline__ void cholesky_solve(const BaProb &P_, double *lds_) {
 // that are not factored yet -- is a handful of blocks: they are kept as W x W tiles of 16 x 16 doubles in LDS (slots assigned by the
 // host, a block keeps its slot while it is active), every tile is read from S once when its later block enters, updated in LDS
 // (v_mfma_f64_16x16x4_f64, operands from LDS), and written once when its column is factored.  The rhs is forward-substituted along.
-// Stamps inside cholesky_window (build with -DMS_CW_PROF, read with tools/ba_chol_prof.py): per-thread cycle sums in registers, thread 0's and
-// thread 64's written out once per call (a stamp that went through memory cost a round trip of its own and drained the prefetches it was meant to time).
-#ifdef MS_CW_PROF
-__device__ long long g_cwprof[48];
-#define CWP_DECL long long cwt = clock64(), cwacc[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define CWP(i) do { const long long _t = clock64(); cwacc[i] += _t - cwt; cwt = _t; } while (0)
-#define CWP_FLUSH do { if (tid == 0) { for (int i = 0; i < 24; ++i) g_cwprof[i] += cwacc[i]; g_cwprof[7] += 1; } if (tid == 64) { for (int i = 0; i < 24; ++i) g_cwprof[24 + i] += cwacc[i]; } } while (0)
-#else
-#define CWP_DECL
-#define CWP(i) do { } while (0)
-#define CWP_FLUSH do { } while (0)
-#endif
 constexpr int CT_LD = 18;                 // doubles per tile row (16 + 2: the 32-byte operand reads of 16 rows fall into different banks)
 constexpr int CT = 16 * CT_LD;            // doubles per tile
 // ML: the per-panel index arrays (slots, active blocks, entering tiles) are copied to LDS first -- every step below starts from them, and as global
@@ -2219,7 +2119,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
     } else { slot = gslot; act_start = gact_start; act = gact; load_start = gload_start; loads = gloads; }
     if constexpr (!ZG) for (int i = tid; i < ((n + 15) & ~15); i += NT) z[i] = i < n ? P.y[i] : 0.0;
     if constexpr (ML) { if (tid < 16) dvec[((n + 15) & ~15) - 16 + tid] = 0.0; }      // (the pad of the last block; the pivots overwrite the rest)
-    CWP_DECL
     auto fetch_tiles = [&](int pnl, int skip) {               // tiles entering the window at panel pnl: S -> LDS, one tile per wave and trip (waves 1..7; wave 0 factors)
         for (int e = load_start[pnl] + skip + wave - 1; e < load_start[pnl + 1]; e += NW - 1) {
             const int ea = loads[2 * e], eb = loads[2 * e + 1], bi = ea & 0xFFFF, si = ea >> 16, bj = eb & 0xFFFF, sj = eb >> 16;
@@ -2237,9 +2136,7 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
         const int c0 = 16 * pnl, nb = min(16, n - c0), sp = slot[pnl];
         MS_LDS double *Lpp = tiles + (sp * W + sp) * CT;
         double r[NB], di;
-        CWP(3);
         const bool ok = chol_factor_diag<CT_LD>((const double *)Lpp, nb, lane, r, di);
-        CWP(14);
         // L11 into the tile (the garbage above the diagonal goes along: nothing reads it) and transposed into LT: column j of L11 as a contiguous row for phase A
         if (lane < NB) {
 #pragma unroll
@@ -2299,7 +2196,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
             publish(0, r, di, ok);
         }
         __syncthreads();
-        CWP(0);
         for (int p = 0; p < nblk; ++p) {
             if (tid == NT - 1 && (p & 7) == 0) team_heartbeat(P);            // (a lane of the last wave: wave 0 carries the pivot chain)
             const int c0 = 16 * p, nb = min(16, n - c0), sp = slot[p];
@@ -2372,9 +2268,7 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     }
                 }
             }
-            CWP(1);
             __syncthreads();
-            CWP(2);
             if (wave == 0) {
                 if (has_next) {
 #pragma unroll
@@ -2382,7 +2276,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     const bool ok = chol_factor_regs(r, nb1, ln, di);
                     publish(p + 1, r, di, ok);
                 }
-                CWP(4);
             } else {
                 // trailing update: pair q of the lower triangle of the m active blocks (row-major: (0,0), (1,0), (1,1), (2,0) ...) goes to wave 1 + q % 7;
                 // (0,0) is the next diagonal tile when block p+1 is active already -- wave 0 has it
@@ -2395,7 +2288,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     if (next_active && q == 0) continue;
                     update_pair(act[a0 + i] >> 16, act[a0 + j] >> 16, sp);
                 }
-                CWP(19);
                 const int t7 = tid - 64, N7 = NT - 64;
                 for (int idx = t7; idx < 16 * m; idx += N7) {         // the rhs below the panel: z_b -= L[b,p] z_p
                     const int ea = act[a0 + (idx >> 4)], gr = 16 * (ea & 0xFFFF) + (idx & 15);
@@ -2409,7 +2301,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     for (int k = 0; k < NB; ++k) sacc -= ((k & 1) ? rv[k / 2].y : rv[k / 2].x) * z[c0 + k];
                     z[gr] = sacc;
                 }
-                CWP(20);
                 // column p of L goes out: tile wave-1 (+7 ...) of the panel's m + 1, four rows of 16 per lane and trip
                 for (int t = wave - 1; t <= m; t += NW - 1) {
                     const int ea = t == 0 ? (p | (sp << 16)) : act[a0 + t - 1];
@@ -2423,16 +2314,13 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                         if (gr < n && ln < nb && (t > 0 || ln <= rr)) Sw[(size_t)gr * n + c0 + ln] = v[k];
                     }
                 }
-                CWP(21);
                 if (pf_dst >= 0) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) tiles[pf_dst + 4 * k * CT_LD] = pf[k];
                 }
-                CWP(22);
                 if (has_next) fetch_tiles(p + 1, NW - 1);             // a front that brings in more than seven tiles at once: the rest the plain way
             }
             __syncthreads();
-            CWP(5);
         }
     } else {
         if (nblk > 0 && wave > 0) fetch_tiles(0, 0);
@@ -2445,7 +2333,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
         __syncthreads();
         if (wave == 0 && nblk > 0) factor_diag(0);
         __syncthreads();
-        CWP(0);
         for (int p = 0; p < nblk; ++p) {
             if (tid == NT - 1 && (p & 7) == 0) team_heartbeat(P);
             const int c0 = 16 * p, nb = min(16, n - c0), sp = slot[p];
@@ -2496,9 +2383,7 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                 MS_LDS d2_t *row2 = reinterpret_cast<MS_LDS d2_t *>(row);
     #pragma unroll
                 for (int j = 0; j < NB / 2; ++j) { const d2_t v = row2[j]; x[2 * j] = v.x; x[2 * j + 1] = v.y; }
-                CWP(15);
                 solve_row(x);
-                CWP(16);
                 if (nb == NB) {
     #pragma unroll
                     for (int j = 0; j < NB / 2; ++j) row2[j] = d2_t{x[2 * j], x[2 * j + 1]};
@@ -2506,7 +2391,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
     #pragma unroll
                     for (int j = 0; j < NB; ++j) if (j < nb) row[j] = x[j];
                 }
-                CWP(17);
             }
             if (ZG && tid == NT - 1) {
                 double x[NB];
@@ -2516,9 +2400,7 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
     #pragma unroll
                 for (int j = 0; j < NB; ++j) if (j < nb) z[c0 + j] = x[j];
             }
-            CWP(1);
             __syncthreads();
-            CWP(2);
             // B. look-ahead: wave 0 brings the NEXT diagonal tile up to date (its update by this panel, or its first fetch) and factors it at
             //    once -- the serial pivot chain runs beside the trailing update, the rhs update, the write-back of column p and the fetch of the
             //    tiles that enter at the next panel, which the other seven waves share
@@ -2538,9 +2420,7 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     }
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    CWP(3);
                     factor_diag(p + 1);
-                    CWP(4);
                 }
             } else {
                 // the tiles that enter at the next panel are requested FIRST and parked in registers: their trip to L2 runs beside the updates
@@ -2554,7 +2434,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
     #pragma unroll
                     for (int k = 0; k < 4; ++k) { const int gr = 16 * bi + (lane >> 4) + 4 * k; if (gr < n && gc < n) pf[k] = Sg[(size_t)gr * n + gc]; }
                 }
-                CWP(18);
                 // trailing update: pair q of the lower triangle of the m active blocks (row-major: (0,0), (1,0), (1,1), (2,0) ...) goes to wave 1 + q % 7;
                 // (0,0) is the next diagonal tile when block p+1 is active already -- wave 0 has it
                 {
@@ -2568,7 +2447,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                         update_pair(act[a0 + i] >> 16, act[a0 + j] >> 16, sp);
                     }
                 }
-                CWP(19);
                 const int t7 = tid - 64, N7 = NT - 64;
                 for (int idx = t7; idx < 16 * m; idx += N7) {         // the rhs below the panel: z_b -= L[b,p] z_p
                     const int ea = act[a0 + (idx >> 4)], gr = 16 * (ea & 0xFFFF) + (idx & 15);
@@ -2587,7 +2465,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     }
                     z[gr] = sacc;
                 }
-                CWP(20);
                 // column p of L goes out: tile wave-1 (+7 ...) of the panel's m + 1, four rows of 16 per lane and trip
                 for (int t = wave - 1; t <= m; t += NW - 1) {
                     const int ea = t == 0 ? (p | (sp << 16)) : act[a0 + t - 1], c = lane & 15;
@@ -2601,17 +2478,13 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                         if (gr < n && c < nb && (t > 0 || c <= r)) Sw[(size_t)gr * n + c0 + c] = v[k];
                     }
                 }
-                CWP(21);
                 if (pf_dst >= 0) {
     #pragma unroll
                     for (int k = 0; k < 4; ++k) tiles[pf_dst + 4 * k * CT_LD] = pf[k];
                 }
-                CWP(22);
                 if (p + 1 < nblk) fetch_tiles(p + 1, NW - 1);     // a front that brings in more than seven tiles at once: the rest the plain way
             }
-            if (wave != 0) CWP(23);
             __syncthreads();
-            CWP(5);
         }
     }
     // back substitution L^T x = z, panels in reverse, again in LDS: column p of L (the tiles this loop wrote out above) comes back one panel
@@ -2643,7 +2516,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
         const int ln = lane & 15;
         for (int q = nblk - 1; q >= nblk - 2 && q >= 0; --q) fetch_col(q, q % 3, 0, false);
         __syncthreads();
-        CWP(6);
         double xprev = 0;
         bool adjacent = false;                                 // block p+1 is coupled to panel p (the last panel has nothing below it)
         for (int p = nblk - 1; p >= 0; --p) {
@@ -2660,7 +2532,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     for (int k = 0; k < 4; ++k) { const int r = (lane >> 4) + 4 * k, gr = 16 * b + r; if (gr < n && gc < n && (wave > 0 || c < r)) pf[k] = Sg[(size_t)gr * n + gc]; }
                 }
             };
-            CWP(8);
             if (wave == 0) {
                 // everything this step reads is addressed without the index lists (they were read a step ago): the loads go out together
                 const MS_LDS double *T0 = tiles + ((p % 3) * W) * CT, *T1 = T0 + CT;
@@ -2680,7 +2551,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                 if (lane < NB) z[c0 + lane] = xprev;
                 adjacent = firstn == p;
                 request_tile();
-                CWP(10);
             } else {
                 request_tile();
                 if (wave == 1 && p > 0) {
@@ -2699,7 +2569,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     if (lane < NB) z[16 * q + lane] -= (part[lane] + part[16 + lane]) + (part[32 + lane] + part[48 + lane]);
-                    CWP(10);
                 }
             }
             if (pf_dst >= 0) {
@@ -2707,19 +2576,14 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
                 for (int k = 0; k < 4; ++k) tiles[pf_dst + 4 * k * CT_LD] = pf[k];
             }
             if (p > 1) fetch_col(p - 2, (p - 2) % 3, NW, false);
-            CWP(11);
             __syncthreads();
-            CWP(12);
         }
         for (int i = tid; i < n; i += NT) P.dp[i] = z[i];
         __syncthreads();
-        CWP(13);
-        CWP_FLUSH;
         return;
     }
     if (nblk > 0) fetch_col(nblk - 1, 0, 0, true);
     __syncthreads();
-    CWP(6);
     for (int p = nblk - 1; p >= 0; --p) {
         const int c0 = 16 * p, nb = min(16, n - c0), buf = (nblk - 1 - p) & 1;
         const int a0 = act_start[p], m = act_start[p + 1] - a0;
@@ -2750,9 +2614,7 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
             }
             part[tid] = sum;
         }
-        CWP(8);
         __syncthreads();
-        CWP(9);
         if (wave == 0) {
             const MS_LDS double *T0 = tiles + (buf * W) * CT;
             double rr = 0, di = 0, col[NB];
@@ -2774,7 +2636,6 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
             }
             if (lane < nb) z[c0 + lane] = rr * di;
         }
-        CWP(10);
         if (pf_dst >= 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) tiles[pf_dst + 4 * k * CT_LD] = pf[k];
@@ -2783,18 +2644,11 @@ __device__ __noinline__ void cholesky_window(const BaProb &P_, double *lds_) {
             if (wave == NW - 1 && lane < 16) dv[16 * (buf ^ 1) + lane] = pf_dv;
             fetch_col(p - 1, buf ^ 1, NW, false);
         }
-        CWP(11);
         __syncthreads();
-        CWP(12);
     }
     for (int i = tid; i < n; i += NT) P.dp[i] = z[i];
     __syncthreads();
-    CWP(13);
-    CWP_FLUSH;
 }
-#ifdef MS_CW_PROF
-extern "C" int ms_debug_cwprof(long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cwprof), sizeof(long long) * 48); }
-#endif
 
 // The same factorisation for systems whose panel does not fit the LDS (more than kMaxFreePoses free poses: global bundle
 // adjustment, bundle_adjuster.cpp:493-604), spread over the team: the row tiles of a panel are updated by all waves of all
@@ -2909,7 +2763,7 @@ __device__ bool solve_step(const BaProb &P, double lambda, double *lds, long lon
     const bool ok = s_sound != 0;
     __syncthreads();
     if (!ok) return false;
-    if (fused && P.team == 1 && P.fo_lo != nullptr && 3 * (size_t)P.n_point + 7 * (size_t)P.n_pose + 6 * (size_t)P.np_free <= kLdsBytes / 8 && !MS_LIN_NO_STREAM) backsub_stream(P, lambda, lds);
+    if (fused && P.team == 1 && P.fo_lo != nullptr && 3 * (size_t)P.n_point + 7 * (size_t)P.n_pose + 6 * (size_t)P.np_free <= kLdsBytes / 8) backsub_stream(P, lambda, lds);
     else if (fused) point_backsub_fused(P, lambda, lds); else point_backsub(P);
     cyc[4] += clock64() - t0;
     return true;
@@ -2957,16 +2811,11 @@ __global__ __launch_bounds__(256) void k_ba_copy_state(const BaProb *dst, const 
 }
 
 // grid = problems x team workgroups; workgroup b works on problem b / team
-#ifdef MS_BA_WAVES_PER_EU
-#define MS_BA_OCC __attribute__((amdgpu_waves_per_eu(MS_BA_WAVES_PER_EU, MS_BA_WAVES_PER_EU)))
-#else
-#define MS_BA_OCC
-#endif
 // alt (one workgroup per problem, streamed phases; else nullptr): the same problems with the linearisation's outputs -- Hpp, bp, Hll, bl -- pointing at a SECOND set of
 // arrays.  The chi2 of a trial state and the linearisation of the next iteration walk the same observations at the same state when the trial is accepted: a trial
 // then linearises into the set that is not in use and takes its chi2 from the same pass (build_system's chi2_share); accepted, the two descriptors change roles,
 // rejected, the old set is still there.  One pass over the observations per trial instead of two per iteration.
-__global__ __launch_bounds__(NT) MS_BA_OCC void k_ba_lm(const BaProb *probs, int team, const BaProb *alt) {
+__global__ __launch_bounds__(NT) void k_ba_lm(const BaProb *probs, int team, const BaProb *alt) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double s_red[NW];
     const BaProb &P = probs[blockIdx.x / (unsigned)team];      // fields stay in constant memory: uniform scalar loads, no private copy
@@ -2983,8 +2832,8 @@ __global__ __launch_bounds__(NT) MS_BA_OCC void k_ba_lm(const BaProb *probs, int
     long long cyc[7] = {0, 0, 0, 0, 0, 0, 0};
     const long long t_begin = clock64();
     // one workgroup per window, streams built, pose table in LDS: the streamed phases (eval_stream, backsub_stream)
-    const bool ev_stream = P.team == 1 && P.fo_lo != nullptr && 7 * (size_t)P.n_pose <= kLdsBytes / 8 && !MS_LIN_NO_STREAM;
-    const bool fuse = ev_stream && alt != nullptr && lin_streams(P) && !MS_BA_NO_FUSED_TRIAL;
+    const bool ev_stream = P.team == 1 && P.fo_lo != nullptr && 7 * (size_t)P.n_pose <= kLdsBytes / 8;
+    const bool fuse = ev_stream && alt != nullptr && lin_streams(P);
     const BaProb *Pc = &P, *Pa = fuse ? &alt[blockIdx.x] : &P;            // the descriptor whose linearisation belongs to the accepted state / the other one
     // chi2 of the state as it stands + its linearisation into *Q, one pass (fused schedule); extra / extra_sum as in eval_stream
     auto linearise_and_chi2 = [&](const BaProb &Q, double extra, double *extra_sum) {
@@ -3165,14 +3014,6 @@ __device__ __noinline__ double po_edges_setup(const BaProb &P, int pi, int lane,
     return cacc;
 }
 
-#ifndef MS_PO_PROF
-#define MS_PO_PROF 0            // 1: cycle stamps per phase in stats[8 .. 12) (tools/pose_only_prof.py; each stamp is an s_memtime and a wait, ~10 % of the kernel together)
-#endif
-#if MS_PO_PROF
-#define PO_CLOCK() clock64()
-#else
-#define PO_CLOCK() 0ll
-#endif
 __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
     extern __shared__ __attribute__((aligned(16))) double po_red[];         // [PO_NV][PO_ROW]
     __shared__ __attribute__((aligned(16))) double s_sum[2][32];       // the sums of the last two sweeps: [cur] belongs to the accepted state (its H and b), the other to the trial
@@ -3245,13 +3086,11 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
     __syncthreads();
     const int ne = s_ne;
     const bool overflow = P.n_obs > PO_OT * PO_K;                           // more observations than the registers take: those come from memory in every sweep
-    long long pc[4] = {0, 0, 0, 0};                                         // cycles of thread 0: a sweep's observations, (thread PO_OT:) its SE3 edges, its reduction, the 6 x 6 solve + exp
     const long long t_begin = clock64();
     int cur = 1;                                                            // which half of s_sum belongs to the accepted state
     // ---- one sweep over the free pose's edges at `pose`: the robust chi2 (returned), the upper triangle of H and b (left in s_sum[1 - cur][0 .. 27)), the chi2 per observation in c2t
     auto sweep = [&]() {
         double A[21], g[6], acc = 0;
-        long long ts = PO_CLOCK();
 #pragma unroll
         for (int a = 0; a < 21; ++a) A[a] = 0;
 #pragma unroll
@@ -3287,7 +3126,6 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
                 const double uvo[2] = {P.obs_uv[2 * (size_t)o], P.obs_uv[2 * (size_t)o + 1]};
                 (void)one(Xo, uvo, P.obs_info[o]);
             }
-        if (MS_PO_PROF && tid == 0) { const long long t1 = PO_CLOCK(); pc[0] += t1 - ts; }
         if (tid >= PO_OT && tid - PO_OT < ne) {                             // wave 3: the SE3 edges of the free pose
             const int k = tid - PO_OT;
             double Bm[7], e[6], We[6];
@@ -3297,9 +3135,7 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
             for (int i = 0; i < 6; ++i) { double v = 0; for (int j = 0; j < 6; ++j) v += s_eW[k][6 * i + j] * e[j]; We[i] = v; }
             for (int i = 0; i < 6; ++i) acc += e[i] * We[i];
             for (int a = 0; a < 6; ++a) { double v = 0; for (int c = 0; c < 6; ++c) v += s_eG[k][6 * a + c] * e[c]; g[a] += v; }
-            if (MS_PO_PROF && k == 0) pc[1] += PO_CLOCK() - ts;
         }
-        ts = PO_CLOCK();
         {
             MS_LDS double *row = (MS_LDS double *)po_red + tid;
 #pragma unroll
@@ -3322,7 +3158,6 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
             if (part == 0) s_sum[1 - cur][v] = s + (v < 21 ? s_Hc[v] : (v == 27 ? s_const : 0.0));
         }
         __syncthreads();
-        if (MS_PO_PROF && tid == 0) pc[2] += PO_CLOCK() - ts;
         return s_sum[1 - cur][27];
     };
     double lambda = 0, ni = 2;
@@ -3349,7 +3184,6 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
             // cheaper than one thread doing it behind a barrier and a trip through LDS)
             double Lm[21], dpv[6], b[6];                                     // lower triangle, row-major: Lm[i (i + 1) / 2 + j]
             bool ok2 = true;
-            const long long tc = PO_CLOCK();
             const double *H = s_sum[cur];
 #pragma unroll
             for (int a = 0; a < 6; ++a) b[a] = H[21 + a];
@@ -3402,7 +3236,6 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
                 for (int a = 0; a < 6; ++a) { dp[a] = dpv[a]; sc += dp[a] * (lambda * dp[a] + b[a]); }
                 se3_exp(dp, ex);
                 se3_mul(ex, bk, pose);                                                      // every thread moves its own copy of the pose: the same arithmetic, the same result
-                if (MS_PO_PROF && tid == 0) pc[3] += PO_CLOCK() - tc;
                 temp = sweep();
             } else temp = DBL_MAX;
             const double scale = sc + 1e-3;
@@ -3437,11 +3270,11 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
             if (pk) pk_chi2[o] = P.chi2_obs[o];
         }
     const double chi2_final = chi2_carried;                                 // the sweep that was accepted last evaluated exactly this state
-    if (tid == PO_OT) { P.stats[9] = (double)pc[1]; if (pk) pk[9] = (double)pc[1]; }
+    if (tid == PO_OT) { P.stats[9] = 0.0; if (pk) pk[9] = 0.0; }
     if (tid == 0) {
-        // [13], [14]: cycles of the iterations and of what came before them (the only stamps with MS_PO_PROF off); [9] is the edge wave's (above)
+        // [8 .. 12] are zero ([9] is written by thread PO_OT, above); [13], [14]: cycles of the iterations and of what came before them
         const double st[16] = {(double)it, (double)trials, (double)stop, lambda, chi2_init, chi2_final, isfinite(chi2_final) ? 1.0 : 0.0, 0.0,
-                               (double)pc[0], 0.0, (double)pc[2], (double)pc[3], 0.0, (double)(clock64() - t_begin), (double)(t_begin - t_kernel), 0.0};
+                               0.0, 0.0, 0.0, 0.0, 0.0, (double)(clock64() - t_begin), (double)(t_begin - t_kernel), 0.0};
         for (int a = 0; a < 7; ++a) { P.pose[7 * (size_t)pi + a] = pose[a]; if (pk) pk_pose[7 * (size_t)pi + a] = pose[a]; }
 #pragma unroll
         for (int q = 0; q < 16; ++q) if (q != 9) { P.stats[q] = st[q]; if (pk) pk[q] = st[q]; }
@@ -3465,9 +3298,6 @@ __global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
 // restore pass.  Observation data comes from copies sorted by point (pose index, u, v, information side by side: one round trip instead of three dependent
 // ones), the poses from an LDS table.  Same LM schedule and the same arithmetic per edge as k_ba_lm.
 constexpr int OP_NT = 512, OP_NW = OP_NT / 64, OP_NV = 64, OP_MAX_LDS_POSES = 512;
-#ifndef OP_PROF_GL
-#define OP_PROF_GL 0
-#endif
 constexpr int OP_S0 = 32, OP_BAD = 59, OP_MAX = 63;          // accumulators: 0..20 Hpp, 21..26 bp | 32..52 Schur matrix terms, 53..58 rhs terms, 59 unsound point blocks | 63 largest diagonal entry
 __host__ __device__ constexpr int op_slab_cap(int lgG) { return lgG == 0 ? 64 : 32; }     // entries of a wave's staging slab
 constexpr size_t kOpLdsBytes = (((size_t)7 * OP_MAX_LDS_POSES + 2) + (size_t)OP_NW * 27 * 64) * sizeof(double);     // dynamic LDS at most: the pose table + the slabs (136 KB; ~11 KB are static)
@@ -4026,7 +3856,7 @@ __global__ __launch_bounds__(OP_NT) void k_ba_one_pose(const BaProb *probs, int 
         P.stats[6] = (isfinite(chi2_final) && !hung) ? 1 : 0; P.stats[7] = hung ? 1 : 0;
         P.stats[15] = 0;
     }
-    if (gl == (OP_PROF_GL < team * OP_NT ? OP_PROF_GL : 0)) {              // the phase stamps of one wave (-DOP_PROF_GL=<global lane>: another wave than the first)
+    if (gl == 0) {                                                         // the phase stamps of the first wave
         P.stats[8] = (double)cyc[0]; P.stats[9] = (double)cyc[1]; P.stats[10] = (double)cyc[2]; P.stats[11] = (double)cyc[3]; P.stats[12] = (double)cyc[4];
         P.stats[13] = (double)(clock64() - t_begin); P.stats[14] = (double)cyc[5];
         P.stats[15] = (double)(t_begin - t_kernel);                           // what comes before the first sweep (not part of [13])
@@ -4093,9 +3923,8 @@ static int g_team_query_errors = 0;        // hipEventQuery answers other than s
 
 constexpr size_t kBaEagerMax = (size_t)64 << 10;        // results of a single problem up to this size are packed and copied behind every launch (ms_ba struct: h_result).
                                                         // (Tried at 512 KB, i.e. for a whole C4 window too: -0.025 ms for the window alone, but the front end of the same
-                                                        //  sequence, running beside it, fell from 2.7-3.0 k to 2.0-2.2 k frames/s -- tools/together_ab.sh; kept for small problems)
+                                                        //  sequence, running beside it, fell from 2.7-3.0 k to 2.0-2.2 k frames/s; kept for small problems)
 constexpr size_t kBaStageMax = (size_t)4 << 20;        // creates whose inputs fit are uploaded from the context's page-locked staging block without a wait
-static size_t ba_eager_max() { static const size_t v = std::getenv("MS_BA_EAGER_MAX") ? (size_t)std::atoll(std::getenv("MS_BA_EAGER_MAX")) : kBaEagerMax; return v; }     // (experiment knob)
 // SE3 edges that touch pose `pi` (k_ba_pose_only / k_ba_one_pose keep their constants in PO_MAXE LDS slots; edges between fixed poses need none)
 static int ba_edges_at_free_pose(const ms_ba_problem &Q, int pi) {
     int t = 0;
@@ -4145,20 +3974,19 @@ static void ba_delete_object(ms_ba *B) {
 // 0.18 ms in ms_ba_download for a 0.08 ms kernel, tools/pose_path_probe.py).
 static int ba_wait_event(ms_ctx *c, hipEvent_t ev) {
     thread_local bool slack_set = false;
-    static const int spin_us = std::getenv("MS_WAIT_SPIN_US") ? std::atoi(std::getenv("MS_WAIT_SPIN_US")) : 120;          // (experiment knobs)
-    static const int sleep_us = std::getenv("MS_WAIT_SLEEP_US") ? std::atoi(std::getenv("MS_WAIT_SLEEP_US")) : 20;
+    constexpr auto kSpin = std::chrono::microseconds(120), kSleep = std::chrono::microseconds(20);
     static const bool fine_slack = !std::getenv("MS_WAIT_COARSE");
     const auto t0 = std::chrono::steady_clock::now();
-    for (bool spinning = spin_us > 0;;) {
+    for (bool spinning = true;;) {
         const hipError_t q = hipEventQuery(ev);
         if (q == hipSuccess) return MS_OK;
         if (q != hipErrorNotReady) { (void)hipGetLastError(); return ms_fail(c, MS_ERR_HIP, "waiting for a solver launch failed: %s", hipGetErrorString(q)); }
         if (spinning) {
             std::this_thread::yield();
-            spinning = std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(spin_us);
+            spinning = std::chrono::steady_clock::now() - t0 < kSpin;
         } else {
             if (!slack_set && fine_slack) { (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0UL, 0UL, 0UL); slack_set = true; }      // (nanoseconds; the calling thread only)
-            std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+            std::this_thread::sleep_for(kSleep);
         }
     }
 }
@@ -4530,7 +4358,7 @@ int ms_ba_create(ms_ctx *c, const ms_ba_problem *problems, int n, ms_ba **out) {
                             while (a0 < k && fp_f[j0 + a0] < r0) ++a0;
                             // (only for pass sets that own points = team launches: one window per keyframe, where the index build is a fifth of the call; a 256-window launch keeps the
                             //  lists -- enumerating costs its Schur pass 4 %, 11.4 against 10.9 ms, and its handles are built once.  schur_fused<true> runs exactly these sets)
-                            if (F.by_points && k <= 31 && G <= 127 && kProceduralPairs) {      // the kernel enumerates the pairs of such a batch itself: nothing to build, nothing to upload
+                            if (F.by_points && k <= 31 && G <= 127) {      // the kernel enumerates the pairs of such a batch itself: nothing to build, nothing to upload
                                 F.b_fmt.push_back(-1 - (G | (k << 7) | (a0 << 12)));
                                 pad_slots();
                                 F.b_obs_start.push_back((int32_t)(F.pobs.size() / 4)); F.b_run_start.push_back((int32_t)F.pairs.size());
@@ -4693,7 +4521,7 @@ int ms_ba_create(ms_ctx *c, const ms_ba_problem *problems, int n, ms_ba **out) {
         O.Hpp2 = bump(alt_set ? n6 * n6 * D : 8); O.bp2 = bump(alt_set ? n6 * D : 8); O.Hll2 = bump(alt_set ? 6 * Q.n_point * D : 8); O.bl2 = bump(alt_set ? 3 * Q.n_point * D : 8);
         // a single small problem gets its results packed behind every launch (ba_after_launch): status, poses, points, chi2 per observation
         const size_t pack_doubles = 16 + 7 * (size_t)Q.n_pose + 3 * (size_t)Q.n_point + (size_t)Q.n_obs;
-        O.pack = bump(n == 1 && pack_doubles * D <= ba_eager_max() ? pack_doubles * D : 8);
+        O.pack = bump(n == 1 && pack_doubles * D <= kBaEagerMax ? pack_doubles * D : 8);
     }
     const double tm1 = tm_now();
     ms_ba *B = nullptr;
@@ -4743,7 +4571,7 @@ int ms_ba_create(ms_ctx *c, const ms_ba_problem *problems, int n, ms_ba **out) {
     }
     {   // the eager results of a single small problem: a page-locked block that stays with the handle object
         const size_t pack_doubles = n == 1 ? 16 + 7 * (size_t)problems[0].n_pose + 3 * (size_t)problems[0].n_point + (size_t)problems[0].n_obs : 0;
-        B->pack_doubles = pack_doubles * sizeof(double) <= ba_eager_max() ? pack_doubles : 0;
+        B->pack_doubles = pack_doubles * sizeof(double) <= kBaEagerMax ? pack_doubles : 0;
         if (B->pack_doubles * sizeof(double) > B->h_result_bytes) {
             if (B->h_result) (void)hipHostFree(B->h_result);
             B->h_result = nullptr; B->h_result_bytes = 0;
@@ -4963,8 +4791,7 @@ int ms_ba_set_factor_team(ms_ba *B, int workgroups) {
 // what follows every solver launch of ms_ba_solve: the eager results of a small single problem, then the handle's completion event
 static int ba_after_launch(ms_ctx *c, ms_ba *B) {
     B->eager = false; B->verdict_eager = false;
-    static const bool no_eager_verdict = std::getenv("MS_BA_NO_EAGER_VERDICT") != nullptr;                       // (experiment knob)
-    if (!B->team_checked && (B->n > 1 || B->last_one_pose) && !no_eager_verdict) {      // a team launch: its verdict travels behind it, so that whoever needs it (ms_ba_copy_state between the
+    if (!B->team_checked && (B->n > 1 || B->last_one_pose)) {      // a team launch: its verdict travels behind it, so that whoever needs it (ms_ba_copy_state between the
         if (!B->h_verdict) {                                       // two stages, ms_ba_download of a batch) finds it on the host once the launch's event has been seen
                                                                    // (a single window's stage 2 is read by ms_ba_download, whose packed results carry the marker: nothing extra)
             MS_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&B->h_verdict), 64, hipHostMallocDefault)); ++g_ba_host_allocs;

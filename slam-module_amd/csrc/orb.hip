@@ -893,9 +893,6 @@ __global__ __launch_bounds__(256) void k_slots(const int16_t *__restrict__ det_x
 // instructions (the moment sums below and the degree -> radian product).
 constexpr int kDescPerWave = 1;
 
-#ifndef MS_DESC_WAVES
-#define MS_DESC_WAVES 8       // waves per SIMD the register allocation of k_describe aims at (the kernel is bound by how many keypoints are in flight)
-#endif
 struct DescKp { int x, y, oct, tid_out; float ox, oy; bool valid; };
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 // r[m] in lane row q (the wave's four rows of 16 lanes)  ->  r[q] of lane row m: the 2 x 2 blocks trade places across the wave's halves
@@ -908,7 +905,8 @@ __device__ __forceinline__ void transpose4_rows(uint32_t (&r)[4]) {
     s = __builtin_amdgcn_permlane16_swap(r[2], r[3], false, false); r[2] = s[0]; r[3] = s[1];
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MS_DESC_WAVES, 8))) void k_describe(FrameSrc src, TileLevels TL, const uint4 *__restrict__ moment_tab, const float4 *__restrict__ pattern_f,
+// amdgpu_waves_per_eu(8, 8): the register allocation aims at 8 waves per SIMD (the kernel is bound by how many keypoints are in flight)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_describe(FrameSrc src, TileLevels TL, const uint4 *__restrict__ moment_tab, const float4 *__restrict__ pattern_f,
                                                   const uint2 *__restrict__ slot_tab, int capacity, int max_tracks, int lk_level,
                                                   const int16_t *__restrict__ trk_x, const int16_t *__restrict__ trk_y, const float *__restrict__ trk_px,
                                                   const float *__restrict__ trk_py, const int32_t *__restrict__ trk_id, const int32_t *__restrict__ trk_count,

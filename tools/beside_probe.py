@@ -1,5 +1,5 @@
 """The front end of ONE sequence (extract + match + ratio test per frame, bench.SequenceRunner without BA) alone and beside a bundle adjuster that another
-context keeps busy: how much slower do the front end's small kernels run, and does it depend on what the BA launch does at its team barriers?
+context keeps busy: how much slower do the front end's small kernels run beside a team launch and beside a batch launch?
    python tools/beside_probe.py <mode> [frames] [lib.so]     mode: alone | team (one C4 window on the library's team of 32, solved over and over)
                                                                  | batch (256 C4 windows, one workgroup each: no team barrier in the launch)
 Under `GPU_MAX_HW_QUEUES=8 rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/beside_probe.py ...` the kernel trace has the per-kernel durations
