@@ -256,6 +256,9 @@ __device__ __forceinline__ uint32_t dot2(uint32_t a, unsigned lo, unsigned hi, u
 // lane i <- lane i-1 / lane i+1 of the 64-wide wave in one VALU op (gfx9 DPP wave shifts); the end lane's value is unspecified
 __device__ __forceinline__ uint32_t wave_from_prev(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /*wave_shr:1*/, 0xf, 0xf, false); }
 __device__ __forceinline__ uint32_t wave_from_next(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /*wave_shl:1*/, 0xf, 0xf, false); }
+// the same where lanes 0 / 63 may receive anything (bound_ctrl: no register to initialise in front of the DPP move)
+__device__ __forceinline__ uint32_t wave_from_prev_dc(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /*wave_shr:1*/, 0xf, 0xf, true); }
+__device__ __forceinline__ uint32_t wave_from_next_dc(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /*wave_shl:1*/, 0xf, 0xf, true); }
 
 // inclusive prefix sum over the 64 lanes: four row_shr steps inside each row of 16, then row_bcast 15 / 31 across rows
 __device__ __forceinline__ int wave_scan_add(int v) {
@@ -365,8 +368,9 @@ __global__ __launch_bounds__(256) void k_blur(FrameSrc src, TileLevels TL, TileM
 //             pixel without a brighter pixel in each opposite pair AND without a darker one in each cannot
 //             be a corner (exact reject).  Survivors are compacted into an LDS list.
 //   phase A2  dense over the survivors: the FAST score itself (max over the 16 arcs of 9 of min(c-r) / min(r-c)) on packed
-//             16-bit lanes (two ring pixels per v_pk_min/max_i16), ring bytes through the vector cache; a pixel is a
-//             corner iff score > threshold, so no separate mask test is needed; scores go to the LDS score tile
+//             16-bit lanes (two ring pixels per v_pk_min_i16), ring bytes from the tile's pixels in LDS, only on the side whose
+//             pre-test the survivor passed; a pixel is a corner iff score > threshold, so no separate mask test is needed;
+//             scores go to the LDS score tile
 //   phase C   3x3 strict-maximum NMS, dense over the corner list, against the LDS score tile; survivors leave as 32-bit keys
 //             ((255-score)<<24 | y*w+x) with ONE global atomic per tile
 constexpr int kFastWaves = 8, kFastThreads = 64 * kFastWaves;     // waves per tile: 4 position rows each
@@ -381,60 +385,61 @@ __device__ __forceinline__ int mbcnt64(unsigned long long m) {      // number of
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// Compass pre-test on packed 16-bit lanes (pixels 0,2 of a lane's dword in "E" registers, pixels 1,3 in "O").
-// One v_perm_b32 both shifts a 4-byte window out of a dword pair and zero-extends two of its bytes to 16-bit lanes.
-// "At least two of N,S,E,W brighter than c+t" is "the SECOND LARGEST of the four exceeds c+t" (and likewise the second smallest
-// for darker): two sorted pairs give both order statistics in 8 packed min/max, then one packed subtract each exposes the sign.
+// Compass pre-test on packed 16-bit lanes (pixels 0,2 of a lane's dword in "even" registers, pixels 1,3 in "odd" ones).
 // Returns bit 15 of each 16-bit lane set where the pixel survives (the lower bits are not meaningful).
 __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(s2_t, a), __builtin_bit_cast(s2_t, b))); }
 __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s2_t, a), __builtin_bit_cast(s2_t, b))); }
-__device__ __forceinline__ uint32_t compass_pass(uint32_t n, uint32_t s_, uint32_t e, uint32_t w, uint32_t hi, uint32_t lo) {
+__device__ __forceinline__ uint32_t compass_pass(uint32_t n, uint32_t s_, uint32_t e, uint32_t w, uint32_t c, uint32_t T2) {
     // Round 2: a tighter exact reject for two operations less.  The complement of an arc of 9 is an arc of 7, which cannot hold two ring
     // pixels that are 8 apart: every arc of 9 contains N or S, and E or W.  So a brighter corner needs max(N, S) > c + t AND max(E, W) > c + t
     // (a darker one min(N, S) < c - t AND min(E, W) < c - t) -- one pixel from EACH opposite pair, not any two of the four.
-    const uint32_t a = pk_max(n, s_), b = pk_min(n, s_), c = pk_max(e, w), d = pk_min(e, w);
-    return pk_sub(hi, pk_min(a, c)) | pk_sub(pk_max(b, d), lo);
+    // Both sides in one sign: t - max(min(max(N, S), max(E, W)) - c, c - max(min(N, S), min(E, W))) < 0.
+    const uint32_t a = pk_max(n, s_), b = pk_min(n, s_), cx = pk_max(e, w), d = pk_min(e, w);
+    return pk_sub(T2, pk_max(pk_sub(pk_min(a, cx), c), pk_sub(c, pk_max(b, d))));
 }
 
-// FAST score = max over the 16 arcs of 9 of min(c - r) and of min(r - c), on packed 16-bit lanes: P[k] = (d[k], d[k+8]) with
-// d = centre - ring pixel.  A 9-arc starting at k < 8 is the suffix d[k..7] of the first half plus the prefix d[8..8+k] of the
-// second, the one starting at k+8 the mirror image, so running prefix / suffix minima of P (7 packed ops each) and one combine
-// per k with the halves swapped (free operand select) give all 16 arc minima in 22 ops; the same for the maxima.
-__device__ __forceinline__ int fast_ring_score(const uint32_t R[9]) {
-    const uint32_t cc = R[8] * 0x00010001u;
-    s2_t P[8], pmn[8], pmx[8], smn[8], smx[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) P[k] = __builtin_bit_cast(s2_t, pk_sub(cc, R[k]));
-    pmn[0] = pmx[0] = P[0];
-    smn[7] = smx[7] = P[7];
+// One side of the FAST score: max over the 16 arcs of 9 of min(v), on packed 16-bit lanes P[k] = (v[k], v[k+8]).  A 9-arc starting
+// at k < 8 is the suffix v[k..7] of the first half plus the prefix v[8..8+k] of the second, the one starting at k+8 the mirror
+// image, so running prefix / suffix minima of P (7 packed ops each) and one combine per k with the halves swapped (free operand
+// select) give all 16 arc minima, and their maximum, in 29 ops.
+// With v = d = centre - ring this is the "ring darker" score; with v = ~d = -d - 1 (ring - centre - 1) it is the "ring brighter"
+// score minus one, because ~ reverses the order: max over arcs of min(~d) = ~(min over arcs of max(d)).
+__device__ __forceinline__ int arc_score(const s2_t P[8]) {
+    s2_t pmn[8], smn[8];
+    pmn[0] = P[0];
+    smn[7] = P[7];
 #pragma unroll
     for (int k = 1; k < 8; ++k) {
-        pmn[k] = __builtin_elementwise_min(pmn[k - 1], P[k]); pmx[k] = __builtin_elementwise_max(pmx[k - 1], P[k]);
-        smn[7 - k] = __builtin_elementwise_min(smn[8 - k], P[7 - k]); smx[7 - k] = __builtin_elementwise_max(smx[8 - k], P[7 - k]);
+        pmn[k] = __builtin_elementwise_min(pmn[k - 1], P[k]);
+        smn[7 - k] = __builtin_elementwise_min(smn[8 - k], P[7 - k]);
     }
-    s2_t bright = {-32768, -32768}, dark = {32767, 32767};
+    s2_t best = __builtin_elementwise_min(smn[0], pmn[0].yx);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        bright = __builtin_elementwise_max(bright, __builtin_elementwise_min(smn[k], pmn[k].yx));   // arcs starting at k (.x) and k+8 (.y)
-        dark = __builtin_elementwise_min(dark, __builtin_elementwise_max(smx[k], pmx[k].yx));
-    }
-    return max(max((int)bright.x, (int)bright.y), -min((int)dark.x, (int)dark.y));
+    for (int k = 1; k < 8; ++k) best = __builtin_elementwise_max(best, __builtin_elementwise_min(smn[k], pmn[k].yx));   // arcs starting at k (.x) and k+8 (.y)
+    return max((int)best.x, (int)best.y);
 }
 
-// One step of a lane's list append: the mask's top bit is shifted out into the carry (v_add_co m, m, m), lanes whose bit was set
-// write `entry` as a 16-bit value at LDS byte address `at` and advance it.  Exec is narrowed to the writers for the two
-// instructions in between and restored, so unset pixels cost no select and no store.
-__device__ __forceinline__ void list_append_top_bit(uint32_t &m, uint32_t &at, uint32_t entry) {
-    unsigned long long saved;
-    asm volatile("v_add_co_u32 %[m], vcc, %[m], %[m]\n\t"
-                 "s_and_saveexec_b64 %[sv], vcc\n\t"
-                 "ds_write_b16 %[at], %[e]\n\t"
-                 "v_add_u32 %[at], 2, %[at]\n\t"
-                 "s_mov_b64 exec, %[sv]"
-                 : [m] "+v"(m), [at] "+v"(at), [sv] "=&s"(saved)
-                 : [e] "v"(entry)
-                 : "vcc", "memory");
+// v_pk_mad_u16: s * r + k per 16-bit lane (modulo 2^16, so it serves signed lanes as well)
+__device__ __forceinline__ s2_t pk_mad(uint32_t s, uint32_t r, uint32_t k) {
+    return __builtin_bit_cast(s2_t, (us2_t)(__builtin_bit_cast(us2_t, s) * __builtin_bit_cast(us2_t, r) + __builtin_bit_cast(us2_t, k)));
 }
+
+// One step of a lane's list append: one SDWA compare copies the top bit of byte B of `m` (the survivor bit of pixel B) into VCC, lanes
+// whose bit is set write a 16-bit entry at LDS byte address `at` and advance it -- STORE is ds_write_b16 for the low half of `entry`,
+// ds_write_b16_d16_hi for its high half, so one register carries the entries of two pixels.  Exec is narrowed to the writers for the
+// two instructions in between and restored, so unset pixels cost no select and no store.
+#define FAST_LIST_APPEND(m, at, entry, B, STORE)                                                                      \
+    do {                                                                                                              \
+        unsigned long long saved_;                                                                                    \
+        asm volatile("v_cmp_gt_i32_sdwa vcc, 0, sext(%[mm]) src0_sel:DWORD src1_sel:BYTE_" #B "\n\t"                 \
+                     "s_and_saveexec_b64 %[sv], vcc\n\t"                                                              \
+                     STORE " %[a], %[e]\n\t"                                                                         \
+                     "v_add_u32 %[a], 2, %[a]\n\t"                                                                    \
+                     "s_mov_b64 exec, %[sv]"                                                                          \
+                     : [a] "+v"(at), [sv] "=&s"(saved_)                                                               \
+                     : [mm] "v"(m), [e] "v"(entry)                                                                    \
+                     : "vcc", "memory");                                                                              \
+    } while (0)
 
 __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGeom *g, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count,
                                               const uint32_t *__restrict__ tile_tab, TileLevels TL) {
@@ -483,12 +488,14 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
     // ---- phase A1: position rows pr = wave*4 .. wave*4+3  <->  image rows Y0-1+pr; columns X0-4+4*lane .. +3
     {
         const uint32_t T2 = (uint32_t)thr * 0x00010001u;
-        uint32_t vmask = 0;                              // which of the lane's 4 pixels are valid positions (same for every row): bit 8i + 7
+        // which of the lane's 4 pixels are valid positions (the same for every row): bit 8i + 7 for pixel i.  Column c = 4 lane + i in
+        // [3, 252] and image column x + i in [3, w - 4] (x = X0 - 4 + 4 lane) is one run lo <= i <= hi whose ends are a scalar minus 4 lane
+        const int lo = min(max(max(3, 7 - X0) - 4 * lane, 0), 4), hi = min(max(min(252, w - X0) - 4 * lane, -1), 3);
+        const uint32_t vmask = (uint32_t)(0x80808080ull << (8 * lo)) & (uint32_t)(0x80808080ull >> (8 * (3 - hi)));
+        // every loaded row split ONCE into its even / odd bytes as 16-bit lanes: a row serves as S, centre and N of three position rows
+        uint32_t re[kFastRowsPerWave + 6], ro[kFastRowsPerWave + 6];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = 4 * lane + i, px = x + i;
-            vmask |= (uint32_t)(c >= 3 && c <= 252 && px >= 3 && px < w - 3) << (8 * i + 7);
-        }
+        for (int j = 0; j < kFastRowsPerWave + 6; ++j) { re[j] = rows[j] & 0x00FF00FFu; ro[j] = __builtin_amdgcn_perm(0u, rows[j], 0x0C030C01u); }
         uint32_t fr[kFastRowsPerWave];                   // survivors of row r: the top bit of byte i <-> pixel i
         uint32_t cnt4 = 0;                               // their number, row r in byte r (a row has at most 250 positions, so sums over lanes stay in the byte)
 #pragma unroll
@@ -496,17 +503,13 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
             const int y = Y0 - 1 + wave * kFastRowsPerWave + r;
             fr[r] = 0;
             if (y < 3 || y >= h - 3) continue;                           // wave-uniform
-            const uint32_t C = rows[r + 3], Cn = rows[r + 6], Cs = rows[r];
-            // neighbours' dwords by DPP wave shifts (one VALU op each); lanes 0 / 63 get a don't-care: their edge pixels are masked by vmask
-            const uint32_t Lw = wave_from_prev(C), Rw = wave_from_next(C);
-            const uint32_t ce = C & 0x00FF00FFu, co = (C >> 8) & 0x00FF00FFu;
-            const uint32_t hie = ce + T2, hio = co + T2, loe = pk_sub(ce, T2), loo = pk_sub(co, T2);
-            // byte selectors: 0-3 = bytes of the low dword, 4-7 = bytes of the high dword, 0x0C = zero
-            const uint32_t pe = compass_pass(__builtin_amdgcn_perm(0u, Cn, 0x0C020C00u), __builtin_amdgcn_perm(0u, Cs, 0x0C020C00u),     // (0,+3), (0,-3): bytes 0,2
-                                             __builtin_amdgcn_perm(Rw, C, 0x0C050C03u), __builtin_amdgcn_perm(C, Lw, 0x0C030C01u),      // (+3,0): x+3, x+5 of {Rw,C}; (-3,0): x-3, x-1 of {C,Lw}
-                                             hie, loe);
-            const uint32_t po = compass_pass(__builtin_amdgcn_perm(0u, Cn, 0x0C030C01u), __builtin_amdgcn_perm(0u, Cs, 0x0C030C01u),     // bytes 1,3
-                                             __builtin_amdgcn_perm(Rw, C, 0x0C060C04u), __builtin_amdgcn_perm(C, Lw, 0x0C040C02u), hio, loo);
+            const uint32_t ce = re[r + 3], co = ro[r + 3];
+            // the neighbour lanes' halves by DPP wave shifts (one VALU op each); lanes 0 / 63 get a don't-care: their edge pixels are masked by vmask
+            const uint32_t cep = wave_from_prev_dc(ce), cen = wave_from_next_dc(ce), cop = wave_from_prev_dc(co), con = wave_from_next_dc(co);
+            // even pixels x, x+2: (+3,0) = x+3, x+5 = odd byte 3 of this lane, odd byte 1 of the next; (-3,0) = x-3, x-1 = the previous lane's odd bytes
+            const uint32_t pe = compass_pass(re[r + 6], re[r], __builtin_amdgcn_alignbit(con, co, 16), cop, ce, T2);
+            // odd pixels x+1, x+3: (+3,0) = x+4, x+6 = the next lane's even bytes; (-3,0) = x-2, x = even byte 2 of the previous lane, even byte 0 of this one
+            const uint32_t po = compass_pass(ro[r + 6], ro[r], cen, __builtin_amdgcn_alignbit(ce, cep, 16), co, T2);
             fr[r] = __builtin_amdgcn_perm(po, pe, 0x07030501u) & vmask;  // the sign bytes of the four pixels side by side (pixel i in byte i)
             cnt4 += (uint32_t)__popc(fr[r]) << (8 * r);
         }
@@ -518,24 +521,24 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
         int base = 0;
         if (lane == 0) base = atomicAdd(&s_np, (int)((tot4 & 255u) + ((tot4 >> 8) & 255u) + ((tot4 >> 16) & 255u) + (tot4 >> 24)));
         base = __builtin_amdgcn_readfirstlane(base);
-        const uint32_t ebase = (uint32_t)((wave * kFastRowsPerWave) << 8) | (uint32_t)(4 * lane);
+        const uint32_t ebase = ((uint32_t)((wave * kFastRowsPerWave) << 8) | (uint32_t)(4 * lane)) * 0x00010001u;   // in both 16-bit halves
         const uint32_t pre_addr = (uint32_t)(uintptr_t)s_pre;
 #pragma unroll
         for (int r = 0; r < kFastRowsPerWave; ++r) {
             uint32_t at = pre_addr + 2u * ((uint32_t)base + ((excl >> (8 * r)) & 255u));      // byte address of the lane's first slot of this row
             base += (int)((tot4 >> (8 * r)) & 255u);
-            uint32_t f = fr[r];
-            list_append_top_bit(f, at, ebase + (r << 8) + 3); f <<= 7;
-            list_append_top_bit(f, at, ebase + (r << 8) + 2); f <<= 7;
-            list_append_top_bit(f, at, ebase + (r << 8) + 1); f <<= 7;
-            list_append_top_bit(f, at, ebase + (r << 8) + 0);
+            const uint32_t e32 = ebase + ((uint32_t)((r << 8) + 3) | ((uint32_t)((r << 8) + 2) << 16));   // the entries of pixels 3 | 2
+            const uint32_t e10 = ebase + ((uint32_t)((r << 8) + 1) | ((uint32_t)(r << 8) << 16));         // and of pixels 1 | 0
+            FAST_LIST_APPEND(fr[r], at, e32, 3, "ds_write_b16");
+            FAST_LIST_APPEND(fr[r], at, e32, 2, "ds_write_b16_d16_hi");
+            FAST_LIST_APPEND(fr[r], at, e10, 1, "ds_write_b16");
+            FAST_LIST_APPEND(fr[r], at, e10, 0, "ds_write_b16_d16_hi");
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     __syncthreads();
     // ---- phase A2 + B: the survivors are SCORED directly (corner <=> score > threshold), on packed 16-bit lanes:
-    //      P[k] = (d[k], d[k+8]) with d = centre - ring pixel; the sliding min / max of 9 over the circular ring is four
-    //      v_pk_min_i16 / v_pk_max_i16 levels (windows 2, 4, 8, 9) with lane swaps providing the wrap-around.
+    //      P[k] = (d[k], d[k+8]) with d = centre - ring pixel (or ~d for the other side), one arc ladder (arc_score) per side.
     //      The ring comes from the tile's pixels in LDS (17 byte reads with immediate offsets from one base): as 7 wide global loads per
     //      survivor the texture addresser had ~30 cache lines to look up per instruction.  A wave appends its corners IN PLACE, into the
     //      slots of the survivor list it has already consumed (slots 64w + kFastThreads i + j belong to wave w), so no second list is needed.
@@ -550,9 +553,38 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
             const int rdy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
             R[8] = q[3 * 256 + 3];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) R[k] = (uint32_t)q[(3 + rdy[k]) * 256 + 3 + rdx[k]] | ((uint32_t)q[(3 + rdy[k + 8]) * 256 + 3 + rdx[k + 8]] << 16);
+            for (int k = 0; k < 8; ++k) {                                // ring pixels k and k+8 as the two 16-bit lanes (the second byte read lands in the high half)
+                us2_t v;
+                v.x = q[(3 + rdy[k]) * 256 + 3 + rdx[k]];
+                v.y = q[(3 + rdy[k + 8]) * 256 + 3 + rdx[k + 8]];
+                R[k] = __builtin_bit_cast(uint32_t, v);
+            }
         }
-        const int best = fast_ring_score(R);
+        // A corner is a corner on ONE side only: with t >= 1, an arc of 9 whose pixels are all darker than c - t overlaps every other
+        // arc of 9 (9 + 9 > 16), so the "ring brighter" score is negative there, and vice versa.  And a side scores above t only where
+        // its compass pre-test holds (phase A1's test, redone here on the pairs (0,+-3) = R[0] and (+-3,0) = R[4]).  So a survivor scores
+        // the side it passed with ONE arc ladder; the few that passed both (0.24 % of the survivors on the benchmark's frames) and are not corners
+        // on the darker-ring side score the other side as well, in a pass the wave takes only when one of its lanes needs it.
+        const uint32_t cc = R[8] * 0x00010001u;
+        const s2_t dv = __builtin_bit_cast(s2_t, pk_sub(cc, R[0])), dh = __builtin_bit_cast(s2_t, pk_sub(cc, R[4]));     // d = c - r, pairs (N, S) and (E, W)
+        const s2_t up = __builtin_elementwise_min(__builtin_elementwise_max(dv, dv.yx), __builtin_elementwise_max(dh, dh.yx));
+        const s2_t dn = __builtin_elementwise_max(__builtin_elementwise_min(dv, dv.yx), __builtin_elementwise_min(dh, dh.yx));
+        const bool ring_dark = up.x > thr, ring_bright = dn.x < -thr;
+        // ring darker: P = d = c - r = (-1) r + c;  ring brighter: P = ~d = r - c - 1 = r + ~c, whose ladder is the score minus one
+        const uint32_t m = ring_dark ? 0u : 0xFFFFFFFFu;
+        const uint32_t sgn = ring_dark ? 0xFFFFFFFFu : 0x00010001u;
+        s2_t P[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) P[k] = pk_mad(sgn, R[k], cc ^ m);
+        int best = arc_score(P) - (int)m;
+        const bool again = ring_dark && ring_bright && best <= thr;
+        if (__ballot(again) != 0) {                                     // wave-uniform
+            const uint32_t cc1 = cc + 0x00010001u;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) P[k] = __builtin_bit_cast(s2_t, pk_sub(R[k], cc1));
+            const int b2 = arc_score(P) + 1;
+            if (again) best = max(best, b2);
+        }
         const bool corner = best > thr;
         const unsigned long long cm = __ballot(corner);
         if (corner) {
