@@ -286,6 +286,46 @@ void ms_bow_vocab_destroy(ms_bow_vocab *vocab);
 int ms_bow_transform(ms_ctx *ctx, const ms_bow_vocab *vocab, const uint32_t *desc, int n, int levels_up,
                      int32_t *word, double *weight, int32_t *node);
 
+/* ---- N3b: keyframe database behind BowIndex::add / remove / getBowSimilar (bow_index.cpp:44-57, :95-176) ---------------
+ * The reference keeps an inverted index std::vector<std::list<MapKf>> over every vocabulary word and scores candidates with
+ * DBoW2's L1Scoring.  ms_bow_db keeps, on the device, one entry per keyframe: (map_id, kf_id) and its BowVector (the sparse,
+ * L1-normalised map the host mirror assembles after ms_bow_transform: words strictly ascending in [0, n_words), finite values).
+ * Queries scan the live entries; results are bit-identical to the reference: the same entries in the same order with the same
+ * float scores (order among equal scores: (map_id, kf_id) ascending, the std::map order the reference's std::sort starts from).
+ * All arguments are HOST pointers.  add / remove enqueue their work and return; a query synchronises once and fills its outputs.
+ * Capacity is grow-only; a steady add / remove / query cycle allocates nothing after warm-up (ms_debug_host_allocs). */
+typedef struct ms_bow_db ms_bow_db;
+/* An empty database for a vocabulary of n_words words, sized for initial_entries entries of initial_words words in all (grows as needed). */
+int ms_bow_db_create(ms_ctx *ctx, int n_words, int initial_entries, long long initial_words, ms_bow_db **out);
+void ms_bow_db_destroy(ms_bow_db *db);
+/* BowIndex::add (bow_index.cpp:44-48): enter (map_id, kf_id) with its n words / values.  MS_ERR_INVALID, database unchanged, for
+ * words out of order or range, a non-finite value, or an id that is already live (the reference never adds one twice).  n = 0 is
+ * allowed: such an entry shares no word with anything. */
+int ms_bow_db_add(ms_bow_db *db, int32_t map_id, int32_t kf_id, int n, const int32_t *words, const double *values);
+/* BowIndex::remove (bow_index.cpp:50-57): O(1); an id that is not live is ignored (MS_OK), like the reference's loop. */
+int ms_bow_db_remove(ms_bow_db *db, int32_t map_id, int32_t kf_id);
+/* Live entries (MS_ERR_INVALID for NULL). */
+int ms_bow_db_size(const ms_bow_db *db);
+/* BowIndex::getBowSimilar (bow_index.cpp:95-176) for a BowVector given by the caller (validated like ms_bow_db_add).
+ * (ex_map, ex_kf) is excluded from counting and scoring (:100, :113); ex_kf = -1: nothing excluded.
+ *   common(e)   = the number of words the query and the entry share; maxInCommon = max over entries with common > 0 (:136-139); none: empty result
+ *   minInCommon = (unsigned)(min_in_common_ratio * (float)maxInCommon); an entry survives if common > minInCommon (:143-151)
+ *   score       = (float)(-s / 2.0), s = sum over common words in ascending word order of fabs(vi - wi) - fabs(vi) - fabs(wi),
+ *                 in double, vi the query's value (DBoW2 L1Scoring::score) (:149)
+ *   order       = score descending, then (map_id, kf_id) ascending (:165-166); the entries with score < best * score_ratio (float)
+ *                 are cut (:169-173).
+ * *n_total = the number of results; the first min(n_total, max_out) are written to out_map / out_kf / out_score. */
+int ms_bow_db_query(ms_bow_db *db, int n, const int32_t *words, const double *values, int32_t ex_map, int32_t ex_kf,
+                    float min_in_common_ratio, float score_ratio,
+                    int max_out, int32_t *out_map, int32_t *out_kf, float *out_score, int *n_total);
+/* getBowSimilar for q entries already in the database, each query excluding its own id (loop_closer.cpp:132, :139-141 for a batch):
+ * the query vectors are read where they lie, nothing is uploaded.  MS_ERR_INVALID if an id is not live.  Output in CSR form:
+ * query i's first min(n_total[i], max_out_per_query) results follow those of query i - 1 in out_map / out_kf / out_score (which hold
+ * q * max_out_per_query entries); n_total[q] = each query's full count. */
+int ms_bow_db_query_ids(ms_bow_db *db, int q, const int32_t *map_ids, const int32_t *kf_ids,
+                        float min_in_common_ratio, float score_ratio, int max_out_per_query,
+                        int32_t *out_map, int32_t *out_kf, float *out_score, int *n_total);
+
 /* FeatureSearch (feature_search.{hpp,cpp}): the keyframe's keypoints sorted by y.  Host helper; std::stable_sort, so points
  * with equal y keep index order (the reference's std::sort leaves that order unspecified).  sorted_idx[p] = keypoint index. */
 int ms_feature_search_sort(const float *x, const float *y, int n, float *sorted_x, float *sorted_y, int32_t *sorted_idx);

@@ -4,8 +4,9 @@
 // transform with levelsUp = 4.  DBoW2 is an external library (not in the reference tree); the mirror keeps the vocabulary as
 // the flat arrays DBoW2 holds per node, sends the tree descent to the device (ms_bow_transform) and assembles the two ordered
 // maps on the host in feature order, exactly as DBoW2's batch transform does: v[word] += weight and fv[node].push_back(i) for
-// weight > 0, then BowVector::normalize(L1).  add / remove / getBowSimilar of the reference are inverted-index bookkeeping on
-// the map graph and stay in the reference's own class; only `transform` is replaced.
+// weight > 0, then BowVector::normalize(L1).  add / remove / getBowSimilar (bow_index.cpp:44-57, :95-176) go to the device
+// keyframe database (ms_bow_db), created on the first add: the reference's inverted index std::vector<std::list<MapKf>> and
+// DBoW2's L1 scoring are replaced, and the results are the reference's (ties in score in (mapId, kfId) order).
 #pragma once
 #include <cmath>
 #include <fstream>
@@ -21,6 +22,7 @@ using FeatureVector = std::map<unsigned, std::vector<unsigned>>;     // DBoW2::F
 // The vocabulary as DBoW2 stores it (TemplatedVocabulary::m_nodes): node 0 is the root.
 struct VocabularyTree {
     int branchingFactor = 0, depthLevels = 0;                        // m_k, m_L
+    int scoring = 0, weighting = 0;                                  // m_scoring (0 = L1_NORM), m_weighting (0 = TF_IDF), as in the file header
     std::vector<std::int32_t> parent, wordId;                        // wordId = -1 for inner nodes
     std::vector<std::uint32_t> descriptor;                           // 8 words per node
     std::vector<double> weight;
@@ -37,6 +39,7 @@ struct VocabularyTree {
         std::getline(f, line);
         int scoring = 0, weighting = 0;
         { std::stringstream ss(line); ss >> v.branchingFactor >> v.depthLevels >> scoring >> weighting; }
+        v.scoring = scoring; v.weighting = weighting;
         if (v.branchingFactor < 0 || v.branchingFactor > 20 || v.depthLevels < 1 || v.depthLevels > 10 || scoring < 0 || scoring > 5 || weighting < 0 || weighting > 3)
             throw std::runtime_error("mi355slam: vocabulary header out of range in " + path);
         v.parent.push_back(0); v.wordId.push_back(-1); v.weight.push_back(0.0); v.descriptor.resize(8, 0u);
@@ -59,13 +62,26 @@ struct VocabularyTree {
     }
 };
 
+// bow_index.hpp:21-30 (MapId / KfId are plain integers here)
+struct MapKf {
+    std::int32_t mapId, kfId;
+};
+inline bool operator==(const MapKf &a, const MapKf &b) { return a.mapId == b.mapId && a.kfId == b.kfId; }
+inline bool operator<(const MapKf &a, const MapKf &b) { return a.mapId == b.mapId ? a.kfId < b.kfId : a.mapId < b.mapId; }
+
+struct BowSimilar {
+    MapKf mapKf;
+    float score;
+};
+
 class BowIndex {
 public:
-    BowIndex(Context &ctx, const VocabularyTree &tree) : ctx_(ctx) {
+    BowIndex(Context &ctx, const VocabularyTree &tree) : ctx_(ctx), scoring_(tree.scoring) {
+        for (std::int32_t w : tree.wordId) nWords_ = std::max(nWords_, w + 1);
         ctx_.check(ms_bow_vocab_create(ctx_.get(), (int)tree.size(), tree.parent.data(), tree.descriptor.data(), tree.weight.data(), tree.wordId.data(),
                                        tree.depthLevels, &vocab_), "ms_bow_vocab_create");
     }
-    ~BowIndex() { ms_bow_vocab_destroy(vocab_); for (void *p : {d_desc_, d_word_, d_weight_, d_node_}) if (p) ms_dev_free(ctx_.get(), p); }
+    ~BowIndex() { ms_bow_db_destroy(db_); ms_bow_vocab_destroy(vocab_); for (void *p : {d_desc_, d_word_, d_weight_, d_node_}) if (p) ms_dev_free(ctx_.get(), p); }
     BowIndex(const BowIndex &) = delete;
 
     // bow_index.cpp:59-93
@@ -100,7 +116,47 @@ public:
         if (norm > 0.0) for (auto &kv : v) kv.second /= norm;
     }
 
+    // bow_index.cpp:44-48: the reference passes the keyframe (its shared->bowVec and id) and the map id
+    void add(const BowVector &bowVec, MapKf mapKf) {
+        requireL1();
+        if (!db_) ctx_.check(ms_bow_db_create(ctx_.get(), std::max(nWords_, 1), 1024, 1024ll * 500, &db_), "ms_bow_db_create");
+        flatten(bowVec);
+        ctx_.check(ms_bow_db_add(db_, mapKf.mapId, mapKf.kfId, (int)qWords_.size(), qWords_.data(), qValues_.data()), "ms_bow_db_add");
+    }
+
+    // bow_index.cpp:50-57
+    void remove(MapKf mapKf) {
+        if (db_) ctx_.check(ms_bow_db_remove(db_, mapKf.mapId, mapKf.kfId), "ms_bow_db_remove");
+    }
+
+    // bow_index.cpp:95-176: `current` is the query keyframe's own id ({CURRENT_MAP_ID, kf.id}, :100); the ratios are the
+    // reference's parameters.bowMinInCommonRatio and parameters.bowScoreRatio
+    std::vector<BowSimilar> getBowSimilar(const BowVector &query, MapKf current, float minInCommonRatio, float scoreRatio) {
+        requireL1();
+        if (!db_) return {};
+        flatten(query);
+        int total = 0;
+        for (;;) {
+            outMap_.resize(outCap_); outKf_.resize(outCap_); outScore_.resize(outCap_);
+            ctx_.check(ms_bow_db_query(db_, (int)qWords_.size(), qWords_.data(), qValues_.data(), current.mapId, current.kfId, minInCommonRatio, scoreRatio,
+                                       (int)outCap_, outMap_.data(), outKf_.data(), outScore_.data(), &total), "ms_bow_db_query");
+            if ((std::size_t)total <= outCap_) break;
+            outCap_ = (std::size_t)total;
+        }
+        std::vector<BowSimilar> similar((std::size_t)total);
+        for (int i = 0; i < total; ++i) similar[(std::size_t)i] = BowSimilar{MapKf{outMap_[(std::size_t)i], outKf_[(std::size_t)i]}, outScore_[(std::size_t)i]};
+        return similar;
+    }
+
 private:
+    void requireL1() const {
+        if (scoring_ != 0)
+            throw std::runtime_error("mi355slam: BowIndex add / getBowSimilar support L1 scoring only (vocabulary scoring type " + std::to_string(scoring_) + ")");
+    }
+    void flatten(const BowVector &v) {
+        qWords_.clear(); qValues_.clear();
+        for (const auto &kv : v) { qWords_.push_back((std::int32_t)kv.first); qValues_.push_back(kv.second); }
+    }
     void reserve(std::size_t n) {
         if (n <= cap_) return;
         for (void **p : {&d_desc_, &d_word_, &d_weight_, &d_node_}) if (*p) { ms_dev_free(ctx_.get(), *p); *p = nullptr; }
@@ -111,7 +167,13 @@ private:
         ctx_.check(ms_dev_alloc(ctx_.get(), 4 * cap_, &d_node_), "ms_dev_alloc");
     }
     Context &ctx_;
+    int scoring_ = 0, nWords_ = 0;
     ms_bow_vocab *vocab_ = nullptr;
+    ms_bow_db *db_ = nullptr;                                                     // created on the first add
+    std::vector<std::int32_t> qWords_, outMap_, outKf_;
+    std::vector<double> qValues_;
+    std::vector<float> outScore_;
+    std::size_t outCap_ = 64;
     void *d_desc_ = nullptr, *d_word_ = nullptr, *d_weight_ = nullptr, *d_node_ = nullptr;
     std::size_t cap_ = 0;
     std::vector<std::uint32_t> host_desc_;

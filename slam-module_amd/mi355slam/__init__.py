@@ -532,6 +532,81 @@ class BowVocabulary:
         except Exception: pass
 
 
+class BowDatabase:
+    """Keyframe database behind BowIndex::add / remove / getBowSimilar (ms_bow_db): entries (map_id, kf_id) with their BowVectors
+    (ascending word ids, values), queried on the device.  Results are (map_ids i32, kf_ids i32, scores f32) in the reference's order."""
+
+    def __init__(self, ctx, n_words, capacity=1024, words_per_entry=500, max_out=64):
+        self.ctx, self.max_out = ctx, int(max_out)
+        h = C.c_void_p()
+        ctx.check(lib().ms_bow_db_create(ctx._h, int(n_words), int(capacity), C.c_longlong(int(capacity) * int(words_per_entry)), C.byref(h)), "ms_bow_db_create")
+        self._h = h
+        ctx._adopt(self)
+
+    @staticmethod
+    def _vec(words, values):
+        w = np.ascontiguousarray(words, np.int32); v = np.ascontiguousarray(values, np.float64)
+        if w.shape != v.shape or w.ndim != 1: raise ValueError("words and values must be 1-D arrays of one length")
+        return w, v
+
+    def add(self, map_id, kf_id, words, values):
+        w, v = self._vec(words, values)
+        self.ctx.check(lib().ms_bow_db_add(self._h, int(map_id), int(kf_id), len(w), w.ctypes.data_as(i32p), v.ctypes.data_as(f64p)), "ms_bow_db_add")
+
+    def remove(self, map_id, kf_id):
+        self.ctx.check(lib().ms_bow_db_remove(self._h, int(map_id), int(kf_id)), "ms_bow_db_remove")
+
+    @property
+    def size(self):
+        n = lib().ms_bow_db_size(self._h)
+        self.ctx.check(min(n, 0), "ms_bow_db_size")
+        return n
+
+    def query(self, words, values, exclude=None, min_in_common_ratio=0.8, score_ratio=0.75):
+        """getBowSimilar for a BowVector; exclude = (map_id, kf_id) or None."""
+        w, v = self._vec(words, values)
+        ex_map, ex_kf = exclude if exclude is not None else (0, -1)
+        mo = self.max_out
+        for attempt in range(2):
+            om, ok, os_ = np.zeros(mo, np.int32), np.zeros(mo, np.int32), np.zeros(mo, np.float32)
+            nt = C.c_int(0)
+            self.ctx.check(lib().ms_bow_db_query(self._h, len(w), w.ctypes.data_as(i32p), v.ctypes.data_as(f64p), int(ex_map), int(ex_kf),
+                                                 C.c_float(min_in_common_ratio), C.c_float(score_ratio), mo,
+                                                 om.ctypes.data_as(i32p), ok.ctypes.data_as(i32p), os_.ctypes.data_as(f32p), C.byref(nt)), "ms_bow_db_query")
+            if nt.value <= mo: return om[:nt.value], ok[:nt.value], os_[:nt.value]
+            mo = nt.value
+        raise MsError("ms_bow_db_query: the result grew between two calls")
+
+    def query_ids(self, ids, min_in_common_ratio=0.8, score_ratio=0.75):
+        """getBowSimilar for entries already in the database (each excludes itself); ids = [(map_id, kf_id), ...].  Returns a list of triples."""
+        ids = np.asarray(ids, np.int32).reshape(-1, 2)
+        q = len(ids)
+        if q == 0: return []
+        mi, ki = np.ascontiguousarray(ids[:, 0]), np.ascontiguousarray(ids[:, 1])
+        mo = self.max_out
+        for attempt in range(2):
+            om, ok, os_ = np.zeros(q * mo, np.int32), np.zeros(q * mo, np.int32), np.zeros(q * mo, np.float32)
+            nt = np.zeros(q, np.int32)
+            self.ctx.check(lib().ms_bow_db_query_ids(self._h, q, mi.ctypes.data_as(i32p), ki.ctypes.data_as(i32p), C.c_float(min_in_common_ratio),
+                                                     C.c_float(score_ratio), mo, om.ctypes.data_as(i32p), ok.ctypes.data_as(i32p),
+                                                     os_.ctypes.data_as(f32p), nt.ctypes.data_as(i32p)), "ms_bow_db_query_ids")
+            if int(nt.max()) <= mo:
+                out, at = [], 0
+                for n in nt:
+                    out.append((om[at:at + n], ok[at:at + n], os_[at:at + n])); at += int(n)
+                return out
+            mo = int(nt.max())
+        raise MsError("ms_bow_db_query_ids: the result grew between two calls")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ms_bow_db_destroy(self._h); self._h = None
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+
 def hamming_candidates(ctx, q_desc, t_desc, cand_lists, t_skip=None, t_octave=None):
     """cand_lists: list (per query) of keypoint index arrays.  Returns (best_idx, best_dist, second_dist, best_oct, second_oct)."""
     q = np.ascontiguousarray(q_desc, np.uint32).reshape(-1, 8); t = np.ascontiguousarray(t_desc, np.uint32).reshape(-1, 8)
