@@ -499,7 +499,8 @@ int ms_ba_debug_fail_team_barriers(ms_ba *ba, int on);
  * per vertex and edge, bundle_adjuster.cpp:55,73,247,265,279).  tests/host_shim_smoke.cpp holds 20 consecutive windows against it. */
 long long ms_debug_host_allocs(void);
 /* Test hook: the first `first_trials` damped trials of the following solves count as rejected whatever their gain (state restored, lambda *= nu, nu *= 2): ten of them
- * in one iteration drive g2o's Terminate path (OptimizationAlgorithmLevenberg, _maxTrialsAfterFailure = 10) deterministically.  General solver only. */
+ * in one iteration drive g2o's Terminate path (OptimizationAlgorithmLevenberg, _maxTrialsAfterFailure = 10) deterministically.  Every solver honours it: the general
+ * one (k_ba_lm), the pose-only one (poseBundleAdjust) and the one-pose one (stage 1 of localBundleAdjust).  0 switches it off; a new handle starts at 0. */
 int ms_ba_debug_force_reject(ms_ba *ba, int first_trials);
 /* Results of problem i (synchronises): poses [n_pose*7], points [n_point*3], per-observation chi2
  * (what the outlier rule chi2 > 5.991 of :376-388 reads).  They are evaluated at the state that is RETURNED, i.e. the last accepted one.  g2o's edge->chi2() is the

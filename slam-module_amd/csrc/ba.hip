@@ -76,7 +76,7 @@ struct BaProb {
     int32_t n_pose, n_point, n_obs, n_edge, np_free, n6, max_iters;
     int32_t team;                            // workgroups that share this problem (1 = the whole solve in one workgroup)
     int32_t chol_team;                       // of these, the workgroups that share the distributed Cholesky (systems beyond kMaxFreePoses)
-    int32_t debug_reject;                    // test hook (ms_ba_debug_force_reject): the first n damped trials of k_ba_lm count as rejected
+    int32_t debug_reject;                    // test hook (ms_ba_debug_force_reject): the first n damped trials count as rejected (k_ba_lm, k_ba_pose_only, k_ba_one_pose)
     double huber;
     // state
     double *pose, *pose_bk, *point, *point_bk;
@@ -5055,10 +5055,11 @@ int ms_ba_admission_errors(void) { std::lock_guard<std::mutex> lk(g_team_mu); re
 int ms_ba_debug_fail_team_barriers(ms_ba *B, int on) { if (!B) return MS_ERR_INVALID; B->debug_fail_barriers = on ? 1 : 0; return MS_OK; }
 int ms_ba_debug_force_reject(ms_ba *B, int first_trials) {
     if (!B || first_trials < 0 || first_trials > 255) return MS_ERR_INVALID;
-    if (B->pose_only || B->one_pose) return ms_fail(B->ctx, MS_ERR_INVALID, "ms_ba_debug_force_reject: only the general solver (k_ba_lm) has the hook");
     for (auto &h : B->host) h.debug_reject = first_trials;
     MS_HIP(B->ctx, hipSetDevice(B->ctx->device));
-    MS_HIP(B->ctx, ba_upload_descriptors(B, B->ctx->stream));          // (both sets: the fused trial schedule reads whichever is in use)
+    // (both sets: the fused trial schedule reads whichever is in use; a single problem's descriptors sit in its arena, where k_ba_pose_only and k_ba_one_pose read
+    // them too; ms_ba_create sets the field to 0, so a handle object recycled from the pool starts without the hook)
+    MS_HIP(B->ctx, ba_upload_descriptors(B, B->ctx->stream));
     return MS_OK;
 }
 

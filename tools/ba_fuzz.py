@@ -1,5 +1,8 @@
 """Differential fuzz of the bundle adjuster against the CPU oracle: N random windows (2..70 keyframes, ragged visibility, fixed poses and
-points, outliers, loop-closure edges, pose-only cases, stage-1 shaped batches with one free keyframe), solved alone / in a batch / on teams; residuals within 1e-7 (north_star: 1e-5; observed 2e-10 over 8000 windows), LM trajectory equal.
+points, outliers, loop-closure edges, pose-only cases, stage-1 shaped batches with one free keyframe, poseBundleAdjust-shaped batches with one free keyframe and
+every point fixed), solved alone / in a batch / on teams, some with forced rejections (the test hook, passed to the oracle too); residuals within 1e-7 (north_star:
+1e-5; observed 2e-10 over 8000 windows), LM trajectory equal, chi2 per observation at test_gpu_ba._check's bar, fixed poses and points unmoved.  Every batch is
+classified by the host's routing rule (k_ba_pose_only / k_ba_one_pose / k_ba_lm) and the summary line counts the routes.
 usage: python tools/ba_fuzz.py [N] [seed]"""
 import os, sys
 R = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,19 +42,74 @@ def random_problem(one_pose=False):
     return p
 
 
+def pose_only_problem():
+    """poseBundleAdjust-shaped: one free keyframe, every other keyframe and every point fixed; 0..8 SE3 edges at the free keyframe (either side), the chain's
+    edges between fixed keyframes; the free keyframe's observations on both sides of what k_ba_pose_only keeps in registers (192 x 8), optionally the fixed
+    keyframes' too."""
+    n_pose = int(rng.integers(2, 9)); run = n_pose if rng.random() < 0.5 else int(rng.integers(1, n_pose + 1))
+    n_point = int(rng.integers(1700, 3500)) if run == n_pose and rng.random() < 0.5 else int(rng.integers(5, 1500))
+    w = ba_synth.make_problem(n_pose, n_point, run, seed=int(rng.integers(0, 1 << 30)), outlier_frac=float(rng.choice([0, 0, 0.05, 0.15])))
+    cur = int(rng.choice(np.unique(w["obs_pose"])))                                          # (a keyframe that sees something: its 6 x 6 system is not empty)
+    p = dict(w)
+    p["pose_fixed"] = np.ones(n_pose, np.uint8); p["pose_fixed"][cur] = 0
+    p["point_fixed"] = np.ones(n_point, np.uint8)
+    if rng.random() < 0.5: p["point"] = w["gt_point"].copy()
+    if rng.random() < 0.5:                                                                    # only the free keyframe's observations, as poseBundleAdjust builds it
+        sel = w["obs_pose"] == cur
+        for k in ("obs_pose", "obs_point", "obs_uv", "obs_info"): p[k] = w[k][sel]
+    touch = (w["edge_i"] == cur) | (w["edge_j"] == cur)
+    ei, ej, em, ew = list(w["edge_i"][~touch]), list(w["edge_j"][~touch]), list(w["edge_meas"][~touch]), list(w["edge_info"][~touch])
+    for _ in range(int(rng.integers(0, 9))):                                                  # edges at the free keyframe (a pair may repeat)
+        o = int(rng.integers(0, n_pose - 1)); o += o >= cur
+        a, b = (cur, o) if rng.random() < 0.5 else (o, cur)
+        ei.append(a); ej.append(b); em.append(ba_synth._compose(w["gt_pose"][b], ba_synth._inverse(w["gt_pose"][a]))); ew.append(w["edge_info"][0])
+    p["edge_i"], p["edge_j"] = np.array(ei, np.int32), np.array(ej, np.int32)
+    p["edge_meas"], p["edge_info"] = np.array(em, np.float64).reshape(-1, 7), np.array(ew, np.float64).reshape(-1, 36)
+    return p
+
+
+def route(probs, team):
+    """The kernel ms_ba_solve launches for this batch (ba.hip: ms_ba_create's per-problem flags, ms_ba_solve's choice): k_ba_pose_only when every problem has
+    ONE free pose, at most PO_MAXE = 8 SE3 edges touching it and every point fixed, and no team above 1 was asked for; k_ba_one_pose when every problem has
+    ONE free pose, at least one free point, at most OP_NT = 512 SE3 edges and at most PO_MAXE touching the free pose; else k_ba_lm."""
+    po = op = True
+    for p in probs:
+        free = np.flatnonzero(p["pose_fixed"] == 0)
+        touching = int(((p["edge_i"] == free[0]) | (p["edge_j"] == free[0])).sum()) if len(free) == 1 else 0
+        one = len(free) == 1 and touching <= 8
+        all_fixed = (p.get("point_fixed") is not None and bool(np.all(p["point_fixed"] != 0))) or len(p["point"]) == 0
+        po = po and one and all_fixed
+        op = op and one and not all_fixed and len(p["edge_i"]) <= 512
+    return "pose_only" if po and team <= 1 else "one_pose" if op else "general"
+
+
 bad = done = 0
 worst = 0.0
+routes = dict(pose_only=0, one_pose=0, general=0)
 while done < N:
-    one_pose = rng.random() < 0.25                                       # the whole batch in the shape k_ba_one_pose takes (teams, lanes per point and rounds by the sizes drawn)
-    probs = [random_problem(one_pose) for _ in range(int(rng.integers(1, 5)))]
-    iters = int(rng.integers(1, 9)); team = int(rng.choice([0, 1, 2, 5, 16]))
-    want = [mso.ba_solve(p, iters, False) for p in probs]
-    ba = mi355slam.BundleAdjuster(ctx, probs, max_iters=iters); ba.set_team(team); ba.solve()
+    shape = rng.random()
+    if shape < 0.2:                                                      # the whole batch in the shape k_ba_pose_only takes
+        probs = [pose_only_problem() for _ in range(int(rng.integers(1, 5)))]
+        team = int(rng.choice([0, 1]))
+    else:
+        one_pose = shape < 0.4                                           # the whole batch in the shape k_ba_one_pose takes (teams, lanes per point and rounds by the sizes drawn)
+        probs = [random_problem(one_pose) for _ in range(int(rng.integers(1, 5)))]
+        team = int(rng.choice([0, 1, 2, 5, 16]))
+    iters = int(rng.integers(1, 9)); n_rej = int(rng.choice([0, 0, 0, 0, 0, 0, 3, 7, 10]))
+    routes[route(probs, team)] += 1
+    want = [mso.ba_solve(p, iters, False, force_reject=n_rej) for p in probs]
+    ba = mi355slam.BundleAdjuster(ctx, probs, max_iters=iters); ba.set_team(team); ba.debug_force_reject(n_rej); ba.solve()
     for p, w, i in zip(probs, want, range(len(probs))):
         g = ba.download(i)
         rg, rw = ba_synth.residuals_fast(p, g["pose"], g["point"]), ba_synth.residuals_fast(p, w["pose"], w["point"])
         worst = max(worst, float(np.abs(rg - rw).max()))
         ok = np.abs(rg - rw).max() < 1e-7 and abs(g["stats"]["chi2_final"] - w["stats"]["chi2_final"]) <= 1e-7 * abs(w["stats"]["chi2_final"]) + 1e-8
+        ok = ok and np.allclose(g["chi2"], w["chi2"], rtol=1e-4, atol=1e-6)                  # (the bar of test_gpu_ba._check)
+        pf = p["pose_fixed"] != 0
+        ok = ok and np.array_equal(g["pose"][pf], p["pose"][pf])
+        if p.get("point_fixed") is not None:
+            lf = p["point_fixed"] != 0
+            ok = ok and np.array_equal(g["point"][lf], p["point"][lf])
         # the LM trajectory (iterations, trials, stop reason) must be the oracle's, except once the solve has converged and the gain ratio is
         # rounding noise (then a trial or an iteration more or less is taken at the same minimum): the same robust chi2 to 1e-10 relative.  (Round 4: the bar for
         # that case used to be 1e-8 on the residuals; one window in 6000 -- 27 keyframes on a team of 16, 15 trials against 14 -- ended 1.17e-8 away with chi2 equal
@@ -62,8 +120,10 @@ while done < N:
         if not ok:
             bad += 1
             print("MISMATCH", dict(poses=len(p["pose"]), points=len(p["point"]), obs=len(p["obs_pose"]), iters=iters, team=team, fixed=int(p["pose_fixed"].sum()),
+                                   route=route(probs, team), forced=n_rej,
                                    dres=float(np.abs(rg - rw).max()), stats=(g["stats"]["iters"], g["stats"]["trials"], w["stats"]["iters"], w["stats"]["trials"]),
                                    chi2=(g["stats"]["chi2_final"], w["stats"]["chi2_final"])), flush=True)
     ba.close()
-print("ba fuzz: %d windows, %d mismatches; largest residual difference to the oracle %.2e (the fuzz fails above 1e-7; north_star's tolerance is 1e-5)" % (done, bad, worst))
+print("ba fuzz: %d windows, %d mismatches; largest residual difference to the oracle %.2e (the fuzz fails above 1e-7; north_star's tolerance is 1e-5); "
+      "routes: pose_only=%d one_pose=%d general=%d (batches)" % (done, bad, worst, routes["pose_only"], routes["one_pose"], routes["general"]))
 sys.exit(1 if bad else 0)
