@@ -326,6 +326,59 @@ int ms_bow_db_query_ids(ms_bow_db *db, int q, const int32_t *map_ids, const int3
                         float min_in_common_ratio, float score_ratio, int max_out_per_query,
                         int32_t *out_map, int32_t *out_kf, float *out_score, int *n_total);
 
+/* ---- N4: loop-closure RANSAC behind LoopRansac::ransacSolve (loop_ransac.cpp:8-314) --------------------------------------
+ * Camera stand-in: tracker::Camera lives in the parent project, outside the reference tree, so the reprojection of
+ * reprojectToImage (keyframe.cpp:340-356) is restated for a PINHOLE camera only (other models are not supported):
+ *   p_c = A * p + t;  visible iff p_c.z > 0 and (u, v) lies in [0, width) x [0, height), u = fx * (p_c.x / p_c.z) + cx,
+ *   v = fy * (p_c.y / p_c.z) + cy, all in double.  Comparisons with NaN are false, so a non-finite hypothesis sees nothing. */
+typedef struct { double fx, fy, cx, cy; int32_t width, height; } ms_pinhole;
+
+#define MS_RANSAC_SIM3 0                 /* LoopRansac::DoF::SIM3: computeSim3, Horn's quaternion method (:112-196) */
+#define MS_RANSAC_ZROT 1                 /* LoopRansac::DoF::ZROT: computeRotZ, rotation about z only (:277-314) */
+#define MS_LOOP_RANSAC_MAX_MATCHES (1 << 20)    /* per problem */
+#define MS_LOOP_RANSAC_MAX_ITER (1 << 20)       /* per problem (the packed best key needs n_iter < 2^32) */
+#define MS_LOOP_RANSAC_MAX_PROBLEMS 65535       /* per call */
+
+/* One LoopRansac object (loop_ransac.cpp:8-45) and its ransacSolve arguments.  All pointers are HOST pointers. */
+typedef struct {
+    int32_t n_matches;                   /* matchCount */
+    const double *pts1, *pts2;           /* [n*3] commonPtsInKeyframe1/2: the matched map points in each keyframe's camera frame */
+    const float *thr1, *thr2;            /* [n] chiSqSigmaSq1/2 = CHI_SQ_2D * levelSigmaSq[octave], a float product (CHI_SQ_2D = 9.21034f) */
+    ms_pinhole cam1, cam2;               /* the keyframes' cameras (width, height >= 1) */
+    int32_t n_iter;                      /* max_num_iter, >= 0 */
+    const int32_t *samples;              /* [n_iter*3] the triplet of each iteration: distinct indices in [0, n) (create_random_array(3, 0, n-1));
+                                            not read (may be NULL) when the early return applies */
+    int32_t dof;                         /* MS_RANSAC_SIM3 or MS_RANSAC_ZROT */
+    int32_t fix_scale;                   /* loopClosureRansacFixScale */
+    int32_t min_inliers;                 /* loopClosureRansacMinInliers, >= 0 */
+} ms_loop_ransac_problem;
+
+typedef struct {
+    int32_t solution_ok;                 /* solutionOk */
+    int32_t best_inlier_count;           /* bestInlierCount */
+    int32_t best_iter;                   /* the earliest iteration with the most inliers; -1 when none scored above 0 (or the early return applied) */
+    double R12[9];                       /* bestR12, row-major; bestT12; bestScale12.  Zero when best_iter = -1 (the reference leaves them unassigned) */
+    double t12[3];
+    float scale12;
+} ms_loop_ransac_result;
+
+/* LoopRansac::ransacSolve (loop_ransac.cpp:47-110) for n problems in one chain of launches on the context stream; synchronous.
+ *   early return (:52-54): n_matches < 3 or n_matches < min_inliers -> solution_ok = 0, count 0, best_iter -1, no samples read.
+ *   iteration i: the hypothesis (R21, t21, s21) of samples[3i..3i+2]; s21 = (float)(numer / denom); with fix_scale s21 = 1 while t21
+ *     keeps the translation of the unfixed scale (:85-86); s12 = 1 / s21 in float, R12 = R21^T, t12 = -s12 * R12 * t21 (:88-91).
+ *   inliers (:198-229): both own-image projections (identity pose) and both cross projections visible, and both squared pixel errors,
+ *     in double, < their float thresholds.  The best is the earliest iteration with the largest count (:98); solution_ok = count >= min_inliers.
+ * union_inliers[p] (optional, [n_matches] bytes): the reference's bestInliers -- its inlier vector is never cleared between iterations (:64, :202),
+ *   so it is the UNION of the inlier sets of iterations 0 .. best_iter, the mask loop_closer.cpp:239-243 selects matches with.  All 0 when best_iter = -1.
+ * best_inliers[p] (optional, [n_matches] bytes): the inlier set of the best hypothesis alone.
+ * hyp_inliers[p] (optional, [n_iter] int32): every iteration's inlier count.
+ * A coincident or collinear triplet gives a non-finite or arbitrary hypothesis; non-finite ones score 0, never an error.
+ * MS_ERR_INVALID (nothing written) for a sample outside [0, n_matches), a triplet with a repeated index, a bad dof / camera / count;
+ * MS_ERR_CAPACITY beyond the MS_LOOP_RANSAC_MAX_* caps.  One upload and one download per call; the workspace belongs to the context and only
+ * grows, so calls no larger than an earlier one allocate nothing (ms_debug_host_allocs). */
+int ms_loop_ransac(ms_ctx *ctx, const ms_loop_ransac_problem *problems, int n, ms_loop_ransac_result *results,
+                   uint8_t *const *union_inliers, uint8_t *const *best_inliers, int32_t *const *hyp_inliers);
+
 /* FeatureSearch (feature_search.{hpp,cpp}): the keyframe's keypoints sorted by y.  Host helper; std::stable_sort, so points
  * with equal y keep index order (the reference's std::sort leaves that order unspecified).  sorted_idx[p] = keypoint index. */
 int ms_feature_search_sort(const float *x, const float *y, int n, float *sorted_x, float *sorted_y, int32_t *sorted_idx);

@@ -142,6 +142,8 @@ void ms_ctx_destroy(ms_ctx *c) {
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->pinned) (void)hipHostFree(c->pinned);
+    if (c->lr_dev) (void)hipFree(c->lr_dev);
+    if (c->lr_host) (void)hipHostFree(c->lr_host);
     for (auto &b : c->ba_cache) if (b.p) (void)hipFree(b.p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

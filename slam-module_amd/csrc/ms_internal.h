@@ -36,6 +36,9 @@ struct ms_ctx {
     hipEvent_t ba_stage_ev = nullptr;
     bool ba_stage_busy = false;
     void *ba_handle_pool[4] = {nullptr, nullptr, nullptr, nullptr};      // destroyed bundle-adjustment handle OBJECTS (their vectors keep their capacity, their event stays): ms_ba_create takes one back
+    // ms_loop_ransac's workspace (loop_ransac.hip): device inputs / work / results and their page-locked staging, grow-only
+    void *lr_dev = nullptr, *lr_host = nullptr;
+    size_t lr_dev_bytes = 0, lr_host_bytes = 0;
     char err[512] = {0};
 };
 

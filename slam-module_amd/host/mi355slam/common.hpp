@@ -30,6 +30,10 @@ struct Parameters {
     float epipolarCheckThresholdDegrees = 2.0f;
     double odometryPriorStrengthRotation = 100.0, odometryPriorStrengthPosition = 50.0;
     unsigned minVisibleMapPointsInNeighborhoodBA = 0;
+    // loop_closer.cpp:230, loop_ransac.cpp:50, :85: set by the parent project, whose defaults are not in the reference tree
+    unsigned loopClosureRansacIterations = 300;
+    unsigned loopClosureRansacMinInliers = 10;
+    bool loopClosureRansacFixScale = false;
 };
 
 // slam::StaticSettings (static_settings.hpp:9-21)

@@ -774,3 +774,75 @@ class BundleAdjuster:
             self.close()
         except Exception:
             pass
+
+
+# ---- loop-closure RANSAC (ms_loop_ransac) ----
+RANSAC_SIM3, RANSAC_ZROT = 0, 1
+
+
+class Pinhole(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class LoopRansacProblemC(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("pts1", C.c_void_p), ("pts2", C.c_void_p), ("thr1", C.c_void_p), ("thr2", C.c_void_p),
+                ("cam1", Pinhole), ("cam2", Pinhole), ("n_iter", C.c_int32), ("samples", C.c_void_p),
+                ("dof", C.c_int32), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32)]
+
+
+class LoopRansacResultC(C.Structure):
+    _fields_ = [("solution_ok", C.c_int32), ("best_inlier_count", C.c_int32), ("best_iter", C.c_int32),
+                ("R12", C.c_double * 9), ("t12", C.c_double * 3), ("scale12", C.c_float)]
+
+
+def draw_samples(n_matches, n_iter, rng):
+    """n_iter triplets of distinct indices in [0, n_matches) from a numpy Generator.  NOT the reference's sampler (openvslam's thread_local
+    std::mt19937 with create_random_array): only the C++ mirror (host/mi355slam/loop_ransac.hpp) reproduces that one."""
+    if n_iter == 0 or n_matches < 3:
+        return np.zeros((n_iter, 3), np.int32)
+    return np.stack([rng.choice(n_matches, 3, replace=False) for _ in range(n_iter)]).astype(np.int32)
+
+
+def loop_ransac(ctx, problems, hyp_counts=False, rng=None):
+    """LoopRansac::ransacSolve for a batch of problems in one ms_loop_ransac call.  Each problem is a dict:
+      pts1, pts2  [n, 3] float64: the matched points in each keyframe's camera frame (commonPtsInKeyframe1/2)
+      thr1, thr2  [n] float32: CHI_SQ_2D * levelSigmaSq[octave] (chiSqSigmaSq1/2)
+      cam1, cam2  (fx, fy, cx, cy, width, height) pinhole cameras
+      n_iter, dof (RANSAC_SIM3 / RANSAC_ZROT), fix_scale, min_inliers
+      samples     [n_iter, 3] int32, optional: drawn with draw_samples(n, n_iter, rng) when missing (rng: a numpy Generator)
+    Returns one dict per problem: ok, count, best_iter, R12 [3, 3], t12 [3], scale12 (float32), union (the reference's bestInliers: the union of
+    the inlier sets of iterations 0 .. best_iter), best (the best hypothesis's own inliers), samples, and counts [n_iter] when hyp_counts."""
+    n = len(problems)
+    keep, structs = [], []
+    for p in problems:
+        pts1 = np.ascontiguousarray(p["pts1"], np.float64).reshape(-1, 3)
+        pts2 = np.ascontiguousarray(p["pts2"], np.float64).reshape(-1, 3)
+        thr1 = np.ascontiguousarray(p["thr1"], np.float32).reshape(-1)
+        thr2 = np.ascontiguousarray(p["thr2"], np.float32).reshape(-1)
+        m, it = len(pts1), int(p["n_iter"])
+        if not (len(pts2) == len(thr1) == len(thr2) == m):
+            raise ValueError("pts1, pts2, thr1 and thr2 must describe the same matches")
+        smp = p.get("samples")
+        if smp is None:
+            smp = draw_samples(m, it, rng if rng is not None else np.random.default_rng(0))
+        smp = np.ascontiguousarray(smp, np.int32).reshape(-1, 3)
+        keep.append((pts1, pts2, thr1, thr2, smp))
+        structs.append(LoopRansacProblemC(m, pts1.ctypes.data, pts2.ctypes.data, thr1.ctypes.data, thr2.ctypes.data, Pinhole(*p["cam1"]), Pinhole(*p["cam2"]),
+                                          it, smp.ctypes.data if smp.size else 0, int(p.get("dof", RANSAC_SIM3)), int(bool(p.get("fix_scale", False))),
+                                          int(p.get("min_inliers", 0))))
+    P = (LoopRansacProblemC * max(n, 1))(*structs)
+    R = (LoopRansacResultC * max(n, 1))()
+    um = [np.zeros(len(k[0]), np.uint8) for k in keep]
+    bm = [np.zeros(len(k[0]), np.uint8) for k in keep]
+    cn = [np.zeros(int(p["n_iter"]), np.int32) for p in problems]
+    ptr = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    ctx.check(lib().ms_loop_ransac(ctx._h, P, n, R, ptr(um), ptr(bm), ptr(cn) if hyp_counts else None), "ms_loop_ransac")
+    out = []
+    for i in range(n):
+        r = R[i]
+        d = dict(ok=bool(r.solution_ok), count=int(r.best_inlier_count), best_iter=int(r.best_iter), R12=np.array(r.R12[:]).reshape(3, 3),
+                 t12=np.array(r.t12[:]), scale12=np.float32(r.scale12), union=um[i].astype(bool), best=bm[i].astype(bool), samples=keep[i][4])
+        if hyp_counts:
+            d["counts"] = cn[i]
+        out.append(d)
+    return out
