@@ -379,6 +379,57 @@ typedef struct {
 int ms_loop_ransac(ms_ctx *ctx, const ms_loop_ransac_problem *problems, int n, ms_loop_ransac_result *results,
                    uint8_t *const *union_inliers, uint8_t *const *best_inliers, int32_t *const *hyp_inliers);
 
+/* ---- N5: the Sim3 refinement behind OptimizeSim3Transform (optimize_transform.cpp:63-155) ---------------------------------
+ * g2o is outside the reference tree; tests/sim3_opt_ref.py restates the solve and is this entry point's specification.
+ * The unknown is one g2o::Sim3 S12 = (r, t, s), S.map(p) = s * (r * p) + t.  Match i gives two edges with focal lengths 1 and
+ * principal points 0 (:89-97), proj(y) = (y.x / y.z, y.y / y.z) a plain division without a visibility test:
+ *   edge 12 (EdgeSim3ProjectXYZ, :118-127)         e = obs1 - proj(S12.map(p2))
+ *   edge 21 (EdgeInverseSim3ProjectXYZ, :133-142)  e = obs2 - proj(S12^-1.map(p1))
+ * Information levelSigmaSq[octave] * I2: the reference multiplies by levelSigmaSq, NOT by its inverse (:122, :137); that is kept.
+ * RobustKernelHuber on chi2 = info * |e|^2 (:124-126, :139-141).  Update S <- Sim3::exp(dx) * S, dx = (omega, upsilon, sigma), dx[6] = 0
+ * under fix_scale (:87).  Levenberg-Marquardt as g2o's OptimizationAlgorithmLevenberg runs it (the schedule of ms_ba_solve), 7 x 7
+ * Cholesky.  The Jacobian is the analytic derivative of that update; g2o differentiates these two edges numerically. */
+#define MS_SIM3_OPT_MAX_MATCHES (1 << 20)       /* per problem */
+#define MS_SIM3_OPT_MAX_PROBLEMS 65535          /* per call */
+
+/* One OptimizeSim3Transform call.  All pointers are HOST pointers. */
+typedef struct {
+    int32_t n_matches;                   /* matches.size() (:101) */
+    const double *pts1, *pts2;           /* [n*3] kf1.poseCW * mp1.position, kf2.poseCW * mp2.position: the fixed vertices (getMpVertex, :44-59) */
+    const double *obs1, *obs2;           /* [n*2] bearing.xy / bearing.z of the observing keypoints (:116, :131) */
+    const float *info1, *info2;          /* [n] settings.levelSigmaSq.at(octave) (:122, :137) */
+    double huber_delta;                  /* (double)(float)sqrt(loopClosureInlierThreshold) (:72-73, :125); <= 0: no robust kernel */
+    int32_t fix_scale;                   /* loopClosureRansacFixScale -> VertexSim3Expmap::_fix_scale (:74, :87) */
+    int32_t max_iters;                   /* optimizer.optimize(20) (:146), >= 0 */
+    double R12[9];                       /* the initial transform12 (:85): Sim3(bestR12, bestT12, bestScale12) of loop_closer.cpp:273-276, */
+    double t12[3];                       /* R12 row-major -- what ms_loop_ransac_result holds, its float scale12 widened */
+    double scale12;
+} ms_sim3_opt_problem;
+
+typedef struct {
+    double R12[9];                       /* the refined transform12 (:151), row-major rotation, never re-orthonormalised */
+    double t12[3];
+    double scale12;                      /* bit-identical to the input under fix_scale */
+    double chi2_init, chi2_final;        /* activeRobustChi2 before / at the returned state (as ms_ba_result: chi2_initial, chi2_final) */
+    double lambda;                       /* final_lambda */
+    int32_t iters;                       /* LM iterations run (iterations) */
+    int32_t trials_total;                /* damped solves, including rejected ones (trials) */
+    int32_t stop_reason;                 /* 1 if g2o's Terminate condition ended the run (stopped_early) */
+    int32_t reserved;                    /* 0 */
+} ms_sim3_opt_result;
+
+/* OptimizeSim3Transform (optimize_transform.cpp:63-155) for n independent problems: one launch on the context stream, one workgroup per
+ * problem; synchronous.  The reference's return value is matches.size() (:153-154); its inlier check is a TODO (:148) and is not invented.
+ *   n_matches = 0 or max_iters = 0: the estimate comes back unchanged with iters = 0 (no match: chi2 0).
+ *   Non-finite input: every trial is rejected, the initial estimate comes back bit for bit with a non-finite chi2, no error.
+ * chi2_per_edge (optional; chi2_per_edge[p] optional): [2 * n_matches] info * |e|^2 at the returned state, edge 12 of match i at 2 i,
+ *   edge 21 at 2 i + 1; through the Huber kernel they sum to chi2_final.
+ * The same input gives the same bits on every call and at every position of a batch (fixed reduction order, no float atomics).
+ * MS_ERR_INVALID (nothing written) for a negative count, max_iters < 0, a non-finite huber_delta or a missing array with n_matches > 0;
+ * MS_ERR_CAPACITY beyond the MS_SIM3_OPT_MAX_* caps.  One upload and one download per call; the workspace belongs to the context and
+ * only grows, so calls no larger than an earlier one allocate nothing (ms_debug_host_allocs). */
+int ms_sim3_optimize(ms_ctx *ctx, const ms_sim3_opt_problem *problems, int n, ms_sim3_opt_result *results, double *const *chi2_per_edge);
+
 /* FeatureSearch (feature_search.{hpp,cpp}): the keyframe's keypoints sorted by y.  Host helper; std::stable_sort, so points
  * with equal y keep index order (the reference's std::sort leaves that order unspecified).  sorted_idx[p] = keypoint index. */
 int ms_feature_search_sort(const float *x, const float *y, int n, float *sorted_x, float *sorted_y, int32_t *sorted_idx);

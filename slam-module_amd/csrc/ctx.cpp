@@ -144,6 +144,8 @@ void ms_ctx_destroy(ms_ctx *c) {
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->lr_dev) (void)hipFree(c->lr_dev);
     if (c->lr_host) (void)hipHostFree(c->lr_host);
+    if (c->s3_dev) (void)hipFree(c->s3_dev);
+    if (c->s3_host) (void)hipHostFree(c->s3_host);
     for (auto &b : c->ba_cache) if (b.p) (void)hipFree(b.p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

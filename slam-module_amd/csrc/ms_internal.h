@@ -39,6 +39,9 @@ struct ms_ctx {
     // ms_loop_ransac's workspace (loop_ransac.hip): device inputs / work / results and their page-locked staging, grow-only
     void *lr_dev = nullptr, *lr_host = nullptr;
     size_t lr_dev_bytes = 0, lr_host_bytes = 0;
+    // ms_sim3_optimize's workspace (sim3_opt.hip): device inputs / results and their page-locked staging, grow-only
+    void *s3_dev = nullptr, *s3_host = nullptr;
+    size_t s3_dev_bytes = 0, s3_host_bytes = 0;
     char err[512] = {0};
 };
 

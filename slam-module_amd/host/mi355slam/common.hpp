@@ -34,6 +34,8 @@ struct Parameters {
     unsigned loopClosureRansacIterations = 300;
     unsigned loopClosureRansacMinInliers = 10;
     bool loopClosureRansacFixScale = false;
+    // optimize_transform.cpp:72-73: the Huber delta of OptimizeSim3Transform is (float)sqrt of it; set by the parent project (a stand-in default)
+    double loopClosureInlierThreshold = 1e-4;
 };
 
 // slam::StaticSettings (static_settings.hpp:9-21)

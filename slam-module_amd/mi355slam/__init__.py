@@ -846,3 +846,62 @@ def loop_ransac(ctx, problems, hyp_counts=False, rng=None):
             d["counts"] = cn[i]
         out.append(d)
     return out
+
+
+# ---- Sim3 refinement (ms_sim3_optimize) ----
+class Sim3OptProblemC(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("pts1", C.c_void_p), ("pts2", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p),
+                ("info1", C.c_void_p), ("info2", C.c_void_p), ("huber_delta", C.c_double), ("fix_scale", C.c_int32), ("max_iters", C.c_int32),
+                ("R12", C.c_double * 9), ("t12", C.c_double * 3), ("scale12", C.c_double)]
+
+
+class Sim3OptResultC(C.Structure):
+    _fields_ = [("R12", C.c_double * 9), ("t12", C.c_double * 3), ("scale12", C.c_double), ("chi2_init", C.c_double), ("chi2_final", C.c_double),
+                ("lam", C.c_double), ("iters", C.c_int32), ("trials_total", C.c_int32), ("stop_reason", C.c_int32), ("reserved", C.c_int32)]
+
+
+def sim3_opt_pack(problems):
+    """(ctypes problem array, the numpy arrays it points into) for ms_sim3_optimize; see sim3_optimize for the problem dicts."""
+    keep, structs = [], []
+    for p in problems:
+        pts1 = np.ascontiguousarray(p["pts1"], np.float64).reshape(-1, 3)
+        pts2 = np.ascontiguousarray(p["pts2"], np.float64).reshape(-1, 3)
+        obs1 = np.ascontiguousarray(p["obs1"], np.float64).reshape(-1, 2)
+        obs2 = np.ascontiguousarray(p["obs2"], np.float64).reshape(-1, 2)
+        info1 = np.ascontiguousarray(p["info1"], np.float32).reshape(-1)
+        info2 = np.ascontiguousarray(p["info2"], np.float32).reshape(-1)
+        m = len(pts1)
+        if not (len(pts2) == len(obs1) == len(obs2) == len(info1) == len(info2) == m):
+            raise ValueError("pts1, pts2, obs1, obs2, info1 and info2 must describe the same matches")
+        keep.append((pts1, pts2, obs1, obs2, info1, info2))
+        R = np.ascontiguousarray(p["R12"], np.float64).reshape(9)
+        t = np.ascontiguousarray(p["t12"], np.float64).reshape(3)
+        structs.append(Sim3OptProblemC(m, *[a.ctypes.data if m else 0 for a in keep[-1]], float(p["huber_delta"]), int(bool(p.get("fix_scale", False))),
+                                       int(p.get("max_iters", 20)), (C.c_double * 9)(*R), (C.c_double * 3)(*t), float(p["scale12"])))
+    return (Sim3OptProblemC * max(len(problems), 1))(*structs), keep
+
+
+def sim3_optimize(ctx, problems, chi2=False):
+    """OptimizeSim3Transform for a batch of independent problems in one ms_sim3_optimize call.  Each problem is a dict:
+      pts1, pts2    [n, 3] float64: the matched map points in each keyframe's camera frame
+      obs1, obs2    [n, 2] float64: bearing.xy / bearing.z of the observing keypoints
+      info1, info2  [n] float32: levelSigmaSq[octave]
+      huber_delta   (double)(float)sqrt(loopClosureInlierThreshold); fix_scale; max_iters (default 20)
+      R12 [3, 3], t12 [3], scale12: the initial Sim3 (what loop_ransac returns)
+    Returns one dict per problem: R12, t12, scale12, chi2_init, chi2_final, lam, iters, trials_total, stop_reason, and chi2 [2 n] (edge 12 then
+    edge 21 of each match, at the returned state) when chi2=True."""
+    n = len(problems)
+    P, keep = sim3_opt_pack(problems)
+    R = (Sim3OptResultC * max(n, 1))()
+    per_edge = [np.zeros(2 * len(k[0])) for k in keep]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in per_edge]) if chi2 else None
+    ctx.check(lib().ms_sim3_optimize(ctx._h, P, n, R, ptrs), "ms_sim3_optimize")
+    out = []
+    for i in range(n):
+        r = R[i]
+        d = dict(R12=np.array(r.R12[:]).reshape(3, 3), t12=np.array(r.t12[:]), scale12=float(r.scale12), chi2_init=float(r.chi2_init),
+                 chi2_final=float(r.chi2_final), lam=float(r.lam), iters=int(r.iters), trials_total=int(r.trials_total), stop_reason=int(r.stop_reason))
+        if chi2:
+            d["chi2"] = per_edge[i]
+        out.append(d)
+    return out
