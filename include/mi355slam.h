@@ -523,13 +523,21 @@ typedef struct {
     const int32_t *obs_point;    /* [n_obs] index of its map-point vertex */
     const double *obs_uv;        /* [n_obs*2] measurement bearing.xy / bearing.z (:52) */
     const double *obs_info;      /* [n_obs]   information = focal^2 / levelSigmaSq[octave] times I2 (:51-53) */
-    double huber_delta;          /* sqrt(5.991) (:56); <= 0 disables the robust kernel */
+    double huber_delta;          /* sqrt(5.991) (:56); <= 0 disables the robust kernel (every projection edge quadratic, as with a delta no chi2 reaches) */
     const int32_t *edge_i;       /* [n_pose_edge] EdgeSE3Expmap vertex 0 (:76, :99, :355) */
     const int32_t *edge_j;       /* [n_pose_edge] vertex 1 */
     const double *edge_meas;     /* [n_pose_edge*7] measurement SE3 */
-    const double *edge_info;     /* [n_pose_edge*36] 6x6 information, row-major, (rotation, translation) order */
+    const double *edge_info;     /* [n_pose_edge*36] 6x6 information W, row-major, (rotation, translation) order: chi2 = e^T W e, b = -J^T (W e),
+                                    H = J^T W J with W as given (rows of W meet the left factor); the factorisation reads H's lower triangle.  A symmetric
+                                    W is what g2o expects; a non-symmetric one is taken literally by all three kernels, neither transposed nor symmetrised */
     int32_t max_iters;           /* optimizer.optimize(iterations) */
-} ms_ba_problem;                 /* all pointers are HOST memory, read during ms_ba_create only */
+} ms_ba_problem;                 /* all pointers are HOST memory, read during ms_ba_create only.  Poses may lie anywhere in the world and carry either quaternion
+                                    sign.  Small shapes SOLVE, they are not rejected: n_obs == 0 and n_point == 0 (a pure pose graph, as globalBundleAdjust builds
+                                    on a fresh map), n_pose_edge == 0, a free point with one observation or none (it stays where it is: its step is 0), a free
+                                    pose without observations and edges (returned bit for bit when its quaternion is normalised with w >= 0, as a solver leaves
+                                    it), an edge between two fixed poses or an observation of a fixed point from a fixed pose (constants of the chi2), repeated
+                                    edges and observations (they count as often as they are listed).  No cheirality test: a point behind a camera is an edge
+                                    like any other, as in g2o */
 
 typedef struct {
     int32_t iterations;          /* LM iterations run */

@@ -414,6 +414,7 @@ int mso_ba_solve(mso_ba_problem *P, double *chi2_per_obs, mso_ba_stats *st, int 
     int have_trial = 0;
     double lambda = 0, ni = 2;
     int it = 0, trials_total = 0, stop = 0;
+    double min_abs_gain = DBL_MAX;
     st->chi2_init = robust_chi2(P, P->pose, P->point, NULL);
     for (it = 0; it < P->max_iters; ++it) {
         double current = robust_chi2(P, P->pose, P->point, NULL), temp = current;
@@ -444,6 +445,7 @@ int mso_ba_solve(mso_ba_problem *P, double *chi2_per_obs, mso_ba_stats *st, int 
             scale += 1e-3;
             rho /= scale;
             if (trials_total < force_reject) rho = -1.0;
+            else if (fabs(rho) < min_abs_gain) min_abs_gain = fabs(rho);
             if (rho > 0 && isfinite(temp)) {
                 double alpha = 1. - pow((2 * rho - 1), 3);
                 alpha = fmin(alpha, 2. / 3.);
@@ -459,7 +461,7 @@ int mso_ba_solve(mso_ba_problem *P, double *chi2_per_obs, mso_ba_stats *st, int 
         } while (rho < 0 && qmax < 10);
         if (qmax == 10 || rho == 0 || !isfinite(lambda)) { stop = 1; ++it; break; }       /* Terminate */
     }
-    st->iters = it; st->lambda = lambda; st->trials_total = trials_total; st->stop_reason = stop;
+    st->iters = it; st->lambda = lambda; st->trials_total = trials_total; st->stop_reason = stop; st->min_abs_gain = min_abs_gain;
     st->chi2_final = robust_chi2(P, P->pose, P->point, chi2_per_obs);
     if (stale_chi2 && have_trial && chi2_per_obs) (void)robust_chi2(P, pose_tr, point_tr, chi2_per_obs);
     free(pose_tr); free(point_tr);

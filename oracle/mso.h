@@ -177,7 +177,9 @@ typedef struct {
     int max_iters;
 } mso_ba_problem;
 
-typedef struct { int iters, trials_total, stop_reason; double lambda, chi2_init, chi2_final; } mso_ba_stats;
+typedef struct { int iters, trials_total, stop_reason; double lambda, chi2_init, chi2_final;
+                 double min_abs_gain;   /* the smallest |rho| (gain ratio) over the trials decided by data: how far the accept / reject decisions stood from rounding */
+} mso_ba_stats;
 
 /* full_system = 1 solves the undamped-ordering-free dense (poses+points) system, 0 the Schur complement. */
 int mso_ba_solve(mso_ba_problem *P, double *chi2_per_obs, mso_ba_stats *st, int flags);      /* flags: see ba.c */

@@ -345,7 +345,7 @@ class BaProblem(C.Structure):
 
 class BaStats(C.Structure):
     _fields_ = [("iters", C.c_int), ("trials_total", C.c_int), ("stop_reason", C.c_int),
-                ("lambda_", C.c_double), ("chi2_init", C.c_double), ("chi2_final", C.c_double)]
+                ("lambda_", C.c_double), ("chi2_init", C.c_double), ("chi2_final", C.c_double), ("min_abs_gain", C.c_double)]
 
 
 def ba_solve(prob, max_iters=10, full_system=False, g2o_stale_chi2=False, force_reject=0):
@@ -367,7 +367,7 @@ def ba_solve(prob, max_iters=10, full_system=False, g2o_stale_chi2=False, force_
     rc = lib().mso_ba_solve(C.byref(P), _p(chi2, f64p), C.byref(st), int(bool(full_system)) | (int(bool(g2o_stale_chi2)) << 1) | ((int(force_reject) & 0xFF) << 8))
     assert rc == 0
     return dict(pose=pose, point=point, chi2=chi2[:len(keep["op"])],
-                stats=dict(iters=st.iters, trials=st.trials_total, stop=st.stop_reason, lam=st.lambda_, chi2_init=st.chi2_init, chi2_final=st.chi2_final))
+                stats=dict(iters=st.iters, trials=st.trials_total, stop=st.stop_reason, lam=st.lambda_, chi2_init=st.chi2_init, chi2_final=st.chi2_final, min_abs_gain=st.min_abs_gain))
 
 
 def se3_exp(u):

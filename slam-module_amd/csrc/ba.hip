@@ -2999,12 +2999,12 @@ __device__ __noinline__ double po_edges_setup(const BaProb &P, int pi, int lane,
             s_eG[36 * sl + lane] = -v;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (lane < 21) {                                                    // upper triangle of J^T W J = -G J, entry (a, b) at a (11 - a) / 2 + b
-            int a2 = 0, rest = lane;
-            while (rest >= 6 - a2) { rest -= 6 - a2; ++a2; }
+        if (lane < 21) {                                                    // J^T W J = -G J packed by (a <= b) at a (11 - a) / 2 + b; the value is entry (b, a), the LOWER
+            int a2 = 0, rest = lane;                                        // triangle -- the one the general kernel's Cholesky and the oracle read: it matters for a W that
+            while (rest >= 6 - a2) { rest -= 6 - a2; ++a2; }                // is not symmetric (mi355slam.h: W is taken as given)
             const int b2 = a2 + rest;
             double v = 0;
-            for (int c = 0; c < 6; ++c) v += s_eG[36 * sl + 6 * a2 + c] * s_J[6 * c + b2];
+            for (int c = 0; c < 6; ++c) v += s_eG[36 * sl + 6 * b2 + c] * s_J[6 * c + a2];
             s_Hc[lane] -= v;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();

@@ -3,14 +3,37 @@ points, outliers, loop-closure edges, pose-only cases, stage-1 shaped batches wi
 every point fixed), solved alone / in a batch / on teams, some with forced rejections (the test hook, passed to the oracle too); residuals within 1e-7 (north_star:
 1e-5; observed 2e-10 over 8000 windows), LM trajectory equal, chi2 per observation at test_gpu_ba._check's bar, fixed poses and points unmoved.  Every batch is
 classified by the host's routing rule (k_ba_pose_only / k_ba_one_pose / k_ba_lm) and the summary line counts the routes.
-usage: python tools/ba_fuzz.py [N] [seed]"""
+With a third argument `domain` every drawn window is also put through a random subset of the transforms of tests/ba_scenes.py (another world frame, flipped
+quaternion signs, full and non-symmetric information matrices, other Huber deltas, large SE3 errors, other units, points close to a camera), drawn from a
+stream of its own; without it the windows and the random stream are what they always were.
+usage: python tools/ba_fuzz.py [N] [seed] [domain]"""
 import os, sys
 R = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-for p in ("slam-module_amd", "oracle", "tests"): sys.path.insert(0, os.path.join(R, p))
+for p in ("slam-module_amd", "oracle", "tests", "tools"): sys.path.insert(0, os.path.join(R, p))
 import numpy as np, mi355slam, mso, ba_synth
+from ba_route import route                                      # the host's routing rule (tools/ba_route.py: one copy, shared with tests/ba_scenes.py)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+DOMAIN = len(sys.argv) > 3 and sys.argv[3] == "domain"
+if DOMAIN: import ba_scenes
+drng = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 3, 77])          # the domain transforms' own stream
 ctx = mi355slam.Context(0)
+
+
+def domain_transforms(p):
+    """A random subset of ba_scenes' transforms (each with probability 0.4) on a drawn window.  degenerate() is left to the scene tests: it fixes keyframes
+    0 and 1, which could leave a one-free-keyframe window without a free keyframe."""
+    ne = len(p["edge_i"])
+    pick = lambda: drng.random() < 0.4
+    cnt = np.bincount(p["obs_point"], minlength=len(p["point"]))
+    if pick() and (cnt >= 2).sum() >= 4: p = ba_scenes.near_points(p, drng, n_near=2)
+    if pick() and ne: p = ba_scenes.edge_errors(p, [float(drng.choice(ba_scenes.SMALL_ANGLES + ba_scenes.LARGE_ANGLES))], drng, edges=[int(drng.integers(0, ne))])
+    if pick() and ne: p = ba_scenes.dense_edge_info(p, drng, nonsymmetric=(int(drng.integers(0, ne)),) if drng.random() < 0.5 else ())
+    if pick(): p = ba_scenes.rescale(p, float(drng.choice([1e3, 1e-3])))
+    if pick(): p = ba_scenes.move_world(p, ba_scenes.random_rigid(drng, float(drng.uniform(1.0, 3.1)), float(drng.uniform(1.0, 8.0))))
+    if pick(): p = ba_scenes.flip_quaternion_signs(p, drng.random(len(p["pose"])) < 0.5, drng.random(ne) < 0.5)
+    if pick(): p = ba_scenes.huber(p, float(drng.choice([0.0, -1.0, 0.5, 1e6])))
+    return p
 
 
 def random_problem(one_pose=False):
@@ -68,21 +91,6 @@ def pose_only_problem():
     return p
 
 
-def route(probs, team):
-    """The kernel ms_ba_solve launches for this batch (ba.hip: ms_ba_create's per-problem flags, ms_ba_solve's choice): k_ba_pose_only when every problem has
-    ONE free pose, at most PO_MAXE = 8 SE3 edges touching it and every point fixed, and no team above 1 was asked for; k_ba_one_pose when every problem has
-    ONE free pose, at least one free point, at most OP_NT = 512 SE3 edges and at most PO_MAXE touching the free pose; else k_ba_lm."""
-    po = op = True
-    for p in probs:
-        free = np.flatnonzero(p["pose_fixed"] == 0)
-        touching = int(((p["edge_i"] == free[0]) | (p["edge_j"] == free[0])).sum()) if len(free) == 1 else 0
-        one = len(free) == 1 and touching <= 8
-        all_fixed = (p.get("point_fixed") is not None and bool(np.all(p["point_fixed"] != 0))) or len(p["point"]) == 0
-        po = po and one and all_fixed
-        op = op and one and not all_fixed and len(p["edge_i"]) <= 512
-    return "pose_only" if po and team <= 1 else "one_pose" if op else "general"
-
-
 bad = done = 0
 worst = 0.0
 routes = dict(pose_only=0, one_pose=0, general=0)
@@ -96,6 +104,7 @@ while done < N:
         probs = [random_problem(one_pose) for _ in range(int(rng.integers(1, 5)))]
         team = int(rng.choice([0, 1, 2, 5, 16]))
     iters = int(rng.integers(1, 9)); n_rej = int(rng.choice([0, 0, 0, 0, 0, 0, 3, 7, 10]))
+    if DOMAIN: probs = [domain_transforms(p) for p in probs]
     routes[route(probs, team)] += 1
     want = [mso.ba_solve(p, iters, False, force_reject=n_rej) for p in probs]
     ba = mi355slam.BundleAdjuster(ctx, probs, max_iters=iters); ba.set_team(team); ba.debug_force_reject(n_rej); ba.solve()
