@@ -18,6 +18,7 @@
 // round-to-nearest intrinsics (no FMA contraction) so results are bit-identical to the reference's
 // x86-64 SSE2 scalar build (CMakeLists.txt:4-5: -O2, no -march).
 #include "ms_internal.h"
+#include "fast_tiles.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -34,8 +35,7 @@ struct LevelGeom {
     int32_t det_base;                 // first slot of this level in det arrays (prefix of quotas)
     int32_t cand_cap;                 // capacity of this level's candidate list (entries)
     int32_t btiles_x, btile_base;     // k_blur tile table (248 x 72 tiles: 4 waves x kBlurRows rows)
-    int32_t ftiles_x, ftile_base;     // k_fast tile table (248 x 30 tiles: 8 waves x 4 position rows, 2 of them halo)
-    uint32_t btiles_inv, ftiles_inv;  // ceil(2^32 / tiles_x): row of a tile = mulhi(t, inv), exact for t < 2^16
+    uint32_t btiles_inv;              // ceil(2^32 / tiles_x): row of a tile = mulhi(t, inv), exact for t < 2^16
     uint64_t img_off, blur_off;       // byte offsets inside a frame slab
     uint64_t cand_off;                // entry offset inside a frame's candidate buffer
     float scale;                      // scaleFactors[l] (float32 chain)
@@ -45,7 +45,7 @@ struct PyrGeom {
     int32_t levels, lk_level, fast_threshold, max_kpts, max_tracks, capacity;
     int32_t det_stride;               // per-frame stride of the det arrays = max(max_kpts, sum of the level quotas): the quotas are rounded per level
                                       // (static_settings.cpp:52) and can add up to more than max_kpts (e.g. 15 levels / 160 keypoints -> 161)
-    int32_t width, height, btiles_total, ftiles_total;
+    int32_t width, height, btiles_total, ftiles_total;      // ftiles_total: entries of k_fast's tile table (fast_tiles.h)
     uint64_t slab_stride, cand_stride;     // per frame: bytes / entries
     int32_t umax[16];
     LevelGeom L[MS_MAX_LEVELS];
@@ -63,7 +63,7 @@ __device__ __forceinline__ int tile_level(const TileMap &tm, int levels, int t) 
 
 // What the tiled kernels (k_blur, k_fast) need about a level, also BY VALUE in the kernel arguments: one batch of scalar loads from the
 // kernel-argument segment once the block knows its level, instead of a chain of dependent loads from the geometry table behind branches.
-struct TileLevel { int32_t w, h, pitch, btiles_x, ftiles_x, cand_cap; uint32_t btiles_inv, ftiles_inv; uint64_t img_off, blur_off, cand_off; float scale; int32_t det_base; };
+struct TileLevel { int32_t w, h, pitch, btiles_x, cand_cap; uint32_t btiles_inv; uint64_t img_off, blur_off, cand_off; float scale; int32_t det_base; };
 struct TileLevels { TileLevel L[MS_MAX_LEVELS]; uint64_t slab_stride, cand_stride; int32_t levels, fast_threshold; };
 
 struct FrameSrc {          // where pyramid level 0 lives for this call
@@ -361,6 +361,11 @@ __global__ __launch_bounds__(256) void k_blur(FrameSrc src, TileLevels TL, TileM
 // Tile = 248 x 30 outputs; 256 x 32 score positions (1 px NMS halo, rounded to dwords), 4 position rows per wave, 8 waves:
 // 34 KB of LDS, so 4 workgroups (32 waves) share a CU -- the kernel is latency-bound (dependent loads,
 // five barriers, one returning atomic per tile), not ALU-bound, and needs the occupancy.
+// A wave runs the whole of phase A1 and a workgroup its skeleton whatever number of their lanes lie inside the image, so the narrow
+// column that is left of a level's width beside the full 248 px columns is cut into TALL tiles of the same area instead: the 64 lanes
+// of a wave as 2 sub-rows of 128 px (120 x 62 outputs) or 4 sub-rows of 64 px (56 x 126 outputs), and tile rows without a valid
+// position are not launched (fast_tiles.h: 401 instead of 452 workgroups for a 720p pyramid).  The layout is a template parameter
+// of the tile body, chosen by one wave-uniform branch on the tile-table entry; the LDS arrays are the same bytes in another pitch.
 //   phase A1  compass pre-test on EVERY position, in registers, two pixels per instruction: a lane owns
 //             one dword (4 pixels) of a row, the even/odd bytes are two 16-bit lanes; the sign bits of
 //             (centre+t - ring) and (ring - (centre-t)) are formed for the ring pixels N, S, E, W.
@@ -441,30 +446,27 @@ __device__ __forceinline__ s2_t pk_mad(uint32_t s, uint32_t r, uint32_t k) {
                      : "vcc", "memory");                                                                              \
     } while (0)
 
-__global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGeom *g, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count,
-                                              const uint32_t *__restrict__ tile_tab, TileLevels TL) {
-    __shared__ uint8_t s_sc[kFastPosRows][256];                                      // score tile (columns 2..253 are touched)
-    __shared__ __attribute__((aligned(16))) uint16_t s_pre[kFastPositions + 8];     // compass survivors (+ dump slot); each wave's corners overwrite its own consumed slots
-    __shared__ __attribute__((aligned(16))) uint8_t s_pix[(kFastPosRows + 6) * 256]; // the tile's pixels (image rows Y0-4 .. Y0+17) for the ring reads; NMS keys afterwards
-    __shared__ int s_np, s_m, s_base;
-    uint32_t *s_out = reinterpret_cast<uint32_t *>(s_pix);              // (rows + 6) * 64 keys >= 124 * rows / 2 possible NMS survivors
-    // The scalar unit is shared by the CU's four SIMDs and every wave of a tile repeats the tile's scalar work, so that work is kept
-    // short: the tile's level, row and column come packed from a host-built table (one scalar load instead of a 15-step search and
-    // a division), and the ten row addresses of an interior wave are one 64-bit base plus the pitch (2 scalar adds per row instead
-    // of two clamps, a 64-bit multiply and an add).
-    const uint32_t te = tile_tab[blockIdx.x];
-    const int l = (int)(te & 15u);
-    const TileLevel G = TL.L[l];                       // one batch of loads; everything below is arithmetic on it
-    const int X0 = (int)((te >> 4) & 0xFFFu) * kFastSeg, Y0 = (int)(te >> 16) * kFastRows;
+// One tile in the lane layout S (fast_tiles.h): a wave's 64 dword-lanes are S sub-rows of LW = 64 / S lanes, group g = S wave + lane / LW owns
+// position rows 4g .. 4g+3 of the tile and a lane the dword column cl = lane mod LW.  S = 1 is the wide tile with its scalar row addresses; for
+// S = 2 and 4 (the narrow remainder columns of a level) the row index is per lane and every wave takes the clamped border loads.
+template <int S>
+__device__ __forceinline__ void fast_tile(const FrameSrc &src, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count, const TileLevels &TL,
+                                          const TileLevel &G, const int l, const int X0, const int Y0,
+                                          uint8_t *s_sc, uint16_t *s_pre, uint8_t *s_pix, int *s_np, int *s_m, int *s_base) {
+    constexpr int LW = 64 / S, TW = 256 / S;                   // lanes and bytes of a tile row
+    constexpr int kOutRows = kFastPosRows * S - 2;             // 30, 62 or 126 output rows
+    uint32_t *s_out = reinterpret_cast<uint32_t *>(s_pix);              // (rows + 6) * LW keys >= (TW - 8) / 2 * (rows / 2) possible NMS survivors
     const int f = blockIdx.y, w = G.w, h = G.h, thr = TL.fast_threshold;
     const int pitch = l == 0 ? src.lvl0_pitch : G.pitch;
     const uint8_t *img = l == 0 ? src.lvl0 + (uint64_t)f * src.lvl0_frame_stride : src.slab + (uint64_t)f * TL.slab_stride + G.img_off;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform, in an SGPR: row addresses stay scalar
+    const int cl = S == 1 ? lane : (lane & (LW - 1));          // the lane's dword column
+    const int grp = S == 1 ? wave : S * wave + lane / LW;      // its group of 4 position rows (wave-uniform for S = 1)
     // The wave's 10 image rows are requested FIRST, so their latency runs under the LDS clear and the barrier.
-    const int x = X0 - 4 + 4 * lane;
+    const int x = X0 - 4 + 4 * cl;
     uint32_t rows[kFastRowsPerWave + 6];
-    const int yw = Y0 - 1 + wave * kFastRowsPerWave;
-    if (__ballot(!(x >= 0 && x + 3 < w)) == 0 && yw >= 3 && yw + kFastRowsPerWave + 2 < h) {     // whole wave inside the image: plain dword loads, one uniform branch
+    const int yw = Y0 - 1 + grp * kFastRowsPerWave;
+    if (S == 1 && __ballot(!(x >= 0 && x + 3 < w)) == 0 && yw >= 3 && yw + kFastRowsPerWave + 2 < h) {     // whole wave inside the image: plain dword loads, one uniform branch
         const uint8_t *rp = img + (int64_t)(yw - 3) * pitch;
 #pragma unroll
         for (int r = 0; r < kFastRowsPerWave + 6; ++r) { rows[r] = *reinterpret_cast<const uint32_t *>(rp + x); rp += pitch; }
@@ -478,39 +480,41 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
         for (int r = 0; r < kFastRowsPerWave + 6; ++r)
             rows[r] = (reinterpret_cast<const U32u *>(img + (uint64_t)min(max(yw - 3 + r, 0), h - 1) * pitch + xa)->v >> sh) & keep;
     }
-    if (tid == 0) { s_np = 0; s_m = 0; }
-    for (int i = tid; i < kFastPosRows * 256 / 4; i += kFastThreads) reinterpret_cast<uint32_t *>(&s_sc[0][0])[i] = 0;
-    // the rows go to LDS as well: wave w owns tile rows 4w .. 4w+3 (image rows Y0-4+4w ..), the last wave also the six below
+    if (tid == 0) { *s_np = 0; *s_m = 0; }
+    for (int i = tid; i < kFastPosRows * 256 / 4; i += kFastThreads) reinterpret_cast<uint32_t *>(s_sc)[i] = 0;
+    // the rows go to LDS as well: group g owns tile rows 4g .. 4g+3 (image rows Y0-4+4g ..), the last group also the six below
 #pragma unroll
     for (int r = 0; r < kFastRowsPerWave + 6; ++r)
-        if (r < kFastRowsPerWave || wave == kFastWaves - 1) reinterpret_cast<uint32_t *>(s_pix)[(wave * kFastRowsPerWave + r) * 64 + lane] = rows[r];
+        if (r < kFastRowsPerWave || grp == kFastWaves * S - 1) reinterpret_cast<uint32_t *>(s_pix)[(grp * kFastRowsPerWave + r) * LW + cl] = rows[r];
     __syncthreads();
-    // ---- phase A1: position rows pr = wave*4 .. wave*4+3  <->  image rows Y0-1+pr; columns X0-4+4*lane .. +3
+    // ---- phase A1: position rows pr = 4 grp .. 4 grp + 3  <->  image rows Y0-1+pr; columns X0-4+4*cl .. +3
     {
         const uint32_t T2 = (uint32_t)thr * 0x00010001u;
-        // which of the lane's 4 pixels are valid positions (the same for every row): bit 8i + 7 for pixel i.  Column c = 4 lane + i in
-        // [3, 252] and image column x + i in [3, w - 4] (x = X0 - 4 + 4 lane) is one run lo <= i <= hi whose ends are a scalar minus 4 lane
-        const int lo = min(max(max(3, 7 - X0) - 4 * lane, 0), 4), hi = min(max(min(252, w - X0) - 4 * lane, -1), 3);
+        // which of the lane's 4 pixels are valid positions (the same for every row): bit 8i + 7 for pixel i.  Column c = 4 cl + i in
+        // [3, TW - 4] and image column x + i in [3, w - 4] (x = X0 - 4 + 4 cl) is one run lo <= i <= hi whose ends are a scalar minus 4 cl
+        const int lo = min(max(max(3, 7 - X0) - 4 * cl, 0), 4), hi = min(max(min(TW - 4, w - X0) - 4 * cl, -1), 3);
         const uint32_t vmask = (uint32_t)(0x80808080ull << (8 * lo)) & (uint32_t)(0x80808080ull >> (8 * (3 - hi)));
         // every loaded row split ONCE into its even / odd bytes as 16-bit lanes: a row serves as S, centre and N of three position rows
         uint32_t re[kFastRowsPerWave + 6], ro[kFastRowsPerWave + 6];
 #pragma unroll
         for (int j = 0; j < kFastRowsPerWave + 6; ++j) { re[j] = rows[j] & 0x00FF00FFu; ro[j] = __builtin_amdgcn_perm(0u, rows[j], 0x0C030C01u); }
         uint32_t fr[kFastRowsPerWave];                   // survivors of row r: the top bit of byte i <-> pixel i
-        uint32_t cnt4 = 0;                               // their number, row r in byte r (a row has at most 250 positions, so sums over lanes stay in the byte)
+        uint32_t cnt4 = 0;                               // their number, row r in byte r (the rows r of a wave have at most 250, 2 x 122 or 4 x 58 positions, so sums over lanes stay in the byte)
 #pragma unroll
         for (int r = 0; r < kFastRowsPerWave; ++r) {
-            const int y = Y0 - 1 + wave * kFastRowsPerWave + r;
+            const int y = yw + r;
             fr[r] = 0;
-            if (y < 3 || y >= h - 3) continue;                           // wave-uniform
+            if (S == 1 && (y < 3 || y >= h - 3)) continue;               // wave-uniform
             const uint32_t ce = re[r + 3], co = ro[r + 3];
-            // the neighbour lanes' halves by DPP wave shifts (one VALU op each); lanes 0 / 63 get a don't-care: their edge pixels are masked by vmask
+            // the neighbour lanes' halves by DPP wave shifts (one VALU op each); the first / last lane of a sub-row gets a don't-care (lanes 0 / 63, or
+            // a lane of the neighbouring sub-row): their edge pixels are masked by vmask, and columns 3 and TW - 4 take both E and W from their own lane or an inner one
             const uint32_t cep = wave_from_prev_dc(ce), cen = wave_from_next_dc(ce), cop = wave_from_prev_dc(co), con = wave_from_next_dc(co);
             // even pixels x, x+2: (+3,0) = x+3, x+5 = odd byte 3 of this lane, odd byte 1 of the next; (-3,0) = x-3, x-1 = the previous lane's odd bytes
             const uint32_t pe = compass_pass(re[r + 6], re[r], __builtin_amdgcn_alignbit(con, co, 16), cop, ce, T2);
             // odd pixels x+1, x+3: (+3,0) = x+4, x+6 = the next lane's even bytes; (-3,0) = x-2, x = even byte 2 of the previous lane, even byte 0 of this one
             const uint32_t po = compass_pass(ro[r + 6], ro[r], cen, __builtin_amdgcn_alignbit(ce, cep, 16), co, T2);
             fr[r] = __builtin_amdgcn_perm(po, pe, 0x07030501u) & vmask;  // the sign bytes of the four pixels side by side (pixel i in byte i)
+            if (S != 1) fr[r] = (y < 3 || y >= h - 3) ? 0u : fr[r];      // the row is per lane here: masked, not branched
             cnt4 += (uint32_t)__popc(fr[r]) << (8 * r);
         }
         // ONE list append per wave, in the order row by row, lane by lane (neighbouring list slots = neighbouring pixels of a row, which
@@ -519,9 +523,9 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
         const uint32_t incl = (uint32_t)wave_scan_add((int)cnt4);
         const uint32_t tot4 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63), excl = incl - cnt4;
         int base = 0;
-        if (lane == 0) base = atomicAdd(&s_np, (int)((tot4 & 255u) + ((tot4 >> 8) & 255u) + ((tot4 >> 16) & 255u) + (tot4 >> 24)));
+        if (lane == 0) base = atomicAdd(s_np, (int)((tot4 & 255u) + ((tot4 >> 8) & 255u) + ((tot4 >> 16) & 255u) + (tot4 >> 24)));
         base = __builtin_amdgcn_readfirstlane(base);
-        const uint32_t ebase = ((uint32_t)((wave * kFastRowsPerWave) << 8) | (uint32_t)(4 * lane)) * 0x00010001u;   // in both 16-bit halves
+        const uint32_t ebase = ((uint32_t)((grp * kFastRowsPerWave) << 8) | (uint32_t)(4 * cl)) * 0x00010001u;   // in both 16-bit halves (pr < 128: 15 bits)
         const uint32_t pre_addr = (uint32_t)(uintptr_t)s_pre;
 #pragma unroll
         for (int r = 0; r < kFastRowsPerWave; ++r) {
@@ -542,21 +546,21 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
     //      The ring comes from the tile's pixels in LDS (17 byte reads with immediate offsets from one base): as 7 wide global loads per
     //      survivor the texture addresser had ~30 cache lines to look up per instruction.  A wave appends its corners IN PLACE, into the
     //      slots of the survivor list it has already consumed (slots 64w + kFastThreads i + j belong to wave w), so no second list is needed.
-    const int np = s_np;
+    const int np = *s_np;
     int ncw = 0;                                                         // corners of this wave so far (wave-uniform)
     for (int i = tid; i < np; i += kFastThreads) {
         const int e = s_pre[i], pr = e >> 8, c = e & 255;
-        const uint8_t *q = s_pix + pr * 256 + (c - 3);                   // top-left of the 7x7 box: tile row pr + 3 is the centre's
+        const uint8_t *q = s_pix + pr * TW + (c - 3);                    // top-left of the 7x7 box: tile row pr + 3 is the centre's
         uint32_t R[9];
         {
             const int rdx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
             const int rdy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
-            R[8] = q[3 * 256 + 3];
+            R[8] = q[3 * TW + 3];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {                                // ring pixels k and k+8 as the two 16-bit lanes (the second byte read lands in the high half)
                 us2_t v;
-                v.x = q[(3 + rdy[k]) * 256 + 3 + rdx[k]];
-                v.y = q[(3 + rdy[k + 8]) * 256 + 3 + rdx[k + 8]];
+                v.x = q[(3 + rdy[k]) * TW + 3 + rdx[k]];
+                v.y = q[(3 + rdy[k + 8]) * TW + 3 + rdx[k + 8]];
                 R[k] = __builtin_bit_cast(uint32_t, v);
             }
         }
@@ -589,33 +593,53 @@ __global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, const PyrGe
         const unsigned long long cm = __ballot(corner);
         if (corner) {
             const int slot = ncw + mbcnt64(cm);
-            s_sc[pr][c] = (uint8_t)best;
+            s_sc[pr * TW + c] = (uint8_t)best;
             s_pre[64 * wave + kFastThreads * (slot >> 6) + (slot & 63)] = (uint16_t)e;
         }
         ncw += (int)__popcll(cm);
     }
     ncw = __builtin_amdgcn_readfirstlane(ncw);          // lanes that left the loop early missed the last updates; lane 0 stays to the end
     __syncthreads();
-    // ---- phase C: 3x3 strict-maximum NMS, dense over the corner list (only outputs: px X0..X0+247 = columns 4..251,
-    //      rows Y0..Y0+13 = position rows 1..14; the halo corners only serve as neighbours)
+    // ---- phase C: 3x3 strict-maximum NMS, dense over the corner list (only outputs: px X0..X0+TW-9 = columns 4..TW-5,
+    //      rows Y0..Y0+kOutRows-1 = position rows 1..kOutRows; the halo corners only serve as neighbours)
     for (int i = lane; i < ncw; i += 64) {                               // every wave walks its own corner sublist
         const int e = s_pre[64 * wave + kFastThreads * (i >> 6) + (i & 63)], pr = e >> 8, c = e & 255;
         const int px = X0 - 4 + c, y = Y0 - 1 + pr;
-        if (pr < 1 || pr > kFastRows || c < 4 || c > 251 || px >= w || y >= h) continue;
-        const int sc = s_sc[pr][c];
-        const bool keep = sc > s_sc[pr - 1][c - 1] && sc > s_sc[pr - 1][c] && sc > s_sc[pr - 1][c + 1] && sc > s_sc[pr][c - 1] &&
-                          sc > s_sc[pr][c + 1] && sc > s_sc[pr + 1][c - 1] && sc > s_sc[pr + 1][c] && sc > s_sc[pr + 1][c + 1];
-        if (keep) s_out[atomicAdd(&s_m, 1)] = ((uint32_t)(255 - sc) << 24) | (uint32_t)(y * w + px);
+        if (pr < 1 || pr > kOutRows || c < 4 || c > TW - 5 || px >= w || y >= h) continue;
+        const uint8_t *sp = s_sc + pr * TW + c;
+        const int sc = sp[0];
+        const bool keep = sc > sp[-TW - 1] && sc > sp[-TW] && sc > sp[-TW + 1] && sc > sp[-1] &&
+                          sc > sp[1] && sc > sp[TW - 1] && sc > sp[TW] && sc > sp[TW + 1];
+        if (keep) s_out[atomicAdd(s_m, 1)] = ((uint32_t)(255 - sc) << 24) | (uint32_t)(y * w + px);
     }
     __syncthreads();
-    const int m = s_m;
+    const int m = *s_m;
     if (m == 0) return;
-    if (tid == 0) s_base = atomicAdd(&cand_count[f * TL.levels + l], m);
+    if (tid == 0) *s_base = atomicAdd(&cand_count[f * TL.levels + l], m);
     __syncthreads();
     for (int i = tid; i < m; i += kFastThreads) {
-        const int pos = s_base + i;
+        const int pos = *s_base + i;
         if (pos < G.cand_cap) cand[(uint64_t)f * TL.cand_stride + G.cand_off + pos] = s_out[i];
     }
+}
+
+__global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count,
+                                              const uint2 *__restrict__ tile_tab, TileLevels TL) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_sc[kFastPosRows * 256];        // score tile, [32 S][256 / S] (the outermost two columns are never touched)
+    __shared__ __attribute__((aligned(16))) uint16_t s_pre[kFastPositions + 8];     // compass survivors (+ dump slot); each wave's corners overwrite its own consumed slots
+    __shared__ __attribute__((aligned(16))) uint8_t s_pix[(kFastPosRows + 6) * 256]; // the tile's pixels, [32 S + 6][256 / S] (image rows Y0-4 ..) for the ring reads; NMS keys afterwards
+    __shared__ int s_np, s_m, s_base;
+    // The scalar unit is shared by the CU's four SIMDs and every wave of a tile repeats the tile's scalar work, so that work is kept
+    // short: the tile's level, layout and first output column / row come from a host-built table (one scalar load instead of a 15-step
+    // search and a division), and the ten row addresses of an interior wave are one 64-bit base plus the pitch (2 scalar adds per row
+    // instead of two clamps, a 64-bit multiply and an add).
+    const uint2 te = tile_tab[blockIdx.x];             // level | S << 4,  X0 | Y0 << 16
+    const int l = (int)(te.x & 15u), X0 = (int)(te.y & 0xFFFFu), Y0 = (int)(te.y >> 16);
+    const TileLevel G = TL.L[l];                       // one batch of loads; everything below is arithmetic on it
+    const uint32_t S = te.x >> 4;
+    if (S == 1u) fast_tile<1>(src, cand, cand_count, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base);         // one wave-uniform branch
+    else if (S == 2u) fast_tile<2>(src, cand, cand_count, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base);
+    else fast_tile<4>(src, cand, cand_count, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1144,8 +1168,8 @@ struct ms_orb {
     ms_orb_config cfg{};
     PyrGeom geom{};
     PyrGeom *d_geom = nullptr;
-    TileMap blur_tiles{}, fast_tiles{};
-    uint32_t *d_ftile_tab = nullptr;   // k_fast: level | column << 4 | row << 16 of every tile
+    TileMap blur_tiles{};
+    uint2 *d_ftile_tab = nullptr;      // k_fast: (level | S << 4, X0 | Y0 << 16) of every tile
     TileLevels tile_levels{};          // per-level geometry of the tiled kernels, passed by value
     uint8_t *d_slab = nullptr;
     uint32_t *d_cand = nullptr;
@@ -1239,15 +1263,15 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
     msgeo::scale_factors(cfg->levels, cfg->scale_factor, sf);
     msgeo::umax(G.umax);
     uint64_t off = 0, coff = 0;
-    int det_base = 0, bt = 0, ft = 0;
+    int det_base = 0, bt = 0;
     for (int l = 0; l < cfg->levels; ++l) {
         if (w[l] < 2 * kPatchRadius + 2 || h[l] < 2 * kPatchRadius + 2 || quota[l] > kMaxQuota) {
             delete o;
             return ms_fail(ctx, MS_ERR_INVALID, "ms_orb_create: level %d is %dx%d (min 40x40) / quota %d (max %d)", l, w[l], h[l], quota[l], kMaxQuota);
         }
-        if ((int64_t)ms_div_up(w[l], kFastSeg) * ms_div_up(h[l], kFastRows) >= 65536) {      // the kernels' mulhi tile division is exact below 2^16 tiles per level
+        if ((int64_t)ms_div_up(w[l], kBlurSeg) * ms_div_up(h[l], 4 * kBlurRows) >= 65536) {      // k_blur's mulhi tile division is exact below 2^16 tiles per level
             delete o;
-            return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: level %d (%dx%d) needs more than 65535 detector tiles", l, w[l], h[l]);
+            return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: level %d (%dx%d) needs more than 65535 blur tiles", l, w[l], h[l]);
         }
         LevelGeom &L = G.L[l];
         L.w = w[l]; L.h = h[l]; L.pitch = (int)ms_align_up(w[l], 64); L.quota = quota[l]; L.scale = sf[l];
@@ -1261,20 +1285,30 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
         L.cand_cap = (int32_t)ms_align_up((size_t)(((w[l] + 1) / 2) * ((h[l] + 1) / 2) + 256), 4);   // strict 3x3 maxima: <= one per 2x2 block; a multiple of 4 so that every level's list starts 16-byte aligned (k_select reads it as uint4)
         L.cand_off = coff; coff += L.cand_cap;
         L.btiles_x = ms_div_up(w[l], kBlurSeg); L.btile_base = bt; bt += L.btiles_x * ms_div_up(h[l], 4 * kBlurRows);
-        L.ftiles_x = ms_div_up(w[l], kFastSeg); L.ftile_base = ft; ft += L.ftiles_x * ms_div_up(h[l], kFastRows);
-        L.btiles_inv = (uint32_t)(((1ull << 32) + L.btiles_x - 1) / L.btiles_x); L.ftiles_inv = (uint32_t)(((1ull << 32) + L.ftiles_x - 1) / L.ftiles_x);
+        L.btiles_inv = (uint32_t)(((1ull << 32) + L.btiles_x - 1) / L.btiles_x);
     }
-    G.btiles_total = bt; G.ftiles_total = ft;
+    G.btiles_total = bt;
+    std::vector<uint2> ftab;                             // k_fast's tile table (the cover of fast_tiles.h): level | S << 4,  X0 | Y0 << 16
+    {
+        std::vector<fast_tiles::Tile> cover;
+        for (int l = 0; l < cfg->levels; ++l) {
+            cover.clear();
+            fast_tiles::cover(w[l], h[l], cover);
+            for (const fast_tiles::Tile &t : cover) ftab.push_back(make_uint2((uint32_t)l | ((uint32_t)t.S << 4), (uint32_t)t.X0 | ((uint32_t)t.Y0 << 16)));
+            if (!cover.empty() && (cover.back().X0 > 0xFFFF || cover.back().Y0 > 0xFFFF)) {      // 16 bits each in the entry; the last tile of a level has the largest of both
+                delete o;
+                return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: level %d (%dx%d) is beyond the detector's tile table (65535 px)", l, w[l], h[l]);
+            }
+        }
+    }
+    G.ftiles_total = (int)ftab.size();
     G.det_stride = std::max(cfg->max_kpts, det_base);       // the reference keeps per-level vectors, so a frame can hold sum(quota) > maxKeypoints points
     G.capacity = G.det_stride + cfg->max_tracks;
     for (int l = 0; l < cfg->levels; ++l) {
         const LevelGeom &L = G.L[l];
-        o->tile_levels.L[l] = TileLevel{L.w, L.h, L.pitch, L.btiles_x, L.ftiles_x, L.cand_cap, L.btiles_inv, L.ftiles_inv, L.img_off, L.blur_off, L.cand_off, L.scale, L.det_base};
+        o->tile_levels.L[l] = TileLevel{L.w, L.h, L.pitch, L.btiles_x, L.cand_cap, L.btiles_inv, L.img_off, L.blur_off, L.cand_off, L.scale, L.det_base};
     }
-    for (int l = 0; l <= MS_MAX_LEVELS; ++l) {
-        o->blur_tiles.base[l] = l < cfg->levels ? G.L[l].btile_base : bt;
-        o->fast_tiles.base[l] = l < cfg->levels ? G.L[l].ftile_base : ft;
-    }
+    for (int l = 0; l <= MS_MAX_LEVELS; ++l) o->blur_tiles.base[l] = l < cfg->levels ? G.L[l].btile_base : bt;
     G.slab_stride = ms_align_up(off, 256); G.cand_stride = coff;
     o->tile_levels.slab_stride = G.slab_stride; o->tile_levels.cand_stride = G.cand_stride; o->tile_levels.levels = G.levels; o->tile_levels.fast_threshold = G.fast_threshold;
     o->lvl0_off = G.L[0].img_off; o->lvl0_pitch = G.L[0].pitch;
@@ -1322,16 +1356,8 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
         };
         up(&o->d_xtab[l], xt); up(&o->d_ytab[l], yt);
     }
-    if (rc == MS_OK) {                                   // k_fast's tile table: level | column << 4 | row << 16
-        std::vector<uint32_t> tt;
-        for (int l = 0; l < cfg->levels; ++l) {
-            const int tx = G.L[l].ftiles_x, ty = ms_div_up(G.L[l].h, kFastRows);
-            if (tx > 0xFFF || ty > 0xFFFF) { rc = MS_ERR_INVALID; break; }
-            for (int r = 0; r < ty; ++r) for (int cx = 0; cx < tx; ++cx) tt.push_back((uint32_t)l | ((uint32_t)cx << 4) | ((uint32_t)r << 16));
-        }
-        if (rc == MS_OK && ((int)tt.size() != G.ftiles_total || hipMalloc(reinterpret_cast<void **>(&o->d_ftile_tab), tt.size() * 4 + 16) != hipSuccess ||
-                            hipMemcpy(o->d_ftile_tab, tt.data(), tt.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) rc = MS_ERR_HIP;
-    }
+    if (rc == MS_OK && (hipMalloc(reinterpret_cast<void **>(&o->d_ftile_tab), ftab.size() * sizeof(uint2) + 16) != hipSuccess ||
+                        hipMemcpy(o->d_ftile_tab, ftab.data(), ftab.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)) rc = MS_ERR_HIP;
     if (rc == MS_OK) {                                   // k_describe's lane tables
         static const int8_t pattern[1024] = {
 #include "orb_pattern.inc"
@@ -1498,7 +1524,7 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     MS_STAGE_MARK();
     MsRange detect_range("detect");
     counters_dirty = true;
-    hipLaunchKernelGGL(k_fast, dim3(G.ftiles_total, nf), dim3(kFastThreads), 0, st, src, o->d_geom, cand, cand_count, o->d_ftile_tab, o->tile_levels);
+    hipLaunchKernelGGL(k_fast, dim3(G.ftiles_total, nf), dim3(kFastThreads), 0, st, src, cand, cand_count, o->d_ftile_tab, o->tile_levels);
     MS_KERNEL_CHECK(c, "k_fast");
     MS_STAGE_MARK();
     const bool few = nf * G.levels <= 64;                           // a frame or a handful: one block per level is the whole launch -- give it 1024 threads
