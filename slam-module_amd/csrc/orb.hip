@@ -105,7 +105,7 @@ typedef short s2_t __attribute__((ext_vector_type(2)));
 // Everything k_resize needs about its two levels, by value in the kernel arguments: the launch is per level, and reading the
 // geometry table instead put nine dependent scalar round trips in front of every wave's first pixel load.
 struct ResizeArgs {
-    const uint8_t *src; uint64_t src_frame_stride; int32_t src_pitch, sw;      // level l-1
+    const uint8_t *src; uint64_t src_frame_stride; int32_t src_pitch, sw, sh;  // level l-1
     uint8_t *dst; uint64_t dst_frame_stride; int32_t dst_pitch, dw, dh;        // level l
 };
 
@@ -131,6 +131,62 @@ __device__ __forceinline__ Window3 window_load(const uint8_t *row, int base, int
             *reinterpret_cast<const uint32_t *>(row + min(base + 8, last_dword))};
 }
 
+// Shared-row path of k_resize.  At a level ratio near 1.2 the tap rows of a group's five destination rows are the NROWS = 6 or 7 consecutive
+// source rows s0 .. s0 + NROWS - 1 (clamped at sh - 1 like the table's entries): row r reads rows s0 + d_r and s0 + d_r + 1 with d_r = r or r + 1.
+// Each of them is loaded once and run through the horizontal pass once (F[i][c] = the r >> 4 term of column c), where the general path loads and
+// filters ten; the destination rows pick their two F rows by the scalar d_r.  Loads, edge-wave handling, taps and the vertical combine are the
+// general path's, so the pixels are the same bit for bit.
+template <int NROWS>
+__device__ __forceinline__ void resize_shared_rows(const uint8_t *S, int spitch, int s0, int sh, int sx0, int base, int last, bool edge, uint4 taps, uint4 sels,
+                                                   const short4 (&yt)[kResizeRows], uint8_t *dst, int dy0, int dx0, int dh, int dpitch) {
+    const uint32_t A[4] = {taps.x, taps.y, taps.z, taps.w}, sel[4] = {sels.x, sels.y, sels.z, sels.w};      // the caller's per-column operands, by value
+    Window3 W[NROWS];
+    if (!edge || last >= 8) {
+        const int from = edge ? min(base, last - 8) : base, shift = base - from;       // as in the general path
+#pragma unroll
+        for (int i = 0; i < NROWS; ++i) {
+            const uint8_t *p = S + (uint64_t)min(s0 + i, sh - 1) * spitch + from;
+            asm volatile("" : "+v"(p));
+            const u3_t a = *(const __attribute__((address_space(1))) u3a_t *)(p);
+            W[i] = {a.x, a.y, a.z};
+        }
+        if (edge) {
+#pragma unroll
+            for (int i = 0; i < NROWS; ++i) W[i] = {shift == 0 ? W[i].d0 : shift == 4 ? W[i].d1 : W[i].d2, shift == 0 ? W[i].d1 : W[i].d2, W[i].d2};
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NROWS; ++i) W[i] = window_load(S + (uint64_t)min(s0 + i, sh - 1) * spitch, base, last);
+    }
+    uint32_t F[NROWS][4];
+#pragma unroll
+    for (int i = 0; i < NROWS; ++i) {
+        const uint32_t lo = __builtin_amdgcn_alignbyte(W[i].d1, W[i].d0, (uint32_t)sx0), hi = __builtin_amdgcn_alignbyte(W[i].d2, W[i].d1, (uint32_t)sx0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            F[i][c] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(hi, lo, sel[c])), __builtin_bit_cast(us2_t, A[c]), 0u, false) >> 4;
+            asm volatile("" : "+v"(F[i][c]));          // the shift happens here, once: left alone the compiler repeats it in every row body that reads the value
+        }
+    }
+    // the two choices of a row are two bodies behind a scalar branch: the empty asm statements differ, which keeps the compiler from merging the
+    // bodies into one with eight per-lane selects in front (as many vector instructions as the shared rows save)
+    auto emit = [&](int r, bool upper, const uint32_t (&f0)[4], const uint32_t (&f1)[4]) {
+        const uint32_t b0 = (uint32_t)yt[r].z, b1 = (uint32_t)yt[r].w;
+        uint32_t v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = ((__umul24(b0, f0[c]) >> 16) + (__umul24(b1, f1[c]) >> 16) + 2) >> 2;
+        uint32_t packed = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        if (upper) asm volatile("; rows d + 1, d + 2" : "+v"(packed)); else asm volatile("; rows d, d + 1" : "+v"(packed));
+        *reinterpret_cast<uint32_t *>(dst + (uint64_t)(dy0 + r) * dpitch + dx0) = packed;
+    };
+#pragma unroll
+    for (int r = 0; r < kResizeRows; ++r) {
+        if (dy0 + r >= dh) continue;                                 // rows of the padded last group (wave-uniform, like every branch here)
+        if (r + 2 >= NROWS || yt[r].x - s0 == r) emit(r, false, F[r], F[r + 1]);      // NROWS = 6: the caller has seen d_4 = 4
+        else emit(r, true, F[r + 1], F[min(r + 2, NROWS - 1)]);
+    }
+}
+
 template <bool WIDE>   // WIDE: tap window of 4 pixels may exceed 8 bytes (scale factor > 2) -> per-tap byte loads
 __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
     const struct { int w, h, pitch; } D = {R.dw, R.dh, R.dst_pitch};
@@ -150,20 +206,37 @@ __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
 #pragma unroll
     for (int r = 0; r < kResizeRows; ++r) yt[r] = reinterpret_cast<const short4 *>(T.ytab)[dy0 + r];
     if (!WIDE) {
-        const int sx0 = xt[0].x, last = (sw - 1) & ~3, base = sx0 & ~3;
+        // the table entries straight from the loaded dwords, (sx | a0 << 16) and (a1 | 0 << 16) per column: read through xt[] they leave the array
+        // in memory (the compiler joins the two 16-bit reads of a0, a1 into one dword read at offset 2 of an entry, and with the two row paths
+        // below it then places the array in LDS)
+        const uint32_t xlo[4] = {xa.x, xa.z, xb.x, xb.z}, xhi[4] = {xa.y, xa.w, xb.y, xb.w};
+        const int sx0 = (int16_t)xlo[0], last = (sw - 1) & ~3, base = sx0 & ~3;
         // per column: the two taps as one v_dot2 operand (a0, a1), and a v_perm selector that lifts source bytes k, k+1 of the
         // row's 8-byte window into 16-bit lanes (k = sx - sx0 <= 6)
         uint32_t A[4], sel[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            A[i] = (uint32_t)(uint16_t)xt[i].y | ((uint32_t)(uint16_t)xt[i].z << 16);
-            sel[i] = 0x0C010C00u + (uint32_t)(xt[i].x - sx0) * 0x00010001u;
+            A[i] = __builtin_amdgcn_alignbit(xhi[i], xlo[i], 16);
+            sel[i] = 0x0C010C00u + (uint32_t)((int16_t)xlo[i] - sx0) * 0x00010001u;
         }
-        Window3 W0[kResizeRows], W1[kResizeRows];
         // The kernel is bound by the NUMBER of vector-memory instructions (measured: dropping the arithmetic changes nothing, halving the
         // loads gives -36 %), so the three dwords of a window are ONE 12-byte load wherever no lane of the wave touches the row's last
         // dwords (a 12-byte load there would run past the row, and past the caller's buffer on the last row of level 0).
         const bool edge = __ballot(base + 8 > last) != 0;        // wave-uniform
+        // Scalar test on the group's five table entries: do its rows share six or seven consecutive source rows?  (Rows past the level's
+        // last one are padding and do not count.)  Other ratios, and any group that fails the test, take the general path below.
+        const int s0 = yt[0].x, sh = R.sh;
+        int shared = 1;
+#pragma unroll
+        for (int r = 0; r < kResizeRows; ++r)
+            shared &= (int)(dy0 + r >= D.h) | ((int)((unsigned)(yt[r].x - s0 - r) <= 1u) & (int)(yt[r].y == min(yt[r].x + 1, sh - 1)));
+        if (shared) {
+            const uint4 taps = make_uint4(A[0], A[1], A[2], A[3]), sels = make_uint4(sel[0], sel[1], sel[2], sel[3]);
+            if (dy0 + 4 < D.h && yt[4].x - s0 == 5) resize_shared_rows<7>(S, spitch, s0, sh, sx0, base, last, edge, taps, sels, yt, dst, dy0, dx0, D.h, D.pitch);
+            else resize_shared_rows<6>(S, spitch, s0, sh, sx0, base, last, edge, taps, sels, yt, dst, dy0, dx0, D.h, D.pitch);
+            return;
+        }
+        Window3 W0[kResizeRows], W1[kResizeRows];
         if (!edge || last >= 8) {
             // edge wave: the 12 bytes are fetched from min(base, last - 8) and moved down by whole dwords afterwards, which reproduces the
             // clamped dwords exactly (d_k = row[min(base + 4k, last)])
@@ -1510,7 +1583,7 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
         ResizeArgs RA{};
         if (l == 1) { RA.src = src.lvl0; RA.src_frame_stride = src.lvl0_frame_stride; RA.src_pitch = src.lvl0_pitch; }
         else { RA.src = src.slab + G.L[l - 1].img_off; RA.src_frame_stride = G.slab_stride; RA.src_pitch = G.L[l - 1].pitch; }
-        RA.sw = G.L[l - 1].w;
+        RA.sw = G.L[l - 1].w; RA.sh = G.L[l - 1].h;
         RA.dst = src.slab + G.L[l].img_off; RA.dst_frame_stride = G.slab_stride; RA.dst_pitch = G.L[l].pitch; RA.dw = G.L[l].w; RA.dh = G.L[l].h;
         if (o->wide[l]) hipLaunchKernelGGL(k_resize<true>, grid, dim3(256), 0, st, RA, RT);
         else hipLaunchKernelGGL(k_resize<false>, grid, dim3(256), 0, st, RA, RT);
