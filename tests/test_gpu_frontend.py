@@ -222,8 +222,9 @@ def test_min_distance_suppression(oracle, ctx):
 
 
 def test_tile_edge_geometries(oracle, ctx):
-    """Widths / heights around the 248 x 30 detector tiles, the 248 x 72 blur tiles and the 5-row resize groups, on noise
-    (corners everywhere, including the first and last columns and rows, where the border waves clamp, shift or reflect their loads)."""
+    """Widths / heights around the 248 x 30 detector tiles and the 5-row resize groups, on noise (corners everywhere, including the first
+    and last columns and rows, where the border waves clamp, shift or reflect their loads).  Nothing here launches k_blur: its 248 x 72
+    tiles have test_gpu_blur_levels.py."""
     rng = np.random.default_rng(31)
     for (w, h) in [(248, 56), (249, 57), (252, 49), (496, 70), (497, 71), (500, 50), (744, 53), (745, 85), (1000, 59),
                    (247, 60), (251, 61), (253, 89), (254, 90), (255, 91), (495, 72), (499, 73), (743, 144), (992, 145)]:
