@@ -8,11 +8,12 @@
 //   ms_match_triangulation  matchForTriangulationDBoW  keyframe_matcher.cpp:160-293
 //
 // The brute-force search is compute-bound, not HBM-bound (32 distance evaluations per input byte at 2000x2000).
-// Unmasked it runs on the matrix cores (k_hamming_mfma: the distance matrix is an i8 product of +-1 bytes).  With bucket /
+// Unmasked it runs on the matrix cores (k_hamming_mfma: the distance matrix is an FP4 product of +-1 and 0/1).  With bucket /
 // validity masks it stays on the VALU (k_hamming_best2<true>): each lane keeps one 256-bit query in 8 VGPRs, targets are
 // staged through LDS in tiles of 256 and read back as wave-uniform broadcasts (2 x ds_read_b128 per target), distance is
 // 8 x (v_xor, v_bcnt_u32_b32-accumulate), best/second are tracked branch-free on packed (distance<<20 | index) keys.
 #include "ms_internal.h"
+#include "hamming_fp4.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -98,32 +99,38 @@ __global__ __launch_bounds__(256) void k_hamming_best2(HamArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The unmasked all-pairs search as an integer matrix product on the matrix cores.  Queries become +-1 bytes (bit 0 -> +1,
-// bit 1 -> -1), targets stay 0 / 1 bytes; then  hamming(q, t) = popcount(q) + sum_k t_k * (1 - 2 q_k)  exactly, i.e. the i8 dot
-// product plus a per-query constant that does not change the order of the targets.  A 32x32 tile of distances is eight
-// v_mfma_i32_32x32x32_i8 (K = 256 bits).
-//   * target bytes cost two full-rate VALU ops per dword: (word >> s) & 0x01010101 puts bits s, s+8, s+16, s+24 of a descriptor
-//     word into the four bytes -- which bit sits in which k slot of a fragment is irrelevant as long as queries and targets use
-//     the same rule, so the k order is chosen to make the expansion free of multiplies and byte shuffles;
-//   * a wave owns 64 queries (two 32-wide column tiles) whose operand fragments live in 64 registers for the whole kernel;
-//   * the workgroup (4 waves = 256 queries) expands 128 targets per stage into LDS, already in operand order
+// The unmasked all-pairs search as a matrix product on the matrix cores.  Queries become +-1 (bit 0 -> +1, bit 1 -> -1), targets stay
+// 0 / 1; then  hamming(q, t) = popcount(q) + sum_k t_k * (1 - 2 q_k)  exactly, i.e. the dot product plus a per-query constant that does
+// not change the order of the targets.  The operands are FP4 (E2M1) nibbles (hamming_fp4.h): +-1, 0 and 1 are exact in it, sums of at most
+// 256 of them are exact in the f32 accumulator, and a 32x32 tile of distances is four v_mfma_scale_f32_32x32x64_f8f6f4 (K = 256 bits) --
+// half the matrix instructions, LDS bytes and expansion work of the i8 form at the same cycles per instruction.
+//   * target nibbles cost two full-rate VALU ops per dword: (word >> j) & 0x11111111 puts bits j, j+4, ..., j+28 of a descriptor
+//     word into the eight nibbles -- which bit sits in which k slot of a fragment is irrelevant as long as queries and targets use
+//     the same rule, so the k order is chosen to make the expansion free of multiplies and shuffles;
+//   * a wave owns 64 queries (two 32-wide column tiles) whose operand fragments live in 32 registers for the whole kernel;
+//   * the workgroup (4 waves = 256 queries) expands kHmStage targets per stage into LDS, already in operand order
 //     ([row tile][k step][lane][16 B]), so an A fragment is one conflict-free ds_read_b128;
+//   * the B scale 2^4 makes the accumulator 16 * dot, and the chain starts from 2^23 + 4096 + register index: for a float in [2^23, 2^24) the
+//     mantissa field is the integer offset, so the low 16 bits of the register are (dot + 256) * 16 + register index, an integer key, with no conversion;
 //   * accumulator layout: column (= query) on the lane, 16 target rows in the registers, so best / second are tracked per lane,
 //     both column tiles at once on packed 16-bit keys (2.5 VALU ops per pair instead of 21).  The two lane halves (rows 4h..)
 //     of a column are merged once at the end, where popcount(q) turns the dot product back into the distance.
 typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef int v16i_t __attribute__((ext_vector_type(16)));
+typedef int v8i_t __attribute__((ext_vector_type(8)));
+typedef float v16f_t __attribute__((ext_vector_type(16)));
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
-constexpr int kHmStage = 128;      // targets per LDS stage (four 32-row tiles, 32 KB of +-1 bytes)
+constexpr int kHmStage = 128;      // targets per LDS stage (32-row tiles of 4 KB each: 128 B of FP4 nibbles per target); 128 or 256
+static_assert(kHmStage == 128 || kHmStage == 256, "the expansion below gives every thread kHmStage / 128 sixteen-byte loads");
 
 __device__ __forceinline__ void best2_push(uint32_t &best, uint32_t &second, uint32_t key) {
     const uint32_t lo = min(best, key), hi = max(best, key);
     second = min(second, hi);
     best = lo;
 }
+__device__ __forceinline__ v8i_t hm_operand(v4i_t v) { return v8i_t{v[0], v[1], v[2], v[3], 0, 0, 0, 0}; }     // FP4 operands are the low four of the builtin's eight dwords
 
 __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_a[kHmStage * 64];
+    __shared__ __attribute__((aligned(16))) uint32_t s_a[kHmStage * 32];
     const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 31, h = lane >> 5;
     const int qs = A.pair_q ? A.pair_q[p] : p, ts = A.pair_t ? A.pair_t[p] : p;
@@ -137,8 +144,9 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
     }
     const uint4 *Q = reinterpret_cast<const uint4 *>(A.q + (uint64_t)qs * A.q_stride * 8);
     const uint4 *T = reinterpret_cast<const uint4 *>(A.t + (uint64_t)ts * A.t_stride * 8);
-    v4i_t bq[2][8];
+    v4i_t bq[2][kHm4Steps];
     int popq[2];
+    const uint32_t hmask = 0u - (uint32_t)h;
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int qi = blockIdx.x * 256 + wave * 64 + n * 32 + col;
@@ -146,54 +154,53 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
         if (qi < nq) { lo = Q[2 * qi]; hi = Q[2 * qi + 1]; }
         const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
-        for (int s = 0; s < 8; ++s)                   // lane half h holds bits 4h+j (+8, +16, +24) of word s in dword j, as +16 / -16
+        for (int s = 0; s < kHm4Steps; ++s) {         // lane half h holds word 2s + h of k-step s, as +1 / -1 nibbles (x 2^4 by the B scale)
+            const uint32_t wq = (w[2 * s + 1] & hmask) | (w[2 * s] & ~hmask);      // a bit select: h ? : on the array becomes an indexed read of a scratch copy
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bq[n][s][j] = (int)((((w[s] >> (4 * h + j)) & 0x01010101u) * 0xE0u) ^ 0x10101010u);   // bit 0 -> +16, bit 1 -> -16: the accumulators come out as 16 * dot, ready to take a 4-bit row tag
+            for (int j = 0; j < 4; ++j) bq[n][s][j] = (int)hm4_query_dword(wq, j);
+        }
         popq[n] = 0;
 #pragma unroll
         for (int s = 0; s < 8; ++s) popq[n] += __popc(w[s]);
     }
     uint32_t best[2] = {kNone, kNone}, second[2] = {kNone, kNone};
-    v16i_t tag;
+    v16f_t tag;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tag[r] = 4096 + r;
+    for (int r = 0; r < 16; ++r) tag[r] = 8388608.0f + 4096.0f + (float)r;
     for (int base = 0; base < nt; base += kHmStage) {
         __syncthreads();
-        {   // expand this stage's targets: thread -> target tid & 127, words 4*(tid>>7) .. +3 (one 16-byte load)
-            const int tau = tid & 127, half = tid >> 7, j = base + tau;
+#pragma unroll
+        for (int it = 0; it < kHmStage / 128; ++it) {   // expand this stage's targets: one 16-byte load = target tau, words 4 * half .. + 3 = k-steps 2 * half, 2 * half + 1
+            const int e = tid + 256 * it, tau = e % kHmStage, half = e / kHmStage, j = base + tau;
             uint4 v = {0, 0, 0, 0};
             if (j < nt) v = T[2 * j + half];
             const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const uint32_t w = w4[k] >> (4 * hh);
-                    *reinterpret_cast<v4i_t *>(&s_a[((tau >> 5) * 8 + 4 * half + k) * 256 + (hh * 32 + (tau & 31)) * 4]) =
-                        v4i_t{(int)(w & 0x01010101u), (int)((w >> 1) & 0x01010101u), (int)((w >> 2) & 0x01010101u), (int)((w >> 3) & 0x01010101u)};
-                }
+            for (int k = 0; k < 4; ++k)                  // word 4 * half + k: k-step 2 * half + (k >> 1), lane half k & 1
+                *reinterpret_cast<v4i_t *>(&s_a[((tau >> 5) * kHm4Steps + 2 * half + (k >> 1)) * 256 + ((k & 1) * 32 + (tau & 31)) * 4]) =
+                    v4i_t{(int)hm4_target_dword(w4[k], 0), (int)hm4_target_dword(w4[k], 1), (int)hm4_target_dword(w4[k], 2), (int)hm4_target_dword(w4[k], 3)};
         }
         __syncthreads();
         const int mtiles = min(kHmStage / 32, (nt - base + 31) >> 5);
         for (int m = 0; m < mtiles; ++m) {
-            v16i_t acc[2];
-            v4i_t a[8];                                               // all eight fragments of the tile are requested before the first MFMA waits
+            v16f_t acc[2];
+            v4i_t a[kHm4Steps];                                       // all four fragments of the tile are requested before the first MFMA waits
 #pragma unroll
-            for (int s = 0; s < 8; ++s) a[s] = *reinterpret_cast<const v4i_t *>(&s_a[(m * 8 + s) * 256 + lane * 4]);
+            for (int s = 0; s < kHm4Steps; ++s) a[s] = *reinterpret_cast<const v4i_t *>(&s_a[(m * kHm4Steps + s) * 256 + lane * 4]);
             __builtin_amdgcn_sched_barrier(0);                        // keep the reads ahead of the chain (the scheduler would re-serialise them to save registers)
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {          // the chain starts from the row tags (4096 + register index), so no add follows it
-                acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[0][s], s == 0 ? tag : acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[1][s], s == 0 ? tag : acc[1], 0, 0, 0);
+            for (int s = 0; s < kHm4Steps; ++s) {  // the chain starts from the row tags (2^23 + 4096 + register index), so no add follows it
+                acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hm_operand(a[s]), hm_operand(bq[0][s]), s == 0 ? tag : acc[0], 4, 4, 0, (int)kHm4ScaleA, 0, (int)kHm4ScaleB);
+                acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hm_operand(a[s]), hm_operand(bq[1][s]), s == 0 ? tag : acc[1], 4, 4, 0, (int)kHm4ScaleA, 0, (int)kHm4ScaleB);
             }
             const int row0 = base + m * 32 + 4 * h;                   // this lane's rows: row0 + (reg & 3) + 8 * (reg >> 2)
             if (base + m * 32 + 32 <= nt) {                           // full tile (uniform)
-                // both column tiles at once on packed 16-bit lanes: key16 = (dot + 256) * 16 + register index (< 2^14); the
-                // register index orders a lane's rows, so the packed minimum is the lowest row among equal distances
+                // both column tiles at once on packed 16-bit lanes: key16 = (dot + 256) * 16 + register index (< 2^14), the low half of the float's
+                // bit pattern; the register index orders a lane's rows, so the packed minimum is the lowest row among equal distances
                 us2_t lb = {0xFFFF, 0xFFFF}, ls = {0xFFFF, 0xFFFF};
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const uint32_t both = __builtin_amdgcn_perm((uint32_t)acc[1][r], (uint32_t)acc[0][r], 0x05040100u);   // low halves: (acc0, acc1)
+                    const uint32_t both = __builtin_amdgcn_perm(__float_as_uint(acc[1][r]), __float_as_uint(acc[0][r]), 0x05040100u);   // low halves: (acc0, acc1)
                     const us2_t key = __builtin_bit_cast(us2_t, both);
                     const us2_t lo = __builtin_elementwise_min(lb, key), hi = __builtin_elementwise_max(lb, key);
                     ls = __builtin_elementwise_min(ls, hi);
@@ -212,7 +219,7 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int row = row0 + (r & 3) + 8 * (r >> 2);
-                        const uint32_t key = (((uint32_t)acc[n][r] - (uint32_t)r) << 16) + (uint32_t)row;  // (dot + 256) << 20
+                        const uint32_t key = ((__float_as_uint(acc[n][r]) - (uint32_t)r) << 16) + (uint32_t)row;  // (dot + 256) << 20: the shift drops the float's exponent field
                         best2_push(best[n], second[n], row < nt ? key : kNone);
                     }
             }
