@@ -460,6 +460,57 @@ int ms_projection_topk(ms_ctx *ctx, const float *sorted_x, const float *sorted_y
                        const float *q_x, const float *q_y, const float *q_radius, const int32_t *q_min_octave, const int32_t *q_max_octave,
                        const uint32_t *q_desc, int nq, int32_t *top_idx, uint16_t *top_dist, int32_t *top_octave, int32_t *n_scored, int32_t *n_candidates);
 
+/* ---- M3-M5 gates: the per-map-point loop in front of searchByProjection / replaceDuplication / findMatchesTranformedMps --------------
+ * (keyframe_matcher.cpp:313-345, :442-471, :573-596; Keyframe::isInFrustum, keyframe.cpp:247-262, is the SEARCH gates without the radius).
+ * One call gates a DEVICE-resident map-point table against n_views views and leaves, per view, the surviving points packed in walk order
+ * as the query arrays of ms_projection_topk: no query array is built on the host or uploaded.  tests/project_gate_ref.py restates the
+ * arithmetic and is this entry point's specification. */
+#define MS_GATE_SEARCH 0   /* searchByProjection :313-345; isInFrustum with view_cos_limit */
+#define MS_GATE_FUSE   1   /* replaceDuplication :442-471 */
+#define MS_GATE_SIM3   2   /* findMatchesTranformedMps :573-596 */
+#define MS_GATE_MAX_LEVELS 32
+#define MS_GATE_MAX_VIEWS 4096
+#define MS_GATE_MAX_ENTRIES (1 << 24)           /* n_entries stays BELOW this */
+typedef struct {
+    double R_cw[9], t_cw[3];   /* row-major; SIM3 mode: rotBAW / transBAW (may carry a scale) */
+    ms_pinhole cam;
+    float threshold;           /* SEARCH: threshold; FUSE / SIM3: margin */
+    float view_cos_limit;      /* SEARCH only (0.5 in the reference) */
+    int32_t mode;
+    int32_t first, count;      /* this view's slice of mp_index */
+} ms_gate_view;
+
+/* Entry e in the slice [first, first + count) of view v is map point mp_index[e] seen from view v; slices must not overlap, entries in no
+ * slice are not touched.  Gates in the reference's order, the first failing one gives the status:
+ *   0 kept | 1 not visible (the ms_pinhole rule above, p_c = R p + t) | 2 viewing distance outside [min, max] (inclusive bounds)
+ *   3 normal exactly zero (FUSE only, :460) | 4 viewing angle (SEARCH: cos < view_cos_limit, FUSE: cos < 0.5; SIM3 has none)
+ * Per entry (device arrays [n_entries], any may be NULL): x, y = the reprojection narrowed to float (0 at status 1); dist = the viewing
+ * distance as predictScaleLevel receives it (0 at status 1); level = predictScaleLevel (map_point.cpp:174-183), radius = the search radius
+ * (-1 and 0 unless kept).  The conversion the reference leaves undefined is pinned: a quotient of +inf gives level n_levels - 1, NaN gives 0.
+ * Per view, packed at offset views[v].first in entry order (device arrays [n_entries], q_desc [n_entries * 8]; any may be NULL): kept_entry
+ * = the entry's position in mp_index, q_* = the arguments of ms_projection_topk for nq = n_kept[v] (the octave window is [level - 1, level]
+ * in SIM3 mode, :611, and -0x7fffffff .. 0x7fffffff otherwise).  mp_desc / q_desc must be 16-byte aligned.
+ * scale_factors [n_levels] as ms_scale_factors gives them; scale_factor = orbScaleFactor (positive, not 1).
+ * The same input gives the same bits on every call and at every position of a batch; three launches whatever n_views is.  Synchronous: one
+ * upload, one download (n_kept).  MS_ERR_INVALID (nothing written) for a bad mode, an index outside [0, n_mp) inside a slice, a slice outside
+ * [0, n_entries), overlapping slices, a camera with width or height < 1, n_levels < 1, a scale_factor that is not positive and finite or is 1;
+ * MS_ERR_CAPACITY beyond the MS_GATE_MAX_* caps.  n_entries = 0 and empty views are fine (n_kept = 0).  The workspace belongs to the context
+ * and only grows, so calls no larger than an earlier one allocate nothing (ms_debug_host_allocs). */
+int ms_project_gate(ms_ctx *ctx,
+    /* map-point table, DEVICE */
+    const double *mp_pos, const float *mp_norm, const float *mp_min_dist,
+    const float *mp_max_dist, const uint32_t *mp_desc, int n_mp,
+    /* HOST */
+    const int32_t *mp_index, int n_entries, const ms_gate_view *views, int n_views,
+    const float *scale_factors, int n_levels, float scale_factor,
+    /* per entry, DEVICE, [n_entries] (any may be NULL) */
+    uint8_t *status, float *x, float *y, float *dist, int32_t *level, float *radius,
+    /* compacted per view at offset views[v].first, DEVICE */
+    int32_t *kept_entry, float *q_x, float *q_y, float *q_radius,
+    int32_t *q_min_octave, int32_t *q_max_octave, uint32_t *q_desc,
+    /* HOST [n_views] */
+    int32_t *n_kept);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

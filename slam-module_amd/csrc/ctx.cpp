@@ -146,6 +146,8 @@ void ms_ctx_destroy(ms_ctx *c) {
     if (c->lr_host) (void)hipHostFree(c->lr_host);
     if (c->s3_dev) (void)hipFree(c->s3_dev);
     if (c->s3_host) (void)hipHostFree(c->s3_host);
+    if (c->pg_dev) (void)hipFree(c->pg_dev);
+    if (c->pg_host) (void)hipHostFree(c->pg_host);
     for (auto &b : c->ba_cache) if (b.p) (void)hipFree(b.p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

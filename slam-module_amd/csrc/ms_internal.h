@@ -42,6 +42,9 @@ struct ms_ctx {
     // ms_sim3_optimize's workspace (sim3_opt.hip): device inputs / results and their page-locked staging, grow-only
     void *s3_dev = nullptr, *s3_host = nullptr;
     size_t s3_dev_bytes = 0, s3_host_bytes = 0;
+    // ms_project_gate's workspace (project_gate.hip): device tables / ranks / offsets and their page-locked staging, grow-only
+    void *pg_dev = nullptr, *pg_host = nullptr;
+    size_t pg_dev_bytes = 0, pg_host_bytes = 0;
     char err[512] = {0};
 };
 

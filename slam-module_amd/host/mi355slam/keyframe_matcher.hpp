@@ -6,7 +6,9 @@
 #pragma once
 #include <algorithm>
 #include <cstring>
+#include <array>
 #include <map>
+#include <stdexcept>
 #include <utility>
 #include "common.hpp"
 
@@ -263,6 +265,40 @@ inline Best2 rescan_on_host(const DeviceKeyframe &kf, const RadiusQuery &q, cons
     }
     return b;
 }
+
+// The greedy replay of searchByProjection (keyframe_matcher.cpp:356-389) over the top-4 lists of queries [first, first + count) of `l`: per query
+// the first two list entries that no earlier query of this call has bound are the reference's best and second best; a query whose list ran
+// out before its candidate set did (fewer than two free entries, more than four scored) is settled by rescan(q) -> Best2 against the CURRENT
+// mask.  accepted(q, keypoint) is called for every match, in walk order; `bound` is updated.  Returns the number of rescans.
+template <class Rescan, class Accepted>
+inline unsigned replay_search(const CandidateLists &l, std::size_t first, std::size_t count, std::vector<std::uint8_t> &bound, Rescan rescan, Accepted accepted) {
+    std::vector<std::uint8_t> taken(bound.size(), 0);            // bound during this call
+    unsigned again = 0;
+    for (std::size_t q = first; q < first + count; ++q) {
+        Best2 b;
+        int found = 0;
+        for (int e = 0; e < 4 && found < 2; ++e) {
+            const int j = l.idx[4 * q + e];
+            if (j < 0) break;
+            if (taken[(std::size_t)j]) continue;
+            if (found == 0) { b.best = j; b.bestDist = l.dist[4 * q + e]; b.bestLevel = l.octave[4 * q + e]; }
+            else { b.bestDist2 = l.dist[4 * q + e]; b.bestLevel2 = l.octave[4 * q + e]; }
+            ++found;
+        }
+        if (found < 2 && l.nScored[q] > 4) { b = rescan(q); ++again; }                         // `bound` = initial mask + everything taken so far
+        if (b.best == -1) continue;                                                          // :380
+        if (b.bestDist <= (int)HAMMING_DIST_THR_HIGH) {                                        // :382-383
+            if (b.bestLevel == b.bestLevel2 && b.bestDist > 0.8 * b.bestDist2) continue;       // :385-386
+            accepted(q, b.best); bound[(std::size_t)b.best] = 1; taken[(std::size_t)b.best] = 1;
+        }
+    }
+    return again;
+}
+
+// replaceDuplication (:479-499) / findMatchesTranformedMps (:600-627): the best candidate of query q when it is close enough, else -1
+inline int best_candidate(const CandidateLists &l, std::size_t q, unsigned maxDist) {
+    return l.idx[4 * q] >= 0 && l.dist[4 * q] <= maxDist ? l.idx[4 * q] : -1;
+}
 }  // namespace detail
 
 // Scoring + accept rule of searchByProjection (keyframe_matcher.cpp:349-389).  `bound[k]` != 0 marks keypoints that already
@@ -279,33 +315,8 @@ inline std::vector<int> searchByProjectionCore(Context &ctx, const DeviceKeyfram
                                                std::vector<std::uint8_t> &bound, unsigned *rescored = nullptr) {
     std::vector<int> match(queries.size(), -1);
     const CandidateLists s = detail::score_candidates(ctx, kf, queries, &bound);
-    std::vector<std::uint8_t> taken(bound.size(), 0);            // bound during this call
-    unsigned again = 0;
-    for (std::size_t i = 0; i < queries.size(); ++i) {
-        int best = -1, bestDist = 256, bestDist2 = 256, bestLevel = -1, bestLevel2 = -1, found = 0;
-        auto walk = [&](const CandidateLists &l, std::size_t q) {
-            best = -1; bestDist = 256; bestDist2 = 256; bestLevel = -1; bestLevel2 = -1; found = 0;
-            for (int e = 0; e < 4 && found < 2; ++e) {
-                const int j = l.idx[4 * q + e];
-                if (j < 0) break;
-                if (taken[(std::size_t)j]) continue;
-                if (found == 0) { best = j; bestDist = l.dist[4 * q + e]; bestLevel = l.octave[4 * q + e]; }
-                else { bestDist2 = l.dist[4 * q + e]; bestLevel2 = l.octave[4 * q + e]; }
-                ++found;
-            }
-        };
-        walk(s, i);
-        if (found < 2 && s.nScored[i] > 4) {                       // the list ran out before the candidate set did
-            const detail::Best2 r = detail::rescan_on_host(kf, queries[i], bound);               // `bound` = initial mask + everything taken so far
-            best = r.best; bestDist = r.bestDist; bestDist2 = r.bestDist2; bestLevel = r.bestLevel; bestLevel2 = r.bestLevel2;
-            ++again;
-        }
-        if (best == -1) continue;                                                          // :380
-        if (bestDist <= (int)HAMMING_DIST_THR_HIGH) {                                        // :382-383
-            if (bestLevel == bestLevel2 && bestDist > 0.8 * bestDist2) continue;             // :385-386
-            match[i] = best; bound[(std::size_t)best] = 1; taken[(std::size_t)best] = 1;
-        }
-    }
+    const unsigned again = detail::replay_search(s, 0, queries.size(), bound, [&](std::size_t q) { return detail::rescan_on_host(kf, queries[q], bound); },
+                                                 [&](std::size_t q, int best) { match[q] = best; });
     if (rescored) *rescored = again;
     return match;
 }
@@ -316,7 +327,7 @@ template <class Query>
 inline std::vector<int> bestCandidateCore(Context &ctx, const DeviceKeyframe &kf, const std::vector<Query> &queries, unsigned maxDist) {
     const CandidateLists s = detail::score_candidates(ctx, kf, queries, nullptr);
     std::vector<int> match(queries.size(), -1);
-    for (std::size_t i = 0; i < queries.size(); ++i) if (s.idx[4 * i] >= 0 && s.dist[4 * i] <= maxDist) match[i] = s.idx[4 * i];
+    for (std::size_t i = 0; i < queries.size(); ++i) match[i] = detail::best_candidate(s, i, maxDist);
     return match;
 }
 
@@ -397,6 +408,243 @@ inline unsigned matchMapPointsSim3(Context &ctx, const DeviceKeyframe &kf1, cons
     // a pair is kept when each side names the other (:672-685), in ascending kf1 index
     const std::size_t before = matches.size();
     for (std::size_t i1 = 0; i1 < fwd.size(); ++i1)
+        if (fwd[i1] >= 0 && bwd.at((std::size_t)fwd[i1]) == (int)i1) matches.emplace_back((int)i1, fwd[i1]);
+    return (unsigned)(matches.size() - before);
+}
+
+// ---- M3-M5 with the gates on the device (ms_project_gate) ------------------------------------------------------------------------
+// The per-map-point loop in front of the three matchers (reprojection, viewing distance, viewing angle, predictScaleLevel, radius;
+// keyframe_matcher.cpp:313-345, :442-471, :573-596) runs on the device over a table of map points that lives there, and its output IS the
+// query block of ms_projection_topk: no query array is built or uploaded by the host.  What reads the map graph stays with the caller
+// (observations.count, the BAD / NOT_TRIANGULATED test, erasedMapPointIds): it passes the rows that survive those filters, in walk order.
+
+// The map points the gates read, structure-of-arrays on the device.  Row i = one MapPoint: position, norm, minViewingDistance,
+// maxViewingDistance, descriptor.  update() re-uploads a range after the map changed (MapPoint::updateDistanceAndNorm / updateDescriptor).
+class DeviceMapPoints {
+public:
+    using Vec3d = std::array<double, 3>;
+    using Vec3f = std::array<float, 3>;
+    DeviceMapPoints(Context &ctx, const std::vector<Vec3d> &position, const std::vector<Vec3f> &norm, const std::vector<float> &minDistance,
+                    const std::vector<float> &maxDistance, const std::vector<KeyPoint::Descriptor> &descriptor) : ctx_(ctx), n_(position.size()) {
+        if (norm.size() != n_ || minDistance.size() != n_ || maxDistance.size() != n_ || descriptor.size() != n_)
+            throw std::runtime_error("DeviceMapPoints: the arrays describe different numbers of map points");
+        pos_ = alloc<double>(3 * n_); norm_ = alloc<float>(3 * n_); min_ = alloc<float>(n_); max_ = alloc<float>(n_); desc_ = alloc<std::uint32_t>(8 * n_);
+        update(0, n_, position.data(), norm.data(), minDistance.data(), maxDistance.data(), descriptor.data());
+    }
+    ~DeviceMapPoints() { for (void *p : owned_) ms_dev_free(ctx_.get(), p); }
+    DeviceMapPoints(const DeviceMapPoints &) = delete;
+    // rows [first, first + count) of the fields that are not nullptr
+    void update(std::size_t first, std::size_t count, const Vec3d *position, const Vec3f *norm, const float *minDistance, const float *maxDistance,
+                const KeyPoint::Descriptor *descriptor) {
+        if (first + count > n_) throw std::runtime_error("DeviceMapPoints::update: range outside the table");
+        if (count == 0) return;
+        if (position) up(pos_ + 3 * first, position, 24 * count);
+        if (norm) up(norm_ + 3 * first, norm, 12 * count);
+        if (minDistance) up(min_ + first, minDistance, 4 * count);
+        if (maxDistance) up(max_ + first, maxDistance, 4 * count);
+        if (descriptor) up(desc_ + 8 * first, descriptor, 32 * count);
+    }
+    std::size_t size() const { return n_; }
+    const double *position() const { return pos_; }
+    const float *norm() const { return norm_; }
+    const float *minDistance() const { return min_; }
+    const float *maxDistance() const { return max_; }
+    const std::uint32_t *descriptor() const { return desc_; }
+private:
+    template <typename T> T *alloc(std::size_t n) {
+        void *d = nullptr;
+        ctx_.check(ms_dev_alloc(ctx_.get(), n * sizeof(T) + 16, &d), "ms_dev_alloc");
+        owned_.push_back(d);
+        return static_cast<T *>(d);
+    }
+    void up(void *dst, const void *src, std::size_t bytes) { ctx_.check(ms_dev_upload(ctx_.get(), dst, src, bytes), "ms_dev_upload"); }
+    Context &ctx_;
+    std::size_t n_;
+    double *pos_ = nullptr;
+    float *norm_ = nullptr, *min_ = nullptr, *max_ = nullptr;
+    std::uint32_t *desc_ = nullptr;
+    std::vector<void *> owned_;
+};
+
+// One view of a gate call: a pose (p_c = R p + t, row-major; for MS_GATE_SIM3 rotBAW / transBAW, which may carry a scale), a pinhole camera
+// (the stand-in of ms_pinhole), the loop's threshold / margin, and the table rows to walk, in the reference's order.
+struct GateView {
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+    ms_pinhole camera{};
+    float threshold = 0.f;              // searchByProjection: threshold; replaceDuplication / findMatchesTranformedMps: margin
+    float cosLimit = 0.5f;              // searchByProjection's viewAngleLimitCos (:304) / isInFrustum's argument
+    int mode = MS_GATE_SEARCH;
+    std::vector<std::int32_t> indices;
+};
+
+namespace detail {
+// the result of gate + scoring for a list of views: view v's kept entries are slice positions [first[v], first[v] + nKept[v]) of the lists
+struct GatedLists {
+    std::vector<std::int32_t> first, nKept, keptEntry;       // keptEntry: position in the views' concatenated index lists
+    CandidateLists lists;
+    const unsigned char *ws = nullptr;                       // the device block (query arrays), for the rare host rescan
+    std::size_t oX = 0, oY = 0, oR = 0, oD = 0;
+};
+
+inline void pack_views(const std::vector<GateView> &views, std::vector<ms_gate_view> &V, std::vector<std::int32_t> &index) {
+    V.clear(); index.clear();
+    for (const GateView &g : views) {
+        ms_gate_view v{};
+        std::memcpy(v.R_cw, g.R, sizeof(v.R_cw)); std::memcpy(v.t_cw, g.t, sizeof(v.t_cw));
+        v.cam = g.camera; v.threshold = g.threshold; v.view_cos_limit = g.cosLimit; v.mode = g.mode;
+        v.first = (std::int32_t)index.size(); v.count = (std::int32_t)g.indices.size();
+        index.insert(index.end(), g.indices.begin(), g.indices.end());
+        V.push_back(v);
+    }
+}
+
+// ms_project_gate over all views, then ms_projection_topk per view against kfs[v] on the packed slices where they lie; one download of the lists.
+// skip (optional) = searchByProjection's bound mask, uploaded for every view's keyframe alike (used with one view).
+inline GatedLists gate_and_score(Context &ctx, const DeviceMapPoints &table, const std::vector<GateView> &views, const std::vector<const DeviceKeyframe *> &kfs,
+                                 const StaticSettings &settings, const std::vector<std::uint8_t> *skip) {
+    std::vector<ms_gate_view> V;
+    std::vector<std::int32_t> index;
+    pack_views(views, V, index);
+    const std::size_t ne = index.size(), sec = pad16(4 * ne), nk = skip ? skip->size() : 0;
+    GatedLists g;
+    g.nKept.assign(views.size(), 0);
+    for (const ms_gate_view &v : V) g.first.push_back(v.first);
+    const std::size_t oX = 0, oY = oX + sec, oR = oY + sec, oLo = oR + sec, oHi = oLo + sec, oD = oHi + sec, oK = oD + 32 * ne;
+    const std::size_t oE = oK + pad16(nk), oTi = oE + sec, oTo = oTi + 16 * ne, oN = oTo + 16 * ne, oTd = oN + sec, total = oTd + pad16(8 * ne);
+    unsigned char *ws = ctx.workspace(total + 16);
+    g.ws = ws; g.oX = oX; g.oY = oY; g.oR = oR; g.oD = oD;
+    auto F = [&](std::size_t o) { return reinterpret_cast<float *>(ws + o); };
+    auto I = [&](std::size_t o) { return reinterpret_cast<std::int32_t *>(ws + o); };
+    ctx.check(ms_project_gate(ctx.get(), table.position(), table.norm(), table.minDistance(), table.maxDistance(), table.descriptor(), (int)table.size(),
+                              index.data(), (int)ne, V.data(), (int)V.size(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(),
+                              settings.parameters.orbScaleFactor, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, I(oE), F(oX), F(oY), F(oR), I(oLo), I(oHi),
+                              reinterpret_cast<std::uint32_t *>(ws + oD), g.nKept.data()), "ms_project_gate");
+    g.keptEntry.assign(ne, -1);
+    g.lists.idx.assign(4 * ne, -1); g.lists.octave.assign(4 * ne, -1); g.lists.nScored.assign(ne, 0); g.lists.dist.assign(4 * ne, MS_HAMMING_MAX);
+    if (ne == 0) return g;
+    if (nk) ctx.check(ms_dev_upload(ctx.get(), ws + oK, skip->data(), nk), "ms_dev_upload");
+    for (std::size_t v = 0; v < V.size(); ++v) {
+        const std::size_t f = (std::size_t)V[v].first;
+        const ms_match_frame &fr = kfs[v]->frame();
+        ctx.check(ms_projection_topk(ctx.get(), kfs[v]->sortedX(), kfs[v]->sortedY(), kfs[v]->sortedIndex(), fr.n, fr.desc, fr.octave, nk ? ws + oK : nullptr,
+                                     F(oX) + f, F(oY) + f, F(oR) + f, I(oLo) + f, I(oHi) + f, reinterpret_cast<const std::uint32_t *>(ws + oD) + 8 * f, g.nKept[v],
+                                     I(oTi) + 4 * f, reinterpret_cast<std::uint16_t *>(ws + oTd) + 4 * f, I(oTo) + 4 * f, I(oN) + f, nullptr), "ms_projection_topk");
+    }
+    std::vector<unsigned char> &st = ctx.staging();
+    st.resize(total - oE);
+    ctx.check(ms_dev_download(ctx.get(), st.data(), ws + oE, total - oE), "ms_dev_download");
+    for (std::size_t v = 0; v < V.size(); ++v) {              // only the kept part of every slice was written
+        const std::size_t f = (std::size_t)V[v].first, k = (std::size_t)g.nKept[v];
+        if (k == 0) continue;
+        std::memcpy(g.keptEntry.data() + f, st.data() + 4 * f, 4 * k);
+        std::memcpy(g.lists.idx.data() + 4 * f, st.data() + (oTi - oE) + 16 * f, 16 * k);
+        std::memcpy(g.lists.octave.data() + 4 * f, st.data() + (oTo - oE) + 16 * f, 16 * k);
+        std::memcpy(g.lists.nScored.data() + f, st.data() + (oN - oE) + 4 * f, 4 * k);
+        std::memcpy(g.lists.dist.data() + 4 * f, st.data() + (oTd - oE) + 8 * f, 8 * k);
+    }
+    return g;
+}
+}  // namespace detail
+
+// Keyframe::isInFrustum (keyframe.cpp:247-262) for many map points at once: reprojection, viewing distance and viewing angle of the table rows
+// `indices` against one pose and camera.
+inline std::vector<bool> isInFrustum(Context &ctx, const DeviceMapPoints &table, const std::vector<std::int32_t> &indices, const double R[9], const double t[3],
+                                     const ms_pinhole &camera, float cosLimit, const StaticSettings &settings) {
+    ms_gate_view v{};
+    std::memcpy(v.R_cw, R, sizeof(v.R_cw)); std::memcpy(v.t_cw, t, sizeof(v.t_cw));
+    v.cam = camera; v.view_cos_limit = cosLimit; v.mode = MS_GATE_SEARCH; v.first = 0; v.count = (std::int32_t)indices.size();
+    std::vector<bool> in(indices.size(), false);
+    if (indices.empty()) return in;
+    unsigned char *ws = ctx.workspace(indices.size() + 16);
+    std::int32_t kept = 0;
+    ctx.check(ms_project_gate(ctx.get(), table.position(), table.norm(), table.minDistance(), table.maxDistance(), table.descriptor(), (int)table.size(),
+                              indices.data(), (int)indices.size(), &v, 1, settings.scaleFactors.data(), (int)settings.scaleFactors.size(),
+                              settings.parameters.orbScaleFactor, ws, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, &kept), "ms_project_gate");
+    std::vector<unsigned char> &st = ctx.staging();
+    st.resize(indices.size());
+    ctx.check(ms_dev_download(ctx.get(), st.data(), ws, indices.size()), "ms_dev_download");
+    for (std::size_t i = 0; i < indices.size(); ++i) in[i] = st[i] == 0;
+    return in;
+}
+
+// searchByProjection (keyframe_matcher.cpp:295-414) over table rows: view.indices = the map points `mps` in the caller's order, view.mode =
+// MS_GATE_SEARCH, view.threshold = threshold.  Gates, radius query and scoring run on the device; the replay is the one searchByProjectionCore runs
+// (detail::replay_search; a list that ran out is settled by one host scan of that query, for which the kept queries are read back once).  Returns, per entry of view.indices, the matched keypoint or -1; `bound` is updated.
+inline std::vector<int> searchByProjection(Context &ctx, const DeviceKeyframe &kf, const DeviceMapPoints &table, const GateView &view,
+                                           std::vector<std::uint8_t> &bound, const StaticSettings &settings, unsigned *rescored = nullptr) {
+    std::vector<int> match(view.indices.size(), -1);
+    const detail::GatedLists g = detail::gate_and_score(ctx, table, {view}, {&kf}, settings, &bound);
+    // the kept queries' position, radius and descriptor, read back once and only if a list ran out.  g.ws points into Context::workspace, which a
+    // larger request would free: nothing between gate_and_score and the end of this function asks the context for workspace.
+    const std::size_t nq = (std::size_t)g.nKept[0];
+    std::vector<float> qx, qy, qr;
+    std::vector<std::uint32_t> qd;
+    auto rescan = [&](std::size_t q) {
+        if (qx.empty()) {
+            qx.resize(nq); qy.resize(nq); qr.resize(nq); qd.resize(8 * nq);
+            ctx.check(ms_dev_download(ctx.get(), qx.data(), g.ws + g.oX, 4 * nq), "ms_dev_download");
+            ctx.check(ms_dev_download(ctx.get(), qy.data(), g.ws + g.oY, 4 * nq), "ms_dev_download");
+            ctx.check(ms_dev_download(ctx.get(), qr.data(), g.ws + g.oR, 4 * nq), "ms_dev_download");
+            ctx.check(ms_dev_download(ctx.get(), qd.data(), g.ws + g.oD, 32 * nq), "ms_dev_download");
+        }
+        RadiusQuery rq;
+        rq.x = qx[q]; rq.y = qy[q]; rq.radius = qr[q];
+        std::memcpy(rq.descriptor.data(), qd.data() + 8 * q, 32);
+        return detail::rescan_on_host(kf, rq, bound);
+    };
+    const unsigned again = detail::replay_search(g.lists, 0, nq, bound, rescan, [&](std::size_t q, int best) { match[(std::size_t)g.keptEntry[q]] = best; });
+    if (rescored) *rescored = again;
+    return match;
+}
+
+// The candidate search of replaceDuplication (keyframe_matcher.cpp:442-499) for ALL adjacent keyframes of a fuse step in one gate call:
+// views[v] (MS_GATE_FUSE, threshold = margin, indices = the rows that pass the graph filters of :429-440 for keyframe v) against kfs[v].
+// Returns, per view and entry, the best keypoint inside the radius at Hamming distance <= HAMMING_DIST_THR_LOW, or -1 (:495-499); the
+// caller walks them in order and performs the graph surgery of :501-525 (a point erased on the way is skipped there, :429).
+inline std::vector<std::vector<int>> replaceDuplicationCandidates(Context &ctx, const DeviceMapPoints &table, const std::vector<GateView> &views,
+                                                                  const std::vector<const DeviceKeyframe *> &kfs, const StaticSettings &settings) {
+    const detail::GatedLists g = detail::gate_and_score(ctx, table, views, kfs, settings, nullptr);
+    std::vector<std::vector<int>> out(views.size());
+    for (std::size_t v = 0; v < views.size(); ++v) {
+        out[v].assign(views[v].indices.size(), -1);
+        const std::size_t f = (std::size_t)g.first[v];
+        for (std::size_t q = f; q < f + (std::size_t)g.nKept[v]; ++q)
+            out[v][(std::size_t)g.keptEntry[q] - f] = detail::best_candidate(g.lists, q, HAMMING_DIST_THR_LOW);
+    }
+    return out;
+}
+
+// matchMapPointsSim3 (keyframe_matcher.cpp:633-686) over table rows instead of the caller's `project` lambda: mps1[i] / mps2[i] = the table row
+// of the TRIANGULATED map point of keypoint i of kf1 / kf2, or -1 (:568-571).  (R1in2, t1in2) = transform12^-1 * kf1.poseCW takes world points
+// into kf2 (:650), (R2in1, t2in1) = transform12 * kf2.poseCW into kf1 (:661); both may carry the Sim3's scale.  One gate call, two scoring launches.
+inline unsigned matchMapPointsSim3(Context &ctx, const DeviceKeyframe &kf1, const DeviceKeyframe &kf2, const DeviceMapPoints &table,
+                                   const std::vector<std::int32_t> &mps1, const std::vector<std::int32_t> &mps2, const double R1in2[9], const double t1in2[3],
+                                   const double R2in1[9], const double t2in1[3], const ms_pinhole &camera1, const ms_pinhole &camera2,
+                                   std::vector<std::pair<int, int>> &matches, const StaticSettings &settings) {
+    constexpr float margin = 7.5;                                                              // :641
+    std::vector<bool> taken1(mps1.size(), false), taken2(mps2.size(), false);                  // :645-648
+    for (const std::pair<int, int> &m : matches) { taken1.at((std::size_t)m.first) = true; taken2.at((std::size_t)m.second) = true; }
+    std::vector<GateView> views(2);
+    std::vector<std::size_t> owner[2];
+    auto fill = [&](int v, const std::vector<std::int32_t> &mps, const std::vector<bool> &taken, const double *R, const double *t, const ms_pinhole &cam) {
+        std::memcpy(views[v].R, R, 72); std::memcpy(views[v].t, t, 24);
+        views[v].camera = cam; views[v].threshold = margin; views[v].mode = MS_GATE_SIM3;
+        for (std::size_t i = 0; i < mps.size(); ++i)
+            if (!taken[i] && mps[i] >= 0) { views[v].indices.push_back(mps[i]); owner[v].push_back(i); }
+    };
+    fill(0, mps1, taken1, R1in2, t1in2, camera2);
+    fill(1, mps2, taken2, R2in1, t2in1, camera1);
+    const detail::GatedLists g = detail::gate_and_score(ctx, table, views, {&kf2, &kf1}, settings, nullptr);
+    std::vector<int> fwd(mps1.size(), -1), bwd(mps2.size(), -1);
+    for (int v = 0; v < 2; ++v) {
+        std::vector<int> &dst = v == 0 ? fwd : bwd;
+        const std::size_t f = (std::size_t)g.first[v];
+        for (std::size_t q = f; q < f + (std::size_t)g.nKept[v]; ++q)
+            dst[owner[v][(std::size_t)g.keptEntry[q] - f]] = detail::best_candidate(g.lists, q, HAMMING_DIST_THR_HIGH);   // :625-627
+    }
+    const std::size_t before = matches.size();
+    for (std::size_t i1 = 0; i1 < fwd.size(); ++i1)                                            // :672-685
         if (fwd[i1] >= 0 && bwd.at((std::size_t)fwd[i1]) == (int)i1) matches.emplace_back((int)i1, fwd[i1]);
     return (unsigned)(matches.size() - before);
 }

@@ -905,3 +905,193 @@ def sim3_optimize(ctx, problems, chi2=False):
             d["chi2"] = per_edge[i]
         out.append(d)
     return out
+
+
+# ---- map-point gates in front of the projection-guided matchers (ms_project_gate) ----
+GATE_SEARCH, GATE_FUSE, GATE_SIM3 = 0, 1, 2
+MS_HAMMING_THR_HIGH = 100             # keyframe_matcher.hpp:11
+
+
+class GateViewC(C.Structure):
+    _fields_ = [("R_cw", C.c_double * 9), ("t_cw", C.c_double * 3), ("cam", Pinhole), ("threshold", C.c_float), ("view_cos_limit", C.c_float),
+                ("mode", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
+
+
+class MapPointTable:
+    """The map points the gates read, structure-of-arrays on the device: pos [n, 3] float64 (MapPoint::position), norm [n, 3] float32,
+    min_dist / max_dist [n] float32 (minViewingDistance / maxViewingDistance), desc [n, 8] uint32 (MapPoint::descriptor)."""
+    _FIELDS = (("pos", np.float64, 3), ("norm", np.float32, 3), ("min_dist", np.float32, 1), ("max_dist", np.float32, 1), ("desc", np.uint32, 8))
+
+    def __init__(self, ctx, pos, norm, min_dist, max_dist, desc):
+        self.ctx = ctx
+        arrs = dict(pos=pos, norm=norm, min_dist=min_dist, max_dist=max_dist, desc=desc)
+        self.n = len(np.asarray(pos).reshape(-1, 3))
+        for name, dt, w in self._FIELDS:
+            a = np.ascontiguousarray(arrs[name], dt).reshape(-1, w)
+            if len(a) != self.n:
+                raise ValueError("%s describes %d map points, pos %d" % (name, len(a), self.n))
+            setattr(self, name, ctx.upload(a if self.n else np.zeros((1, w), dt)))
+
+    def update(self, first, count, **fields):
+        """Re-upload rows [first, first + count) of the named fields (e.g. pos=..., norm=...) after the map changed."""
+        if first < 0 or count < 0 or first + count > self.n:
+            raise ValueError("rows [%d, %d) outside the table of %d" % (first, first + count, self.n))
+        for name, dt, w in self._FIELDS:
+            if name in fields and count:
+                a = np.ascontiguousarray(fields[name], dt).reshape(count, w)
+                self.ctx.check(lib().ms_dev_upload(self.ctx._h, C.c_void_p(getattr(self, name).ptr + first * a.itemsize * w), _vp(a), C.c_size_t(a.nbytes)), "ms_dev_upload")
+
+
+def gate_views_pack(views):
+    """(GateViewC array, mp_index) for a list of view dicts: R [3, 3], t [3], cam (fx, fy, cx, cy, width, height), threshold, view_cos_limit
+    (SEARCH only), mode (GATE_*), indices (rows of the table in walk order).  The slices follow each other in mp_index."""
+    structs, idx, at = [], [], 0
+    for v in views:
+        ind = np.ascontiguousarray(v["indices"], np.int32).reshape(-1)
+        R = np.ascontiguousarray(v["R"], np.float64).reshape(9); t = np.ascontiguousarray(v["t"], np.float64).reshape(3)
+        structs.append(GateViewC((C.c_double * 9)(*R), (C.c_double * 3)(*t), Pinhole(*v["cam"]), float(v["threshold"]), float(v.get("view_cos_limit", 0.5)),
+                                 int(v["mode"]), at, len(ind)))
+        idx.append(ind); at += len(ind)
+    return (GateViewC * max(len(views), 1))(*structs), np.concatenate(idx + [np.zeros(0, np.int32)]).astype(np.int32)
+
+
+def gate_buffers(ctx, n_entries, per_entry=True):
+    """The device outputs of ms_project_gate for up to n_entries entries, as a dict of DevBufs (reusable across calls)."""
+    ne, out = n_entries, {}
+    if per_entry:
+        out.update(status=ctx.alloc(ne + 16), x=ctx.alloc(4 * ne + 16), y=ctx.alloc(4 * ne + 16), dist=ctx.alloc(4 * ne + 16), level=ctx.alloc(4 * ne + 16),
+                   radius=ctx.alloc(4 * ne + 16))
+    out.update(kept_entry=ctx.alloc(4 * ne + 16), q_x=ctx.alloc(4 * ne + 16), q_y=ctx.alloc(4 * ne + 16), q_radius=ctx.alloc(4 * ne + 16),
+               q_min_octave=ctx.alloc(4 * ne + 16), q_max_octave=ctx.alloc(4 * ne + 16), q_desc=ctx.alloc(32 * ne + 16))
+    return out
+
+
+def project_gate_device(ctx, table, views, scale_factors_, scale_factor, per_entry=True, out=None):
+    """ms_project_gate with everything left on the device: returns (out, n_kept, V) -- out: DevBufs status, x, y, dist, level, radius (when
+    per_entry) and kept_entry, q_x, q_y, q_radius, q_min_octave, q_max_octave, q_desc (allocated here unless the caller passes the dict of
+    an earlier gate_buffers call that is large enough); n_kept [n_views]; V the packed views (V[v].first)."""
+    V, idx = gate_views_pack(views)
+    ne = len(idx)
+    sf = np.ascontiguousarray(scale_factors_, np.float32)
+    if out is None:
+        out = gate_buffers(ctx, ne, per_entry)
+    n_kept = np.zeros(max(len(views), 1), np.int32)
+    pe = [_vp(out.get(k)) for k in ("status", "x", "y", "dist", "level", "radius")]
+    ctx.check(lib().ms_project_gate(ctx._h, _vp(table.pos), _vp(table.norm), _vp(table.min_dist), _vp(table.max_dist), _vp(table.desc), table.n,
+                                    _vp(idx), ne, V, len(views), _vp(sf), len(sf), C.c_float(scale_factor), *pe,
+                                    *[_vp(out[k]) for k in ("kept_entry", "q_x", "q_y", "q_radius", "q_min_octave", "q_max_octave", "q_desc")], _vp(n_kept)),
+              "ms_project_gate")
+    return out, n_kept[:len(views)], V
+
+
+_GATE_DTYPES = dict(status=np.uint8, x=np.float32, y=np.float32, dist=np.float32, level=np.int32, radius=np.float32, kept_entry=np.int32,
+                    q_x=np.float32, q_y=np.float32, q_radius=np.float32, q_min_octave=np.int32, q_max_octave=np.int32)
+
+
+def project_gate(ctx, table, views, scale_factors_, scale_factor):
+    """The gates of searchByProjection / replaceDuplication / findMatchesTranformedMps for a list of views (see gate_views_pack) over a
+    MapPointTable.  Returns (entries, per_view): entries = dict of per-entry arrays over all views back to back (status, x, y, dist, level,
+    radius); per_view[v] = dict of view v's packed arrays, n_kept long (kept = positions in the view's indices, q_x, q_y, q_radius,
+    q_min_octave, q_max_octave, q_desc [n_kept, 8])."""
+    out, n_kept, V = project_gate_device(ctx, table, views, scale_factors_, scale_factor)
+    ne = sum(V[v].count for v in range(len(views)))
+    host = {k: out[k].download(dt, (ne,)) for k, dt in _GATE_DTYPES.items()}
+    host["q_desc"] = out["q_desc"].download(np.uint32, (ne, 8))
+    entries = {k: host[k] for k in ("status", "x", "y", "dist", "level", "radius")}
+    per_view = []
+    for v in range(len(views)):
+        f, k = V[v].first, int(n_kept[v])
+        d = {name: host[name][f:f + k].copy() for name in ("q_x", "q_y", "q_radius", "q_min_octave", "q_max_octave", "q_desc")}
+        d["kept"] = host["kept_entry"][f:f + k] - f
+        per_view.append(d)
+    for b in out.values():
+        b.free()
+    return entries, per_view
+
+
+class ProjectionKeyframe:
+    """One keyframe's side of the projection-guided matchers on the device (FeatureSearch order, descriptors, octaves) with the host copies the
+    replay needs."""
+
+    def __init__(self, ctx, x, y, desc, octave):
+        self.x = np.ascontiguousarray(x, np.float32); self.y = np.ascontiguousarray(y, np.float32)
+        self.desc = np.ascontiguousarray(desc, np.uint32).reshape(-1, 8); self.octave = np.ascontiguousarray(octave, np.int32)
+        self.n = len(self.x)
+        self.sx, self.sy, self.si = feature_search_sort(self.x, self.y)
+        up = lambda a: ctx.upload(a if len(a) else np.zeros((4,) + a.shape[1:], a.dtype))
+        self.d_sx, self.d_sy, self.d_si, self.d_desc, self.d_oct = up(self.sx), up(self.sy), up(self.si), up(self.desc), up(self.octave)
+
+
+def _gate_then_topk(ctx, kf, table, view, scale_factors_, scale_factor, t_skip):
+    """gate -> ms_projection_topk on one view with the query arrays staying on the device.  Returns (kept positions, top_idx, top_dist, top_octave,
+    n_scored, the gate's device buffers)."""
+    out, n_kept, _ = project_gate_device(ctx, table, [view], scale_factors_, scale_factor, per_entry=False)
+    nq = int(n_kept[0])
+    dsk = ctx.upload(np.ascontiguousarray(t_skip, np.uint8)) if t_skip is not None and kf.n else None
+    ti, td, to, ns = ctx.alloc(16 * nq + 16), ctx.alloc(8 * nq + 16), ctx.alloc(16 * nq + 16), ctx.alloc(4 * nq + 16)
+    ctx.check(lib().ms_projection_topk(ctx._h, _vp(kf.d_sx), _vp(kf.d_sy), _vp(kf.d_si), kf.n, _vp(kf.d_desc), _vp(kf.d_oct), _vp(dsk),
+                                       _vp(out["q_x"]), _vp(out["q_y"]), _vp(out["q_radius"]), _vp(out["q_min_octave"]), _vp(out["q_max_octave"]),
+                                       _vp(out["q_desc"]), nq, _vp(ti), _vp(td), _vp(to), _vp(ns), None), "ms_projection_topk")
+    ctx.sync()
+    res = (out["kept_entry"].download(np.int32, (nq,)), ti.download(np.int32, (nq, 4)), td.download(np.uint16, (nq, 4)), to.download(np.int32, (nq, 4)),
+           ns.download(np.int32, (nq,)), out)
+    for b in (ti, td, to, ns, dsk):
+        if b is not None:
+            b.free()
+    return res
+
+
+def _hamming256(a, b):
+    return int(np.unpackbits((a ^ b).view(np.uint8)).sum())
+
+
+def search_by_projection(ctx, kf, table, view, bound, scale_factors_, scale_factor):
+    """searchByProjection (keyframe_matcher.cpp:313-400) with the gates, the radius query and the scoring on the device: ms_project_gate ->
+    ms_projection_topk -> the host replay of mi355slam::searchByProjectionCore (the first two list entries no earlier map point of this call
+    has bound; a query whose list ran out is scanned again on the host).  kf: ProjectionKeyframe; view: a GATE_SEARCH view dict; bound [n]
+    uint8 (keypoints that carry an observed map point), updated in place.  Returns [(position in view['indices'], keypoint index)]."""
+    kept, ti, td, to, ns, dev = _gate_then_topk(ctx, kf, table, view, scale_factors_, scale_factor, bound)
+    taken = np.zeros(kf.n, bool)
+    q = None
+    matches = []
+    for i in range(len(kept)):
+        free = [e for e in range(4) if ti[i, e] >= 0 and not taken[ti[i, e]]][:2]
+        best, best_d, lvl = (int(ti[i, free[0]]), int(td[i, free[0]]), int(to[i, free[0]])) if free else (-1, 256, -1)
+        best2_d, lvl2 = (int(td[i, free[1]]), int(to[i, free[1]])) if len(free) > 1 else (256, -1)
+        if len(free) < 2 and ns[i] > 4:                       # the list ran out before the candidate set did: this one query again, on the host
+            if q is None:
+                n = len(kept)
+                q = (dev["q_x"].download(np.float32, (n,)), dev["q_y"].download(np.float32, (n,)), dev["q_radius"].download(np.float32, (n,)),
+                     dev["q_desc"].download(np.uint32, (n, 8)))
+            x, y, r = q[0][i], q[1][i], q[2][i]
+            lo, hi = np.searchsorted(kf.sy, y - r, "left"), np.searchsorted(kf.sy, y + r, "right")
+            dx, dy = x - kf.sx[lo:hi], y - kf.sy[lo:hi]
+            best, best_d, best2_d, lvl, lvl2 = -1, 256, 256, -1, -1
+            for j in kf.si[lo:hi][(dx * dx + dy * dy) < r * r]:
+                if bound[j]:
+                    continue
+                d = _hamming256(q[3][i], kf.desc[j])
+                if d < best_d:
+                    best2_d, best_d, lvl2, lvl, best = best_d, d, lvl, int(kf.octave[j]), int(j)
+                elif d < best2_d:
+                    lvl2, best2_d = int(kf.octave[j]), d
+        if best == -1 or best_d > MS_HAMMING_THR_HIGH or (lvl == lvl2 and best_d > 0.8 * best2_d):
+            continue
+        bound[best] = 1; taken[best] = True
+        matches.append((int(kept[i]), best))
+    for b in dev.values():
+        b.free()
+    return matches
+
+
+
+def find_matches_transformed(ctx, kf, table, view, scale_factors_, scale_factor):
+    """findMatchesTranformedMps (keyframe_matcher.cpp:564-631) for a GATE_SIM3 view: per entry of view['indices'] the best keypoint of kf inside
+    the radius and the octave window [level - 1, level], accepted at <= 100, or -1."""
+    kept, ti, td, _, _, dev = _gate_then_topk(ctx, kf, table, view, scale_factors_, scale_factor, None)
+    out = np.full(len(np.asarray(view["indices"]).reshape(-1)), -1, np.int32)
+    ok = (ti[:, 0] >= 0) & (td[:, 0] <= MS_HAMMING_THR_HIGH)
+    out[kept[ok]] = ti[ok, 0]
+    for b in dev.values():
+        b.free()
+    return out
