@@ -19,6 +19,7 @@
 // x86-64 SSE2 scalar build (CMakeLists.txt:4-5: -O2, no -march).
 #include "ms_internal.h"
 #include "fast_tiles.h"
+#include "describe_lanes.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -26,7 +27,7 @@
 namespace {
 
 constexpr int kPatchRadius = MS_ORB_PATCH_RADIUS;   // 19
-constexpr int kHalfPatch = 15;                       // ORB_FAST_PATCH_HALF_SIZE
+using describe_lanes::kHalfPatch;                    // 15, ORB_FAST_PATCH_HALF_SIZE
 constexpr int kMaxQuota = 4096;                      // per-level selection capacity (LDS sort)
 
 struct LevelGeom {
@@ -1056,6 +1057,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     s_tab[64 + threadIdx.x] = reinterpret_cast<const uint4 *>(pattern_f)[threadIdx.x];
     const uint4 dm = moment_tab[lane];                       // disc mask of the lane's four patch dwords
     const uint32_t dmask[4] = {dm.x, dm.y, dm.z, dm.w};
+    const uint32_t wpack = reinterpret_cast<const uint32_t *>(moment_tab + 128)[lane];   // (row, byte) of the lane's first three window pieces (describe_lanes::win_pack)
     // the frame's keypoint total and this wave's table entry (k_slots): both addresses are known from the block index, one round trip
     const int total = out_count[f], nt = trk_count[f];
     const uint2 ent = slot_tab[(uint64_t)f * capacity + min(slot0, capacity - 1)];
@@ -1079,27 +1081,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
     }
     // ONE window of the (unblurred) level is copied into the wave's LDS slab with coalesced row loads: 45 rows x 48 B around the keypoint
-    // (x-23 .. x+24, y-22 .. y+22; 9 wave-wide dword loads).  It holds the 31 x 31 orientation patch (copied out once more with everything
-    // outside the radius-15 disc zeroed) AND everything the 39 x 39 BLURRED patch of the BRIEF tests depends on (19 + 3 pixels each way),
+    // (x-23 .. x+24, y-22 .. y+22; 9 wave-wide dword loads).  It holds the 31 x 31 orientation patch (each lane takes four of its dwords, with everything
+    // outside the radius-15 disc zeroed, into registers for the moments) AND everything the 39 x 39 BLURRED patch of the BRIEF tests depends on (19 + 3 pixels each way),
     // so the blur (image_pyramid.cpp:84: 7 x 7, sigma 2, REFLECT_101) is computed here, for the patch only, with k_blur's own arithmetic --
     // vertical pass on packed 16-bit lanes, horizontal pass with v_dot2 and one rounding -- and the blurred pyramid is no longer
     // written and read back for every frame (2 P bytes and a 0.49 ms kernel per 256-frame step; round 1 fetched 31 x 32 B of the level plus
     // 39 x 40 B of its blurred twin = 70 row pieces per keypoint, now 45).  k_blur still exists: ImagePyramid::getBlurredLevel runs it on demand.
-    __shared__ __attribute__((aligned(16))) uint32_t s_patch[4][kDescPerWave][45 * 12 + 32 * 8 + 4];   // window + orientation patch (a whole number of 16-byte units: the window rows are read as ds_read_b128); the blurred patch takes the window's place
+    __shared__ __attribute__((aligned(16))) uint32_t s_patch[4][kDescPerWave][45 * 12 + 32 * 8 + 4];   // the window (a whole number of 16-byte units: its rows are read as ds_read_b128); the blurred patch takes its place.  The 32 x 8 dwords behind it held a masked copy of the orientation patch until the moments were taken from registers: pass 1 of the blur still reads window "rows" 45 .. 47 there (zero weights), and the slab keeps its size and bank layout
     const int wv = threadIdx.x >> 6;
+    int m10[kDescPerWave], m01[kDescPerWave];
 #pragma unroll
     for (int k = 0; k < kDescPerWave; ++k) {
         const TileLevel GL = TL.L[K[k].oct];               // (kernel arguments: no load from the geometry table behind the level)
         const int pitch = K[k].oct == 0 ? src.lvl0_pitch : GL.pitch;
         const uint8_t *img = K[k].oct == 0 ? src.lvl0 + (uint64_t)f * src.lvl0_frame_stride : src.slab + (uint64_t)f * TL.slab_stride + GL.img_off;
         const int w = GL.w, h = GL.h, kx = K[k].x, ky = K[k].y;
-        uint32_t *win = &s_patch[wv][k][0], *pu = win + 45 * 12, *pb = win;      // (pass 1 of the blur has read the whole window into registers before pass 2 writes the first blurred dword)
+        uint32_t *win = &s_patch[wv][k][0], *pb = win;      // (pass 1 of the blur has read the whole window into registers before pass 2 writes the first blurred dword)
         if (kx >= 23 && kx + 24 < w && ky >= 22 && ky + 22 < h) {          // wave-uniform: the whole window lies inside the level
+            // piece t = 3 a + b is window dword lane + 64 t: the dword column of piece b, 16 a rows further down (describe_lanes.h).  Three lane offsets from
+            // the packed table (all >= 0: the uniform part of each address is the minimum of what the piece reads, §11 of DESIGN.md), three uniform row bases.
+            // The last piece exists for lanes 0 .. 27 only; the others fetch the first dword of its row base once more and park it behind the window (dwords
+            // 540 .. 575 of the slab, which nothing reads as data), so that all nine loads are in flight together: behind a lane test the ninth load was
+            // issued only after the first eight had returned -- one more round trip in every keypoint's chain.
             const uint8_t *corner = img + (int64_t)(ky - 22) * pitch + (kx - 23);
+            uint32_t off[3];
 #pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int i = lane + 64 * t, r = i / 12, c = i - 12 * r;
-                if (i < 45 * 12) win[i] = reinterpret_cast<const U32u *>(corner + (uint32_t)r * (uint32_t)pitch + 4u * c)->v;
+            for (int b = 0; b < 3; ++b) off[b] = __umul24((wpack >> (10 * b)) & 15u, (uint32_t)pitch) + ((wpack >> (10 * b + 4)) & 63u);
+#pragma unroll
+            for (int t = 0; t < describe_lanes::kWinPieces; ++t) {
+                const uint8_t *rows = corner + (uint32_t)(16 * (t / 3)) * (uint32_t)pitch;
+                win[lane + 64 * t] = reinterpret_cast<const U32u *>(rows + (describe_lanes::win_active(lane, t) ? off[t % 3] : 0u))->v;
             }
         } else {                                                          // a keypoint within 24 pixels of the border (a few per cent): BORDER_REFLECT_101 byte by byte
 #pragma unroll 1
@@ -1115,11 +1126,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        {   // orientation patch: rows y-15 .. y+15 = window rows 7 .., columns x-15 .. = window dword 2 ..; everything outside the radius-15 disc zeroed (the mask of
+            // the 32nd row is zero).  Patch dword lane + 64 t is 8 window rows below dword lane + 64 (t - 1): one lane base, four reads at constant offsets.
+            // O1: moments m10 = sum u I, m01 = sum v I over the disc (orb_extractor.cpp:245-275; integer sums, any order) on the lane's own four masked dwords,
+            // straight from the registers (describe_lanes::lane_moments: v_sad_u8 / v_dot4_u32_u8); the wave sums run under the blur's matrix products.
+            const uint32_t *ob = win + describe_lanes::ori_base(lane);
+            uint32_t d[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {                                   // orientation patch: rows y-15 .. y+15 = window rows 7 .., columns x-15 .. = window dword 2 ..;
-            const int i = lane + 64 * t, r = i >> 3, c4 = i & 7;        // everything outside the radius-15 disc zeroed (the mask of the 32nd row is zero)
-            const uint32_t v = i < 31 * 8 ? win[(r + 7) * 12 + c4 + 2] : 0u;
-            pu[i] = v & dmask[t];
+            for (int t = 0; t < 4; ++t) d[t] = (describe_lanes::ori_active(lane, t) ? ob[8 * describe_lanes::kWinDwords * t] : 0u) & dmask[t];
+            int p10, p01;
+            describe_lanes::lane_moments(d, describe_lanes::moment_col_weights(lane), describe_lanes::moment_row_bias(lane), p10, p01);
+            m10[k] = wave_sum(p10); m01[k] = wave_sum(p01);
         }
         {   // blurred patch rows y-19 .. y+19 (output row ro <- window rows ro .. ro+6), columns x-19 .. x+19 = window bytes 4 .. 42, ON THE MATRIX CORES (round 3):
             // a separable 7-tap filter is two products with banded constant matrices, out = V (P Hh), and every quantity of k_blur's fixed-point arithmetic is an
@@ -1136,12 +1153,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             // the VALU issue limit and the matrix pipe was idle.
             const int n = lane & 15, q = lane >> 4;
             // B operands of tile t: lane (n, kg) holds rows 16 kg .. + 15 of column 16 t + n -- non-zero only for kg - t = 0 or 1, and for columns <= 38
-            auto taps = [&](int base, int t) {
-                const int dt = q - t;
-                const bool on = (dt == 0 || dt == 1) && (t < 2 || n <= 6);
-                const uint4 zero4 = {0u, 0u, 0u, 0u};
-                return __builtin_bit_cast(v4i_t, on ? s_tab[base + (dt & 1) * 16 + n] : zero4);
-            };
+            // -- entry lane - 16 t of the table, or the table's all-zero entry: the lane selects the index, not the four dwords (describe_lanes::tap_slot)
+            auto taps = [&](int base, int t) { return __builtin_bit_cast(v4i_t, s_tab[base + describe_lanes::tap_slot(lane, t)]); };
             v4i_t Aw[3], Vb[3];                              // the window rows as pass 1's A operands (read BEFORE the first blurred dword takes the window's place), the vertical taps
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
@@ -1181,25 +1194,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // O1: moments m10 = sum u I, m01 = sum v I over the disc (orb_extractor.cpp:245-275; integer sums, any order).  Lane = one column
-    // u of one half of the rows (v = -15..0 | 1..16, the 32nd row is zero): 16 byte reads at constant offsets from one address,
-    // S = sum I and J = sum j I; then m10 = u S and m01 = J + v0 S.  The disc shape is already in the data (zeros outside).
-    const int half = lane >= 31 ? 1 : 0, col = lane - 31 * half;
     float angle_deg[kDescPerWave], ca[kDescPerWave], sa[kDescPerWave];
 #pragma unroll
     for (int k = 0; k < kDescPerWave; ++k) {
-        const uint8_t *colp = reinterpret_cast<const uint8_t *>(&s_patch[wv][k][45 * 12]) + half * (16 * 32) + col;
-        int S = 0, J = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int I = colp[j * 32];
-            S += I;
-            J += j * I;
-        }
-        int m10 = lane < 62 ? (col - kHalfPatch) * S : 0;
-        int m01 = lane < 62 ? J + (half ? 1 : -kHalfPatch) * S : 0;
-        m10 = wave_sum(m10); m01 = wave_sum(m01);
-        angle_deg[k] = dev_fast_atan2((float)m01, (float)m10);
+        angle_deg[k] = dev_fast_atan2((float)m01[k], (float)m10[k]);
         // float(angleDeg * M_PI / 180.0) in double (orb_extractor.cpp:286).  One multiplication by the double M_PI / 180.0 gives the same
         // float for EVERY float in [0, 361] (checked exhaustively, tests/test_oracle_frontend.py::test_degree_to_radian_constant_is_exact),
         // and it replaces a software double division per keypoint.
@@ -1435,33 +1433,18 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
         static const int8_t pattern[1024] = {
 #include "orb_pattern.inc"
         };
-        // disc mask of the 31 x 31 orientation patch as k_describe stages it: dword i = lane + 64 t covers columns 4 (i & 7) .. + 3 of row
+        // disc mask of the 31 x 31 orientation patch as k_describe's lanes hold it: dword i = lane + 64 t (the t-th of the lane) covers columns 4 (i & 7) .. + 3 of row
         // i >> 3; a byte is kept when |u| <= u_max[|v|] (orb_extractor.cpp:174-186, :259-271), the 32nd column and row are cleared
-        std::vector<uint32_t> mt(64 * 4, 0u);
+        std::vector<uint32_t> mt(64 * 4 + 64 * 4 + 64, 0u);
         for (int lane = 0; lane < 64; ++lane)
-            for (int t = 0; t < 4; ++t) {
-                const int i = lane + 64 * t, r = i >> 3, c4 = i & 7;
-                if (r >= 31) continue;
-                for (int b = 0; b < 4; ++b) {
-                    const int u = 4 * c4 + b - kHalfPatch, v = r - kHalfPatch;
-                    if (u <= kHalfPatch && std::abs(u) <= G.umax[std::abs(v)]) mt[lane * 4 + t] |= 0xFFu << (8 * b);
-                }
-            }
+            for (int t = 0; t < 4; ++t) mt[lane * 4 + t] = describe_lanes::disc_mask(lane, t, G.umax);
         // behind it, k_describe's blur as matrix operands (B of v_mfma_i32_16x16x64_i8: lane (n, kg) holds rows k = 16 kg .. + 15 of column 16 t + n, one byte each): the taps
         // 18 34 48 56 48 34 18 by patch column x -- window byte k contributes to x when 0 <= k - x - 1 <= 6 -- and by patch row y (window row k, 0 <= k - y <= 6).  Only
         // dt = kg - t = 0 and 1 can be non-zero, and the pattern depends on (dt, n) alone: [table 0 = horizontal, 1 = vertical][dt][n][4 dwords]
-        {
-            static const int w7[7] = {18, 34, 48, 56, 48, 34, 18};
-            mt.resize(64 * 4 + 64 * 4, 0u);
-            for (int tab = 0; tab < 2; ++tab)
-                for (int dt = 0; dt < 2; ++dt)
-                    for (int n = 0; n < 16; ++n)
-                        for (int j = 0; j < 16; ++j) {
-                            const int tap = 16 * dt + j - n - (tab == 0 ? 1 : 0);
-                            const uint32_t v = (tap >= 0 && tap <= 6) ? (uint32_t)w7[tap] : 0u;
-                            mt[64 * 4 + ((tab * 2 + dt) * 16 + n) * 4 + j / 4] |= v << (8 * (j % 4));
-                        }
-        }
+        // (describe_lanes::tap_table; entry [1][0] of either table is all zero and serves as the zero operand), and behind that the packed (row, byte) of every lane's
+        // first three window pieces
+        describe_lanes::tap_table(&mt[64 * 4]);
+        for (int lane = 0; lane < 64; ++lane) mt[64 * 4 + 64 * 4 + lane] = describe_lanes::win_pack(lane);
         std::vector<float> pf(1024);
         for (int i = 0; i < 1024; ++i) pf[i] = (float)pattern[i];
         if (hipMalloc(reinterpret_cast<void **>(&o->d_moment_tab), mt.size() * 4) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&o->d_pattern_f), pf.size() * 4) != hipSuccess ||
