@@ -203,6 +203,10 @@ int ms_orb_download_level(ms_orb *orb, int frame, int level, int blurred, uint8_
 /* FeatureDetector::detect (feature_detector.cpp:20-28): per-level detector output of the last batch
  * BEFORE orientation: integer level coordinates + FAST score, `*n` points (<= quota of the level). */
 int ms_orb_download_detections(ms_orb *orb, int frame, int level, int32_t *x, int32_t *y, int32_t *score, int32_t *n);
+/* How many candidates (3x3 non-maximum-suppressed corners) the detector appended per (frame, level) in the last ms_orb_extract, BEFORE the selection.
+ * Within a batch the detector raises a tile's threshold to the score that the level's quota already excludes, so these counts are at most the number
+ * of NMS maxima above fast_threshold and vary from run to run; the selected keypoints do not.  A one-frame call finds all of them. */
+int ms_orb_last_candidate_counts(ms_orb *orb, int32_t *out /* [n_frames * levels] */);
 
 /* ---------------------------------------------------------------------------------------------
  * Descriptor matching -- the scoring core of keyframe_matcher.cpp (compute_descriptor_distance_32,

@@ -64,7 +64,8 @@ __device__ __forceinline__ int tile_level(const TileMap &tm, int levels, int t) 
 
 // What the tiled kernels (k_blur, k_fast) need about a level, also BY VALUE in the kernel arguments: one batch of scalar loads from the
 // kernel-argument segment once the block knows its level, instead of a chain of dependent loads from the geometry table behind branches.
-struct TileLevel { int32_t w, h, pitch, btiles_x, cand_cap; uint32_t btiles_inv; uint64_t img_off, blur_off, cand_off; float scale; int32_t det_base; };
+struct TileLevel { int32_t w, h, pitch, btiles_x, cand_cap; uint32_t btiles_inv; uint64_t img_off, blur_off, cand_off; float scale; int32_t det_base;
+                   int32_t sel_k; };     // sel_k: how many of the level's strongest candidates k_select looks at (its `want`)
 struct TileLevels { TileLevel L[MS_MAX_LEVELS]; uint64_t slab_stride, cand_stride; int32_t levels, fast_threshold; };
 
 struct FrameSrc {          // where pyramid level 0 lives for this call
@@ -102,6 +103,7 @@ struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
 struct __attribute__((packed, aligned(1))) U64u { uint32_t lo, hi; };
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 typedef short s2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 // Everything k_resize needs about its two levels, by value in the kernel arguments: the launch is per level, and reading the
 // geometry table instead put nine dependent scalar round trips in front of every wave's first pixel load.
@@ -454,6 +456,7 @@ __global__ __launch_bounds__(256) void k_blur(FrameSrc src, TileLevels TL, TileM
 //             ((255-score)<<24 | y*w+x) with ONE global atomic per tile
 constexpr int kFastWaves = 8, kFastThreads = 64 * kFastWaves;     // waves per tile: 4 position rows each
 constexpr int kFastSeg = 248, kFastRows = 4 * kFastWaves - 2, kFastPosRows = kFastRows + 2, kFastRowsPerWave = 4;
+constexpr int kFastPruneMinBlocks = 2 * 4 * 256;               // launches with more workgroups than this learn a raised threshold (k_fast)
 constexpr int kFastPositions = kFastPosRows * (kFastSeg + 2);   // scored positions of a tile: columns 3..252 of its position rows
 
 __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) {
@@ -523,19 +526,24 @@ __device__ __forceinline__ s2_t pk_mad(uint32_t s, uint32_t r, uint32_t k) {
 // One tile in the lane layout S (fast_tiles.h): a wave's 64 dword-lanes are S sub-rows of LW = 64 / S lanes, group g = S wave + lane / LW owns
 // position rows 4g .. 4g+3 of the tile and a lane the dword column cl = lane mod LW.  S = 1 is the wide tile with its scalar row addresses; for
 // S = 2 and 4 (the narrow remainder columns of a level) the row index is per lane and every wave takes the clamped border loads.
-template <int S>
-__device__ __forceinline__ void fast_tile(const FrameSrc &src, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count, const TileLevels &TL,
+template <int S, bool PRUNE>
+__device__ __forceinline__ void fast_tile(const FrameSrc &src, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count, uint32_t *score_hist, const TileLevels &TL,
                                           const TileLevel &G, const int l, const int X0, const int Y0,
-                                          uint8_t *s_sc, uint16_t *s_pre, uint8_t *s_pix, int *s_np, int *s_m, int *s_base) {
+                                          uint8_t *s_sc, uint16_t *s_pre, uint8_t *s_pix, int *s_np, int *s_m, int *s_base, int *s_thr) {
     constexpr int LW = 64 / S, TW = 256 / S;                   // lanes and bytes of a tile row
     constexpr int kOutRows = kFastPosRows * S - 2;             // 30, 62 or 126 output rows
     uint32_t *s_out = reinterpret_cast<uint32_t *>(s_pix);              // (rows + 6) * LW keys >= (TW - 8) / 2 * (rows / 2) possible NMS survivors
-    const int f = blockIdx.y, w = G.w, h = G.h, thr = TL.fast_threshold;
+    const int f = PRUNE ? blockIdx.x : blockIdx.y, w = G.w, h = G.h;
     const int pitch = l == 0 ? src.lvl0_pitch : G.pitch;
     const uint8_t *img = l == 0 ? src.lvl0 + (uint64_t)f * src.lvl0_frame_stride : src.slab + (uint64_t)f * TL.slab_stride + G.img_off;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform, in an SGPR: row addresses stay scalar
     const int cl = S == 1 ? lane : (lane & (LW - 1));          // the lane's dword column
     const int grp = S == 1 ? wave : S * wave + lane / LW;      // its group of 4 position rows (wave-uniform for S = 1)
+    // The level's score histogram (see k_fast) is requested by wave 0 in front of its rows (the last wave has the six extra rows to fetch): one 16-byte
+    // load per lane, 4 bins each, past the CU's L1 (sc1), so what other tiles have added during this launch is seen.
+    uint32_t *hbin = PRUNE ? score_hist + ((size_t)(f * TL.levels + l) << 8) : nullptr;
+    u32x4_t hq = {0u, 0u, 0u, 0u};
+    if (PRUNE && wave == 0) hq = __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc(hbin, 0, 1024, 0x00020000), 16 * lane, 0, 16 /* sc1 */);
     // The wave's 10 image rows are requested FIRST, so their latency runs under the LDS clear and the barrier.
     const int x = X0 - 4 + 4 * cl;
     uint32_t rows[kFastRowsPerWave + 6];
@@ -560,7 +568,20 @@ __device__ __forceinline__ void fast_tile(const FrameSrc &src, uint32_t *__restr
 #pragma unroll
     for (int r = 0; r < kFastRowsPerWave + 6; ++r)
         if (r < kFastRowsPerWave || grp == kFastWaves * S - 1) reinterpret_cast<uint32_t *>(s_pix)[(grp * kFastRowsPerWave + r) * LW + cl] = rows[r];
+    // The tile's threshold: sigma = the largest s >= threshold with at least sel_k known candidates of score > s, else the configured threshold.
+    // n(s) = sum of the bins above s falls with s, so the lanes whose FIRST bin still has n >= sel_k are a prefix of the wave and the last of them
+    // holds sigma among its four bins.
+    if (PRUNE && wave == 0) {
+        const int K = G.sel_k;
+        const int incl = wave_scan_add((int)(hq.x + hq.y + hq.z + hq.w));
+        const int n3 = __builtin_amdgcn_readlane(incl, 63) - incl, n2 = n3 + (int)hq.w, n1 = n2 + (int)hq.z, n0 = n1 + (int)hq.y;     // n(4 lane + i)
+        const unsigned long long reach = __ballot(n0 >= K);
+        const int top = reach ? 63 - __clzll((long long)reach) : 0;
+        const int sigma = 4 * lane + (n3 >= K ? 3 : n2 >= K ? 2 : n1 >= K ? 1 : 0);
+        if (lane == top) *s_thr = (reach && K > 0) ? max(TL.fast_threshold, sigma) : TL.fast_threshold;
+    }
     __syncthreads();
+    const int thr = PRUNE ? __builtin_amdgcn_readfirstlane(*s_thr) : TL.fast_threshold;
     // ---- phase A1: position rows pr = 4 grp .. 4 grp + 3  <->  image rows Y0-1+pr; columns X0-4+4*cl .. +3
     {
         const uint32_t T2 = (uint32_t)thr * 0x00010001u;
@@ -684,7 +705,10 @@ __device__ __forceinline__ void fast_tile(const FrameSrc &src, uint32_t *__restr
         const int sc = sp[0];
         const bool keep = sc > sp[-TW - 1] && sc > sp[-TW] && sc > sp[-TW + 1] && sc > sp[-1] &&
                           sc > sp[1] && sc > sp[TW - 1] && sc > sp[TW] && sc > sp[TW + 1];
-        if (keep) s_out[atomicAdd(s_m, 1)] = ((uint32_t)(255 - sc) << 24) | (uint32_t)(y * w + px);
+        if (keep) {
+            s_out[atomicAdd(s_m, 1)] = ((uint32_t)(255 - sc) << 24) | (uint32_t)(y * w + px);
+            if (PRUNE) (void)__hip_atomic_fetch_add(hbin + sc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // result unused: no return value to wait for
+        }
     }
     __syncthreads();
     const int m = *s_m;
@@ -697,23 +721,38 @@ __device__ __forceinline__ void fast_tile(const FrameSrc &src, uint32_t *__restr
     }
 }
 
-__global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count,
+//
+// The threshold a tile works with is raised by what the launch has already found.  k_select looks at the sel_k strongest
+// candidates of a (frame, level) only, and keys order by score first: once sel_k candidates of score > sigma are known, no candidate of score
+// <= sigma can be selected, so a tile may run ALL of FAST with max(threshold, sigma).  Every candidate above it is still found, and its NMS
+// outcome is the same (only a strictly greater neighbour suppresses it, and that one is above the raised threshold too); ties at the cut are
+// safe because the count is of STRICTLY greater scores.  The known candidates are a histogram of 256 score bins per (frame, level): phase C adds
+// every candidate it appends (the tile's own outputs inside the image, never the halo), k_select zeroes the bins when it consumes the level,
+// nothing is carried from one call to the next.  Bins only grow during a launch, so a stale or torn read is a lower bound of every bin and gives
+// a sigma that is merely smaller: still exact.  The grid runs the frame as its FASTEST dimension: a frame's tiles then start one after another
+// (about resident workgroups / frames at a time), and later tiles see what earlier ones found.
+// PRUNE = false is the kernel without any of this, in the tile-fastest launch shape: a launch whose workgroups (nearly) all start together has nothing to
+// learn from -- a single frame, a few frames -- and must not pay for the bin load, the scan, the atomics and k_select's zeroing (frame by frame, eight
+// sequences side by side, they cost 12 % of the frame rate).  The host's rule (orb_enqueue_kernels): prune when the launch has more than kFastPruneMinBlocks
+// workgroups.
+template <bool PRUNE>
+__global__ __launch_bounds__(kFastThreads) void k_fast(FrameSrc src, uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count, uint32_t *score_hist,
                                               const uint2 *__restrict__ tile_tab, TileLevels TL) {
     __shared__ __attribute__((aligned(16))) uint8_t s_sc[kFastPosRows * 256];        // score tile, [32 S][256 / S] (the outermost two columns are never touched)
     __shared__ __attribute__((aligned(16))) uint16_t s_pre[kFastPositions + 8];     // compass survivors (+ dump slot); each wave's corners overwrite its own consumed slots
     __shared__ __attribute__((aligned(16))) uint8_t s_pix[(kFastPosRows + 6) * 256]; // the tile's pixels, [32 S + 6][256 / S] (image rows Y0-4 ..) for the ring reads; NMS keys afterwards
-    __shared__ int s_np, s_m, s_base;
+    __shared__ int s_np, s_m, s_base, s_thr;
     // The scalar unit is shared by the CU's four SIMDs and every wave of a tile repeats the tile's scalar work, so that work is kept
     // short: the tile's level, layout and first output column / row come from a host-built table (one scalar load instead of a 15-step
     // search and a division), and the ten row addresses of an interior wave are one 64-bit base plus the pitch (2 scalar adds per row
     // instead of two clamps, a 64-bit multiply and an add).
-    const uint2 te = tile_tab[blockIdx.x];             // level | S << 4,  X0 | Y0 << 16
+    const uint2 te = tile_tab[PRUNE ? blockIdx.y : blockIdx.x];             // level | S << 4,  X0 | Y0 << 16
     const int l = (int)(te.x & 15u), X0 = (int)(te.y & 0xFFFFu), Y0 = (int)(te.y >> 16);
     const TileLevel G = TL.L[l];                       // one batch of loads; everything below is arithmetic on it
     const uint32_t S = te.x >> 4;
-    if (S == 1u) fast_tile<1>(src, cand, cand_count, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base);         // one wave-uniform branch
-    else if (S == 2u) fast_tile<2>(src, cand, cand_count, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base);
-    else fast_tile<4>(src, cand, cand_count, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base);
+    if (S == 1u) fast_tile<1, PRUNE>(src, cand, cand_count, score_hist, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base, &s_thr);         // one wave-uniform branch
+    else if (S == 2u) fast_tile<2, PRUNE>(src, cand, cand_count, score_hist, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base, &s_thr);
+    else fast_tile<4, PRUNE>(src, cand, cand_count, score_hist, TL, G, l, X0, Y0, s_sc, s_pre, s_pix, &s_np, &s_m, &s_base, &s_thr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -735,7 +774,7 @@ template <bool SPACED, int NTH>   // SPACED: some level has a minimum keypoint d
 __global__ __launch_bounds__(NTH) void k_select(const PyrGeom *g, const uint32_t *__restrict__ cand, int32_t *__restrict__ cand_count,
                                                 const uint8_t *__restrict__ valid_mask,
                                                 int16_t *__restrict__ det_x, int16_t *__restrict__ det_y, uint8_t *__restrict__ det_score,
-                                                int32_t *__restrict__ det_count) {
+                                                int32_t *__restrict__ det_count, uint32_t *__restrict__ score_hist, int32_t *__restrict__ last_count) {
     __shared__ uint32_t s_key[kMaxQuota];
     __shared__ int s_hist[256];
     __shared__ int s_cnt, s_digit, s_k, s_run, s_kept, s_open;
@@ -744,7 +783,8 @@ __global__ __launch_bounds__(NTH) void k_select(const PyrGeom *g, const uint32_t
     const int l = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
     const LevelGeom &G = g->L[l];
     const uint32_t *keys = cand + (uint64_t)f * g->cand_stride + G.cand_off;
-    const int n = min(cand_count[f * g->levels + l], G.cand_cap), n4 = n >> 2;
+    const int n_found = cand_count[f * g->levels + l];
+    const int n = min(n_found, G.cand_cap), n4 = n >> 2;
     const uint4 *keys4 = reinterpret_cast<const uint4 *>(keys);          // (every level's list starts 16-byte aligned: cand_cap is a multiple of 4)
     const int quota = G.quota, min_dist = G.min_dist;
     const bool spaced = SPACED && min_dist >= 2;
@@ -912,7 +952,8 @@ __global__ __launch_bounds__(NTH) void k_select(const PyrGeom *g, const uint32_t
         if (tid == 0) { s_run = run + out_chunk; s_kept = kept_before + kept_chunk; }
         __syncthreads();
     }
-    if (tid == 0) { det_count[f * g->levels + l] = s_run; cand_count[f * g->levels + l] = 0; }      // the list is consumed: k_fast of the next extract appends from zero (no memset launch per call)
+    if (tid == 0) { det_count[f * g->levels + l] = s_run; last_count[f * g->levels + l] = n_found; cand_count[f * g->levels + l] = 0; }      // the list is consumed: k_fast of the next extract appends from zero (no memset launch per call)
+    if (score_hist && n_found > 0 && tid < 256) score_hist[((size_t)(f * g->levels + l) << 8) + tid] = 0;       // and so are the level's score bins (k_fast's raised threshold; null when the launch did not prune): nothing is carried into the next call
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1245,7 +1286,9 @@ struct ms_orb {
     uint8_t *d_slab = nullptr;
     uint32_t *d_cand = nullptr;
     int32_t *d_cand_count = nullptr, *d_det_count = nullptr, *d_trk_count = nullptr;
-    size_t cand_count_bytes = 0;
+    size_t cand_count_bytes = 0, score_hist_bytes = 0;
+    uint32_t *d_score_hist = nullptr;  // k_fast: 256 score bins per (frame, level) of the candidates found so far in the launch; zero between calls
+    int32_t *d_last_count = nullptr;   // candidates k_fast appended per (frame, level) in the last call (ms_orb_last_candidate_counts)
     int16_t *d_det_x = nullptr, *d_det_y = nullptr, *d_trk_x = nullptr, *d_trk_y = nullptr;
     uint8_t *d_det_score = nullptr, *d_mask = nullptr;
     float *d_trk_px = nullptr, *d_trk_py = nullptr, *d_track_xy = nullptr;
@@ -1373,11 +1416,16 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
         }
     }
     G.ftiles_total = (int)ftab.size();
+    if (ftab.size() > 65535) {                           // the tile index is k_fast's grid y
+        delete o;
+        return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: %zu detector tiles per frame (max 65535)", ftab.size());
+    }
     G.det_stride = std::max(cfg->max_kpts, det_base);       // the reference keeps per-level vectors, so a frame can hold sum(quota) > maxKeypoints points
     G.capacity = G.det_stride + cfg->max_tracks;
     for (int l = 0; l < cfg->levels; ++l) {
         const LevelGeom &L = G.L[l];
-        o->tile_levels.L[l] = TileLevel{L.w, L.h, L.pitch, L.btiles_x, L.cand_cap, L.btiles_inv, L.img_off, L.blur_off, L.cand_off, L.scale, L.det_base};
+        const int sel_k = (cfg->min_distance > 0.f && L.min_dist >= 2) ? std::min(4 * L.quota, kMaxQuota) : L.quota;     // k_select's `want`
+        o->tile_levels.L[l] = TileLevel{L.w, L.h, L.pitch, L.btiles_x, L.cand_cap, L.btiles_inv, L.img_off, L.blur_off, L.cand_off, L.scale, L.det_base, sel_k};
     }
     for (int l = 0; l <= MS_MAX_LEVELS; ++l) o->blur_tiles.base[l] = l < cfg->levels ? G.L[l].btile_base : bt;
     G.slab_stride = ms_align_up(off, 256); G.cand_stride = coff;
@@ -1391,6 +1439,9 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
     A(dev_calloc(ctx, &o->d_cand, B * G.cand_stride));
     A(dev_calloc(ctx, &o->d_cand_count, B * MS_MAX_LEVELS));
     o->cand_count_bytes = sizeof(int32_t) * B * MS_MAX_LEVELS;
+    A(dev_calloc(ctx, &o->d_score_hist, B * MS_MAX_LEVELS * 256));
+    o->score_hist_bytes = sizeof(uint32_t) * B * MS_MAX_LEVELS * 256;
+    A(dev_calloc(ctx, &o->d_last_count, B * MS_MAX_LEVELS));
     A(dev_calloc(ctx, &o->d_det_count, B * MS_MAX_LEVELS));
     A(dev_calloc(ctx, &o->d_trk_count, B));
     A(dev_calloc(ctx, &o->d_det_x, B * (size_t)G.det_stride));
@@ -1470,7 +1521,7 @@ void ms_orb_destroy(ms_orb *o) {
     if (!o) return;
     (void)hipSetDevice(o->ctx->device);
     (void)hipStreamSynchronize(o->ctx->stream);
-    void *ptrs[] = {o->d_geom, o->d_slab, o->d_cand, o->d_cand_count, o->d_det_count, o->d_trk_count, o->d_det_x, o->d_det_y,
+    void *ptrs[] = {o->d_geom, o->d_slab, o->d_cand, o->d_cand_count, o->d_score_hist, o->d_last_count, o->d_det_count, o->d_trk_count, o->d_det_x, o->d_det_y,
                     o->d_det_score, o->d_mask, o->d_trk_x, o->d_trk_y, o->d_trk_px, o->d_trk_py, o->d_trk_id, o->d_track_xy,
                     o->d_track_id, o->d_n_tracks, o->d_x, o->d_y, o->d_angle, o->d_octave, o->d_track, o->d_count, o->d_desc, o->d_slot_tab};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1539,7 +1590,10 @@ int ms_orb_extract(ms_orb *o, const uint8_t *images, int on_device, int n_frames
     bool counters_dirty = false;
     const int rc = orb_extract_enqueue(o, images, on_device, n_frames, frame_stride, row_stride, track_xy, track_id, n_tracks, counters_dirty);
     // k_fast fills the candidate counters and k_select puts them back to zero; a call that fails in between must not leave them to the next one
-    if (rc != MS_OK && counters_dirty) (void)hipMemsetAsync(o->d_cand_count, 0, o->cand_count_bytes, o->ctx->stream);
+    if (rc != MS_OK && counters_dirty) {
+        (void)hipMemsetAsync(o->d_cand_count, 0, o->cand_count_bytes, o->ctx->stream);
+        (void)hipMemsetAsync(o->d_score_hist, 0, o->score_hist_bytes, o->ctx->stream);
+    }
     return rc;
 }
 
@@ -1552,7 +1606,11 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     const size_t F = (size_t)f0, T = (size_t)o->cfg.max_tracks, L = (size_t)G.levels;
     src.lvl0 += F * src.lvl0_frame_stride; src.slab += F * G.slab_stride;
     uint32_t *cand = o->d_cand + F * G.cand_stride;
-    int32_t *cand_count = o->d_cand_count + F * L, *det_count = o->d_det_count + F * L, *trk_count = o->d_trk_count + F;
+    int32_t *cand_count = o->d_cand_count + F * L, *det_count = o->d_det_count + F * L, *trk_count = o->d_trk_count + F, *last_count = o->d_last_count + F * L;
+    // k_fast learns a raised threshold from its own launch only where a frame's tiles run at different times: with more workgroups than twice what the
+    // device holds at once (4 per CU on 256 CUs).  Below that (nearly) all tiles start before any has finished; they run the plain kernel, tile-fastest.
+    const bool prune = (long long)nf * G.ftiles_total > kFastPruneMinBlocks;
+    uint32_t *score_hist = prune ? o->d_score_hist + F * L * 256 : nullptr;
     int16_t *det_x = o->d_det_x + F * G.det_stride, *det_y = o->d_det_y + F * G.det_stride;
     uint8_t *det_score = o->d_det_score + F * G.det_stride;
     int stage = 0;
@@ -1580,16 +1638,17 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     MS_STAGE_MARK();
     MsRange detect_range("detect");
     counters_dirty = true;
-    hipLaunchKernelGGL(k_fast, dim3(G.ftiles_total, nf), dim3(kFastThreads), 0, st, src, cand, cand_count, o->d_ftile_tab, o->tile_levels);
+    if (prune) hipLaunchKernelGGL(k_fast<true>, dim3(nf, G.ftiles_total), dim3(kFastThreads), 0, st, src, cand, cand_count, score_hist, o->d_ftile_tab, o->tile_levels);     // frame fastest: see k_fast
+    else hipLaunchKernelGGL(k_fast<false>, dim3(G.ftiles_total, nf), dim3(kFastThreads), 0, st, src, cand, cand_count, score_hist, o->d_ftile_tab, o->tile_levels);
     MS_KERNEL_CHECK(c, "k_fast");
     MS_STAGE_MARK();
     const bool few = nf * G.levels <= 64;                           // a frame or a handful: one block per level is the whole launch -- give it 1024 threads
     if (o->cfg.min_distance > 0.f) {
-        if (few) hipLaunchKernelGGL((k_select<true, 1024>), dim3(G.levels, nf), dim3(1024), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count);
-        else hipLaunchKernelGGL((k_select<true, 256>), dim3(G.levels, nf), dim3(256), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count);
+        if (few) hipLaunchKernelGGL((k_select<true, 1024>), dim3(G.levels, nf), dim3(1024), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count, score_hist, last_count);
+        else hipLaunchKernelGGL((k_select<true, 256>), dim3(G.levels, nf), dim3(256), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count, score_hist, last_count);
     } else {
-        if (few) hipLaunchKernelGGL((k_select<false, 1024>), dim3(G.levels, nf), dim3(1024), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count);
-        else hipLaunchKernelGGL((k_select<false, 256>), dim3(G.levels, nf), dim3(256), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count);
+        if (few) hipLaunchKernelGGL((k_select<false, 1024>), dim3(G.levels, nf), dim3(1024), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count, score_hist, last_count);
+        else hipLaunchKernelGGL((k_select<false, 256>), dim3(G.levels, nf), dim3(256), 0, st, o->d_geom, cand, cand_count, o->d_mask, det_x, det_y, det_score, det_count, score_hist, last_count);
     }
     MS_KERNEL_CHECK(c, "k_select");
     counters_dirty = false;
@@ -1752,6 +1811,15 @@ int ms_orb_download(ms_orb *o, int frame, float *x, float *y, float *angle, int3
     if (desc) MS_HIP(c, hipMemcpy(desc, o->d_desc + b * 8, k * 32, hipMemcpyDeviceToHost));
     if (track_id) MS_HIP(c, hipMemcpy(track_id, o->d_track + b, k * 4, hipMemcpyDeviceToHost));
     *n = cnt;
+    return MS_OK;
+}
+
+int ms_orb_last_candidate_counts(ms_orb *o, int32_t *out) {
+    if (!o || !out) return MS_ERR_INVALID;
+    ms_ctx *c = o->ctx;
+    if (o->last_frames < 1) return ms_fail(c, MS_ERR_INVALID, "ms_orb_last_candidate_counts: nothing ran");
+    MS_HIP(c, hipStreamSynchronize(c->stream));
+    MS_HIP(c, hipMemcpy(out, o->d_last_count, sizeof(int32_t) * (size_t)o->last_frames * o->geom.levels, hipMemcpyDeviceToHost));
     return MS_OK;
 }
 

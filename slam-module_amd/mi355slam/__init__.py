@@ -356,6 +356,12 @@ class OrbExtractor:
         self.ctx.check(lib().ms_orb_download_detections(self._h, frame, level, _vp(x), _vp(y), _vp(s), C.byref(n)), "ms_orb_download_detections")
         return x[:n.value].copy(), y[:n.value].copy(), s[:n.value].copy()
 
+    def last_candidate_counts(self):
+        """Candidates the detector appended per (frame, level) in the last extract, before the selection: int32 [n_frames, levels]."""
+        out = np.zeros((self.n_frames, self.cfg.levels), np.int32)
+        self.ctx.check(lib().ms_orb_last_candidate_counts(self._h, _vp(out)), "ms_orb_last_candidate_counts")
+        return out
+
     def close(self):
         if self._h and self.ctx._h:
             lib().ms_orb_destroy(self._h)
