@@ -515,6 +515,57 @@ int ms_project_gate(ms_ctx *ctx,
     /* HOST [n_views] */
     int32_t *n_kept);
 
+/* ---- the writers of the map-point table --------------------------------------------------------------------------------
+ * ms_map_refresh: MapPoint::updateDescriptor and MapPoint::updateDistanceAndNorm (map_point.cpp:75-116, :158-172) for chosen rows of the table
+ * ms_project_gate reads, written where the table lies -- what mapper_helpers.cpp:1062-1077 runs for the map points of a new keyframe.
+ * Entry r refreshes table row rows[r] from its observations obs_start[r] .. obs_start[r + 1], listed in the reference's iteration order
+ * (ascending KfId; the first one is getFirstObservation()): obs_kf = the observing keyframe's slot in kf_pose ([n_kf * 12] doubles, rows 0-2
+ * of poseCW, row-major), obs_desc = the observing keypoint's descriptor in desc_pool ([n_pool * 8]) or -1 for a keyframe without descriptors
+ * (:80), first_octave[r] = the octave of the first observation's keypoint (:168).
+ *   normal   = float(sum over the list, left to right, of (c - p).normalized() in float64) / float(n), c = -R^T t summed left to right; the
+ *              squared norm is x^2 + (y^2 + z^2), a zero vector stays as it is
+ *   max dist = float(|c_0 - p|) * sf[octave], min dist = (float(|c_0 - p|) * sf[octave]) / sf[n_levels - 1], in float32
+ *   descriptor = the list's median-Hamming medoid (ms_descriptor_medoid on the observations that have a descriptor)
+ * every operation rounded once, in one order: the result does not depend on the launch shape.  desc_pool == NULL or obs_desc == NULL skips
+ * the descriptor half.  medoid (HOST, [n_rows], may be NULL): the chosen observation's position in the row's list, -1 when no observation has a
+ * descriptor (the row keeps its descriptor, :86), -2 when more than MS_MEDOID_MAX_OBS have one (the row keeps its descriptor; normal and
+ * distances are refreshed all the same).  Synchronous: one upload, five launches (two without descriptors), at most one download; the
+ * workspace belongs to the context and only grows.  mp_desc and desc_pool are 16-byte aligned.
+ * MS_ERR_INVALID, with nothing written and before any device call: a row, slot or pool index out of range, a row listed twice, obs_start not
+ * starting at 0 or decreasing, an empty list (the reference asserts), an octave outside [0, n_levels), a missing array.  n_rows = 0 is fine.
+ * ms_map_refresh_check is that validation alone (no context, no device; `why` receives the message). */
+int ms_map_refresh(ms_ctx *ctx,
+    /* map-point table, DEVICE: mp_pos is read, the others are written */
+    const double *mp_pos, float *mp_norm, float *mp_min_dist, float *mp_max_dist, uint32_t *mp_desc, int n_mp,
+    /* DEVICE */
+    const double *kf_pose, int n_kf, const uint32_t *desc_pool /* may be NULL */, int n_pool,
+    /* HOST */
+    const int32_t *rows, int n_rows, const int32_t *obs_start, const int32_t *obs_kf, const int32_t *obs_desc /* may be NULL */,
+    const int32_t *first_octave, const float *scale_factors, int n_levels,
+    /* HOST [n_rows], may be NULL */
+    int32_t *medoid);
+int ms_map_refresh_check(const double *mp_pos, const float *mp_norm, const float *mp_min_dist, const float *mp_max_dist, const uint32_t *mp_desc,
+                         int n_mp, const double *kf_pose, int n_kf, const uint32_t *desc_pool, int n_pool, const int32_t *rows, int n_rows,
+                         const int32_t *obs_start, const int32_t *obs_kf, const int32_t *obs_desc, const int32_t *first_octave,
+                         const float *scale_factors, int n_levels, char *why, size_t why_bytes);
+
+/* ms_loop_correct: the pose correction and map-point transfer of LoopCloser::correctLoop (loop_closer.cpp:398-503) on the pose table and the
+ * map-point positions, both DEVICE and updated in place.  T = the Sim3 of :405 as 8 HOST doubles: unit quaternion w, x, y, z, translation,
+ * scale.  Keyframe entry i corrects pose kf_slot[i]: pose <- sim3ToSe3(se3ToSim3(pose) * Tl) with Tl = T where kf_rigid[i] (:427) and
+ * interpolateSim3(identity, T, kf_lambda[i]) otherwise (:458-463: Eigen's slerp with its linear branch for |d| >= 1 - eps and the sign flip
+ * for d < 0, linear translation and scale; the scale is dropped by sim3ToSe3).  Point entry j moves row mp_row[j] with its reference keyframe,
+ * entry mp_ref[j] of kf_slot (the localMapPoints value): p <- (corrected^-1 * previous).map(p), both with scale 1 (:500-503).  The Sim3
+ * algebra is mi355slam::Sim3's (host/mi355slam/optimize_transform.hpp), operation for operation.  Two launches, synchronous, deterministic.
+ * MS_ERR_INVALID, with nothing written and before any device call: a slot, row or reference out of range, a slot or row listed twice, a
+ * lambda that is read and is not in [0, 1], a T that is not finite, a missing array.  ms_loop_correct_check is that validation alone. */
+int ms_loop_correct(ms_ctx *ctx, double *kf_pose, int n_kf, double *mp_pos, int n_mp,
+    /* HOST */
+    const double *T, const int32_t *kf_slot, const uint8_t *kf_rigid, const double *kf_lambda, int n_corr,
+    const int32_t *mp_row, const int32_t *mp_ref, int n_pts);
+int ms_loop_correct_check(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const double *T, const int32_t *kf_slot,
+                          const uint8_t *kf_rigid, const double *kf_lambda, int n_corr, const int32_t *mp_row, const int32_t *mp_ref, int n_pts,
+                          char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

@@ -148,6 +148,8 @@ void ms_ctx_destroy(ms_ctx *c) {
     if (c->s3_host) (void)hipHostFree(c->s3_host);
     if (c->pg_dev) (void)hipFree(c->pg_dev);
     if (c->pg_host) (void)hipHostFree(c->pg_host);
+    if (c->mr_dev) (void)hipFree(c->mr_dev);
+    if (c->mr_host) (void)hipHostFree(c->mr_host);
     for (auto &b : c->ba_cache) if (b.p) (void)hipFree(b.p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

@@ -45,6 +45,9 @@ struct ms_ctx {
     // ms_project_gate's workspace (project_gate.hip): device tables / ranks / offsets and their page-locked staging, grow-only
     void *pg_dev = nullptr, *pg_host = nullptr;
     size_t pg_dev_bytes = 0, pg_host_bytes = 0;
+    // ms_map_refresh's and ms_loop_correct's workspace (map_refresh.hip): device lists / centres / packed descriptors / previous poses and their page-locked staging, grow-only
+    void *mr_dev = nullptr, *mr_host = nullptr;
+    size_t mr_dev_bytes = 0, mr_host_bytes = 0;
     char err[512] = {0};
 };
 

@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <utility>
 #include "common.hpp"
+#include "optimize_transform.hpp"
 
 namespace mi355slam {
 
@@ -418,8 +419,62 @@ inline unsigned matchMapPointsSim3(Context &ctx, const DeviceKeyframe &kf1, cons
 // query block of ms_projection_topk: no query array is built or uploaded by the host.  What reads the map graph stays with the caller
 // (observations.count, the BAD / NOT_TRIANGULATED test, erasedMapPointIds): it passes the rows that survive those filters, in walk order.
 
+// Keyframe poses on the device, one slot per keyframe: rows 0-2 of poseCW, row-major (12 doubles).  What ms_map_refresh reads the camera
+// centres from and ms_loop_correct corrects in place.  update() re-uploads a range after the host changed poses (bundle adjustment).
+class DeviceKeyframePoses {
+public:
+    using Pose = std::array<double, 12>;
+    DeviceKeyframePoses(Context &ctx, const std::vector<Pose> &poseCW) : ctx_(ctx), n_(poseCW.size()) {
+        ctx_.check(ms_dev_alloc(ctx_.get(), 96 * n_ + 16, &pose_), "ms_dev_alloc");
+        update(0, n_, poseCW.data());
+    }
+    ~DeviceKeyframePoses() { ms_dev_free(ctx_.get(), pose_); }
+    DeviceKeyframePoses(const DeviceKeyframePoses &) = delete;
+    void update(std::size_t first, std::size_t count, const Pose *poseCW) {
+        if (first + count > n_) throw std::runtime_error("DeviceKeyframePoses::update: range outside the table");
+        if (count) ctx_.check(ms_dev_upload(ctx_.get(), static_cast<double *>(pose_) + 12 * first, poseCW, 96 * count), "ms_dev_upload");
+    }
+    std::vector<Pose> download() const {
+        std::vector<Pose> out(n_);
+        if (n_) ctx_.check(ms_dev_download(ctx_.get(), out.data(), pose_, 96 * n_), "ms_dev_download");
+        return out;
+    }
+    std::size_t size() const { return n_; }
+    double *pose() const { return static_cast<double *>(pose_); }
+private:
+    Context &ctx_;
+    std::size_t n_;
+    void *pose_ = nullptr;
+};
+
+// Keypoint descriptors on the device, the pool MapObservation::descriptor indexes (the descriptors of the keyframes' keypoints, uploaded as the
+// keyframes arrive).
+class DeviceDescriptorPool {
+public:
+    DeviceDescriptorPool(Context &ctx, const std::vector<KeyPoint::Descriptor> &descriptors) : ctx_(ctx), n_(descriptors.size()) {
+        ctx_.check(ms_dev_alloc(ctx_.get(), 32 * n_ + 16, &desc_), "ms_dev_alloc");
+        if (n_) ctx_.check(ms_dev_upload(ctx_.get(), desc_, descriptors.data(), 32 * n_), "ms_dev_upload");
+    }
+    ~DeviceDescriptorPool() { ms_dev_free(ctx_.get(), desc_); }
+    DeviceDescriptorPool(const DeviceDescriptorPool &) = delete;
+    std::size_t size() const { return n_; }
+    const std::uint32_t *descriptor() const { return static_cast<const std::uint32_t *>(desc_); }
+private:
+    Context &ctx_;
+    std::size_t n_;
+    void *desc_ = nullptr;
+};
+
+// One entry of MapPoint::observations as the refresh reads it: the observing keyframe's slot in DeviceKeyframePoses and the observing
+// keypoint's descriptor in the pool (-1: the keyframe has no descriptors, map_point.cpp:80).
+struct MapObservation {
+    std::int32_t keyframe = 0;
+    std::int32_t descriptor = -1;
+};
+
 // The map points the gates read, structure-of-arrays on the device.  Row i = one MapPoint: position, norm, minViewingDistance,
-// maxViewingDistance, descriptor.  update() re-uploads a range after the map changed (MapPoint::updateDistanceAndNorm / updateDescriptor).
+// maxViewingDistance, descriptor.  update() uploads a range the host computed; refresh() recomputes rows where they lie (MapPoint::updateDistanceAndNorm /
+// updateDescriptor on the device), and mi355slam::correctLoop moves positions there.
 class DeviceMapPoints {
 public:
     using Vec3d = std::array<double, 3>;
@@ -444,6 +499,27 @@ public:
         if (maxDistance) up(max_ + first, maxDistance, 4 * count);
         if (descriptor) up(desc_ + 8 * first, descriptor, 32 * count);
     }
+    // MapPoint::updateDescriptor + MapPoint::updateDistanceAndNorm (map_point.cpp:75-116, :158-172) for the rows `rows`, computed and written on the
+    // device (ms_map_refresh).  observations[i] = row rows[i]'s observations in the order of the observations map (ascending KfId, so the first is
+    // getFirstObservation()); firstOctave[i] = the octave of that first observation's keypoint (:168).  Without a pool the descriptors stay as
+    // they are.  Returns, per row, the position of the chosen descriptor's observation in its list (-1 / -2: the row kept its descriptor).
+    std::vector<int> refresh(Context &ctx, const DeviceKeyframePoses &poses, const std::vector<std::int32_t> &rows,
+                             const std::vector<std::vector<MapObservation>> &observations, const std::vector<std::int32_t> &firstOctave,
+                             const StaticSettings &settings, const DeviceDescriptorPool *pool = nullptr) {
+        if (observations.size() != rows.size() || firstOctave.size() != rows.size())
+            throw std::invalid_argument("DeviceMapPoints::refresh: one observation list and one octave per row");
+        std::vector<std::int32_t> start(rows.size() + 1, 0), kf, desc;
+        for (std::size_t i = 0; i < rows.size(); ++i) {
+            for (const MapObservation &o : observations[i]) { kf.push_back(o.keyframe); desc.push_back(o.descriptor); }
+            start[i + 1] = (std::int32_t)kf.size();
+        }
+        std::vector<std::int32_t> medoid(rows.size(), -1);
+        ctx.check(ms_map_refresh(ctx.get(), pos_, norm_, min_, max_, desc_, (int)n_, poses.pose(), (int)poses.size(), pool ? pool->descriptor() : nullptr,
+                                 pool ? (int)pool->size() : 0, rows.data(), (int)rows.size(), start.data(), kf.data(), pool ? desc.data() : nullptr,
+                                 firstOctave.data(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(), medoid.data()), "ms_map_refresh");
+        return std::vector<int>(medoid.begin(), medoid.end());
+    }
+    double *mutablePosition() { return pos_; }
     std::size_t size() const { return n_; }
     const double *position() const { return pos_; }
     const float *norm() const { return norm_; }
@@ -465,6 +541,39 @@ private:
     std::uint32_t *desc_ = nullptr;
     std::vector<void *> owned_;
 };
+
+// The keyframes LoopCloser::correctLoop moves (loop_closer.cpp:420-470), as slots of DeviceKeyframePoses: rigid = a member of
+// rigidlyTransformedKfIds (:427, T itself), otherwise lambda = (t - t0) / (t1 - t0) of :458.
+struct LoopCorrections {
+    std::vector<std::int32_t> slot;
+    std::vector<std::uint8_t> rigid;
+    std::vector<double> lambda;
+};
+// localMapPoints (:418, :429-433, :465-469) as table rows: row[j] moves with the keyframe at position reference[j] of LoopCorrections::slot.
+struct LoopPoints {
+    std::vector<std::int32_t> row, reference;
+};
+// What DeviceMapPoints::refresh takes for the moved points (:504-505).
+struct RefreshArgs {
+    std::vector<std::int32_t> rows;
+    std::vector<std::vector<MapObservation>> observations;
+    std::vector<std::int32_t> firstOctave;
+    const DeviceDescriptorPool *pool = nullptr;
+};
+
+// LoopCloser::correctLoop from the pose correction to the refresh of the moved map points (loop_closer.cpp:398-506) on the device tables:
+// ms_loop_correct (poses, then points), then DeviceMapPoints::refresh of refreshArgs.rows.  T = the Sim3 of :405.  Re-triangulation (:508-523)
+// stays with the caller.  Returns refresh's medoids.
+inline std::vector<int> correctLoop(Context &ctx, DeviceMapPoints &table, DeviceKeyframePoses &poses, const Sim3 &T, const LoopCorrections &corrections,
+                                    const LoopPoints &points, const RefreshArgs &refreshArgs, const StaticSettings &settings) {
+    if (corrections.rigid.size() != corrections.slot.size() || corrections.lambda.size() != corrections.slot.size() || points.reference.size() != points.row.size())
+        throw std::invalid_argument("correctLoop: the correction lists have different lengths");
+    const double t8[8] = {T.q[0], T.q[1], T.q[2], T.q[3], T.t[0], T.t[1], T.t[2], T.s};
+    ctx.check(ms_loop_correct(ctx.get(), poses.pose(), (int)poses.size(), table.mutablePosition(), (int)table.size(), t8, corrections.slot.data(),
+                              corrections.rigid.data(), corrections.lambda.data(), (int)corrections.slot.size(), points.row.data(), points.reference.data(),
+                              (int)points.row.size()), "ms_loop_correct");
+    return table.refresh(ctx, poses, refreshArgs.rows, refreshArgs.observations, refreshArgs.firstOctave, settings, refreshArgs.pool);
+}
 
 // One view of a gate call: a pose (p_c = R p + t, row-major; for MS_GATE_SIM3 rotBAW / transBAW, which may carry a scale), a pinhole camera
 // (the stand-in of ms_pinhole), the loop's threshold / margin, and the table rows to walk, in the reference's order.

@@ -1015,6 +1015,64 @@ def project_gate(ctx, table, views, scale_factors_, scale_factor):
     return entries, per_view
 
 
+# ---- the writers of the map-point table (ms_map_refresh, ms_loop_correct) ----
+class KeyframePoseTable:
+    """Keyframe poses on the device: [n, 12] float64, rows 0-2 of poseCW, row-major; slot k is what obs_kf / kf_slot name."""
+
+    def __init__(self, ctx, poses):
+        self.ctx = ctx
+        a = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        self.n = len(a)
+        self.pose = ctx.upload(a if self.n else np.zeros((1, 12)))
+
+    def update(self, first, count, poses):
+        """Re-upload slots [first, first + count)."""
+        if first < 0 or count < 0 or first + count > self.n:
+            raise ValueError("slots [%d, %d) outside the table of %d" % (first, first + count, self.n))
+        if count:
+            a = np.ascontiguousarray(poses, np.float64).reshape(count, 12)
+            self.ctx.check(lib().ms_dev_upload(self.ctx._h, C.c_void_p(self.pose.ptr + 96 * first), _vp(a), C.c_size_t(a.nbytes)), "ms_dev_upload")
+
+    def download(self):
+        return self.pose.download(np.float64, (self.n, 12))
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+def map_refresh(ctx, table, poses, prob, scale_factors_, pool=None):
+    """MapPoint::updateDescriptor + updateDistanceAndNorm for rows of a MapPointTable, written on the device (ms_map_refresh).  prob: rows,
+    obs_start, obs_kf (slots of the KeyframePoseTable `poses`), obs_desc (indices into pool, -1 = none; may be absent), first_octave.  pool = a
+    device buffer of [n_pool, 8] uint32 descriptors (ctx.upload(...)) or None to leave the descriptors alone.  Returns medoid [n_rows]: the
+    chosen observation's position in each row's list, -1 / -2 where the row kept its descriptor."""
+    rows, start, okf, octv = _i32(prob["rows"]), _i32(prob["obs_start"]), _i32(prob["obs_kf"]), _i32(prob["first_octave"])
+    od = _i32(prob["obs_desc"]) if prob.get("obs_desc") is not None else None
+    sf = np.ascontiguousarray(scale_factors_, np.float32)
+    n_rows = len(rows)
+    if len(start) != n_rows + 1 or len(octv) != n_rows or (n_rows and (len(okf) < start[-1] or (od is not None and len(od) < start[-1]))):
+        raise ValueError("map_refresh: the lists do not describe %d rows" % n_rows)
+    medoid = np.full(n_rows, -1, np.int32)
+    n_pool = int(np.prod(pool.shape)) // 8 if pool is not None else 0
+    ctx.check(lib().ms_map_refresh(ctx._h, _vp(table.pos), _vp(table.norm), _vp(table.min_dist), _vp(table.max_dist), _vp(table.desc), table.n,
+                                   _vp(poses.pose), poses.n, _vp(pool), n_pool, _vp(rows), n_rows, _vp(start), _vp(okf), _vp(od), _vp(octv),
+                                   _vp(sf), len(sf), _vp(medoid)), "ms_map_refresh")
+    return medoid
+
+
+def loop_correct(ctx, table, poses, T, prob):
+    """The pose correction and map-point transfer of LoopCloser::correctLoop on a KeyframePoseTable and a MapPointTable's positions, in place
+    (ms_loop_correct).  T = (w, x, y, z, tx, ty, tz, s); prob: kf_slot, kf_rigid, kf_lambda, mp_row, mp_ref (position in kf_slot)."""
+    T = np.ascontiguousarray(T, np.float64).reshape(8)
+    slot, row, ref = _i32(prob["kf_slot"]), _i32(prob["mp_row"]), _i32(prob["mp_ref"])
+    rigid = np.ascontiguousarray(prob["kf_rigid"], np.uint8).reshape(-1)
+    lam = np.ascontiguousarray(prob["kf_lambda"], np.float64).reshape(-1)
+    if len(rigid) != len(slot) or len(lam) != len(slot) or len(ref) != len(row):
+        raise ValueError("loop_correct: the lists have different lengths")
+    ctx.check(lib().ms_loop_correct(ctx._h, _vp(poses.pose), poses.n, _vp(table.pos), table.n, _vp(T), _vp(slot), _vp(rigid), _vp(lam), len(slot),
+                                    _vp(row), _vp(ref), len(row)), "ms_loop_correct")
+
+
 class ProjectionKeyframe:
     """One keyframe's side of the projection-guided matchers on the device (FeatureSearch order, descriptors, octaves) with the host copies the
     replay needs."""
