@@ -566,6 +566,75 @@ int ms_loop_correct_check(const double *kf_pose, int n_kf, const double *mp_pos,
                           const uint8_t *kf_rigid, const double *kf_lambda, int n_corr, const int32_t *mp_row, const int32_t *mp_ref, int n_pts,
                           char *why, size_t why_bytes);
 
+/* ---- set queries over the keyframe table -------------------------------------------------------------------------------
+ * kf_mp (DEVICE, int32 [n_kf * stride], row-major): entry (k, j) = the map-point table row bound to keypoint j of the keyframe in slot k
+ * (Keyframe::mapPoints), -1 for none; a removed keyframe's slot is all -1.  An entry r is VALID iff (uint32)r < n_mp; the kernels make that
+ * comparison before any access that uses r, and every other value counts as "none".  mp_flags (DEVICE, uint8 [n_mp], may be NULL when no
+ * query asks for flags): the caller's encoding of MapPoint::status, bit 0 = TRIANGULATED, bit 1 = neither NOT_TRIANGULATED nor BAD.
+ *
+ * ms_covisibility: Keyframe::getNeighbors (keyframe.cpp:192-230) for n_q queries in one call.  S(q) = the valid entries r of slot q.slot
+ * with (mp_flags[r] & require) == require (require = 1: triangulatedOnly; 0: no flags read).
+ *   count[q * n_kf + k]  = the number of valid entries of slot k, with multiplicity, that lie in S(q) -- under the reference's invariant (a
+ *                          keyframe lists a map point at most once) the value of the `covisibilities` map, k = slot included
+ *   neighbour rule       k != slot and (k == force_a or k == force_b or (count >= 1 and count >= min_covis)); force_a / force_b =
+ *                          previousKfId / nextKfId as slots, -1 for none (the reference seeds them with minCovisibilities and only adds)
+ *   neighbours           the neighbour slots of q, ascending (the std::map walk), packed at neighbours + q * n_kf; what lies behind
+ *                          n_neighbours[q] of them is unspecified
+ * Four launches whatever n_q is (clear, mark, count, compact), one upload, one download; synchronous on the context stream.  The marks (one
+ * bitmap of n_mp bits per query, in the context's grow-only workspace) are cleared on every call.  Atomics only OR bits into bitmap words; the
+ * packed order comes from ballot prefix sums in slot order, so the same query gives the same bits at any batch position.
+ * MS_ERR_INVALID, with nothing written and before any device call: a slot outside [0, n_kf), a forced slot outside [-1, n_kf), require != 0
+ * with mp_flags == NULL, stride < 1, a negative count, a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps.  n_q = 0 and
+ * n_mp = 0 are fine.  ms_covisibility_check is the validation alone (no context, no device; `why` receives the message). */
+#define MS_COVIS_MAX_KF 65536
+#define MS_COVIS_MAX_STRIDE 8192
+#define MS_COVIS_MAX_QUERIES 4096               /* queries of ms_covisibility, problems of ms_map_point_union */
+#define MS_COVIS_MAX_MP (1 << 24)               /* n_mp stays BELOW this */
+#define MS_UNION_MAX_ENTRIES (1 << 20)          /* the problems' list slices together */
+typedef struct {
+    int32_t slot, force_a, force_b, min_covis;
+    uint8_t require;
+} ms_covis_query;
+int ms_covisibility(ms_ctx *ctx,
+    /* DEVICE */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags /* may be NULL */, int n_mp,
+    /* HOST */
+    const ms_covis_query *queries, int n_q,
+    /* DEVICE [n_q * n_kf] each; count may be NULL */
+    int32_t *count, int32_t *neighbours,
+    /* HOST [n_q] */
+    int32_t *n_neighbours);
+int ms_covisibility_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const ms_covis_query *queries, int n_q,
+                          const int32_t *neighbours, const int32_t *n_neighbours, char *why, size_t why_bytes);
+
+/* ms_map_point_union: the ordered union of the map points of a list of keyframes -- localMps of matchLocalMapPoints (mapper_helpers.cpp:
+ * 241-261), adjacentMapPointsSet of deduplicateMapPoints (:337-345), loopMapPoints of searchAndDeduplicate (loop_closer.cpp:569-584) and
+ * localMapPoints of correctLoop (:418-433, :465-469).  Problem u unites the valid entries of the slots kf_list[first .. first + count) in
+ * the caller's order (a slot may repeat), drops rows with (mp_flags[r] & require) != require and rows that are a valid entry of
+ * exclude_slot (-1 for none: !mp.observations.count(currentKeyframe.id)).  Packed at u * n_mp in ASCENDING ROW ORDER (the std::set /
+ * std::map walk): rows, and owner = the smallest position p of the problem's list whose slot lists the row (the emplace-if-absent of
+ * loop_closer.cpp:430-432; the list position, not the slot) -- mp_row / mp_ref of ms_loop_correct, mp_index of ms_project_gate.
+ * Six launches whatever n_u is (fill, mark, exclude, count, offsets, pack), one upload, one download; synchronous.  The marks (one int32 per
+ * row and problem in the context's workspace) are overwritten on every call; atomics only take the minimum of positions.
+ * MS_ERR_INVALID, with nothing written and before any device call: a slice outside kf_list, a listed slot outside [0, n_kf), an exclude slot
+ * outside [-1, n_kf), require != 0 with mp_flags == NULL, stride < 1, a negative count, a missing array.  MS_ERR_CAPACITY beyond the caps
+ * above.  n_u = 0, n_mp = 0 and empty lists are fine (n_rows = 0).  ms_map_point_union_check is the validation alone. */
+typedef struct {
+    int32_t first, count, exclude_slot;
+    uint8_t require;
+} ms_union_problem;
+int ms_map_point_union(ms_ctx *ctx,
+    /* DEVICE */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags /* may be NULL */, int n_mp,
+    /* HOST */
+    const int32_t *kf_list, int n_list, const ms_union_problem *problems, int n_u,
+    /* DEVICE [n_u * n_mp] each; owner may be NULL */
+    int32_t *rows, int32_t *owner,
+    /* HOST [n_u] */
+    int32_t *n_rows);
+int ms_map_point_union_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const int32_t *kf_list, int n_list,
+                             const ms_union_problem *problems, int n_u, const int32_t *rows, const int32_t *n_rows, char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

@@ -48,6 +48,9 @@ struct ms_ctx {
     // ms_map_refresh's and ms_loop_correct's workspace (map_refresh.hip): device lists / centres / packed descriptors / previous poses and their page-locked staging, grow-only
     void *mr_dev = nullptr, *mr_host = nullptr;
     size_t mr_dev_bytes = 0, mr_host_bytes = 0;
+    // ms_covisibility's and ms_map_point_union's workspace (covis.hip): device queries / bitmaps / owner marks / block counts and their page-locked staging, grow-only
+    void *cv_dev = nullptr, *cv_host = nullptr;
+    size_t cv_dev_bytes = 0, cv_host_bytes = 0;
     char err[512] = {0};
 };
 

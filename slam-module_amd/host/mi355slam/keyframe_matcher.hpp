@@ -575,6 +575,167 @@ inline std::vector<int> correctLoop(Context &ctx, DeviceMapPoints &table, Device
     return table.refresh(ctx, poses, refreshArgs.rows, refreshArgs.observations, refreshArgs.firstOctave, settings, refreshArgs.pool);
 }
 
+// ---- set queries over the map graph (ms_covisibility, ms_map_point_union) ---------------------------------------------------------
+// Keyframe::mapPoints of every keyframe on the device, one slot per keyframe: entry j of a slot = the DeviceMapPoints row bound to keypoint j,
+// -1 for none.  What getNeighbors and the map-point unions read; the lists those produce are what GateView::indices / LoopPoints take.
+class DeviceKeyframeMapPoints {
+public:
+    DeviceKeyframeMapPoints(Context &ctx, std::size_t slots, std::size_t stride, std::size_t mapPoints) : ctx_(ctx), n_(slots), stride_(stride), nMp_(mapPoints) {
+        if (stride_ < 1) throw std::invalid_argument("DeviceKeyframeMapPoints: stride < 1");
+        ctx_.check(ms_dev_alloc(ctx_.get(), 4 * n_ * stride_ + 16, &table_), "ms_dev_alloc");
+        const std::vector<std::int32_t> none(n_ * stride_, -1);
+        if (n_) ctx_.check(ms_dev_upload(ctx_.get(), table_, none.data(), 4 * none.size()), "ms_dev_upload");
+    }
+    ~DeviceKeyframeMapPoints() { ms_dev_free(ctx_.get(), table_); }
+    DeviceKeyframeMapPoints(const DeviceKeyframeMapPoints &) = delete;
+    // Keyframe::mapPoints of the keyframe in `slot` (shorter than the stride: padded with -1).  The host still holds the data here, so this is
+    // where an entry outside [-1, mapPoints) is turned away; the kernels treat whatever they find outside [0, mapPoints) as "none".
+    void update(std::size_t slot, const std::vector<std::int32_t> &mapPoints) {
+        if (slot >= n_ || mapPoints.size() > stride_) throw std::invalid_argument("DeviceKeyframeMapPoints::update: slot or length outside the table");
+        for (std::int32_t r : mapPoints)
+            if (r < -1 || r >= (std::int64_t)nMp_) throw std::invalid_argument("DeviceKeyframeMapPoints::update: entry " + std::to_string(r) + " outside [-1, " + std::to_string(nMp_) + ")");
+        std::vector<std::int32_t> row(stride_, -1);
+        std::copy(mapPoints.begin(), mapPoints.end(), row.begin());
+        ctx_.check(ms_dev_upload(ctx_.get(), static_cast<std::int32_t *>(table_) + slot * stride_, row.data(), 4 * stride_), "ms_dev_upload");
+    }
+    void clear(std::size_t slot) { update(slot, {}); }      // a removed keyframe
+    std::size_t size() const { return n_; }
+    std::size_t stride() const { return stride_; }
+    std::size_t mapPointCount() const { return nMp_; }
+    const std::int32_t *table() const { return static_cast<const std::int32_t *>(table_); }
+private:
+    Context &ctx_;
+    std::size_t n_, stride_, nMp_;
+    void *table_ = nullptr;
+};
+
+// MapPoint::status of every table row as the queries read it: bit 0 = TRIANGULATED, bit 1 = neither NOT_TRIANGULATED nor BAD.
+class DeviceMapPointFlags {
+public:
+    static constexpr std::uint8_t TRIANGULATED = 1, USABLE = 2;
+    DeviceMapPointFlags(Context &ctx, const std::vector<std::uint8_t> &flags) : ctx_(ctx), n_(flags.size()) {
+        ctx_.check(ms_dev_alloc(ctx_.get(), n_ + 16, &flags_), "ms_dev_alloc");
+        update(0, n_, flags.data());
+    }
+    ~DeviceMapPointFlags() { ms_dev_free(ctx_.get(), flags_); }
+    DeviceMapPointFlags(const DeviceMapPointFlags &) = delete;
+    void update(std::size_t first, std::size_t count, const std::uint8_t *flags) {
+        if (first + count > n_) throw std::runtime_error("DeviceMapPointFlags::update: range outside the table");
+        if (count) ctx_.check(ms_dev_upload(ctx_.get(), static_cast<std::uint8_t *>(flags_) + first, flags, count), "ms_dev_upload");
+    }
+    std::size_t size() const { return n_; }
+    const std::uint8_t *flags() const { return static_cast<const std::uint8_t *>(flags_); }
+private:
+    Context &ctx_;
+    std::size_t n_;
+    void *flags_ = nullptr;
+};
+
+// One call of Keyframe::getNeighbors (keyframe.cpp:192-230): the keyframe's slot, its previousKfId / nextKfId as slots (-1 for none).
+struct NeighborQuery {
+    std::int32_t slot = 0, previous = -1, next = -1;
+    int minCovisibilities = 1;
+    bool triangulatedOnly = false;
+};
+
+// getNeighbors for every query in one device call: per query the neighbour slots, ascending (the order of the reference's std::map walk).
+inline std::vector<std::vector<std::int32_t>> getNeighbors(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags,
+                                                           const std::vector<NeighborQuery> &queries) {
+    std::vector<std::vector<std::int32_t>> out(queries.size());
+    if (queries.empty()) return out;
+    if (flags && flags->size() < table.mapPointCount()) throw std::invalid_argument("getNeighbors: fewer flags than map points");
+    std::vector<ms_covis_query> q(queries.size());
+    for (std::size_t i = 0; i < queries.size(); ++i)
+        q[i] = ms_covis_query{queries[i].slot, queries[i].previous, queries[i].next, (std::int32_t)queries[i].minCovisibilities,
+                              (std::uint8_t)(queries[i].triangulatedOnly ? DeviceMapPointFlags::TRIANGULATED : 0)};
+    const std::size_t nKf = table.size(), bytes = 4 * queries.size() * nKf;
+    std::int32_t *packed = reinterpret_cast<std::int32_t *>(ctx.workspace(bytes));
+    std::vector<std::int32_t> n(queries.size(), 0);
+    ctx.check(ms_covisibility(ctx.get(), table.table(), (int)nKf, (int)table.stride(), flags ? flags->flags() : nullptr, (int)table.mapPointCount(), q.data(), (int)q.size(),
+                              nullptr, packed, n.data()), "ms_covisibility");
+    std::vector<std::int32_t> host(queries.size() * nKf);
+    ctx.check(ms_dev_download(ctx.get(), host.data(), packed, bytes), "ms_dev_download");
+    for (std::size_t i = 0; i < queries.size(); ++i) out[i].assign(host.begin() + i * nKf, host.begin() + i * nKf + n[i]);
+    return out;
+}
+
+// What computeAdjacentKeyframes reads of the map besides the covisibilities: per slot the previousKfId / nextKfId links (as slots, -1 for
+// none) and Keyframe::cameraCenter().
+struct KeyframeChain {
+    std::vector<std::int32_t> previous, next;
+    std::vector<std::array<double, 3>> cameraCenter;
+};
+
+// computeAdjacentKeyframes (mapper_helpers.cpp:144-229): the getNeighbors calls of every second keyframe of the chain behind `current`
+// (:160-176) are ONE ms_covisibility call; the chain walks from the parents and the squared-distance sort (:178-216) stay on the host.
+inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, std::int32_t current,
+                                                          int minCovisibilities, int maxKeyframes, const KeyframeChain &chain) {
+    if (chain.previous.size() != table.size() || chain.next.size() != table.size() || chain.cameraCenter.size() != table.size())
+        throw std::invalid_argument("computeAdjacentKeyframes: one link pair and one camera centre per slot");
+    auto inTable = [&](std::int32_t s) { return s >= 0 && (std::size_t)s < table.size(); };
+    if (!inTable(current)) throw std::invalid_argument("computeAdjacentKeyframes: current keyframe outside the table");
+    std::vector<char> adjacentSet(table.size(), 0);          // std::set<KfId> over slots: walked in ascending order below
+    std::vector<NeighborQuery> queries;
+    int i = 0;
+    for (std::int32_t backwards = current; backwards != -1; backwards = chain.previous[backwards]) {
+        if (!inTable(backwards)) throw std::invalid_argument("computeAdjacentKeyframes: a link leaves the table");
+        adjacentSet[backwards] = 1;
+        if (i % 2 == 0) queries.push_back({backwards, chain.previous[backwards], chain.next[backwards], minCovisibilities, false});
+        if (++i >= maxKeyframes) break;
+    }
+    std::vector<char> parents(table.size(), 0);
+    for (const std::vector<std::int32_t> &nb : getNeighbors(ctx, table, flags, queries))
+        for (std::int32_t k : nb) parents[k] = 1;
+    for (std::size_t parent = 0; parent < parents.size(); ++parent) {
+        if (!parents[parent]) continue;
+        for (const std::vector<std::int32_t> *link : {&chain.previous, &chain.next}) {
+            i = 0;
+            for (std::int32_t at = (std::int32_t)parent; at != -1; at = (*link)[at]) {
+                if (!inTable(at)) throw std::invalid_argument("computeAdjacentKeyframes: a link leaves the table");
+                adjacentSet[at] = 1;
+                if (++i >= maxKeyframes / 2) break;
+            }
+        }
+    }
+    adjacentSet[current] = 0;
+    std::vector<std::int32_t> adjacent;
+    for (std::size_t k = 0; k < adjacentSet.size(); ++k) if (adjacentSet[k]) adjacent.push_back((std::int32_t)k);
+    const std::array<double, 3> &c = chain.cameraCenter[current];
+    auto dist2 = [&](std::int32_t k) {                       // squaredNorm of a 3-vector, Eigen's unrolled redux: x^2 + (y^2 + z^2)
+        const std::array<double, 3> &p = chain.cameraCenter[k];
+        const double x = p[0] - c[0], y = p[1] - c[1], z = p[2] - c[2];
+        return x * x + (y * y + z * z);
+    };
+    std::sort(adjacent.begin(), adjacent.end(), [&](std::int32_t a, std::int32_t b) { return dist2(a) < dist2(b); });
+    if ((int)adjacent.size() > maxKeyframes) adjacent.erase(adjacent.begin() + maxKeyframes, adjacent.end());
+    return adjacent;
+}
+
+// The ordered union of the map points of a list of keyframes: rows ascending (the std::set / std::map walk) and, for each, the first
+// position of the list whose keyframe lists it (localMapPoints.emplace of loop_closer.cpp:430-432) -- LoopPoints as it stands.
+//   matchLocalMapPoints (mapper_helpers.cpp:241-261)   localMapPoints(ctx, table, &flags, adjacentSlots, currentSlot, DeviceMapPointFlags::USABLE).row
+//                                                      is GateView::indices in front of isInFrustum
+//   deduplicateMapPoints (:337-345), searchAndDeduplicate (loop_closer.cpp:569-584)   exclude = -1, require = 0
+//   correctLoop (:418-433, :465-469)                   keyframes = LoopCorrections::slot; the result is its LoopPoints
+inline LoopPoints localMapPoints(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &keyframes,
+                                 std::int32_t excludeSlot = -1, std::uint8_t require = 0, bool withOwner = true) {
+    LoopPoints out;
+    const std::size_t nMp = table.mapPointCount();
+    if (flags && flags->size() < nMp) throw std::invalid_argument("localMapPoints: fewer flags than map points");
+    const ms_union_problem problem{0, (std::int32_t)keyframes.size(), excludeSlot, require};
+    std::int32_t *rows = reinterpret_cast<std::int32_t *>(ctx.workspace(8 * nMp + 256)), *owner = rows + (nMp + 63) / 64 * 64;
+    std::int32_t n = 0;
+    ctx.check(ms_map_point_union(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), flags ? flags->flags() : nullptr, (int)nMp, keyframes.data(),
+                                 (int)keyframes.size(), &problem, 1, rows, withOwner ? owner : nullptr, &n), "ms_map_point_union");
+    out.row.resize((std::size_t)n);
+    if (withOwner) out.reference.resize((std::size_t)n);
+    if (n) {
+        ctx.check(ms_dev_download(ctx.get(), out.row.data(), rows, 4 * (std::size_t)n), "ms_dev_download");
+        if (withOwner) ctx.check(ms_dev_download(ctx.get(), out.reference.data(), owner, 4 * (std::size_t)n), "ms_dev_download");
+    }
+    return out;
+}
+
 // One view of a gate call: a pose (p_c = R p + t, row-major; for MS_GATE_SIM3 rotBAW / transBAW, which may carry a scale), a pinhole camera
 // (the stand-in of ms_pinhole), the loop's threshold / margin, and the table rows to walk, in the reference's order.
 struct GateView {

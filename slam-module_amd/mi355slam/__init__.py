@@ -1073,6 +1073,113 @@ def loop_correct(ctx, table, poses, T, prob):
                                     _vp(row), _vp(ref), len(row)), "ms_loop_correct")
 
 
+# ---- set queries over the keyframe table (ms_covisibility, ms_map_point_union) ----
+class CovisQueryC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("force_a", C.c_int32), ("force_b", C.c_int32), ("min_covis", C.c_int32), ("require", C.c_uint8)]
+
+
+class UnionProblemC(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("exclude_slot", C.c_int32), ("require", C.c_uint8)]
+
+
+def _download_i32(buf, shape):
+    return buf.download(np.int32, shape) if shape[0] * shape[1] else np.zeros(shape, np.int32)
+
+
+class KeyframeTable:
+    """Keyframe::mapPoints of every keyframe on the device: kf_mp [n_kf, stride] int32, entry (k, j) = the map-point table row bound to
+    keypoint j of the keyframe in slot k, -1 for none.  The queries take n_mp (rows of the map-point table; an entry outside [0, n_mp)
+    counts as none) and mp_flags ([n_mp] uint8, bit 0 = TRIANGULATED, bit 1 = neither NOT_TRIANGULATED nor BAD; a DevBuf, an array that
+    is uploaded for the call, or None when no query requires flags)."""
+
+    def __init__(self, ctx, kf_mp):
+        self.ctx = ctx
+        a = np.ascontiguousarray(kf_mp, np.int32)
+        if a.ndim != 2 or a.shape[1] < 1:
+            raise ValueError("kf_mp is [n_kf, stride] with stride >= 1")
+        self.n_kf, self.stride = a.shape
+        self.kf_mp = ctx.upload(a if self.n_kf else np.full((1, self.stride), -1, np.int32))
+
+    def update(self, slot, row):
+        """Re-upload one slot (a shorter row is padded with -1)."""
+        r = _i32(row)
+        if not 0 <= slot < self.n_kf or len(r) > self.stride:
+            raise ValueError("slot %d with %d entries outside the table of %d x %d" % (slot, len(r), self.n_kf, self.stride))
+        a = np.full(self.stride, -1, np.int32)
+        a[:len(r)] = r
+        self.ctx.check(lib().ms_dev_upload(self.ctx._h, C.c_void_p(self.kf_mp.ptr + 4 * self.stride * slot), _vp(a), C.c_size_t(a.nbytes)), "ms_dev_upload")
+
+    def download(self):
+        return self.kf_mp.download(np.int32, (self.n_kf, self.stride))
+
+    def _flags(self, mp_flags, n_mp):
+        if mp_flags is None or isinstance(mp_flags, DevBuf):
+            return mp_flags, None
+        f = np.ascontiguousarray(mp_flags, np.uint8).reshape(-1)
+        if len(f) != n_mp:
+            raise ValueError("mp_flags describes %d map points, n_mp is %d" % (len(f), n_mp))
+        b = self.ctx.upload(f if n_mp else np.zeros(1, np.uint8))
+        return b, b
+
+    def covisibility_device(self, queries, n_mp, flags, d_count, d_neighbours):
+        """ms_covisibility with the outputs left on the device (DevBufs of n_q * n_kf int32; d_count may be None); flags = a DevBuf or None.
+        Returns n_neighbours [n_q]."""
+        n_q = len(queries)
+        Q = (CovisQueryC * max(n_q, 1))(*[CovisQueryC(*[int(x) for x in q]) for q in queries])
+        n_nb = np.zeros(max(n_q, 1), np.int32)
+        self.ctx.check(lib().ms_covisibility(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(flags), int(n_mp), Q, n_q, _vp(d_count), _vp(d_neighbours),
+                                             _vp(n_nb)), "ms_covisibility")
+        return n_nb[:n_q]
+
+    def covisibility(self, queries, n_mp, mp_flags=None, want_count=True):
+        """Keyframe::getNeighbors for a list of queries (slot, force_a, force_b, min_covis, require) in one call (ms_covisibility).  Returns
+        (count [n_q, n_kf] or None, neighbours: one ascending int32 array per query, n_neighbours [n_q])."""
+        n_q = len(queries)
+        flags, own = self._flags(mp_flags, n_mp)
+        n_out = max(n_q * self.n_kf, 1)
+        d_count = self.ctx.alloc(4 * n_out) if want_count else None
+        d_nb = self.ctx.alloc(4 * n_out)
+        try:
+            n_nb = self.covisibility_device(queries, n_mp, flags, d_count, d_nb)
+            count = _download_i32(d_count, (n_q, self.n_kf)) if want_count else None
+            packed = _download_i32(d_nb, (n_q, self.n_kf))
+        finally:
+            for b in (d_count, d_nb, own):
+                if b is not None:
+                    b.free()
+        return count, [packed[q, :n_nb[q]].copy() for q in range(n_q)], n_nb
+
+    def map_point_union_device(self, kf_list, problems, n_mp, flags, d_rows, d_owner):
+        """ms_map_point_union with the outputs left on the device (DevBufs of n_u * n_mp int32; d_owner may be None); flags = a DevBuf or None.
+        Returns n_rows [n_u]."""
+        kf_list = _i32(kf_list)
+        n_u = len(problems)
+        P = (UnionProblemC * max(n_u, 1))(*[UnionProblemC(*[int(x) for x in p]) for p in problems])
+        n_rows = np.zeros(max(n_u, 1), np.int32)
+        self.ctx.check(lib().ms_map_point_union(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(flags), int(n_mp), _vp(kf_list), len(kf_list), P, n_u,
+                                                _vp(d_rows), _vp(d_owner), _vp(n_rows)), "ms_map_point_union")
+        return n_rows[:n_u]
+
+    def map_point_union(self, kf_list, problems, n_mp, mp_flags=None, want_owner=True):
+        """The ordered unions of the map points of lists of keyframes (ms_map_point_union).  problems: (first, count, exclude_slot, require) over
+        kf_list.  Returns (rows, owner or None, n_rows): per problem the rows in ascending order and, for each, the smallest position of the
+        problem's list whose slot lists it."""
+        n_u, n_mp = len(problems), int(n_mp)
+        flags, own = self._flags(mp_flags, n_mp)
+        n_out = max(n_u * n_mp, 1)
+        d_rows = self.ctx.alloc(4 * n_out)
+        d_owner = self.ctx.alloc(4 * n_out) if want_owner else None
+        try:
+            n_rows = self.map_point_union_device(kf_list, problems, n_mp, flags, d_rows, d_owner)
+            rows = _download_i32(d_rows, (n_u, n_mp))
+            owner = _download_i32(d_owner, (n_u, n_mp)) if want_owner else None
+        finally:
+            for b in (d_rows, d_owner, own):
+                if b is not None:
+                    b.free()
+        return ([rows[u, :n_rows[u]].copy() for u in range(n_u)], [owner[u, :n_rows[u]].copy() for u in range(n_u)] if want_owner else None, n_rows)
+
+
 class ProjectionKeyframe:
     """One keyframe's side of the projection-guided matchers on the device (FeatureSearch order, descriptors, octaves) with the host copies the
     replay needs."""
