@@ -635,6 +635,62 @@ int ms_map_point_union(ms_ctx *ctx,
 int ms_map_point_union_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const int32_t *kf_list, int n_list,
                              const ms_union_problem *problems, int n_u, const int32_t *rows, const int32_t *n_rows, char *why, size_t why_bytes);
 
+/* ---- the map-point triangulator -----------------------------------------------------------------------------------------
+ * ms_triangulate: triangulateMapPoint (mapper_helpers.cpp:600-722; MS_TRI_TME, MS_TRI_MIDPOINT) or triangulateMapPointFirstLastObs
+ * (:724-812; MS_TRI_FIRST_LAST) for chosen rows of the map-point table, positions and status flags written where ms_project_gate,
+ * ms_map_refresh and ms_covisibility read them -- the re-triangulation of LoopCloser::correctLoop (loop_closer.cpp:508-523),
+ * createNewMapPoints (:308), the pass after local BA (:1083-1090) and matchTrackedFeatures (:90).  Entry r re-triangulates row rows[r] from
+ * its observations obs_start[r] .. obs_start[r + 1], listed in the reference's iteration order (ascending KfId): obs_kf = the observing
+ * keyframe's slot in kf_pose / kf_cam / kf_focal, obs_x / obs_y / obs_octave = the keypoint's pixel and octave, obs_depth = its
+ * keyPointDepth (NULL: no depth anywhere).  was_triangulated[r] = status != NOT_TRIANGULATED on entry (:607); kf_focal = getFocalLength.
+ * tests/triangulate_ref.py restates the arithmetic and is this entry point's specification: the camera is the ms_pinhole stand-in
+ * (normalizePixel = ((x - cx) / fx, (y - cy) / fy), always true; bearing = its unit vector; reproject = the rule above narrowed to float32),
+ * and the three Theia solvers, which are outside the reference tree, are pinned there (N-view: smallest eigenvector of sum C^T C; two views:
+ * Lindstrom's niter2, then DLT; midpoint: the 3x3 normal equations), with one cyclic-Jacobi eigen-solve and one summation order.
+ * Written for a listed row, exactly when the reference writes them: mp_flags[row] (when given; the 9.6 encoding, TRIANGULATED = 3, UNSURE = 2,
+ * NOT_TRIANGULATED = 0 -- the status is reset at entry, so every listed row gets one) and mp_pos[row] (on success; on the depth branch of
+ * :622 and at :746 / :776 also when a later check fails).  Rows not listed are not touched.
+ * HOST outputs, [n_rows], each may be NULL: status (0 NOT_TRIANGULATED, 1 UNSURE, 2 TRIANGULATED), reason = the first gate that stopped the
+ * point (0 none | 1 fewer than two observations | 2 triangulation angle | 3 solver failed | 4 negative depth | 5 reprojection error |
+ * 6 fewer than two passing observations, FIRST_LAST | 7 dense-stereo skip, :748), n_pass = FIRST_LAST's nNew.  The trailing updateDescriptor
+ * (:811) is ms_map_refresh's.
+ * Any number of observations per point (rounds of 16 per point); at most MS_TRI_MAX_OBS observations and MS_TRI_MAX_ROWS rows per call
+ * (MS_ERR_CAPACITY beyond).  The same input gives the same bits on every call and at every position of a batch.  Two launches whatever
+ * n_rows is; synchronous: one upload, at most one download; the workspace belongs to the context and only grows (ms_debug_host_allocs).
+ * MS_ERR_INVALID, with nothing written and before any device call: a row or slot out of range, a row listed twice, obs_start not starting
+ * at 0 or decreasing, an octave outside [0, n_levels), an observing camera with width or height < 1 or fx / fy not positive and finite, a
+ * bad mode, n_levels outside [1, MS_TRI_MAX_LEVELS], a setting that is not finite, a missing array.  n_rows = 0 and empty observation
+ * lists are fine (reason 1).  ms_triangulate_check is that validation alone (no context, no device; `why` receives the message). */
+#define MS_TRI_TME        0   /* TriangulationMethod::TME: theia::Triangulate for two observations, TriangulateNView for more */
+#define MS_TRI_MIDPOINT   1   /* TriangulationMethod::MIDPOINT: theia::TriangulateMidpoint */
+#define MS_TRI_FIRST_LAST 2   /* triangulateMapPointFirstLastObs */
+#define MS_TRI_MAX_LEVELS 32
+#define MS_TRI_MAX_ROWS (1 << 24)
+#define MS_TRI_MAX_OBS (1 << 22)                /* observations of all rows of one call together */
+typedef struct {
+    const float *level_sigma_sq;         /* HOST [n_levels], StaticSettings::levelSigmaSq; the reference level is n_levels / 2 */
+    int32_t n_levels;
+    double min_angle_two_obs, min_angle_multiple_obs;    /* degrees: minTriangulationAngleTwoObs / MultipleObs */
+    float rel_reprojection_threshold;    /* relativeReprojectionErrorThreshold */
+    int32_t dense_stereo_depth;          /* tracker.computeDenseStereoDepth (FIRST_LAST, :748) */
+} ms_tri_settings;
+int ms_triangulate(ms_ctx *ctx,
+    /* DEVICE: mp_pos [n_mp * 3] read and written, mp_flags [n_mp] written (may be NULL), kf_pose [n_kf * 12] */
+    double *mp_pos, uint8_t *mp_flags, int n_mp, const double *kf_pose, int n_kf,
+    /* HOST, per keyframe slot */
+    const ms_pinhole *kf_cam, const int32_t *kf_focal,
+    /* HOST, per entry */
+    const int32_t *rows, const uint8_t *was_triangulated, int n_rows, const int32_t *obs_start,
+    /* HOST, per observation */
+    const int32_t *obs_kf, const float *obs_x, const float *obs_y, const int32_t *obs_octave, const float *obs_depth /* may be NULL */,
+    const ms_tri_settings *settings, int mode,
+    /* HOST [n_rows], each may be NULL */
+    uint8_t *status, uint8_t *reason, int32_t *n_pass);
+int ms_triangulate_check(const double *mp_pos, int n_mp, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam, const int32_t *kf_focal,
+                         const int32_t *rows, const uint8_t *was_triangulated, int n_rows, const int32_t *obs_start, const int32_t *obs_kf,
+                         const float *obs_x, const float *obs_y, const int32_t *obs_octave, const ms_tri_settings *settings, int mode,
+                         char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

@@ -152,6 +152,8 @@ void ms_ctx_destroy(ms_ctx *c) {
     if (c->mr_host) (void)hipHostFree(c->mr_host);
     if (c->cv_dev) (void)hipFree(c->cv_dev);
     if (c->cv_host) (void)hipHostFree(c->cv_host);
+    if (c->tr_dev) (void)hipFree(c->tr_dev);
+    if (c->tr_host) (void)hipHostFree(c->tr_host);
     for (auto &b : c->ba_cache) if (b.p) (void)hipFree(b.p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

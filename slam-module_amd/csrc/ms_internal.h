@@ -51,6 +51,9 @@ struct ms_ctx {
     // ms_covisibility's and ms_map_point_union's workspace (covis.hip): device queries / bitmaps / owner marks / block counts and their page-locked staging, grow-only
     void *cv_dev = nullptr, *cv_host = nullptr;
     size_t cv_dev_bytes = 0, cv_host_bytes = 0;
+    // ms_triangulate's workspace (triangulate.hip): device lists / cameras / rays / results and their page-locked staging, grow-only
+    void *tr_dev = nullptr, *tr_host = nullptr;
+    size_t tr_dev_bytes = 0, tr_host_bytes = 0;
     char err[512] = {0};
 };
 

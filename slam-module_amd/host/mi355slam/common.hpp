@@ -36,6 +36,10 @@ struct Parameters {
     bool loopClosureRansacFixScale = false;
     // optimize_transform.cpp:72-73: the Huber delta of OptimizeSim3Transform is (float)sqrt of it; set by the parent project (a stand-in default)
     double loopClosureInlierThreshold = 1e-4;
+    // mapper_helpers.cpp:631-633, :712, :748 (triangulateMapPoint): set by the parent project (stand-in defaults)
+    double minTriangulationAngleTwoObs = 1.0, minTriangulationAngleMultipleObs = 3.0;       // degrees
+    float relativeReprojectionErrorThreshold = 0.004f;
+    bool computeDenseStereoDepth = false;         // tracker.computeDenseStereoDepth
 };
 
 // slam::StaticSettings (static_settings.hpp:9-21)

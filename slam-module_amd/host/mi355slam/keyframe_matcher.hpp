@@ -625,11 +625,61 @@ public:
     }
     std::size_t size() const { return n_; }
     const std::uint8_t *flags() const { return static_cast<const std::uint8_t *>(flags_); }
+    std::uint8_t *mutableFlags() { return static_cast<std::uint8_t *>(flags_); }          // what triangulateMapPoints writes
 private:
     Context &ctx_;
     std::size_t n_;
     void *flags_ = nullptr;
 };
+
+// ---- the map-point triangulator (ms_triangulate) ------------------------------------------------------------------------------------
+// TriangulationMethod of mapper_helpers.hpp plus the first / last variant (triangulateMapPointFirstLastObs).
+enum class TriangulationMethod { TME = MS_TRI_TME, MIDPOINT = MS_TRI_MIDPOINT, FIRST_LAST = MS_TRI_FIRST_LAST };
+// Per keyframe slot of DeviceKeyframePoses: the pinhole stand-in of kf.shared->camera and its getFocalLength().
+struct KeyframeCameras {
+    std::vector<ms_pinhole> camera;
+    std::vector<std::int32_t> focalLength;
+};
+// The map points to triangulate and MapPoint::observations of each, flattened in the reference's iteration order (ascending KfId):
+// row r's observations are [obsStart[r], obsStart[r + 1]); obsKf = the keyframe's slot, obsX / obsY / obsOctave = kp.pt and kp.octave,
+// obsDepth = keyPointDepth (empty: no depth anywhere); wasTriangulated = status != NOT_TRIANGULATED on entry (mapper_helpers.cpp:607).
+struct TriangulateArgs {
+    std::vector<std::int32_t> rows;
+    std::vector<std::uint8_t> wasTriangulated;
+    std::vector<std::int32_t> obsStart, obsKf, obsOctave;
+    std::vector<float> obsX, obsY, obsDepth;
+};
+// Per entry of TriangulateArgs::rows: status (0 NOT_TRIANGULATED, 1 UNSURE, 2 TRIANGULATED), the first gate that stopped the point (the reason
+// codes of ms_triangulate) and nNew of triangulateMapPointFirstLastObs.
+struct TriangulateResult {
+    std::vector<std::uint8_t> status, reason;
+    std::vector<std::int32_t> passCount;
+};
+
+// triangulateMapPoint / triangulateMapPointFirstLastObs (mapper_helpers.cpp:600-812) for args.rows, on the device: positions are written into
+// `table`, the status flags (DeviceMapPointFlags encoding) into `flags` when given.  The debug counters of loop_closer.cpp:516-521 follow from
+// the result and the entry state: `failed` = the entry status was TRIANGULATED and status != 2; `changed` (a comparison of position values in
+// the reference) = the position was written: status != 0, or the depth branch of :621 ran (not wasTriangulated, a positive depth, reason != 1).
+inline TriangulateResult triangulateMapPoints(Context &ctx, DeviceMapPoints &table, DeviceMapPointFlags *flags, const DeviceKeyframePoses &poses,
+                                              const KeyframeCameras &cams, const TriangulateArgs &args, const StaticSettings &settings, TriangulationMethod method) {
+    const std::size_t n = args.rows.size();
+    if (args.wasTriangulated.size() != n || args.obsStart.size() != n + 1) throw std::invalid_argument("triangulateMapPoints: one flag and one list per row");
+    const std::size_t nObs = (std::size_t)std::max<std::int32_t>(args.obsStart.back(), 0);
+    if (args.obsKf.size() < nObs || args.obsOctave.size() < nObs || args.obsX.size() < nObs || args.obsY.size() < nObs || (!args.obsDepth.empty() && args.obsDepth.size() < nObs))
+        throw std::invalid_argument("triangulateMapPoints: the observation arrays are shorter than obsStart says");
+    if (cams.camera.size() != poses.size() || cams.focalLength.size() != poses.size()) throw std::invalid_argument("triangulateMapPoints: one camera per keyframe slot");
+    if (flags && flags->size() < table.size()) throw std::invalid_argument("triangulateMapPoints: fewer flags than map points");
+    const Parameters &p = settings.parameters;
+    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    TriangulateResult out;
+    out.status.assign(n, 0); out.reason.assign(n, 0); out.passCount.assign(n, 0);
+    ctx.check(ms_triangulate(ctx.get(), table.mutablePosition(), flags ? flags->mutableFlags() : nullptr, (int)table.size(), poses.pose(), (int)poses.size(),
+                             cams.camera.data(), cams.focalLength.data(), args.rows.data(), args.wasTriangulated.data(), (int)n, args.obsStart.data(), args.obsKf.data(),
+                             args.obsX.data(), args.obsY.data(), args.obsOctave.data(), args.obsDepth.empty() ? nullptr : args.obsDepth.data(), &s, (int)method,
+                             out.status.data(), out.reason.data(), out.passCount.data()), "ms_triangulate");
+    return out;
+}
 
 // One call of Keyframe::getNeighbors (keyframe.cpp:192-230): the keyframe's slot, its previousKfId / nextKfId as slots (-1 for none).
 struct NeighborQuery {

@@ -923,6 +923,15 @@ class GateViewC(C.Structure):
                 ("mode", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
 
 
+TRI_TME, TRI_MIDPOINT, TRI_FIRST_LAST = 0, 1, 2
+TRI_MAX_LEVELS, TRI_MAX_ROWS, TRI_MAX_OBS = 32, 1 << 24, 1 << 22
+
+
+class TriSettingsC(C.Structure):
+    _fields_ = [("level_sigma_sq", C.c_void_p), ("n_levels", C.c_int32), ("min_angle_two_obs", C.c_double), ("min_angle_multiple_obs", C.c_double),
+                ("rel_reprojection_threshold", C.c_float), ("dense_stereo_depth", C.c_int32)]
+
+
 class MapPointTable:
     """The map points the gates read, structure-of-arrays on the device: pos [n, 3] float64 (MapPoint::position), norm [n, 3] float32,
     min_dist / max_dist [n] float32 (minViewingDistance / maxViewingDistance), desc [n, 8] uint32 (MapPoint::descriptor)."""
@@ -946,6 +955,36 @@ class MapPointTable:
             if name in fields and count:
                 a = np.ascontiguousarray(fields[name], dt).reshape(count, w)
                 self.ctx.check(lib().ms_dev_upload(self.ctx._h, C.c_void_p(getattr(self, name).ptr + first * a.itemsize * w), _vp(a), C.c_size_t(a.nbytes)), "ms_dev_upload")
+
+    def triangulate(self, poses, cams, focal, prob, settings, mode, flags=None, outputs=True):
+        """triangulateMapPoint (TRI_TME, TRI_MIDPOINT) / triangulateMapPointFirstLastObs (TRI_FIRST_LAST) for rows of this table, positions
+        written on the device (ms_triangulate).  poses = a KeyframePoseTable; cams [n_kf, 6] (fx, fy, cx, cy, width, height) and focal [n_kf]
+        int32 per slot; prob: rows, was_triangulated, obs_start, obs_kf, obs_x, obs_y, obs_octave, obs_depth (None / absent: no depth);
+        settings: level_sigma_sq, min_angle_two_obs, min_angle_multiple_obs, rel_reprojection_threshold, dense_stereo_depth; flags = a
+        DevBuf of [n] uint8 status flags to write (bit 0 TRIANGULATED, bit 1 usable) or None.  Returns (status, reason, n_pass) per entry,
+        or None with outputs=False."""
+        rows, start = _i32(prob["rows"]), _i32(prob["obs_start"])
+        was = np.ascontiguousarray(prob["was_triangulated"], np.uint8).reshape(-1)
+        okf, octv = _i32(prob["obs_kf"]), _i32(prob["obs_octave"])
+        x, y = (np.ascontiguousarray(prob[k], np.float32).reshape(-1) for k in ("obs_x", "obs_y"))
+        depth = np.ascontiguousarray(prob["obs_depth"], np.float32).reshape(-1) if prob.get("obs_depth") is not None else None
+        n_rows = len(rows)
+        n_obs = int(start[-1]) if len(start) else 0
+        if len(start) != n_rows + 1 or len(was) != n_rows or any(len(a) < n_obs for a in (okf, octv, x, y)) or (depth is not None and len(depth) < n_obs):
+            raise ValueError("triangulate: the lists do not describe %d rows" % n_rows)
+        cam_rows = np.asarray(cams, np.float64).reshape(-1, 6)
+        focal = _i32(focal)
+        if len(cam_rows) != poses.n or len(focal) != poses.n:
+            raise ValueError("triangulate: one camera and one focal length per keyframe slot")
+        K = (Pinhole * max(poses.n, 1))(*[Pinhole(c[0], c[1], c[2], c[3], int(c[4]), int(c[5])) for c in cam_rows])
+        sig = np.ascontiguousarray(settings["level_sigma_sq"], np.float32).reshape(-1)
+        S = TriSettingsC(sig.ctypes.data, len(sig), float(settings["min_angle_two_obs"]), float(settings["min_angle_multiple_obs"]),
+                         float(settings["rel_reprojection_threshold"]), int(bool(settings.get("dense_stereo_depth", False))))
+        status, reason, n_pass = (np.zeros(n_rows, np.uint8), np.zeros(n_rows, np.uint8), np.zeros(n_rows, np.int32)) if outputs else (None, None, None)
+        self.ctx.check(lib().ms_triangulate(self.ctx._h, _vp(self.pos), _vp(flags), self.n, _vp(poses.pose), poses.n, K, _vp(focal), _vp(rows), _vp(was), n_rows,
+                                            _vp(start), _vp(okf), _vp(x), _vp(y), _vp(octv), _vp(depth), C.byref(S), int(mode), _vp(status), _vp(reason),
+                                            _vp(n_pass)), "ms_triangulate")
+        return (status, reason, n_pass) if outputs else None
 
 
 def gate_views_pack(views):
