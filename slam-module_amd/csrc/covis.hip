@@ -218,33 +218,6 @@ __global__ __launch_bounds__(kBlock) void k_union_pack(const UnionArgs A) {
     if (A.owner) A.owner[dst] = mark;
 }
 
-// grow-only context workspace
-int grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
-    if (bytes <= cap) return MS_OK;
-    if (p) {
-        MS_HIP(c, hipStreamSynchronize(c->stream));
-        if (pinned) MS_HIP(c, hipHostFree(p));
-        else MS_HIP(c, hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
-    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-    else MS_HIP(c, hipMalloc(&p, want));
-    cap = want;
-    ++g_ms_host_allocs;
-    return MS_OK;
-}
-
-int why_not(char *why, size_t bytes, const char *fmt, ...) {
-    if (why && bytes) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(why, bytes, fmt, ap);
-        va_end(ap);
-    }
-    return MS_ERR_INVALID;
-}
-
 bool over_capacity(int n_kf, int stride, int n_mp, int n) {
     return n_kf > MS_COVIS_MAX_KF || stride > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || n > MS_COVIS_MAX_QUERIES;
 }
@@ -253,16 +226,16 @@ bool over_capacity(int n_kf, int stride, int n_mp, int n) {
 
 extern "C" int ms_covisibility_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const ms_covis_query *queries, int n_q,
                                      const int32_t *neighbours, const int32_t *n_neighbours, char *why, size_t why_bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_q < 0) return why_not(why, why_bytes, "covisibility: negative count (%d slots, %d map points, %d queries)", n_kf, n_mp, n_q);
-    if (stride < 1) return why_not(why, why_bytes, "covisibility: stride %d", stride);
+    if (n_kf < 0 || n_mp < 0 || n_q < 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: negative count (%d slots, %d map points, %d queries)", n_kf, n_mp, n_q);
+    if (stride < 1) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: stride %d", stride);
     if (n_q == 0) return MS_OK;
-    if (!kf_mp || !queries || !neighbours || !n_neighbours) return why_not(why, why_bytes, "covisibility: missing array");
+    if (!kf_mp || !queries || !neighbours || !n_neighbours) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: missing array");
     for (int q = 0; q < n_q; ++q) {
         const ms_covis_query &Q = queries[q];
-        if (Q.slot < 0 || Q.slot >= n_kf) return why_not(why, why_bytes, "covisibility: query %d: slot %d outside [0, %d)", q, Q.slot, n_kf);
+        if (Q.slot < 0 || Q.slot >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: query %d: slot %d outside [0, %d)", q, Q.slot, n_kf);
         if (Q.force_a < -1 || Q.force_a >= n_kf || Q.force_b < -1 || Q.force_b >= n_kf)
-            return why_not(why, why_bytes, "covisibility: query %d: forced slots %d, %d outside [-1, %d)", q, Q.force_a, Q.force_b, n_kf);
-        if (Q.require && !mp_flags) return why_not(why, why_bytes, "covisibility: query %d requires flags 0x%x and there is no mp_flags", q, (unsigned)Q.require);
+            return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: query %d: forced slots %d, %d outside [-1, %d)", q, Q.force_a, Q.force_b, n_kf);
+        if (Q.require && !mp_flags) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: query %d requires flags 0x%x and there is no mp_flags", q, (unsigned)Q.require);
     }
     return MS_OK;
 }
@@ -277,30 +250,34 @@ extern "C" int ms_covisibility(ms_ctx *c, const int32_t *kf_mp, int n_kf, int st
                        MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_QUERIES);
     if (n_q == 0) return MS_OK;
     MsRange range("covisibility");
-    const size_t nq = (size_t)n_q, a4 = 256, words = ((size_t)n_mp + 31) / 32;
+    const size_t nq = (size_t)n_q, words = ((size_t)n_mp + 31) / 32;
     // upload block: queries; then (host only) the neighbour counts
-    const size_t up_bytes = ms_align_up(sizeof(QDev) * nq, a4), o_down = up_bytes, host_bytes = o_down + ms_align_up(4 * nq, a4);
+    MsLayout up;
+    const auto l_q = up.array<QDev>(nq);
+    MsLayout host = up, dev = up;
+    const auto l_down = host.array<int32_t>(nq);
     // device-only block: neighbour counts | bitmaps | counts when the caller does not want them
-    const size_t o_nn = up_bytes, o_bm = o_nn + ms_align_up(4 * nq, a4), o_cnt = o_bm + ms_align_up(4 * nq * (words + 1), a4),
-                 dev_bytes = o_cnt + (count ? 0 : ms_align_up(4 * nq * (size_t)n_kf, a4));
+    const auto l_nn = dev.array<int32_t>(nq);
+    const auto l_bm = dev.array<uint32_t>(nq * (words + 1));
+    const auto l_cnt = dev.array<int32_t>(count ? 0 : nq * (size_t)n_kf);
     MS_HIP(c, hipSetDevice(c->device));
-    if ((rc = grow(c, c->cv_host, c->cv_host_bytes, host_bytes, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->cv_host);
-    if ((rc = grow(c, c->cv_dev, c->cv_dev_bytes, dev_bytes, false))) return rc;
-    uint8_t *ds = static_cast<uint8_t *>(c->cv_dev);
-    QDev *hq = reinterpret_cast<QDev *>(hs);
+    MsWorkspace &W = c->ws[MS_WS_COVIS];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    QDev *hq = l_q.at(hs);
     for (int q = 0; q < n_q; ++q) hq[q] = QDev{queries[q].slot, queries[q].force_a, queries[q].force_b, queries[q].min_covis, (int32_t)queries[q].require};
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     CovisArgs A;
     A.kf_mp = kf_mp; A.mp_flags = mp_flags;
-    A.q = reinterpret_cast<const QDev *>(ds);
-    A.bitmap = reinterpret_cast<uint32_t *>(ds + o_bm);
-    A.count = count ? count : reinterpret_cast<int32_t *>(ds + o_cnt);
+    A.q = l_q.at(ds);
+    A.bitmap = l_bm.at(ds);
+    A.count = count ? count : l_cnt.at(ds);
     A.neighbours = neighbours;
-    A.n_neighbours = reinterpret_cast<int32_t *>(ds + o_nn);
+    A.n_neighbours = l_nn.at(ds);
     A.n_kf = n_kf; A.stride = stride; A.n_mp = n_mp; A.n_q = n_q; A.words = (int32_t)words;
     A.vec = stride % 4 == 0 && (reinterpret_cast<uintptr_t>(kf_mp) & 15u) == 0;
-    MS_HIP(c, hipMemsetAsync(A.bitmap, 0, 4 * nq * (words + 1), c->stream));
+    MS_HIP(c, hipMemsetAsync(A.bitmap, 0, l_bm.bytes(), c->stream));
     hipLaunchKernelGGL(k_covis_mark, dim3(ms_div_up(stride, kBlock), (unsigned)n_q), dim3(kBlock), 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_covis_mark");
     const dim3 slots((unsigned)n_kf), block(kBlock);
@@ -311,27 +288,27 @@ extern "C" int ms_covisibility(ms_ctx *c, const int32_t *kf_mp, int n_kf, int st
     MS_KERNEL_CHECK(c, "k_covis_count");
     hipLaunchKernelGGL(k_covis_pick, dim3(ms_div_up(n_q, kBlock / 64)), block, 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_covis_pick");
-    MS_HIP(c, hipMemcpyAsync(hs + o_down, ds + o_nn, 4 * nq, hipMemcpyDeviceToHost, c->stream));
+    MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_nn.at(ds), l_nn.bytes(), hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(n_neighbours, hs + o_down, 4 * nq);
+    std::memcpy(n_neighbours, l_down.at(hs), l_down.bytes());
     return MS_OK;
 }
 
 extern "C" int ms_map_point_union_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const int32_t *kf_list, int n_list,
                                         const ms_union_problem *problems, int n_u, const int32_t *rows, const int32_t *n_rows, char *why, size_t why_bytes) {
     if (n_kf < 0 || n_mp < 0 || n_list < 0 || n_u < 0)
-        return why_not(why, why_bytes, "map point union: negative count (%d slots, %d map points, %d list entries, %d problems)", n_kf, n_mp, n_list, n_u);
-    if (stride < 1) return why_not(why, why_bytes, "map point union: stride %d", stride);
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: negative count (%d slots, %d map points, %d list entries, %d problems)", n_kf, n_mp, n_list, n_u);
+    if (stride < 1) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: stride %d", stride);
     if (n_u == 0) return MS_OK;
-    if (!kf_mp || !problems || !rows || !n_rows || (n_list > 0 && !kf_list)) return why_not(why, why_bytes, "map point union: missing array");
+    if (!kf_mp || !problems || !rows || !n_rows || (n_list > 0 && !kf_list)) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: missing array");
     for (int u = 0; u < n_u; ++u) {
         const ms_union_problem &P = problems[u];
         if (P.count < 0 || P.first < 0 || (long long)P.first + P.count > n_list)
-            return why_not(why, why_bytes, "map point union: problem %d: slice [%d, %d + %d) outside [0, %d)", u, P.first, P.first, P.count, n_list);
-        if (P.exclude_slot < -1 || P.exclude_slot >= n_kf) return why_not(why, why_bytes, "map point union: problem %d: exclude slot %d outside [-1, %d)", u, P.exclude_slot, n_kf);
-        if (P.require && !mp_flags) return why_not(why, why_bytes, "map point union: problem %d requires flags 0x%x and there is no mp_flags", u, (unsigned)P.require);
+            return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: problem %d: slice [%d, %d + %d) outside [0, %d)", u, P.first, P.first, P.count, n_list);
+        if (P.exclude_slot < -1 || P.exclude_slot >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: problem %d: exclude slot %d outside [-1, %d)", u, P.exclude_slot, n_kf);
+        if (P.require && !mp_flags) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: problem %d requires flags 0x%x and there is no mp_flags", u, (unsigned)P.require);
         for (int i = P.first; i < P.first + P.count; ++i)       // list entries in no slice are never read, so only the slices are checked
-            if (kf_list[i] < 0 || kf_list[i] >= n_kf) return why_not(why, why_bytes, "map point union: list entry %d: slot %d outside [0, %d)", i, kf_list[i], n_kf);
+            if (kf_list[i] < 0 || kf_list[i] >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: list entry %d: slot %d outside [0, %d)", i, kf_list[i], n_kf);
     }
     return MS_OK;
 }
@@ -352,20 +329,23 @@ extern "C" int ms_map_point_union(ms_ctx *c, const int32_t *kf_mp, int n_kf, int
         return MS_OK;
     }
     MsRange range("mapPointUnion");
-    const size_t nu = (size_t)n_u, ne = (size_t)n_entries, a4 = 256, n_blk = ((size_t)n_mp + kBlock - 1) / kBlock;
+    const size_t nu = (size_t)n_u, ne = (size_t)n_entries, n_blk = ((size_t)n_mp + kBlock - 1) / kBlock;
     // upload block: problems | list entries; then (host only) the row counts
-    const size_t o_u = 0, o_en = o_u + ms_align_up(sizeof(UDev) * nu, a4), up_bytes = o_en + ms_align_up(12 * ne, a4), o_down = up_bytes,
-                 host_bytes = o_down + ms_align_up(4 * nu, a4);
+    MsLayout up;
+    const auto l_u = up.array<UDev>(nu);
+    const auto l_en = up.array<int32_t>(3 * ne);
+    MsLayout host = up, dev = up;
+    const auto l_down = host.array<int32_t>(nu);
     // device-only block: row counts | marks | block counts | block offsets
-    const size_t o_nr = up_bytes, o_mark = o_nr + ms_align_up(4 * nu, a4), o_bc = o_mark + ms_align_up(4 * nu * (size_t)n_mp, a4),
-                 o_bo = o_bc + ms_align_up(4 * nu * n_blk, a4), dev_bytes = o_bo + ms_align_up(4 * nu * n_blk, a4);
+    const auto l_nr = dev.array<int32_t>(nu), l_mark = dev.array<int32_t>(nu * (size_t)n_mp);
+    const auto l_bc = dev.array<int32_t>(nu * n_blk), l_bo = dev.array<int32_t>(nu * n_blk);
     MS_HIP(c, hipSetDevice(c->device));
-    if ((rc = grow(c, c->cv_host, c->cv_host_bytes, host_bytes, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->cv_host);
-    if ((rc = grow(c, c->cv_dev, c->cv_dev_bytes, dev_bytes, false))) return rc;
-    uint8_t *ds = static_cast<uint8_t *>(c->cv_dev);
-    UDev *hu = reinterpret_cast<UDev *>(hs + o_u);
-    int32_t *he = reinterpret_cast<int32_t *>(hs + o_en);
+    MsWorkspace &W = c->ws[MS_WS_COVIS];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    UDev *hu = l_u.at(hs);
+    int32_t *he = l_en.at(hs);
     bool any_exclude = false;
     for (int u = 0, at = 0; u < n_u; ++u) {
         const ms_union_problem &P = problems[u];
@@ -373,16 +353,13 @@ extern "C" int ms_map_point_union(ms_ctx *c, const int32_t *kf_mp, int n_kf, int
         any_exclude |= P.exclude_slot >= 0;
         for (int p = 0; p < P.count; ++p, ++at) { he[3 * at] = u; he[3 * at + 1] = p; he[3 * at + 2] = kf_list[P.first + p]; }
     }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     UnionArgs A;
     A.kf_mp = kf_mp; A.mp_flags = mp_flags;
-    A.u = reinterpret_cast<const UDev *>(ds + o_u);
-    A.entry = reinterpret_cast<const int32_t *>(ds + o_en);
-    A.mark = reinterpret_cast<int32_t *>(ds + o_mark);
-    A.blk_count = reinterpret_cast<int32_t *>(ds + o_bc);
-    A.blk_off = reinterpret_cast<int32_t *>(ds + o_bo);
+    A.u = l_u.at(ds); A.entry = l_en.at(ds);
+    A.mark = l_mark.at(ds); A.blk_count = l_bc.at(ds); A.blk_off = l_bo.at(ds);
     A.rows = rows; A.owner = owner;
-    A.n_rows = reinterpret_cast<int32_t *>(ds + o_nr);
+    A.n_rows = l_nr.at(ds);
     A.n_kf = n_kf; A.stride = stride; A.n_mp = n_mp; A.n_u = n_u; A.n_blk = (int32_t)n_blk; A.per_slot = ms_div_up(stride, kBlock);
     const size_t n_mark = nu * (size_t)n_mp;
     const dim3 block(kBlock), by_row((unsigned)n_blk, (unsigned)n_u);
@@ -402,8 +379,8 @@ extern "C" int ms_map_point_union(ms_ctx *c, const int32_t *kf_mp, int n_kf, int
     MS_KERNEL_CHECK(c, "k_union_offsets");
     hipLaunchKernelGGL(k_union_pack, by_row, block, 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_union_pack");
-    MS_HIP(c, hipMemcpyAsync(hs + o_down, ds + o_nr, 4 * nu, hipMemcpyDeviceToHost, c->stream));
+    MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_nr.at(ds), l_nr.bytes(), hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(n_rows, hs + o_down, 4 * nu);
+    std::memcpy(n_rows, l_down.at(hs), l_down.bytes());
     return MS_OK;
 }

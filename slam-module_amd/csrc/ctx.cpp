@@ -64,6 +64,34 @@ int ms_scratch(ms_ctx *c, size_t bytes, void **out) {
 
 std::atomic<long long> g_ms_host_allocs{0};
 
+int ms_grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
+    if (bytes <= cap) return MS_OK;
+    if (p) {
+        MS_HIP(c, hipStreamSynchronize(c->stream));
+        if (pinned) MS_HIP(c, hipHostFree(p));
+        else MS_HIP(c, hipFree(p));
+    }
+    p = nullptr; cap = 0;
+    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
+    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
+    else MS_HIP(c, hipMalloc(&p, want));
+    cap = want;
+    ++g_ms_host_allocs;
+    return MS_OK;
+}
+
+bool ms_distinct_in_range(const int32_t *idx, int n, int limit, int *bad) {
+    for (int i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= limit) { *bad = i; return false; }
+    thread_local std::vector<int32_t> tmp;
+    if (tmp.capacity() < (size_t)n) { tmp.reserve((size_t)n + (size_t)n / 2); ++g_ms_host_allocs; }
+    tmp.assign(idx, idx + n);
+    std::sort(tmp.begin(), tmp.end());
+    for (int i = 1; i < n; ++i)
+        if (tmp[i - 1] == tmp[i]) { *bad = -1 - tmp[i]; return false; }
+    return true;
+}
+
 extern "C" {
 
 long long ms_debug_host_allocs(void) { return g_ms_host_allocs.load(); }
@@ -142,18 +170,10 @@ void ms_ctx_destroy(ms_ctx *c) {
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->lr_dev) (void)hipFree(c->lr_dev);
-    if (c->lr_host) (void)hipHostFree(c->lr_host);
-    if (c->s3_dev) (void)hipFree(c->s3_dev);
-    if (c->s3_host) (void)hipHostFree(c->s3_host);
-    if (c->pg_dev) (void)hipFree(c->pg_dev);
-    if (c->pg_host) (void)hipHostFree(c->pg_host);
-    if (c->mr_dev) (void)hipFree(c->mr_dev);
-    if (c->mr_host) (void)hipHostFree(c->mr_host);
-    if (c->cv_dev) (void)hipFree(c->cv_dev);
-    if (c->cv_host) (void)hipHostFree(c->cv_host);
-    if (c->tr_dev) (void)hipFree(c->tr_dev);
-    if (c->tr_host) (void)hipHostFree(c->tr_host);
+    for (auto &w : c->ws) {
+        if (w.dev) (void)hipFree(w.dev);
+        if (w.host) (void)hipHostFree(w.host);
+    }
     for (auto &b : c->ba_cache) if (b.p) (void)hipFree(b.p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

@@ -357,23 +357,6 @@ __global__ __launch_bounds__(256) void k_ransac_finish(const LrDesc *__restrict_
     }
 }
 
-// grow-only context workspace
-int grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
-    if (bytes <= cap) return MS_OK;
-    if (p) {
-        MS_HIP(c, hipStreamSynchronize(c->stream));
-        if (pinned) MS_HIP(c, hipHostFree(p));
-        else MS_HIP(c, hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
-    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-    else MS_HIP(c, hipMalloc(&p, want));
-    cap = want;
-    ++g_ms_host_allocs;
-    return MS_OK;
-}
-
 bool cam_ok(const ms_pinhole &c) { return c.width >= 1 && c.height >= 1; }
 
 }  // namespace
@@ -410,70 +393,78 @@ extern "C" int ms_loop_ransac(ms_ctx *c, const ms_loop_ransac_problem *problems,
         max_iter = std::max(max_iter, P.n_iter);
     }
     // upload block: descriptors | pts1 | pts2 | thr1 | thr2 | samples
-    const size_t o_desc = 0, o_p1 = ms_align_up(sizeof(LrDesc) * n, 256), o_p2 = o_p1 + ms_align_up(24 * (size_t)M, 256),
-                 o_t1 = o_p2 + ms_align_up(24 * (size_t)M, 256), o_t2 = o_t1 + ms_align_up(4 * (size_t)M, 256),
-                 o_smp = o_t2 + ms_align_up(4 * (size_t)M, 256), up_bytes = o_smp + ms_align_up(12 * (size_t)H, 256);
-    // download block: results | union masks | best masks | per-hypothesis counts
-    const size_t o_res = 0, o_um = ms_align_up(sizeof(ms_loop_ransac_result) * n, 256), o_sm = o_um + ms_align_up((size_t)M, 256),
-                 o_cnt = o_sm + ms_align_up((size_t)M, 256), down_all = o_cnt + ms_align_up(4 * (size_t)H, 256);
+    const size_t np = (size_t)n, nm_all = (size_t)M, nh = (size_t)H;
+    MsLayout up;
+    const auto l_desc = up.array<LrDesc>(np);
+    const auto l_p1 = up.array<double>(3 * nm_all), l_p2 = up.array<double>(3 * nm_all);
+    const auto l_t1 = up.array<float>(nm_all), l_t2 = up.array<float>(nm_all);
+    const auto l_smp = up.array<int32_t>(3 * nh);
+    // download block (offsets from its own start): results | union masks | best masks | per-hypothesis counts
+    MsLayout down;
+    const auto l_res = down.array<ms_loop_ransac_result>(np);
+    const auto l_um = down.array<uint8_t>(nm_all), l_sm = down.array<uint8_t>(nm_all);
+    const auto l_cnt = down.array<int32_t>(nh);
     bool want_counts = false;
     if (hyp_inliers)
         for (int p = 0; p < n; ++p) want_counts |= hyp_inliers[p] != nullptr && problems[p].n_iter > 0;
-    const size_t down_bytes = want_counts ? down_all : o_cnt;
-    // device-only work block: hypotheses | keys | first inlier iterations
-    const size_t o_hyp = up_bytes + down_all, o_key = o_hyp + ms_align_up(sizeof(LrHyp) * (size_t)H, 256),
-                 o_first = o_key + ms_align_up(8 * (size_t)n, 256), dev_bytes = o_first + ms_align_up(4 * (size_t)M, 256);
+    const size_t down_bytes = want_counts ? down.end : l_cnt.off;
+    // host block: upload block | download block; the device block goes on with the work block: hypotheses | keys | first inlier iterations
+    MsLayout host = up;
+    const size_t o_down = host.take(down.end);
+    MsLayout dev = host;
+    const auto l_hyp = dev.array<LrHyp>(nh);
+    const auto l_key = dev.array<unsigned long long>(np);
+    const auto l_first = dev.array<uint32_t>(nm_all);
     MS_HIP(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = grow(c, c->lr_dev, c->lr_dev_bytes, dev_bytes, false)) || (rc = grow(c, c->lr_host, c->lr_host_bytes, up_bytes + down_all, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->lr_host), *ds = static_cast<uint8_t *>(c->lr_dev);
-    LrDesc *hd = reinterpret_cast<LrDesc *>(hs + o_desc);
+    MsWorkspace &W = c->ws[MS_WS_LOOP_RANSAC];
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false)) || (rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    LrDesc *hd = l_desc.at(hs);
     long long mo = 0, ho = 0;
     for (int p = 0; p < n; ++p) {
         const ms_loop_ransac_problem &P = problems[p];
         const bool early = P.n_matches < 3 || P.n_matches < P.min_inliers;
         const int it = early ? 0 : P.n_iter;
         hd[p] = LrDesc{mo, ho, P.n_matches, it, P.dof, P.fix_scale ? 1 : 0, P.min_inliers, early ? 1 : 0, P.cam1, P.cam2};
-        if (P.n_matches > 0) {
-            std::memcpy(hs + o_p1 + 24 * mo, P.pts1, 24 * (size_t)P.n_matches);
-            std::memcpy(hs + o_p2 + 24 * mo, P.pts2, 24 * (size_t)P.n_matches);
-            std::memcpy(hs + o_t1 + 4 * mo, P.thr1, 4 * (size_t)P.n_matches);
-            std::memcpy(hs + o_t2 + 4 * mo, P.thr2, 4 * (size_t)P.n_matches);
-        }
-        if (it > 0) std::memcpy(hs + o_smp + 12 * ho, P.samples, 12 * (size_t)it);
+        const size_t nm = (size_t)P.n_matches;
+        l_p1.put(hs, 3 * (size_t)mo, P.pts1, 3 * nm);
+        l_p2.put(hs, 3 * (size_t)mo, P.pts2, 3 * nm);
+        l_t1.put(hs, (size_t)mo, P.thr1, nm);
+        l_t2.put(hs, (size_t)mo, P.thr2, nm);
+        l_smp.put(hs, 3 * (size_t)ho, P.samples, 3 * (size_t)it);
         mo += P.n_matches;
         ho += it;
     }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
-    const LrDesc *dd = reinterpret_cast<const LrDesc *>(ds + o_desc);
-    const double *dp1 = reinterpret_cast<const double *>(ds + o_p1), *dp2 = reinterpret_cast<const double *>(ds + o_p2);
-    const float *dt1 = reinterpret_cast<const float *>(ds + o_t1), *dt2 = reinterpret_cast<const float *>(ds + o_t2);
-    uint8_t *dout = ds + up_bytes;
-    LrHyp *dh = reinterpret_cast<LrHyp *>(ds + o_hyp);
-    unsigned long long *dk = reinterpret_cast<unsigned long long *>(ds + o_key);
-    uint32_t *df = reinterpret_cast<uint32_t *>(ds + o_first);
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
+    const LrDesc *dd = l_desc.at(ds);
+    const double *dp1 = l_p1.at(ds), *dp2 = l_p2.at(ds);
+    const float *dt1 = l_t1.at(ds), *dt2 = l_t2.at(ds);
+    void *dout = ms_at<uint8_t>(ds, o_down), *hout = ms_at<uint8_t>(hs, o_down);
+    LrHyp *dh = l_hyp.at(ds);
+    unsigned long long *dk = l_key.at(ds);
+    uint32_t *df = l_first.at(ds);
     hipLaunchKernelGGL(k_ransac_hyp, dim3((unsigned)std::max(1, ms_div_up(max_iter, kHypPerLane)), (unsigned)n), dim3(kHypPerLane), 0, c->stream,
-                       dd, dp1, dp2, reinterpret_cast<const int32_t *>(ds + o_smp), dh, dk, df);
+                       dd, dp1, dp2, l_smp.at(ds), dh, dk, df);
     MS_KERNEL_CHECK(c, "k_ransac_hyp");
     if (max_iter > 0) {
         hipLaunchKernelGGL(k_ransac_count, dim3((unsigned)ms_div_up(max_iter, kHypPerBlock), (unsigned)n), dim3(256), 0, c->stream,
-                           dd, dp1, dp2, dt1, dt2, dh, dk, df, reinterpret_cast<int32_t *>(dout + o_cnt));
+                           dd, dp1, dp2, dt1, dt2, dh, dk, df, l_cnt.at(dout));
         MS_KERNEL_CHECK(c, "k_ransac_count");
     }
     hipLaunchKernelGGL(k_ransac_finish, dim3((unsigned)n), dim3(256), 0, c->stream, dd, dp1, dp2, dt1, dt2, dh, dk, df,
-                       reinterpret_cast<ms_loop_ransac_result *>(dout + o_res), dout + o_um, dout + o_sm);
+                       l_res.at(dout), l_um.at(dout), l_sm.at(dout));
     MS_KERNEL_CHECK(c, "k_ransac_finish");
-    uint8_t *hout = hs + up_bytes;
     MS_HIP(c, hipMemcpyAsync(hout, dout, down_bytes, hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(results, hout + o_res, sizeof(ms_loop_ransac_result) * n);
+    l_res.get(hout, 0, results, np);
     mo = 0; ho = 0;
     for (int p = 0; p < n; ++p) {
         const int nm = problems[p].n_matches, it = hd[p].n_iter;
-        if (union_inliers && union_inliers[p] && nm > 0) std::memcpy(union_inliers[p], hout + o_um + mo, (size_t)nm);
-        if (best_inliers && best_inliers[p] && nm > 0) std::memcpy(best_inliers[p], hout + o_sm + mo, (size_t)nm);
+        if (union_inliers && union_inliers[p]) l_um.get(hout, (size_t)mo, union_inliers[p], (size_t)nm);
+        if (best_inliers && best_inliers[p]) l_sm.get(hout, (size_t)mo, best_inliers[p], (size_t)nm);
         if (hyp_inliers && hyp_inliers[p] && problems[p].n_iter > 0) {
-            if (it > 0) std::memcpy(hyp_inliers[p], hout + o_cnt + 4 * ho, 4 * (size_t)it);
+            if (it > 0) l_cnt.get(hout, (size_t)ho, hyp_inliers[p], (size_t)it);
             else std::memset(hyp_inliers[p], 0, 4 * (size_t)problems[p].n_iter);      // early return: nothing was tried
         }
         mo += nm;

@@ -244,76 +244,36 @@ __global__ __launch_bounds__(kBlock) void k_loop_points(const LoopArgs A) {
     p[2] = s * (X[6] * x + X[7] * y + X[8] * z) + X[11];
 }
 
-// grow-only context workspace
-int grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
-    if (bytes <= cap) return MS_OK;
-    if (p) {
-        MS_HIP(c, hipStreamSynchronize(c->stream));
-        if (pinned) MS_HIP(c, hipHostFree(p));
-        else MS_HIP(c, hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
-    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-    else MS_HIP(c, hipMalloc(&p, want));
-    cap = want;
-    ++g_ms_host_allocs;
-    return MS_OK;
-}
-
-// true when idx[0 .. n) are distinct values of [0, limit).  The sorted copy lives in a per-thread vector that only grows.
-bool distinct_in_range(const int32_t *idx, int n, int limit, int *bad) {
-    for (int i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= limit) { *bad = i; return false; }
-    thread_local std::vector<int32_t> tmp;
-    if (tmp.capacity() < (size_t)n) { tmp.reserve((size_t)n + (size_t)n / 2); ++g_ms_host_allocs; }
-    tmp.assign(idx, idx + n);
-    std::sort(tmp.begin(), tmp.end());
-    for (int i = 1; i < n; ++i)
-        if (tmp[i - 1] == tmp[i]) { *bad = -1 - tmp[i]; return false; }
-    return true;
-}
-
-int why_not(char *why, size_t bytes, const char *fmt, ...) {
-    if (why && bytes) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(why, bytes, fmt, ap);
-        va_end(ap);
-    }
-    return MS_ERR_INVALID;
-}
-
 }  // namespace
 
 extern "C" int ms_map_refresh_check(const double *mp_pos, const float *mp_norm, const float *mp_min_dist, const float *mp_max_dist, const uint32_t *mp_desc, int n_mp,
                                     const double *kf_pose, int n_kf, const uint32_t *desc_pool, int n_pool, const int32_t *rows, int n_rows,
                                     const int32_t *obs_start, const int32_t *obs_kf, const int32_t *obs_desc, const int32_t *first_octave,
                                     const float *scale_factors, int n_levels, char *why, size_t why_bytes) {
-    if (n_mp < 0 || n_kf < 0 || n_pool < 0 || n_rows < 0 || n_levels < 1 || !scale_factors) return why_not(why, why_bytes, "map refresh: bad arguments");
+    if (n_mp < 0 || n_kf < 0 || n_pool < 0 || n_rows < 0 || n_levels < 1 || !scale_factors) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: bad arguments");
     if (n_rows == 0) return MS_OK;
     if (!mp_pos || !mp_norm || !mp_min_dist || !mp_max_dist || !kf_pose || !rows || !obs_start || !obs_kf || !first_octave)
-        return why_not(why, why_bytes, "map refresh: missing array");
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: missing array");
     const bool with_desc = desc_pool != nullptr && obs_desc != nullptr;
-    if (with_desc && !mp_desc) return why_not(why, why_bytes, "map refresh: a descriptor pool without the table's descriptors");
+    if (with_desc && !mp_desc) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: a descriptor pool without the table's descriptors");
     if (with_desc && ((reinterpret_cast<uintptr_t>(mp_desc) | reinterpret_cast<uintptr_t>(desc_pool)) & 15u))
-        return why_not(why, why_bytes, "map refresh: descriptor arrays must be 16-byte aligned");
-    if (obs_start[0] != 0) return why_not(why, why_bytes, "map refresh: obs_start[0] = %d", obs_start[0]);
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: descriptor arrays must be 16-byte aligned");
+    if (obs_start[0] != 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: obs_start[0] = %d", obs_start[0]);
     for (int r = 0; r < n_rows; ++r) {
-        if (obs_start[r + 1] < obs_start[r]) return why_not(why, why_bytes, "map refresh: obs_start decreases at row entry %d", r);
-        if (obs_start[r + 1] == obs_start[r]) return why_not(why, why_bytes, "map refresh: row entry %d has no observations", r);
+        if (obs_start[r + 1] < obs_start[r]) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: obs_start decreases at row entry %d", r);
+        if (obs_start[r + 1] == obs_start[r]) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row entry %d has no observations", r);
         if (first_octave[r] < 0 || first_octave[r] >= n_levels)
-            return why_not(why, why_bytes, "map refresh: row entry %d: octave %d outside [0, %d)", r, first_octave[r], n_levels);
+            return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row entry %d: octave %d outside [0, %d)", r, first_octave[r], n_levels);
     }
     for (int o = 0; o < obs_start[n_rows]; ++o) {
-        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) return why_not(why, why_bytes, "map refresh: observation %d: keyframe slot %d outside [0, %d)", o, obs_kf[o], n_kf);
+        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: observation %d: keyframe slot %d outside [0, %d)", o, obs_kf[o], n_kf);
         if (with_desc && (obs_desc[o] < -1 || obs_desc[o] >= n_pool))
-            return why_not(why, why_bytes, "map refresh: observation %d: descriptor %d outside [0, %d)", o, obs_desc[o], n_pool);
+            return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: observation %d: descriptor %d outside [0, %d)", o, obs_desc[o], n_pool);
     }
     int bad = 0;
-    if (!distinct_in_range(rows, n_rows, n_mp, &bad)) {
-        if (bad >= 0) return why_not(why, why_bytes, "map refresh: row entry %d: row %d outside [0, %d)", bad, rows[bad], n_mp);
-        return why_not(why, why_bytes, "map refresh: row %d is listed twice", -1 - bad);
+    if (!ms_distinct_in_range(rows, n_rows, n_mp, &bad)) {
+        if (bad >= 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row entry %d: row %d outside [0, %d)", bad, rows[bad], n_mp);
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row %d is listed twice", -1 - bad);
     }
     return MS_OK;
 }
@@ -339,25 +299,28 @@ extern "C" int ms_map_refresh(ms_ctx *c, const double *mp_pos, float *mp_norm, f
     }
     MsRange range("mapRefresh");
     // upload block: rows | octaves | obs_start | obs_kf | scale factors | packed descriptor lists: start, pool index; then (host only) medoids
-    const size_t nr = (size_t)n_rows, a4 = 256;
-    const size_t o_rows = 0, o_oct = o_rows + ms_align_up(4 * nr, a4), o_start = o_oct + ms_align_up(4 * nr, a4), o_kf = o_start + ms_align_up(4 * (nr + 1), a4),
-                 o_sf = o_kf + ms_align_up(4 * (size_t)n_obs, a4), o_dstart = o_sf + ms_align_up(4 * (size_t)n_levels, a4),
-                 o_dsrc = o_dstart + ms_align_up(4 * (nr + 1), a4), up_bytes = o_dsrc + ms_align_up(4 * (size_t)n_dobs, a4),
-                 o_down = up_bytes, host_bytes = o_down + ms_align_up(4 * nr, a4);
-    // device-only block: camera centres | packed descriptors | identity list | medoids
-    const size_t o_centre = up_bytes, o_packed = o_centre + ms_align_up(24 * (size_t)n_kf, a4), o_ident = o_packed + ms_align_up(32 * (size_t)n_dobs + 32, a4),
-                 o_best = o_ident + ms_align_up(4 * (size_t)n_dobs + 4, a4), dev_bytes = o_best + ms_align_up(4 * nr, a4);
+    const size_t nr = (size_t)n_rows, nd = (size_t)n_dobs;
+    MsLayout up;
+    const auto l_rows = up.array<int32_t>(nr), l_oct = up.array<int32_t>(nr), l_start = up.array<int32_t>(nr + 1), l_kf = up.array<int32_t>((size_t)n_obs);
+    const auto l_sf = up.array<float>((size_t)n_levels);
+    const auto l_dstart = up.array<int32_t>(nr + 1), l_dsrc = up.array<int32_t>(nd);
+    MsLayout host = up, dev = up;
+    const auto l_down = host.array<int32_t>(nr);
+    // device-only block: camera centres | packed descriptors | identity list | medoids (the descriptors and the list with one entry of slack)
+    const auto l_centre = dev.array<double>(3 * (size_t)n_kf);
+    const auto l_packed = dev.array<uint4>(2 * nd + 2);
+    const auto l_ident = dev.array<int32_t>(nd + 1), l_best = dev.array<int32_t>(nr);
     MS_HIP(c, hipSetDevice(c->device));
-    if ((rc = grow(c, c->mr_host, c->mr_host_bytes, host_bytes, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->mr_host);
-    if ((rc = grow(c, c->mr_dev, c->mr_dev_bytes, dev_bytes, false))) return rc;
-    uint8_t *ds = static_cast<uint8_t *>(c->mr_dev);
-    std::memcpy(hs + o_rows, rows, 4 * nr);
-    std::memcpy(hs + o_oct, first_octave, 4 * nr);
-    std::memcpy(hs + o_start, obs_start, 4 * (nr + 1));
-    std::memcpy(hs + o_kf, obs_kf, 4 * (size_t)n_obs);
-    std::memcpy(hs + o_sf, scale_factors, 4 * (size_t)n_levels);
-    int32_t *dstart = reinterpret_cast<int32_t *>(hs + o_dstart), *dsrc = reinterpret_cast<int32_t *>(hs + o_dsrc);
+    MsWorkspace &W = c->ws[MS_WS_MAP_REFRESH];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    l_rows.fill(hs, rows);
+    l_oct.fill(hs, first_octave);
+    l_start.fill(hs, obs_start);
+    l_kf.fill(hs, obs_kf);
+    l_sf.fill(hs, scale_factors);
+    int32_t *dstart = l_dstart.at(hs), *dsrc = l_dsrc.at(hs);
     dstart[0] = 0;
     for (int r = 0, at = 0; r < n_rows; ++r) {               // the `descriptors` vector of :76-84: observations of keyframes that have descriptors
         if (with_desc)
@@ -365,34 +328,33 @@ extern "C" int ms_map_refresh(ms_ctx *c, const double *mp_pos, float *mp_norm, f
                 if (obs_desc[o] != -1) dsrc[at++] = obs_desc[o];
         dstart[r + 1] = at;
     }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
-    auto I = [&](size_t o) { return reinterpret_cast<int32_t *>(ds + o); };
-    double *centre = reinterpret_cast<double *>(ds + o_centre);
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
+    double *centre = l_centre.at(ds);
     hipLaunchKernelGGL(k_refresh_centres, dim3(ms_div_up(std::max(n_kf, 1), kBlock)), dim3(kBlock), 0, c->stream, kf_pose, n_kf, centre);
     MS_KERNEL_CHECK(c, "k_refresh_centres");
     RefreshArgs A;
     A.mp_pos = mp_pos; A.centre = centre; A.mp_norm = mp_norm; A.mp_min = mp_min_dist; A.mp_max = mp_max_dist;
-    A.rows = I(o_rows); A.obs_start = I(o_start); A.obs_kf = I(o_kf); A.octave = I(o_oct);
-    A.sf = reinterpret_cast<const float *>(ds + o_sf);
+    A.rows = l_rows.at(ds); A.obs_start = l_start.at(ds); A.obs_kf = l_kf.at(ds); A.octave = l_oct.at(ds);
+    A.sf = l_sf.at(ds);
     A.n_rows = n_rows; A.n_levels = n_levels;
     hipLaunchKernelGGL(k_refresh_geom, dim3((unsigned)((nr * kTeam + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_refresh_geom");
     if (with_desc) {
-        uint4 *packed = reinterpret_cast<uint4 *>(ds + o_packed);
+        uint4 *packed = l_packed.at(ds);
         hipLaunchKernelGGL(k_refresh_gather, dim3(ms_div_up(std::max(2 * n_dobs, 1), kBlock)), dim3(kBlock), 0, c->stream,
-                           reinterpret_cast<const uint4 *>(desc_pool), I(o_dsrc), n_dobs, packed, I(o_ident));
+                           reinterpret_cast<const uint4 *>(desc_pool), l_dsrc.at(ds), n_dobs, packed, l_ident.at(ds));
         MS_KERNEL_CHECK(c, "k_refresh_gather");
-        if ((rc = ms_descriptor_medoid(c, reinterpret_cast<const uint32_t *>(packed), I(o_dstart), I(o_ident), n_rows, std::min(longest, MS_MEDOID_MAX_OBS),
-                                       I(o_best), nullptr)))
+        if ((rc = ms_descriptor_medoid(c, reinterpret_cast<const uint32_t *>(packed), l_dstart.at(ds), l_ident.at(ds), n_rows, std::min(longest, MS_MEDOID_MAX_OBS),
+                                       l_best.at(ds), nullptr)))
             return rc;
-        hipLaunchKernelGGL(k_refresh_winner, dim3(ms_div_up(2 * n_rows, kBlock)), dim3(kBlock), 0, c->stream, packed, I(o_dstart), I(o_best), I(o_rows), n_rows,
+        hipLaunchKernelGGL(k_refresh_winner, dim3(ms_div_up(2 * n_rows, kBlock)), dim3(kBlock), 0, c->stream, packed, l_dstart.at(ds), l_best.at(ds), l_rows.at(ds), n_rows,
                            reinterpret_cast<uint4 *>(mp_desc));
         MS_KERNEL_CHECK(c, "k_refresh_winner");
-        if (medoid) MS_HIP(c, hipMemcpyAsync(hs + o_down, ds + o_best, 4 * nr, hipMemcpyDeviceToHost, c->stream));
+        if (medoid) MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_best.at(ds), l_best.bytes(), hipMemcpyDeviceToHost, c->stream));
     }
     MS_HIP(c, hipStreamSynchronize(c->stream));
     if (medoid) {
-        const int32_t *best = reinterpret_cast<const int32_t *>(hs + o_down);
+        const int32_t *best = l_down.at(hs);
         for (int r = 0; r < n_rows; ++r) {
             int m = with_desc ? best[r] : -1;
             if (m >= 0)                                      // position among the descriptors -> position in the row's observation list
@@ -406,24 +368,24 @@ extern "C" int ms_map_refresh(ms_ctx *c, const double *mp_pos, float *mp_norm, f
 
 extern "C" int ms_loop_correct_check(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const double *T, const int32_t *kf_slot, const uint8_t *kf_rigid,
                                      const double *kf_lambda, int n_corr, const int32_t *mp_row, const int32_t *mp_ref, int n_pts, char *why, size_t why_bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_corr < 0 || n_pts < 0 || !T) return why_not(why, why_bytes, "loop correct: bad arguments");
+    if (n_kf < 0 || n_mp < 0 || n_corr < 0 || n_pts < 0 || !T) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: bad arguments");
     for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(T[k])) return why_not(why, why_bytes, "loop correct: T[%d] is not finite", k);
+        if (!std::isfinite(T[k])) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: T[%d] is not finite", k);
     if ((n_corr > 0 && (!kf_pose || !kf_slot || !kf_rigid || !kf_lambda)) || (n_pts > 0 && (!mp_pos || !mp_row || !mp_ref)))
-        return why_not(why, why_bytes, "loop correct: missing array");
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: missing array");
     for (int i = 0; i < n_corr; ++i)                         // a rigid member's lambda is not read
         if (!kf_rigid[i] && !(kf_lambda[i] >= 0.0 && kf_lambda[i] <= 1.0))
-            return why_not(why, why_bytes, "loop correct: keyframe entry %d: lambda %g outside [0, 1]", i, kf_lambda[i]);
+            return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: keyframe entry %d: lambda %g outside [0, 1]", i, kf_lambda[i]);
     for (int j = 0; j < n_pts; ++j)
-        if (mp_ref[j] < 0 || mp_ref[j] >= n_corr) return why_not(why, why_bytes, "loop correct: point entry %d: reference %d outside [0, %d)", j, mp_ref[j], n_corr);
+        if (mp_ref[j] < 0 || mp_ref[j] >= n_corr) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: point entry %d: reference %d outside [0, %d)", j, mp_ref[j], n_corr);
     int bad = 0;
-    if (!distinct_in_range(kf_slot, n_corr, n_kf, &bad)) {
-        if (bad >= 0) return why_not(why, why_bytes, "loop correct: keyframe entry %d: slot %d outside [0, %d)", bad, kf_slot[bad], n_kf);
-        return why_not(why, why_bytes, "loop correct: keyframe slot %d is listed twice", -1 - bad);
+    if (!ms_distinct_in_range(kf_slot, n_corr, n_kf, &bad)) {
+        if (bad >= 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: keyframe entry %d: slot %d outside [0, %d)", bad, kf_slot[bad], n_kf);
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: keyframe slot %d is listed twice", -1 - bad);
     }
-    if (!distinct_in_range(mp_row, n_pts, n_mp, &bad)) {
-        if (bad >= 0) return why_not(why, why_bytes, "loop correct: point entry %d: row %d outside [0, %d)", bad, mp_row[bad], n_mp);
-        return why_not(why, why_bytes, "loop correct: map-point row %d is listed twice", -1 - bad);
+    if (!ms_distinct_in_range(mp_row, n_pts, n_mp, &bad)) {
+        if (bad >= 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: point entry %d: row %d outside [0, %d)", bad, mp_row[bad], n_mp);
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: map-point row %d is listed twice", -1 - bad);
     }
     return MS_OK;
 }
@@ -435,30 +397,33 @@ extern "C" int ms_loop_correct(ms_ctx *c, double *kf_pose, int n_kf, double *mp_
     if ((rc = ms_loop_correct_check(kf_pose, n_kf, mp_pos, n_mp, T, kf_slot, kf_rigid, kf_lambda, n_corr, mp_row, mp_ref, n_pts, c->err, sizeof(c->err)))) return rc;
     if (n_corr == 0) return MS_OK;                           // no point can have a reference then
     MsRange range("loopCorrect");
-    const size_t nc = (size_t)n_corr, np = (size_t)n_pts, a4 = 256;
+    const size_t nc = (size_t)n_corr, np = (size_t)n_pts;
     // upload block: T | lambda | slots | rigid flags | point rows | point references
-    const size_t o_T = 0, o_lam = o_T + a4, o_slot = o_lam + ms_align_up(8 * nc, a4), o_rigid = o_slot + ms_align_up(4 * nc, a4), o_row = o_rigid + ms_align_up(nc, a4),
-                 o_ref = o_row + ms_align_up(4 * np, a4), up_bytes = o_ref + ms_align_up(4 * np, a4);
-    const size_t o_prev = up_bytes, o_xfer = o_prev + ms_align_up(96 * nc, a4), dev_bytes = o_xfer + ms_align_up(8 * kXfer * nc, a4);
+    MsLayout up;
+    const auto l_T = up.array<double>(8), l_lam = up.array<double>(nc);
+    const auto l_slot = up.array<int32_t>(nc);
+    const auto l_rigid = up.array<uint8_t>(nc);
+    const auto l_row = up.array<int32_t>(np), l_ref = up.array<int32_t>(np);
+    // device-only block: previous poses | keyframe transfers
+    MsLayout dev = up;
+    const auto l_prev = dev.array<double>(12 * nc), l_xfer = dev.array<double>(kXfer * nc);
     MS_HIP(c, hipSetDevice(c->device));
-    if ((rc = grow(c, c->mr_host, c->mr_host_bytes, up_bytes, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->mr_host);
-    if ((rc = grow(c, c->mr_dev, c->mr_dev_bytes, dev_bytes, false))) return rc;
-    uint8_t *ds = static_cast<uint8_t *>(c->mr_dev);
-    std::memcpy(hs + o_T, T, 64);
-    std::memcpy(hs + o_lam, kf_lambda, 8 * nc);
-    std::memcpy(hs + o_slot, kf_slot, 4 * nc);
-    std::memcpy(hs + o_rigid, kf_rigid, nc);
-    if (np) { std::memcpy(hs + o_row, mp_row, 4 * np); std::memcpy(hs + o_ref, mp_ref, 4 * np); }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
+    MsWorkspace &W = c->ws[MS_WS_MAP_REFRESH];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, up.end, true))) return rc;
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    l_T.fill(hs, T);
+    l_lam.fill(hs, kf_lambda);
+    l_slot.fill(hs, kf_slot);
+    l_rigid.fill(hs, kf_rigid);
+    l_row.fill(hs, mp_row);
+    l_ref.fill(hs, mp_ref);
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     LoopArgs A;
     A.kf_pose = kf_pose; A.mp_pos = mp_pos;
-    A.prev = reinterpret_cast<double *>(ds + o_prev); A.xfer = reinterpret_cast<double *>(ds + o_xfer);
-    A.T = reinterpret_cast<const double *>(ds + o_T);
-    A.kf_lambda = reinterpret_cast<const double *>(ds + o_lam);
-    A.kf_slot = reinterpret_cast<const int32_t *>(ds + o_slot);
-    A.kf_rigid = ds + o_rigid;
-    A.mp_row = reinterpret_cast<const int32_t *>(ds + o_row); A.mp_ref = reinterpret_cast<const int32_t *>(ds + o_ref);
+    A.prev = l_prev.at(ds); A.xfer = l_xfer.at(ds);
+    A.T = l_T.at(ds); A.kf_lambda = l_lam.at(ds); A.kf_slot = l_slot.at(ds); A.kf_rigid = l_rigid.at(ds);
+    A.mp_row = l_row.at(ds); A.mp_ref = l_ref.at(ds);
     A.n_corr = n_corr; A.n_pts = n_pts;
     hipLaunchKernelGGL(k_loop_poses, dim3(ms_div_up(n_corr, 64)), dim3(64), 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_loop_poses");

@@ -7,6 +7,21 @@
 #include <string>
 #include <vector>
 #include "../../include/mi355slam.h"
+#include "ms_layout.h"
+
+struct MsWorkspace {
+    void *dev = nullptr, *host = nullptr;
+    size_t dev_bytes = 0, host_bytes = 0;
+};
+enum MsWorkspaceId {
+    MS_WS_LOOP_RANSAC,      // ms_loop_ransac (loop_ransac.hip): device inputs / work / results
+    MS_WS_SIM3_OPT,         // ms_sim3_optimize (sim3_opt.hip): device inputs / results
+    MS_WS_PROJECT_GATE,     // ms_project_gate (project_gate.hip): device tables / ranks / offsets
+    MS_WS_MAP_REFRESH,      // ms_map_refresh and ms_loop_correct (map_refresh.hip): device lists / centres / packed descriptors / previous poses
+    MS_WS_COVIS,            // ms_covisibility and ms_map_point_union (covis.hip): device queries / bitmaps / owner marks / block counts
+    MS_WS_TRIANGULATE,      // ms_triangulate (triangulate.hip): device lists / cameras / rays / results
+    MS_WS_COUNT
+};
 
 struct ms_ctx {
     int device = -1;
@@ -36,24 +51,8 @@ struct ms_ctx {
     hipEvent_t ba_stage_ev = nullptr;
     bool ba_stage_busy = false;
     void *ba_handle_pool[4] = {nullptr, nullptr, nullptr, nullptr};      // destroyed bundle-adjustment handle OBJECTS (their vectors keep their capacity, their event stays): ms_ba_create takes one back
-    // ms_loop_ransac's workspace (loop_ransac.hip): device inputs / work / results and their page-locked staging, grow-only
-    void *lr_dev = nullptr, *lr_host = nullptr;
-    size_t lr_dev_bytes = 0, lr_host_bytes = 0;
-    // ms_sim3_optimize's workspace (sim3_opt.hip): device inputs / results and their page-locked staging, grow-only
-    void *s3_dev = nullptr, *s3_host = nullptr;
-    size_t s3_dev_bytes = 0, s3_host_bytes = 0;
-    // ms_project_gate's workspace (project_gate.hip): device tables / ranks / offsets and their page-locked staging, grow-only
-    void *pg_dev = nullptr, *pg_host = nullptr;
-    size_t pg_dev_bytes = 0, pg_host_bytes = 0;
-    // ms_map_refresh's and ms_loop_correct's workspace (map_refresh.hip): device lists / centres / packed descriptors / previous poses and their page-locked staging, grow-only
-    void *mr_dev = nullptr, *mr_host = nullptr;
-    size_t mr_dev_bytes = 0, mr_host_bytes = 0;
-    // ms_covisibility's and ms_map_point_union's workspace (covis.hip): device queries / bitmaps / owner marks / block counts and their page-locked staging, grow-only
-    void *cv_dev = nullptr, *cv_host = nullptr;
-    size_t cv_dev_bytes = 0, cv_host_bytes = 0;
-    // ms_triangulate's workspace (triangulate.hip): device lists / cameras / rays / results and their page-locked staging, grow-only
-    void *tr_dev = nullptr, *tr_host = nullptr;
-    size_t tr_dev_bytes = 0, tr_host_bytes = 0;
+    // grow-only workspaces of the map-side entry points: a device block and its page-locked staging each (ms_grow; laid out with ms_layout.h)
+    MsWorkspace ws[MS_WS_COUNT];
     char err[512] = {0};
 };
 
@@ -72,11 +71,30 @@ int ms_ctx_order_after_downloads(ms_ctx *ctx);
 // device scratch of at least `bytes`, reused across calls on the context stream
 int ms_scratch(ms_ctx *ctx, size_t bytes, void **out);
 
+// grow-only block of a workspace: at least `bytes` in p (device memory, or page-locked host memory with `pinned`), capacity in cap.  Growing waits
+// for the context stream, frees the block and allocates half as much again as asked for; the contents are not kept.
+int ms_grow(ms_ctx *ctx, void *&p, size_t &cap, size_t bytes, bool pinned);
+
+// true when idx[0 .. n) are distinct values of [0, limit).  Otherwise *bad = the first entry outside the range, or -1 - v for a value v that is
+// listed twice (entries are ranged before duplicates are looked for).  The sorted copy lives in a per-thread vector that only grows.
+bool ms_distinct_in_range(const int32_t *idx, int n, int limit, int *bad);
+
 inline int ms_fail(ms_ctx *ctx, int code, const char *fmt, ...) {
     if (ctx) {
         va_list ap;
         va_start(ap, fmt);
         vsnprintf(ctx->err, sizeof(ctx->err), fmt, ap);
+        va_end(ap);
+    }
+    return code;
+}
+
+// ms_fail for the *_check entry points, which report into the caller's buffer (may be null)
+inline int ms_why(int code, char *why, size_t bytes, const char *fmt, ...) {
+    if (why && bytes) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(why, bytes, fmt, ap);
         va_end(ap);
     }
     return code;
@@ -122,4 +140,3 @@ struct MsRange {
 };
 
 inline int ms_div_up(int a, int b) { return (a + b - 1) / b; }
-inline size_t ms_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }

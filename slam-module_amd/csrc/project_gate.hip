@@ -204,23 +204,6 @@ __global__ __launch_bounds__(kBlock) void k_gate_pack(const GateArgs A) {
     }
 }
 
-// grow-only context workspace
-int grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
-    if (bytes <= cap) return MS_OK;
-    if (p) {
-        MS_HIP(c, hipStreamSynchronize(c->stream));
-        if (pinned) MS_HIP(c, hipHostFree(p));
-        else MS_HIP(c, hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
-    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-    else MS_HIP(c, hipMalloc(&p, want));
-    cap = want;
-    ++g_ms_host_allocs;
-    return MS_OK;
-}
-
 }  // namespace
 
 extern "C" int ms_project_gate(ms_ctx *c, const double *mp_pos, const float *mp_norm, const float *mp_min_dist, const float *mp_max_dist,
@@ -258,30 +241,35 @@ extern "C" int ms_project_gate(ms_ctx *c, const double *mp_pos, const float *mp_
     if (n_views == 0) return MS_OK;
     MsRange range("projectGate");
     // upload block: views | block table | mp_index | scale factors | (host only) the views ordered by `first`
-    const size_t nb = (size_t)n_blocks;
-    const size_t o_view = 0, o_blk = ms_align_up(sizeof(GvDev) * (size_t)n_views, 256), o_idx = o_blk + ms_align_up(8 * nb, 256),
-                 o_sf = o_idx + ms_align_up(4 * (size_t)n_entries, 256), up_bytes = o_sf + ms_align_up(4 * (size_t)n_levels, 256),
-                 o_order = up_bytes, o_down = o_order + ms_align_up(4 * (size_t)n_views, 256), host_bytes = o_down + ms_align_up(4 * (size_t)n_views, 256);
+    const size_t nb = (size_t)n_blocks, nv = (size_t)n_views, ne = (size_t)n_entries;
+    MsLayout up;
+    const auto l_view = up.array<GvDev>(nv);
+    const auto l_blk = up.array<int2>(nb);
+    const auto l_idx = up.array<int32_t>(ne);
+    const auto l_sf = up.array<float>((size_t)n_levels);
+    MsLayout host = up, dev = up;
+    const auto l_order = host.array<int32_t>(nv), l_down = host.array<int32_t>(nv);
     // device-only block: n_kept | rank | block counts | block offsets | stand-ins for per-entry outputs the caller does not want
-    const size_t ne4 = ms_align_up(4 * (size_t)n_entries, 256);
-    const size_t o_nk = up_bytes, o_rank = o_nk + ms_align_up(4 * (size_t)n_views, 256), o_bc = o_rank + ne4, o_bo = o_bc + ms_align_up(4 * nb, 256),
-                 o_x = o_bo + ms_align_up(4 * nb, 256), o_y = o_x + ne4, o_r = o_y + ne4, o_l = o_r + ne4, dev_bytes = o_l + ne4;
+    const auto l_nk = dev.array<int32_t>(nv), l_rank = dev.array<int32_t>(ne), l_bc = dev.array<int32_t>(nb), l_bo = dev.array<int32_t>(nb);
+    const auto l_x = dev.array<float>(ne), l_y = dev.array<float>(ne), l_r = dev.array<float>(ne);
+    const auto l_l = dev.array<int32_t>(ne);
     MS_HIP(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = grow(c, c->pg_host, c->pg_host_bytes, host_bytes, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->pg_host);
+    MsWorkspace &W = c->ws[MS_WS_PROJECT_GATE];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    void *hs = W.host;
     // overlapping slices: order the non-empty views by `first` (before anything is allocated on the device or written)
-    int32_t *order = reinterpret_cast<int32_t *>(hs + o_order);
+    int32_t *order = l_order.at(hs);
     int n_live = 0;
     for (int v = 0; v < n_views; ++v) if (views[v].count > 0) order[n_live++] = v;
     std::sort(order, order + n_live, [&](int32_t a, int32_t b) { return views[a].first < views[b].first; });
     for (int i = 1; i < n_live; ++i)
         if (views[order[i - 1]].first + views[order[i - 1]].count > views[order[i]].first)
             return ms_fail(c, MS_ERR_INVALID, "project gate: the slices of views %d and %d overlap", order[i - 1], order[i]);
-    if ((rc = grow(c, c->pg_dev, c->pg_dev_bytes, dev_bytes, false))) return rc;
-    uint8_t *ds = static_cast<uint8_t *>(c->pg_dev);
-    GvDev *hv = reinterpret_cast<GvDev *>(hs + o_view);
-    int2 *hb = reinterpret_cast<int2 *>(hs + o_blk);
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *ds = W.dev;
+    GvDev *hv = l_view.at(hs);
+    int2 *hb = l_blk.at(hs);
     int at = 0;
     for (int v = 0; v < n_views; ++v) {
         const ms_gate_view &V = views[v];
@@ -298,25 +286,19 @@ extern "C" int ms_project_gate(ms_ctx *c, const double *mp_pos, const float *mp_
         D.blk0 = at; D.nblk = ms_div_up(V.count, kBlock); D.pad = 0;
         for (int b = 0; b < D.nblk; ++b) hb[at++] = make_int2(v, b * kBlock);
     }
-    if (n_entries > 0) std::memcpy(hs + o_idx, mp_index, 4 * (size_t)n_entries);
-    std::memcpy(hs + o_sf, scale_factors, 4 * (size_t)n_levels);
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
+    l_idx.fill(hs, mp_index);
+    l_sf.fill(hs, scale_factors);
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     GateArgs A;
-    A.views = reinterpret_cast<const GvDev *>(ds + o_view);
-    A.blocks = reinterpret_cast<const int2 *>(ds + o_blk);
-    A.mp_index = reinterpret_cast<const int32_t *>(ds + o_idx);
-    A.sf = reinterpret_cast<const float *>(ds + o_sf);
+    A.views = l_view.at(ds); A.blocks = l_blk.at(ds); A.mp_index = l_idx.at(ds); A.sf = l_sf.at(ds);
     A.mp_pos = mp_pos; A.mp_norm = mp_norm; A.mp_min = mp_min_dist; A.mp_max = mp_max_dist; A.mp_desc = mp_desc;
     A.n_levels = n_levels; A.scale_factor = scale_factor;
     A.status = status; A.dist = dist;
-    A.x = x ? x : reinterpret_cast<float *>(ds + o_x);
-    A.y = y ? y : reinterpret_cast<float *>(ds + o_y);
-    A.radius = radius ? radius : reinterpret_cast<float *>(ds + o_r);
-    A.level = level ? level : reinterpret_cast<int32_t *>(ds + o_l);
-    A.rank = reinterpret_cast<int32_t *>(ds + o_rank);
-    A.blk_count = reinterpret_cast<int32_t *>(ds + o_bc);
-    A.blk_off = reinterpret_cast<int32_t *>(ds + o_bo);
-    A.n_kept = reinterpret_cast<int32_t *>(ds + o_nk);
+    A.x = x ? x : l_x.at(ds);
+    A.y = y ? y : l_y.at(ds);
+    A.radius = radius ? radius : l_r.at(ds);
+    A.level = level ? level : l_l.at(ds);
+    A.rank = l_rank.at(ds); A.blk_count = l_bc.at(ds); A.blk_off = l_bo.at(ds); A.n_kept = l_nk.at(ds);
     A.kept_entry = kept_entry; A.q_x = q_x; A.q_y = q_y; A.q_radius = q_radius; A.q_min_octave = q_min_octave; A.q_max_octave = q_max_octave; A.q_desc = q_desc;
     if (nb > 0) {
         hipLaunchKernelGGL(k_gate, dim3((unsigned)nb), dim3(kBlock), 0, c->stream, A);
@@ -328,8 +310,8 @@ extern "C" int ms_project_gate(ms_ctx *c, const double *mp_pos, const float *mp_
         hipLaunchKernelGGL(k_gate_pack, dim3((unsigned)nb), dim3(kBlock), 0, c->stream, A);
         MS_KERNEL_CHECK(c, "k_gate_pack");
     }
-    MS_HIP(c, hipMemcpyAsync(hs + o_down, ds + o_nk, 4 * (size_t)n_views, hipMemcpyDeviceToHost, c->stream));
+    MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_nk.at(ds), l_nk.bytes(), hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(n_kept, hs + o_down, 4 * (size_t)n_views);
+    std::memcpy(n_kept, l_down.at(hs), l_down.bytes());
     return MS_OK;
 }

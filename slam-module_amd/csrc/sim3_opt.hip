@@ -371,23 +371,6 @@ __global__ __launch_bounds__(kThreads) void k_sim3_opt(const S3Desc *__restrict_
     }
 }
 
-// grow-only context workspace
-int grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
-    if (bytes <= cap) return MS_OK;
-    if (p) {
-        MS_HIP(c, hipStreamSynchronize(c->stream));
-        if (pinned) MS_HIP(c, hipHostFree(p));
-        else MS_HIP(c, hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
-    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-    else MS_HIP(c, hipMalloc(&p, want));
-    cap = want;
-    ++g_ms_host_allocs;
-    return MS_OK;
-}
-
 }  // namespace
 
 extern "C" int ms_sim3_optimize(ms_ctx *c, const ms_sim3_opt_problem *problems, int n, ms_sim3_opt_result *results, double *const *chi2_per_edge) {
@@ -413,17 +396,27 @@ extern "C" int ms_sim3_optimize(ms_ctx *c, const ms_sim3_opt_problem *problems, 
         for (int p = 0; p < n; ++p) want_chi2 |= chi2_per_edge[p] != nullptr && problems[p].n_matches > 0;
     // upload block: descriptors | 10 planes of doubles (p1 xyz, p2 xyz, obs1 uv, obs2 uv) | 2 planes of floats (info1, info2); a plane holds every problem's matches
     const size_t stride = ms_align_up((size_t)std::max<long long>(M, 1), 32);
-    const size_t o_desc = 0, o_pl = ms_align_up(sizeof(S3Desc) * n, 256), o_info = o_pl + 8 * kPlanes * stride, up_bytes = ms_align_up(o_info + 4 * 2 * stride, 256);
-    // download block: results | chi2 per edge
-    const size_t o_res = 0, o_chi = ms_align_up(sizeof(ms_sim3_opt_result) * n, 256), down_all = o_chi + ms_align_up(16 * (size_t)M, 256);
-    const size_t down_bytes = want_chi2 ? down_all : o_chi;
+    // (the planes lie back to back: stride is a multiple of 32 elements, so each group of planes ends on a 256-byte boundary by itself)
+    MsLayout up;
+    const auto l_desc = up.array<S3Desc>((size_t)n);
+    const auto l_pl = up.array<double>(kPlanes * stride);
+    const auto l_info = up.array<float>(2 * stride);
+    // download block (offsets from its own start): results | chi2 per edge
+    MsLayout down;
+    const auto l_res = down.array<ms_sim3_opt_result>((size_t)n);
+    const auto l_chi = down.array<double>(2 * (size_t)M);
+    const size_t down_bytes = want_chi2 ? down.end : l_chi.off;
+    // host block and device block alike: upload block | download block
+    MsLayout both = up;
+    const size_t o_down = both.take(down.end);
     MS_HIP(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = grow(c, c->s3_dev, c->s3_dev_bytes, up_bytes + down_all, false)) || (rc = grow(c, c->s3_host, c->s3_host_bytes, up_bytes + down_all, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->s3_host), *ds = static_cast<uint8_t *>(c->s3_dev);
-    S3Desc *hd = reinterpret_cast<S3Desc *>(hs + o_desc);
-    double *hp = reinterpret_cast<double *>(hs + o_pl);
-    float *hi = reinterpret_cast<float *>(hs + o_info);
+    MsWorkspace &W = c->ws[MS_WS_SIM3_OPT];
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, both.end, false)) || (rc = ms_grow(c, W.host, W.host_bytes, both.end, true))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    S3Desc *hd = l_desc.at(hs);
+    double *hp = l_pl.at(hs);
+    float *hi = l_info.at(hs);
     long long mo = 0;
     for (int p = 0; p < n; ++p) {
         const ms_sim3_opt_problem &P = problems[p];
@@ -442,19 +435,18 @@ extern "C" int ms_sim3_optimize(ms_ctx *c, const ms_sim3_opt_problem *problems, 
         }
         mo += P.n_matches;
     }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
-    uint8_t *dout = ds + up_bytes, *hout = hs + up_bytes;
-    hipLaunchKernelGGL(k_sim3_opt, dim3((unsigned)n), dim3(kThreads), 0, c->stream, reinterpret_cast<const S3Desc *>(ds + o_desc),
-                       reinterpret_cast<const double *>(ds + o_pl), (long long)stride, reinterpret_cast<const float *>(ds + o_info),
-                       reinterpret_cast<ms_sim3_opt_result *>(dout + o_res), reinterpret_cast<double *>(dout + o_chi));
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
+    void *dout = ms_at<uint8_t>(ds, o_down), *hout = ms_at<uint8_t>(hs, o_down);
+    hipLaunchKernelGGL(k_sim3_opt, dim3((unsigned)n), dim3(kThreads), 0, c->stream, l_desc.at(ds), l_pl.at(ds), (long long)stride, l_info.at(ds),
+                       l_res.at(dout), l_chi.at(dout));
     MS_KERNEL_CHECK(c, "k_sim3_opt");
     MS_HIP(c, hipMemcpyAsync(hout, dout, down_bytes, hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(results, hout + o_res, sizeof(ms_sim3_opt_result) * n);
+    l_res.get(hout, 0, results, (size_t)n);
     mo = 0;
     for (int p = 0; p < n; ++p) {
         const int nm = problems[p].n_matches;
-        if (chi2_per_edge && chi2_per_edge[p] && nm > 0) std::memcpy(chi2_per_edge[p], hout + o_chi + 16 * mo, 16 * (size_t)nm);
+        if (chi2_per_edge && chi2_per_edge[p]) l_chi.get(hout, 2 * (size_t)mo, chi2_per_edge[p], 2 * (size_t)nm);
         mo += nm;
     }
     return MS_OK;

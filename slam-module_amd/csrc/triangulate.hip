@@ -432,36 +432,9 @@ __global__ __launch_bounds__(kBlock) void k_tri_points(const TriArgs A) {
     A.out[2 * (size_t)r + 1] = res.n_pass;
 }
 
-// grow-only context workspace
-int grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
-    if (bytes <= cap) return MS_OK;
-    if (p) {
-        MS_HIP(c, hipStreamSynchronize(c->stream));
-        if (pinned) MS_HIP(c, hipHostFree(p));
-        else MS_HIP(c, hipFree(p));
-    }
-    p = nullptr; cap = 0;
-    const size_t want = ms_align_up(bytes + bytes / 2, 4096);
-    if (pinned) MS_HIP(c, hipHostMalloc(&p, want, hipHostMallocDefault));
-    else MS_HIP(c, hipMalloc(&p, want));
-    cap = want;
-    ++g_ms_host_allocs;
-    return MS_OK;
-}
-
-int why_not(int code, char *why, size_t bytes, const char *fmt, ...) {
-    if (why && bytes) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(why, bytes, fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
 }  // namespace
 
-#define TRI_INVALID(...) return why_not(MS_ERR_INVALID, why, why_bytes, "triangulate: " __VA_ARGS__)
+#define TRI_INVALID(...) return ms_why(MS_ERR_INVALID, why, why_bytes, "triangulate: " __VA_ARGS__)
 
 extern "C" int ms_triangulate_check(const double *mp_pos, int n_mp, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam, const int32_t *kf_focal,
                                     const int32_t *rows, const uint8_t *was_triangulated, int n_rows, const int32_t *obs_start, const int32_t *obs_kf,
@@ -476,13 +449,13 @@ extern "C" int ms_triangulate_check(const double *mp_pos, int n_mp, const double
     for (int l = 0; l < settings->n_levels; ++l)
         if (!std::isfinite(settings->level_sigma_sq[l])) TRI_INVALID("level_sigma_sq[%d] is not finite", l);
     if (n_rows == 0) return MS_OK;
-    if (n_rows > MS_TRI_MAX_ROWS) return why_not(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d rows, at most %d per call", n_rows, MS_TRI_MAX_ROWS);
+    if (n_rows > MS_TRI_MAX_ROWS) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d rows, at most %d per call", n_rows, MS_TRI_MAX_ROWS);
     if (!mp_pos || !kf_pose || !kf_cam || !kf_focal || !rows || !was_triangulated || !obs_start) TRI_INVALID("missing array");
     if (obs_start[0] != 0) TRI_INVALID("obs_start[0] = %d", obs_start[0]);
     for (int r = 0; r < n_rows; ++r)
         if (obs_start[r + 1] < obs_start[r]) TRI_INVALID("obs_start decreases at row entry %d", r);
     const int n_obs = obs_start[n_rows];
-    if (n_obs > MS_TRI_MAX_OBS) return why_not(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d observations, at most %d per call", n_obs, MS_TRI_MAX_OBS);
+    if (n_obs > MS_TRI_MAX_OBS) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d observations, at most %d per call", n_obs, MS_TRI_MAX_OBS);
     if (n_obs > 0 && (!obs_kf || !obs_x || !obs_y || !obs_octave)) TRI_INVALID("missing array");
     for (int o = 0; o < n_obs; ++o) {
         if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) TRI_INVALID("observation %d: keyframe slot %d outside [0, %d)", o, obs_kf[o], n_kf);
@@ -491,14 +464,11 @@ extern "C" int ms_triangulate_check(const double *mp_pos, int n_mp, const double
         if (c.width < 1 || c.height < 1 || !(c.fx > 0.0) || !(c.fy > 0.0) || !std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy))
             TRI_INVALID("keyframe slot %d: bad camera (%d x %d, fx %g, fy %g)", obs_kf[o], c.width, c.height, c.fx, c.fy);
     }
-    for (int r = 0; r < n_rows; ++r)
-        if (rows[r] < 0 || rows[r] >= n_mp) TRI_INVALID("row entry %d: row %d outside [0, %d)", r, rows[r], n_mp);
-    thread_local std::vector<int32_t> tmp;                   // the sorted copy only grows
-    if (tmp.capacity() < (size_t)n_rows) { tmp.reserve((size_t)n_rows + (size_t)n_rows / 2); ++g_ms_host_allocs; }
-    tmp.assign(rows, rows + n_rows);
-    std::sort(tmp.begin(), tmp.end());
-    for (int r = 1; r < n_rows; ++r)
-        if (tmp[r - 1] == tmp[r]) TRI_INVALID("row %d is listed twice", tmp[r]);
+    int bad = 0;
+    if (!ms_distinct_in_range(rows, n_rows, n_mp, &bad)) {
+        if (bad >= 0) TRI_INVALID("row entry %d: row %d outside [0, %d)", bad, rows[bad], n_mp);
+        TRI_INVALID("row %d is listed twice", -1 - bad);
+    }
     return MS_OK;
 }
 
@@ -513,49 +483,47 @@ extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int 
         return rc;
     if (n_rows == 0) return MS_OK;
     MsRange range("triangulate");
-    const size_t nr = (size_t)n_rows, no = (size_t)obs_start[n_rows], nk = (size_t)n_kf, nl = (size_t)settings->n_levels, a4 = 256;
+    const size_t nr = (size_t)n_rows, no = (size_t)obs_start[n_rows], nk = (size_t)n_kf, nl = (size_t)settings->n_levels;
     // upload block: cameras | focal lengths | sigmas | rows | was | obs_start | obs_kf | obs_octave | obs_x | obs_y | obs_depth; then (host only) the results
-    const size_t o_cam = 0, o_focal = o_cam + ms_align_up(sizeof(ms_pinhole) * nk, a4), o_sigma = o_focal + ms_align_up(4 * nk, a4),
-                 o_rows = o_sigma + ms_align_up(4 * nl, a4), o_was = o_rows + ms_align_up(4 * nr, a4), o_start = o_was + ms_align_up(nr, a4),
-                 o_kf = o_start + ms_align_up(4 * (nr + 1), a4), o_oct = o_kf + ms_align_up(4 * no, a4), o_x = o_oct + ms_align_up(4 * no, a4),
-                 o_y = o_x + ms_align_up(4 * no, a4), o_depth = o_y + ms_align_up(4 * no, a4), up_bytes = o_depth + ms_align_up(4 * no, a4),
-                 o_down = up_bytes, host_bytes = o_down + ms_align_up(8 * nr, a4);
+    MsLayout up;
+    const auto l_cam = up.array<ms_pinhole>(nk);
+    const auto l_focal = up.array<int32_t>(nk);
+    const auto l_sigma = up.array<float>(nl);
+    const auto l_rows = up.array<int32_t>(nr);
+    const auto l_was = up.array<uint8_t>(nr);
+    const auto l_start = up.array<int32_t>(nr + 1);
+    const auto l_kf = up.array<int32_t>(no), l_oct = up.array<int32_t>(no);
+    const auto l_x = up.array<float>(no), l_y = up.array<float>(no), l_depth = up.array<float>(no);
+    MsLayout host = up, dev = up;
+    const auto l_down = host.array<int32_t>(2 * nr);
     // device-only block: rays | results
-    const size_t o_ray = up_bytes, o_out = o_ray + ms_align_up(24 * no, a4), dev_bytes = o_out + ms_align_up(8 * nr, a4);
+    const auto l_ray = dev.array<double>(3 * no);
+    const auto l_out = dev.array<int32_t>(2 * nr);
     MS_HIP(c, hipSetDevice(c->device));
-    if ((rc = grow(c, c->tr_host, c->tr_host_bytes, host_bytes, true))) return rc;
-    uint8_t *hs = static_cast<uint8_t *>(c->tr_host);
-    if ((rc = grow(c, c->tr_dev, c->tr_dev_bytes, dev_bytes, false))) return rc;
-    uint8_t *ds = static_cast<uint8_t *>(c->tr_dev);
-    std::memcpy(hs + o_cam, kf_cam, sizeof(ms_pinhole) * nk);
-    std::memcpy(hs + o_focal, kf_focal, 4 * nk);
-    std::memcpy(hs + o_sigma, settings->level_sigma_sq, 4 * nl);
-    std::memcpy(hs + o_rows, rows, 4 * nr);
-    std::memcpy(hs + o_was, was_triangulated, nr);
-    std::memcpy(hs + o_start, obs_start, 4 * (nr + 1));
-    if (no) {
-        std::memcpy(hs + o_kf, obs_kf, 4 * no);
-        std::memcpy(hs + o_oct, obs_octave, 4 * no);
-        std::memcpy(hs + o_x, obs_x, 4 * no);
-        std::memcpy(hs + o_y, obs_y, 4 * no);
-        if (obs_depth) std::memcpy(hs + o_depth, obs_depth, 4 * no);
-    }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, c->stream));
+    MsWorkspace &W = c->ws[MS_WS_TRIANGULATE];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    l_cam.fill(hs, kf_cam);
+    l_focal.fill(hs, kf_focal);
+    l_sigma.fill(hs, settings->level_sigma_sq);
+    l_rows.fill(hs, rows);
+    l_was.fill(hs, was_triangulated);
+    l_start.fill(hs, obs_start);
+    l_kf.fill(hs, obs_kf);
+    l_oct.fill(hs, obs_octave);
+    l_x.fill(hs, obs_x);
+    l_y.fill(hs, obs_y);
+    if (obs_depth) l_depth.fill(hs, obs_depth);
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     TriArgs A;
     A.mp_pos = mp_pos; A.mp_flags = mp_flags; A.kf_pose = kf_pose;
-    A.cam = reinterpret_cast<const ms_pinhole *>(ds + o_cam);
-    A.focal = reinterpret_cast<const int32_t *>(ds + o_focal);
-    A.sigma = reinterpret_cast<const float *>(ds + o_sigma);
-    A.rows = reinterpret_cast<const int32_t *>(ds + o_rows);
-    A.was = ds + o_was;
-    A.obs_start = reinterpret_cast<const int32_t *>(ds + o_start);
-    A.obs_kf = reinterpret_cast<const int32_t *>(ds + o_kf);
-    A.obs_oct = reinterpret_cast<const int32_t *>(ds + o_oct);
-    A.obs_x = reinterpret_cast<const float *>(ds + o_x);
-    A.obs_y = reinterpret_cast<const float *>(ds + o_y);
-    A.obs_depth = obs_depth ? reinterpret_cast<const float *>(ds + o_depth) : nullptr;
-    A.ray = reinterpret_cast<double *>(ds + o_ray);
-    A.out = reinterpret_cast<int32_t *>(ds + o_out);
+    A.cam = l_cam.at(ds); A.focal = l_focal.at(ds); A.sigma = l_sigma.at(ds);
+    A.rows = l_rows.at(ds); A.was = l_was.at(ds); A.obs_start = l_start.at(ds);
+    A.obs_kf = l_kf.at(ds); A.obs_oct = l_oct.at(ds); A.obs_x = l_x.at(ds); A.obs_y = l_y.at(ds);
+    A.obs_depth = obs_depth ? l_depth.at(ds) : nullptr;
+    A.ray = l_ray.at(ds);
+    A.out = l_out.at(ds);
     A.cos_two = std::cos(settings->min_angle_two_obs * M_PI / 180.0);            // checkTriangulationAngle, :560
     A.cos_multi = std::cos(settings->min_angle_multiple_obs * M_PI / 180.0);
     A.rel_thr = settings->rel_reprojection_threshold;
@@ -565,10 +533,10 @@ extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int 
     hipLaunchKernelGGL(k_tri_points, dim3((unsigned)((nr * kGroup + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_tri_points");
     const bool want = status || reason || n_pass;
-    if (want) MS_HIP(c, hipMemcpyAsync(hs + o_down, ds + o_out, 8 * nr, hipMemcpyDeviceToHost, c->stream));
+    if (want) MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_out.at(ds), l_out.bytes(), hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
     if (want) {
-        const int32_t *out = reinterpret_cast<const int32_t *>(hs + o_down);
+        const int32_t *out = l_down.at(hs);
         for (size_t r = 0; r < nr; ++r) {
             if (status) status[r] = (uint8_t)(out[2 * r] & 0xff);
             if (reason) reason[r] = (uint8_t)(out[2 * r] >> 8);

@@ -151,6 +151,7 @@ def test_prepare_process_says_when_it_is_too_late():
     The child opens /dev/kfd itself, as the runtime would (no HIP call): where the node exists (the GPU box) the late half is checked, elsewhere the early half."""
     import subprocess
     import sys
+    import mi355slam
     code = r'''
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.join(%r, "slam-module_amd"))
