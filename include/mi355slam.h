@@ -635,6 +635,83 @@ int ms_map_point_union(ms_ctx *ctx,
 int ms_map_point_union_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const int32_t *kf_list, int n_list,
                              const ms_union_problem *problems, int n_u, const int32_t *rows, const int32_t *n_rows, char *why, size_t why_bytes);
 
+/* ---- observation counts and culling on the keyframe table ---------------------------------------------------------------
+ * What cullMapPoints (mapper_helpers.cpp:349-373) and cullKeyframes (:433-482) read of a map point is mp.observations.size() and
+ * getFirstObservation(); on the device that is the transpose of kf_mp.  kf_mp, mp_flags and the validity rule are those of 9.6.  New:
+ *   mp_live (DEVICE, uint8 [n_mp])  non-zero = the row holds a map point of mapDB.mapPoints (a free row and a point whose observations
+ *                                    are all gone both count zero observations; ms_triangulate overwrites mp_flags, so no flag bit says it)
+ *   kf_id   (HOST, int32 [n_kf])    the slot's KfId, -1 for an empty slot, distinct where >= 0
+ *   kf_t    (HOST, double [n_kf])   Keyframe::t
+ *
+ * ms_observation_count:
+ *   n_obs[r]       the number of valid entries equal to r over the slots with kf_id >= 0, with multiplicity (observations.size() under
+ *                  the reference's invariant that a keyframe lists a map point at most once)
+ *   first_slot[r]  the slot with the smallest kf_id among the slots that list r (getFirstObservation, map_point.cpp:45-63); last_slot[r]
+ *                  the one with the largest (getLastObservation); -1 when n_obs[r] == 0
+ * Three launches whatever the sizes (fill, count, finish); integer atomics only (add on the counts; min / max on the slot's position in
+ * KfId order), so the same table gives the same bits on every call.  Synchronous on the context stream: one upload, no download.
+ * MS_ERR_INVALID, with nothing written and before any device call: stride < 1, a negative size, a missing table or kf_id, a non-negative
+ * kf_id listed twice.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps. */
+int ms_observation_count(ms_ctx *ctx,
+    /* DEVICE */
+    const int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    /* HOST */
+    const int32_t *kf_id,
+    /* DEVICE [n_mp], each may be NULL */
+    int32_t *n_obs, int32_t *first_slot, int32_t *last_slot);
+
+/* ms_map_cull: cullMapPoints, then cullKeyframes, on the tables in place.
+ * Pass 1, when cull_points != 0: with the counts and first observations of ms_observation_count, a LIVE row r is removed iff
+ *   reason 1   n_obs[r] == 0 (:359), or
+ *   reason 2   r is not a valid entry of current_slot, and (double)(int32)(kf_t[current_slot] - kf_t[first_slot[r]]) > min_age (the cast
+ *              truncates toward zero, the reference's `const int obsAge`), and (mp_flags[r] & 1) == 0 (:365-367).
+ * Removal is MapDB::removeMapPoint (mapdb.cpp:161-174): mp_live[r] = 0, mp_flags[r] = 0 when flags are given, n_obs[r] = 0, and every
+ * entry of kf_mp equal to r becomes -1.  A row that is not live is never removed; its entries count like any other.
+ * Pass 2: `cand` (slots; the adjacent keyframes) is sorted by descending kf_id on the host (:445) and the candidates with cand_keep[i] != 0
+ * are dropped (the first keyframe and the keyframes of loop-closure edges, :453-464).  ONE workgroup walks the rest in that order.  For a
+ * candidate, nMapPoints = its valid entries, nCritical = those with n_obs[row] <= min_obs_for_ba, n_obs being the current value: after
+ * pass 1 and after every removal made earlier in the walk.  If nCritical < nMapPoints * max_critical_ratio the slot is removed
+ * (removeKeyframe, :375-431): n_obs[row] -= 1 per valid entry, a live row that reaches 0 is removed as above (reason 3, orphaned), the
+ * whole slot becomes -1 and cand_removed[i] = 1 (i = the caller's position in cand; 0 for every other candidate).
+ * Arithmetic: ratio_float32 == 0: (double)nCritical < (double)nMapPoints * max_critical_ratio; ratio_float32 != 0:
+ * (float)nCritical < (float)nMapPoints * (float)max_critical_ratio, the product rounded once to float32 -- what C++ does for a float
+ * parameter.  min_age is compared in float64 against the truncated int: exact for an int, float or double parameter below 2^24.
+ * removed_rows / removed_why (DEVICE [n_mp]): the removed rows of both passes in ascending row order and their reasons at the same
+ * positions; what lies behind n_removed_rows of them is unspecified.  n_obs (DEVICE [n_mp], may be NULL): the counts after both passes.
+ * Eight launches whatever n_mp, n_kf and n_cand are (fill, count, points, keyframes, sweep, block counts, offsets, pack; `points` is left
+ * out for cull_points == 0); synchronous: one upload, one download (cand_removed and the two counts).  Integer atomics only; the same
+ * input gives the same bits on every call; the workspace belongs to the context and only grows.
+ * Left to the caller, who derives them from cand_removed and the downloaded removed_rows: the previousKfId / nextKfId links, the
+ * `uncertainty` accumulation, re-pointing referenceKeyframe, trackIdToMapPoint and bowIndex->remove.
+ * MS_ERR_INVALID, with nothing written and before any device call: current_slot or a candidate outside [0, n_kf); a candidate listed
+ * twice or equal to current_slot; kf_id < 0 at current_slot or at a candidate; a non-negative kf_id listed twice; kf_t of a slot with
+ * kf_id >= 0 not finite, or its difference to kf_t[current_slot] outside int32 (the reference's cast is undefined there); min_age or
+ * max_critical_ratio not finite; min_obs_for_ba < 0; stride < 1; a negative size; a missing array; mp_flags == NULL with cull_points != 0.
+ * MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_cand: MS_COVIS_MAX_QUERIES).  n_cand = 0, n_mp = 0 and cull_points = 0 are fine.
+ * ms_map_cull_check is the validation alone (no context, no device; `why` receives the message). */
+typedef struct {
+    int32_t current_slot;          /* currentKeyframe: exempts its rows from the age rule; never a candidate */
+    int32_t cull_points;           /* 0 skips the cullMapPoints pass */
+    double  min_age;               /* minMapPointCullingAge */
+    int32_t min_obs_for_ba;        /* minObservationsForBA */
+    double  max_critical_ratio;    /* keyframeCullMaxCriticalRatio */
+    int32_t ratio_float32;         /* the ratio test in float32 (a float parameter) instead of float64 */
+} ms_cull_settings;
+int ms_map_cull(ms_ctx *ctx,
+    /* DEVICE, updated in place; mp_flags may be NULL iff cull_points == 0 */
+    int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, int n_mp,
+    /* HOST */
+    const int32_t *kf_id, const double *kf_t, const int32_t *cand, const uint8_t *cand_keep /* may be NULL */, int n_cand,
+    const ms_cull_settings *settings,
+    /* DEVICE [n_mp]; n_obs and removed_why may be NULL */
+    int32_t *n_obs, int32_t *removed_rows, uint8_t *removed_why,
+    /* HOST: [n_cand], one, one */
+    uint8_t *cand_removed, int32_t *n_removed_rows, int32_t *n_removed_kf);
+int ms_map_cull_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, int n_mp,
+                      const int32_t *kf_id, const double *kf_t, const int32_t *cand, const uint8_t *cand_keep, int n_cand,
+                      const ms_cull_settings *settings, const int32_t *removed_rows, const uint8_t *cand_removed,
+                      const int32_t *n_removed_rows, const int32_t *n_removed_kf, char *why, size_t why_bytes);
+
 /* ---- the map-point triangulator -----------------------------------------------------------------------------------------
  * ms_triangulate: triangulateMapPoint (mapper_helpers.cpp:600-722; MS_TRI_TME, MS_TRI_MIDPOINT) or triangulateMapPointFirstLastObs
  * (:724-812; MS_TRI_FIRST_LAST) for chosen rows of the map-point table, positions and status flags written where ms_project_gate,

@@ -603,6 +603,7 @@ public:
     std::size_t stride() const { return stride_; }
     std::size_t mapPointCount() const { return nMp_; }
     const std::int32_t *table() const { return static_cast<const std::int32_t *>(table_); }
+    std::int32_t *mutableTable() { return static_cast<std::int32_t *>(table_); }            // what cullMap writes
 private:
     Context &ctx_;
     std::size_t n_, stride_, nMp_;
@@ -714,6 +715,9 @@ inline std::vector<std::vector<std::int32_t>> getNeighbors(Context &ctx, const D
 struct KeyframeChain {
     std::vector<std::int32_t> previous, next;
     std::vector<std::array<double, 3>> cameraCenter;
+    // what observationCounts and cullMap read in addition: per slot the KfId (-1 for an empty slot) and Keyframe::t
+    std::vector<std::int32_t> id;
+    std::vector<double> t;
 };
 
 // computeAdjacentKeyframes (mapper_helpers.cpp:144-229): the getNeighbors calls of every second keyframe of the chain behind `current`
@@ -782,6 +786,121 @@ inline LoopPoints localMapPoints(Context &ctx, const DeviceKeyframeMapPoints &ta
     if (n) {
         ctx.check(ms_dev_download(ctx.get(), out.row.data(), rows, 4 * (std::size_t)n), "ms_dev_download");
         if (withOwner) ctx.check(ms_dev_download(ctx.get(), out.reference.data(), owner, 4 * (std::size_t)n), "ms_dev_download");
+    }
+    return out;
+}
+
+// ---- observation counts and culling on the map tables (ms_observation_count, ms_map_cull) -----------------------------------------
+// Non-zero = the table row holds a map point of mapDB.mapPoints.  A free row and a point whose observations are all gone both have zero
+// observations, and triangulateMapPoints overwrites the flags, so this is an array of its own.
+class DeviceMapPointLive {
+public:
+    DeviceMapPointLive(Context &ctx, const std::vector<std::uint8_t> &live) : ctx_(ctx), n_(live.size()) {
+        ctx_.check(ms_dev_alloc(ctx_.get(), n_ + 16, &live_), "ms_dev_alloc");
+        update(0, n_, live.data());
+    }
+    ~DeviceMapPointLive() { ms_dev_free(ctx_.get(), live_); }
+    DeviceMapPointLive(const DeviceMapPointLive &) = delete;
+    void update(std::size_t first, std::size_t count, const std::uint8_t *live) {
+        if (first + count > n_) throw std::runtime_error("DeviceMapPointLive::update: range outside the table");
+        if (count) ctx_.check(ms_dev_upload(ctx_.get(), static_cast<std::uint8_t *>(live_) + first, live, count), "ms_dev_upload");
+    }
+    std::vector<std::uint8_t> download() const {
+        std::vector<std::uint8_t> out(n_);
+        if (n_) ctx_.check(ms_dev_download(ctx_.get(), out.data(), live_, n_), "ms_dev_download");
+        return out;
+    }
+    std::size_t size() const { return n_; }
+    const std::uint8_t *live() const { return static_cast<const std::uint8_t *>(live_); }
+    std::uint8_t *mutableLive() { return static_cast<std::uint8_t *>(live_); }              // what cullMap writes
+private:
+    Context &ctx_;
+    std::size_t n_;
+    void *live_ = nullptr;
+};
+
+// Per table row: mp.observations.size(), getFirstObservation() and getLastObservation() as slots (-1 for a row nobody observes).
+struct ObservationCounts {
+    std::vector<std::int32_t> count, first, last;
+};
+
+// The transpose of the keyframe table, computed where it lies: what the status promotion of mapper_helpers.cpp:1072 and the row selection of
+// :1088 read, without a std::map of observations per point on the host.  kfIds: per slot the KfId, -1 for an empty slot.
+inline ObservationCounts observationCounts(Context &ctx, const DeviceKeyframeMapPoints &table, const std::vector<std::int32_t> &kfIds) {
+    if (kfIds.size() != table.size()) throw std::invalid_argument("observationCounts: one KfId per slot");
+    const std::size_t nMp = table.mapPointCount(), pitch = (nMp + 63) / 64 * 64;
+    ObservationCounts out;
+    out.count.resize(nMp); out.first.resize(nMp); out.last.resize(nMp);
+    std::int32_t *dev = reinterpret_cast<std::int32_t *>(ctx.workspace(12 * pitch + 256));
+    ctx.check(ms_observation_count(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), (int)nMp, kfIds.data(), dev, dev + pitch, dev + 2 * pitch),
+              "ms_observation_count");
+    if (nMp) {
+        ctx.check(ms_dev_download(ctx.get(), out.count.data(), dev, 4 * nMp), "ms_dev_download");
+        ctx.check(ms_dev_download(ctx.get(), out.first.data(), dev + pitch, 4 * nMp), "ms_dev_download");
+        ctx.check(ms_dev_download(ctx.get(), out.last.data(), dev + 2 * pitch, 4 * nMp), "ms_dev_download");
+    }
+    return out;
+}
+
+// The three ParametersSlam fields the culling step reads.  Their types are not in the reference tree: ratioFloat32 says whether
+// keyframeCullMaxCriticalRatio is a float there (the product of :476 is then rounded to float32); see INTEGRATION.md.
+struct CullSettings {
+    double minMapPointCullingAge = 0.0;
+    int minObservationsForBA = 0;
+    double keyframeCullMaxCriticalRatio = 0.0;
+    bool cullPoints = true;             // false: cullKeyframes alone
+    bool ratioFloat32 = false;
+};
+
+// What the host side of the map still has to do after a cull: the removed rows (ascending) with the reason of each (1 no observation left,
+// 2 aged and not triangulated, 3 orphaned by a removed keyframe) -- trackIdToMapPoint.erase and the host copies of those points -- and the
+// removed keyframes as slots, in the order of removal (descending KfId) -- bowIndex->remove, the `uncertainty` accumulation onto the next
+// keyframe and re-pointing referenceKeyframe to the previous one (mapper_helpers.cpp:384, :408-426), with the links as they were before.
+struct CullResult {
+    std::vector<std::int32_t> removedRows;
+    std::vector<std::uint8_t> removedWhy;
+    std::vector<std::int32_t> removedKeyframes, removedPrevious, removedNext;
+};
+
+// cullMapPoints + cullKeyframes (mapper_helpers.cpp:1095-1096) in ONE device call on the tables in place.  `current` and adjacentKfIds /
+// loopClosureKeyframes are slots; a candidate without a previous keyframe (:453) or named by a loop-closure edge (:455-464) is kept.  The
+// previous / next links of `chain` are relinked as removeKeyframe does (:414-420) and a removed slot's id becomes -1.
+inline CullResult cullMap(Context &ctx, DeviceKeyframeMapPoints &table, DeviceMapPointFlags *flags, DeviceMapPointLive &live, KeyframeChain &chain, std::int32_t current,
+                          const std::vector<std::int32_t> &adjacentKfIds, const std::vector<std::int32_t> &loopClosureKeyframes, const CullSettings &settings) {
+    const std::size_t nKf = table.size(), nMp = table.mapPointCount();
+    if (chain.previous.size() != nKf || chain.next.size() != nKf || chain.id.size() != nKf || chain.t.size() != nKf)
+        throw std::invalid_argument("cullMap: one link pair, one KfId and one time per slot");
+    if (live.size() < nMp || (flags && flags->size() < nMp)) throw std::invalid_argument("cullMap: fewer live bytes or flags than map points");
+    if (settings.cullPoints && !flags) throw std::invalid_argument("cullMap: cullMapPoints reads the flags");
+    std::vector<std::uint8_t> keep(adjacentKfIds.size(), 0), removed(adjacentKfIds.size(), 0);
+    for (std::size_t i = 0; i < adjacentKfIds.size(); ++i) {
+        const std::int32_t k = adjacentKfIds[i];
+        if (k < 0 || (std::size_t)k >= nKf) throw std::invalid_argument("cullMap: adjacent keyframe outside the table");
+        keep[i] = chain.previous[k] < 0 || std::find(loopClosureKeyframes.begin(), loopClosureKeyframes.end(), k) != loopClosureKeyframes.end();
+    }
+    const ms_cull_settings s{current, settings.cullPoints ? 1 : 0, settings.minMapPointCullingAge, (std::int32_t)settings.minObservationsForBA,
+                             settings.keyframeCullMaxCriticalRatio, settings.ratioFloat32 ? 1 : 0};
+    const std::size_t pitch = (nMp + 63) / 64 * 64;
+    std::int32_t *rows = reinterpret_cast<std::int32_t *>(ctx.workspace(5 * pitch + 256));
+    std::uint8_t *why = reinterpret_cast<std::uint8_t *>(rows + pitch);
+    std::int32_t nRows = 0, nKfs = 0;
+    ctx.check(ms_map_cull(ctx.get(), table.mutableTable(), (int)nKf, (int)table.stride(), flags ? flags->mutableFlags() : nullptr, live.mutableLive(), (int)nMp, chain.id.data(),
+                          chain.t.data(), adjacentKfIds.data(), keep.data(), (int)adjacentKfIds.size(), &s, nullptr, rows, why, removed.data(), &nRows, &nKfs), "ms_map_cull");
+    CullResult out;
+    out.removedRows.resize((std::size_t)nRows); out.removedWhy.resize((std::size_t)nRows);
+    if (nRows) {
+        ctx.check(ms_dev_download(ctx.get(), out.removedRows.data(), rows, 4 * (std::size_t)nRows), "ms_dev_download");
+        ctx.check(ms_dev_download(ctx.get(), out.removedWhy.data(), why, (std::size_t)nRows), "ms_dev_download");
+    }
+    for (std::size_t i = 0; i < adjacentKfIds.size(); ++i) if (removed[i]) out.removedKeyframes.push_back(adjacentKfIds[i]);
+    std::sort(out.removedKeyframes.begin(), out.removedKeyframes.end(), [&](std::int32_t a, std::int32_t b) { return chain.id[a] > chain.id[b]; });
+    for (std::int32_t k : out.removedKeyframes) {            // :414-420, in the order of removal
+        const std::int32_t prev = chain.previous[k], next = chain.next[k];
+        out.removedPrevious.push_back(prev); out.removedNext.push_back(next);
+        if (next != -1) chain.previous[next] = prev;
+        if (prev != -1) chain.next[prev] = next;
+        chain.previous[k] = chain.next[k] = -1;
+        chain.id[k] = -1;
     }
     return out;
 }

@@ -1121,6 +1121,12 @@ class UnionProblemC(C.Structure):
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("exclude_slot", C.c_int32), ("require", C.c_uint8)]
 
 
+class CullSettingsC(C.Structure):
+    """ms_cull_settings (ms_map_cull)."""
+    _fields_ = [("current_slot", C.c_int32), ("cull_points", C.c_int32), ("min_age", C.c_double), ("min_obs_for_ba", C.c_int32),
+                ("max_critical_ratio", C.c_double), ("ratio_float32", C.c_int32)]
+
+
 def _download_i32(buf, shape):
     return buf.download(np.int32, shape) if shape[0] * shape[1] else np.zeros(shape, np.int32)
 
@@ -1217,6 +1223,68 @@ class KeyframeTable:
                 if b is not None:
                     b.free()
         return ([rows[u, :n_rows[u]].copy() for u in range(n_u)], [owner[u, :n_rows[u]].copy() for u in range(n_u)] if want_owner else None, n_rows)
+
+    def observation_count(self, kf_id, n_mp, want_n_obs=True, want_first=True, want_last=True):
+        """mp.observations.size(), getFirstObservation and getLastObservation of every row (ms_observation_count).  kf_id [n_kf] int32: the
+        slots' KfIds, -1 for an empty slot.  Returns (n_obs, first_slot, last_slot), int32 [n_mp] each, None for an output not asked for."""
+        kf_id, n_mp = _i32(kf_id), int(n_mp)
+        if len(kf_id) != self.n_kf:
+            raise ValueError("kf_id describes %d slots, the table has %d" % (len(kf_id), self.n_kf))
+        bufs = [self.ctx.alloc(4 * max(n_mp, 1)) if w else None for w in (want_n_obs, want_first, want_last)]
+        try:
+            self.ctx.check(lib().ms_observation_count(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, n_mp, _vp(kf_id), _vp(bufs[0]), _vp(bufs[1]), _vp(bufs[2])),
+                           "ms_observation_count")
+            out = tuple(None if b is None else (b.download(np.int32, (n_mp,)) if n_mp else np.zeros(0, np.int32)) for b in bufs)
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+        return out
+
+    def cull_device(self, flags, live, n_mp, kf_id, kf_t, cand, cand_keep, settings, d_n_obs, d_rows, d_why):
+        """ms_map_cull with the tables and outputs left on the device: flags (DevBuf or None), live, d_rows (DevBufs), d_n_obs / d_why (DevBufs
+        or None).  settings: a dict of the fields of CullSettingsC.  Returns (cand_removed [n_cand] uint8, n_removed_rows, n_removed_kf)."""
+        kf_id, cand = _i32(kf_id), _i32(cand)
+        kf_t = np.ascontiguousarray(kf_t, np.float64).reshape(-1)
+        if len(kf_id) != self.n_kf or len(kf_t) != self.n_kf:
+            raise ValueError("kf_id / kf_t describe %d / %d slots, the table has %d" % (len(kf_id), len(kf_t), self.n_kf))
+        keep = None if cand_keep is None else np.ascontiguousarray(cand_keep, np.uint8).reshape(-1)
+        if keep is not None and len(keep) != len(cand):
+            raise ValueError("cand_keep has %d entries for %d candidates" % (len(keep), len(cand)))
+        S = CullSettingsC(int(settings["current_slot"]), int(settings["cull_points"]), float(settings["min_age"]), int(settings["min_obs_for_ba"]),
+                          float(settings["max_critical_ratio"]), int(settings["ratio_float32"]))
+        removed = np.zeros(max(len(cand), 1), np.uint8)
+        n_rows, n_kfs = C.c_int32(0), C.c_int32(0)
+        self.ctx.check(lib().ms_map_cull(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(flags), _vp(live), int(n_mp), _vp(kf_id), _vp(kf_t), _vp(cand),
+                                         _vp(keep), len(cand), C.byref(S), _vp(d_n_obs), _vp(d_rows), _vp(d_why), _vp(removed), C.byref(n_rows), C.byref(n_kfs)),
+                       "ms_map_cull")
+        return removed[:len(cand)], n_rows.value, n_kfs.value
+
+    def cull(self, mp_flags, mp_live, n_mp, kf_id, kf_t, cand, cand_keep, settings, want_n_obs=True, want_why=True):
+        """cullMapPoints, then cullKeyframes (mapper_helpers.cpp:349-373, :433-482) on this table in place (ms_map_cull).  mp_flags / mp_live:
+        DevBufs, updated in place, or arrays, uploaded for the call and returned as they are afterwards (mp_flags may be None when
+        settings['cull_points'] == 0).  Returns a dict: removed_rows (ascending), removed_why (1 no observation, 2 aged, 3 orphaned; None when
+        not asked for), cand_removed, n_removed_kf, n_obs (after both passes, or None), mp_flags / mp_live (arrays, when arrays were given)."""
+        n_mp = int(n_mp)
+        flags, own_f = self._flags(mp_flags, n_mp)
+        live, own_l = self._flags(mp_live, n_mp)
+        d_n = self.ctx.alloc(4 * max(n_mp, 1)) if want_n_obs else None
+        d_rows = self.ctx.alloc(4 * max(n_mp, 1))
+        d_why = self.ctx.alloc(max(n_mp, 1)) if want_why else None
+        try:
+            removed, n_rows, n_kfs = self.cull_device(flags, live, n_mp, kf_id, kf_t, cand, cand_keep, settings, d_n, d_rows, d_why)
+            some = lambda b, dtype, n: b.download(dtype, (n,)) if n else np.zeros(0, dtype)
+            out = dict(removed_rows=some(d_rows, np.int32, n_rows), removed_why=some(d_why, np.uint8, n_rows) if want_why else None, cand_removed=removed,
+                       n_removed_kf=n_kfs, n_obs=some(d_n, np.int32, n_mp) if want_n_obs else None)
+            if own_f is not None:
+                out["mp_flags"] = some(own_f, np.uint8, n_mp)
+            if own_l is not None:
+                out["mp_live"] = some(own_l, np.uint8, n_mp)
+        finally:
+            for b in (d_n, d_rows, d_why, own_f, own_l):
+                if b is not None:
+                    b.free()
+        return out
 
 
 class ProjectionKeyframe:
