@@ -768,6 +768,116 @@ int ms_triangulate_check(const double *mp_pos, int n_mp, const double *kf_pose, 
                          const float *obs_x, const float *obs_y, const int32_t *obs_octave, const ms_tri_settings *settings, int mode,
                          char *why, size_t why_bytes);
 
+/* ---- observation lists on the device -------------------------------------------------------------------------------------
+ * ms_observation_lists: the transpose of kf_mp for chosen rows -- MapPoint::observations (`std::map<KfId, KpId>`) of each, as CSR lists in
+ * DEVICE memory, with the observing keypoints' table entries gathered next to them, in the form ms_map_refresh and ms_triangulate take
+ * their host lists.  kf_mp, n_mp, kf_id and mp_flags are those of 9.6 / 9.8.  New:
+ *   kp_x, kp_y, kp_depth (DEVICE float [n_kf * stride]), kp_octave (DEVICE int32 [n_kf * stride])   the keypoint table, parallel to kf_mp;
+ *                                     each may be NULL when the outputs that read it are NULL
+ *   kf_desc_base (HOST int32 [n_kf])  the index of keypoint 0 of the slot in desc_pool, -1 for a keyframe without descriptors
+ *                                     (map_point.cpp:80); may be NULL when obs_desc is
+ * The selection: MS_OBS_FROM_ROWS takes rows_in (DEVICE [n_in]; e.g. the output of ms_map_point_union, or removed_rows) in the given order,
+ * skips entries outside [0, n_mp) and keeps a row at its first occurrence; MS_OBS_FROM_SLOT takes the valid entries of `slot` in ascending
+ * keypoint order, each row at its first occurrence (the loops of mapper_helpers.cpp:1062 / :1085).  The filter drops selected rows:
+ * MS_OBS_REFRESH keeps (mp_flags[r] & 2) != 0 (:1066), MS_OBS_RETRIANGULATE keeps (mp_flags[r] & 1) == 0 || n_obs[r] >= 2 (:1088).
+ * drop_empty != 0 leaves out rows without observations (ms_map_refresh rejects an empty list).
+ * Outputs (DEVICE, the caller's: rows, first_octave, was_triangulated, n_obs_row hold cap_rows, obs_start cap_rows + 1, the obs_* arrays
+ * cap_obs; all but rows and obs_start may be NULL):
+ *   rows [n_rows], obs_start [n_rows + 1], n_obs_row [n_rows]   the kept rows, the start and the length of each list
+ *   obs_kf, obs_kp [n_obs]            the observing slot and the keypoint index j in it
+ *   obs_x, obs_y, obs_octave, obs_depth [n_obs]   kp_*[slot * stride + j]
+ *   obs_desc [n_obs]                  kf_desc_base[slot] + j, or -1 when the base is negative
+ *   first_octave [n_rows]             the octave of the row's first observation, 0 for an empty list
+ *   was_triangulated [n_rows]         (mp_flags[row] & 2) != 0 at the time of the call (:607); needs mp_flags
+ * Observations come from the slots with kf_id >= 0 only, in ascending kf_id; entries of one slot that name the same row are all kept, in
+ * ascending j (the multiplicity convention of ms_observation_count).  n_rows / n_obs (HOST) receive the counts.
+ * Ten launches whatever the sizes; synchronous: one upload (the slot order by kf_id, kf_desc_base), one download (the two counts and the
+ * violation counter); the lists never cross the bus.  Integer atomics only; entries wait behind an atomic cursor and every row's segment is
+ * then put in (kf_id position, j) order -- inside a wave up to 64 observations, by a workgroup through LDS up to 1024, from global memory
+ * beyond (correct up to n_kf * stride, quadratic in the length) -- so the same input gives the same bits on every call and at any capacity.
+ * MS_ERR_INVALID, with nothing written and before any device call: slot outside [0, n_kf) or with kf_id < 0, a non-negative kf_id listed
+ * twice, a flag filter (or was_triangulated) without mp_flags, stride < 1, a negative size, a missing array, a bad source or filter.
+ * MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_in: 1 << 24), and when n_rows > cap_rows or n_obs > cap_obs: nothing is written past
+ * either capacity (the arrays' contents are unspecified then) and the needed counts are returned, so the caller can regrow and call again.
+ * MS_ERR_INVALID after the device pass when n_levels > 0 and a gathered octave lies outside [0, n_levels): the lists are complete, the
+ * offending octaves are stored clamped into the range.  n_levels = 0 gathers octaves as they are.
+ * n_in = 0, n_mp = 0 and a slot without valid entries are fine and return zero counts and obs_start = {0} (for n_in = 0 and n_mp = 0 without a kernel launch).
+ * ms_observation_lists_check is the validation alone (no context, no device; `why` receives the message). */
+#define MS_OBS_FROM_ROWS      0
+#define MS_OBS_FROM_SLOT      1
+#define MS_OBS_ALL            0
+#define MS_OBS_REFRESH        1
+#define MS_OBS_RETRIANGULATE  2
+typedef struct {
+    int32_t source;                /* MS_OBS_FROM_ROWS | MS_OBS_FROM_SLOT */
+    int32_t filter;                /* MS_OBS_ALL | MS_OBS_REFRESH | MS_OBS_RETRIANGULATE */
+    int32_t drop_empty;
+    int32_t slot;                  /* MS_OBS_FROM_SLOT */
+    const int32_t *rows_in;        /* MS_OBS_FROM_ROWS: DEVICE [n_in] */
+    int32_t n_in;
+} ms_obs_select;
+typedef struct {
+    int32_t *rows, *obs_start, *n_obs_row, *first_octave;
+    uint8_t *was_triangulated;
+    int32_t *obs_kf, *obs_kp, *obs_octave, *obs_desc;
+    float *obs_x, *obs_y, *obs_depth;
+} ms_obs_lists;
+int ms_observation_lists(ms_ctx *ctx,
+    /* DEVICE */
+    const int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    /* HOST */
+    const int32_t *kf_id,
+    /* DEVICE; see above for which may be NULL */
+    const uint8_t *mp_flags, const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth,
+    /* HOST */
+    const int32_t *kf_desc_base, const ms_obs_select *select, int n_levels,
+    /* HOST struct of DEVICE pointers, and their capacities */
+    const ms_obs_lists *lists, int cap_rows, int cap_obs,
+    /* HOST */
+    int32_t *n_rows, int32_t *n_obs);
+int ms_observation_lists_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *kf_id, const uint8_t *mp_flags,
+                               const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth,
+                               const int32_t *kf_desc_base, const ms_obs_select *select, int n_levels, const ms_obs_lists *lists,
+                               int cap_rows, int cap_obs, const int32_t *n_rows, const int32_t *n_obs, char *why, size_t why_bytes);
+
+/* ms_triangulate_lists / ms_map_refresh_lists: ms_triangulate (9.7) and ms_map_refresh (9.5) with the observation lists read from DEVICE
+ * memory where ms_observation_lists left them: the same kernels, the same arithmetic and the same bits as the host-list entry points given
+ * the same lists, and no list upload -- only the per-slot (kf_cam, kf_focal) and per-level (level_sigma_sq, scale_factors) HOST arrays are.
+ * n_rows / n_obs are the counts ms_observation_lists returned.  ms_triangulate_lists reads rows, was_triangulated, obs_start, obs_kf, obs_x,
+ * obs_y, obs_octave and obs_depth (NULL: no depth anywhere); ms_map_refresh_lists reads rows, obs_start, obs_kf, first_octave and obs_desc
+ * (NULL, or desc_pool NULL: the descriptors are left alone).
+ * Validation covers the HOST arguments only (sizes, settings, mode, pointers; MS_ERR_CAPACITY beyond MS_TRI_MAX_ROWS / MS_TRI_MAX_OBS).  The
+ * lists are valid by construction when they come from ms_observation_lists -- built with drop_empty != 0 and the same n_levels for
+ * ms_map_refresh_lists, with n_pool covering kf_desc_base[slot] + stride; the cameras of the observing slots must be those
+ * ms_triangulate_check accepts.  Lists from anywhere else are the caller's responsibility: nothing on the device checks them again.
+ * ms_map_refresh_lists builds the rows' descriptor lists (the observations with obs_desc != -1) on the device: a count per row, a scan that
+ * also gives the total and the longest list (downloaded: the medoid kernel's LDS is sized by it), a pack; `medoid` (HOST [n_rows], may be
+ * NULL) keeps its meaning, the position in the row's list or -1 / -2, and is mapped from the position among the descriptors by a kernel.
+ * promote_min_obs > 0 adds the status promotion of mapper_helpers.cpp:1072-1076 to the end of the geometry kernel:
+ * mp_flags[row] = list length >= promote_min_obs ? 3 (TRIANGULATED) : 2 (UNSURE); with 0 mp_flags is not touched and may be NULL. */
+int ms_triangulate_lists(ms_ctx *ctx,
+    /* DEVICE, as ms_triangulate */
+    double *mp_pos, uint8_t *mp_flags, int n_mp, const double *kf_pose, int n_kf,
+    /* HOST, per keyframe slot */
+    const ms_pinhole *kf_cam, const int32_t *kf_focal,
+    /* HOST struct of DEVICE pointers */
+    const ms_obs_lists *lists, int n_rows, int n_obs,
+    const ms_tri_settings *settings, int mode,
+    /* HOST [n_rows], each may be NULL */
+    uint8_t *status, uint8_t *reason, int32_t *n_pass);
+int ms_map_refresh_lists(ms_ctx *ctx,
+    /* DEVICE, as ms_map_refresh */
+    const double *mp_pos, float *mp_norm, float *mp_min_dist, float *mp_max_dist, uint32_t *mp_desc, int n_mp,
+    const double *kf_pose, int n_kf, const uint32_t *desc_pool, int n_pool,
+    /* HOST struct of DEVICE pointers */
+    const ms_obs_lists *lists, int n_rows, int n_obs,
+    /* HOST */
+    const float *scale_factors, int n_levels, int promote_min_obs,
+    /* DEVICE [n_mp], written for promote_min_obs > 0 */
+    uint8_t *mp_flags,
+    /* HOST [n_rows] or NULL */
+    int32_t *medoid);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

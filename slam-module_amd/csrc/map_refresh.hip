@@ -3,6 +3,11 @@
 //                    as mapper_helpers.cpp:1062-1077 runs them for the map points of a new keyframe
 //   ms_loop_correct  the pose correction and map-point transfer of LoopCloser::correctLoop (loop_closer.cpp:398-503)
 //
+// ms_map_refresh takes the observation lists as host arrays and uploads them; ms_map_refresh_lists reads the device lists of
+// ms_observation_lists where they lie, builds the descriptor lists with k_refresh_dcount / k_refresh_dscan / k_refresh_dpack,
+// maps the medoid to its list position with k_refresh_medoid_pos and, for promote_min_obs > 0, sets the status flags at the end of
+// k_refresh_geom.  Both run the one launch sequence of refresh_run.
+//
 // Refresh, five launches whatever the number of rows (two without a descriptor pool):
 //   k_refresh_centres  one lane per keyframe slot: the camera centre -R^T t
 //   k_refresh_geom     a team of 8 lanes per row: the lanes compute eight observations' unit vectors at a time, then every lane of the team
@@ -47,7 +52,8 @@ struct RefreshArgs {
     float *mp_norm, *mp_min, *mp_max;
     const int32_t *rows, *obs_start, *obs_kf, *octave;
     const float *sf;
-    int32_t n_rows, n_levels;
+    uint8_t *mp_flags;                       // written for promote_min_obs > 0 only
+    int32_t n_rows, n_levels, promote_min_obs;
 };
 
 __device__ __forceinline__ double sq_norm3(double x, double y, double z) {       // Eigen's unrolled redux of three elements: x^2 + (y^2 + z^2)
@@ -88,6 +94,7 @@ __global__ __launch_bounds__(kBlock) void k_refresh_geom(const RefreshArgs A) {
     const float sfo = A.sf[A.octave[r]];
     A.mp_max[row] = __fmul_rn(dist, sfo);                                        // :170
     A.mp_min[row] = __fdiv_rn(__fmul_rn(dist, sfo), A.sf[A.n_levels - 1]);       // :171
+    if (A.promote_min_obs > 0) A.mp_flags[row] = n >= A.promote_min_obs ? 3 : 2;   // mapper_helpers.cpp:1072-1076: TRIANGULATED, else UNSURE
 }
 
 // packed[e] = pool[src[e]] (two 16-byte halves per descriptor, one lane each); ident[e] = e, the index list k_descriptor_medoid walks
@@ -106,6 +113,73 @@ __global__ __launch_bounds__(kBlock) void k_refresh_winner(const uint4 *__restri
     const int b = best[r];
     if (b < 0) return;                                       // -1: no descriptors (:86), -2: list beyond MS_MEDOID_MAX_OBS -- the row keeps its descriptor
     mp_desc[2 * (size_t)rows[r] + h] = packed[2 * ((size_t)start[r] + (size_t)b) + h];
+}
+
+// The descriptor lists of the device form (ms_map_refresh_lists), what ms_map_refresh packs on the host: a row's `descriptors` vector of
+// map_point.cpp:76-84 is its observations with obs_desc != -1.  Count per row, scan, pack; the scan also leaves the total and the longest list.
+constexpr int kScan = 1024;
+
+__global__ __launch_bounds__(kBlock) void k_refresh_dcount(const int32_t *__restrict__ obs_start, const int32_t *__restrict__ obs_desc, int n_rows, int32_t *__restrict__ dstart) {
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n_rows) return;
+    int have = 0;
+    for (int o = obs_start[r]; o < obs_start[r + 1]; ++o) have += obs_desc[o] != -1;
+    dstart[r] = have;
+}
+
+// dstart[0 .. n_rows]: counts -> exclusive offsets, in place (one workgroup, kScan rows per trip); info = total, longest list
+__global__ __launch_bounds__(kScan) void k_refresh_dscan(int32_t *__restrict__ dstart, int n_rows, int32_t *__restrict__ info) {
+    __shared__ int32_t s_sum[kScan / 64], s_max[kScan / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0, longest = 0;
+    for (int r0 = 0; r0 < n_rows; r0 += kScan) {
+        const int r = r0 + (int)threadIdx.x;
+        const int c = r < n_rows ? dstart[r] : 0;
+        int inc = c, mx = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(inc, d);
+            if (lane >= d) inc += t;
+            mx = max(mx, __shfl_xor(mx, d));
+        }
+        if (lane == 63) { s_sum[wave] = inc; s_max[wave] = mx; }
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kScan / 64; ++w) {
+            const int x = s_sum[w];
+            if (w < wave) before += x;
+            total += x;
+            longest = max(longest, s_max[w]);
+        }
+        if (r < n_rows) dstart[r] = carry + before + inc - c;
+        carry += total;
+        __syncthreads();                                     // s_sum / s_max are written again in the next trip
+    }
+    if (threadIdx.x == 0) { dstart[n_rows] = carry; info[0] = carry; info[1] = longest; }
+}
+
+__global__ __launch_bounds__(kBlock) void k_refresh_dpack(const int32_t *__restrict__ obs_start, const int32_t *__restrict__ obs_desc, int n_rows,
+                                                          const int32_t *__restrict__ dstart, int32_t *__restrict__ dsrc) {
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n_rows) return;
+    int at = dstart[r];
+    for (int o = obs_start[r]; o < obs_start[r + 1]; ++o) {
+        const int32_t d = obs_desc[o];
+        if (d != -1) dsrc[at++] = d;                         // below dstart[r + 1]: the count k_refresh_dcount took from the same list
+    }
+}
+
+// medoid[r]: the position among the row's descriptors -> the position in the row's observation list; -1 / -2 stay
+__global__ __launch_bounds__(kBlock) void k_refresh_medoid_pos(const int32_t *__restrict__ obs_start, const int32_t *__restrict__ obs_desc, int n_rows,
+                                                               int32_t *__restrict__ best_pos, const int32_t *__restrict__ best) {
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n_rows) return;
+    int m = best[r];
+    if (m >= 0)
+        for (int o = obs_start[r], k = 0; o < obs_start[r + 1]; ++o)
+            if (obs_desc[o] != -1 && k++ == m) { m = o - obs_start[r]; break; }
+    best_pos[r] = m;
 }
 
 // ------------------------------------------------------------------------------------------------ loop correction
@@ -278,6 +352,126 @@ extern "C" int ms_map_refresh_check(const double *mp_pos, const float *mp_norm, 
     return MS_OK;
 }
 
+namespace {
+
+// The lists of one call: HOST arrays that are uploaded (ms_map_refresh), or DEVICE arrays the kernels read where they lie (ms_map_refresh_lists).
+struct RefreshLists {
+    const int32_t *rows, *obs_start, *obs_kf, *obs_desc, *first_octave;
+    bool on_device;
+};
+
+// the one launch sequence of both entry points; everything is validated by the caller
+int refresh_run(ms_ctx *c, const double *mp_pos, float *mp_norm, float *mp_min_dist, float *mp_max_dist, uint32_t *mp_desc, const double *kf_pose, int n_kf,
+                const uint32_t *desc_pool, const RefreshLists &L, int n_rows, int n_obs, const float *scale_factors, int n_levels, int promote_min_obs, uint8_t *mp_flags,
+                int32_t *medoid) {
+    int rc;
+    const bool with_desc = desc_pool != nullptr && L.obs_desc != nullptr, on_dev = L.on_device;
+    int n_dobs = 0, longest = 0;
+    for (int r = 0; !on_dev && with_desc && r < n_rows; ++r) {
+        int have = 0;
+        for (int o = L.obs_start[r]; o < L.obs_start[r + 1]; ++o) have += L.obs_desc[o] != -1;
+        n_dobs += have;
+        longest = std::max(longest, have);
+    }
+    MsRange range("mapRefresh");
+    // upload block: rows | octaves | obs_start | obs_kf | scale factors | packed descriptor lists: start, pool index; then (host only) medoids
+    // (device lists: only the scale factors are uploaded; the descriptor lists are built on the device, for n_obs descriptors at most)
+    const size_t nr = (size_t)n_rows, nd = on_dev ? (with_desc ? (size_t)n_obs : 0) : (size_t)n_dobs, ur = on_dev ? 0 : nr;
+    MsLayout up;
+    const auto l_rows = up.array<int32_t>(ur), l_oct = up.array<int32_t>(ur), l_start = up.array<int32_t>(on_dev ? 0 : nr + 1), l_kf = up.array<int32_t>(on_dev ? 0 : (size_t)n_obs);
+    const auto l_sf = up.array<float>((size_t)n_levels);
+    const auto l_dstart = up.array<int32_t>(on_dev ? 0 : nr + 1), l_dsrc = up.array<int32_t>(on_dev ? 0 : nd);
+    MsLayout host = up, dev = up;
+    const auto l_down = host.array<int32_t>(std::max(nr, (size_t)2));
+    // device-only block: camera centres | packed descriptors | identity list | medoids (the descriptors and the list with one entry of slack);
+    // for device lists also: descriptor starts | pool indices | total and longest | medoid positions
+    const auto l_centre = dev.array<double>(3 * (size_t)n_kf);
+    const auto l_packed = dev.array<uint4>(2 * nd + 2);
+    const auto l_ident = dev.array<int32_t>(nd + 1), l_best = dev.array<int32_t>(nr);
+    const auto l_ddstart = dev.array<int32_t>(on_dev ? nr + 1 : 0), l_ddsrc = dev.array<int32_t>(on_dev ? nd : 0);
+    const auto l_info = dev.array<int32_t>(on_dev ? 2 : 0), l_pos = dev.array<int32_t>(on_dev ? nr : 0);
+    MS_HIP(c, hipSetDevice(c->device));
+    MsWorkspace &W = c->ws[MS_WS_MAP_REFRESH];
+    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
+    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
+    void *hs = W.host, *ds = W.dev;
+    l_sf.fill(hs, scale_factors);
+    const int32_t *d_rows = L.rows, *d_start = L.obs_start, *d_kf = L.obs_kf, *d_oct = L.first_octave, *d_dstart = l_ddstart.at(ds), *d_dsrc = l_ddsrc.at(ds);
+    if (!on_dev) {
+        l_rows.fill(hs, L.rows);
+        l_oct.fill(hs, L.first_octave);
+        l_start.fill(hs, L.obs_start);
+        l_kf.fill(hs, L.obs_kf);
+        int32_t *dstart = l_dstart.at(hs), *dsrc = l_dsrc.at(hs);
+        dstart[0] = 0;
+        for (int r = 0, at = 0; r < n_rows; ++r) {           // the `descriptors` vector of :76-84: observations of keyframes that have descriptors
+            if (with_desc)
+                for (int o = L.obs_start[r]; o < L.obs_start[r + 1]; ++o)
+                    if (L.obs_desc[o] != -1) dsrc[at++] = L.obs_desc[o];
+            dstart[r + 1] = at;
+        }
+        d_rows = l_rows.at(ds); d_start = l_start.at(ds); d_kf = l_kf.at(ds); d_oct = l_oct.at(ds); d_dstart = l_dstart.at(ds); d_dsrc = l_dsrc.at(ds);
+    }
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
+    double *centre = l_centre.at(ds);
+    hipLaunchKernelGGL(k_refresh_centres, dim3(ms_div_up(std::max(n_kf, 1), kBlock)), dim3(kBlock), 0, c->stream, kf_pose, n_kf, centre);
+    MS_KERNEL_CHECK(c, "k_refresh_centres");
+    RefreshArgs A;
+    A.mp_pos = mp_pos; A.centre = centre; A.mp_norm = mp_norm; A.mp_min = mp_min_dist; A.mp_max = mp_max_dist;
+    A.rows = d_rows; A.obs_start = d_start; A.obs_kf = d_kf; A.octave = d_oct;
+    A.sf = l_sf.at(ds);
+    A.mp_flags = mp_flags;
+    A.n_rows = n_rows; A.n_levels = n_levels; A.promote_min_obs = promote_min_obs;
+    hipLaunchKernelGGL(k_refresh_geom, dim3((unsigned)((nr * kTeam + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
+    MS_KERNEL_CHECK(c, "k_refresh_geom");
+    if (with_desc) {
+        const dim3 by_row((unsigned)ms_div_up(n_rows, kBlock));
+        if (on_dev) {                                        // the descriptor lists, their total and the longest one
+            int32_t *dstart = l_ddstart.at(ds);
+            hipLaunchKernelGGL(k_refresh_dcount, by_row, dim3(kBlock), 0, c->stream, d_start, L.obs_desc, n_rows, dstart);
+            MS_KERNEL_CHECK(c, "k_refresh_dcount");
+            hipLaunchKernelGGL(k_refresh_dscan, dim3(1), dim3(kScan), 0, c->stream, dstart, n_rows, l_info.at(ds));
+            MS_KERNEL_CHECK(c, "k_refresh_dscan");
+            hipLaunchKernelGGL(k_refresh_dpack, by_row, dim3(kBlock), 0, c->stream, d_start, L.obs_desc, n_rows, dstart, l_ddsrc.at(ds));
+            MS_KERNEL_CHECK(c, "k_refresh_dpack");
+            MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_info.at(ds), l_info.bytes(), hipMemcpyDeviceToHost, c->stream));
+            MS_HIP(c, hipStreamSynchronize(c->stream));      // the medoid kernel's LDS is sized by the longest list
+            n_dobs = l_down.at(hs)[0]; longest = l_down.at(hs)[1];
+        }
+        uint4 *packed = l_packed.at(ds);
+        hipLaunchKernelGGL(k_refresh_gather, dim3(ms_div_up(std::max(2 * n_dobs, 1), kBlock)), dim3(kBlock), 0, c->stream,
+                           reinterpret_cast<const uint4 *>(desc_pool), d_dsrc, n_dobs, packed, l_ident.at(ds));
+        MS_KERNEL_CHECK(c, "k_refresh_gather");
+        if ((rc = ms_descriptor_medoid(c, reinterpret_cast<const uint32_t *>(packed), d_dstart, l_ident.at(ds), n_rows, std::min(longest, MS_MEDOID_MAX_OBS),
+                                       l_best.at(ds), nullptr)))
+            return rc;
+        hipLaunchKernelGGL(k_refresh_winner, dim3(ms_div_up(2 * n_rows, kBlock)), dim3(kBlock), 0, c->stream, packed, d_dstart, l_best.at(ds), d_rows, n_rows,
+                           reinterpret_cast<uint4 *>(mp_desc));
+        MS_KERNEL_CHECK(c, "k_refresh_winner");
+        if (medoid && on_dev) {
+            hipLaunchKernelGGL(k_refresh_medoid_pos, by_row, dim3(kBlock), 0, c->stream, d_start, L.obs_desc, n_rows, l_pos.at(ds), l_best.at(ds));
+            MS_KERNEL_CHECK(c, "k_refresh_medoid_pos");
+            MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_pos.at(ds), l_pos.bytes(), hipMemcpyDeviceToHost, c->stream));
+        } else if (medoid) {
+            MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_best.at(ds), l_best.bytes(), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    MS_HIP(c, hipStreamSynchronize(c->stream));
+    if (medoid) {
+        const int32_t *best = l_down.at(hs);
+        for (int r = 0; r < n_rows; ++r) {
+            int m = with_desc ? best[r] : -1;
+            if (m >= 0 && !on_dev)                           // position among the descriptors -> position in the row's observation list
+                for (int o = L.obs_start[r], k = 0; o < L.obs_start[r + 1]; ++o)
+                    if (L.obs_desc[o] != -1 && k++ == m) { m = o - L.obs_start[r]; break; }
+            medoid[r] = m;
+        }
+    }
+    return MS_OK;
+}
+
+}  // namespace
+
 extern "C" int ms_map_refresh(ms_ctx *c, const double *mp_pos, float *mp_norm, float *mp_min_dist, float *mp_max_dist, uint32_t *mp_desc, int n_mp,
                               const double *kf_pose, int n_kf, const uint32_t *desc_pool, int n_pool, const int32_t *rows, int n_rows,
                               const int32_t *obs_start, const int32_t *obs_kf, const int32_t *obs_desc, const int32_t *first_octave,
@@ -288,82 +482,34 @@ extern "C" int ms_map_refresh(ms_ctx *c, const double *mp_pos, float *mp_norm, f
                                    first_octave, scale_factors, n_levels, c->err, sizeof(c->err))))
         return rc;
     if (n_rows == 0) return MS_OK;
-    const bool with_desc = desc_pool != nullptr && obs_desc != nullptr;
-    const int n_obs = obs_start[n_rows];
-    int n_dobs = 0, longest = 0;
-    for (int r = 0; with_desc && r < n_rows; ++r) {
-        int have = 0;
-        for (int o = obs_start[r]; o < obs_start[r + 1]; ++o) have += obs_desc[o] != -1;
-        n_dobs += have;
-        longest = std::max(longest, have);
-    }
-    MsRange range("mapRefresh");
-    // upload block: rows | octaves | obs_start | obs_kf | scale factors | packed descriptor lists: start, pool index; then (host only) medoids
-    const size_t nr = (size_t)n_rows, nd = (size_t)n_dobs;
-    MsLayout up;
-    const auto l_rows = up.array<int32_t>(nr), l_oct = up.array<int32_t>(nr), l_start = up.array<int32_t>(nr + 1), l_kf = up.array<int32_t>((size_t)n_obs);
-    const auto l_sf = up.array<float>((size_t)n_levels);
-    const auto l_dstart = up.array<int32_t>(nr + 1), l_dsrc = up.array<int32_t>(nd);
-    MsLayout host = up, dev = up;
-    const auto l_down = host.array<int32_t>(nr);
-    // device-only block: camera centres | packed descriptors | identity list | medoids (the descriptors and the list with one entry of slack)
-    const auto l_centre = dev.array<double>(3 * (size_t)n_kf);
-    const auto l_packed = dev.array<uint4>(2 * nd + 2);
-    const auto l_ident = dev.array<int32_t>(nd + 1), l_best = dev.array<int32_t>(nr);
-    MS_HIP(c, hipSetDevice(c->device));
-    MsWorkspace &W = c->ws[MS_WS_MAP_REFRESH];
-    if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
-    if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
-    void *hs = W.host, *ds = W.dev;
-    l_rows.fill(hs, rows);
-    l_oct.fill(hs, first_octave);
-    l_start.fill(hs, obs_start);
-    l_kf.fill(hs, obs_kf);
-    l_sf.fill(hs, scale_factors);
-    int32_t *dstart = l_dstart.at(hs), *dsrc = l_dsrc.at(hs);
-    dstart[0] = 0;
-    for (int r = 0, at = 0; r < n_rows; ++r) {               // the `descriptors` vector of :76-84: observations of keyframes that have descriptors
-        if (with_desc)
-            for (int o = obs_start[r]; o < obs_start[r + 1]; ++o)
-                if (obs_desc[o] != -1) dsrc[at++] = obs_desc[o];
-        dstart[r + 1] = at;
-    }
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
-    double *centre = l_centre.at(ds);
-    hipLaunchKernelGGL(k_refresh_centres, dim3(ms_div_up(std::max(n_kf, 1), kBlock)), dim3(kBlock), 0, c->stream, kf_pose, n_kf, centre);
-    MS_KERNEL_CHECK(c, "k_refresh_centres");
-    RefreshArgs A;
-    A.mp_pos = mp_pos; A.centre = centre; A.mp_norm = mp_norm; A.mp_min = mp_min_dist; A.mp_max = mp_max_dist;
-    A.rows = l_rows.at(ds); A.obs_start = l_start.at(ds); A.obs_kf = l_kf.at(ds); A.octave = l_oct.at(ds);
-    A.sf = l_sf.at(ds);
-    A.n_rows = n_rows; A.n_levels = n_levels;
-    hipLaunchKernelGGL(k_refresh_geom, dim3((unsigned)((nr * kTeam + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
-    MS_KERNEL_CHECK(c, "k_refresh_geom");
-    if (with_desc) {
-        uint4 *packed = l_packed.at(ds);
-        hipLaunchKernelGGL(k_refresh_gather, dim3(ms_div_up(std::max(2 * n_dobs, 1), kBlock)), dim3(kBlock), 0, c->stream,
-                           reinterpret_cast<const uint4 *>(desc_pool), l_dsrc.at(ds), n_dobs, packed, l_ident.at(ds));
-        MS_KERNEL_CHECK(c, "k_refresh_gather");
-        if ((rc = ms_descriptor_medoid(c, reinterpret_cast<const uint32_t *>(packed), l_dstart.at(ds), l_ident.at(ds), n_rows, std::min(longest, MS_MEDOID_MAX_OBS),
-                                       l_best.at(ds), nullptr)))
-            return rc;
-        hipLaunchKernelGGL(k_refresh_winner, dim3(ms_div_up(2 * n_rows, kBlock)), dim3(kBlock), 0, c->stream, packed, l_dstart.at(ds), l_best.at(ds), l_rows.at(ds), n_rows,
-                           reinterpret_cast<uint4 *>(mp_desc));
-        MS_KERNEL_CHECK(c, "k_refresh_winner");
-        if (medoid) MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_best.at(ds), l_best.bytes(), hipMemcpyDeviceToHost, c->stream));
-    }
-    MS_HIP(c, hipStreamSynchronize(c->stream));
-    if (medoid) {
-        const int32_t *best = l_down.at(hs);
-        for (int r = 0; r < n_rows; ++r) {
-            int m = with_desc ? best[r] : -1;
-            if (m >= 0)                                      // position among the descriptors -> position in the row's observation list
-                for (int o = obs_start[r], k = 0; o < obs_start[r + 1]; ++o)
-                    if (obs_desc[o] != -1 && k++ == m) { m = o - obs_start[r]; break; }
-            medoid[r] = m;
-        }
-    }
-    return MS_OK;
+    const RefreshLists L{rows, obs_start, obs_kf, obs_desc, first_octave, false};
+    return refresh_run(c, mp_pos, mp_norm, mp_min_dist, mp_max_dist, mp_desc, kf_pose, n_kf, desc_pool, L, n_rows, obs_start[n_rows], scale_factors, n_levels, 0, nullptr,
+                       medoid);
+}
+
+// The lists are DEVICE arrays here, so only the host arguments can be looked at.  What the lists hold -- rows in range and distinct, no
+// empty list (drop_empty of ms_observation_lists), slots, octaves and descriptor indices in range -- is the caller's: ms_observation_lists
+// makes them valid by construction when n_pool covers kf_desc_base + stride and n_levels is the one it was given.
+extern "C" int ms_map_refresh_lists(ms_ctx *c, const double *mp_pos, float *mp_norm, float *mp_min_dist, float *mp_max_dist, uint32_t *mp_desc, int n_mp,
+                                    const double *kf_pose, int n_kf, const uint32_t *desc_pool, int n_pool, const ms_obs_lists *lists, int n_rows, int n_obs,
+                                    const float *scale_factors, int n_levels, int promote_min_obs, uint8_t *mp_flags, int32_t *medoid) {
+    if (!c) return MS_ERR_INVALID;
+    char *why = c->err;
+    const size_t why_bytes = sizeof(c->err);
+    if (n_mp < 0 || n_kf < 0 || n_pool < 0 || n_rows < 0 || n_obs < 0 || n_levels < 1 || promote_min_obs < 0 || !scale_factors)
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: bad arguments");
+    if (n_rows == 0) return MS_OK;
+    if (n_obs < n_rows || n_kf < 1) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: %d observations for %d rows: a row entry has no observations", n_obs, n_rows);
+    if (!mp_pos || !mp_norm || !mp_min_dist || !mp_max_dist || !kf_pose || !lists || !lists->rows || !lists->obs_start || !lists->obs_kf || !lists->first_octave)
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: missing array");
+    if (promote_min_obs > 0 && !mp_flags) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: promote_min_obs %d and there is no mp_flags", promote_min_obs);
+    const bool with_desc = desc_pool != nullptr && lists->obs_desc != nullptr;
+    if (with_desc && !mp_desc) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: a descriptor pool without the table's descriptors");
+    if (with_desc && ((reinterpret_cast<uintptr_t>(mp_desc) | reinterpret_cast<uintptr_t>(desc_pool)) & 15u))
+        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: descriptor arrays must be 16-byte aligned");
+    const RefreshLists L{lists->rows, lists->obs_start, lists->obs_kf, lists->obs_desc, lists->first_octave, true};
+    return refresh_run(c, mp_pos, mp_norm, mp_min_dist, mp_max_dist, mp_desc, kf_pose, n_kf, desc_pool, L, n_rows, n_obs, scale_factors, n_levels, promote_min_obs, mp_flags,
+                       medoid);
 }
 
 extern "C" int ms_loop_correct_check(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const double *T, const int32_t *kf_slot, const uint8_t *kf_rigid,

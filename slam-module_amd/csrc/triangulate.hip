@@ -2,6 +2,9 @@
 // the device map-point table, written where the table lies.  tests/triangulate_ref.py is the specification; this file follows
 // it operation for operation.
 //
+// ms_triangulate takes the observation lists as host arrays and uploads them; ms_triangulate_lists reads the device lists of
+// ms_observation_lists where they lie.  Both run the one launch sequence of tri_run.
+//
 // Two launches whatever the number of rows:
 //   k_tri_rays    one lane per observation: the world ray R^T * bearing into the workspace (what the pair test of the angle check reads)
 //   k_tri_points  a group of 16 lanes per map point, one observation per lane per round of 16:
@@ -472,28 +475,34 @@ extern "C" int ms_triangulate_check(const double *mp_pos, int n_mp, const double
     return MS_OK;
 }
 
-extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int n_mp, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam,
-                              const int32_t *kf_focal, const int32_t *rows, const uint8_t *was_triangulated, int n_rows, const int32_t *obs_start,
-                              const int32_t *obs_kf, const float *obs_x, const float *obs_y, const int32_t *obs_octave, const float *obs_depth,
-                              const ms_tri_settings *settings, int mode, uint8_t *status, uint8_t *reason, int32_t *n_pass) {
-    if (!c) return MS_ERR_INVALID;
+namespace {
+
+// The lists of one call: HOST arrays that are uploaded (ms_triangulate), or DEVICE arrays the kernels read where they lie (ms_triangulate_lists).
+struct TriLists {
+    const int32_t *rows;
+    const uint8_t *was;
+    const int32_t *obs_start, *obs_kf, *obs_octave;
+    const float *obs_x, *obs_y, *obs_depth;                  // obs_depth may be null
+    bool on_device;
+};
+
+// the one launch sequence of both entry points; everything is validated by the caller
+int tri_run(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam, const int32_t *kf_focal, const TriLists &L, int n_rows,
+            int n_obs, const ms_tri_settings *settings, int mode, uint8_t *status, uint8_t *reason, int32_t *n_pass) {
     int rc;
-    if ((rc = ms_triangulate_check(mp_pos, n_mp, kf_pose, n_kf, kf_cam, kf_focal, rows, was_triangulated, n_rows, obs_start, obs_kf, obs_x, obs_y, obs_octave,
-                                   settings, mode, c->err, sizeof(c->err))))
-        return rc;
-    if (n_rows == 0) return MS_OK;
     MsRange range("triangulate");
-    const size_t nr = (size_t)n_rows, no = (size_t)obs_start[n_rows], nk = (size_t)n_kf, nl = (size_t)settings->n_levels;
+    const size_t nr = (size_t)n_rows, no = (size_t)n_obs, nk = (size_t)n_kf, nl = (size_t)settings->n_levels;
+    const size_t ur = L.on_device ? 0 : nr, uo = L.on_device ? 0 : no;               // what of the lists is uploaded
     // upload block: cameras | focal lengths | sigmas | rows | was | obs_start | obs_kf | obs_octave | obs_x | obs_y | obs_depth; then (host only) the results
     MsLayout up;
     const auto l_cam = up.array<ms_pinhole>(nk);
     const auto l_focal = up.array<int32_t>(nk);
     const auto l_sigma = up.array<float>(nl);
-    const auto l_rows = up.array<int32_t>(nr);
-    const auto l_was = up.array<uint8_t>(nr);
-    const auto l_start = up.array<int32_t>(nr + 1);
-    const auto l_kf = up.array<int32_t>(no), l_oct = up.array<int32_t>(no);
-    const auto l_x = up.array<float>(no), l_y = up.array<float>(no), l_depth = up.array<float>(no);
+    const auto l_rows = up.array<int32_t>(ur);
+    const auto l_was = up.array<uint8_t>(ur);
+    const auto l_start = up.array<int32_t>(L.on_device ? 0 : nr + 1);
+    const auto l_kf = up.array<int32_t>(uo), l_oct = up.array<int32_t>(uo);
+    const auto l_x = up.array<float>(uo), l_y = up.array<float>(uo), l_depth = up.array<float>(uo);
     MsLayout host = up, dev = up;
     const auto l_down = host.array<int32_t>(2 * nr);
     // device-only block: rays | results
@@ -507,21 +516,27 @@ extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int 
     l_cam.fill(hs, kf_cam);
     l_focal.fill(hs, kf_focal);
     l_sigma.fill(hs, settings->level_sigma_sq);
-    l_rows.fill(hs, rows);
-    l_was.fill(hs, was_triangulated);
-    l_start.fill(hs, obs_start);
-    l_kf.fill(hs, obs_kf);
-    l_oct.fill(hs, obs_octave);
-    l_x.fill(hs, obs_x);
-    l_y.fill(hs, obs_y);
-    if (obs_depth) l_depth.fill(hs, obs_depth);
-    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     TriArgs A;
+    if (L.on_device) {
+        A.rows = L.rows; A.was = L.was; A.obs_start = L.obs_start;
+        A.obs_kf = L.obs_kf; A.obs_oct = L.obs_octave; A.obs_x = L.obs_x; A.obs_y = L.obs_y;
+        A.obs_depth = L.obs_depth;
+    } else {
+        l_rows.fill(hs, L.rows);
+        l_was.fill(hs, L.was);
+        l_start.fill(hs, L.obs_start);
+        l_kf.fill(hs, L.obs_kf);
+        l_oct.fill(hs, L.obs_octave);
+        l_x.fill(hs, L.obs_x);
+        l_y.fill(hs, L.obs_y);
+        if (L.obs_depth) l_depth.fill(hs, L.obs_depth);
+        A.rows = l_rows.at(ds); A.was = l_was.at(ds); A.obs_start = l_start.at(ds);
+        A.obs_kf = l_kf.at(ds); A.obs_oct = l_oct.at(ds); A.obs_x = l_x.at(ds); A.obs_y = l_y.at(ds);
+        A.obs_depth = L.obs_depth ? l_depth.at(ds) : nullptr;
+    }
+    MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     A.mp_pos = mp_pos; A.mp_flags = mp_flags; A.kf_pose = kf_pose;
     A.cam = l_cam.at(ds); A.focal = l_focal.at(ds); A.sigma = l_sigma.at(ds);
-    A.rows = l_rows.at(ds); A.was = l_was.at(ds); A.obs_start = l_start.at(ds);
-    A.obs_kf = l_kf.at(ds); A.obs_oct = l_oct.at(ds); A.obs_x = l_x.at(ds); A.obs_y = l_y.at(ds);
-    A.obs_depth = obs_depth ? l_depth.at(ds) : nullptr;
     A.ray = l_ray.at(ds);
     A.out = l_out.at(ds);
     A.cos_two = std::cos(settings->min_angle_two_obs * M_PI / 180.0);            // checkTriangulationAngle, :560
@@ -544,4 +559,42 @@ extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int 
         }
     }
     return MS_OK;
+}
+
+}  // namespace
+
+extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int n_mp, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam,
+                              const int32_t *kf_focal, const int32_t *rows, const uint8_t *was_triangulated, int n_rows, const int32_t *obs_start,
+                              const int32_t *obs_kf, const float *obs_x, const float *obs_y, const int32_t *obs_octave, const float *obs_depth,
+                              const ms_tri_settings *settings, int mode, uint8_t *status, uint8_t *reason, int32_t *n_pass) {
+    if (!c) return MS_ERR_INVALID;
+    int rc;
+    if ((rc = ms_triangulate_check(mp_pos, n_mp, kf_pose, n_kf, kf_cam, kf_focal, rows, was_triangulated, n_rows, obs_start, obs_kf, obs_x, obs_y, obs_octave,
+                                   settings, mode, c->err, sizeof(c->err))))
+        return rc;
+    if (n_rows == 0) return MS_OK;
+    const TriLists L{rows, was_triangulated, obs_start, obs_kf, obs_octave, obs_x, obs_y, obs_depth, false};
+    return tri_run(c, mp_pos, mp_flags, kf_pose, n_kf, kf_cam, kf_focal, L, n_rows, obs_start[n_rows], settings, mode, status, reason, n_pass);
+}
+
+// The lists are DEVICE arrays here, so only the host arguments can be looked at: the settings and the mode as ms_triangulate_check does, the
+// sizes and the pointers.  What the lists hold is the caller's: ms_observation_lists makes them valid by construction.
+extern "C" int ms_triangulate_lists(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int n_mp, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam,
+                                    const int32_t *kf_focal, const ms_obs_lists *lists, int n_rows, int n_obs, const ms_tri_settings *settings, int mode,
+                                    uint8_t *status, uint8_t *reason, int32_t *n_pass) {
+    if (!c) return MS_ERR_INVALID;
+    int rc;
+    char *why = c->err;
+    const size_t why_bytes = sizeof(c->err);
+    if ((rc = ms_triangulate_check(mp_pos, n_mp, kf_pose, n_kf, kf_cam, kf_focal, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, settings, mode, why,
+                                   why_bytes)))
+        return rc;
+    if (n_rows < 0 || n_obs < 0) TRI_INVALID("bad arguments");
+    if (n_rows == 0) return MS_OK;
+    if (n_rows > MS_TRI_MAX_ROWS) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d rows, at most %d per call", n_rows, MS_TRI_MAX_ROWS);
+    if (n_obs > MS_TRI_MAX_OBS) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d observations, at most %d per call", n_obs, MS_TRI_MAX_OBS);
+    if (!mp_pos || !kf_pose || !kf_cam || !kf_focal || !lists || !lists->rows || !lists->was_triangulated || !lists->obs_start) TRI_INVALID("missing array");
+    if (n_obs > 0 && (!lists->obs_kf || !lists->obs_x || !lists->obs_y || !lists->obs_octave || n_kf < 1)) TRI_INVALID("missing array");
+    const TriLists L{lists->rows, lists->was_triangulated, lists->obs_start, lists->obs_kf, lists->obs_octave, lists->obs_x, lists->obs_y, lists->obs_depth, true};
+    return tri_run(c, mp_pos, mp_flags, kf_pose, n_kf, kf_cam, kf_focal, L, n_rows, n_obs, settings, mode, status, reason, n_pass);
 }

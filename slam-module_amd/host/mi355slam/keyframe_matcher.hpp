@@ -520,6 +520,10 @@ public:
         return std::vector<int>(medoid.begin(), medoid.end());
     }
     double *mutablePosition() { return pos_; }
+    float *mutableNorm() { return norm_; }                   // what updateMapPoints writes, with the two distances and the descriptors
+    float *mutableMinDistance() { return min_; }
+    float *mutableMaxDistance() { return max_; }
+    std::uint32_t *mutableDescriptor() { return desc_; }
     std::size_t size() const { return n_; }
     const double *position() const { return pos_; }
     const float *norm() const { return norm_; }
@@ -902,6 +906,158 @@ inline CullResult cullMap(Context &ctx, DeviceKeyframeMapPoints &table, DeviceMa
         chain.previous[k] = chain.next[k] = -1;
         chain.id[k] = -1;
     }
+    return out;
+}
+
+// ---- observation lists on the device (ms_observation_lists, ms_map_refresh_lists, ms_triangulate_lists) -------------------------------
+// The keypoints of every keyframe on the device, parallel to DeviceKeyframeMapPoints: kp.pt.x / kp.pt.y, kp.octave and keyPointDepth of
+// keypoint j of the keyframe in a slot (a depth <= 0 is "none", as the triangulator reads it).  update() uploads one slot when its keyframe arrives.
+class DeviceKeypointTable {
+public:
+    DeviceKeypointTable(Context &ctx, std::size_t slots, std::size_t stride) : ctx_(ctx), n_(slots), stride_(stride) {
+        if (stride_ < 1) throw std::invalid_argument("DeviceKeypointTable: stride < 1");
+        for (void **p : {&x_, &y_, &octave_, &depth_}) ctx_.check(ms_dev_alloc(ctx_.get(), 4 * n_ * stride_ + 16, p), "ms_dev_alloc");
+        const std::vector<float> zero(n_ * stride_, 0.0f);   // all-zero bits: x = y = 0, octave 0, no depth
+        for (void *p : {x_, y_, octave_, depth_})
+            if (n_) ctx_.check(ms_dev_upload(ctx_.get(), p, zero.data(), 4 * zero.size()), "ms_dev_upload");
+    }
+    ~DeviceKeypointTable() { for (void *p : {x_, y_, octave_, depth_}) ms_dev_free(ctx_.get(), p); }
+    DeviceKeypointTable(const DeviceKeypointTable &) = delete;
+    // the keypoints of the keyframe in `slot` (shorter than the stride: the rest keeps what it held; no map point is bound there).  depth may be empty
+    void update(std::size_t slot, const std::vector<float> &x, const std::vector<float> &y, const std::vector<std::int32_t> &octave, const std::vector<float> &depth) {
+        const std::size_t n = x.size();
+        if (slot >= n_ || n > stride_ || y.size() != n || octave.size() != n || (!depth.empty() && depth.size() != n))
+            throw std::invalid_argument("DeviceKeypointTable::update: slot or lengths outside the table");
+        if (n == 0) return;
+        const std::vector<float> none(n, -1.0f);
+        const void *src[4] = {x.data(), y.data(), octave.data(), depth.empty() ? none.data() : depth.data()};
+        void *dst[4] = {x_, y_, octave_, depth_};
+        for (int i = 0; i < 4; ++i) ctx_.check(ms_dev_upload(ctx_.get(), static_cast<char *>(dst[i]) + 4 * slot * stride_, src[i], 4 * n), "ms_dev_upload");
+    }
+    std::size_t size() const { return n_; }
+    std::size_t stride() const { return stride_; }
+    const float *x() const { return static_cast<const float *>(x_); }
+    const float *y() const { return static_cast<const float *>(y_); }
+    const std::int32_t *octave() const { return static_cast<const std::int32_t *>(octave_); }
+    const float *depth() const { return static_cast<const float *>(depth_); }
+private:
+    Context &ctx_;
+    std::size_t n_, stride_;
+    void *x_ = nullptr, *y_ = nullptr, *octave_ = nullptr, *depth_ = nullptr;
+};
+
+// Which rows an observation-list call takes: the map points of one keyframe slot (the loops of mapper_helpers.cpp:1062 / :1085), or rows
+// that already lie on the device (the output of a map-point union, removed rows), and the filter of the loop (MS_OBS_*).
+struct ObservationSelection {
+    std::int32_t slot = -1;                  // >= 0: MS_OBS_FROM_SLOT
+    const std::int32_t *deviceRows = nullptr;   // otherwise MS_OBS_FROM_ROWS: DEVICE [rowCount]
+    std::size_t rowCount = 0;
+    int filter = MS_OBS_ALL;
+    bool dropEmpty = false;
+};
+
+// MapPoint::observations of chosen rows as CSR lists in device memory (ms_observation_lists): owns the buffers of ms_obs_lists and regrows
+// them when a call reports MS_ERR_CAPACITY.  Nothing of the lists is on the host; rows() and friends are DEVICE pointers for the next call.
+class DeviceObservationLists {
+public:
+    explicit DeviceObservationLists(Context &ctx, std::size_t rows = 256, std::size_t observations = 2048) : ctx_(ctx) { reserve(rows, observations); }
+    ~DeviceObservationLists() { release(); }
+    DeviceObservationLists(const DeviceObservationLists &) = delete;
+    // kfIds: per slot the KfId, -1 for an empty slot; descBase: per slot the DeviceDescriptorPool index of its keypoint 0, -1 for none
+    // (empty: no descriptor indices); levels: octaves outside [0, levels) are an error (0: not looked at).
+    void build(const DeviceKeyframeMapPoints &table, const DeviceKeypointTable &keypoints, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &kfIds,
+               const std::vector<std::int32_t> &descBase, const ObservationSelection &selection, int levels) {
+        if (kfIds.size() != table.size() || (!descBase.empty() && descBase.size() != table.size())) throw std::invalid_argument("DeviceObservationLists::build: one KfId and one base per slot");
+        if (keypoints.size() != table.size() || keypoints.stride() != table.stride()) throw std::invalid_argument("DeviceObservationLists::build: the keypoint table does not match the keyframe table");
+        if (flags && flags->size() < table.mapPointCount()) throw std::invalid_argument("DeviceObservationLists::build: fewer flags than map points");
+        const ms_obs_select sel{selection.slot >= 0 ? MS_OBS_FROM_SLOT : MS_OBS_FROM_ROWS, selection.filter, selection.dropEmpty ? 1 : 0, selection.slot, selection.deviceRows,
+                                (std::int32_t)selection.rowCount};
+        for (int attempt = 0;; ++attempt) {
+            ms_obs_lists l = lists();
+            if (descBase.empty()) l.obs_desc = nullptr;
+            if (!flags) l.was_triangulated = nullptr;
+            std::int32_t nRows = 0, nObs = 0;
+            const int rc = ms_observation_lists(ctx_.get(), table.table(), (int)table.size(), (int)table.stride(), (int)table.mapPointCount(), kfIds.data(),
+                                                flags ? flags->flags() : nullptr, keypoints.x(), keypoints.y(), keypoints.octave(), keypoints.depth(),
+                                                descBase.empty() ? nullptr : descBase.data(), &sel, levels, &l, (int)capRows_, (int)capObs_, &nRows, &nObs);
+            if (rc == MS_ERR_CAPACITY && attempt == 0 && ((std::size_t)nRows > capRows_ || (std::size_t)nObs > capObs_)) {
+                reserve(std::max<std::size_t>(nRows, capRows_), std::max<std::size_t>(nObs, capObs_));      // the needed counts came back: once is enough
+                continue;
+            }
+            ctx_.check(rc, "ms_observation_lists");
+            nRows_ = (std::size_t)nRows; nObs_ = (std::size_t)nObs;
+            hasDesc_ = !descBase.empty();
+            return;
+        }
+    }
+    std::size_t rowCount() const { return nRows_; }
+    std::size_t observationCount() const { return nObs_; }
+    bool hasDescriptors() const { return hasDesc_; }
+    ms_obs_lists lists() const {
+        return ms_obs_lists{i32(0), i32(1), i32(2), i32(3), static_cast<std::uint8_t *>(buf_[4]), i32(5), i32(6), i32(7), i32(8), f32(9), f32(10), f32(11)};
+    }
+    // a copy for the host (tests, debugging): `count` int32 from a row array (rows, obs_start, n_obs_row, first_octave) or an observation array
+    std::vector<std::int32_t> download(const std::int32_t *deviceArray, std::size_t count) const {
+        std::vector<std::int32_t> out(count);
+        if (count) ctx_.check(ms_dev_download(ctx_.get(), out.data(), deviceArray, 4 * count), "ms_dev_download");
+        return out;
+    }
+private:
+    std::int32_t *i32(int i) const { return static_cast<std::int32_t *>(buf_[i]); }
+    float *f32(int i) const { return static_cast<float *>(buf_[i]); }
+    void release() { for (void *&p : buf_) { if (p) ms_dev_free(ctx_.get(), p); p = nullptr; } }
+    void reserve(std::size_t rows, std::size_t observations) {
+        release();
+        capRows_ = rows + rows / 2; capObs_ = observations + observations / 2;
+        for (int i = 0; i < 12; ++i) ctx_.check(ms_dev_alloc(ctx_.get(), 4 * ((i < 5 ? capRows_ + 1 : capObs_)) + 16, &buf_[i]), "ms_dev_alloc");
+    }
+    Context &ctx_;
+    void *buf_[12] = {nullptr};              // in the order of ms_obs_lists' fields
+    std::size_t capRows_ = 0, capObs_ = 0, nRows_ = 0, nObs_ = 0;
+    bool hasDesc_ = false;
+};
+
+// The map-point update of a new keyframe, mapper_helpers.cpp:1062-1077, without a per-point host structure: the observation lists of the
+// current keyframe's usable map points (status neither NOT_TRIANGULATED nor BAD, :1066) are built on the device, then updateDescriptor +
+// updateDistanceAndNorm (:1069-1070) and the status promotion of :1072-1076 run on them where they lie.  `pool` may be null (descriptors stay).
+// Returns the number of refreshed map points; `lists` holds them afterwards.
+inline std::size_t updateMapPoints(Context &ctx, DeviceObservationLists &lists, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags, const DeviceKeyframeMapPoints &table,
+                                   const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses, const std::vector<std::int32_t> &kfIds,
+                                   const std::vector<std::int32_t> &descBase, const DeviceDescriptorPool *pool, std::int32_t currentSlot, int minObservationsForBA,
+                                   const StaticSettings &settings) {
+    ObservationSelection sel;
+    sel.slot = currentSlot; sel.filter = MS_OBS_REFRESH; sel.dropEmpty = true;
+    const int levels = (int)settings.scaleFactors.size();
+    lists.build(table, keypoints, &flags, kfIds, pool ? descBase : std::vector<std::int32_t>(), sel, levels);
+    const ms_obs_lists l = lists.lists();
+    ctx.check(ms_map_refresh_lists(ctx.get(), mapPoints.position(), mapPoints.mutableNorm(), mapPoints.mutableMinDistance(), mapPoints.mutableMaxDistance(),
+                                   mapPoints.mutableDescriptor(), (int)mapPoints.size(), poses.pose(),
+                                   (int)poses.size(), pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, &l, (int)lists.rowCount(), (int)lists.observationCount(),
+                                   settings.scaleFactors.data(), levels, std::max(minObservationsForBA, 1), flags.mutableFlags(), nullptr), "ms_map_refresh_lists");
+    return lists.rowCount();
+}
+
+// The re-triangulation after local BA, mapper_helpers.cpp:1085-1092: the current keyframe's map points that are not TRIANGULATED or have at
+// least two observations (:1088), triangulated from device lists.  The per-point results come back as from triangulateMapPoints, in the
+// order of the keyframe's keypoints.
+inline TriangulateResult retriangulateCurrent(Context &ctx, DeviceObservationLists &lists, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags,
+                                              const DeviceKeyframeMapPoints &table, const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses,
+                                              const KeyframeCameras &cams, const std::vector<std::int32_t> &kfIds, std::int32_t currentSlot, const StaticSettings &settings,
+                                              TriangulationMethod method) {
+    if (cams.camera.size() != poses.size() || cams.focalLength.size() != poses.size()) throw std::invalid_argument("retriangulateCurrent: one camera per keyframe slot");
+    ObservationSelection sel;
+    sel.slot = currentSlot; sel.filter = MS_OBS_RETRIANGULATE;
+    lists.build(table, keypoints, &flags, kfIds, {}, sel, (int)settings.levelSigmaSq.size());
+    const Parameters &p = settings.parameters;
+    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    const std::size_t n = lists.rowCount();
+    TriangulateResult out;
+    out.status.assign(n, 0); out.reason.assign(n, 0); out.passCount.assign(n, 0);
+    const ms_obs_lists l = lists.lists();
+    ctx.check(ms_triangulate_lists(ctx.get(), mapPoints.mutablePosition(), flags.mutableFlags(), (int)mapPoints.size(), poses.pose(), (int)poses.size(), cams.camera.data(),
+                                   cams.focalLength.data(), &l, (int)n, (int)lists.observationCount(), &s, (int)method, out.status.data(), out.reason.data(),
+                                   out.passCount.data()), "ms_triangulate_lists");
     return out;
 }
 

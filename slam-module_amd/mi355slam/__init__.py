@@ -986,6 +986,40 @@ class MapPointTable:
                                             _vp(n_pass)), "ms_triangulate")
         return (status, reason, n_pass) if outputs else None
 
+    def triangulate_lists(self, poses, cams, focal, lists, n_rows, n_obs, settings, mode, flags=None, outputs=True, with_depth=True):
+        """triangulate() with the observation lists read on the device (ms_triangulate_lists): lists = an ObservationLists filled by
+        KeyframeTable.observation_lists, n_rows / n_obs its counts.  with_depth=False passes no obs_depth.  Returns (status, reason,
+        n_pass) per entry, or None with outputs=False."""
+        cam_rows = np.asarray(cams, np.float64).reshape(-1, 6)
+        focal = _i32(focal)
+        if len(cam_rows) != poses.n or len(focal) != poses.n:
+            raise ValueError("triangulate_lists: one camera and one focal length per keyframe slot")
+        K = (Pinhole * max(poses.n, 1))(*[Pinhole(c[0], c[1], c[2], c[3], int(c[4]), int(c[5])) for c in cam_rows])
+        sig = np.ascontiguousarray(settings["level_sigma_sq"], np.float32).reshape(-1)
+        S = TriSettingsC(sig.ctypes.data, len(sig), float(settings["min_angle_two_obs"]), float(settings["min_angle_multiple_obs"]),
+                         float(settings["rel_reprojection_threshold"]), int(bool(settings.get("dense_stereo_depth", False))))
+        L = lists.struct()
+        if not with_depth:
+            L.obs_depth = None
+        n = max(int(n_rows), 1)
+        status, reason, n_pass = (np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.int32)) if outputs else (None, None, None)
+        self.ctx.check(lib().ms_triangulate_lists(self.ctx._h, _vp(self.pos), _vp(flags), self.n, _vp(poses.pose), poses.n, K, _vp(focal), C.byref(L), int(n_rows),
+                                                  int(n_obs), C.byref(S), int(mode), _vp(status), _vp(reason), _vp(n_pass)), "ms_triangulate_lists")
+        return (status[:n_rows], reason[:n_rows], n_pass[:n_rows]) if outputs else None
+
+    def refresh_lists(self, poses, lists, n_rows, n_obs, scale_factors_, pool=None, promote_min_obs=0, flags=None, want_medoid=True):
+        """map_refresh() with the observation lists read on the device (ms_map_refresh_lists): lists = an ObservationLists filled by
+        KeyframeTable.observation_lists with drop_empty set, n_rows / n_obs its counts.  promote_min_obs > 0 also sets flags (a DevBuf of
+        [n] uint8) of the listed rows to 3 (at least that many observations) or 2.  Returns medoid [n_rows] or None."""
+        sf = np.ascontiguousarray(scale_factors_, np.float32)
+        medoid = np.full(max(int(n_rows), 1), -1, np.int32) if want_medoid else None
+        n_pool = int(np.prod(pool.shape)) // 8 if pool is not None else 0
+        L = lists.struct()
+        self.ctx.check(lib().ms_map_refresh_lists(self.ctx._h, _vp(self.pos), _vp(self.norm), _vp(self.min_dist), _vp(self.max_dist), _vp(self.desc), self.n,
+                                                  _vp(poses.pose), poses.n, _vp(pool), n_pool, C.byref(L), int(n_rows), int(n_obs), _vp(sf), len(sf),
+                                                  int(promote_min_obs), _vp(flags), _vp(medoid)), "ms_map_refresh_lists")
+        return medoid[:n_rows] if want_medoid else None
+
 
 def gate_views_pack(views):
     """(GateViewC array, mp_index) for a list of view dicts: R [3, 3], t [3], cam (fx, fy, cx, cy, width, height), threshold, view_cos_limit
@@ -1285,6 +1319,154 @@ class KeyframeTable:
                 if b is not None:
                     b.free()
         return out
+
+    def observation_lists_device(self, lists, kf_id, n_mp, select, kp=None, desc_base=None, flags=None, n_levels=0, cap_rows=None, cap_obs=None):
+        """ms_observation_lists into an ObservationLists, everything left on the device.  select: dict(source, filter, drop_empty, slot,
+        rows_in) -- rows_in a DevBuf plus n_in, or an array that is uploaded for the call; kp = a KeypointTable or None; desc_base [n_kf]
+        int32 or None; flags = a DevBuf or None.  cap_rows / cap_obs below the buffers' sizes may be given.  Returns (rc, n_rows, n_obs)
+        without raising: MS_ERR_CAPACITY still reports the needed counts."""
+        kf_id = _i32(kf_id)
+        if len(kf_id) != self.n_kf:
+            raise ValueError("kf_id describes %d slots, the table has %d" % (len(kf_id), self.n_kf))
+        if kp is not None and (kp.n_kf, kp.stride) != (self.n_kf, self.stride):
+            raise ValueError("the keypoint table is %d x %d, kf_mp %d x %d" % (kp.n_kf, kp.stride, self.n_kf, self.stride))
+        base = None if desc_base is None else _i32(desc_base)
+        if base is not None and len(base) != self.n_kf:
+            raise ValueError("desc_base describes %d slots, the table has %d" % (len(base), self.n_kf))
+        rows_in, own = select.get("rows_in"), None
+        if rows_in is not None and not isinstance(rows_in, DevBuf):
+            a = _i32(rows_in)
+            n_in = len(a)
+            rows_in = own = self.ctx.upload(a if n_in else np.zeros(1, np.int32))
+        else:
+            n_in = int(select.get("n_in", 0))
+        S = ObsSelectC(int(select["source"]), int(select.get("filter", OBS_ALL)), int(select.get("drop_empty", 0)), int(select.get("slot", -1)),
+                       rows_in.ptr if rows_in is not None else None, n_in)
+        L = lists.struct(kp, base is not None, flags is not None)
+        n_rows, n_obs = C.c_int32(0), C.c_int32(0)
+        x, y, octv, depth = (getattr(kp, k) for k in ("x", "y", "octave", "depth")) if kp is not None else (None,) * 4
+        try:
+            rc = lib().ms_observation_lists(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, int(n_mp), _vp(kf_id), _vp(flags), _vp(x), _vp(y), _vp(octv),
+                                            _vp(depth), _vp(base), C.byref(S), int(n_levels), C.byref(L), lists.cap_rows if cap_rows is None else int(cap_rows),
+                                            lists.cap_obs if cap_obs is None else int(cap_obs), C.byref(n_rows), C.byref(n_obs))
+        finally:
+            if own is not None:
+                own.free()
+        return rc, n_rows.value, n_obs.value
+
+    def observation_lists(self, kf_id, n_mp, select, kp=None, desc_base=None, mp_flags=None, n_levels=0, lists=None):
+        """MapPoint::observations of chosen rows as CSR lists on the device (ms_observation_lists; see observation_lists_device).  Fills
+        `lists` (an ObservationLists; allocated here when None), growing it when the call reports MS_ERR_CAPACITY.  mp_flags: a DevBuf,
+        an array that is uploaded for the call, or None.  Returns (lists, n_rows, n_obs)."""
+        flags, own = self._flags(mp_flags, int(n_mp))
+        if lists is None:
+            lists = ObservationLists(self.ctx, 256, 1024)
+        try:
+            rc, n_rows, n_obs = self.observation_lists_device(lists, kf_id, n_mp, select, kp, desc_base, flags, n_levels)
+            if rc == MS_ERR_CAPACITY and (n_rows > lists.cap_rows or n_obs > lists.cap_obs):
+                lists.grow(n_rows, n_obs)
+                rc, n_rows, n_obs = self.observation_lists_device(lists, kf_id, n_mp, select, kp, desc_base, flags, n_levels)
+            self.ctx.check(rc, "ms_observation_lists")
+        finally:
+            if own is not None:
+                own.free()
+        return lists, n_rows, n_obs
+
+
+# ---- observation lists on the device (ms_observation_lists) ----
+MS_ERR_INVALID, MS_ERR_CAPACITY = -1, -4
+OBS_FROM_ROWS, OBS_FROM_SLOT = 0, 1
+OBS_ALL, OBS_REFRESH, OBS_RETRIANGULATE = 0, 1, 2
+
+
+class ObsSelectC(C.Structure):
+    """ms_obs_select."""
+    _fields_ = [("source", C.c_int32), ("filter", C.c_int32), ("drop_empty", C.c_int32), ("slot", C.c_int32), ("rows_in", C.c_void_p), ("n_in", C.c_int32)]
+
+
+class ObsListsC(C.Structure):
+    """ms_obs_lists: device pointers."""
+    _fields_ = [(k, C.c_void_p) for k in ("rows", "obs_start", "n_obs_row", "first_octave", "was_triangulated", "obs_kf", "obs_kp", "obs_octave", "obs_desc",
+                                          "obs_x", "obs_y", "obs_depth")]
+
+
+class KeypointTable:
+    """The keypoints of every keyframe slot on the device, parallel to KeyframeTable.kf_mp: x, y, depth float32 and octave int32, each
+    [n_kf, stride] (KeyPoint::pt, ::octave and keyPointDepth of keypoint j of the keyframe in slot k)."""
+    _FIELDS = (("x", np.float32), ("y", np.float32), ("octave", np.int32), ("depth", np.float32))
+
+    def __init__(self, ctx, x, y, octave, depth):
+        self.ctx = ctx
+        arrs = dict(x=x, y=y, octave=octave, depth=depth)
+        self.n_kf, self.stride = np.asarray(x).shape
+        for name, dt in self._FIELDS:
+            a = np.ascontiguousarray(arrs[name], dt)
+            if a.shape != (self.n_kf, self.stride):
+                raise ValueError("%s is %s, x %d x %d" % (name, a.shape, self.n_kf, self.stride))
+            setattr(self, name, ctx.upload(a if a.size else np.zeros((1, 1), dt)))
+
+    def update(self, slot, **fields):
+        """Re-upload one slot of the named fields (x=..., octave=...), each [stride]."""
+        if not 0 <= slot < self.n_kf:
+            raise ValueError("slot %d outside the table of %d" % (slot, self.n_kf))
+        for name, dt in self._FIELDS:
+            if name in fields:
+                a = np.ascontiguousarray(fields[name], dt).reshape(self.stride)
+                self.ctx.check(lib().ms_dev_upload(self.ctx._h, C.c_void_p(getattr(self, name).ptr + 4 * self.stride * slot), _vp(a), C.c_size_t(a.nbytes)), "ms_dev_upload")
+
+    def free(self):
+        for name, _ in self._FIELDS:
+            getattr(self, name).free()
+
+
+class ObservationLists:
+    """The device buffers of ms_obs_lists for up to cap_rows rows and cap_obs observations (reusable across calls; grow() reallocates)."""
+    _ROW = (("rows", np.int32), ("obs_start", np.int32), ("n_obs_row", np.int32), ("first_octave", np.int32), ("was_triangulated", np.uint8))
+    _OBS = (("obs_kf", np.int32), ("obs_kp", np.int32), ("obs_octave", np.int32), ("obs_desc", np.int32), ("obs_x", np.float32), ("obs_y", np.float32),
+            ("obs_depth", np.float32))
+
+    def __init__(self, ctx, cap_rows, cap_obs, guard=0):
+        self.ctx, self.guard = ctx, int(guard)               # guard: bytes kept behind every buffer (tests look at them)
+        self.cap_rows = self.cap_obs = 0
+        self._bufs = {}
+        self.grow(cap_rows, cap_obs)
+
+    def grow(self, cap_rows, cap_obs):
+        self.free()
+        self.cap_rows, self.cap_obs = int(cap_rows), int(cap_obs)
+        for name, dt in self._ROW:
+            self._bufs[name] = self.ctx.alloc(np.dtype(dt).itemsize * (self.cap_rows + (name == "obs_start")) + self.guard + 16)
+        for name, dt in self._OBS:
+            self._bufs[name] = self.ctx.alloc(np.dtype(dt).itemsize * self.cap_obs + self.guard + 16)
+
+    def __getitem__(self, name):
+        return self._bufs[name]
+
+    def struct(self, kp=True, desc=True, flags=True):
+        """ms_obs_lists over the buffers; the outputs whose inputs are missing (no keypoint table, descriptor bases or flags) are NULL."""
+        skip = set()
+        if not kp:
+            skip |= {"first_octave", "obs_octave", "obs_x", "obs_y", "obs_depth"}
+        if not desc:
+            skip.add("obs_desc")
+        if not flags:
+            skip.add("was_triangulated")
+        return ObsListsC(*[None if k in skip else self._bufs[k].ptr for k, _ in ObsListsC._fields_])
+
+    def download(self, n_rows, n_obs, names=None):
+        """dict of the arrays, n_rows / n_rows + 1 / n_obs long."""
+        out = {}
+        for name, dt in self._ROW + self._OBS:
+            if names is not None and name not in names:
+                continue
+            n = n_obs if (name, dt) in self._OBS else n_rows + (name == "obs_start")
+            out[name] = self._bufs[name].download(dt, (n,)) if n else np.zeros(0, dt)
+        return out
+
+    def free(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
 
 
 class ProjectionKeyframe:
