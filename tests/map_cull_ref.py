@@ -157,6 +157,68 @@ def run_scene(scene, s, n_cand=None):
     return map_cull(scene["kf_mp"], scene["mp_flags"], scene["mp_live"], scene["n_mp"], scene["kf_id"], scene["kf_t"], scene["cand"][:n], scene["cand_keep"][:n], s)
 
 
+LARGE_N_KF, LARGE_STRIDE = 12, 2048
+LARGE_TRIP = 256 * 256                                       # rows whose block totals k_cull_offsets scans in one trip
+LARGE_N_MP = (LARGE_TRIP, LARGE_TRIP + 1, LARGE_TRIP + 300)  # exactly one trip; one row into the second; a second trip of two blocks
+
+
+def large_scene(n_mp, seed=5):
+    """A table of 12 slots x 2048 entries over n_mp > 65 000 rows, so that the 256-row blocks of the removed-row compaction number more than
+    the 256 whose totals are scanned at a time.  Entries as the GPU tests' random tables draw them: -1, the valid rows, n_mp and n_mp + 1.
+    Slot k is at t = 3 k seconds, the ids are shuffled, every non-current slot is a candidate and none is kept.  Most rows have no
+    observation; the last row is live and has none, so it is removed whatever else is.  Returns the inputs of map_cull plus `current`."""
+    rng = np.random.default_rng(seed)
+    n_kf, stride = LARGE_N_KF, LARGE_STRIDE
+    kf_mp = rng.integers(-1, n_mp + 2, (n_kf, stride)).astype(np.int32)
+    kf_mp[rng.random((n_kf, stride)) < 0.3] = -1
+    kf_mp[kf_mp == n_mp - 1] = -1
+    kf_mp[:, 7] = n_mp + (np.arange(n_kf) & 1)               # among so many rows the draw may leave the two out-of-range values out
+    kf_id = rng.permutation(3 * n_kf)[:n_kf].astype(np.int32)
+    current = int(rng.integers(0, n_kf))
+    kf_id[current] = 3 * n_kf
+    kf_t = 3.0 * np.arange(n_kf)
+    cand = rng.permutation([k for k in range(n_kf) if k != current]).astype(np.int32)
+    mp_flags = rng.integers(0, 4, n_mp).astype(np.uint8)
+    mp_live = ((rng.random(n_mp) < 0.85) * rng.integers(1, 256, n_mp)).astype(np.uint8)
+    mp_live[n_mp - 1] = 1
+    return dict(kf_mp=kf_mp, mp_flags=mp_flags, mp_live=mp_live, n_mp=n_mp, kf_id=kf_id, kf_t=kf_t, cand=cand, cand_keep=np.zeros(len(cand), np.uint8),
+                current=current)
+
+
+def large_settings(scene, ratio_float32=0):
+    return settings(scene["current"], cull_points=1, min_age=10.0, min_obs_for_ba=1, max_critical_ratio=0.9, ratio_float32=ratio_float32)
+
+
+FILL_N_KF, FILL_STRIDE, FILL_N_MP, FILL_N_CAND = 304, 8, 200, 300
+FILL_FIRST = 256 - 2                                         # the first candidate whose entry of the result block [2 + n_cand] lies behind the rows' one workgroup
+
+
+def fill_scene(seed=8):
+    """200 rows (one 256-row workgroup) and 300 candidates: the device's result block of 2 + 300 words is longer than the rows, so the launch
+    that zeroes both has to be sized by the block.  Returns (scene, settings): about nine observations per row and min_obs_for_ba = 8, so that
+    candidates are removed and kept all along the caller's order."""
+    rng = np.random.default_rng(seed)
+    n_kf, stride, n_mp = FILL_N_KF, FILL_STRIDE, FILL_N_MP
+    kf_mp = rng.integers(-1, n_mp + 2, (n_kf, stride)).astype(np.int32)
+    kf_mp[rng.random((n_kf, stride)) < 0.3] = -1
+    kf_id = rng.permutation(3 * n_kf)[:n_kf].astype(np.int32)
+    current = int(rng.integers(0, n_kf))
+    kf_id[current] = 3 * n_kf
+    kf_t = np.round(rng.normal(0, 8, n_kf), 2)
+    cand = rng.permutation([k for k in range(n_kf) if k != current])[:FILL_N_CAND].astype(np.int32)
+    scene = dict(kf_mp=kf_mp, mp_flags=rng.integers(0, 4, n_mp).astype(np.uint8), mp_live=np.ones(n_mp, np.uint8), n_mp=n_mp, kf_id=kf_id, kf_t=kf_t, cand=cand,
+                 cand_keep=np.zeros(len(cand), np.uint8), current=current)
+    return scene, settings(current, cull_points=1, min_age=2.0, min_obs_for_ba=8, max_critical_ratio=0.6)
+
+
+def fill_second_call(scene, first):
+    """The scene again with cand_keep = 1 for every candidate that the first call removed at positions >= FILL_FIRST: those never reach the
+    device, and their cand_removed is the zero the call wrote itself."""
+    keep = np.zeros(len(scene["cand"]), np.uint8)
+    keep[FILL_FIRST:] = first["cand_removed"][FILL_FIRST:]
+    return dict(scene, cand_keep=keep)
+
+
 def find_ratio_pair(scene, s):
     """Settings (differing in ratio_float32 alone) under which some candidate of the scene is decided differently in float32 and in float64:
     a ratio nCritical / nMapPoints of one of the walked candidates, where the two products round to different sides of nCritical."""

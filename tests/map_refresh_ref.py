@@ -299,6 +299,45 @@ def sub_problem(prob, entries):
     return dict(rows=prob["rows"][entries], obs_start=s, obs_kf=prob["obs_kf"][sel], obs_desc=prob["obs_desc"][sel], first_octave=prob["first_octave"][entries])
 
 
+SCAN_TRIP = 1024                                             # rows whose descriptor counts k_refresh_dscan scans in one trip
+SCAN_CASES = ((1024, False), (1025, False), (2100, False), (2100, True))      # (n_rows, longest_last): one trip exactly, one row more, three trips
+
+
+def make_scan_scene(n_rows, longest_last=False):
+    """The refresh fixture at n_rows rows for the device form (ms_map_refresh_lists), whose descriptor lists are counted on the device and
+    scanned SCAN_TRIP rows per trip.  Device-built lists hold obs_desc = -1 for the keyframes without descriptors only, so two such slots
+    (40, 41) are added and every observation the fixture gives obs_desc = -1 (entries 12 and 13) becomes an observation by them, behind the
+    row's others (the lists are in slot order).  Entry 12 (no descriptor at all) changes places with entry 1023 and entry 13 (some) with
+    entry 1024 where there is one: equal neighbouring descriptor offsets on the two sides of the first trip's end.  longest_last: the lists
+    of 256 and 257 descriptors (entries 6 and 7: the longest with a medoid, and the `-2`) change places with entries n_rows - 40 and
+    n_rows - 39, in the last trip.  Returns the scene of make_refresh_scene with kf_pose of 42 slots and prob in that order."""
+    sc = make_refresh_scene(n_mp=2600, n_rows=n_rows, n_pool=20000)
+    rng = np.random.default_rng(78)
+    n_kf = len(sc["kf_pose"])
+    sc["kf_pose"] = np.concatenate([sc["kf_pose"], np.stack([random_pose(rng) for _ in range(2)])])
+    old = sc["prob"]
+    obs_kf, obs_desc = [], []
+    for a, b in zip(old["obs_start"][:-1], old["obs_start"][1:]):
+        kf, od = old["obs_kf"][a:b], old["obs_desc"][a:b]
+        bare = int((od == -1).sum())
+        obs_kf.append(np.concatenate([kf[od != -1], np.full((bare + 1) // 2, n_kf), np.full(bare // 2, n_kf + 1)]).astype(np.int32))
+        obs_desc.append(np.concatenate([od[od != -1], np.full(bare, -1)]).astype(np.int32))
+    prob = dict(old, obs_kf=np.concatenate(obs_kf), obs_desc=np.concatenate(obs_desc))
+    order = np.arange(n_rows)
+    swaps = [(12, SCAN_TRIP - 1), (13, SCAN_TRIP)] + ([(6, n_rows - 40), (7, n_rows - 39)] if longest_last else [])
+    for a, b in swaps:
+        if b < n_rows:
+            order[[a, b]] = order[[b, a]]
+    sc["prob"] = sub_problem(prob, order)
+    sc["lengths"] = np.diff(sc["prob"]["obs_start"]).tolist()
+    return sc
+
+
+def descriptor_counts(prob):
+    """Per row entry: how many of its observations have a descriptor."""
+    return np.add.reduceat((np.asarray(prob["obs_desc"]) != -1).astype(np.int64), prob["obs_start"][:-1])
+
+
 LOOP_LAMBDAS = (0.0, 1e-9, 0.5, 1.0)
 
 

@@ -165,6 +165,28 @@ def scene_b(seed=29):
                 desc_base=base, lengths=dict(B_LENGTHS))
 
 
+C_KF, C_STRIDE, C_MP, C_LONG = 66, 1040, 1100, 1030
+
+
+def scene_c(seed=31):
+    """66 slots x 1040, ids a permutation of the slots.  Row r < 1030 is observed by every slot but slot r % 66: 1030 lists of 65
+    observations, six more than the 1024 workgroups that sort the lists longer than a wave, so some of them sort a second list through the
+    LDS that held their first.  Rows 1030 .. 1099 have up to three observations."""
+    rng = np.random.default_rng(seed)
+    n_kf, stride, n_mp = C_KF, C_STRIDE, C_MP
+    kf_mp = np.full((n_kf, stride), -1, np.int32)
+    for k in range(n_kf):
+        rows = [r for r in range(C_LONG) if r % n_kf != k] + rng.integers(C_LONG, n_mp, 3).tolist()
+        row = np.full(stride, -1, np.int32)
+        row[:len(rows)] = rows
+        kf_mp[k] = rng.permutation(row)
+    short = kf_mp >= C_LONG
+    kf_mp[short & (rng.random(kf_mp.shape) < 0.5)] = -1
+    kp, base = keypoint_table(rng, n_kf, stride)
+    return dict(kf_mp=kf_mp, n_mp=n_mp, kf_id=rng.permutation(n_kf).astype(np.int32) * 2 + 1, mp_flags=rng.integers(0, 4, n_mp).astype(np.uint8), kp=kp,
+                desc_base=base, lengths={r: n_kf - 1 for r in range(C_LONG)})
+
+
 def run_scene(scene, sel, n_levels=N_LEVELS):
     if "transposed" not in scene:
         scene["transposed"] = transpose(scene["kf_mp"], scene["n_mp"], scene["kf_id"])

@@ -268,6 +268,24 @@ def gpu_test_draws():
     return draws
 
 
+LARGE_TRIP = 256 * 256                                       # entries of a view whose workgroup counts k_gate_offsets scans in one trip
+LARGE_N_MP = 3000
+
+
+def large_draws():
+    """(seed, counts, modes, special) of the draws whose long views have more workgroups than the 256 whose counts are scanned at a time; over
+    LARGE_N_MP map points.  The first has a second trip of two workgroups, a view of exactly one trip and a short view; the second has the long
+    view (one entry into its second trip) behind a short one, so that its workgroups do not start the block table.
+    test_project_gate_ref.py holds near_level under 0.1 % of each and the kept entries on both sides of LARGE_TRIP."""
+    return [(3, [LARGE_TRIP + 300, LARGE_TRIP, 700], [SEARCH, SIM3, FUSE], None),
+            (7, [700, LARGE_TRIP + 1], [FUSE, SEARCH], None)]        # seeds 4 .. 6 reject the one entry of the second trip
+
+
+def large_scene(draw):
+    seed, counts, modes, special = draw
+    return make_views(np.random.default_rng(seed), counts, modes, n_mp=LARGE_N_MP, special=special)
+
+
 def make_matcher_scene(seed=77):
     """The end-to-end scene of the GPU tests: 300 map points under a SEARCH and a SIM3 view, and per view a keyframe of 500 keypoints.  The
     map points' descriptors come in 60 clusters of five and each keypoint sits near the projection of a kept map point with that point's

@@ -175,3 +175,38 @@ def test_the_fixed_scene_exercises_every_rule():
     # without the point pass nothing is removed for reasons 1 and 2
     out0 = R.run_scene(scene, R.scene_settings(cull_points=0))
     assert set(out0["removed_why"].tolist()) <= {R.ORPHANED} and np.array_equal(R.run_scene(scene, s, n_cand=0)["cand_removed"], np.zeros(0, np.uint8))
+
+
+def test_the_large_scenes_remove_rows_on_both_sides_of_the_second_scan_trip():
+    # what tests/test_gpu_scan_trips.py relies on: the offsets of the blocks past 65 536 rows are a carry (non-zero, and used)
+    for n_mp in R.LARGE_N_MP:
+        sc = R.large_scene(n_mp)
+        assert sc["kf_mp"].shape == (12, 2048) and len(sc["cand"]) == 11 and sc["current"] not in sc["cand"]
+        assert {-1, n_mp, n_mp + 1} <= set(np.unique(sc["kf_mp"]).tolist())
+        for ratio_float32 in (0, 1):
+            out = R.run_scene(sc, R.large_settings(sc, ratio_float32))
+            rows, why = out["removed_rows"], out["removed_why"]
+            past = rows >= R.LARGE_TRIP
+            print(n_mp, ratio_float32, "removed", len(rows), "past the trip", int(past.sum()), "reasons there", np.bincount(why[past], minlength=4)[1:].tolist(),
+                  "keyframes", out["n_removed_kf"])
+            assert (~past).sum() >= 1000 and set(why.tolist()) == {R.EMPTY, R.AGED, R.ORPHANED} and 1 <= out["n_removed_kf"] < len(sc["cand"])
+            if n_mp == R.LARGE_TRIP + 300:                   # a second trip of two blocks: every reason occurs in it
+                assert past.sum() >= 50 and set(why[past].tolist()) == {R.EMPTY, R.AGED, R.ORPHANED}
+            elif n_mp == R.LARGE_TRIP + 1:                   # a second trip of one row: that row is removed
+                assert rows[-1] == R.LARGE_TRIP and past.sum() == 1
+            else:
+                assert past.sum() == 0
+
+
+def test_the_fill_scene_removes_candidates_behind_the_rows_one_workgroup():
+    sc, s = R.fill_scene()
+    assert sc["n_mp"] <= 256 and len(sc["cand"]) == 300 == len(set(sc["cand"].tolist())) and 2 + len(sc["cand"]) > 256 * ((sc["n_mp"] + 255) // 256)
+    first = R.run_scene(sc, s)
+    assert first["cand_removed"][R.FILL_FIRST:].sum() >= 5 and 0 < first["cand_removed"][:R.FILL_FIRST].sum() < R.FILL_FIRST
+    again = R.fill_second_call(sc, first)
+    kept = again["cand_keep"] != 0
+    assert np.array_equal(kept[R.FILL_FIRST:], first["cand_removed"][R.FILL_FIRST:] != 0) and not kept[:R.FILL_FIRST].any()
+    second = R.run_scene(again, s)
+    assert not second["cand_removed"][kept].any()            # where the first call left a 1, the second call's answer is 0
+    print("first call removes", int(first["cand_removed"][R.FILL_FIRST:].sum()), "of", 300 - R.FILL_FIRST, "candidates behind position", R.FILL_FIRST,
+          "and", int(first["cand_removed"].sum()), "in all; the second", int(second["cand_removed"].sum()))

@@ -90,6 +90,32 @@ def test_scene_has_the_lengths_and_special_rows():
         assert not np.array_equal(out[k][prob["rows"]], sc["table"][k][prob["rows"]])
 
 
+@pytest.mark.parametrize("n_rows,longest_last", R.SCAN_CASES)
+def test_scan_scenes_put_the_special_lists_where_the_trips_of_the_descriptor_scan_meet(n_rows, longest_last):
+    # what tests/test_gpu_scan_trips.py relies on: equal neighbouring offsets across the first trip's end, and the longest list (which sizes
+    # the medoid pass) in the first trip for one order and in the last trip for the other, every other trip far below it
+    sc = R.make_scan_scene(n_rows, longest_last)
+    prob = sc["prob"]
+    assert len(prob["rows"]) == n_rows == len(set(prob["rows"].tolist())) and len(sc["kf_pose"]) == 42 and len(sc["table"]["pos"]) == 2600
+    n_obs, n_desc = np.diff(prob["obs_start"]), R.descriptor_counts(prob)
+    assert np.array_equal(prob["obs_desc"] == -1, prob["obs_kf"] >= 40)      # no descriptor: one of the two added slots, and only then
+    for a, b in zip(prob["obs_start"][:-1], prob["obs_start"][1:]):
+        assert (np.diff(prob["obs_kf"][a:b]) >= 0).all()                    # slot order, as device-built lists are
+    assert n_desc[R.SCAN_TRIP - 1] == 0 and n_desc[R.SCAN_TRIP - 2] > 0
+    if n_rows > R.SCAN_TRIP:
+        assert 0 < n_desc[R.SCAN_TRIP] < n_obs[R.SCAN_TRIP]
+    trips = [n_desc[a:a + R.SCAN_TRIP] for a in range(0, n_rows, R.SCAN_TRIP)]
+    assert len(trips) == {1024: 1, 1025: 2, 2100: 3}[n_rows]
+    at = len(trips) - 1 if longest_last else 0
+    assert sorted(trips[at])[-2:] == [256, 257] and all(t.max() <= 65 for i, t in enumerate(trips) if i != at)
+    print(n_rows, longest_last, "observations", int(prob["obs_start"][-1]), "descriptors per trip", [int(t.sum()) for t in trips], "longest per trip",
+          [int(t.max()) for t in trips])
+    _, med = R.refresh(sc["table"], sc["kf_pose"], sc["pool"], prob, sc["sf"])
+    where = np.flatnonzero(n_desc >= 256)
+    assert med[where].tolist() == [int(med[where[0]]), -2] and med[where[0]] >= 0 and med[R.SCAN_TRIP - 1] == -1
+    assert (med[n_desc > 0] != -1).all() and (med[R.SCAN_TRIP:] >= 0).sum() >= min(n_rows - R.SCAN_TRIP, 1)
+
+
 def test_lambda_zero_returns_the_pose_and_identity_changes_nothing():
     sc = R.make_loop_scene()
     T = R.loop_transforms()

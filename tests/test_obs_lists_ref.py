@@ -148,3 +148,13 @@ def test_scene_b_has_the_long_lists_and_two_scan_trips():
     assert s["kf_mp"].shape == (1100, 8) and all(out["n_obs_row"][r] == n for r, n in s["lengths"].items())
     assert out["n_obs_row"][6] == 1100 and out["n_obs_row"][5] == 1025
     assert -(-s["n_mp"] // 256) > 256                        # more block totals than one trip of the offsets scan takes
+
+
+def test_scene_c_has_more_long_lists_than_the_long_sort_has_workgroups():
+    s = R.scene_c()
+    out = R.run_scene(s, R.select(R.FROM_ROWS, rows_in=np.arange(s["n_mp"])))
+    assert s["kf_mp"].shape == (66, 1040) and all(out["n_obs_row"][r] == n for r, n in s["lengths"].items())
+    n_long = int((out["n_obs_row"] > 64).sum())              # the lists a wave does not sort on its own
+    assert n_long == 1030 > 1024 and out["n_obs_row"].max() == 65 and {0, 1} <= set(out["n_obs_row"].tolist())
+    a, b = out["obs_start"][7], out["obs_start"][8]          # a list is in id order, which is not slot order, and its keypoints are not in order either
+    assert (np.diff(s["kf_id"][out["obs_kf"][a:b]]) > 0).all() and (np.diff(out["obs_kf"][a:b]) < 0).any() and (np.diff(out["obs_kp"][a:b]) < 0).any()

@@ -126,6 +126,30 @@ def test_generator_draws_cover_every_status_and_stay_clear_of_level_boundaries()
     assert (seen > 50).all(), seen
 
 
+def test_large_draws_stay_clear_of_level_boundaries_and_keep_entries_on_both_sides_of_the_second_scan_trip():
+    for draw in R.large_draws():
+        seed, counts, modes, special = draw
+        sc = R.large_scene(draw)
+        n = sum(counts)
+        assert len(sc["table"]["pos"]) == 3000 and [len(v["indices"]) for v in sc["views"]] == counts and [v["mode"] for v in sc["views"]] == modes
+        print(seed, "near_level", int(sc["near_level"].sum()), "of", n)
+        assert len(sc["near_level"]) == n and sc["near_level"].sum() <= 1e-3 * n, (seed, int(sc["near_level"].sum()), n)
+        long_views = 0
+        for cnt, g in zip(counts, sc["ref"]):
+            if cnt <= R.LARGE_TRIP:
+                continue
+            long_views += 1
+            past = int((g["kept"] >= R.LARGE_TRIP).sum())
+            print(seed, "a view of", cnt, "keeps", len(g["kept"]), "entries,", past, "of them in the second trip")
+            assert len(g["kept"]) - past >= 1000             # the carry into the second trip is not zero ...
+            if cnt >= R.LARGE_TRIP + 300:                    # ... and is used: by at least 50 kept entries,
+                assert past >= 50
+            else:                                            # or, in a second trip of one entry, by that entry
+                assert cnt == R.LARGE_TRIP + 1 and past == 1 and g["kept"][-1] == R.LARGE_TRIP
+        assert long_views == 1
+    assert R.large_draws()[1][1][0] > 0                      # the second draw's long view does not start the block table
+
+
 def test_sequential_search_binds_each_keypoint_once():
     rng = np.random.default_rng(9)
     sc = R.make_views(rng, [120], [R.SEARCH], n_mp=120)
