@@ -16,10 +16,11 @@
 //   k_union_fill    mark[u][r] = kNone
 //   k_union_mark    one lane per (list entry, entry of its slot): atomicMin(mark[u][r], position in the problem's list)
 //   k_union_exclude the valid entries of the problem's exclude slot go back to kNone
-//   k_union_count / k_union_offsets / k_union_pack   the ballot-rank, per-workgroup count and offsets-scan pattern of project_gate.hip over
-//                   256-row blocks: the packed order is ascending row order
+//   k_union_count / k_union_offsets / k_union_pack   block_rank, per-workgroup count and block_offsets (ms_scan.h) over 256-row
+//                   blocks: the packed order is ascending row order
 // The only atomics are OR on bitmap words and MIN on owner words: no order of arrival decides anything.
 #include "ms_internal.h"
+#include "ms_scan.h"
 #include <algorithm>
 #include <cstring>
 
@@ -27,7 +28,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kQueryBatch = 64;                              // queries whose wave totals share one trip through LDS
-constexpr int32_t kNone = 0x7fffffff;
 
 struct QDev { int32_t slot, force_a, force_b, min_covis, require; };
 
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void k_covis_pick(const CovisArgs A) {
             is = k == Q.force_a || k == Q.force_b || (c >= 1 && c >= Q.min_covis);
         }
         const unsigned long long mask = __ballot(is);
-        if (is) out[base + __popcll(mask & ((1ull << lane) - 1ull))] = k;
+        if (is) out[base + lanes_before(mask)] = k;
         base += __popcll(mask);
     }
     if (lane == 0) A.n_neighbours[q] = base;
@@ -159,19 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_union_exclude(const UnionArgs A) {
 __device__ inline int union_rank(const UnionArgs &A, int32_t *s_wave, int u, int &r, int32_t &mark, int &total) {
     r = blockIdx.x * kBlock + (int)threadIdx.x;
     mark = r < A.n_mp ? A.mark[(size_t)u * A.n_mp + r] : kNone;
-    const unsigned long long mask = __ballot(mark != kNone);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        const int c = s_wave[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    return before + __popcll(mask & ((1ull << lane) - 1ull));
+    return block_rank<kBlock>(mark != kNone, s_wave, total);
 }
 
 __global__ __launch_bounds__(kBlock) void k_union_count(const UnionArgs A) {
@@ -183,27 +171,10 @@ __global__ __launch_bounds__(kBlock) void k_union_count(const UnionArgs A) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_union_offsets(const UnionArgs A) {
-    __shared__ int32_t s_scan[kBlock];
+    __shared__ int32_t s_wave[kBlock / 64];
     const int u = blockIdx.x;
-    const int32_t *cnt = A.blk_count + (size_t)u * A.n_blk;
-    int32_t *off = A.blk_off + (size_t)u * A.n_blk;
-    int carry = 0;
-    for (int b0 = 0; b0 < A.n_blk; b0 += kBlock) {
-        const int b = b0 + (int)threadIdx.x;
-        const int c = b < A.n_blk ? cnt[b] : 0;
-        s_scan[threadIdx.x] = c;
-        __syncthreads();
-        for (int d = 1; d < kBlock; d <<= 1) {               // inclusive scan
-            const int add = (int)threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_scan[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (b < A.n_blk) off[b] = carry + s_scan[threadIdx.x] - c;
-        carry += s_scan[kBlock - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) A.n_rows[u] = carry;
+    const int rows = block_offsets<kBlock>(A.blk_count + (size_t)u * A.n_blk, A.blk_off + (size_t)u * A.n_blk, A.n_blk, s_wave);
+    if (threadIdx.x == 0) A.n_rows[u] = rows;
 }
 
 __global__ __launch_bounds__(kBlock) void k_union_pack(const UnionArgs A) {
@@ -216,10 +187,6 @@ __global__ __launch_bounds__(kBlock) void k_union_pack(const UnionArgs A) {
     const size_t dst = (size_t)u * A.n_mp + (size_t)A.blk_off[(size_t)u * A.n_blk + blockIdx.x] + (size_t)rank;
     A.rows[dst] = r;
     if (A.owner) A.owner[dst] = mark;
-}
-
-bool over_capacity(int n_kf, int stride, int n_mp, int n) {
-    return n_kf > MS_COVIS_MAX_KF || stride > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || n > MS_COVIS_MAX_QUERIES;
 }
 
 }  // namespace
@@ -245,7 +212,7 @@ extern "C" int ms_covisibility(ms_ctx *c, const int32_t *kf_mp, int n_kf, int st
     if (!c) return MS_ERR_INVALID;
     int rc;
     if ((rc = ms_covisibility_check(kf_mp, n_kf, stride, mp_flags, n_mp, queries, n_q, neighbours, n_neighbours, c->err, sizeof(c->err)))) return rc;
-    if (over_capacity(n_kf, stride, n_mp, n_q))
+    if (ms_map_over_capacity(n_kf, stride, n_mp, n_q))
         return ms_fail(c, MS_ERR_CAPACITY, "covisibility: %d slots / stride %d / %d map points / %d queries, caps %d / %d / below %d / %d", n_kf, stride, n_mp, n_q,
                        MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_QUERIES);
     if (n_q == 0) return MS_OK;
@@ -320,7 +287,7 @@ extern "C" int ms_map_point_union(ms_ctx *c, const int32_t *kf_mp, int n_kf, int
     if ((rc = ms_map_point_union_check(kf_mp, n_kf, stride, mp_flags, n_mp, kf_list, n_list, problems, n_u, rows, n_rows, c->err, sizeof(c->err)))) return rc;
     long long n_entries = 0;
     for (int u = 0; u < n_u; ++u) n_entries += problems[u].count;
-    if (over_capacity(n_kf, stride, n_mp, n_u) || n_entries > MS_UNION_MAX_ENTRIES)
+    if (ms_map_over_capacity(n_kf, stride, n_mp, n_u) || n_entries > MS_UNION_MAX_ENTRIES)
         return ms_fail(c, MS_ERR_CAPACITY, "map point union: %d slots / stride %d / %d map points / %d problems / %lld list entries, caps %d / %d / below %d / %d / %d", n_kf,
                        stride, n_mp, n_u, n_entries, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_QUERIES, MS_UNION_MAX_ENTRIES);
     if (n_u == 0) return MS_OK;

@@ -18,13 +18,14 @@
 //                   decrements of their observation counts are parallel.  The decrements are agent-scope atomics and the counts of the next
 //                   candidate are read with agent-scope atomic loads behind a workgroup barrier (a plain load may be served from the CU's L1)
 //   k_cull_sweep    one lane per entry of the table: an entry whose row was removed becomes -1 (removeMapPoint's eraseObservation)
-//   k_cull_count / k_cull_offsets / k_cull_pack   the ballot-rank, per-workgroup count and offsets-scan pattern of project_gate.hip over
-//                   256-row blocks: removed_rows is in ascending row order
+//   k_cull_count / k_cull_offsets / k_cull_pack   block_rank, per-workgroup count and block_offsets (ms_scan.h) over 256-row
+//                   blocks: removed_rows is in ascending row order
 // Nothing here depends on which lane's atomic arrives first: the same input gives the same bits on every call.
 //
 // What stays with the host mirror (it derives them from cand_removed and the downloaded removed_rows): the previousKfId / nextKfId links, the
 // `uncertainty` accumulation, re-pointing referenceKeyframe, trackIdToMapPoint and bowIndex->remove.
 #include "ms_internal.h"
+#include "ms_scan.h"
 #include "map_cull_check.h"
 #include <algorithm>
 #include <cstring>
@@ -33,7 +34,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWalk = 1024;                                  // lanes of the one workgroup of k_cull_keyframes
-constexpr int32_t kNone = 0x7fffffff;
 
 struct CullArgs {
     int32_t *kf_mp;
@@ -159,19 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_cull_sweep(const CullArgs A) {
 __device__ inline int cull_rank(const CullArgs &A, int32_t *s_wave, int &r, uint8_t &why, int &total) {
     r = blockIdx.x * kBlock + (int)threadIdx.x;
     why = r < A.n_mp ? (uint8_t)(A.why1[r] | A.why3[r]) : (uint8_t)0;      // a row has at most one of the two
-    const unsigned long long mask = __ballot(why != 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        const int c = s_wave[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    return before + __popcll(mask & ((1ull << lane) - 1ull));
+    return block_rank<kBlock>(why != 0, s_wave, total);
 }
 
 __global__ __launch_bounds__(kBlock) void k_cull_count(const CullArgs A) {
@@ -183,24 +171,9 @@ __global__ __launch_bounds__(kBlock) void k_cull_count(const CullArgs A) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_cull_offsets(const CullArgs A) {
-    __shared__ int32_t s_scan[kBlock];
-    int carry = 0;
-    for (int b0 = 0; b0 < A.n_blk; b0 += kBlock) {
-        const int b = b0 + (int)threadIdx.x;
-        const int c = b < A.n_blk ? A.blk_count[b] : 0;
-        s_scan[threadIdx.x] = c;
-        __syncthreads();
-        for (int d = 1; d < kBlock; d <<= 1) {               // inclusive scan
-            const int add = (int)threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_scan[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (b < A.n_blk) A.blk_off[b] = carry + s_scan[threadIdx.x] - c;
-        carry += s_scan[kBlock - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) A.down[0] = carry;
+    __shared__ int32_t s_wave[kBlock / 64];
+    const int removed = block_offsets<kBlock>(A.blk_count, A.blk_off, A.n_blk, s_wave);
+    if (threadIdx.x == 0) A.down[0] = removed;
 }
 
 __global__ __launch_bounds__(kBlock) void k_cull_pack(const CullArgs A) {
@@ -214,19 +187,9 @@ __global__ __launch_bounds__(kBlock) void k_cull_pack(const CullArgs A) {
     if (A.removed_why) A.removed_why[dst] = why;
 }
 
-bool over_capacity(int n_kf, int stride, int n_mp, int n) {
-    return n_kf > MS_COVIS_MAX_KF || stride > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || n > MS_COVIS_MAX_QUERIES;
-}
-
 // the per-thread vectors of the validation (slots in KfId order, sorted candidates): they only grow
 std::vector<int32_t> &tl_order() { thread_local std::vector<int32_t> v; return v; }
 std::vector<int32_t> &tl_sorted() { thread_local std::vector<int32_t> v; return v; }
-
-// slot_rank / rank_slot of the upload block from the slots in KfId order
-void fill_ranks(const std::vector<int32_t> &order, int n_kf, int32_t *slot_rank, int32_t *rank_slot) {
-    for (int k = 0; k < n_kf; ++k) slot_rank[k] = -1;
-    for (size_t i = 0; i < order.size(); ++i) { slot_rank[order[i]] = (int32_t)i; rank_slot[i] = order[i]; }
-}
 
 }  // namespace
 
@@ -236,7 +199,7 @@ extern "C" int ms_observation_count(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
     int rc;
     std::vector<int32_t> &order = tl_order();
     if ((rc = ms_cull::check_table("observation count", kf_mp, n_kf, stride, n_mp, kf_id, order, c->err, sizeof(c->err)))) return rc;
-    if (over_capacity(n_kf, stride, n_mp, 0))
+    if (ms_map_over_capacity(n_kf, stride, n_mp, 0))
         return ms_fail(c, MS_ERR_CAPACITY, "observation count: %d slots / stride %d / %d map points, caps %d / %d / below %d", n_kf, stride, n_mp, MS_COVIS_MAX_KF,
                        MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP);
     if (n_mp == 0 || (!n_obs && !first_slot && !last_slot)) return MS_OK;
@@ -253,7 +216,7 @@ extern "C" int ms_observation_count(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
     if ((rc = ms_grow(c, W.host, W.host_bytes, up.end, true))) return rc;
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
-    fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
+    ms_cull::fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
     if (up.end) MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     CullArgs A{};
     A.kf_mp = const_cast<int32_t *>(kf_mp);                  // read only here
@@ -292,7 +255,7 @@ extern "C" int ms_map_cull(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint
     if ((rc = ms_map_cull_check(kf_mp, n_kf, stride, mp_flags, mp_live, n_mp, kf_id, kf_t, cand, cand_keep, n_cand, s, removed_rows, cand_removed, n_removed_rows, n_removed_kf,
                                 c->err, sizeof(c->err))))
         return rc;
-    if (over_capacity(n_kf, stride, n_mp, n_cand))
+    if (ms_map_over_capacity(n_kf, stride, n_mp, n_cand))
         return ms_fail(c, MS_ERR_CAPACITY, "map cull: %d slots / stride %d / %d map points / %d candidates, caps %d / %d / below %d / %d", n_kf, stride, n_mp, n_cand,
                        MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_QUERIES);
     if (n_mp == 0) {                                         // no entry can be valid: nMapPoints = 0 everywhere, and 0 < 0 * ratio never holds
@@ -321,7 +284,7 @@ extern "C" int ms_map_cull(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint
     if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
-    fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
+    ms_cull::fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
     l_t.fill(hs, kf_t);
     // :445: descending KfId; :453-464: the kept ones never reach the device
     int2 *walk = l_walk.at(hs);

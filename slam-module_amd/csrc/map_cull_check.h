@@ -33,6 +33,12 @@ inline bool slots_by_id(const int32_t *kf_id, int n_kf, std::vector<int32_t> &or
     return true;
 }
 
+// slot_rank / rank_slot of an upload block from the slots in KfId order
+inline void fill_ranks(const std::vector<int32_t> &order, int n_kf, int32_t *slot_rank, int32_t *rank_slot) {
+    for (int k = 0; k < n_kf; ++k) slot_rank[k] = -1;
+    for (size_t i = 0; i < order.size(); ++i) { slot_rank[order[i]] = (int32_t)i; rank_slot[i] = order[i]; }
+}
+
 inline int check_table(const char *who, const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *kf_id, std::vector<int32_t> &order, char *why, size_t bytes) {
     if (n_kf < 0 || n_mp < 0) return why_is(MS_ERR_INVALID, why, bytes, "%s: negative size (%d slots, %d map points)", who, n_kf, n_mp);
     if (stride < 1) return why_is(MS_ERR_INVALID, why, bytes, "%s: stride %d", who, stride);

@@ -26,6 +26,7 @@
 // reassociate).  Square roots and divisions are the correctly rounded ones (sqrt / sqrtf, operator/); acos and sin of the slerp are the device
 // library's and carry its error.  No atomics anywhere.  Everything a kernel indexes with is validated on the host first.
 #include "ms_internal.h"
+#include "ms_scan.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -127,36 +128,21 @@ __global__ __launch_bounds__(kBlock) void k_refresh_dcount(const int32_t *__rest
     dstart[r] = have;
 }
 
-// dstart[0 .. n_rows]: counts -> exclusive offsets, in place (one workgroup, kScan rows per trip); info = total, longest list
+// dstart[0 .. n_rows]: counts -> exclusive offsets, in place (one workgroup: block_offsets of ms_scan.h, kScan rows per trip); info = total,
+// longest list
 __global__ __launch_bounds__(kScan) void k_refresh_dscan(int32_t *__restrict__ dstart, int n_rows, int32_t *__restrict__ info) {
-    __shared__ int32_t s_sum[kScan / 64], s_max[kScan / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0, longest = 0;
-    for (int r0 = 0; r0 < n_rows; r0 += kScan) {
-        const int r = r0 + (int)threadIdx.x;
-        const int c = r < n_rows ? dstart[r] : 0;
-        int inc = c, mx = c;
+    __shared__ int32_t s_wave[kScan / 64], s_max[kScan / 64];
+    int longest = 0;                                         // of this thread's rows, then of its wave's
+    for (int r = threadIdx.x; r < n_rows; r += kScan) longest = max(longest, dstart[r]);
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-            mx = max(mx, __shfl_xor(mx, d));
-        }
-        if (lane == 63) { s_sum[wave] = inc; s_max[wave] = mx; }
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kScan / 64; ++w) {
-            const int x = s_sum[w];
-            if (w < wave) before += x;
-            total += x;
-            longest = max(longest, s_max[w]);
-        }
-        if (r < n_rows) dstart[r] = carry + before + inc - c;
-        carry += total;
-        __syncthreads();                                     // s_sum / s_max are written again in the next trip
+    for (int d = 1; d < 64; d <<= 1) longest = max(longest, __shfl_xor(longest, d));
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = longest;
+    __syncthreads();
+    const int total = block_offsets<kScan>(dstart, dstart, n_rows, s_wave);      // a thread overwrites only the counts it read above
+    if (threadIdx.x == 0) {
+        for (int w = 0; w < kScan / 64; ++w) longest = max(longest, s_max[w]);
+        dstart[n_rows] = total; info[0] = total; info[1] = longest;
     }
-    if (threadIdx.x == 0) { dstart[n_rows] = carry; info[0] = carry; info[1] = longest; }
 }
 
 __global__ __launch_bounds__(kBlock) void k_refresh_dpack(const int32_t *__restrict__ obs_start, const int32_t *__restrict__ obs_desc, int n_rows,

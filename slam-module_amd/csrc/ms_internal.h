@@ -142,3 +142,8 @@ struct MsRange {
 };
 
 inline int ms_div_up(int a, int b) { return (a + b - 1) / b; }
+
+// the sizes every entry point over the keyframe table kf_mp accepts; n = its queries, problems or candidates
+inline bool ms_map_over_capacity(int n_kf, int stride, int n_mp, int n) {
+    return n_kf > MS_COVIS_MAX_KF || stride > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || n > MS_COVIS_MAX_QUERIES;
+}

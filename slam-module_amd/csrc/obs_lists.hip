@@ -8,9 +8,9 @@
 //   k_ol_count     one lane per entry of every slot with kf_id >= 0: atomicAdd(n_obs[r]) -- the count kernel of map_cull.hip
 //   k_ol_mark      one lane per position of the selection (rows_in[i], or keypoint i of the slot): atomicMin(sel[r], i), so a row is kept
 //                  at its first occurrence whatever lane arrives first
-//   k_ol_blocks / k_ol_offsets / k_ol_pack   the ballot-rank, per-workgroup count and offsets-scan pattern of project_gate.hip over 256
-//                  positions per block, with a second column: the sum of the kept rows' list lengths, whose exclusive scan is obs_start.
-//                  The scan of the block totals is one workgroup that walks them 256 at a time with a carry
+//   k_ol_blocks / k_ol_offsets / k_ol_pack   block_rank, per-workgroup count and block_offsets (ms_scan.h) over 256 positions
+//                  per block, with a second column through block_exclusive: the sum of the kept rows' list lengths, whose exclusive scan
+//                  is obs_start.  k_ol_offsets scans the two columns of block totals one after the other
 //   k_ol_scatter   one lane per entry: the entry's (KfId position, j) key goes behind an atomic cursor into its row's segment
 //   k_ol_sort_short  a wave per kept row: segments of up to 64 keys are ranked inside the wave
 //   k_ol_sort_long   the longer ones (listed by k_ol_pack) a workgroup each: up to kLds keys are ranked through LDS, beyond that from global
@@ -20,6 +20,7 @@
 // every call and at any capacity.  Integer atomics only.  When the kept rows or their observations exceed the capacities, the totals are
 // still computed and nothing behind the block scan writes.
 #include "ms_internal.h"
+#include "ms_scan.h"
 #include "map_cull_check.h"
 #include <algorithm>
 #include <cstring>
@@ -30,7 +31,6 @@ constexpr int kBlock = 256;
 constexpr int kLds = 1024;                                   // keys a workgroup ranks through LDS
 constexpr int kLongGrid = 1024;                              // workgroups of k_ol_sort_long (they stride over the long rows)
 constexpr int kJBits = 13;                                   // key = position in KfId order << kJBits | j
-constexpr int32_t kNone = 0x7fffffff;
 static_assert(MS_COVIS_MAX_STRIDE <= (1 << kJBits) && MS_COVIS_MAX_KF <= (1 << (31 - kJBits)), "the sort key is one int32");
 constexpr int kMaxIn = 1 << 24;                              // entries of rows_in
 
@@ -93,25 +93,8 @@ __device__ inline bool list_rank(const ListArgs &A, int32_t (*s_wave)[kBlock / 6
             if (A.drop_empty && n == 0) kept = false;
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long mask = __ballot(kept);
-    int inc = kept ? n : 0;                                  // inclusive scan of the lengths inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) { s_wave[0][wave] = __popcll(mask); s_wave[1][wave] = inc; }
-    __syncthreads();
-    rank = __popcll(mask & ((1ull << lane) - 1ull));
-    obs_before = inc - (kept ? n : 0);
-    total_rows = 0; total_obs = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        const int cr = s_wave[0][w], co = s_wave[1][w];
-        if (w < wave) { rank += cr; obs_before += co; }
-        total_rows += cr; total_obs += co;
-    }
+    rank = block_rank<kBlock>(kept, s_wave[0], total_rows);                    // an LDS array each: no barrier separates the two
+    obs_before = block_exclusive<kBlock>(kept ? n : 0, s_wave[1], total_obs);
     return kept;
 }
 
@@ -124,24 +107,9 @@ __global__ __launch_bounds__(kBlock) void k_ol_blocks(const ListArgs A) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_ol_offsets(const ListArgs A) {
-    __shared__ int32_t s_rows[kBlock], s_obs[kBlock];
-    int carry_rows = 0, carry_obs = 0;
-    for (int b0 = 0; b0 < A.n_blk; b0 += kBlock) {
-        const int b = b0 + (int)threadIdx.x;
-        const int cr = b < A.n_blk ? A.blk_rows[b] : 0, co = b < A.n_blk ? A.blk_obs[b] : 0;
-        s_rows[threadIdx.x] = cr; s_obs[threadIdx.x] = co;
-        __syncthreads();
-        for (int d = 1; d < kBlock; d <<= 1) {               // inclusive scans
-            const bool on = (int)threadIdx.x >= d;
-            const int ar = on ? s_rows[threadIdx.x - d] : 0, ao = on ? s_obs[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_rows[threadIdx.x] += ar; s_obs[threadIdx.x] += ao;
-            __syncthreads();
-        }
-        if (b < A.n_blk) { A.off_rows[b] = carry_rows + s_rows[threadIdx.x] - cr; A.off_obs[b] = carry_obs + s_obs[threadIdx.x] - co; }
-        carry_rows += s_rows[kBlock - 1]; carry_obs += s_obs[kBlock - 1];
-        __syncthreads();
-    }
+    __shared__ int32_t s_wave[kBlock / 64];
+    const int carry_rows = block_offsets<kBlock>(A.blk_rows, A.off_rows, A.n_blk, s_wave);
+    const int carry_obs = block_offsets<kBlock>(A.blk_obs, A.off_obs, A.n_blk, s_wave);
     if (threadIdx.x == 0) {
         A.down[0] = carry_rows; A.down[1] = carry_obs;
         if (carry_rows <= A.cap_rows && carry_obs <= A.cap_obs) A.out.obs_start[carry_rows] = carry_obs;      // obs_start holds cap_rows + 1
@@ -303,7 +271,7 @@ extern "C" int ms_observation_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
                           order, c->err, sizeof(c->err))))
         return rc;
     const bool from_slot = sel->source == MS_OBS_FROM_SLOT;
-    if (n_kf > MS_COVIS_MAX_KF || stride > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || sel->n_in > kMaxIn)
+    if (ms_map_over_capacity(n_kf, stride, n_mp, 0) || sel->n_in > kMaxIn)
         return ms_fail(c, MS_ERR_CAPACITY, "observation lists: %d slots / stride %d / %d map points / %d rows_in, caps %d / %d / below %d / %d", n_kf, stride, n_mp,
                        sel->n_in, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, kMaxIn);
     const int n_pos = from_slot ? stride : sel->n_in;
@@ -333,9 +301,7 @@ extern "C" int ms_observation_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
     if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
-    int32_t *slot_rank = l_sr.at(hs), *rank_slot = l_rs.at(hs);
-    for (int k = 0; k < n_kf; ++k) slot_rank[k] = -1;
-    for (size_t i = 0; i < order.size(); ++i) { slot_rank[order[i]] = (int32_t)i; rank_slot[i] = order[i]; }
+    ms_cull::fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
     l_base.fill(hs, kf_desc_base);
     if (up.end) MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     ListArgs A{};

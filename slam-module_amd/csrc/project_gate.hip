@@ -9,8 +9,8 @@
 //
 //   k_gate          one lane per entry, 256-lane workgroups that never straddle two views (a block -> (view, first entry) table); the view
 //                   record is staged in LDS once per workgroup.  Writes the per-entry outputs, the lane's rank among the workgroup's kept
-//                   entries (ballot per wave, wave totals through LDS) and the workgroup's kept count.
-//   k_gate_offsets  one workgroup per view: exclusive scan of the view's workgroup counts -> each workgroup's offset in the view's slice, n_kept.
+//                   entries (block_rank of ms_scan.h) and the workgroup's kept count.
+//   k_gate_offsets  one workgroup per view: block_offsets of the view's workgroup counts -> each workgroup's offset in the view's slice, n_kept.
 //   k_gate_pack     one lane per entry again: a kept entry writes its query to slice position offset + rank and gathers its descriptor.
 //
 // Ranks and offsets are prefix sums in entry order, so the packed order is the walk order of the reference's loops and no atomic decides anything.
@@ -18,6 +18,7 @@
 // whose order matters; the float square root is sqrtf, which hipcc rounds correctly by default -- __fsqrt_rn is the native approximation here);
 // logf is the one function whose last bit is the implementation's (near_level).
 #include "ms_internal.h"
+#include "ms_scan.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -135,21 +136,11 @@ __global__ __launch_bounds__(kBlock) void k_gate(const GateArgs A) {
     }
     // rank among the workgroup's kept entries, in entry order
     const bool kept = live && status == 0;
-    const unsigned long long mask = __ballot(kept);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int in_wave = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        const int c = s_wave[w];
-        if (w < wave) before += c;
-        total += c;
-    }
+    int total;
+    const int rank = block_rank<kBlock>(kept, s_wave, total);
     if (threadIdx.x == 0) A.blk_count[blockIdx.x] = total;
     if (live) {
-        A.rank[e] = kept ? before + in_wave : -1;
+        A.rank[e] = kept ? rank : -1;
         if (A.status) A.status[e] = status;
         A.x[e] = xf; A.y[e] = yf; A.radius[e] = radius; A.level[e] = level;
         if (A.dist) A.dist[e] = dist;
@@ -157,26 +148,11 @@ __global__ __launch_bounds__(kBlock) void k_gate(const GateArgs A) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_gate_offsets(const GateArgs A) {
-    __shared__ int32_t s_scan[kBlock];
+    __shared__ int32_t s_wave[kBlock / 64];
     const int v = blockIdx.x;
     const int blk0 = A.views[v].blk0, nblk = A.views[v].nblk;
-    int carry = 0;
-    for (int b0 = 0; b0 < nblk; b0 += kBlock) {
-        const int b = b0 + (int)threadIdx.x;
-        const int c = b < nblk ? A.blk_count[blk0 + b] : 0;
-        s_scan[threadIdx.x] = c;
-        __syncthreads();
-        for (int d = 1; d < kBlock; d <<= 1) {               // inclusive scan
-            const int add = (int)threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_scan[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (b < nblk) A.blk_off[blk0 + b] = carry + s_scan[threadIdx.x] - c;
-        carry += s_scan[kBlock - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) A.n_kept[v] = carry;
+    const int kept = block_offsets<kBlock>(A.blk_count + blk0, A.blk_off + blk0, nblk, s_wave);
+    if (threadIdx.x == 0) A.n_kept[v] = kept;
 }
 
 __global__ __launch_bounds__(kBlock) void k_gate_pack(const GateArgs A) {
