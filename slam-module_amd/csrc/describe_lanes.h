@@ -62,14 +62,16 @@ inline uint32_t disc_mask(int lane, int t, const int *u_max) {
 //     m10 = sum_t dot4(d[t], u + 15) - 15 T                                   (non-negative byte weights 4 (lane & 7) + b)
 //     m01 = sum_t (v_0 + 8 t) S_t = (v_0 + 24) T - 8 (P_0 + P_1 + P_2)        (sum_t t S_t = 3 T - P_0 - P_1 - P_2)
 // All of it is exact integer arithmetic far inside 32 bits (T <= 1024 * 255), so the wave's totals are the reference's.
-constexpr uint32_t moment_col_weights(int lane) { return 0x03020100u + 0x04040404u * (uint32_t)(lane & 7); }
+constexpr uint32_t moment_col_weights(int lane) { return 0x03020100u + 0x04040404u * (uint32_t)(lane & 7); }   // (the one full 32-bit multiply k_describe keeps: its constant has 27 bits, and shift-ors in its place are folded back into it)
 constexpr int moment_row_bias(int lane) { return (lane >> 3) - kHalfPatch + 24; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ uint32_t sad_u8(uint32_t a, uint32_t acc) { return __builtin_amdgcn_sad_u8(a, 0u, acc); }
 __device__ __forceinline__ uint32_t dot4_u8(uint32_t a, uint32_t w, uint32_t acc) { return __builtin_amdgcn_udot4(a, w, acc, false); }
+__device__ __forceinline__ int mul_small(int a, int b) { return __mul24(a, b); }          // both factors far below 2^23: v_mul_i32_i24, full rate
 #define DESCRIBE_LANES_FN __device__ __forceinline__
 #else
+inline int mul_small(int a, int b) { return a * b; }
 inline uint32_t sad_u8(uint32_t a, uint32_t acc) { return acc + (a & 255u) + ((a >> 8) & 255u) + ((a >> 16) & 255u) + (a >> 24); }
 inline uint32_t dot4_u8(uint32_t a, uint32_t w, uint32_t acc) {
     for (int b = 0; b < 4; ++b) acc += ((a >> (8 * b)) & 255u) * ((w >> (8 * b)) & 255u);
@@ -82,7 +84,7 @@ DESCRIBE_LANES_FN void lane_moments(const uint32_t (&d)[4], uint32_t col_weights
     const uint32_t p0 = sad_u8(d[0], 0u), p1 = sad_u8(d[1], p0), p2 = sad_u8(d[2], p1), T = sad_u8(d[3], p2);
     const uint32_t D = dot4_u8(d[3], col_weights, dot4_u8(d[2], col_weights, dot4_u8(d[1], col_weights, dot4_u8(d[0], col_weights, 0u))));
     m10 = (int)D - kHalfPatch * (int)T;
-    m01 = row_bias * (int)T - 8 * (int)(p0 + p1 + p2);
+    m01 = mul_small(row_bias, (int)T) - 8 * (int)(p0 + p1 + p2);        // row_bias 9 .. 16, T <= 16 * 255
 }
 #undef DESCRIBE_LANES_FN
 

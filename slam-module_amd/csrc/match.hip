@@ -129,8 +129,13 @@ __device__ __forceinline__ void best2_push(uint32_t &best, uint32_t &second, uin
 }
 __device__ __forceinline__ v8i_t hm_operand(v4i_t v) { return v8i_t{v[0], v[1], v[2], v[3], 0, 0, 0, 0}; }     // FP4 operands are the low four of the builtin's eight dwords
 
+// KEY32 (sets of at most kHmKeyMaxRows targets; the host picks it at the launch): best / second are kept per column tile on the accumulator registers'
+// own bit patterns (hamming_fp4.h: B scale 2^13, ageing by 32 per tile): 4 subtracts and 16 x (v_min3_u32, v_med3_u32, v_min_u32) per tile, no
+// v_perm and no per-tile merge.  Larger sets keep the packed 16-bit keys, whose index field has the ABI's 20 bits.
+template <bool KEY32>
 __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t s_a[kHmStage * 32];
+    constexpr int kScaleB = (int)(KEY32 ? kHm4ScaleBKey : kHm4ScaleB);
     const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 31, h = lane >> 5;
     const int qs = A.pair_q ? A.pair_q[p] : p, ts = A.pair_t ? A.pair_t[p] : p;
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
     uint32_t best[2] = {kNone, kNone}, second[2] = {kNone, kNone};
     v16f_t tag;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tag[r] = 8388608.0f + 4096.0f + (float)r;
+    for (int r = 0; r < 16; ++r) tag[r] = KEY32 ? hm_key_start(r, h) : 8388608.0f + 4096.0f + (float)r;
     for (int base = 0; base < nt; base += kHmStage) {
         __syncthreads();
 #pragma unroll
@@ -190,11 +195,26 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
             __builtin_amdgcn_sched_barrier(0);                        // keep the reads ahead of the chain (the scheduler would re-serialise them to save registers)
 #pragma unroll
             for (int s = 0; s < kHm4Steps; ++s) {  // the chain starts from the row tags (2^23 + 4096 + register index), so no add follows it
-                acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hm_operand(a[s]), hm_operand(bq[0][s]), s == 0 ? tag : acc[0], 4, 4, 0, (int)kHm4ScaleA, 0, (int)kHm4ScaleB);
-                acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hm_operand(a[s]), hm_operand(bq[1][s]), s == 0 ? tag : acc[1], 4, 4, 0, (int)kHm4ScaleA, 0, (int)kHm4ScaleB);
+                acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hm_operand(a[s]), hm_operand(bq[0][s]), s == 0 ? tag : acc[0], 4, 4, 0, (int)kHm4ScaleA, 0, kScaleB);
+                acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hm_operand(a[s]), hm_operand(bq[1][s]), s == 0 ? tag : acc[1], 4, 4, 0, (int)kHm4ScaleA, 0, kScaleB);
             }
             const int row0 = base + m * 32 + 4 * h;                   // this lane's rows: row0 + (reg & 3) + 8 * (reg >> 2)
-            if (base + m * 32 + 32 <= nt) {                           // full tile (uniform)
+            if constexpr (KEY32) {
+                hm_key_age(best[0], second[0]); hm_key_age(best[1], second[1]);
+                if (base + m * 32 + 32 <= nt) {                       // full tile (uniform): the registers are the keys
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+#pragma unroll
+                        for (int r = 0; r < 16; r += 2) hm_key_push2(best[n], second[n], __float_as_uint(acc[n][r]), __float_as_uint(acc[n][r + 1]));
+                } else {                                              // last tile of the set: rows beyond nt do not exist
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+#pragma unroll
+                        for (int r = 0; r < 16; r += 2)
+                            hm_key_push2(best[n], second[n], row0 + hm_key_row_in_tile(r, 0) < nt ? __float_as_uint(acc[n][r]) : kNone,
+                                         row0 + hm_key_row_in_tile(r + 1, 0) < nt ? __float_as_uint(acc[n][r + 1]) : kNone);
+                }
+            } else if (base + m * 32 + 32 <= nt) {                           // full tile (uniform)
                 // both column tiles at once on packed 16-bit lanes: key16 = (dot + 256) * 16 + register index (< 2^14), the low half of the float's
                 // bit pattern; the register index orders a lane's rows, so the packed minimum is the lowest row among equal distances
                 us2_t lb = {0xFFFF, 0xFFFF}, ls = {0xFFFF, 0xFFFF};
@@ -233,9 +253,16 @@ __global__ __launch_bounds__(256) void k_hamming_mfma(HamArgs A) {
         if (h == 0 && qi < A.q_stride) {
             const uint64_t o = (uint64_t)p * A.q_stride + qi;
             const bool live = qi < nq;
-            A.best_idx[o] = (!live || b == kNone) ? -1 : (int32_t)(b & 0xFFFFFu);
-            A.best_dist[o] = (!live || b == kNone) ? (uint16_t)MS_HAMMING_MAX : (uint16_t)((int)(b >> 20) - 256 + popq[n]);
-            A.second_dist[o] = (!live || s2 == kNone) ? (uint16_t)MS_HAMMING_MAX : (uint16_t)((int)(s2 >> 20) - 256 + popq[n]);
+            if constexpr (KEY32) {                                    // an empty slot is recognised by its range (ageing has moved it off 0xFFFFFFFF)
+                const bool nb = !live || hm_key_empty(b), ns = !live || hm_key_empty(s2);
+                A.best_idx[o] = nb ? -1 : (int32_t)hm_key_row(b, (nt + 31) >> 5);
+                A.best_dist[o] = nb ? (uint16_t)MS_HAMMING_MAX : (uint16_t)(hm_key_dot256(b) - 256 + popq[n]);
+                A.second_dist[o] = ns ? (uint16_t)MS_HAMMING_MAX : (uint16_t)(hm_key_dot256(s2) - 256 + popq[n]);
+            } else {
+                A.best_idx[o] = (!live || b == kNone) ? -1 : (int32_t)(b & 0xFFFFFu);
+                A.best_dist[o] = (!live || b == kNone) ? (uint16_t)MS_HAMMING_MAX : (uint16_t)((int)(b >> 20) - 256 + popq[n]);
+                A.second_dist[o] = (!live || s2 == kNone) ? (uint16_t)MS_HAMMING_MAX : (uint16_t)((int)(s2 >> 20) - 256 + popq[n]);
+            }
         }
     }
 }
@@ -999,7 +1026,8 @@ static int launch_hamming(ms_ctx *c, const HamArgs &A, int n_pairs) {
     dim3 grid(ms_div_up(A.q_stride, 256), n_pairs);
     if (A.qb || A.tv) hipLaunchKernelGGL(k_hamming_best2<true>, grid, dim3(256), 0, c->stream, A);
     else if (c->hamming_path == 1) hipLaunchKernelGGL(k_hamming_best2<false>, grid, dim3(256), 0, c->stream, A);
-    else hipLaunchKernelGGL(k_hamming_mfma, grid, dim3(256), 0, c->stream, A);
+    else if (A.nt <= kHmKeyMaxRows) hipLaunchKernelGGL(k_hamming_mfma<true>, grid, dim3(256), 0, c->stream, A);   // rows of a set the 32-bit keys' ageing can hold
+    else hipLaunchKernelGGL(k_hamming_mfma<false>, grid, dim3(256), 0, c->stream, A);
     MS_KERNEL_CHECK(c, "k_hamming_best2");
     return MS_OK;
 }

@@ -20,6 +20,7 @@
 #include "ms_internal.h"
 #include "fast_tiles.h"
 #include "describe_lanes.h"
+#include "describe_steer.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -999,42 +1000,7 @@ __global__ __launch_bounds__(64) void k_tracks(const PyrGeom *g, const float *__
 //   descriptor (orb_extractor.cpp:284-352): lane j evaluates BRIEF tests j, j+64, j+128, j+192 on the
 //   BLURRED level; four 64-bit ballots are the 256 descriptor bits (test t -> word t/32, bit t%32).
 
-__device__ __forceinline__ float dev_fast_atan2(float y, float x) {   // cv::fastAtan2 (atan_f32), degrees
-    const float p1 = 0.9997878412794807f * (float)(180 / 3.1415926535897932384626433832795);
-    const float p3 = -0.3258083974640975f * (float)(180 / 3.1415926535897932384626433832795);
-    const float p5 = 0.1555786518463281f * (float)(180 / 3.1415926535897932384626433832795);
-    const float p7 = -0.04432655554792128f * (float)(180 / 3.1415926535897932384626433832795);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, __fadd_rn(ax, (float)DBL_EPSILON));
-        c2 = __fmul_rn(c, c);
-        a = __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c);
-    } else {
-        c = __fdiv_rn(ax, __fadd_rn(ay, (float)DBL_EPSILON));
-        c2 = __fmul_rn(c, c);
-        a = __fsub_rn(90.f, __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c));
-    }
-    if (x < 0) a = __fsub_rn(180.f, a);
-    if (y < 0) a = __fsub_rn(360.f, a);
-    return a;
-}
-
-__device__ __forceinline__ float dev_poly_cos(float v) {   // openvslam/trigonometric.h:17-24
-    const float c1 = 0.99940307f, c2 = -0.49558072f, c3 = 0.03679168f;
-    const float v2 = __fmul_rn(v, v);
-    return __fadd_rn(c1, __fmul_rn(v2, __fadd_rn(c2, __fmul_rn(c3, v2))));
-}
-__device__ __forceinline__ float dev_cos(float v) {        // openvslam/trigonometric.h:26-42
-    const float PI = 3.14159265358979f, PI_2 = PI / 2.0f, TWO_PI = 2.0f * PI, INV_TWO_PI = 1.0f / TWO_PI, THREE_PI_2 = 3.0f * PI_2;
-    v = __fsub_rn(v, __fmul_rn((float)(int)floorf(__fmul_rn(v, INV_TWO_PI)), TWO_PI));
-    v = (0.0f < v) ? v : -v;
-    if (v < PI_2) return dev_poly_cos(v);
-    else if (v < PI) return -dev_poly_cos(__fsub_rn(PI, v));
-    else if (v < THREE_PI_2) return -dev_poly_cos(__fsub_rn(v, PI));
-    else return dev_poly_cos(__fsub_rn(TWO_PI, v));
-}
-__device__ __forceinline__ float dev_sin(float v) { return dev_cos(__fsub_rn(3.14159265358979f / 2.0f, v)); }
+// moments -> angle -> (cos, sin): describe_steer.h (plain C++, checked on the CPU by tests/describe_steer_check.cpp)
 
 __device__ __forceinline__ int wave_sum(int v) {      // DPP inclusive scan, total broadcast from lane 63
     return __builtin_amdgcn_readlane(wave_scan_add(v), 63);
@@ -1238,12 +1204,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     float angle_deg[kDescPerWave], ca[kDescPerWave], sa[kDescPerWave];
 #pragma unroll
     for (int k = 0; k < kDescPerWave; ++k) {
-        angle_deg[k] = dev_fast_atan2((float)m01[k], (float)m10[k]);
-        // float(angleDeg * M_PI / 180.0) in double (orb_extractor.cpp:286).  One multiplication by the double M_PI / 180.0 gives the same
-        // float for EVERY float in [0, 361] (checked exhaustively, tests/test_oracle_frontend.py::test_degree_to_radian_constant_is_exact),
-        // and it replaces a software double division per keypoint.
-        const float angle = (float)__dmul_rn((double)angle_deg[k], M_PI / 180.0);
-        ca[k] = dev_cos(angle); sa[k] = dev_sin(angle);
+        angle_deg[k] = describe_steer::fast_atan2((float)m01[k], (float)m10[k]);
+        const float angle = describe_steer::deg_to_rad(angle_deg[k]);
+        // sin(v) is cos(pi / 2 - v): lane 1 evaluates the shifted argument while lane 0 evaluates v, one cos_approx for both; every lane reads the two
+        // results back as scalars
+        const float cs = describe_steer::cos_approx(lane == 1 ? describe_steer::sin_argument(angle) : angle);
+        ca[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 0));
+        sa[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 1));
     }
     // O2: steered BRIEF on the blurred patch; the lane's point pairs are shared by the wave's keypoints
     unsigned long long bits[kDescPerWave][4];
@@ -1258,7 +1225,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const int c1 = __float2int_rn(__fsub_rn(__fmul_rn(x1, ca[k]), __fmul_rn(y1, sa[k])));
             const int r2 = __float2int_rn(__fadd_rn(__fmul_rn(x2, sa[k]), __fmul_rn(y2, ca[k])));
             const int c2 = __float2int_rn(__fsub_rn(__fmul_rn(x2, ca[k]), __fmul_rn(y2, sa[k])));
-            bits[k][q] = __ballot(pb[(r1 + kPatchRadius) * 40 + (c1 + kPatchRadius)] < pb[(r2 + kPatchRadius) * 40 + (c2 + kPatchRadius)]);
+            // rows and columns + 19 lie in 0 .. 38 (the pattern stays inside the 39 x 39 patch under every rotation): 24-bit multiply-adds, not full 32-bit multiplies
+            const uint32_t i1 = __umul24((uint32_t)(r1 + kPatchRadius), 40u) + (uint32_t)(c1 + kPatchRadius), i2 = __umul24((uint32_t)(r2 + kPatchRadius), 40u) + (uint32_t)(c2 + kPatchRadius);
+            bits[k][q] = __ballot(pb[i1] < pb[i2]);
         }
     }
 #pragma unroll

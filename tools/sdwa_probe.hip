@@ -49,6 +49,23 @@ DEF(k_seq_sdwa_mul_s,  "v_dot2_u32_u16 %0, %0, %1, 0\n v_mul_u32_u24_sdwa %0, %0
 DEF(k_seq_mul_s,       "v_dot2_u32_u16 %0, %0, %1, 0\n v_mul_u32_u24_e32 %0, s4, %0")
 DEF(k_seq_add_sdwa,    "v_add_u32_e32 %0, %0, %1\n v_add_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1")
 DEF(k_seq_add_add,     "v_add_u32_e32 %0, %0, %1\n v_add_u32_e32 %0, %0, %1")
+// the matcher's key update and k_describe's BRIEF rotation: v_med3_u32 beside v_min3_u32 / v_min_u32, and the packed float multiply (a register pair per
+// operand) beside the two plain multiplies it replaces
+DEF(k_med3,       "v_med3_u32 %0, %0, %1, %1")
+DEF(k_min_u32,    "v_min_u32_e32 %0, %0, %1")
+DEF(k_seq_mul_f32_x2,  "v_mul_f32_e32 %0, %0, %1\n v_mul_f32_e32 %0, %1, %0")
+__global__ __launch_bounds__(256) void k_pk_mul_f32(uint32_t *out, int n, long long *cyc) {
+    uint64_t v[CHAINS], b = (uint64_t)(threadIdx.x * 2654435761u | 1u) * 0x100000001ull;
+    for (int k = 0; k < CHAINS; ++k) v[k] = (uint64_t)(threadIdx.x + k * 977u) * 0x100000001ull;
+    const long long t0 = clock64();
+    for (int i = 0; i < n; ++i) {
+        _Pragma("unroll") for (int k = 0; k < CHAINS; ++k) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(v[k]) : "v"(b));
+    }
+    const long long t1 = clock64();
+    uint64_t s = 0; for (int k = 0; k < CHAINS; ++k) s ^= v[k];
+    out[blockIdx.x * 256 + threadIdx.x] = (uint32_t)(s ^ (s >> 32));
+    if (threadIdx.x == 0 && blockIdx.x == 0) cyc[0] = t1 - t0;
+}
 template <class K> void run(const char *name, K kern, uint32_t *d_out, long long *d_cyc) {
     const int n = 20000;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
@@ -63,8 +80,12 @@ int main() {
     uint32_t *d_out; long long *d_cyc; hipMalloc(&d_out, 1024 * 256 * 4); hipMalloc(&d_cyc, 8);
 #define R(k) run(#k, k, d_out, d_cyc)
     R(k_add); R(k_add_sdwa); R(k_add_sdwa_b); R(k_mul24); R(k_mul24_sdwa); R(k_lshr); R(k_perm); R(k_dot2); R(k_mad24); R(k_alignbyte); R(k_lshl_add); R(k_add3);
-    R(k_pk_add); R(k_pk_mad); R(k_bfe); R(k_mul_lo); R(k_mul_hi24); R(k_min3); R(k_and_or); R(k_cndmask); R(k_mov_dpp); R(k_add_dpp); R(k_sad); R(k_pk_min); R(k_pk_max_i); R(k_pk_sub_sat);
+    R(k_pk_add); R(k_pk_mad); R(k_bfe); R(k_mul_lo); R(k_mul_hi24); R(k_min3); R(k_and_or); R(k_cndmask); R(k_mov_dpp); R(k_add_dpp); R(k_sad); R(k_pk_min); R(k_pk_max_i); R(k_pk_sub_sat); R(k_med3); R(k_min_u32);
     std::printf("two- and three-instruction sequences (per SEQUENCE):\n");
+    R(k_seq_mul_f32_x2);
+    std::printf("one packed instruction (two products):\n");
+    R(k_pk_mul_f32);
+    std::printf("integer sequences (per SEQUENCE):\n");
     R(k_seq_shift_mul); R(k_seq_sdwa_mul); R(k_seq_sdwa_mul_s); R(k_seq_mul_s); R(k_seq_add_sdwa); R(k_seq_add_add);
     return 0;
 }
