@@ -878,6 +878,90 @@ int ms_map_refresh_lists(ms_ctx *ctx,
     /* HOST [n_rows] or NULL */
     int32_t *medoid);
 
+/* ---- matchTrackedFeatures on the device map tables -----------------------------------------------------------------------
+ * ms_match_tracked: the walk of mapper_helpers.cpp:76-141 over the keypoints of the current frame, whose keyframe slot is frame->slot.
+ * The tables are those of 9.6 / 9.8 / 9.9 (kf_mp, mp_flags, mp_live, the map-point table, the keypoint table, desc_pool).  New:
+ *   mp_track  (DEVICE int32 [n_mp])     MapPoint::trackId, -1 for none
+ *   track_row (DEVICE int32 [n_track])  trackIdToMapPoint as a window: entry t - frame->track_base = the row of track t, -1 for absent
+ *   kp_track  (HOST int32 [n_kp])       keyPointToTrackId, negative for none; n_kp <= stride
+ *   new_rows  (HOST int32 [n_new])      the rows offered to new map points: the k-th created point in keypoint order takes new_rows[k]
+ * A track t is PRESENT iff r = track_row[t - track_base] has (uint32)r < n_mp, mp_live[r] != 0 and mp_track[r] == t: a row that
+ * ms_map_cull removed or that was given to another point counts as erased (trackIdToMapPoint.erase, mapdb.cpp:166-173) without anybody
+ * touching track_row.  outcome (DEVICE uint8 [n_kp]), decided in the reference's order:
+ *   0 no track | 1 created (:126-139: absent and desc_base >= 0) | 2 just tracked (:85-90: present and (mp_flags[r] & 1) == 0) |
+ *   3 bound after isInFrustum and checkReprojectionError (:96-116) | 4 outside the frustum | 5 reprojection error |
+ *   6 absent and the frame has no descriptors (nothing happens)
+ * The gates are the SEARCH gates of 9.4 (statuses 1, 2, 4; view_cos_limit) and checkReprojectionError of 9.7, bit for bit.
+ * Written: outcomes 2 and 3: kf_mp[slot * stride + j] = r.  Outcome 1 with r = new_rows[k]: that entry, mp_live[r] = 1, mp_flags[r] = 0,
+ * mp_track[r] = t, track_row[t - track_base] = r, mp_desc[r] = desc_pool[desc_base + j] (updateDescriptor of one observation); mp_pos and
+ * the rest of the row are left alone.  Packed in keypoint order (DEVICE, each may be NULL): created_rows / created_kp [n_new],
+ * tracked_rows (outcome 2) and checked_rows (outcome 3) [n_kp].  counts (HOST [5]): created, just tracked, checked, frustum failures,
+ * reprojection failures -- the reference's debug counters.
+ * One launch: ONE workgroup of 256 lanes walks the keypoints in trips of 256 and decides and counts everything (phase A, which writes
+ * nothing but `outcome`); behind a barrier it writes the tables and the lists (phase B), unless phase A counted a violation:
+ * MS_ERR_INVALID with the tables untouched for a bound keypoint (outcome 1, 2, 3) whose kf_mp entry is already valid (keyframe.cpp:275), a
+ * used new_rows entry that is live, the octave of a keypoint with a track outside [0, n_levels).  (Two keypoints cannot resolve to one
+ * row: present tracks have mp_track[r] == t and kp_track holds an id once.)  MS_ERR_CAPACITY when the frame creates more than n_new
+ * points: nothing but `outcome` is written and counts[0] is the needed number, so the caller can call again.
+ * Synchronous: one upload, one download; the workspace belongs to the context and only grows.
+ * MS_ERR_INVALID, with nothing written and before any device call: slot outside [0, n_kf); a track id listed twice or outside
+ * [track_base, track_base + n_track); new_rows out of range or listed twice; n_kp > stride; level_sigma_sq, rel_reprojection_threshold or
+ * view_cos_limit not finite; n_levels outside [1, MS_TRI_MAX_LEVELS]; a camera ms_triangulate_check rejects; desc_base >= 0 with
+ * desc_base + n_kp > n_pool; descriptor arrays not 16-byte aligned; stride < 1; a negative size; a missing array.  MS_ERR_CAPACITY beyond
+ * the MS_COVIS_MAX_* caps and MS_TRACKED_MAX_WINDOW.  n_kp = 0 is fine.
+ *
+ * ms_match_tracked_finish: after ms_observation_lists (MS_OBS_FROM_ROWS over tracked_rows) and ms_triangulate_lists (MS_TRI_FIRST_LAST)
+ * on those lists.  (a) For every listed row with mp_flags == 2 (UNSURE: exactly two observations, :810) the updateDescriptor of :811:
+ * mp_desc[row] = the descriptor of the FIRST observation with obs_desc != -1, nothing when there is none -- the reference's median rule
+ * (map_point.cpp:101-113) reads index (unsigned)(0.5 * (n - 1)) = 0 of each descriptor's sorted distances, which is 0 for both, and keeps
+ * the first under a strict `<`.  Skipped when desc_pool or lists->obs_desc is NULL.  (b) refresh_rows (DEVICE [cap_refresh]) = the listed
+ * rows with mp_flags & 1 in list order, then, when append_checked != 0, checked_rows [n_checked]; n_refresh (HOST) = their number.
+ * One launch in the same trip shape; one download.  MS_ERR_CAPACITY when cap_refresh < n_rows + the appended rows or a count exceeds
+ * MS_COVIS_MAX_STRIDE.  The *_check twins are the validation alone (no context, no device; `why` receives the message). */
+#define MS_TRACKED_MAX_WINDOW (1 << 24)         /* n_track */
+typedef struct {
+    int32_t slot;                        /* the current frame's keyframe slot */
+    double pose[12];                     /* rows 0-2 of its poseCW, row-major */
+    ms_pinhole cam;
+    int32_t focal;                       /* getFocalLength */
+    int32_t desc_base;                   /* index of keypoint 0 in desc_pool; negative: !hasFeatureDescriptors() */
+    int32_t track_base;                  /* the track id of track_row[0] */
+    const float *level_sigma_sq;         /* HOST [n_levels] */
+    int32_t n_levels;
+    float rel_reprojection_threshold;    /* relativeReprojectionErrorThreshold */
+    float view_cos_limit;                /* isInFrustum's viewAngleLimitCos: 0.5 in the reference */
+} ms_tracked_frame;
+int ms_match_tracked(ms_ctx *ctx,
+    /* DEVICE tables, updated in place */
+    int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live,
+    const double *mp_pos, const float *mp_norm, const float *mp_min_dist, const float *mp_max_dist, uint32_t *mp_desc, int32_t *mp_track, int n_mp,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const uint32_t *desc_pool, int n_pool,
+    int32_t *track_row, int n_track,
+    /* HOST */
+    const ms_tracked_frame *frame, const int32_t *kp_track, int n_kp, const int32_t *new_rows, int n_new,
+    /* DEVICE; all but outcome may be NULL */
+    uint8_t *outcome, int32_t *created_rows, int32_t *created_kp, int32_t *tracked_rows, int32_t *checked_rows,
+    /* HOST [5] */
+    int32_t *counts);
+int ms_match_tracked_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live,
+    const double *mp_pos, const float *mp_norm, const float *mp_min_dist, const float *mp_max_dist, const uint32_t *mp_desc, const int32_t *mp_track, int n_mp,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const uint32_t *desc_pool, int n_pool,
+    const int32_t *track_row, int n_track,
+    const ms_tracked_frame *frame, const int32_t *kp_track, int n_kp, const int32_t *new_rows, int n_new,
+    const uint8_t *outcome, const int32_t *counts, char *why, size_t why_bytes);
+int ms_match_tracked_finish(ms_ctx *ctx,
+    /* HOST struct of DEVICE pointers (rows, obs_start, obs_desc are read), the count ms_observation_lists returned */
+    const ms_obs_lists *lists, int n_rows,
+    /* DEVICE */
+    const uint8_t *mp_flags, const uint32_t *desc_pool, uint32_t *mp_desc, int n_mp,
+    const int32_t *checked_rows, int n_checked, int append_checked,
+    int32_t *refresh_rows, int cap_refresh,
+    /* HOST */
+    int32_t *n_refresh);
+int ms_match_tracked_finish_check(const ms_obs_lists *lists, int n_rows, const uint8_t *mp_flags, const uint32_t *desc_pool, const uint32_t *mp_desc,
+    int n_mp, const int32_t *checked_rows, int n_checked, int append_checked, const int32_t *refresh_rows, int cap_refresh,
+    const int32_t *n_refresh, char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

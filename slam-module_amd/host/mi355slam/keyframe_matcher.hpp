@@ -1061,6 +1061,172 @@ inline TriangulateResult retriangulateCurrent(Context &ctx, DeviceObservationLis
     return out;
 }
 
+// ---- matchTrackedFeatures on the device tables (ms_match_tracked, ms_match_tracked_finish) ----------------------------------------------
+// MapPoint::trackId of every table row and mapDB.trackIdToMapPoint as a window of track ids on the device.  A track counts as present only
+// while its row is live and carries the id back, so cullMap and the reuse of a row need no write here: the entries go stale and are read
+// as erased.  Grow-only: ensureTrack() widens the window (the contents move through the host; rare).
+class DeviceTrackTable {
+public:
+    DeviceTrackTable(Context &ctx, std::size_t mapPoints, std::int32_t trackBase = 0, std::size_t window = 4096) : ctx_(ctx), nMp_(mapPoints), base_(trackBase) {
+        ctx_.check(ms_dev_alloc(ctx_.get(), 4 * nMp_ + 16, &mpTrack_), "ms_dev_alloc");
+        const std::vector<std::int32_t> none(nMp_, -1);
+        if (nMp_) ctx_.check(ms_dev_upload(ctx_.get(), mpTrack_, none.data(), 4 * nMp_), "ms_dev_upload");
+        reserve(window);
+    }
+    ~DeviceTrackTable() { ms_dev_free(ctx_.get(), mpTrack_); if (trackRow_) ms_dev_free(ctx_.get(), trackRow_); }
+    DeviceTrackTable(const DeviceTrackTable &) = delete;
+    // the window holds at least [trackBase, trackId]
+    void ensureTrack(std::int32_t trackId) {
+        if (trackId < base_) throw std::invalid_argument("DeviceTrackTable::ensureTrack: track id below the window base");
+        const std::size_t need = (std::size_t)(trackId - base_) + 1;
+        if (need > window_) reserve(std::max(need, 2 * window_));
+    }
+    // rows that already hold points of known tracks (a map loaded from the host): mp_track[row] = trackId and track_row[trackId] = row
+    void bind(const std::vector<std::int32_t> &rows, const std::vector<std::int32_t> &trackIds) {
+        if (rows.size() != trackIds.size()) throw std::invalid_argument("DeviceTrackTable::bind: one track id per row");
+        for (std::size_t i = 0; i < rows.size(); ++i) {
+            if (rows[i] < 0 || (std::size_t)rows[i] >= nMp_) throw std::invalid_argument("DeviceTrackTable::bind: row outside the table");
+            ensureTrack(trackIds[i]);
+        }
+        for (std::size_t i = 0; i < rows.size(); ++i) {
+            ctx_.check(ms_dev_upload(ctx_.get(), mpTrack() + rows[i], &trackIds[i], 4), "ms_dev_upload");
+            ctx_.check(ms_dev_upload(ctx_.get(), trackRow() + (trackIds[i] - base_), &rows[i], 4), "ms_dev_upload");
+        }
+    }
+    std::vector<std::int32_t> downloadMapPointTracks() const { return download(mpTrack_, nMp_); }
+    std::vector<std::int32_t> downloadTrackRows() const { return download(trackRow_, window_); }
+    std::size_t mapPointCount() const { return nMp_; }
+    std::size_t window() const { return window_; }
+    std::int32_t trackBase() const { return base_; }
+    std::int32_t *mpTrack() const { return static_cast<std::int32_t *>(mpTrack_); }
+    std::int32_t *trackRow() const { return static_cast<std::int32_t *>(trackRow_); }
+private:
+    std::vector<std::int32_t> download(const void *p, std::size_t n) const {
+        std::vector<std::int32_t> out(n);
+        if (n) ctx_.check(ms_dev_download(ctx_.get(), out.data(), p, 4 * n), "ms_dev_download");
+        return out;
+    }
+    void reserve(std::size_t window) {
+        std::vector<std::int32_t> rows = trackRow_ ? downloadTrackRows() : std::vector<std::int32_t>();
+        rows.resize(std::max<std::size_t>(window, 1), -1);
+        void *grown = nullptr;
+        ctx_.check(ms_dev_alloc(ctx_.get(), 4 * rows.size() + 16, &grown), "ms_dev_alloc");
+        ctx_.check(ms_dev_upload(ctx_.get(), grown, rows.data(), 4 * rows.size()), "ms_dev_upload");
+        if (trackRow_) ms_dev_free(ctx_.get(), trackRow_);
+        trackRow_ = grown; window_ = rows.size();
+    }
+    Context &ctx_;
+    std::size_t nMp_, window_ = 0;
+    std::int32_t base_;
+    void *mpTrack_ = nullptr, *trackRow_ = nullptr;
+};
+
+// The current frame as matchTrackedFeatures reads it: its keyframe slot (the keypoints are in DeviceKeypointTable, the pose in
+// DeviceKeyframePoses; poseCW is the same pose on the host) and keyPointToTrackId per keypoint, -1 for none.
+struct TrackedFrame {
+    std::int32_t slot = 0;
+    DeviceKeyframePoses::Pose poseCW{};
+    std::vector<std::int32_t> keyPointToTrackId;
+};
+// Per keypoint the outcome (0 no track | 1 created | 2 just tracked | 3 bound after isInFrustum and checkReprojectionError | 4 outside the
+// frustum | 5 reprojection error | 6 absent track, no descriptors), the rows of the created map points with their keypoints (in keypoint
+// order: what nextMpId, the host MapPoint objects and their colours are derived from), the reference's debug counters, and FIRST_LAST's
+// result per just-tracked point.
+struct MatchTrackedResult {
+    std::vector<std::uint8_t> outcome;
+    std::vector<std::int32_t> createdRows, createdKeyPoints;
+    std::size_t newPoints = 0, justTriangulated = 0, checked = 0, frustumFail = 0, reproFail = 0, success = 0;
+    TriangulateResult firstLast;
+};
+
+// matchTrackedFeatures (mapper_helpers.cpp:67-142) for one frame on the device tables, nothing per keypoint on the host:
+//   ms_match_tracked (the walk: bind, gate, create) -> ms_observation_lists of the just-tracked rows -> ms_triangulate_lists FIRST_LAST (:90)
+//   -> ms_match_tracked_finish (the descriptor of the points that are now UNSURE, :811; the rows of :121) -> the refresh of :121-124: one pass
+//   when the frame has descriptors, otherwise the just-tracked TRIANGULATED rows with the descriptor half and the checked rows without it.
+// freeRows: table rows the caller offers to new map points, at least as many as the frame can create (the k-th created point takes the
+// k-th); `pool` must hold the frame's descriptors at descBase[slot] when that is >= 0.  `lists` is scratch and holds the last refresh's rows.
+inline MatchTrackedResult matchTrackedFeatures(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &table, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags,
+                                               DeviceMapPointLive &live, DeviceTrackTable &tracks, const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses,
+                                               const KeyframeCameras &cams, const std::vector<std::int32_t> &kfIds, const std::vector<std::int32_t> &descBase,
+                                               const DeviceDescriptorPool *pool, const TrackedFrame &frame, const std::vector<std::int32_t> &freeRows,
+                                               const StaticSettings &settings, float viewAngleLimitCos = 0.5f) {
+    const std::size_t nKf = table.size(), nMp = table.mapPointCount(), nKp = frame.keyPointToTrackId.size(), nNew = freeRows.size();
+    if (frame.slot < 0 || (std::size_t)frame.slot >= nKf) throw std::invalid_argument("matchTrackedFeatures: slot outside the table");
+    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || kfIds.size() != nKf || descBase.size() != nKf || poses.size() != nKf)
+        throw std::invalid_argument("matchTrackedFeatures: one camera, focal length, KfId, descriptor base and pose per slot");
+    if (mapPoints.size() != nMp || flags.size() < nMp || live.size() < nMp || tracks.mapPointCount() != nMp) throw std::invalid_argument("matchTrackedFeatures: the map-point tables differ in size");
+    if (keypoints.size() != nKf || keypoints.stride() != table.stride()) throw std::invalid_argument("matchTrackedFeatures: the keypoint table does not match the keyframe table");
+    const bool hasDescriptors = descBase[frame.slot] >= 0;
+    if (hasDescriptors && !pool) throw std::invalid_argument("matchTrackedFeatures: the frame has descriptors and there is no pool");
+    for (std::int32_t t : frame.keyPointToTrackId) if (t >= 0) tracks.ensureTrack(t);
+    const int levels = (int)settings.levelSigmaSq.size();
+    const Parameters &p = settings.parameters;
+    ms_tracked_frame f{};
+    f.slot = frame.slot;
+    std::copy(frame.poseCW.begin(), frame.poseCW.end(), f.pose);
+    f.cam = cams.camera[frame.slot]; f.focal = cams.focalLength[frame.slot];
+    f.desc_base = descBase[frame.slot]; f.track_base = tracks.trackBase();
+    f.level_sigma_sq = settings.levelSigmaSq.data(); f.n_levels = levels;
+    f.rel_reprojection_threshold = p.relativeReprojectionErrorThreshold; f.view_cos_limit = viewAngleLimitCos;
+    // device scratch: created rows | created keypoints | just-tracked rows | checked rows | refresh rows | outcomes
+    const std::size_t pitchKp = (nKp + 63) / 64 * 64 + 64, pitchNew = (nNew + 63) / 64 * 64 + 64;
+    std::int32_t *createdRows = reinterpret_cast<std::int32_t *>(ctx.workspace(4 * (2 * pitchNew + 4 * pitchKp) + pitchKp + 256));
+    std::int32_t *createdKp = createdRows + pitchNew, *trackedRows = createdKp + pitchNew, *checkedRows = trackedRows + pitchKp, *refreshRows = checkedRows + pitchKp;
+    std::uint8_t *outcome = reinterpret_cast<std::uint8_t *>(refreshRows + 2 * pitchKp);
+    std::int32_t counts[5] = {0, 0, 0, 0, 0};
+    ctx.check(ms_match_tracked(ctx.get(), table.mutableTable(), (int)nKf, (int)table.stride(), flags.mutableFlags(), live.mutableLive(), mapPoints.position(), mapPoints.norm(),
+                               mapPoints.minDistance(), mapPoints.maxDistance(), mapPoints.mutableDescriptor(), tracks.mpTrack(), (int)nMp, keypoints.x(), keypoints.y(),
+                               keypoints.octave(), pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, tracks.trackRow(), (int)tracks.window(), &f,
+                               frame.keyPointToTrackId.data(), (int)nKp, freeRows.data(), (int)nNew, outcome, createdRows, createdKp, trackedRows, checkedRows, counts),
+              "ms_match_tracked");
+    MatchTrackedResult out;
+    out.newPoints = (std::size_t)counts[0]; out.justTriangulated = (std::size_t)counts[1]; out.checked = (std::size_t)counts[2];
+    out.frustumFail = (std::size_t)counts[3]; out.reproFail = (std::size_t)counts[4];
+    out.outcome.resize(nKp); out.createdRows.resize(out.newPoints); out.createdKeyPoints.resize(out.newPoints);
+    if (nKp) ctx.check(ms_dev_download(ctx.get(), out.outcome.data(), outcome, nKp), "ms_dev_download");
+    if (out.newPoints) {
+        ctx.check(ms_dev_download(ctx.get(), out.createdRows.data(), createdRows, 4 * out.newPoints), "ms_dev_download");
+        ctx.check(ms_dev_download(ctx.get(), out.createdKeyPoints.data(), createdKp, 4 * out.newPoints), "ms_dev_download");
+    }
+    const std::vector<std::int32_t> noBase;
+    auto listsOf = [&](const std::int32_t *rows, std::size_t n, bool dropEmpty) {
+        ObservationSelection sel;
+        sel.deviceRows = rows; sel.rowCount = n; sel.dropEmpty = dropEmpty;
+        lists.build(table, keypoints, &flags, kfIds, pool ? descBase : noBase, sel, levels);
+    };
+    std::size_t nTracked = 0;
+    if (out.justTriangulated) {                              // :90
+        listsOf(trackedRows, out.justTriangulated, false);
+        nTracked = lists.rowCount();
+        const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)levels, p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                                p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+        out.firstLast.status.assign(nTracked, 0); out.firstLast.reason.assign(nTracked, 0); out.firstLast.passCount.assign(nTracked, 0);
+        const ms_obs_lists l = lists.lists();
+        ctx.check(ms_triangulate_lists(ctx.get(), mapPoints.mutablePosition(), flags.mutableFlags(), (int)nMp, poses.pose(), (int)nKf, cams.camera.data(), cams.focalLength.data(), &l,
+                                       (int)nTracked, (int)lists.observationCount(), &s, MS_TRI_FIRST_LAST, out.firstLast.status.data(), out.firstLast.reason.data(),
+                                       out.firstLast.passCount.data()), "ms_triangulate_lists");
+    }
+    ms_obs_lists l = lists.lists();
+    if (!pool) l.obs_desc = nullptr;
+    std::int32_t nRefresh = 0;
+    ctx.check(ms_match_tracked_finish(ctx.get(), &l, (int)nTracked, flags.flags(), pool ? pool->descriptor() : nullptr, mapPoints.mutableDescriptor(), (int)nMp, checkedRows,
+                                      (int)out.checked, hasDescriptors ? 1 : 0, refreshRows, (int)(2 * pitchKp), &nRefresh), "ms_match_tracked_finish");
+    auto refresh = [&](const std::int32_t *rows, std::size_t n, bool descriptors) {                      // :121-124
+        if (n == 0) return;
+        listsOf(rows, n, true);
+        const ms_obs_lists r = lists.lists();
+        const bool withPool = descriptors && pool;
+        ctx.check(ms_map_refresh_lists(ctx.get(), mapPoints.position(), mapPoints.mutableNorm(), mapPoints.mutableMinDistance(), mapPoints.mutableMaxDistance(),
+                                       mapPoints.mutableDescriptor(), (int)nMp, poses.pose(), (int)nKf, withPool ? pool->descriptor() : nullptr, withPool ? (int)pool->size() : 0, &r,
+                                       (int)lists.rowCount(), (int)lists.observationCount(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(), 0, nullptr, nullptr),
+                  "ms_map_refresh_lists");
+    };
+    refresh(refreshRows, (std::size_t)nRefresh, true);
+    if (!hasDescriptors) refresh(checkedRows, out.checked, false);
+    out.success = (std::size_t)nRefresh + (hasDescriptors ? 0 : out.checked);
+    return out;
+}
+
 // One view of a gate call: a pose (p_c = R p + t, row-major; for MS_GATE_SIM3 rotBAW / transBAW, which may carry a scale), a pinhole camera
 // (the stand-in of ms_pinhole), the loop's threshold / margin, and the table rows to walk, in the reference's order.
 struct GateView {

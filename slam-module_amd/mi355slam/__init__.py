@@ -1020,6 +1020,17 @@ class MapPointTable:
                                                   int(promote_min_obs), _vp(flags), _vp(medoid)), "ms_map_refresh_lists")
         return medoid[:n_rows] if want_medoid else None
 
+    def match_tracked_finish_device(self, lists, n_rows, flags, pool, checked_rows, n_checked, append_checked, refresh_rows, cap_refresh):
+        """ms_match_tracked_finish on the first n_rows rows of `lists` (an ObservationLists over the just-tracked rows, after their FIRST_LAST
+        triangulation): this table's descriptor of every row whose flags are 2 (UNSURE) becomes that of its first observation with a
+        descriptor in `pool` (a DevBuf; None: descriptors stay), and refresh_rows (a DevBuf of cap_refresh int32) receives the rows with
+        flags & 1 in list order, then checked_rows[:n_checked] (a DevBuf) when append_checked.  Returns (rc, n_refresh) without raising."""
+        L = lists.struct(True, True, True)
+        n_refresh = C.c_int32(0)
+        rc = lib().ms_match_tracked_finish(self.ctx._h, C.byref(L), int(n_rows), _vp(flags), _vp(pool), _vp(self.desc), self.n, _vp(checked_rows), int(n_checked),
+                                           int(bool(append_checked)), _vp(refresh_rows), int(cap_refresh), C.byref(n_refresh))
+        return rc, n_refresh.value
+
 
 def gate_views_pack(views):
     """(GateViewC array, mp_index) for a list of view dicts: R [3, 3], t [3], cam (fx, fy, cx, cy, width, height), threshold, view_cos_limit
@@ -1371,6 +1382,143 @@ class KeyframeTable:
             if own is not None:
                 own.free()
         return lists, n_rows, n_obs
+
+    def match_tracked_device(self, table, flags, live, tracks, kp, pool, frame, kp_track, new_rows, out):
+        """ms_match_tracked with everything left on the device.  table = a MapPointTable, flags / live = DevBufs of [n_mp] uint8, tracks = a
+        TrackTable, kp = a KeypointTable, pool = a DevBuf of [n_pool, 8] uint32 or None.  frame: dict(slot, pose [12], cam (fx, fy, cx, cy,
+        width, height), focal, desc_base (negative: the frame has no descriptors), level_sigma_sq, rel_reprojection_threshold,
+        view_cos_limit (0.5 when absent)).  kp_track [n_kp] int32, new_rows [n_new] int32.  out: dict of DevBufs outcome [n_kp] uint8,
+        created_rows / created_kp [n_new], tracked_rows / checked_rows [n_kp] int32 (all but outcome may be None or absent).  Returns
+        (rc, counts [5]) without raising: MS_ERR_CAPACITY reports the number of new rows needed in counts[0]."""
+        if (kp.n_kf, kp.stride) != (self.n_kf, self.stride):
+            raise ValueError("the keypoint table is %d x %d, kf_mp %d x %d" % (kp.n_kf, kp.stride, self.n_kf, self.stride))
+        if tracks.n_mp != table.n:
+            raise ValueError("mp_track describes %d map points, the table %d" % (tracks.n_mp, table.n))
+        kp_track, new_rows = _i32(kp_track), _i32(new_rows)
+        sig = np.ascontiguousarray(frame["level_sigma_sq"], np.float32).reshape(-1)
+        pose = np.ascontiguousarray(frame["pose"], np.float64).reshape(12)
+        cam = frame["cam"]
+        Fr = TrackedFrameC(int(frame["slot"]), (C.c_double * 12)(*pose), Pinhole(cam[0], cam[1], cam[2], cam[3], int(cam[4]), int(cam[5])), int(frame["focal"]),
+                           int(frame["desc_base"]), tracks.track_base, sig.ctypes.data, len(sig), float(frame["rel_reprojection_threshold"]),
+                           float(frame.get("view_cos_limit", 0.5)))
+        n_pool = int(np.prod(pool.shape)) // 8 if pool is not None else 0
+        counts = np.zeros(5, np.int32)
+        rc = lib().ms_match_tracked(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(flags), _vp(live), _vp(table.pos), _vp(table.norm), _vp(table.min_dist),
+                                    _vp(table.max_dist), _vp(table.desc), _vp(tracks.mp_track), table.n, _vp(kp.x), _vp(kp.y), _vp(kp.octave), _vp(pool), n_pool,
+                                    _vp(tracks.track_row), tracks.n_track, C.byref(Fr), _vp(kp_track), len(kp_track), _vp(new_rows), len(new_rows),
+                                    *[_vp(out.get(k)) for k in ("outcome", "created_rows", "created_kp", "tracked_rows", "checked_rows")], _vp(counts))
+        return rc, counts
+
+    def match_tracked_bind(self, table, flags, live, tracks, kp, pool, poses, kf_id, cams, focal, desc_base, frame, new_rows, settings, view_cos_limit=0.5,
+                           lists=None):
+        """The first half of match_tracked(): the walk (ms_match_tracked), then the observation lists of the just-tracked rows and their
+        FIRST_LAST triangulation (skipped when nothing was just tracked).  Returns the dict match_tracked_refresh() takes: outcome [n_kp],
+        created_rows, created_kp, counts (created, just tracked, checked, frustum failures, reprojection failures), status (of the
+        just-tracked rows, in tracked_rows order), and the device buffers of the second half."""
+        kf_id, desc_base, kp_track, new_rows = _i32(kf_id), _i32(desc_base), _i32(frame["kp_track"]), _i32(new_rows)
+        slot, n_kp, n_new, n_mp = int(frame["slot"]), len(kp_track), len(new_rows), table.n
+        if not 0 <= slot < self.n_kf or len(desc_base) != self.n_kf or len(_i32(focal)) != self.n_kf:
+            raise ValueError("slot %d, or desc_base / focal, do not describe the table's %d slots" % (slot, self.n_kf))
+        frame = dict(slot=slot, pose=frame["pose"], cam=np.asarray(cams, np.float64).reshape(-1, 6)[slot], focal=_i32(focal)[slot], desc_base=desc_base[slot],
+                     level_sigma_sq=settings["level_sigma_sq"], rel_reprojection_threshold=settings["rel_reprojection_threshold"], view_cos_limit=view_cos_limit)
+        out = dict(outcome=self.ctx.alloc(max(n_kp, 1)), created_rows=self.ctx.alloc(4 * max(n_new, 1)), created_kp=self.ctx.alloc(4 * max(n_new, 1)),
+                   tracked_rows=self.ctx.alloc(4 * max(n_kp, 1)), checked_rows=self.ctx.alloc(4 * max(n_kp, 1)), refresh_rows=self.ctx.alloc(8 * max(n_kp, 1)))
+        rc, counts = self.match_tracked_device(table, flags, live, tracks, kp, pool, frame, kp_track, new_rows, out)
+        if rc != 0:
+            for b in out.values():
+                b.free()
+            self.ctx.check(rc, "ms_match_tracked")
+        n_created, n_tracked, n_checked = (int(v) for v in counts[:3])
+        some = lambda b, dtype, n: b.download(dtype, (n,)) if n else np.zeros(0, dtype)
+        res = dict(outcome=some(out["outcome"], np.uint8, n_kp), created_rows=some(out["created_rows"], np.int32, n_created),
+                   created_kp=some(out["created_kp"], np.int32, n_created), counts=counts, status=np.zeros(0, np.uint8), bufs=out,
+                   lists=lists if lists is not None else ObservationLists(self.ctx, 256, 1024), own_lists=lists is None, n_rows=0, n_obs=0,
+                   args=(table, flags, tracks, kp, pool, poses, kf_id, desc_base, slot, len(settings["level_sigma_sq"])))
+        if n_tracked:
+            sel = dict(source=OBS_FROM_ROWS, rows_in=out["tracked_rows"], n_in=n_tracked)
+            res["n_rows"], res["n_obs"] = self._lists_of(res["lists"], kf_id, n_mp, sel, kp, desc_base, flags, res["args"][-1])
+            res["status"] = table.triangulate_lists(poses, cams, focal, res["lists"], res["n_rows"], res["n_obs"], settings, TRI_FIRST_LAST, flags=flags)[0]
+        return res
+
+    def _lists_of(self, lists, kf_id, n_mp, sel, kp, desc_base, flags, n_levels):
+        """observation_lists_device into `lists`, grown when it is too small; (n_rows, n_obs)."""
+        rc, n_rows, n_obs = self.observation_lists_device(lists, kf_id, n_mp, sel, kp, desc_base, flags, n_levels)
+        if rc == MS_ERR_CAPACITY and (n_rows > lists.cap_rows or n_obs > lists.cap_obs):
+            lists.grow(n_rows, n_obs)
+            rc, n_rows, n_obs = self.observation_lists_device(lists, kf_id, n_mp, sel, kp, desc_base, flags, n_levels)
+        self.ctx.check(rc, "ms_observation_lists")
+        return n_rows, n_obs
+
+    def match_tracked_refresh(self, res, scale_factors_):
+        """The second half of match_tracked(): ms_match_tracked_finish (the descriptor of the rows that are now UNSURE; the rows to refresh),
+        then the refresh of mapper_helpers.cpp:121-124 -- one pass when the frame has descriptors; otherwise the tracked-and-TRIANGULATED
+        rows with the descriptor half (the updateDescriptor of :811) and the checked rows without it.  Adds refresh_rows to res and frees
+        the device buffers of the chain (the lists too, unless the caller passed its own to match_tracked_bind)."""
+        table, flags, tracks, kp, pool, poses, kf_id, desc_base, slot, n_levels = res["args"]
+        out, lists, n_mp = res["bufs"], res["lists"], table.n
+        n_tracked, n_checked = int(res["counts"][1]), int(res["counts"][2])
+        has_desc = desc_base[slot] >= 0
+        n_kp = len(res["outcome"])
+        try:
+            rc, n_refresh = table.match_tracked_finish_device(lists, res["n_rows"], flags, pool, out["checked_rows"], n_checked, has_desc, out["refresh_rows"], 2 * max(n_kp, 1))
+            self.ctx.check(rc, "ms_match_tracked_finish")
+            res["refresh_rows"] = out["refresh_rows"].download(np.int32, (n_refresh,)) if n_refresh else np.zeros(0, np.int32)
+            passes = [(out["refresh_rows"], n_refresh, pool)]
+            if not has_desc:
+                passes.append((out["checked_rows"], n_checked, None))
+            for rows, n, with_pool in passes:
+                if n == 0:
+                    continue
+                sel = dict(source=OBS_FROM_ROWS, drop_empty=1, rows_in=rows, n_in=n)
+                n_rows, n_obs = self._lists_of(lists, kf_id, n_mp, sel, kp, desc_base, flags, n_levels)
+                table.refresh_lists(poses, lists, n_rows, n_obs, scale_factors_, pool=with_pool, promote_min_obs=0, want_medoid=False)
+        finally:
+            for b in out.values():
+                b.free()
+            if res["own_lists"]:
+                lists.free()
+        del res["bufs"], res["args"], res["own_lists"]
+        return res
+
+    def match_tracked(self, table, flags, live, tracks, kp, pool, poses, kf_id, cams, focal, desc_base, frame, new_rows, settings, scale_factors_,
+                      view_cos_limit=0.5):
+        """matchTrackedFeatures (mapper_helpers.cpp:67-142) for one frame on the device tables, in place: this KeyframeTable, the
+        MapPointTable `table`, flags / live (DevBufs), the TrackTable `tracks`; kp = the KeypointTable, pool = the descriptor pool (DevBuf),
+        poses = the KeyframePoseTable; kf_id, cams [n_kf, 6], focal, desc_base per slot; frame = dict(slot, pose [12]: rows 0-2 of its
+        poseCW as the pose table holds them, kp_track [n_kp] = keyPointToTrackId, -1 none);
+        new_rows = free rows for the points the frame creates; settings as MapPointTable.triangulate.  Returns a dict: outcome [n_kp]
+        (0 no track, 1 created, 2 just tracked, 3 bound after both checks, 4 outside the frustum, 5 reprojection error, 6 absent and no
+        descriptors), created_rows, created_kp, counts, status (FIRST_LAST's, per just-tracked row), refresh_rows.  nextMpId, the host
+        MapPoint objects and their colours stay with the caller, who derives them from created_rows / created_kp."""
+        res = self.match_tracked_bind(table, flags, live, tracks, kp, pool, poses, kf_id, cams, focal, desc_base, frame, new_rows, settings, view_cos_limit)
+        return self.match_tracked_refresh(res, scale_factors_)
+
+
+class TrackedFrameC(C.Structure):
+    """ms_tracked_frame."""
+    _fields_ = [("slot", C.c_int32), ("pose", C.c_double * 12), ("cam", Pinhole), ("focal", C.c_int32), ("desc_base", C.c_int32), ("track_base", C.c_int32),
+                ("level_sigma_sq", C.c_void_p), ("n_levels", C.c_int32), ("rel_reprojection_threshold", C.c_float), ("view_cos_limit", C.c_float)]
+
+
+class TrackTable:
+    """MapPoint::trackId and mapDB.trackIdToMapPoint on the device: mp_track [n_mp] int32 (-1 none) and track_row [n_track] int32, the row of
+    track id track_base + i (-1 absent).  ms_match_tracked reads a track as present only when its row is live and carries the id back, so
+    culling and recycling rows needs no write here."""
+
+    def __init__(self, ctx, mp_track, track_row, track_base):
+        self.ctx, self.track_base = ctx, int(track_base)
+        a, b = _i32(mp_track), _i32(track_row)
+        self.n_mp, self.n_track = len(a), len(b)
+        self.mp_track = ctx.upload(a if len(a) else np.full(1, -1, np.int32))
+        self.track_row = ctx.upload(b if len(b) else np.full(1, -1, np.int32))
+
+    def download(self):
+        """(mp_track, track_row)"""
+        return (self.mp_track.download(np.int32, (self.n_mp,)) if self.n_mp else np.zeros(0, np.int32),
+                self.track_row.download(np.int32, (self.n_track,)) if self.n_track else np.zeros(0, np.int32))
+
+    def free(self):
+        self.mp_track.free(); self.track_row.free()
 
 
 # ---- observation lists on the device (ms_observation_lists) ----
