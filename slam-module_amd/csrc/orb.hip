@@ -21,6 +21,8 @@
 #include "fast_tiles.h"
 #include "describe_lanes.h"
 #include "describe_steer.h"
+#include "describe_brief_index.h"
+#include "resize_vpass.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -98,7 +100,13 @@ __global__ __launch_bounds__(256) void k_copy_level0(const uint8_t *src, uint64_
 // 4 destination pixels per lane, one dword store.  Per source row a lane fetches three aligned dwords
 // (12 bytes cover the <= 8-byte tap window of its 4 pixels for scale factors up to 2) and funnel-shifts
 // them into a 64-bit window; the per-column (offset, a0, a1) and per-row (row0, row1, b0, b1) tables are
-// packed so a lane needs two 16-byte table loads.  HBM-bound by design: reads level l-1, writes level l.
+// packed so a lane needs two 16-byte table loads.  What bounds it, as measured: a level's launch moves the same bytes per
+// second whether its planes fit in the last-level cache (45 MB in 13.9 us at the smallest level) or not (400 MB in 110 us at the largest), a
+// constant cost per pixel at every footprint -- yet taking a fifth of the vector instructions out (127.2 M -> 100.0 M per 256-frame step: scalar
+// row addresses, resize_row; three instructions per pixel in the vertical pass, resize_vpass.h) while the scalar count rose from 81.8 M to 101.9 M
+// bought 3.6 % (0.2935 -> 0.2830 ms for the seven launches).  The time followed the SUM of vector and scalar instructions (-3.4 %), not the vector
+// count: neither "HBM-bound by design" nor "bound by vector issue" describes it.  The step's 1.0 .. 1.5 GB (counter as read .. corrected) pass at
+// 3.6 .. 5.4 TB/s.
 // unaligned dword / qword accesses (global memory takes them)
 struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
 struct __attribute__((packed, aligned(1))) U64u { uint32_t lo, hi; };
@@ -130,9 +138,19 @@ constexpr int kResizeRows = 5;   // destination rows per lane: the table fetch i
 struct Window3 { uint32_t d0, d1, d2; };
 typedef uint32_t u3_t __attribute__((ext_vector_type(3)));
 typedef u3_t u3a_t __attribute__((aligned(4)));       // a 12-byte load from a dword-aligned address
+// `row` is wave-uniform; the three lane offsets are >= 0 and below the pitch (0 <= base, last_dword <= sw - 1), so they are added as unsigned 32-bit numbers
 __device__ __forceinline__ Window3 window_load(const uint8_t *row, int base, int last_dword) {
-    return {*reinterpret_cast<const uint32_t *>(row + min(base, last_dword)), *reinterpret_cast<const uint32_t *>(row + min(base + 4, last_dword)),
-            *reinterpret_cast<const uint32_t *>(row + min(base + 8, last_dword))};
+    typedef const __attribute__((address_space(1))) uint32_t gdword_t;        // (global_load: a generic pointer would become a flat load)
+    return {*(gdword_t *)(row + (uint32_t)min(base, last_dword)), *(gdword_t *)(row + (uint32_t)min(base + 4, last_dword)), *(gdword_t *)(row + (uint32_t)min(base + 8, last_dword))};
+}
+// Start of row `row` of a plane: row and pitch are wave-uniform and >= 0, so the product and the sum are scalar arithmetic, and a load or store of the row is
+// this scalar base plus the lane's unsigned 32-bit byte offset (global_load / global_store v_offset, s[base:base+1]) -- no 64-bit multiply-add per lane.
+// The empty statement holds the sum in scalar registers: left alone the compiler adds the lane offset to the plane first and the row's product to that,
+// one v_mad_u64_u32 per row.
+template <class T> __device__ __forceinline__ T *resize_row(T *plane, int row, int pitch) {
+    T *p = plane + (uint64_t)(uint32_t)row * (uint32_t)pitch;
+    asm("" : "+s"(p));
+    return p;
 }
 
 // Shared-row path of k_resize.  At a level ratio near 1.2 the tap rows of a group's five destination rows are the NROWS = 6 or 7 consecutive
@@ -143,15 +161,15 @@ __device__ __forceinline__ Window3 window_load(const uint8_t *row, int base, int
 template <int NROWS>
 __device__ __forceinline__ void resize_shared_rows(const uint8_t *S, int spitch, int s0, int sh, int sx0, int base, int last, bool edge, uint4 taps, uint4 sels,
                                                    const short4 (&yt)[kResizeRows], uint8_t *dst, int dy0, int dx0, int dh, int dpitch) {
-    const uint32_t A[4] = {taps.x, taps.y, taps.z, taps.w}, sel[4] = {sels.x, sels.y, sels.z, sels.w};      // the caller's per-column operands, by value
+    const uint32_t A[4] = {taps.x, taps.y, taps.z, taps.w}, sel[4] = {sels.x, sels.y, sels.z, sels.w};      // the caller's per-column operands (taps times 16), by value
     Window3 W[NROWS];
     if (!edge || last >= 8) {
-        const int from = edge ? min(base, last - 8) : base, shift = base - from;       // as in the general path
+        const int from0 = edge ? min(base, last - 8) : base, shift = base - from0;       // as in the general path
+        uint32_t from = (uint32_t)from0;               // 0 <= from <= last - 8 < pitch: an unsigned 32-bit lane offset beside the row's scalar base
+        asm volatile("" : "+v"(from));                 // (an offset the compiler cannot see through: the 12-byte branch stays apart from the three-dword one)
 #pragma unroll
         for (int i = 0; i < NROWS; ++i) {
-            const uint8_t *p = S + (uint64_t)min(s0 + i, sh - 1) * spitch + from;
-            asm volatile("" : "+v"(p));
-            const u3_t a = *(const __attribute__((address_space(1))) u3a_t *)(p);
+            const u3_t a = *(const __attribute__((address_space(1))) u3a_t *)(resize_row(S, min(s0 + i, sh - 1), spitch) + from);
             W[i] = {a.x, a.y, a.z};
         }
         if (edge) {
@@ -160,7 +178,7 @@ __device__ __forceinline__ void resize_shared_rows(const uint8_t *S, int spitch,
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < NROWS; ++i) W[i] = window_load(S + (uint64_t)min(s0 + i, sh - 1) * spitch, base, last);
+        for (int i = 0; i < NROWS; ++i) W[i] = window_load(resize_row(S, min(s0 + i, sh - 1), spitch), base, last);
     }
     uint32_t F[NROWS][4];
 #pragma unroll
@@ -168,20 +186,23 @@ __device__ __forceinline__ void resize_shared_rows(const uint8_t *S, int spitch,
         const uint32_t lo = __builtin_amdgcn_alignbyte(W[i].d1, W[i].d0, (uint32_t)sx0), hi = __builtin_amdgcn_alignbyte(W[i].d2, W[i].d1, (uint32_t)sx0);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            F[i][c] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(hi, lo, sel[c])), __builtin_bit_cast(us2_t, A[c]), 0u, false) >> 4;
-            asm volatile("" : "+v"(F[i][c]));          // the shift happens here, once: left alone the compiler repeats it in every row body that reads the value
+            F[i][c] = resize_vpass::f8(__builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(hi, lo, sel[c])), __builtin_bit_cast(us2_t, A[c]), 0u, false));
+            asm volatile("" : "+v"(F[i][c]));          // the mask happens here, once: left alone the compiler repeats it in every row body that reads the value
         }
     }
     // the two choices of a row are two bodies behind a scalar branch: the empty asm statements differ, which keeps the compiler from merging the
     // bodies into one with eight per-lane selects in front (as many vector instructions as the shared rows save)
     auto emit = [&](int r, bool upper, const uint32_t (&f0)[4], const uint32_t (&f1)[4]) {
-        const uint32_t b0 = (uint32_t)yt[r].z, b1 = (uint32_t)yt[r].w;
+        const uint32_t b0 = resize_vpass::row_tap((uint32_t)yt[r].z), b1 = resize_vpass::row_tap((uint32_t)yt[r].w);      // scalar
         uint32_t v[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = ((__umul24(b0, f0[c]) >> 16) + (__umul24(b1, f1[c]) >> 16) + 2) >> 2;
-        uint32_t packed = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        for (int c = 0; c < 4; ++c) {
+            v[c] = resize_vpass::vsum(b0, f0[c], b1, f1[c]);
+            asm("" : "+v"(v[c]));                      // one v_add3_u32: left alone the + 2 of the odd columns moves behind their shift into the pair (two more instructions)
+        }
+        uint32_t packed = resize_vpass::pack4(v[0], v[1], v[2], v[3]);
         if (upper) asm volatile("; rows d + 1, d + 2" : "+v"(packed)); else asm volatile("; rows d, d + 1" : "+v"(packed));
-        *reinterpret_cast<uint32_t *>(dst + (uint64_t)(dy0 + r) * dpitch + dx0) = packed;
+        *(__attribute__((address_space(1))) uint32_t *)(resize_row(dst, dy0 + r, dpitch) + (uint32_t)dx0) = packed;       // 0 <= dx0 < pitch
     };
 #pragma unroll
     for (int r = 0; r < kResizeRows; ++r) {
@@ -220,12 +241,12 @@ __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
         uint32_t A[4], sel[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            A[i] = __builtin_amdgcn_alignbit(xhi[i], xlo[i], 16);
+            A[i] = resize_vpass::preshift_taps(__builtin_amdgcn_alignbit(xhi[i], xlo[i], 16));      // times 16: the horizontal pass delivers 16 r (resize_vpass.h)
             sel[i] = 0x0C010C00u + (uint32_t)((int16_t)xlo[i] - sx0) * 0x00010001u;
         }
-        // The kernel is bound by the NUMBER of vector-memory instructions (measured: dropping the arithmetic changes nothing, halving the
-        // loads gives -36 %), so the three dwords of a window are ONE 12-byte load wherever no lane of the wave touches the row's last
-        // dwords (a 12-byte load there would run past the row, and past the caller's buffer on the last row of level 0).
+        // The three dwords of a window are ONE 12-byte load wherever no lane of the wave touches the row's last dwords (a 12-byte load there
+        // would run past the row, and past the caller's buffer on the last row of level 0): a third of the vector-memory instructions and of the
+        // address arithmetic in front of them (measured when the three dword loads became one: -36 % for half the loads).
         const bool edge = __ballot(base + 8 > last) != 0;        // wave-uniform
         // Scalar test on the group's five table entries: do its rows share six or seven consecutive source rows?  (Rows past the level's
         // last one are padding and do not count.)  Other ratios, and any group that fails the test, take the general path below.
@@ -244,11 +265,12 @@ __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
         if (!edge || last >= 8) {
             // edge wave: the 12 bytes are fetched from min(base, last - 8) and moved down by whole dwords afterwards, which reproduces the
             // clamped dwords exactly (d_k = row[min(base + 4k, last)])
-            const int from = edge ? min(base, last - 8) : base, shift = base - from;       // shift = 0, 4 or 8 bytes
+            const int from0 = edge ? min(base, last - 8) : base, shift = base - from0;       // shift = 0, 4 or 8 bytes
+            uint32_t from = (uint32_t)from0;              // 0 <= from <= last - 8 < pitch: an unsigned 32-bit lane offset beside each row's scalar base
+            asm volatile("" : "+v"(from));                // keeps the compiler from folding this branch into the clamped one below (equal values, three loads each)
 #pragma unroll
             for (int r = 0; r < kResizeRows; ++r) {
-                const uint8_t *p0 = S + (uint64_t)yt[r].x * spitch + from, *p1 = S + (uint64_t)yt[r].y * spitch + from;
-                asm volatile("" : "+v"(p0), "+v"(p1));        // keeps the compiler from folding this branch into the clamped one below (equal values, three loads each)
+                const uint8_t *p0 = resize_row(S, yt[r].x, spitch) + from, *p1 = resize_row(S, yt[r].y, spitch) + from;
                 const u3_t a = *(const __attribute__((address_space(1))) u3a_t *)(p0), b = *(const __attribute__((address_space(1))) u3a_t *)(p1);   // global_load_dwordx3 (a generic pointer would become a flat load)
                 W0[r] = {a.x, a.y, a.z};
                 W1[r] = {b.x, b.y, b.z};
@@ -263,8 +285,8 @@ __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
         } else {
 #pragma unroll
             for (int r = 0; r < kResizeRows; ++r) {
-                W0[r] = window_load(S + (uint64_t)yt[r].x * spitch, base, last);
-                W1[r] = window_load(S + (uint64_t)yt[r].y * spitch, base, last);
+                W0[r] = window_load(resize_row(S, yt[r].x, spitch), base, last);
+                W1[r] = window_load(resize_row(S, yt[r].y, spitch), base, last);
             }
         }
 #pragma unroll
@@ -272,16 +294,17 @@ __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
             // window = source bytes sx0 .. sx0+7 of each tap row (byte funnel of the three aligned dwords)
             const uint32_t lo0 = __builtin_amdgcn_alignbyte(W0[r].d1, W0[r].d0, (uint32_t)sx0), hi0 = __builtin_amdgcn_alignbyte(W0[r].d2, W0[r].d1, (uint32_t)sx0);
             const uint32_t lo1 = __builtin_amdgcn_alignbyte(W1[r].d1, W1[r].d0, (uint32_t)sx0), hi1 = __builtin_amdgcn_alignbyte(W1[r].d2, W1[r].d1, (uint32_t)sx0);
-            const uint32_t b0 = (uint32_t)yt[r].z, b1 = (uint32_t)yt[r].w;
+            const uint32_t b0 = resize_vpass::row_tap((uint32_t)yt[r].z), b1 = resize_vpass::row_tap((uint32_t)yt[r].w);      // scalar
             uint32_t v[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const uint32_t r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(hi0, lo0, sel[i])), __builtin_bit_cast(us2_t, A[i]), 0u, false);
                 const uint32_t r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(hi1, lo1, sel[i])), __builtin_bit_cast(us2_t, A[i]), 0u, false);
-                v[i] = ((__umul24(b0, r0 >> 4) >> 16) + (__umul24(b1, r1 >> 4) >> 16) + 2) >> 2;      // <= 255 by construction (taps sum to 2048 +- 1)
+                v[i] = resize_vpass::vsum(b0, resize_vpass::f8(r0), b1, resize_vpass::f8(r1));      // v >> 2 <= 255 by construction (taps sum to 2048 +- 1)
+                asm("" : "+v"(v[i]));                  // one v_add3_u32, as in the shared-row path
             }
-            const uint32_t packed = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-            if (dy0 + r < D.h) *reinterpret_cast<uint32_t *>(dst + (uint64_t)(dy0 + r) * D.pitch + dx0) = packed;
+            const uint32_t packed = resize_vpass::pack4(v[0], v[1], v[2], v[3]);
+            if (dy0 + r < D.h) *(__attribute__((address_space(1))) uint32_t *)(resize_row(dst, dy0 + r, D.pitch) + (uint32_t)dx0) = packed;       // 0 <= dx0 < pitch
         }
     } else {
 #pragma unroll
@@ -1201,7 +1224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    float angle_deg[kDescPerWave], ca[kDescPerWave], sa[kDescPerWave];
+    float angle_deg[kDescPerWave], ca[kDescPerWave], sa[kDescPerWave], nsa[kDescPerWave];
 #pragma unroll
     for (int k = 0; k < kDescPerWave; ++k) {
         angle_deg[k] = describe_steer::fast_atan2((float)m01[k], (float)m10[k]);
@@ -1211,23 +1234,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const float cs = describe_steer::cos_approx(lane == 1 ? describe_steer::sin_argument(angle) : angle);
         ca[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 0));
         sa[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 1));
+        // the column is x cos - y sin = x cos + y (-sin), the same float bit for bit (a product's sign is exact): with the sign turned once per keypoint, row and
+        // column of a point are the same two multiplies and one add, and the compiler packs each step of the pair into one v_pk_*_f32.  The empty statement
+        // keeps it from folding the negation back into a subtraction.
+        nsa[k] = -sa[k];
+        asm volatile("" : "+s"(nsa[k]));
     }
     // O2: steered BRIEF on the blurred patch; the lane's point pairs are shared by the wave's keypoints
     unsigned long long bits[kDescPerWave][4];
+    typedef __attribute__((address_space(3))) uint8_t lds_u8_t;
+    uint32_t pbase[kDescPerWave];                            // the blurred patch's LDS address and the index's constant in one (wave-uniform)
+#pragma unroll
+    for (int k = 0; k < kDescPerWave; ++k) pbase[k] = (uint32_t)(uintptr_t)(const lds_u8_t *)&s_patch[wv][k][0] + describe_brief_index::kIndexBias;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float4 pt = __builtin_bit_cast(float4, s_tab[64 + q * 64 + lane]);             // the test's two points, already float
         const float x1 = pt.x, y1 = pt.y, x2 = pt.z, y2 = pt.w;
 #pragma unroll
         for (int k = 0; k < kDescPerWave; ++k) {
-            const uint8_t *pb = reinterpret_cast<const uint8_t *>(&s_patch[wv][k][0]);
-            const int r1 = __float2int_rn(__fadd_rn(__fmul_rn(x1, sa[k]), __fmul_rn(y1, ca[k])));
-            const int c1 = __float2int_rn(__fsub_rn(__fmul_rn(x1, ca[k]), __fmul_rn(y1, sa[k])));
-            const int r2 = __float2int_rn(__fadd_rn(__fmul_rn(x2, sa[k]), __fmul_rn(y2, ca[k])));
-            const int c2 = __float2int_rn(__fsub_rn(__fmul_rn(x2, ca[k]), __fmul_rn(y2, sa[k])));
-            // rows and columns + 19 lie in 0 .. 38 (the pattern stays inside the 39 x 39 patch under every rotation): 24-bit multiply-adds, not full 32-bit multiplies
-            const uint32_t i1 = __umul24((uint32_t)(r1 + kPatchRadius), 40u) + (uint32_t)(c1 + kPatchRadius), i2 = __umul24((uint32_t)(r2 + kPatchRadius), 40u) + (uint32_t)(c2 + kPatchRadius);
-            bits[k][q] = __ballot(pb[i1] < pb[i2]);
+            // rows and columns + 19 lie in 0 .. 38 (the pattern stays inside the 39 x 39 patch under every rotation).  The products and the add / sub are the
+            // reference's, one rounding each; rounding to the integer is one more float add, and the conversion, both + 19 and the patch's LDS address are one
+            // constant behind one 24-bit multiply-add (describe_brief_index.h: 6 instructions per point where v_rndne + v_cvt per coordinate made it 11)
+            const uint32_t r1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, sa[k]), __fmul_rn(y1, ca[k])));
+            const uint32_t c1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, ca[k]), __fmul_rn(y1, nsa[k])));
+            const uint32_t r2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, sa[k]), __fmul_rn(y2, ca[k])));
+            const uint32_t c2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, ca[k]), __fmul_rn(y2, nsa[k])));
+            const uint32_t i1 = describe_brief_index::index_from_bits(r1, c1, pbase[k]), i2 = describe_brief_index::index_from_bits(r2, c2, pbase[k]);
+            bits[k][q] = __ballot(*(const lds_u8_t *)(uintptr_t)i1 < *(const lds_u8_t *)(uintptr_t)i2);
         }
     }
 #pragma unroll

@@ -66,6 +66,24 @@ __global__ __launch_bounds__(256) void k_pk_mul_f32(uint32_t *out, int n, long l
     out[blockIdx.x * 256 + threadIdx.x] = (uint32_t)(s ^ (s >> 32));
     if (threadIdx.x == 0 && blockIdx.x == 0) cyc[0] = t1 - t0;
 }
+// k_resize's row addresses before they became scalar: the 64-bit multiply-add (row * pitch + lane offset, one per row load and store) and the 64-bit add
+// that is left on its stores; a register pair per chain, the carry-out of the multiply-add goes to vcc
+#define DEF64(NAME, ASM)                                                                                 \
+__global__ __launch_bounds__(256) void NAME(uint32_t *out, int n, long long *cyc) {                      \
+    uint64_t v[CHAINS]; uint32_t b = threadIdx.x * 2654435761u | 1u;                                     \
+    for (int k = 0; k < CHAINS; ++k) v[k] = (uint64_t)(threadIdx.x + k * 977u) * 0x100000001ull;         \
+    const long long t0 = clock64();                                                                      \
+    for (int i = 0; i < n; ++i) {                                                                        \
+        _Pragma("unroll") for (int k = 0; k < CHAINS; ++k) asm volatile(ASM : "+v"(v[k]) : "v"(b) : "vcc"); \
+    }                                                                                                    \
+    const long long t1 = clock64();                                                                      \
+    uint64_t s = 0; for (int k = 0; k < CHAINS; ++k) s ^= v[k];                                          \
+    out[blockIdx.x * 256 + threadIdx.x] = (uint32_t)(s ^ (s >> 32));                                     \
+    if (threadIdx.x == 0 && blockIdx.x == 0) cyc[0] = t1 - t0;                                           \
+}
+DEF64(k_mad_i64_i32,  "v_mad_i64_i32 %0, vcc, %1, %1, %0")
+DEF64(k_mad_u64_u32,  "v_mad_u64_u32 %0, vcc, %1, %1, %0")
+DEF64(k_lshl_add_u64, "v_lshl_add_u64 %0, %0, 0, %0")
 template <class K> void run(const char *name, K kern, uint32_t *d_out, long long *d_cyc) {
     const int n = 20000;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
@@ -85,6 +103,8 @@ int main() {
     R(k_seq_mul_f32_x2);
     std::printf("one packed instruction (two products):\n");
     R(k_pk_mul_f32);
+    std::printf("64-bit address arithmetic (a register pair per operand):\n");
+    R(k_mad_i64_i32); R(k_mad_u64_u32); R(k_lshl_add_u64);
     std::printf("integer sequences (per SEQUENCE):\n");
     R(k_seq_shift_mul); R(k_seq_sdwa_mul); R(k_seq_sdwa_mul_s); R(k_seq_mul_s); R(k_seq_add_sdwa); R(k_seq_add_add);
     return 0;
