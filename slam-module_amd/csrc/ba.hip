@@ -35,6 +35,7 @@
 #include <thread>
 #include <type_traits>
 #include <utility>
+#include "ms_lanes_f64.h"
 
 #define g_ba_host_allocs g_ms_host_allocs      // (the library-wide counter of ms_internal.h)
 
@@ -293,22 +294,6 @@ __device__ void pose_edge(const double *Ti, const double *Tj, const double *M, d
     se3_adj(C, Jj);
     for (int i = 0; i < 36; ++i) Jj[i] = -Jj[i];
 }
-__device__ __forceinline__ void huber(double chi2, double delta, double &rho0, double &w) {
-    const double dsqr = delta * delta;
-    if (delta <= 0 || chi2 <= dsqr) { rho0 = chi2; w = 1; }
-    else { const double s = sqrt(chi2); rho0 = 2 * s * delta - dsqr; w = delta / s; }
-}
-
-// 1 / sqrt(d) for the pivots of the small Cholesky factorisations: v_rsq_f64 and two Newton steps (one cubic, one quadratic: full double precision) -- ~10
-// instructions where sqrt and a division are ~60 on the solver's critical path
-__device__ __forceinline__ double rsqrt_d(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    double e = fma(-d * y, y, 1.0);
-    y = fma(y * e, fma(e, 0.375, 0.5), y);
-    e = fma(-d * y, y, 1.0);
-    return fma(y * e, 0.5, y);
-}
-
 // 144-byte (18 double) per-observation records are moved as nine 16-byte pieces: a lane's record sits in its own cache
 // lines, so the vector-memory cost is per instruction, not per byte
 __device__ __forceinline__ void load18(const double *p, double *v) {
@@ -2930,1753 +2915,17 @@ __global__ __launch_bounds__(NT) void k_ba_lm(const BaProb *probs, int team, con
     }
 }
 
-// ---------------------------------------------------------------- pose-only problems: poseBundleAdjust (bundle_adjuster.cpp:396-491)
-// ONE free pose, every point fixed: the projection edges of the current frame (+ the odometry edge to the fixed previous keyframe, :440-447) give a 6 x 6
-// system per trial.  The general kernel walks such a problem through ~20 phases with a workgroup barrier and a round trip to memory each (0.47 ms for
-// 12 iterations of a 6-dof problem -- and poseBundleAdjust runs on EVERY non-keyframe, mapper_helpers.cpp:1043-1050); here a 256-thread workgroup keeps
-// the trial in registers: one sweep over the observations accumulates H (21 entries), b and the robust chi2 per thread, one reduction, lane 0 factors the
-// 6 x 6 matrix, one more sweep gives the chi2 of the moved pose.  Same LM schedule, same arithmetic per edge as k_ba_lm.
-// Round 4: the stamps showed 45 % of the kernel in its reductions (28 sums x 6 ds_bpermute steps, three barriers per sweep), 20 % in the observations and 18 % in
-// the one SE3 edge's logarithm on the thread that also had the most observations -- and two sweeps per iteration where one is enough:
-//   * every sweep linearises.  The trial's sweep at the moved pose already holds H and b of the NEXT iteration when the trial is accepted (g2o linearises the
-//     same state again, optimizable_graph / sparse_optimizer computeActiveErrors + linearizeSystem), and a rejected trial keeps the old H, b in registers: 1 + trials
-//     sweeps instead of 2 + iterations + trials, and the per-observation chi2 of the accepted state stays in registers, so the closing sweep goes too;
-//   * the 28 sums go through LDS transposed: every thread writes its 28 partial sums (value-major rows of PO_ROW doubles), 8 lanes per value add 32 entries each
-//     and meet over the DPP network (3 steps): two barriers, ~100 instructions;
-//   * waves 0-2 take the observations (PO_K per thread in registers), wave 3 takes the SE3 edges, so the logarithm runs beside the observations.  One wave per
-//     SIMD: the whole 512-register file is each wave's (a 512-thread version, two waves per SIMD, spilled ~200 dwords per trial and was no faster than round 3's).
-constexpr int PO_NT = 256, PO_OT = 192, PO_K = 8, PO_MAXE = 8, PO_NV = 28;       // threads; threads with observations; observations a thread keeps in registers; SE3 edges; sums per sweep
-constexpr int PO_ROW = PO_NT + 8;                            // row stride (doubles) of the transposed partial sums: 8 mod 32, so the 8 values x 8 parts a wave reads spread over all banks
-constexpr size_t kPoLdsBytes = (size_t)PO_NV * PO_ROW * sizeof(double);
-static_assert(8 * PO_NV <= PO_NT, "stage 2 of the reduction: 8 lanes per sum");
-template <int CTRL> __device__ __forceinline__ double dpp_d(double v) {               // the double of the lane the DPP control names (all source lanes active)
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false), hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// The SE3 edges of a problem with ONE free pose (k_ba_pose_only, k_ba_one_pose), once per solve, by ONE wave (all its lanes): an edge between fixed poses is a constant chi2
-// (returned: every lane's share); one that touches
-// the free pose leaves its fixed side's transform, G = -J^T W and J^T W J = -G J in LDS.  Only the free side's Jacobian is formed (Ji = adj(Tj^-1 M) or
-// Jj = -adj(Ti^-1 M^-1): no logarithm), and the two 6 x 6 products are spread over the lanes -- as the work of one thread (two Jacobians in scratch, 970 dependent
-// multiply-adds) this was 44 k cycles, a third of the whole kernel.
-__device__ __noinline__ double po_edges_setup(const BaProb &P, int pi, int lane, int *s_ne, int *s_eSide, double *s_eC, double *s_eM, double *s_eG, double *s_eW, double *s_Hc, double *s_J) {
-    double cacc = 0;
-    int ne = 0;
-    for (int k = lane; k < P.n_edge; k += 64) {                             // the edges between fixed poses (a window's stage 1 has ~50): one per lane
-        const int vi = P.edge_i[k], vj = P.edge_j[k];
-        if (vi == pi || vj == pi) continue;
-        const double *W = P.edge_info + 36 * (size_t)k;
-        double e[6];
-        pose_edge(P.pose0 + 7 * (size_t)vi, P.pose0 + 7 * (size_t)vj, P.edge_meas + 7 * (size_t)k, e, nullptr, nullptr, false);
-        for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) cacc += e[i] * W[6 * i + j] * e[j];
-    }
-    // the edges of the free pose: found 64 at a time (a ballot over the lanes' edges -- a scan with one dependent load per edge was 35 us for a window's 50 edges), then
-    // taken by the wave together
-    for (int k0 = 0; k0 < P.n_edge; k0 += 64) {
-      const int kl = k0 + lane;
-      unsigned long long touching = __ballot(kl < P.n_edge && (P.edge_i[kl] == pi || P.edge_j[kl] == pi));
-      while (touching) {
-        const int k = k0 + __builtin_ctzll(touching);
-        touching &= touching - 1;
-        const int vi = P.edge_i[k], vj = P.edge_j[k];
-        const double *W = P.edge_info + 36 * (size_t)k, *M = P.edge_meas + 7 * (size_t)k, *Ti = P.pose0 + 7 * (size_t)vi, *Tj = P.pose0 + 7 * (size_t)vj;
-        const int sl = ne++, side = vi == pi ? 0 : 1;
-        double C7[7], J[36];
-        if (side == 0) { double Tjinv[7]; se3_inv(Tj, Tjinv); se3_mul(Tjinv, M, C7); se3_adj(C7, J); }
-        else { double Tiinv[7], Minv[7]; se3_inv(Ti, Tiinv); se3_inv(M, Minv); se3_mul(Tiinv, Minv, C7); se3_adj(C7, J); for (int i = 0; i < 36; ++i) J[i] = -J[i]; }
-        if (lane == 0) {
-            s_eSide[sl] = side;
-            if (side == 0) for (int i = 0; i < 7; ++i) s_eC[8 * sl + i] = C7[i];
-            else for (int i = 0; i < 7; ++i) { s_eC[8 * sl + i] = Ti[i]; s_eM[8 * sl + i] = M[i]; }
-            for (int i = 0; i < 36; ++i) s_J[i] = J[i];
-        }
-        if (lane < 36) s_eW[36 * sl + lane] = W[lane];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (lane < 36) {                                                    // G = -J^T W
-            const int a2 = lane / 6, c = lane % 6;
-            double v = 0;
-            for (int r2 = 0; r2 < 6; ++r2) v += s_J[6 * r2 + a2] * s_eW[36 * sl + 6 * r2 + c];
-            s_eG[36 * sl + lane] = -v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (lane < 21) {                                                    // J^T W J = -G J packed by (a <= b) at a (11 - a) / 2 + b; the value is entry (b, a), the LOWER
-            int a2 = 0, rest = lane;                                        // triangle -- the one the general kernel's Cholesky and the oracle read: it matters for a W that
-            while (rest >= 6 - a2) { rest -= 6 - a2; ++a2; }                // is not symmetric (mi355slam.h: W is taken as given)
-            const int b2 = a2 + rest;
-            double v = 0;
-            for (int c = 0; c < 6; ++c) v += s_eG[36 * sl + 6 * b2 + c] * s_J[6 * c + a2];
-            s_Hc[lane] -= v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-      }
-    }
-    if (lane == 0) *s_ne = ne;
-    return cacc;
-}
-
-__global__ __launch_bounds__(PO_NT) void k_ba_pose_only(const BaProb *probs) {
-    extern __shared__ __attribute__((aligned(16))) double po_red[];         // [PO_NV][PO_ROW]
-    __shared__ __attribute__((aligned(16))) double s_sum[2][32];       // the sums of the last two sweeps: [cur] belongs to the accepted state (its H and b), the other to the trial
-    __shared__ double s_eC[PO_MAXE][8], s_eM[PO_MAXE][8], s_eG[PO_MAXE][36], s_eW[PO_MAXE][36], s_Hc[24], s_const;
-    __shared__ int s_eSide[PO_MAXE], s_ne, s_any;
-    __shared__ double s_J[36];
-    const long long t_kernel = clock64();
-    const BaProb &P = probs[blockIdx.x];
-    const int tid = threadIdx.x, pi = P.free2pose[0];
-    // the block ms_ba_download fetches -- [16 stats][7 n_pose poses][3 n_point points][n_obs chi2] -- is filled as the values arise (a single problem: BaProb::pack)
-    MS_GLOBAL double *pk = (MS_GLOBAL double *)uglobal(P.pack);
-    MS_GLOBAL double *pk_pose = pk + 16, *pk_point = pk_pose + 7 * P.n_pose, *pk_chi2 = pk_point + 3 * P.n_point;
-    for (int i = tid; i < 7 * P.n_pose; i += PO_NT) { const double v = P.pose0[i]; P.pose[i] = v; if (pk) pk_pose[i] = v; }
-    for (int i = tid; i < 3 * P.n_point; i += PO_NT) { const double v = P.point0[i]; P.point[i] = v; if (pk) pk_point[i] = v; }
-    if (tid < 24) s_Hc[tid] = 0;
-    if (tid == 0) { s_ne = 0; s_const = 0; s_any = P.n_obs; }
-    __syncthreads();
-    {   // the first observation of the free pose
-        int mine = P.n_obs;
-        for (int o = tid; o < P.n_obs; o += PO_NT) if (P.obs_pose[o] == pi) { mine = o; break; }
-        if (mine < P.n_obs) atomicMin(&s_any, mine);
-    }
-    __syncthreads();
-    double pose[7];
-#pragma unroll
-    for (int a = 0; a < 7; ++a) pose[a] = P.pose0[7 * (size_t)pi + a];
-    // ---- what never changes: the observations of the free pose go into registers (PO_K per thread of waves 0-2), the others' chi2 and the edges between fixed
-    //      poses into one constant; an edge that touches the free pose leaves its fixed side's transform, -J^T W and J^T W J in LDS (its Jacobian does not depend
-    //      on the free pose: Ji = adj(Tj^-1 M), Jj = -adj(Ti^-1 M^-1)), so a sweep only takes its logarithm
-    double X[PO_K][3], uv[PO_K][2], info[PO_K], c2[PO_K], c2t[PO_K], cacc = 0;
-    unsigned have = 0;
-    const int o_any = s_any;                                                // an observation of the free pose (n_obs: there is none)
-    double Xd[3] = {0, 0, 1}, uvd[2] = {0, 0};
-    if (o_any < P.n_obs) {
-        const int l = P.obs_point[o_any];
-        Xd[0] = P.point0[3 * (size_t)l]; Xd[1] = P.point0[3 * (size_t)l + 1]; Xd[2] = P.point0[3 * (size_t)l + 2];
-        uvd[0] = P.obs_uv[2 * (size_t)o_any]; uvd[1] = P.obs_uv[2 * (size_t)o_any + 1];
-    }
-#pragma unroll
-    for (int j = 0; j < PO_K; ++j) {
-        const int o = tid + PO_OT * j;
-        X[j][0] = Xd[0]; X[j][1] = Xd[1]; X[j][2] = Xd[2]; uv[j][0] = uvd[0]; uv[j][1] = uvd[1]; info[j] = c2[j] = c2t[j] = 0;
-        if (tid < PO_OT && o < P.n_obs) {
-            const int po = P.obs_pose[o], l = P.obs_point[o];
-            if (po == pi) {
-                have |= 1u << j;
-                X[j][0] = P.point0[3 * (size_t)l]; X[j][1] = P.point0[3 * (size_t)l + 1]; X[j][2] = P.point0[3 * (size_t)l + 2];
-                uv[j][0] = P.obs_uv[2 * (size_t)o]; uv[j][1] = P.obs_uv[2 * (size_t)o + 1]; info[j] = P.obs_info[o];
-            }
-        }
-    }
-    // slots this wave sweeps: observation tid + PO_OT j exists for j < (n_obs - tid) / PO_OT, most for the wave's first lane (wave 3, the edges' wave, and a problem
-    // without observations of the free pose: none)
-    const int w0 = __builtin_amdgcn_readfirstlane(tid & ~63);
-    const int jn = (w0 < PO_OT && o_any < P.n_obs && P.n_obs > w0) ? min(PO_K, (P.n_obs - w0 + PO_OT - 1) / PO_OT) : 0;
-    for (int o = tid; o < P.n_obs; o += PO_NT) {                            // observations from FIXED poses: constant
-        const int po = P.obs_pose[o];
-        if (po == pi) continue;
-        double e[2], r, w;
-        proj_edge<false>(P.pose0 + 7 * (size_t)po, P.point0 + 3 * (size_t)P.obs_point[o], P.obs_uv + 2 * (size_t)o, e, nullptr, nullptr);
-        const double chi2 = P.obs_info[o] * (e[0] * e[0] + e[1] * e[1]);
-        huber(chi2, P.huber, r, w);
-        P.chi2_obs[o] = chi2;
-        if (pk) pk_chi2[o] = chi2;
-        cacc += r;
-    }
-    if (tid >= PO_OT) cacc += po_edges_setup(P, pi, tid - PO_OT, &s_ne, s_eSide, &s_eC[0][0], &s_eM[0][0], &s_eG[0][0], &s_eW[0][0], s_Hc, s_J);   // (wave 3, beside the observation loads)
-    cacc = wave_sum_d(cacc);
-    if ((tid & 63) == 0) lds_addd((MS_LDS double *)&s_const, cacc);
-    __syncthreads();
-    const int ne = s_ne;
-    const bool overflow = P.n_obs > PO_OT * PO_K;                           // more observations than the registers take: those come from memory in every sweep
-    const long long t_begin = clock64();
-    int cur = 1;                                                            // which half of s_sum belongs to the accepted state
-    // ---- one sweep over the free pose's edges at `pose`: the robust chi2 (returned), the upper triangle of H and b (left in s_sum[1 - cur][0 .. 27)), the chi2 per observation in c2t
-    auto sweep = [&]() {
-        double A[21], g[6], acc = 0;
-#pragma unroll
-        for (int a = 0; a < 21; ++a) A[a] = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) g[a] = 0;
-        auto one = [&](const double *Xo, const double *uvo, double inf) {
-            double e[2], Jp[12], Jl[6];
-            proj_edge<true>(pose, Xo, uvo, e, Jp, Jl);
-            const double chi2 = inf * (e[0] * e[0] + e[1] * e[1]);
-            double r, w;
-            huber(chi2, P.huber, r, w);
-            acc += r;
-            const double wi = w * inf;
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                g[a] += -(Jp[a] * e[0] + Jp[6 + a] * e[1]) * wi;
-#pragma unroll
-                for (int b2 = a; b2 < 6; ++b2) A[k++] += wi * (Jp[a] * Jp[b2] + Jp[6 + a] * Jp[6 + b2]);
-            }
-            return chi2;
-        };
-        // slots in pairs, both evaluations in one basic block so that the scheduler interleaves their chains (a lone wave per SIMD has nothing else to hide the
-        // fp64 latency with); a slot without an observation holds a copy of a real one with information 0: finite arithmetic, nothing added
-#pragma unroll
-        for (int j = 0; j < PO_K; j += 2) {
-            if (j + 1 < jn) { c2t[j] = one(X[j], uv[j], info[j]); c2t[j + 1] = one(X[j + 1], uv[j + 1], info[j + 1]); }
-            else if (j < jn) c2t[j] = one(X[j], uv[j], info[j]);
-        }
-        if (overflow && tid < PO_OT)
-            for (int o = tid + PO_OT * PO_K; o < P.n_obs; o += PO_OT) {
-                if (P.obs_pose[o] != pi) continue;
-                const double Xo[3] = {P.point0[3 * (size_t)P.obs_point[o]], P.point0[3 * (size_t)P.obs_point[o] + 1], P.point0[3 * (size_t)P.obs_point[o] + 2]};
-                const double uvo[2] = {P.obs_uv[2 * (size_t)o], P.obs_uv[2 * (size_t)o + 1]};
-                (void)one(Xo, uvo, P.obs_info[o]);
-            }
-        if (tid >= PO_OT && tid - PO_OT < ne) {                             // wave 3: the SE3 edges of the free pose
-            const int k = tid - PO_OT;
-            double Bm[7], e[6], We[6];
-            if (s_eSide[k] == 0) se3_mul(s_eC[k], pose, Bm);                                      // (Tj^-1 M) Ti
-            else { double Tjinv[7], A2[7]; se3_inv(pose, Tjinv); se3_mul(Tjinv, s_eM[k], A2); se3_mul(A2, s_eC[k], Bm); }
-            se3_log(Bm, e);
-            for (int i = 0; i < 6; ++i) { double v = 0; for (int j = 0; j < 6; ++j) v += s_eW[k][6 * i + j] * e[j]; We[i] = v; }
-            for (int i = 0; i < 6; ++i) acc += e[i] * We[i];
-            for (int a = 0; a < 6; ++a) { double v = 0; for (int c = 0; c < 6; ++c) v += s_eG[k][6 * a + c] * e[c]; g[a] += v; }
-        }
-        {
-            MS_LDS double *row = (MS_LDS double *)po_red + tid;
-#pragma unroll
-            for (int a = 0; a < 21; ++a) row[a * PO_ROW] = A[a];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) row[(21 + a) * PO_ROW] = g[a];
-            row[27 * PO_ROW] = acc;
-        }
-        __syncthreads();
-        if (tid < 8 * PO_NV) {                                              // lanes 8 v .. 8 v + 7 add row v up, each 32 entries, then among themselves
-            const int v = tid >> 3, part = tid & 7;
-            const MS_LDS double *row = (const MS_LDS double *)po_red + v * PO_ROW + part;
-            double s0 = 0, s1 = 0;
-#pragma unroll
-            for (int k = 0; k < PO_NT / 8; k += 2) { s0 += row[8 * k]; s1 += row[8 * k + 8]; }
-            double s = s0 + s1;
-            s += dpp_d<0xB1>(s);                                            // quad_perm [1 0 3 2]
-            s += dpp_d<0x4E>(s);                                            // quad_perm [2 3 0 1]
-            s += dpp_d<0x141>(s);                                           // row_half_mirror
-            if (part == 0) s_sum[1 - cur][v] = s + (v < 21 ? s_Hc[v] : (v == 27 ? s_const : 0.0));
-        }
-        __syncthreads();
-        return s_sum[1 - cur][27];
-    };
-    double lambda = 0, ni = 2;
-    int it = 0, trials = 0, stop = 0;
-    auto accept = [&]() {                                                   // the swept state becomes the current one: its H, b (the other half of s_sum) and per-observation chi2
-        cur = 1 - cur;
-#pragma unroll
-        for (int j = 0; j < PO_K; ++j) c2[j] = c2t[j];
-    };
-    const double chi2_init = sweep();
-    accept();
-    double chi2_carried = chi2_init;
-    for (it = 0; it < P.max_iters; ++it) {
-        double current = chi2_carried, temp = current;
-        if (it == 0) {                                                       // computeLambdaInit: 1e-5 x the largest diagonal entry
-            const double *H = s_sum[cur];
-            const double md = fmax(fmax(fmax(fabs(H[0]), fabs(H[6])), fmax(fabs(H[11]), fabs(H[15]))), fmax(fabs(H[18]), fabs(H[20])));
-            lambda = 1e-5 * md; ni = 2;
-        }
-        double rho = 0;
-        int qmax = 0;
-        do {
-            // (H + lambda I) dp = b: Cholesky of the 6 x 6 matrix, by every thread for itself (fully unrolled: 21 + 6 registers, ~150 dependent operations --
-            // cheaper than one thread doing it behind a barrier and a trip through LDS)
-            double Lm[21], dpv[6], b[6];                                     // lower triangle, row-major: Lm[i (i + 1) / 2 + j]
-            bool ok2 = true;
-            const double *H = s_sum[cur];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) b[a] = H[21 + a];
-            {
-                int k = 0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int c = a; c < 6; ++c) { Lm[c * (c + 1) / 2 + a] = H[k] + (a == c ? lambda : 0.0); ++k; }
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                double d = Lm[j * (j + 1) / 2 + j];
-#pragma unroll
-                for (int k = 0; k < j; ++k) d -= Lm[j * (j + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-                if (!(d > 0) || !isfinite(d)) ok2 = false;
-                const double inv = rsqrt_d(d);
-                Lm[j * (j + 1) / 2 + j] = inv;                               // the reciprocal pivot is what the substitutions use
-#pragma unroll
-                for (int i = j + 1; i < 6; ++i) {
-                    double v = Lm[i * (i + 1) / 2 + j];
-#pragma unroll
-                    for (int k = 0; k < j; ++k) v -= Lm[i * (i + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-                    Lm[i * (i + 1) / 2 + j] = v * inv;
-                }
-            }
-            {
-                double y[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    double v = b[i];
-#pragma unroll
-                    for (int k = 0; k < i; ++k) v -= Lm[i * (i + 1) / 2 + k] * y[k];
-                    y[i] = v * Lm[i * (i + 1) / 2 + i];
-                }
-#pragma unroll
-                for (int i = 5; i >= 0; --i) {
-                    double v = y[i];
-#pragma unroll
-                    for (int k = i + 1; k < 6; ++k) v -= Lm[k * (k + 1) / 2 + i] * dpv[k];
-                    dpv[i] = v * Lm[i * (i + 1) / 2 + i];
-                }
-            }
-            double bk[7], sc = 0;
-#pragma unroll
-            for (int a = 0; a < 7; ++a) bk[a] = pose[a];                                    // push()
-            if (ok2) {
-                double dp[6], ex[7];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) { dp[a] = dpv[a]; sc += dp[a] * (lambda * dp[a] + b[a]); }
-                se3_exp(dp, ex);
-                se3_mul(ex, bk, pose);                                                      // every thread moves its own copy of the pose: the same arithmetic, the same result
-                temp = sweep();
-            } else temp = DBL_MAX;
-            const double scale = sc + 1e-3;
-            rho = (current - temp) / scale;
-            if (trials < P.debug_reject) rho = -1.0;                // (test hook: drives the ten-rejections Terminate path)
-            if (rho > 0 && isfinite(temp)) {
-                const double t3 = 2 * rho - 1;
-                double alpha = 1. - t3 * t3 * t3;                                          // (pow(x, 3) of the reference to an ulp or two, without the ~300 instructions of pow)
-                alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha);
-                ni = 2; current = temp; chi2_carried = temp;
-                accept();                                                                   // (the trial's half of s_sum becomes the current one; the next sweep writes the other, behind its first barrier)
-            } else {
-                lambda *= ni; ni *= 2;
-#pragma unroll
-                for (int a = 0; a < 7; ++a) pose[a] = bk[a];                                // pop()
-                if (!isfinite(lambda)) break;
-            }
-            ++qmax; ++trials;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0 || !isfinite(lambda)) { stop = 1; ++it; break; }
-    }
-    // the chi2 per observation of the accepted state: from the registers; the observations beyond them are evaluated once more
-#pragma unroll
-    for (int j = 0; j < PO_K; ++j) if ((have >> j) & 1u) { P.chi2_obs[tid + PO_OT * j] = c2[j]; if (pk) pk_chi2[tid + PO_OT * j] = c2[j]; }
-    if (overflow && tid < PO_OT)
-        for (int o = tid + PO_OT * PO_K; o < P.n_obs; o += PO_OT) {
-            if (P.obs_pose[o] != pi) continue;
-            double e[2], Jp[12], Jl[6];
-            proj_edge<true>(pose, P.point0 + 3 * (size_t)P.obs_point[o], P.obs_uv + 2 * (size_t)o, e, Jp, Jl);     // (the arithmetic of the sweeps)
-            P.chi2_obs[o] = P.obs_info[o] * (e[0] * e[0] + e[1] * e[1]);
-            if (pk) pk_chi2[o] = P.chi2_obs[o];
-        }
-    const double chi2_final = chi2_carried;                                 // the sweep that was accepted last evaluated exactly this state
-    if (tid == PO_OT) { P.stats[9] = 0.0; if (pk) pk[9] = 0.0; }
-    if (tid == 0) {
-        // [8 .. 12] are zero ([9] is written by thread PO_OT, above); [13], [14]: cycles of the iterations and of what came before them
-        const double st[16] = {(double)it, (double)trials, (double)stop, lambda, chi2_init, chi2_final, isfinite(chi2_final) ? 1.0 : 0.0, 0.0,
-                               0.0, 0.0, 0.0, 0.0, 0.0, (double)(clock64() - t_begin), (double)(t_begin - t_kernel), 0.0};
-        for (int a = 0; a < 7; ++a) { P.pose[7 * (size_t)pi + a] = pose[a]; if (pk) pk_pose[7 * (size_t)pi + a] = pose[a]; }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) if (q != 9) { P.stats[q] = st[q]; if (pk) pk[q] = st[q]; }
-    }
-}
-
-
-// ---------------------------------------------------------------- one free pose + free points: stage 1 of localBundleAdjust (bundle_adjuster.cpp:251-252, :268, :322-333)
-// ONE free keyframe, every other keyframe fixed, the map points free: the reduced camera system is 6 x 6 whatever the window's size.  The general kernel
-// still walked it through its whole machinery (pass sets, LDS tile, windowed Cholesky of one block, ~7 team barriers per damped solve): 0.60 ms for the
-// 8 iterations of a C4 window on 32 workgroups, 3.3 ms for 256 such windows with one workgroup each.  Here a point belongs to a GROUP of G = 1 .. 8
-// neighbouring lanes (G chosen so that the launch's lanes cover the points): the group's lanes share the point's observations out, their sums meet over
-// the DPP network.  With a lane group per point (ONE: a single window on a team) the point -- position, Hll, bl, W = sum of Jp^T w Jl over its observations
-// in the free keyframe -- stays in the group's REGISTERS from the first linearisation to the last trial; a batch (one workgroup per window, several points
-// per group) keeps these records in memory that only the owning workgroup touches.  Per iteration: linearise, and in the same pass every group forms its
-// point's W (Hll + lambda I)^-1 W^T and W (Hll + lambda I)^-1 bl (3 x 3 Cholesky, as in schur_fused).  Only ~1 point in 4 is seen by the free keyframe, so
-// these 27-value contributions are SPARSE: the contributing lanes write them side by side into the wave's LDS slab, the wave adds the entries up and issues
-// one atomic per value (27 uniform-address atomics per observation cost a wave reduction each: 5 x the time of everything else).  ONE reduction over the
-// team, the 6 x 6 Cholesky in every thread (as in k_ba_pose_only), then each group back-substitutes its point, moves it, and evaluates the robust chi2 of
-// its observations at the trial state; a second reduction (chi2, gain denominator) decides.  Trial points are separate from the accepted ones: no backup /
-// restore pass.  Observation data comes from copies sorted by point (pose index, u, v, information side by side: one round trip instead of three dependent
-// ones), the poses from an LDS table.  Same LM schedule and the same arithmetic per edge as k_ba_lm.
-constexpr int OP_NT = 512, OP_NW = OP_NT / 64, OP_NV = 64, OP_MAX_LDS_POSES = 512;
-constexpr int OP_S0 = 32, OP_BAD = 59, OP_MAX = 63;          // accumulators: 0..20 Hpp, 21..26 bp | 32..52 Schur matrix terms, 53..58 rhs terms, 59 unsound point blocks | 63 largest diagonal entry
-__host__ __device__ constexpr int op_slab_cap(int lgG) { return lgG == 0 ? 64 : 32; }     // entries of a wave's staging slab
-constexpr size_t kOpLdsBytes = (((size_t)7 * OP_MAX_LDS_POSES + 2) + (size_t)OP_NW * 27 * 64) * sizeof(double);     // dynamic LDS at most: the pose table + the slabs (136 KB; ~11 KB are static)
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_move_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// sum over a group of 2^lg neighbouring lanes (aligned), the result in every lane of the group: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
-__device__ __forceinline__ double group_sum_d(double v, int lg) {
-    if (lg >= 1) v += dpp_move_d<0xB1>(v);
-    if (lg >= 2) v += dpp_move_d<0x4E>(v);
-    if (lg >= 3) v += dpp_move_d<0x141>(v);
-    return v;
-}
-__device__ __forceinline__ int group_sum_i(int v, int lg) {
-    if (lg >= 1) v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);
-    if (lg >= 2) v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);
-    if (lg >= 3) v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);
-    return v;
-}
-
-// Hll + lambda I = L L^T (3 x 3, packed 00 01 02 11 12 22); returns false when a pivot is not positive
-struct Chol3 { double i11, l21, l31, i22, l32, i33; };
-__device__ __forceinline__ bool chol3(const double *H, double lambda, Chol3 &c) {
-    const double a = H[0] + lambda, d = H[3] + lambda, f = H[5] + lambda;
-    c.i11 = rsqrt_d(a); c.l21 = H[1] * c.i11; c.l31 = H[2] * c.i11;
-    const double d2 = d - c.l21 * c.l21;
-    c.i22 = rsqrt_d(d2); c.l32 = (H[4] - c.l31 * c.l21) * c.i22;
-    const double d3 = f - c.l31 * c.l31 - c.l32 * c.l32;
-    c.i33 = rsqrt_d(d3);
-    return a > 0 && d2 > 0 && d3 > 0 && isfinite(c.i11 * c.i22 * c.i33);
-}
-
-// Sparse sums: a few lanes of a wave hold 27 values each whose sums go into acc[0 .. 27).  The contributors write their values side by side into the wave's
-// slab ([27][cap], value-major: neighbouring entries in neighbouring banks; entry = a running index over the wave's contributors), then the wave adds the
-// entries up -- value k by lanes 2k and 2k + 1 (even / odd entries) -- and issues one atomic per value.  A contributor beyond the slab's capacity adds its
-// values with plain atomics.
-__device__ __forceinline__ void slab_put(MS_LDS double *slab, int cap, MS_LDS double *acc, int idx, const double (&v)[27]) {
-    if (idx < cap) {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) slab[k * cap + idx] = v[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 27; ++k) lds_addd(acc + k, v[k]);
-    }
-}
-__device__ __forceinline__ void slab_sum(MS_LDS double *slab, int cap, MS_LDS double *acc, int n, int lane) {      // wave-uniform call, n wave-uniform
-    if (n == 0) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int ns = min(n, cap);
-    if (lane < 54) {
-        const int k = lane >> 1;
-        double t = 0;
-        for (int e = lane & 1; e < ns; e += 2) t += slab[k * cap + e];
-        t += dpp_move_d<0xB1>(t);
-        if ((lane & 1) == 0) lds_addd(acc + k, t);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ int lanes_below(unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
-
-struct OpPoint { double X[3], H[6], bl[3], W[18]; int nf, i0, i1; bool pfree; };       // nf: the point's observations in the free keyframe (group total)
-
-template <bool ONE>     // ONE: the launch has a lane group per point -- the point's record lives in registers for the whole solve
-__global__ __launch_bounds__(OP_NT) void k_ba_one_pose(const BaProb *probs, int team, int lgG, int pose_doubles) {
-    extern __shared__ __attribute__((aligned(16))) double op_lds[];      // [7 n_pose] the poses (when they fit), then the waves' staging slabs [8][27][cap]
-    __shared__ double s_acc[OP_NV], s_sum[OP_NV], s_w[OP_NW * 2], s_part[OP_NW * OP_NV];
-    __shared__ double s_eC[PO_MAXE][8], s_eM[PO_MAXE][8], s_eG[PO_MAXE][36], s_eW[PO_MAXE][36], s_Hc[24], s_const;
-    __shared__ int s_eSide[PO_MAXE], s_ne;
-    __shared__ double s_J[36];
-    const long long t_kernel = clock64();
-    const BaProb &P = probs[blockIdx.x / (unsigned)team];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, rank = team > 1 ? (int)(blockIdx.x % (unsigned)team) : 0;
-    const int G = 1 << lgG, gl = rank * OP_NT + tid, sub = gl & (G - 1), slot = gl >> lgG, nslot = (team * OP_NT) >> lgG;
-    const int pi = P.free2pose[0], n_point = P.n_point, cap = op_slab_cap(lgG);
-    const bool lds_poses = pose_doubles > 0;                              // (the host's decision for the whole launch: every problem's poses fit the table then)
-    MS_LDS double *slab = (MS_LDS double *)op_lds + pose_doubles + wave * 27 * cap;
-    MS_LDS double *acc = (MS_LDS double *)s_acc;
-    const MS_GLOBAL int32_t *o_pose = (const MS_GLOBAL int32_t *)P.op_pose, *o_idx = (const MS_GLOBAL int32_t *)P.op_o, *pt_start = (const MS_GLOBAL int32_t *)P.pt_start;
-    const MS_GLOBAL double *o_uvi = (const MS_GLOBAL double *)P.op_uvi;
-    MS_GLOBAL double *rec = (MS_GLOBAL double *)P.op_rec;                 // (not ONE) [28][n_point]: Hll 0-5, bl 6-8, W 9-26, 27 = observations in the free keyframe, -1 for a fixed point
-    MS_GLOBAL double *point = (MS_GLOBAL double *)P.point, *trial = (MS_GLOBAL double *)P.point_bk;
-    const MS_GLOBAL uint8_t *pfix = (const MS_GLOBAL uint8_t *)P.point_fixed;
-    const int nrounds = ONE ? 1 : (n_point + nslot - 1) / nslot;
-    int seq = 0;
-    // (the free pose's seven entries are written ONCE, at the end, by the launch's first lane: the team's barriers carry no cache maintenance, and two workgroups on
-    //  different XCDs writing the same line -- one here, one at the end -- would leave the order of the two write-backs to chance)
-    for (int i = gl; i < 7 * P.n_pose; i += team * OP_NT) if (i / 7 != pi) P.pose[i] = P.pose0[i];
-    if (lds_poses) for (int i = tid; i < 7 * P.n_pose; i += OP_NT) op_lds[i] = P.pose0[i];
-    OpPoint ps;
-    double Xt[3] = {0, 0, 0};                                             // ONE: the trial point
-    auto point_begin = [&](int l, bool from_point0) {                     // the point's observation range, its flag and its position
-        ps.i0 = ps.i1 = 0; ps.pfree = false; ps.nf = 0; ps.X[0] = ps.X[1] = ps.X[2] = 0;
-        if (l < n_point) {
-            ps.i0 = pt_start[l]; ps.i1 = pt_start[l + 1]; ps.pfree = !(pfix && pfix[l]);
-            const MS_GLOBAL double *src = from_point0 ? (const MS_GLOBAL double *)P.point0 : point;
-            ps.X[0] = src[3 * (size_t)l]; ps.X[1] = src[3 * (size_t)l + 1]; ps.X[2] = src[3 * (size_t)l + 2];
-        }
-    };
-    if (ONE) point_begin(slot, true);
-    else for (int l = slot; l < n_point; l += nslot) if (sub == 0) { point[3 * (size_t)l] = P.point0[3 * (size_t)l]; point[3 * (size_t)l + 1] = P.point0[3 * (size_t)l + 1]; point[3 * (size_t)l + 2] = P.point0[3 * (size_t)l + 2]; }
-    if (tid < OP_NV) s_acc[tid] = 0;
-    if (tid < 24) s_Hc[tid] = 0;
-    if (tid == 0) { s_ne = 0; s_const = 0; }
-    __syncthreads();
-    double pose[7];
-#pragma unroll
-    for (int a = 0; a < 7; ++a) pose[a] = P.pose0[7 * (size_t)pi + a];
-    // ---- the SE3 edges: an edge between fixed poses is a constant, one that touches the free pose leaves its fixed side's transform, -J^T W and J^T W J
-    //      in LDS (its Jacobian does not depend on the free pose), exactly as in k_ba_pose_only.  They belong to the LAST wave of the team's LAST workgroup:
-    //      an edge is ~1 700 dependent instructions (quaternion products, the SE3 logarithm) in one lane, 17 k cycles per sweep, and on the team's first wave
-    //      it sat in front of that wave's points -- the last lanes of a launch have the fewest points (none when the lanes outnumber them)
-    const bool edge_wg = rank == team - 1;
-    if (edge_wg && tid >= OP_NT - 64) {                                     // (the last wave: the one that takes the edges in every sweep)
-        double cc = po_edges_setup(P, pi, tid - (OP_NT - 64), &s_ne, s_eSide, &s_eC[0][0], &s_eM[0][0], &s_eG[0][0], &s_eW[0][0], s_Hc, s_J);
-        cc = wave_sum_d(cc);
-        if (tid == OP_NT - 64) lds_addd((MS_LDS double *)&s_const, cc);
-    }
-    __syncthreads();
-    const int ne = edge_wg ? s_ne : 0, et = tid - (OP_NT - 64);             // lane et of the last wave takes edge et
-    // The workgroups of a team exchange nothing but their partial sums (points, records and trial points belong to the workgroup that owns the lane group):
-    // these go through agent-scope atomic stores and loads, which are coherent across the XCDs' L2s by themselves, so the team barriers carry no L2 write-back
-    // and no invalidate (team_sync_light) -- the observation data stays in the caches from sweep to sweep
-    auto put = [](double *q, double v) { __hip_atomic_store(reinterpret_cast<unsigned long long *>(q), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto get = [](const double *q) { return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); };
-    // ---- sums over the team: the LDS accumulators s_acc[lo .. hi) (contributions of this workgroup) -> s_sum[lo .. hi), the same bits in every
-    //      workgroup (partials combined in rank order); slot OP_MAX is combined as a maximum
-    // after the barrier every thread fetches one or two of the partials (value tid & 63 of ranks tid >> 6, + 8: the loads of one thread wait for each other),
-    // the eight rows meet in LDS
-    auto team_combine = [&](const double *part, double mine, bool mine_slot) {
-        const int k = tid & 63, r0 = tid >> 6;
-        double v = 0;
-        for (int r = r0; r < team; r += OP_NW) { const double x = get(part + (size_t)r * OP_NV + k); v = k == OP_MAX ? fmax(v, x) : v + x; }
-        s_part[r0 * OP_NV + k] = v;
-        __syncthreads();
-        if (mine_slot) {
-            double t = s_part[tid];
-            for (int r = 1; r < OP_NW; ++r) t = tid == OP_MAX ? fmax(t, s_part[r * OP_NV + tid]) : t + s_part[r * OP_NV + tid];
-            mine = t;
-        }
-        return mine;
-    };
-    auto vec_reduce = [&](int lo, int hi, bool with_max) {
-        __syncthreads();
-        const bool mine_slot = (tid >= lo && tid < hi) || (with_max && tid == OP_MAX);
-        double mine = 0;
-        if (mine_slot) { mine = s_acc[tid]; s_acc[tid] = 0; }
-        if (team > 1) {
-            double *part = P.op_red + (size_t)(seq & 1) * team * OP_NV;
-            if (mine_slot) put(part + (size_t)rank * OP_NV + tid, mine);
-            team_sync_light(P, team);
-            mine = team_combine(part, mine, mine_slot);
-        }
-        ++seq;
-        if (mine_slot) s_sum[tid] = mine;
-        __syncthreads();
-    };
-    // two plain sums (fixed order: lanes, waves, ranks) -> s_sum[28], s_sum[29]
-    auto pair_reduce = [&](double a, double b) {
-        a = wave_sum_d(a); b = wave_sum_d(b);
-        __syncthreads();
-        if (lane == 0) { s_w[2 * wave] = a; s_w[2 * wave + 1] = b; }
-        __syncthreads();
-        double mine = 0;
-        const bool mine_slot = tid == 28 || tid == 29;
-        if (mine_slot) { for (int w = 0; w < OP_NW; ++w) mine += s_w[2 * w + tid - 28]; }
-        if (team > 1) {
-            double *part = P.op_red + (size_t)(seq & 1) * team * OP_NV;
-            if (mine_slot) put(part + (size_t)rank * OP_NV + tid, mine);
-            team_sync_light(P, team);
-            mine = team_combine(part, mine, mine_slot);
-        }
-        ++seq;
-        if (mine_slot) s_sum[tid] = mine;
-        __syncthreads();
-    };
-    auto load_pose = [&](int pc, const double (&cur)[7], double (&pz)[7]) {
-        if (pc == pi) {
-#pragma unroll
-            for (int a = 0; a < 7; ++a) pz[a] = cur[a];
-        } else if (lds_poses) {                                           // (explicit address spaces: a flat load would wait for the prefetched global data as well)
-            const MS_LDS double *q = (const MS_LDS double *)op_lds + 7 * pc;
-#pragma unroll
-            for (int a = 0; a < 7; ++a) pz[a] = q[a];
-        } else {
-            const MS_GLOBAL double *q = (const MS_GLOBAL double *)P.pose0 + 7 * (size_t)pc;
-#pragma unroll
-            for (int a = 0; a < 7; ++a) pz[a] = q[a];
-        }
-    };
-    // ---- robust chi2 of this lane's share of the observations [i0, i1) of a point at X, with the free pose at `cur`
-    auto chi2_share = [&](int i0, int i1, const double (&X)[3], const double (&cur)[7], bool store) {
-        double sum = 0;
-        int ii = i0 + sub, pn = 0;
-        double un = 0, vn = 0, fn = 0;
-        if (ii < i1) { pn = o_pose[ii]; un = o_uvi[3 * (size_t)ii]; vn = o_uvi[3 * (size_t)ii + 1]; fn = o_uvi[3 * (size_t)ii + 2]; }
-        while (ii < i1) {
-            const int pc = pn, icur = ii;
-            const double uvc[2] = {un, vn}, infc = fn;
-            ii += G;
-            if (ii < i1) { pn = o_pose[ii]; un = o_uvi[3 * (size_t)ii]; vn = o_uvi[3 * (size_t)ii + 1]; fn = o_uvi[3 * (size_t)ii + 2]; }
-            double pz[7], e[2], r, w;
-            load_pose(pc, cur, pz);
-            proj_edge<false>(pz, X, uvc, e, nullptr, nullptr);
-            const double chi2 = infc * (e[0] * e[0] + e[1] * e[1]);
-            huber(chi2, P.huber, r, w);
-            if (store) P.chi2_obs[o_idx[icur]] = chi2;
-            sum += r;
-        }
-        return sum;
-    };
-    // the SE3 edges at the free pose `cur` (lanes < ne of the team's first workgroup): chi2, and with lin the gradient into the accumulators
-    // (an edge's error at the accepted pose is the error of the trial that was accepted: it is kept, e_acc, and the linearisation only multiplies it)
-    double e_acc[6] = {0, 0, 0, 0, 0, 0}, e_try[6] = {0, 0, 0, 0, 0, 0};
-    auto edge_part = [&](const double (&cur)[7], bool lin) {
-        double sum = 0;
-        if (et >= 0 && et < ne) {
-            if (lin) {
-#pragma unroll
-                for (int a = 0; a < 6; ++a) { double v = 0; for (int c = 0; c < 6; ++c) v += s_eG[et][6 * a + c] * e_acc[c]; lds_addd(acc + 21 + a, v); }
-            } else {
-                double Bm[7], We[6];
-                if (s_eSide[et] == 0) se3_mul(s_eC[et], cur, Bm);
-                else { double Tjinv[7], A2[7]; se3_inv(cur, Tjinv); se3_mul(Tjinv, s_eM[et], A2); se3_mul(A2, s_eC[et], Bm); }
-                se3_log(Bm, e_try);
-                for (int i = 0; i < 6; ++i) { double v = 0; for (int j = 0; j < 6; ++j) v += s_eW[et][6 * i + j] * e_try[j]; We[i] = v; }
-                for (int i = 0; i < 6; ++i) sum += e_try[i] * We[i];
-            }
-        }
-        if (!lin && edge_wg && tid == 0) sum += s_const;
-        return sum;
-    };
-    auto total_chi2 = [&](const double (&cur)[7], bool store) {          // at the accepted state
-        double sum = 0;
-        for (int rnd = 0; rnd < nrounds; ++rnd) {
-            if (!ONE) point_begin(slot + rnd * nslot, false);
-            sum += chi2_share(ps.i0, ps.i1, ps.X, cur, store);
-        }
-        sum += edge_part(cur, false);
-        pair_reduce(sum, 0.0);
-        return s_sum[28];
-    };
-    // ---- the point's part of the damped system: -W (Hll + lambda I)^-1 W^T (upper triangle, 21) and -W (Hll + lambda I)^-1 bl (6)
-    auto schur_point = [&](double lambda, double (&Sv)[27]) {
-        Chol3 c;
-        const bool sound = chol3(ps.H, lambda, c);
-        const double u0 = ps.bl[0] * c.i11, u1 = (ps.bl[1] - c.l21 * u0) * c.i22, u2 = (ps.bl[2] - c.l31 * u0 - c.l32 * u1) * c.i33;
-        double Z[18];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const double z0 = ps.W[3 * r] * c.i11, z1 = (ps.W[3 * r + 1] - z0 * c.l21) * c.i22, z2 = (ps.W[3 * r + 2] - z0 * c.l31 - z1 * c.l32) * c.i33;
-            Z[3 * r] = z0; Z[3 * r + 1] = z1; Z[3 * r + 2] = z2;
-            Sv[21 + r] = -(z0 * u0 + z1 * u1 + z2 * u2);
-        }
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b2 = a; b2 < 6; ++b2) { Sv[k] = -(Z[3 * a] * Z[3 * b2] + Z[3 * a + 1] * Z[3 * b2 + 1] + Z[3 * a + 2] * Z[3 * b2 + 2]); ++k; }
-        return sound;
-    };
-    // one point's Schur terms into the accumulators (the group's first lane contributes); wave-uniform call
-    auto schur_stage = [&](bool live, double lambda) {
-        double Sv[27];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) Sv[k] = 0;
-        bool contributes = false;
-        if (live && sub == 0 && ps.pfree) {
-            if (ps.nf > 0) { contributes = true; if (!schur_point(lambda, Sv)) lds_addd(acc + OP_BAD, 1.0); }
-            else { Chol3 c; if (!chol3(ps.H, lambda, c)) lds_addd(acc + OP_BAD, 1.0); }
-        }
-        const unsigned long long m = __ballot(contributes);
-        if (contributes) slab_put(slab, cap, acc + OP_S0, lanes_below(m), Sv);
-        slab_sum(slab, cap, acc + OP_S0, (int)__popcll(m), lane);
-    };
-    auto rec_store = [&](int l) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) rec[(size_t)q * n_point + l] = ps.H[q];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) rec[(size_t)(6 + q) * n_point + l] = ps.bl[q];
-        if (ps.nf > 0) {
-#pragma unroll
-            for (int q = 0; q < 18; ++q) rec[(size_t)(9 + q) * n_point + l] = ps.W[q];
-        }
-        rec[(size_t)27 * n_point + l] = ps.pfree ? (double)ps.nf : -1.0;
-    };
-    auto rec_load = [&](int l) {
-        const double nfv = rec[(size_t)27 * n_point + l];
-        ps.nf = nfv > 0 ? (int)nfv : 0;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) ps.H[q] = rec[(size_t)q * n_point + l];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) ps.bl[q] = rec[(size_t)(6 + q) * n_point + l];
-        if (nfv > 0) {
-#pragma unroll
-            for (int q = 0; q < 18; ++q) ps.W[q] = rec[(size_t)(9 + q) * n_point + l];
-        }
-    };
-    double lambda = 0, ni = 2;
-    int it = 0, trials = 0, stop = 0;
-    long long cyc[6] = {0, 0, 0, 0, 0, 0}, tq = clock64();                 // 0 chi2 sweeps, 1 linearise (+ Schur terms), 2 the reduction after it, 3 6 x 6 solve, 4 points + trial chi2, 5 the reduction after it
-    const long long t_begin = tq;
-#define OP_LAP(i) do { const long long t_ = clock64(); cyc[i] += t_ - tq; tq = t_; } while (0)
-    const double chi2_init = total_chi2(pose, false);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) e_acc[a] = e_try[a];
-    OP_LAP(0);
-    double chi2_carried = chi2_init;
-    for (it = 0; it < P.max_iters; ++it) {
-        double current = chi2_carried, temp = current;
-        // ---- linearisation: per point Hll, bl, W; the free pose's block and gradient (A: 21 + 6, this lane's part).  From the second iteration on lambda is
-        //      known and the points' Schur terms follow in the same pass: one reduction instead of two
-        double md = 0;
-        for (int rnd = 0; rnd < nrounds; ++rnd) {
-            const int l = slot + rnd * nslot;
-            const bool live = l < n_point;
-            if (!ONE) point_begin(l, false);
-#pragma unroll
-            for (int q = 0; q < 6; ++q) ps.H[q] = 0;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) ps.bl[q] = 0;
-#pragma unroll
-            for (int q = 0; q < 18; ++q) ps.W[q] = 0;
-            const int i1 = ps.i1;
-            int jj = i1, jj2 = i1;                                       // this lane's first and second observation in the free keyframe
-            bool more = false;                                           // ... and there are further ones (found by scanning: never in a SLAM window, where a keyframe sees a point once)
-            double fu = 0, fv = 0, finf = 0;                             // the first one's measurement stays in registers (a reload after the loop is a round trip to L2)
-            bool fkept = false;
-            if (ps.pfree) {                                              // the point's own block and gradient: every observation of the share
-                int ii = ps.i0 + sub, pn = 0;
-                double un = 0, vn = 0, fn = 0;
-                if (ii < i1) { pn = o_pose[ii]; un = o_uvi[3 * (size_t)ii]; vn = o_uvi[3 * (size_t)ii + 1]; fn = o_uvi[3 * (size_t)ii + 2]; }
-                while (ii < i1) {
-                    const int pc = pn;
-                    const double uvc[2] = {un, vn}, infc = fn;
-                    if (pc == pi) { if (jj == i1) { jj = ii; fu = un; fv = vn; finf = fn; fkept = true; } else if (jj2 == i1) jj2 = ii; else more = true; }
-                    ii += G;
-                    if (ii < i1) { pn = o_pose[ii]; un = o_uvi[3 * (size_t)ii]; vn = o_uvi[3 * (size_t)ii + 1]; fn = o_uvi[3 * (size_t)ii + 2]; }
-                    double pz[7], e[2], Jp[12], Jl[6], r, w;
-                    load_pose(pc, pose, pz);
-                    proj_edge<true>(pz, ps.X, uvc, e, Jp, Jl);
-                    const double chi2 = infc * (e[0] * e[0] + e[1] * e[1]);
-                    huber(chi2, P.huber, r, w);
-                    const double wi = w * infc;
-                    ps.H[0] += wi * (Jl[0] * Jl[0] + Jl[3] * Jl[3]); ps.H[1] += wi * (Jl[0] * Jl[1] + Jl[3] * Jl[4]); ps.H[2] += wi * (Jl[0] * Jl[2] + Jl[3] * Jl[5]);
-                    ps.H[3] += wi * (Jl[1] * Jl[1] + Jl[4] * Jl[4]); ps.H[4] += wi * (Jl[1] * Jl[2] + Jl[4] * Jl[5]); ps.H[5] += wi * (Jl[2] * Jl[2] + Jl[5] * Jl[5]);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) ps.bl[c] -= wi * (Jl[c] * e[0] + Jl[3 + c] * e[1]);
-                }
-            } else { jj = ps.i0 + sub; while (jj < i1 && o_pose[jj] != pi) jj += G; more = true; }     // (a fixed point: its share is scanned)
-            // the observations in the free keyframe once more (one lane in four has one; a wave-uniform loop): the pose's block and gradient go straight into the
-            // wave's slab, W = Jp^T w Jl stays with the point -- keeping 27 more sums in registers through the loop above made the kernel spill
-            int nf = 0, cnt = 0;
-            for (;;) {
-                const bool has = jj < i1;
-                const unsigned long long m = __ballot(has);
-                if (m == 0) break;
-                if (has) {
-                    if (!fkept) { fu = o_uvi[3 * (size_t)jj]; fv = o_uvi[3 * (size_t)jj + 1]; finf = o_uvi[3 * (size_t)jj + 2]; }
-                    fkept = false;
-                    const double uvc[2] = {fu, fv}, infc = finf;
-                    double e[2], Jp[12], Jl[6], r, w, A[27];
-                    proj_edge<true>(pose, ps.X, uvc, e, Jp, Jl);
-                    const double chi2 = infc * (e[0] * e[0] + e[1] * e[1]);
-                    huber(chi2, P.huber, r, w);
-                    const double wi = w * infc;
-                    int k = 0;
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) {
-                        A[21 + a] = -(Jp[a] * e[0] + Jp[6 + a] * e[1]) * wi;
-#pragma unroll
-                        for (int b2 = a; b2 < 6; ++b2) { A[k] = wi * (Jp[a] * Jp[b2] + Jp[6 + a] * Jp[6 + b2]); ++k; }
-                    }
-                    slab_put(slab, cap, acc, cnt + lanes_below(m), A);
-                    if (ps.pfree) {
-                        ++nf;
-#pragma unroll
-                        for (int r2 = 0; r2 < 6; ++r2)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) ps.W[3 * r2 + c] += wi * (Jp[r2] * Jl[c] + Jp[6 + r2] * Jl[3 + c]);
-                    }
-                    if (more && jj2 == i1) { jj += G; while (jj < i1 && o_pose[jj] != pi) jj += G; }      // the rare cases: scan on
-                    else { jj = jj2; jj2 = i1; }
-                }
-                cnt += (int)__popcll(m);
-            }
-            slab_sum(slab, cap, acc, cnt, lane);
-            ps.nf = group_sum_i(nf, lgG);
-#pragma unroll
-            for (int q = 0; q < 6; ++q) ps.H[q] = group_sum_d(ps.H[q], lgG);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) ps.bl[q] = group_sum_d(ps.bl[q], lgG);
-            if (ps.nf > 0) {
-#pragma unroll
-                for (int q = 0; q < 18; ++q) ps.W[q] = group_sum_d(ps.W[q], lgG);
-            }
-            if (live && sub == 0) {
-                if (!ONE) rec_store(l);
-                if (ps.pfree) md = fmax(md, fmax(fabs(ps.H[0]), fmax(fabs(ps.H[3]), fabs(ps.H[5]))));
-            }
-            if (it > 0) schur_stage(live, lambda);
-        }
-        (void)edge_part(pose, true);
-        OP_LAP(1);
-        if (edge_wg && tid < 21) lds_addd(acc + tid, s_Hc[tid]);          // the edges' constant J^T W J: into the sums, so that every workgroup of the team gets it
-        if (it == 0) {
-            for (int off = 32; off > 0; off >>= 1) md = fmax(md, __shfl_xor(md, off, 64));
-            if (lane == 0) (void)atomicMax(reinterpret_cast<unsigned long long *>(&s_acc[OP_MAX]), (unsigned long long)__double_as_longlong(md));
-        }
-        vec_reduce(0, it == 0 ? 27 : OP_BAD + 1, it == 0);
-        OP_LAP(2);
-        const double *Hp = s_sum, *bp = s_sum + 21;                         // (they stay in LDS: 27 doubles in every thread's registers were a part of the kernel's spills)
-        if (it == 0) {                                                       // computeLambdaInit: 1e-5 x the largest diagonal entry of the whole system
-            const double mdp = fmax(fmax(fmax(fabs(Hp[0]), fabs(Hp[6])), fmax(fabs(Hp[11]), fabs(Hp[15]))), fmax(fabs(Hp[18]), fabs(Hp[20])));
-            lambda = 1e-5 * fmax(mdp, s_sum[OP_MAX]); ni = 2;
-        }
-        double rho = 0;
-        int qmax = 0;
-        bool have_schur = it > 0;                                            // the Schur terms at this lambda are in s_sum already
-        do {
-            if (!have_schur) {
-                for (int rnd = 0; rnd < nrounds; ++rnd) {
-                    const int l = slot + rnd * nslot;
-                    const bool live = l < n_point;
-                    if (!ONE) { ps.pfree = false; ps.nf = 0; if (live && sub == 0) { ps.pfree = !(pfix && pfix[l]); if (ps.pfree) rec_load(l); } }
-                    schur_stage(live, lambda);
-                }
-                OP_LAP(1);
-                vec_reduce(OP_S0, OP_BAD + 1, false);
-                OP_LAP(2);
-            }
-            have_schur = false;
-            // (S + lambda I) dp = y: the 6 x 6 Cholesky by every thread for itself, as in k_ba_pose_only
-            double Lm[21], dpv[6], yv[6];
-            bool ok2 = s_sum[OP_BAD] == 0.0;
-            {
-                int k = 0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int c = a; c < 6; ++c) { Lm[c * (c + 1) / 2 + a] = Hp[k] + s_sum[OP_S0 + k] + (a == c ? lambda : 0.0); ++k; }
-#pragma unroll
-                for (int a = 0; a < 6; ++a) yv[a] = bp[a] + s_sum[OP_S0 + 21 + a];
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                double d = Lm[j * (j + 1) / 2 + j];
-#pragma unroll
-                for (int k = 0; k < j; ++k) d -= Lm[j * (j + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-                if (!(d > 0) || !isfinite(d)) ok2 = false;
-                const double inv = rsqrt_d(d);
-                Lm[j * (j + 1) / 2 + j] = inv;
-#pragma unroll
-                for (int i = j + 1; i < 6; ++i) {
-                    double v = Lm[i * (i + 1) / 2 + j];
-#pragma unroll
-                    for (int k = 0; k < j; ++k) v -= Lm[i * (i + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-                    Lm[i * (i + 1) / 2 + j] = v * inv;
-                }
-            }
-            {
-                double y2[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    double v = yv[i];
-#pragma unroll
-                    for (int k = 0; k < i; ++k) v -= Lm[i * (i + 1) / 2 + k] * y2[k];
-                    y2[i] = v * Lm[i * (i + 1) / 2 + i];
-                }
-#pragma unroll
-                for (int i = 5; i >= 0; --i) {
-                    double v = y2[i];
-#pragma unroll
-                    for (int k = i + 1; k < 6; ++k) v -= Lm[k * (k + 1) / 2 + i] * dpv[k];
-                    dpv[i] = v * Lm[i * (i + 1) / 2 + i];
-                }
-            }
-            double trial_pose[7];
-#pragma unroll
-            for (int a = 0; a < 7; ++a) trial_pose[a] = pose[a];
-            OP_LAP(3);
-            if (ok2) {
-                double ex[7], sc = 0, sum = 0;
-                se3_exp(dpv, ex);
-                se3_mul(ex, pose, trial_pose);
-                if (gl == 0) { for (int a = 0; a < 6; ++a) sc += dpv[a] * (lambda * dpv[a] + bp[a]); }
-                // ---- the points follow: dl = (Hll + lambda I)^-1 (bl - W^T dp), the trial point, its share of the gain denominator and the chi2 of its observations
-                for (int rnd = 0; rnd < nrounds; ++rnd) {
-                    const int l = slot + rnd * nslot;
-                    const bool live = l < n_point;
-                    if (!ONE) { point_begin(l, false); if (live && ps.pfree) rec_load(l); }
-                    double Xn[3] = {ps.X[0], ps.X[1], ps.X[2]};
-                    if (live && ps.pfree) {
-                        double r0 = ps.bl[0], r1 = ps.bl[1], r2 = ps.bl[2];
-                        if (ps.nf > 0) {
-#pragma unroll
-                            for (int a = 0; a < 6; ++a) { r0 -= ps.W[3 * a] * dpv[a]; r1 -= ps.W[3 * a + 1] * dpv[a]; r2 -= ps.W[3 * a + 2] * dpv[a]; }
-                        }
-                        Chol3 c;
-                        (void)chol3(ps.H, lambda, c);
-                        const double v0 = r0 * c.i11, v1 = (r1 - c.l21 * v0) * c.i22, v2 = (r2 - c.l31 * v0 - c.l32 * v1) * c.i33;       // L^-1 r
-                        const double d2 = v2 * c.i33, d1 = (v1 - c.l32 * d2) * c.i22, d0 = (v0 - c.l21 * d1 - c.l31 * d2) * c.i11;         // L^-T (L^-1 r)
-                        if (sub == 0) sc += d0 * (lambda * d0 + ps.bl[0]) + d1 * (lambda * d1 + ps.bl[1]) + d2 * (lambda * d2 + ps.bl[2]);
-                        Xn[0] += d0; Xn[1] += d1; Xn[2] += d2;
-                    }
-                    if (ONE) { Xt[0] = Xn[0]; Xt[1] = Xn[1]; Xt[2] = Xn[2]; }
-                    else if (live && sub == 0) { trial[3 * (size_t)l] = Xn[0]; trial[3 * (size_t)l + 1] = Xn[1]; trial[3 * (size_t)l + 2] = Xn[2]; }
-                    sum += chi2_share(ps.i0, ps.i1, Xn, trial_pose, false);
-                }
-                sum += edge_part(trial_pose, false);
-                OP_LAP(4);
-                pair_reduce(sum, sc);
-                OP_LAP(5);
-                temp = s_sum[28];
-            } else temp = DBL_MAX;
-            const double scale = (ok2 ? s_sum[29] : 0.0) + 1e-3;
-            rho = (current - temp) / scale;
-            if (trials < P.debug_reject) rho = -1.0;                // (test hook: drives the ten-rejections Terminate path)
-            if (rho > 0 && isfinite(temp)) {
-                const double t3 = 2 * rho - 1;
-                double alpha = 1. - t3 * t3 * t3;                                          // (pow(x, 3) of the reference to an ulp or two)
-                alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha);
-                ni = 2; current = temp; chi2_carried = temp;
-#pragma unroll
-                for (int a = 0; a < 7; ++a) pose[a] = trial_pose[a];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) e_acc[a] = e_try[a];
-                if (ONE) { ps.X[0] = Xt[0]; ps.X[1] = Xt[1]; ps.X[2] = Xt[2]; }
-                else {
-                    for (int l = slot; l < n_point; l += nslot)
-                        if (sub == 0) { point[3 * (size_t)l] = trial[3 * (size_t)l]; point[3 * (size_t)l + 1] = trial[3 * (size_t)l + 1]; point[3 * (size_t)l + 2] = trial[3 * (size_t)l + 2]; }
-                    __syncthreads();                                        // the group's other lanes read the moved points next
-                }
-            } else {
-                lambda *= ni; ni *= 2;
-                if (!isfinite(lambda)) break;
-            }
-            ++qmax; ++trials;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0 || !isfinite(lambda)) { stop = 1; ++it; break; }
-    }
-    tq = clock64();
-    const double chi2_final = total_chi2(pose, true);
-    OP_LAP(0);
-    if (ONE && slot < n_point && sub == 0) { point[3 * (size_t)slot] = ps.X[0]; point[3 * (size_t)slot + 1] = ps.X[1]; point[3 * (size_t)slot + 2] = ps.X[2]; }
-    if (gl == 0) {
-        const bool hung = team > 1 && __hip_atomic_load(P.flag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;      // a team barrier gave up: the result is not to be trusted
-        for (int a = 0; a < 7; ++a) P.pose[7 * (size_t)pi + a] = pose[a];
-        P.stats[0] = it; P.stats[1] = trials; P.stats[2] = stop; P.stats[3] = lambda; P.stats[4] = chi2_init; P.stats[5] = hung ? NAN : chi2_final;
-        P.stats[6] = (isfinite(chi2_final) && !hung) ? 1 : 0; P.stats[7] = hung ? 1 : 0;
-        P.stats[15] = 0;
-    }
-    if (gl == 0) {                                                         // the phase stamps of the first wave
-        P.stats[8] = (double)cyc[0]; P.stats[9] = (double)cyc[1]; P.stats[10] = (double)cyc[2]; P.stats[11] = (double)cyc[3]; P.stats[12] = (double)cyc[4];
-        P.stats[13] = (double)(clock64() - t_begin); P.stats[14] = (double)cyc[5];
-        P.stats[15] = (double)(t_begin - t_kernel);                           // what comes before the first sweep (not part of [13])
-    }
-#undef OP_LAP
-}
+#include "ba_pose_only.h"
+#include "ba_one_pose.h"
 
 }  // namespace
 
 // =================================================================================================
 // host side
 // =================================================================================================
-struct ms_ba {
-    ms_ctx *ctx = nullptr;
-    int n = 0;
-    std::vector<BaProb> host;          // device pointers inside
-    std::vector<ms_ba_problem> dims;   // sizes only
-    BaProb *d_probs = nullptr;
-    // k_ba_lm's fused trial schedule: the same descriptors with Hpp / bp / Hll / bl pointing at a second set of arrays (behind d_probs on the device); alt_ptrs[i].Hpp == nullptr:
-    // problem i has no second set and the whole handle runs the plain schedule
-    struct AltPtrs { double *Hpp, *bp, *Hll, *bl; };
-    std::vector<AltPtrs> alt_ptrs;
-    std::vector<BaProb> host_alt;
-    BaProb *d_probs_alt = nullptr;
-    bool alt_ok = false;
-    char *d_arena = nullptr;
-    size_t arena_bytes = 0;
-    int team = 0;                      // workgroups per problem of the next launch (ms_ba_set_team; 0 = automatic)
-    int factor_team = 0;               // of these, workgroups in the distributed Cholesky of a large system (ms_ba_set_factor_team; 0 = automatic)
-    std::vector<double> chol_tiles;    // per problem: row tiles a Cholesky panel touches on average
-    int cus = 0;
-    bool pose_only = false;            // every problem has ONE free pose and only fixed points: k_ba_pose_only instead of k_ba_lm (poseBundleAdjust)
-    bool one_pose = false;             // every problem has ONE free pose and at least one free point: k_ba_one_pose (stage 1 of localBundleAdjust)
-    int one_pose_lg = 0;               // log2 of the lanes per point of the last k_ba_one_pose launch
-    bool last_one_pose = false;        // the last launch was k_ba_one_pose (its fallback after a barrier gave up is the same kernel with one workgroup)
-    int launched_team = 1;             // team size of the last launch
-    bool team_checked = true;          // the last team launch has been looked at (every problem's gave-up marker) and, if need be, repeated
-    int debug_fail_barriers = 0;       // test hook: team barriers give up at once (ms_ba_debug_fail_team_barriers)
-    int team_fallbacks = 0;            // launches repeated with one workgroup per problem after a team barrier gave up
-    int solves = 0;                    // launches so far (ms_ba_copy_state refuses a source that has never been solved)
-    // a single small problem (poseBundleAdjust): its results are packed and copied into h_result right behind the solver launch, so that ms_ba_download only
-    // waits for ev_done and reads them -- no pack launch and device-to-host round trip after the wait (0.03 ms of a 0.08 ms solve)
-    void *h_result = nullptr;          // page-locked, stays with the handle OBJECT (pooled per context)
-    size_t h_result_bytes = 0, pack_doubles = 0;
-    double *d_pack = nullptr;          // in the arena; nullptr: no eager results for this handle
-    int32_t *h_verdict = nullptr;      // page-locked word, stays with the handle object: "a team barrier gave up somewhere in the last launch", collected behind every team launch
-    bool verdict_eager = false;        // h_verdict belongs to the last launch
-    bool eager = false;                // h_result holds the last launch's results
-    bool self_packed = false;          // the last launch was k_ba_pose_only with BaProb::pack set: d_pack is already what k_ba_pack_result would write
-    bool work_dirty = false;           // a pose-only handle whose work areas [work_lo[p], work_hi[p]) were never cleared: the general kernel needs them zero (ms_ba_solve)
-    std::vector<size_t> work_lo, work_hi;
-    bool quiet = false;                // everything this handle put on the stream is known to have finished (ev_done was seen, nothing enqueued since): ms_ba_destroy need not wait
-    hipEvent_t ev_done = nullptr;      // the end of this handle's last launch (what reads its results waits for it ON THE HOST, politely: ba_wait_event)
-    bool pending = false;
-};
+#include "ba_handle.h"
+#include "ba_prep.h"
 
-// Team launches of this process, per device: what is (or may still be) running, so that the workgroups of all concurrent team launches
-// together never exceed the CUs (see ms_ba_solve)
-struct TeamLaunch { hipEvent_t ev; hipStream_t stream; int wgs; bool live; };
-static std::mutex g_team_mu;
-static std::vector<TeamLaunch> g_team_live[64];
-static int g_team_query_errors = 0;        // hipEventQuery answers other than success / not-ready seen by the admission list (guarded by g_team_mu)
-#define MS_TRY_BA(x) do { int rc__ = (x); if (rc__ != MS_OK) return rc__; } while (0)
-
-constexpr size_t kBaEagerMax = (size_t)64 << 10;        // results of a single problem up to this size are packed and copied behind every launch (ms_ba struct: h_result).
-                                                        // (Tried at 512 KB, i.e. for a whole C4 window too: -0.025 ms for the window alone, but the front end of the same
-                                                        //  sequence, running beside it, fell from 2.7-3.0 k to 2.0-2.2 k frames/s; kept for small problems)
-constexpr size_t kBaStageMax = (size_t)4 << 20;        // creates whose inputs fit are uploaded from the context's page-locked staging block without a wait
-// SE3 edges that touch pose `pi` (k_ba_pose_only / k_ba_one_pose keep their constants in PO_MAXE LDS slots; edges between fixed poses need none)
-static int ba_edges_at_free_pose(const ms_ba_problem &Q, int pi) {
-    int t = 0;
-    for (int k = 0; k < Q.n_pose_edge; ++k) t += Q.edge_i[k] == pi || Q.edge_j[k] == pi;
-    return t;
-}
-// the descriptors of the second linearisation set: host_alt[i] = host[i] with the four output arrays exchanged (rebuilt whenever host[] is about to be uploaded: the
-// two must agree in everything else -- team sizes included)
-static void ba_make_alt(ms_ba *B) {
-    B->host_alt.assign(B->host.begin(), B->host.end());
-    B->alt_ok = !B->host.empty() && B->alt_ptrs.size() == B->host.size();
-    for (size_t i = 0; i < B->host_alt.size() && B->alt_ok; ++i) {
-        const ms_ba::AltPtrs &a = B->alt_ptrs[i];
-        if (!a.Hpp) { B->alt_ok = false; break; }
-        BaProb &q = B->host_alt[i];
-        q.Hpp = a.Hpp; q.bp = a.bp; q.Hll = a.Hll; q.bl = a.bl;
-    }
-}
-// (both descriptor sets, in stream order)
-static hipError_t ba_upload_descriptors(ms_ba *B, hipStream_t st) {
-    ba_make_alt(B);
-    hipError_t e = hipMemcpyAsync(B->d_probs, B->host.data(), sizeof(BaProb) * B->n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(B->d_probs_alt, B->host_alt.data(), sizeof(BaProb) * B->n, hipMemcpyHostToDevice, st);
-    return e;
-}
-// The end of a handle's last launch, as an event the handle owns: whatever reads the launch's results waits for it ON THE HOST, politely (ba_wait_event), before it
-// enqueues anything -- not with hipStreamSynchronize, and not with a wait packet behind the launch (round 4, tools/hog_probe.py: a stream with packets queued behind
-// a 2 ms kernel slowed the front end of ANOTHER sequence 10 ... 90 x, one that holds one launch at a time 3 ... 15 x).
-static int ba_launch_done(ms_ctx *c, ms_ba *B) {
-    B->quiet = false;
-    if (!B->ev_done) { MS_HIP(c, hipEventCreateWithFlags(&B->ev_done, hipEventDisableTiming)); ++g_ba_host_allocs; }
-    MS_HIP(c, hipEventRecord(B->ev_done, c->stream));
-    B->pending = true;
-    return MS_OK;
-}
-static void ba_delete_object(ms_ba *B) {
-    if (B->ev_done) (void)hipEventDestroy(B->ev_done);
-    if (B->h_result) (void)hipHostFree(B->h_result);
-    if (B->h_verdict) (void)hipHostFree(B->h_verdict);
-    delete B;
-}
-// A host wait for a solver launch (milliseconds) that leaves the processor to the other sequences' threads: hipStreamSynchronize / hipEventSynchronize spin, and
-// seven threads spinning in them made the thread that drives another sequence's front end 3 ... 15 x slower (tools/hog_probe.py: x 3.3 beside two streams whose
-// threads wait in hipStreamSynchronize, x 1.09 beside the same streams with the threads asleep) -- on this runtime a waiting thread is not free for the others.
-// Two phases: for the first ~120 us the event is polled with a yield in between (poseBundleAdjust's launch is 0.08 ms: a frame must not pay a timer's granularity
-// for it), after that the thread sleeps 20 us at a time, with its timer slack set to 1 us once (the default 50 us slack turned every 25 us sleep into ~75 us:
-// 0.18 ms in ms_ba_download for a 0.08 ms kernel, tools/pose_path_probe.py).
-static int ba_wait_event(ms_ctx *c, hipEvent_t ev) {
-    thread_local bool slack_set = false;
-    constexpr auto kSpin = std::chrono::microseconds(120), kSleep = std::chrono::microseconds(20);
-    static const bool fine_slack = !std::getenv("MS_WAIT_COARSE");
-    const auto t0 = std::chrono::steady_clock::now();
-    for (bool spinning = true;;) {
-        const hipError_t q = hipEventQuery(ev);
-        if (q == hipSuccess) return MS_OK;
-        if (q != hipErrorNotReady) { (void)hipGetLastError(); return ms_fail(c, MS_ERR_HIP, "waiting for a solver launch failed: %s", hipGetErrorString(q)); }
-        if (spinning) {
-            std::this_thread::yield();
-            spinning = std::chrono::steady_clock::now() - t0 < kSpin;
-        } else {
-            if (!slack_set && fine_slack) { (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0UL, 0UL, 0UL); slack_set = true; }      // (nanoseconds; the calling thread only)
-            std::this_thread::sleep_for(kSleep);
-        }
-    }
-}
-static int ba_wait_pending(ms_ba *B) {
-    if (!B->pending) return MS_OK;
-    MS_TRY_BA(ba_wait_event(B->ctx, B->ev_done));
-    B->pending = false;
-    B->quiet = true;
-    return MS_OK;
-}
-
-// ---------------------------------------------------------------- host scratch of ms_ba_create: no allocation per window after warm-up
-// Everything ms_ba_create builds on the host (index structures, batch lists, the streams: ~40 arrays per problem) lives in a per-thread bump arena that keeps its
-// memory from call to call: a sliding-window BA per keyframe allocates nothing once the first windows have sized it.  (A batch that does not fit overflows into
-// plain blocks, freed at the next call.)  g_ba_host_allocs counts every allocation this file makes on the host or the device -- arena growth, overflow blocks,
-// handle objects, device blocks, events -- so a test can hold "none after warm-up" against it (ms_debug_host_allocs; tests/host_shim_smoke.cpp).
-struct BaArena {
-    static constexpr size_t kKeepMax = (size_t)64 << 20;            // what a thread keeps between calls: enough for a handful of windows per call, not for a 256-window batch
-    char *base = nullptr;
-    size_t cap = 0, used = 0, total = 0;
-    std::vector<void *> overflow;
-    void begin() {                                                  // start of a create: nothing of the previous call is alive any more
-        const size_t want = std::min(kKeepMax, total + total / 4);
-        if (want > cap) { std::free(base); cap = ms_align_up(want, (size_t)1 << 20); base = static_cast<char *>(std::malloc(cap)); ++g_ba_host_allocs; }
-        used = 0; total = 0;
-    }
-    void end() {                                                    // end of a create: what did not fit goes back at once (the arena itself stays)
-        for (void *p : overflow) std::free(p);
-        overflow.clear();
-    }
-    void *take(size_t bytes, size_t align) {
-        const size_t at = ms_align_up(used, align);
-        total = ms_align_up(total, align) + bytes;
-        if (base && at + bytes <= cap) { used = at + bytes; return base + at; }
-        void *p = std::malloc(bytes ? bytes : 1);
-        ++g_ba_host_allocs;
-        overflow.push_back(p);
-        return p;
-    }
-    ~BaArena() { end(); std::free(base); }
-};
-static thread_local BaArena tl_ba_arena;
-template <class T>
-struct BaAlloc {
-    typedef T value_type;
-    BaAlloc() = default;
-    template <class U> BaAlloc(const BaAlloc<U> &) {}
-    T *allocate(size_t n) { return static_cast<T *>(tl_ba_arena.take(n * sizeof(T), alignof(T) < 16 ? 16 : alignof(T))); }
-    void deallocate(T *, size_t) {}
-    template <class U> bool operator==(const BaAlloc<U> &) const { return true; }
-    template <class U> bool operator!=(const BaAlloc<U> &) const { return false; }
-};
-template <class T> using bvec = std::vector<T, BaAlloc<T>>;
-
-// ---------------------------------------------------------------- what ms_ba_create builds per problem (the ba_* steps below, in the order they run)
-// One pass set of the fused Schur phase on the host (FsSet is what the kernels see of it)
-struct FsHost {
-    bvec<int32_t> row0, row1, yoff, rowoff;                  // passes: their rows, their tile layout
-    bvec<int32_t> batch_start, b_obs_start, b_run_start, b_fmt, pobs;
-    bvec<double> puv;
-    bvec<uint16_t> pairs;
-    bool by_points = false;
-};
-struct Prep {
-    int np_free = 0;
-    bvec<int32_t> pidx, free2pose;                            // free-pose index
-    bvec<int32_t> pt_start, pt_obs, fstart, fobs;             // CSR by point and by free pose
-    int auto_team = 1;                                        // what ms_ba_solve will pick on its own (ba_auto_team): a handle that gets teams builds no streams, and only the fine pass set
-    bvec<int32_t> fo_lo, op_pose, op_o;                       // the streams; the one-pose kernel's arrays
-    bvec<double> fo_uvi, op_uvi;
-    bool one_pose = false, pose_only = false;                 // the two shapes with ONE free pose: with free points (k_ba_one_pose), without (k_ba_pose_only)
-    bool fused = false;                                       // the fused Schur pass (else the record-based list below)
-    bvec<int32_t> chunk_items, seg_start, seg_pair;
-    int n_chunks = 0, n_seg = 0;
-    bvec<int32_t> env16, act_start, act_blk;                  // 16-row envelope and panel lists
-    double chol_tiles = 0;
-    bvec<int32_t> fs_cs;
-    int fs_only = 0;                                          // the one pass set that is built
-    FsHost fs[2];
-    bvec<int32_t> cw_slot, cw_act_start, cw_act, cw_load_start, cw_load;      // windowed Cholesky
-    int cw_W = 0;
-    bool cw_zglobal = false, cw_meta_lds = false;
-    size_t in_lo = 0, in_hi = 0, copy_lo = 0, copy_hi = 0;    // the problem's input range of the device block, and its entries of BaLayout::copies
-};
-// Envelope of the reduced camera matrix at pose level, and the free observations of every free point sorted by free pose (flat arrays: the fused Schur pass is built from them)
-struct BaEnvelope {
-    bvec<int> first;                                          // the first free pose each free pose is coupled with (a shared point or a pose-pose edge)
-    bvec<int> hfirst;                                         // ... by a pose-pose EDGE (Hpp has nothing left of that block)
-    bvec<int32_t> fp_start, fp_f, fp_o;
-};
-// MS_BA_TIMING: where the host time of a create goes.  A BaLap adds the time between its construction and its end to one slot.
-struct BaTimes {
-    enum Slot { kCsrEnvelope, kLists, kFused, kPasses, kPointKeys, kSort, kBatches, kValues, kSlots };
-    const char *const mode = std::getenv("MS_BA_TIMING");     // prints the host index build and the allocation + upload time of every create to stderr
-    double part[kSlots] = {};
-    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-};
-struct BaLap {
-    BaTimes &t;
-    const int slot;
-    const double t0;
-    BaLap(BaTimes &times, int s) : t(times), slot(s), t0(times.mode ? BaTimes::now() : 0.0) {}
-    ~BaLap() { if (t.mode) t.part[slot] += BaTimes::now() - t0; }
-};
-// The team size ms_ba_solve picks on its own for the general kernel: as many workgroups per problem as fit the chip beside the other problems, at most 32 (beyond that
-// the single-workgroup Cholesky dominates); small problems are latency-bound on the barriers.  ms_ba_create builds for the regime this predicts.
-static int ba_auto_team(int n_obs, int cus, int n) { return std::max(1, std::min(std::min(32, std::max(1, n_obs / 512)), cus / std::max(n, 1))); }
-static int ba_check_problem(ms_ctx *c, const ms_ba_problem &Q, int p, Prep &R) {
-    if (Q.n_pose < 1 || Q.n_point < 0 || Q.n_obs < 0 || Q.n_pose_edge < 0 || !Q.pose || !Q.pose_fixed || (Q.n_point && !Q.point) ||
-        (Q.n_obs && (!Q.obs_pose || !Q.obs_point || !Q.obs_uv || !Q.obs_info)) || (Q.n_pose_edge && (!Q.edge_i || !Q.edge_j || !Q.edge_meas || !Q.edge_info)))
-        return ms_fail(c, MS_ERR_INVALID, "ms_ba_create: problem %d has missing arrays", p);
-    R.pidx.assign(Q.n_pose, -1);
-    for (int i = 0; i < Q.n_pose; ++i) if (!Q.pose_fixed[i]) { R.pidx[i] = R.np_free++; R.free2pose.push_back(i); }
-    if (R.np_free > kMaxFreePosesTeam) return ms_fail(c, MS_ERR_CAPACITY, "ms_ba_create: %d free poses (max %d in this version)", R.np_free, kMaxFreePosesTeam);
-    for (int o = 0; o < Q.n_obs; ++o)
-        if (Q.obs_pose[o] < 0 || Q.obs_pose[o] >= Q.n_pose || Q.obs_point[o] < 0 || Q.obs_point[o] >= Q.n_point)
-            return ms_fail(c, MS_ERR_INVALID, "ms_ba_create: observation %d of problem %d indexes outside the problem", o, p);
-    for (int k = 0; k < Q.n_pose_edge; ++k)
-        if (Q.edge_i[k] < 0 || Q.edge_i[k] >= Q.n_pose || Q.edge_j[k] < 0 || Q.edge_j[k] >= Q.n_pose)
-            return ms_fail(c, MS_ERR_INVALID, "ms_ba_create: pose edge %d of problem %d indexes outside the problem", k, p);
-    return MS_OK;
-}
-// CSR by point and by free pose
-static void ba_build_csr(const ms_ba_problem &Q, Prep &R) {
-    R.pt_start.assign(Q.n_point + 1, 0);
-    for (int o = 0; o < Q.n_obs; ++o) R.pt_start[Q.obs_point[o] + 1]++;
-    for (int l = 0; l < Q.n_point; ++l) R.pt_start[l + 1] += R.pt_start[l];
-    R.pt_obs.resize(Q.n_obs);
-    { bvec<int32_t> cur(R.pt_start.begin(), R.pt_start.end() - 1); for (int o = 0; o < Q.n_obs; ++o) R.pt_obs[cur[Q.obs_point[o]]++] = o; }
-    R.fstart.assign(R.np_free + 1, 0);
-    for (int o = 0; o < Q.n_obs; ++o) { const int f = R.pidx[Q.obs_pose[o]]; if (f >= 0) R.fstart[f + 1]++; }
-    for (int f = 0; f < R.np_free; ++f) R.fstart[f + 1] += R.fstart[f];
-    R.fobs.resize(R.fstart[R.np_free]);
-    { bvec<int32_t> cur(R.fstart.begin(), R.fstart.end() - 1); for (int o = 0; o < Q.n_obs; ++o) { const int f = R.pidx[Q.obs_pose[o]]; if (f >= 0) R.fobs[cur[f]++] = o; } }
-    for (int o = 0; o < Q.n_obs; ++o) if (R.pidx[Q.obs_pose[o]] < 0) R.fobs.push_back(o);      // behind them: the observations of FIXED poses (fobs[fstart[np_free] .. n_obs))
-}
-// the fobs order as a stream of values (linearise_stream, eval_stream, backsub_stream): read by launches with ONE workgroup per window; a handle that will get teams
-// (a window per keyframe) neither builds nor uploads them
-static void ba_build_streams(const ms_ba_problem &Q, Prep &R) {
-    if (R.auto_team != 1) return;
-    R.fo_lo.resize(4 * (size_t)Q.n_obs); R.fo_uvi.assign(4 * (size_t)Q.n_obs, 0.0);
-    for (int ii = 0; ii < Q.n_obs; ++ii) {
-        const int o = R.fobs[ii];
-        R.fo_lo[4 * (size_t)ii] = Q.obs_point[o]; R.fo_lo[4 * (size_t)ii + 1] = o | ((Q.point_fixed && Q.point_fixed[Q.obs_point[o]]) ? (int32_t)0x80000000 : 0); R.fo_lo[4 * (size_t)ii + 2] = Q.obs_pose[o]; R.fo_lo[4 * (size_t)ii + 3] = R.pidx[Q.obs_pose[o]];
-        R.fo_uvi[4 * (size_t)ii] = Q.obs_uv[2 * (size_t)o]; R.fo_uvi[4 * (size_t)ii + 1] = Q.obs_uv[2 * (size_t)o + 1]; R.fo_uvi[4 * (size_t)ii + 2] = Q.obs_info[o];
-    }
-}
-// The shapes with ONE free pose whose SE3 edges fit the PO_MAXE LDS slots (edges between fixed poses are constants: any number).  No free point: poseBundleAdjust,
-// k_ba_pose_only.  At least one free point (stage 1 of localBundleAdjust): k_ba_one_pose reads the observations in point order, indices and values side by side.
-static void ba_build_one_pose(const ms_ba_problem &Q, Prep &R) {
-    if (R.np_free != 1 || ba_edges_at_free_pose(Q, R.free2pose[0]) > PO_MAXE) return;
-    bool any_free_point = false;
-    for (int l = 0; l < Q.n_point && !any_free_point; ++l) any_free_point = !(Q.point_fixed && Q.point_fixed[l]);
-    R.pose_only = !any_free_point;
-    R.one_pose = any_free_point && Q.n_pose_edge <= OP_NT;
-    if (!R.one_pose) return;
-    R.op_pose.resize(Q.n_obs); R.op_o.resize(Q.n_obs); R.op_uvi.resize(3 * (size_t)Q.n_obs);
-    for (int ii = 0; ii < Q.n_obs; ++ii) {
-        const int o = R.pt_obs[ii];
-        R.op_pose[ii] = Q.obs_pose[o]; R.op_o[ii] = o;
-        R.op_uvi[3 * (size_t)ii] = Q.obs_uv[2 * (size_t)o]; R.op_uvi[3 * (size_t)ii + 1] = Q.obs_uv[2 * (size_t)o + 1]; R.op_uvi[3 * (size_t)ii + 2] = Q.obs_info[o];
-    }
-}
-// The pose-level envelope; decides whether the fused Schur pass applies (R.fused: no point with more than FS_OB free observations, no pose row wider than the LDS tile)
-static void ba_build_envelope(const ms_ba_problem &Q, Prep &R, BaEnvelope &E) {
-    E.first.resize(R.np_free); E.hfirst.resize(R.np_free); E.fp_start.assign(Q.n_point + 1, 0);
-    bvec<int> &first = E.first, &hfirst = E.hfirst;
-    bvec<int32_t> &fp_f = E.fp_f, &fp_o = E.fp_o;
-    for (int f = 0; f < R.np_free; ++f) first[f] = hfirst[f] = f;
-    int max_k = 0;
-    for (int l = 0; l < Q.n_point; ++l) {
-        E.fp_start[l] = (int32_t)fp_f.size();
-        if (Q.point_fixed && Q.point_fixed[l]) continue;
-        const size_t b0 = fp_f.size();
-        for (int ii = R.pt_start[l]; ii < R.pt_start[l + 1]; ++ii) {
-            const int o = R.pt_obs[ii], f = R.pidx[Q.obs_pose[o]];
-            if (f < 0) continue;
-            size_t at = fp_f.size();
-            fp_f.push_back(f); fp_o.push_back(o);
-            while (at > b0 && fp_f[at - 1] > f) { std::swap(fp_f[at - 1], fp_f[at]); std::swap(fp_o[at - 1], fp_o[at]); --at; }     // insertion: lists are short and mostly sorted
-        }
-        const int kk = (int)(fp_f.size() - b0);
-        max_k = std::max(max_k, kk);
-        if (kk) { const int fmin = fp_f[b0]; for (size_t a = b0; a < fp_f.size(); ++a) first[fp_f[a]] = std::min(first[fp_f[a]], fmin); }
-    }
-    E.fp_start[Q.n_point] = (int32_t)fp_f.size();
-    for (int k = 0; k < Q.n_pose_edge; ++k) {
-        const int fi = R.pidx[Q.edge_i[k]], fj = R.pidx[Q.edge_j[k]];
-        if (fi >= 0 && fj >= 0) { first[std::max(fi, fj)] = std::min(first[std::max(fi, fj)], std::min(fi, fj)); hfirst[std::max(fi, fj)] = std::min(hfirst[std::max(fi, fj)], std::min(fi, fj)); }
-    }
-    bool ok = R.np_free > 0 && max_k <= FS_OB;
-    for (int f = 0; f < R.np_free && ok; ++f) if (36 * (f - first[f] + 1) + 6 > kFsTileDoubles) ok = false;
-    R.fused = ok;
-}
-// record-based Schur work list: for every free point, every ordered pair (a, b) of its observations with free poses fb <= fa,
-// counting-sorted by (fa, fb), then cut into chunks of CH items of one pose pair
-static void ba_build_record_list(const ms_ba_problem &Q, Prep &R) {
-    const int np = R.np_free;
-    bvec<int32_t> count((size_t)np * np + 1, 0);
-    auto for_items = [&](auto &&fn) {
-        for (int l = 0; l < Q.n_point; ++l) {
-            if (Q.point_fixed && Q.point_fixed[l]) continue;
-            for (int ia = R.pt_start[l]; ia < R.pt_start[l + 1]; ++ia) {
-                const int a = R.pt_obs[ia], fa = R.pidx[Q.obs_pose[a]];
-                if (fa < 0) continue;
-                for (int ib = R.pt_start[l]; ib < R.pt_start[l + 1]; ++ib) {
-                    const int b = R.pt_obs[ib], fb = R.pidx[Q.obs_pose[b]];
-                    if (fb < 0 || fb > fa) continue;
-                    fn(fa * np + fb, a, b);
-                }
-            }
-        }
-    };
-    for_items([&](int key, int, int) { count[key + 1]++; });
-    bvec<int32_t> kstart(count);
-    for (size_t k = 1; k < kstart.size(); ++k) kstart[k] += kstart[k - 1];
-    bvec<int32_t> sorted(2 * (size_t)kstart.back()), cur(kstart.begin(), kstart.end() - 1);
-    for_items([&](int key, int a, int b) { const int pos = cur[key]++; sorted[2 * (size_t)pos] = a; sorted[2 * (size_t)pos + 1] = b; });
-    R.seg_start.push_back(0);
-    for (int key = 0; key < np * np; ++key) {
-        const int lo = kstart[key], hi = kstart[key + 1];
-        if (hi == lo) continue;
-        for (int i = lo; i < hi; i += CH) {
-            for (int t = 0; t < CH; ++t) {
-                const bool in = i + t < hi;
-                R.chunk_items.push_back(in ? sorted[2 * (size_t)(i + t)] : -1);
-                R.chunk_items.push_back(in ? sorted[2 * (size_t)(i + t) + 1] : -1);
-            }
-            ++R.n_chunks;
-        }
-        R.seg_pair.push_back(((key / np) << 16) | (key % np));
-        R.seg_start.push_back(R.n_chunks);
-        ++R.n_seg;
-    }
-}
-// envelope of the reduced camera matrix per 16-row block: the first structurally non-zero column.  Cholesky creates no fill left of it, so the
-// factorisation skips everything outside.
-static void ba_build_panel_lists(Prep &R, const BaEnvelope &E) {
-    const int np = R.np_free, n6i = 6 * np;
-    R.env16.assign(n6i / 16 + 2, 0);
-    for (int b = 0; b < (int)R.env16.size(); ++b) {
-        int e = n6i;
-        for (int r = 16 * b; r < 16 * b + 16; ++r) e = r < n6i ? std::min(e, 6 * E.first[r / 6]) : 0;     // the rhs row (r = n6) is dense
-        R.env16[b] = std::min(e, n6i);
-    }
-    // row tiles a Cholesky panel touches on average (those whose envelope reaches the panel): sizes the factorisation's sub-team
-    const int nblk = n6i / 16 + 1;
-    long long act = 0;
-    for (int pb = 0; pb * 16 < n6i; ++pb) for (int b = pb; b <= nblk; ++b) act += R.env16[(size_t)std::min(b, (int)R.env16.size() - 1)] <= pb * 16 + 15;
-    R.chol_tiles = n6i ? (double)act / ((n6i + 15) / 16) : 0.0;
-    if (np > kMaxFreePoses) {                   // the distributed factorisation walks these lists
-        R.act_start.push_back(0);
-        for (int pb = 0; pb * 16 < n6i; ++pb) {
-            const int m_rows = n6i - pb * 16 + 1;
-            for (int rt = 0; rt * 16 < m_rows; ++rt) if (R.env16[(size_t)std::min(pb + rt, (int)R.env16.size() - 1)] <= pb * 16 + 15) R.act_blk.push_back(rt);
-            R.act_start.push_back((int32_t)R.act_blk.size());
-        }
-    }
-}
-// A pass of the fused Schur phase, rows [r, r1): their envelope parts side by side in the tile, then the rhs segment
-static void ba_add_pass(FsHost &F, const BaEnvelope &E, int r, int r1) {
-    F.row0.push_back(r); F.row1.push_back(r1);
-    F.yoff.push_back(0); F.yoff.push_back((int32_t)F.rowoff.size());
-    int off2 = 0;
-    for (int f = r; f < r1; ++f) { F.rowoff.push_back(off2); off2 += 36 * (f - E.first[f] + 1); }
-    F.yoff[F.yoff.size() - 2] = off2;
-}
-// The fine set (teams): the POINTS are dealt out, not the rows -- a pass is a run of points (in the order of their first pose) with about 1 / team of the
-// block products; its rows are the poses those points see (they overlap with the neighbours': the sums meet in S through atomics).  Every
-// observation is then linearised once per damped solve.  (Row passes made each of the 32 workgroups re-evaluate every point that touches its
-// one or two rows: 8x the observations, 75 batches per workgroup instead of 10.)  Leaves F.by_points false, and no pass, for a window it does not suit.
-static void ba_choose_point_passes(const ms_ba_problem &Q, const Prep &R, const BaEnvelope &E, FsHost &F, bvec<bvec<int32_t>> &group_pts) {
-    const int np = R.np_free, want_passes = std::max(1, std::min(R.auto_team, np));
-    const bvec<int32_t> &fp_start = E.fp_start, &fp_f = E.fp_f;
-    bvec<int32_t> need_pre(np + 1, 0);                        // tile doubles of rows [0, f): a pass's need is a difference
-    for (int f = 0; f < np; ++f) need_pre[f + 1] = need_pre[f] + 36 * (f - E.first[f] + 1) + 6;
-    auto tile_need = [&](int r, int r1) { return r1 > r ? need_pre[r1] - need_pre[r] : 0; };
-    bvec<std::pair<uint32_t, int32_t>> order;      // (first pose << 16 | last pose, point)
-    double total_cost = 0;
-    for (int l = 0; l < Q.n_point; ++l) {
-        const int k = fp_start[l + 1] - fp_start[l];
-        if (k == 0) continue;
-        order.emplace_back(((uint32_t)fp_f[fp_start[l]] << 16) | (uint32_t)fp_f[fp_start[l + 1] - 1], l);
-        total_cost += 8.0 * k + 0.5 * k * (k + 1);
-    }
-    {   // by (first pose, last pose), then point: a counting sort over the np x np key space (std::sort of 2000 keys was 0.05 ms of the 0.45 ms create)
-        const size_t nk = (size_t)np * np;
-        if (order.size() > 64 && nk <= 65536) {
-            bvec<int32_t> cnt(nk + 1, 0);
-            auto key_of = [&](const std::pair<uint32_t, int32_t> &e) { return (size_t)(e.first >> 16) * np + (e.first & 0xFFFF); };
-            for (const auto &e : order) cnt[key_of(e) + 1]++;
-            for (size_t q = 0; q < nk; ++q) cnt[q + 1] += cnt[q];
-            bvec<std::pair<uint32_t, int32_t>> sorted(order.size());
-            for (const auto &e : order) sorted[cnt[key_of(e)]++] = e;      // (order is in point order: equal keys stay in it)
-            order.swap(sorted);
-        } else std::sort(order.begin(), order.end());
-    }
-    double acc_cost = 0;
-    int g_lo = np, g_hi = 0;
-    group_pts.emplace_back();
-    for (const auto &e : order) {
-        const int l = e.second, k = fp_start[l + 1] - fp_start[l], lo = std::min(g_lo, (int)(e.first >> 16)), hi = std::max(g_hi, (int)(e.first & 0xFFFF) + 1);
-        const bool full = !group_pts.back().empty() && (tile_need(lo, hi) > kFsTileDoubles ||
-                          ((int)group_pts.size() < want_passes && acc_cost >= total_cost * (double)group_pts.size() / want_passes));
-        if (full) { ba_add_pass(F, E, g_lo, g_hi); group_pts.emplace_back(); g_lo = (int)(e.first >> 16); g_hi = (int)(e.first & 0xFFFF) + 1; }
-        else { g_lo = lo; g_hi = hi; }
-        group_pts.back().push_back(l);
-        acc_cost += 8.0 * k + 0.5 * k * (k + 1);
-    }
-    if (!group_pts.back().empty()) ba_add_pass(F, E, g_lo, g_hi); else group_pts.pop_back();
-    F.by_points = true;
-    // a point seen from poses so far apart that the rows between them do not fit the tile (scattered covisibility): row passes for this window
-    for (size_t ps = 0; ps < F.row0.size(); ++ps) if (tile_need(F.row0[ps], F.row1[ps]) > kFsTileDoubles) F.by_points = false;
-    if (!F.by_points) { F.row0.clear(); F.row1.clear(); F.yoff.clear(); F.rowoff.clear(); group_pts.clear(); }
-}
-// Row passes (the coarse set, or a fine set by-points passes do not suit): greedy row ranges under the tile budget, as many rows per pass as the tile takes
-static void ba_choose_row_passes(const Prep &R, const BaEnvelope &E, FsHost &F) {
-    for (int r = 0; r < R.np_free;) {
-        int r1 = r, used = 0;
-        while (r1 < R.np_free) {
-            const int need = 36 * (r1 - E.first[r1] + 1) + 6;
-            if (used + need > kFsTileDoubles) break;
-            used += need; ++r1;
-        }
-        ba_add_pass(F, E, r, r1);
-        r = r1;
-    }
-}
-typedef bvec<std::pair<uint64_t, int32_t>> BaPassPoints;      // (signature of the point's pose set, point)
-// The points of pass ps, each with the signature of its free poses below the pass's last row (later poses have no pair with a row of this pass): points with the
-// same set get the same key, and keys order roughly by position in the window.  A by-points pass owns the points it was dealt; a row pass visits every free point
-// that one of its rows observes.
-static void ba_pass_points(const ms_ba_problem &Q, const Prep &R, const BaEnvelope &E, const FsHost &F, size_t ps, const bvec<bvec<int32_t>> &group_pts, bvec<int32_t> &stamp, BaPassPoints &pts) {
-    const int r0 = F.row0[ps], r1 = F.row1[ps];
-    auto add = [&](int l, int r_end) {
-        uint64_t h = 1469598103934665603ull; int fmin = 0x7fff, fmax = 0, kk = 0;
-        for (int jj = E.fp_start[l]; jj < E.fp_start[l + 1] && E.fp_f[jj] < r_end; ++jj) { h = (h ^ (uint64_t)E.fp_f[jj]) * 1099511628211ull; fmin = std::min(fmin, (int)E.fp_f[jj]); fmax = E.fp_f[jj]; ++kk; }
-        pts.emplace_back(((uint64_t)fmin << 48) | ((uint64_t)fmax << 32) | ((uint64_t)(kk & 0xFF) << 24) | (h & 0xFFFFFFull), l);
-    };
-    pts.clear();
-    if (F.by_points) { for (int l : group_pts[ps]) add(l, INT32_MAX); return; }
-    for (int fa = r0; fa < r1; ++fa)
-        for (int ii = R.fstart[fa]; ii < R.fstart[fa + 1]; ++ii) {
-            const int l = Q.obs_point[R.fobs[ii]];
-            if (stamp[l] == (int32_t)ps || (Q.point_fixed && Q.point_fixed[l])) continue;
-            stamp[l] = (int32_t)ps;
-            add(l, r1);
-        }
-}
-// Cuts the points of one pass (pts, sorted: points with the same set of poses next to each other) into batches of whole points with at most FS_OB observations,
-// and appends every batch's lane slots, format and pair list to F
-struct BaBatchCutter {
-    const ms_ba_problem &Q; const BaEnvelope &E; FsHost &F;
-    const BaPassPoints &pts;
-    bvec<std::pair<int32_t, uint16_t>> &bp2;               // (block key, pair) of the open batch: scratch
-    const int r0, r1;                                       // the pass's rows
-    int in_batch = 0;
-    bool uniform = true;                                    // every point of the open batch has the same pose set
-    uint64_t batch_key = 0;
-    int batch_k = 0, batch_first = -1;                      // poses per point / first point (index into pts) of the open batch
-    int poses_below_r1(int l) const {
-        const int j0 = E.fp_start[l];
-        int kk = 0;
-        while (j0 + kk < E.fp_start[l + 1] && E.fp_f[j0 + kk] < r1) ++kk;
-        return kk;
-    }
-    void pad_pairs() { while (F.pairs.size() % 8) F.pairs.push_back((uint16_t)0xFFFF); }
-    void pad_slots() {                                      // a batch owns FS_OB lane slots (the kernel addresses batch b at slot FS_OB b): the rest hold "no observation"
-        const size_t at = F.pobs.size(), slots = at / 4, padded = (slots + FS_OB - 1) / FS_OB * FS_OB;
-        if (padded == slots) return;
-        F.pobs.resize(4 * padded);
-        for (size_t q = slots; q < padded; ++q) { F.pobs[4 * q] = -1; F.pobs[4 * q + 1] = 0; F.pobs[4 * q + 2] = 0; F.pobs[4 * q + 3] = -1; }
-    }
-    void end_batch(int fmt) {
-        pad_pairs();
-        F.b_fmt.push_back(fmt);
-        pad_slots();
-        F.b_obs_start.push_back((int32_t)(F.pobs.size() / 4)); F.b_run_start.push_back((int32_t)F.pairs.size());
-        in_batch = 0;
-    }
-    // the usual case: G points with the same k poses -> pairs in (a, b) position order are already grouped by block, blocks ascending
-    void close_uniform(int pt_end) {
-        const int G = pt_end - batch_first, k = batch_k, j0 = E.fp_start[pts[batch_first].second];
-        int a0 = 0;
-        while (a0 < k && E.fp_f[j0 + a0] < r0) ++a0;
-        // (only for pass sets that own points = team launches: one window per keyframe, where the index build is a fifth of the call; a 256-window launch keeps the
-        //  lists -- enumerating costs its Schur pass 4 %, 11.4 against 10.9 ms, and its handles are built once.  schur_fused<true> runs exactly these sets)
-        if (F.by_points && k <= 31 && G <= 127) return end_batch(-1 - (G | (k << 7) | (a0 << 12)));      // the kernel enumerates the pairs of such a batch itself: nothing to build, nothing to upload
-        const size_t n_pairs = (size_t)G * ((size_t)k * (k + 1) / 2 - (size_t)a0 * (a0 + 1) / 2);
-        const size_t cap = std::min<size_t>(8, std::max<size_t>(1, (n_pairs + 63) / 64));
-        const int single_fmt = n_pairs <= 64 ? (int)n_pairs : 0;
-        for (int a = a0; a < k; ++a)
-            for (int b2 = 0; b2 <= a; ++b2) {
-                if (single_fmt) { for (int gp = 0; gp < G; ++gp) F.pairs.push_back((uint16_t)((gp * k + a) | ((gp * k + b2) << 8))); continue; }
-                size_t in_chunk = 0;
-                for (int gp = 0; gp < G; ++gp) {
-                    if (in_chunk == cap) { pad_pairs(); in_chunk = 0; }
-                    F.pairs.push_back((uint16_t)((gp * k + a) | ((gp * k + b2) << 8))); ++in_chunk;
-                }
-                pad_pairs();
-            }
-        end_batch(single_fmt);
-    }
-    // points with different pose sets: every pair with its block key, sorted by block
-    void close_mixed(int pt_end) {
-        bp2.clear();
-        int base = 0;
-        for (int q = batch_first; q < pt_end; ++q) {
-            const int l = pts[q].second, j0 = E.fp_start[l], kk = poses_below_r1(l);
-            for (int a = 0; a < kk; ++a) {
-                const int fa = E.fp_f[j0 + a];
-                if (fa < r0) continue;
-                for (int b2 = 0; b2 < kk; ++b2)
-                    if (E.fp_f[j0 + b2] <= fa) bp2.emplace_back((fa << 16) | E.fp_f[j0 + b2], (uint16_t)((base + a) | ((base + b2) << 8)));
-            }
-            base += kk;
-        }
-        std::stable_sort(bp2.begin(), bp2.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-        const int single_fmt = bp2.size() <= 64 ? (int)bp2.size() : 0;
-        if (single_fmt) for (const auto &e : bp2) F.pairs.push_back(e.second);
-        else {
-            // chunks of <= 8 pairs of one block; when the batch has few pairs the chunks get shorter so that more lanes share them
-            const size_t cap = std::min<size_t>(8, std::max<size_t>(1, (bp2.size() + 63) / 64));
-            size_t in_chunk = 0;
-            for (size_t i = 0; i < bp2.size(); ++i) {
-                if (i && (bp2[i].first != bp2[i - 1].first || in_chunk == cap)) { pad_pairs(); in_chunk = 0; }
-                F.pairs.push_back(bp2[i].second); ++in_chunk;
-            }
-        }
-        end_batch(single_fmt);
-    }
-    void close_batch(int pt_end) {
-        if (in_batch == 0) return;
-        if (uniform) close_uniform(pt_end); else close_mixed(pt_end);
-    }
-    void add_point(int q) {
-        const int l = pts[q].second, j0 = E.fp_start[l], kk = poses_below_r1(l);
-        if (in_batch + kk > FS_OB) close_batch(q);
-        if (in_batch == 0) { uniform = true; batch_key = pts[q].first; batch_k = kk; batch_first = q; }
-        else if (pts[q].first != batch_key || kk != batch_k) uniform = false;
-        if (uniform && q > batch_first) {                 // equal signatures: make sure the sets really are equal (the key holds a 24-bit hash)
-            const int jb = E.fp_start[pts[batch_first].second];
-            for (int a = 0; a < kk; ++a) if (E.fp_f[j0 + a] != E.fp_f[jb + a]) { uniform = false; break; }
-        }
-        const size_t at = F.pobs.size();
-        F.pobs.resize(at + 4 * (size_t)kk);
-        int32_t *w = F.pobs.data() + at;
-        for (int a = 0; a < kk; ++a, w += 4) { const int o = E.fp_o[j0 + a]; w[0] = o; w[1] = Q.obs_pose[o]; w[2] = l; w[3] = E.fp_f[j0 + a]; }
-        in_batch += kk;
-    }
-};
-// fused Schur pass (schur_fused): pose rows -> passes whose envelope part fits the LDS tile, points -> batches of <= 64 observations.
-// Only the set the launches will use is built (the other one aliases it: still correct, only slower, should ms_ba_set_team ask for the other regime later):
-// a batch that fills the chip always runs one workgroup per problem and gets the coarse set 0, a handful of windows gets teams and the fine set 1.
-static void ba_build_fused_passes(const ms_ba_problem &Q, Prep &R, const BaEnvelope &E, BaTimes &tm) {
-    const int np = R.np_free;
-    R.fs_cs.resize(2 * (size_t)np);                              // [np] first column of the row's envelope part, then [np] first column of the row's part of Hpp
-    for (int f = 0; f < np; ++f) { R.fs_cs[f] = 6 * E.first[f]; R.fs_cs[(size_t)np + f] = 6 * E.hfirst[f]; }
-    R.fs_only = R.auto_team == 1 ? 0 : 1;
-    if (!R.fused) return;
-    FsHost &F = R.fs[R.fs_only];
-    bvec<int32_t> stamp(Q.n_point, -1);
-    BaPassPoints pts;
-    bvec<std::pair<int32_t, uint16_t>> bp2;
-    bvec<bvec<int32_t>> group_pts;
-    {
-        BaLap lap(tm, BaTimes::kPasses);
-        if (R.fs_only == 1) ba_choose_point_passes(Q, R, E, F, group_pts);
-        if (!F.by_points) ba_choose_row_passes(R, E, F);
-    }
-    F.batch_start.push_back(0); F.b_obs_start.push_back(0); F.b_run_start.push_back(0);
-    F.pobs.reserve(4 * E.fp_f.size() * 2); F.pairs.reserve(8 * E.fp_f.size());
-    for (size_t ps = 0; ps < F.row0.size(); ++ps) {
-        { BaLap lap(tm, BaTimes::kPointKeys); ba_pass_points(Q, R, E, F, ps, group_pts, stamp, pts); }
-        { BaLap lap(tm, BaTimes::kSort); std::sort(pts.begin(), pts.end()); }      // points with the same set of poses next to each other: their pairs fall into the same blocks
-        BaLap lap(tm, BaTimes::kBatches);
-        BaBatchCutter cut{Q, E, F, pts, bp2, F.row0[ps], F.row1[ps]};
-        for (int q = 0; q < (int)pts.size(); ++q) cut.add_point(q);
-        cut.close_batch((int)pts.size());
-        F.batch_start.push_back((int32_t)F.b_obs_start.size() - 1);
-    }
-    BaLap lap(tm, BaTimes::kValues);
-    F.b_obs_start.push_back(F.b_obs_start.back());
-    F.puv.assign(F.pobs.size(), 0.0);                         // per lane slot: u, v, information, 0
-    for (size_t i = 0; i < F.pobs.size() / 4; ++i) {
-        const int o = F.pobs[4 * i];
-        if (o >= 0) { F.puv[4 * i] = Q.obs_uv[2 * (size_t)o]; F.puv[4 * i + 1] = Q.obs_uv[2 * (size_t)o + 1]; F.puv[4 * i + 2] = Q.obs_info[o]; }
-    }
-}
-// windowed Cholesky (cholesky_window): active 16-row blocks per panel, LDS slots, tiles entering per panel
-static void ba_build_chol_window(Prep &R, const BaEnvelope &E) {
-    const int np = R.np_free, n6i = 6 * np, nblk = (n6i + 15) / 16;
-    bvec<int32_t> &slot = R.cw_slot, &act_start = R.cw_act_start, &act = R.cw_act, &load_start = R.cw_load_start, &load = R.cw_load;
-    bvec<int> ent(nblk, 0);
-    for (int b = 0; b < nblk; ++b) {
-        int e = n6i;
-        for (int r = 16 * b; r < std::min(16 * b + 16, n6i); ++r) e = std::min(e, 6 * E.first[r / 6]);
-        ent[b] = std::min(e / 16, b);
-    }
-    for (int b = nblk - 2; b >= 0; --b) ent[b] = std::min(ent[b], b);      // (a block is active at its own panel at the latest)
-    slot.assign(nblk, 0);
-    bvec<int> free_slots, active;
-    int W = 0;
-    bvec<bvec<int>> entering(nblk);
-    for (int b = 0; b < nblk; ++b) entering[ent[b]].push_back(b);
-    act_start.push_back(0); load_start.push_back(0);
-    for (int pnl = 0; pnl < nblk; ++pnl) {
-        if (pnl > 0) active.erase(std::find(active.begin(), active.end(), pnl - 1));      // block pnl-1 is factored ...
-        if (pnl > 1) free_slots.push_back(slot[pnl - 2]);           // ... its slot is reused one panel later: panel pnl's tiles are fetched while pnl-1 is still updating
-        std::sort(free_slots.begin(), free_slots.end(), std::greater<int>());
-        for (int b : entering[pnl]) {
-            int sl;
-            if (!free_slots.empty()) { sl = free_slots.back(); free_slots.pop_back(); } else sl = W++;
-            slot[b] = sl;
-            active.push_back(b);
-        }
-        std::sort(active.begin(), active.end());
-        for (int bi : active)
-            for (int bj : active) {
-                if (bj > bi) break;
-                if (bi == bj && bi == pnl) continue;                       // the panel's own diagonal tile is fetched by the factoring wave
-                if (ent[bi] == pnl || ent[bj] == pnl) { load.push_back(bi | (slot[bi] << 16)); load.push_back(bj | (slot[bj] << 16)); }
-            }
-        load_start.push_back((int32_t)load.size() / 2);
-        for (int b : active) if (b != pnl) act.push_back(b | (slot[b] << 16));
-        act_start.push_back((int32_t)act.size());
-    }
-    if (W < 3) W = 3;                                                // the back substitution keeps three columns (<= W tiles each) in the W x W tile area
-    const size_t fixed = ((size_t)W * W * CT + 16 + 16 * (size_t)W + 32 + 256 + 16) * sizeof(double), zbytes = (size_t)((n6i + 15) & ~15) * sizeof(double);
-    const bool fits = R.fused && nblk < 65536 && W >= 1 && W < 256;
-    R.cw_W = fits && fixed <= kLdsBytes ? W : 0;
-    R.cw_zglobal = fixed + zbytes > kLdsBytes;                       // a long trajectory: the tiles fit, the 8 n bytes of the rhs do not -- it stays in global memory
-    const size_t meta = 4 * (slot.size() + act_start.size() + load_start.size() + act.size() + load.size());
-    R.cw_meta_lds = R.cw_W > 0 && fixed + 2 * zbytes + meta <= kLdsBytes;      // (and the reciprocal pivots: another n doubles)
-}
-
-// ---------------------------------------------------------------- the device block of a handle: every array is named ONCE, in ba_lay_out
-// input() / work() reserve an array's bytes (256-byte aligned, never less than one line), put the array's OFFSET into the descriptor's pointer member and note the
-// member; relocate() turns the offsets into addresses once the block is known.  input() also notes what stage() copies into the problem's staging block.
-// An absent array gets a null pointer and no copy; an absent INPUT still reserves its bytes, an absent WORK area only the minimum.
-struct BaLayout {
-    struct Copy { size_t at; const void *src; size_t bytes; };
-    size_t total = 0, desc_at = 0;                            // bytes so far; where a single problem's two descriptors ride
-    bvec<Copy> copies;
-    bvec<void *> members;                                     // pointer members that hold an offset
-    size_t reserve(size_t bytes) { const size_t o = total; total += ms_align_up(bytes ? bytes : 8, 256); return o; }
-    template <class T> void note(T *&m, size_t at, bool present) {
-        m = present ? reinterpret_cast<T *>(at) : nullptr;
-        if (present) members.push_back(const_cast<void *>(static_cast<const void *>(&m)));
-    }
-    template <class T, class S> void input(T *&m, const S *src, size_t count, bool present = true, size_t slack = 0) {
-        static_assert(sizeof(T) == sizeof(S), "an input array is uploaded as it is");
-        const size_t at = reserve((count + slack) * sizeof(T));
-        note(m, at, present);
-        if (present && count) copies.push_back(Copy{at, src, count * sizeof(T)});
-    }
-    template <class T, class S> void input(T *&m, const bvec<S> &v, bool present = true, size_t slack = 0) { input(m, v.data(), v.size(), present, slack); }
-    template <class T> void work(T *&m, size_t count, bool present = true) { note(m, reserve(present ? count * sizeof(T) : 0), present); }
-    void relocate(char *base) const {
-        for (void *m : members) { uintptr_t v; std::memcpy(&v, m, sizeof(v)); v += reinterpret_cast<uintptr_t>(base); std::memcpy(m, &v, sizeof(v)); }
-    }
-    void stage(const Prep &R, char *block) const {            // (block: the image of [R.in_lo, R.in_hi), zeroed)
-        for (size_t i = R.copy_lo; i < R.copy_hi; ++i) std::memcpy(block + (copies[i].at - R.in_lo), copies[i].src, copies[i].bytes);
-    }
-};
-// One problem's part of the device block and its descriptor H (A: the four arrays of its second linearisation set).  The ORDER is part of the format.
-static void ba_lay_out(const ms_ba_problem &Q, Prep &R, bool single, size_t pack_doubles, BaLayout &L, BaProb &H, ms_ba::AltPtrs &A) {
-    const size_t n6 = 6 * (size_t)R.np_free, n_point = Q.n_point, n_obs = Q.n_obs;
-    const bool streams = !R.fo_lo.empty();
-    H.n_pose = Q.n_pose; H.n_point = Q.n_point; H.n_obs = Q.n_obs; H.n_edge = Q.n_pose_edge; H.np_free = R.np_free; H.n6 = 6 * R.np_free;
-    H.max_iters = Q.max_iters; H.huber = Q.huber_delta; H.team = 1; H.chol_team = 1; H.debug_reject = 0;
-    H.n_chunks = R.n_chunks; H.n_seg = R.n_seg; H.fused = R.fused ? 1 : 0;
-    H.cw_W = R.cw_W; H.cw_zglobal = R.cw_zglobal ? 1 : 0; H.cw_meta_lds = R.cw_meta_lds ? 1 : 0;
-    // inputs first, contiguous: they go up in ONE host->device copy per problem
-    R.in_lo = L.total; R.copy_lo = L.copies.size();
-    L.input(H.pose0, Q.pose, 7 * Q.n_pose); L.input(H.point0, Q.point, 3 * n_point);
-    L.input(H.pidx, R.pidx); L.input(H.point_fixed, Q.point_fixed, n_point, Q.point_fixed != nullptr);
-    L.input(H.obs_pose, Q.obs_pose, n_obs); L.input(H.obs_point, Q.obs_point, n_obs); L.input(H.obs_uv, Q.obs_uv, 2 * n_obs); L.input(H.obs_info, Q.obs_info, n_obs);
-    L.input(H.pt_start, R.pt_start); L.input(H.pt_obs, R.pt_obs); L.input(H.fstart, R.fstart); L.input(H.fobs, R.fobs);
-    L.input(H.fo_lo, R.fo_lo, streams); L.input(H.fo_uvi, R.fo_uvi, streams);
-    L.input(H.free2pose, R.free2pose);
-    L.input(H.edge_i, Q.edge_i, Q.n_pose_edge); L.input(H.edge_j, Q.edge_j, Q.n_pose_edge); L.input(H.edge_meas, Q.edge_meas, 7 * Q.n_pose_edge); L.input(H.edge_info, Q.edge_info, 36 * Q.n_pose_edge);
-    L.input(H.chunk_items, R.chunk_items); L.input(H.seg_start, R.seg_start); L.input(H.seg_pair, R.seg_pair);
-    L.input(H.env16, R.env16); L.input(H.act_start, R.act_start); L.input(H.act_blk, R.act_blk);
-    L.input(H.fs_cs, R.fs_cs);
-    L.input(H.cw_slot, R.cw_slot); L.input(H.cw_act_start, R.cw_act_start); L.input(H.cw_act, R.cw_act); L.input(H.cw_load_start, R.cw_load_start); L.input(H.cw_load, R.cw_load);
-    for (int set = 0; set < 2; ++set) {                      // (the set that was not built is empty here; ms_ba_create makes it an alias of the other)
-        const FsHost &S = R.fs[set];
-        FsSet &F = H.fs[set];
-        const bool built = R.fused && set == R.fs_only;
-        if (built) { F.n_pass = (int32_t)S.row0.size(); F.by_points = S.by_points ? 1 : 0; }
-        L.input(F.row0, S.row0, built); L.input(F.row1, S.row1, built); L.input(F.batch_start, S.batch_start, built);
-        L.input(F.b_obs_start, S.b_obs_start, built); L.input(F.b_run_start, S.b_run_start, built); L.input(F.b_fmt, S.b_fmt, built); L.input(F.pobs, S.pobs, built); L.input(F.puv, S.puv, built);
-        L.input(F.pairs, S.pairs, built, 8); L.input(F.rowoff, S.rowoff, built); L.input(F.yoff, S.yoff, built);
-    }
-    L.input(H.op_pose, R.op_pose, R.one_pose); L.input(H.op_o, R.op_o, R.one_pose); L.input(H.op_uvi, R.op_uvi, R.one_pose);
-    if (single) L.desc_at = L.reserve(2 * sizeof(BaProb));      // a single problem's two descriptors travel with its inputs: ONE copy per create
-    R.in_hi = L.total; R.copy_hi = L.copies.size();
-    // state and work areas
-    L.work(H.pose, 7 * (size_t)Q.n_pose); L.work(H.pose_bk, 7 * (size_t)Q.n_pose); L.work(H.point, 3 * n_point); L.work(H.point_bk, 3 * n_point);
-    L.work(H.Hpp, n6 * n6); L.work(H.S, n6 * n6); L.work(H.bp, n6); L.work(H.dp, n6); L.work(H.y, n6);
-    L.work(H.Hll, 6 * n_point); L.work(H.bl, 3 * n_point); L.work(H.Hinv, 6 * n_point); L.work(H.Hpl, R.fused ? 1 : 18 * (n_obs + 1));      // (the fused pass keeps no Hpl / Y records)
-    L.work(H.dl, 3 * n_point); L.work(H.chi2_obs, n_obs); L.work(H.stats, 16);
-    L.work(H.Y, R.fused ? 1 : 18 * (n_obs + 1)); L.work(H.zrow, n6 + 16);
-    L.work(H.dinv, n6 + 16);
-    if (R.np_free > kMaxFreePoses) L.work(H.panG, (n6 + 17) * NB);
-    L.work(H.bar, 64); L.work(H.red, 4 * kMaxTeam); L.work(H.flag, 64);     // team state on lines of their own (256 B each at least)
-    L.work(H.op_rec, 28 * n_point, R.one_pose); L.work(H.op_red, 2 * (size_t)kMaxTeam * OP_NV, R.one_pose);
-    // the second set of the linearisation's outputs (k_ba_lm's fused trial schedule): only for handles whose launches run one workgroup per problem on the streams
-    const bool alt_set = streams && R.fused;
-    L.work(A.Hpp, n6 * n6, alt_set); L.work(A.bp, n6, alt_set); L.work(A.Hll, 6 * n_point, alt_set); L.work(A.bl, 3 * n_point, alt_set);
-    L.work(H.pack, pack_doubles, pack_doubles != 0);
-}
-// ONE device block per handle (arena + the problem descriptors behind it), taken from the context's cache of destroyed handles when one is large enough
-static int ba_take_block(ms_ctx *c, ms_ba *B, size_t need) {
-    // best fit among the kept blocks, but never one more than kBaCacheSlack times the request: a small window must not sit on the
-    // gigabytes a global-BA handle left behind (that block waits for the next large request, or goes when the cache is trimmed)
-    int best = -1;
-    for (int i = 0; i < 4; ++i)
-        if (c->ba_cache[i].p && c->ba_cache[i].bytes >= need && c->ba_cache[i].bytes / kBaCacheSlack <= need &&
-            (best < 0 || c->ba_cache[i].bytes < c->ba_cache[best].bytes)) best = i;
-    if (best >= 0) { B->d_arena = static_cast<char *>(c->ba_cache[best].p); B->arena_bytes = c->ba_cache[best].bytes; c->ba_cache[best] = {}; return MS_OK; }
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&B->d_arena), need);
-    ++g_ba_host_allocs;
-    if (e != hipSuccess) {                                  // out of memory with blocks kept for later: give them back and try once more
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(c->stream);
-        for (auto &b : c->ba_cache) if (b.p) { (void)hipFree(b.p); b = {}; }
-        e = hipMalloc(reinterpret_cast<void **>(&B->d_arena), need);
-    }
-    if (e != hipSuccess) { (void)hipGetLastError(); return ms_fail(c, MS_ERR_HIP, "ms_ba_create: cannot allocate %zu bytes: %s", need, hipGetErrorString(e)); }
-    B->arena_bytes = need;
-    return MS_OK;
-}
-// the context's page-locked staging block, free for this create and at least `need` bytes
-static hipError_t ba_reserve_stage(ms_ctx *c, size_t need) {
-    if (c->ba_stage_busy) { (void)hipEventSynchronize(c->ba_stage_ev); c->ba_stage_busy = false; }      // (the previous create's upload: long done)
-    hipError_t e = hipSuccess;
-    if (!c->ba_stage_ev) { e = hipEventCreateWithFlags(&c->ba_stage_ev, hipEventDisableTiming); ++g_ba_host_allocs; }
-    if (e == hipSuccess && c->ba_stage_bytes < need) {
-        if (c->ba_stage) (void)hipHostFree(c->ba_stage);
-        c->ba_stage = nullptr; c->ba_stage_bytes = 0;
-        const size_t want = std::min(kBaStageMax, ms_align_up(need + need / 4, (size_t)1 << 16));
-        e = hipHostMalloc(&c->ba_stage, want, hipHostMallocDefault); ++g_ba_host_allocs;
-        if (e == hipSuccess) c->ba_stage_bytes = want;
-    }
-    return e;
-}
-// the eager results of a single small problem (B->pack_doubles): a page-locked block that stays with the handle object
-static hipError_t ba_reserve_result(ms_ba *B) {
-    if (B->pack_doubles * sizeof(double) <= B->h_result_bytes) return hipSuccess;
-    if (B->h_result) (void)hipHostFree(B->h_result);
-    B->h_result = nullptr; B->h_result_bytes = 0;
-    const size_t want = ms_align_up(B->pack_doubles * sizeof(double) * 2, (size_t)4096);
-    const hipError_t e = hipHostMalloc(&B->h_result, want, hipHostMallocDefault); ++g_ba_host_allocs;
-    if (e == hipSuccess) B->h_result_bytes = want;
-    return e;
-}
-// the descriptors of a new handle (both sets) go up; stage_at: the end of the inputs in the context's staging block
-static hipError_t ba_upload_new_descriptors(ms_ctx *c, ms_ba *B, bool staged, size_t stage_at) {
-    const int n = B->n;
-    hipError_t e;
-    ba_make_alt(B);
-    if (n == 1) {                                       // (went up with the inputs)
-        e = staged ? hipEventRecord(c->ba_stage_ev, c->stream) : hipSuccess;
-        if (staged) c->ba_stage_busy = e == hipSuccess;
-    } else if (staged) {                                // the descriptors (both sets, side by side like on the device) follow the inputs out of the same block; its next user waits for ba_stage_ev
-        char *at = static_cast<char *>(c->ba_stage) + stage_at;
-        std::memcpy(at, B->host.data(), sizeof(BaProb) * n);
-        std::memcpy(at + sizeof(BaProb) * n, B->host_alt.data(), sizeof(BaProb) * n);
-        e = hipMemcpyAsync(B->d_probs, at, 2 * sizeof(BaProb) * n, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(c->ba_stage_ev, c->stream);
-        c->ba_stage_busy = e == hipSuccess;
-    } else {
-        e = hipMemcpy(B->d_probs, B->host.data(), sizeof(BaProb) * n, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(B->d_probs_alt, B->host_alt.data(), sizeof(BaProb) * n, hipMemcpyHostToDevice);
-    }
-    return e;
-}
-// the solvers' dynamic LDS sizes: once per device and process
-static hipError_t ba_set_lds_attributes(ms_ctx *c) {
-    static std::atomic<unsigned long long> attr_done{0};
-    if ((attr_done.load() >> (c->device & 63)) & 1ull) return hipSuccess;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_lm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_pose_only), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPoLdsBytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_one_pose<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOpLdsBytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_ba_one_pose<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOpLdsBytes) != hipSuccess) return hipErrorUnknown;
-    attr_done.fetch_or(1ull << (c->device & 63));
-    return hipSuccess;
-}
 extern "C" {
 
 int ms_ba_create(ms_ctx *c, const ms_ba_problem *problems, int n, ms_ba **out) {

@@ -21,6 +21,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include "ms_lanes_f64.h"
 
 namespace {
 
@@ -42,27 +43,6 @@ struct S3Desc {                                  // one problem as the kernel se
 };
 
 struct S3Acc { double H[28], b[7], chi; };
-
-template <int CTRL> __device__ __forceinline__ double dpp_d(double v) {       // the double of the lane the DPP control names (all source lanes active)
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false), hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// 1 / sqrt(d) for the Cholesky pivots: v_rsq_f64 and two Newton steps (full double precision)
-__device__ __forceinline__ double rsqrt_d(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    double e = fma(-d * y, y, 1.0);
-    y = fma(y * e, fma(e, 0.375, 0.5), y);
-    e = fma(-d * y, y, 1.0);
-    return fma(y * e, 0.5, y);
-}
-
-// RobustKernelHuber as oracle/ba.c:172-176 restates it
-__device__ __forceinline__ void huber(double chi2, double delta, double &rho, double &w) {
-    const double dsqr = delta * delta;
-    if (delta <= 0 || chi2 <= dsqr) { rho = chi2; w = 1; }
-    else { const double s = sqrt(chi2); rho = 2 * s * delta - dsqr; w = delta / s; }
-}
 
 // one edge into the sums: H += J^T (w info) J, b += -J^T (w info) e, chi += rho
 __device__ __forceinline__ void add_edge(S3Acc &A, const double (&J0)[7], const double (&J1)[7], double e0, double e1, double info, double delta) {
