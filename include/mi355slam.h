@@ -182,6 +182,11 @@ int ms_orb_capacity(const ms_orb *orb);
 int ms_keypoints_pack(ms_ctx *ctx, const ms_keypoints *view, int frame, int n, const double *bearing, uint8_t *records_host);
 int ms_keypoints_unpack(const uint8_t *records, int n, float *x, float *y, float *angle, int32_t *octave, double *bearing, uint32_t *desc);
 
+/* How many keypoints a wave of the describe kernel walks one after another (a test hook; outputs are bit for bit the same for every value).
+ * 0 = the automatic launch plan (the default: long strips first, a tail of one-keypoint blocks; a small launch is one keypoint per wave);
+ * 1 .. 8 = every workgroup uses r, no taper.  MS_ERR_INVALID for anything else.  Holds for the calls that follow. */
+int ms_orb_set_describe_strip(ms_orb *orb, int r);
+
 /* Per-kernel timing of ms_orb_extract with HIP events on the context stream (off by default).
  * Stage order: 0 resize (all levels), 1 blur, 2 fast, 3 select, 4 tracks, 5 describe.
  * ms_orb_stage_ms synchronises and returns the durations of the LAST ms_orb_extract call. */

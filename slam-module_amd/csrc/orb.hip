@@ -19,6 +19,7 @@
 // x86-64 SSE2 scalar build (CMakeLists.txt:4-5: -O2, no -march).
 #include "ms_internal.h"
 #include "fast_tiles.h"
+#include "describe_strips.h"
 #include "describe_lanes.h"
 #include "describe_steer.h"
 #include "describe_brief_index.h"
@@ -1045,15 +1046,40 @@ __global__ __launch_bounds__(256) void k_slots(const int16_t *__restrict__ det_x
     if (l == TL.levels - 1 && threadIdx.x == 0) out_count[f] = min(base + cnt, capacity);
 }
 
-// Keypoints a wave works on at once.  k_describe is bound by the memory system's throughput of scattered partial-line fetches: 2.0 GB
-// of HBM traffic per 256-frame launch for 0.87 GB of patch bytes, in 0.53 ms = 3.8 TB/s.  Measured without effect on its time: 6, 7
-// or 8 waves per SIMD; two keypoints side by side in a wave (0.64 ms, register pressure) or four one after another with the next
-// one's patches prefetched (0.63 ms); 16-byte row pieces (3 loads per keypoint instead of 11); all outputs in one scattered store; a
-// per-slot table that removes the slot -> counts -> coordinates -> geometry chain of dependent loads; and a quarter fewer VALU
-// instructions (the moment sums below and the degree -> radian product).
-constexpr int kDescPerWave = 1;
+// Keypoints per wave.  A wave of k_describe walks a STRIP of keypoints one after another (describe_strips.h: 4 in the long region of a large launch, then 2, then 1;
+// 1 throughout for a launch without more than two device-fulls of blocks), in the same registers and the same LDS slab, and pays once per strip what a wave of one
+// keypoint paid per keypoint: the tables to LDS, the lane tables, the frame's counts, the block barrier, and the chain of dependent scalar loads slot entry ->
+// level -> geometry -> frame pointers (13 s_waitcnt lgkmcnt(0), 5 vmcnt and the barrier in the 197 instructions in front of the first window load; now 31
+// instructions and no wait between a keypoint's record and its window loads).  Measured on 256 x 720p (profiles/r08_a_ab_describe_strips.txt), ms per launch:
+//     one keypoint per wave (the parent)         0.4376 .. 0.4437
+//     long strips of 2 / 4 / 8                   0.436  / 0.4168 .. 0.4188 / 0.4394 .. 0.4416
+// Longer is not better: the slots in flight at one time span r times as many frames, whose pyramids share the caches (FETCH_SIZE + 17 % at r = 4, + 24 % at
+// r = 8), and that eats what the setup saves.  With the next keypoint's window fetched under the BRIEF tests of the current one (64 VGPRs, no scratch, the
+// same LDS) the kernel took 0.4185 .. 0.4196 ms against 0.4168 .. 0.4188 without: not kept.
+// What round 1 measured on ITS kernel (separate blurred patch, a level search per wave, 7 waves per SIMD, the blur on the vector pipe) does not carry over:
+// "four one after another with the next one's patches prefetched" was 0.63 of 0.60 ms there, and of the same list the per-slot table (0.583 -> 0.542 ms)
+// and the eighth wave per SIMD (0.542 -> 0.511 ms) paid once the kernel had changed.  Still on record from that round: two keypoints SIDE BY SIDE in a wave
+// cost registers (100 VGPRs, 30 KB LDS, slower: DESIGN section 10); 16-byte row pieces and one scattered store for all outputs did nothing.
 
-struct DescKp { int x, y, oct, tid_out; float ox, oy; bool valid; };
+// A keypoint of a wave's strip as the loop wants it: everything a lane resolved in front of the loop (k_describe), read back as scalars
+struct DescKp { int x, y, oct, tid_out, pitch, w, h; float ox, oy; bool inner; uint64_t off; };
+// The per-wave tables live in the dwords of the wave's slab that neither the window (0 .. 575, with the parked ninth piece) nor pass 1 of the
+// blur (row 47's fourth 16-byte unit ends at dword 579) touches: the geometry of the 16 levels, 6 dwords each, and the strip's keypoints, 12 each
+constexpr int kDescGeoDword = 584, kDescGeoStride = 6, kDescRecDword = kDescGeoDword + kDescGeoStride * MS_MAX_LEVELS, kDescRecStride = 12;
+static_assert(kDescRecDword % 4 == 0 && kDescRecDword + kDescRecStride * describe_strips::kMaxStrip <= describe_lanes::kSlabDwords, "per-wave tables fit behind the window");
+struct DescRec { uint4 a, b, c; };                           // a record as the lanes read it (all the same one: the address is wave-uniform)
+__device__ __forceinline__ DescRec desc_read(const uint32_t *rec) {
+    return DescRec{*reinterpret_cast<const uint4 *>(rec), *reinterpret_cast<const uint4 *>(rec + 4), *reinterpret_cast<const uint4 *>(rec + 8)};
+}
+__device__ __forceinline__ DescKp desc_scalars(const DescRec &r) {
+    const uint4 a = r.a, b = r.b, c = r.c;
+    auto s = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    DescKp K;
+    K.x = (int)s(a.x); K.y = (int)s(a.y); K.oct = (int)(s(a.z) & 0xFFu); K.inner = (s(a.z) >> 8) != 0; K.tid_out = (int)s(a.w);
+    K.ox = __uint_as_float(s(b.x)); K.oy = __uint_as_float(s(b.y)); K.pitch = (int)s(b.z); K.w = (int)s(b.w);
+    K.h = (int)s(c.x); K.off = (uint64_t)s(c.y) | ((uint64_t)s(c.z) << 32);
+    return K;
+}
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 // r[m] in lane row q (the wave's four rows of 16 lanes)  ->  r[q] of lane row m: the 2 x 2 blocks trade places across the wave's halves
 // (v_permlane32_swap: lanes 32-63 of the first operand <-> lanes 0-31 of the second), then each block is transposed across neighbouring rows
@@ -1066,15 +1092,18 @@ __device__ __forceinline__ void transpose4_rows(uint32_t (&r)[4]) {
 }
 
 // amdgpu_waves_per_eu(8, 8): the register allocation aims at 8 waves per SIMD (the kernel is bound by how many keypoints are in flight)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_describe(FrameSrc src, TileLevels TL, const uint4 *__restrict__ moment_tab, const float4 *__restrict__ pattern_f,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_describe(FrameSrc src, TileLevels TL, describe_strips::Plan plan, const uint4 *__restrict__ moment_tab, const float4 *__restrict__ pattern_f,
                                                   const uint2 *__restrict__ slot_tab, int capacity, int max_tracks, int lk_level,
                                                   const int16_t *__restrict__ trk_x, const int16_t *__restrict__ trk_y, const float *__restrict__ trk_px,
                                                   const float *__restrict__ trk_py, const int32_t *__restrict__ trk_id, const int32_t *__restrict__ trk_count,
                                                   float *__restrict__ out_x, float *__restrict__ out_y, float *__restrict__ out_angle,
                                                   int32_t *__restrict__ out_octave, uint32_t *__restrict__ out_desc, int32_t *__restrict__ out_track,
                                                   const int32_t *__restrict__ out_count) {
-    const int f = blockIdx.y, lane = threadIdx.x & 63;
-    const int slot0 = (blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * kDescPerWave;   // wave-uniform: everything derived from it is scalar
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // block -> (frame, first slot of the block's strips, strip length): scalar arithmetic on the plan's region records (describe_strips.h), no load
+    const describe_strips::Strip strip = describe_strips::decode(plan, blockIdx.x);
+    const int f = strip.frame, R = min(strip.r, describe_strips::kMaxStrip);
+    const int slot0 = strip.slot0 + wv;                      // the wave's first slot; its k-th keypoint is slot0 + 4 k.  Wave-uniform: everything derived from it is scalar
     // A keypoint is a chain of dependent memory round trips (its slot -> coordinates -> patch -> angle -> BRIEF samples) and the
     // everything that does not depend on the keypoint is requested up front -- the lane's patch-offset table and the counts of
     // ALL levels in one batch (not one load per loop trip).
@@ -1083,33 +1112,67 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // wave's chain, and this kernel is bound by the LENGTH of that chain (ablation: prologue + window fetch alone 0.35 of 0.60 ms, no prologue chain -0.07 ms,
     // a quarter fewer vector instructions 0.00 ms).  They are block-wide tables in LDS now, loaded first thing, under the count loads.
     __shared__ uint4 s_tab[64 + 256];                        // [0..31] horizontal taps (dt, n), [32..63] vertical taps, [64..319] the point pairs [q][lane]
-    if (threadIdx.x < 64) s_tab[threadIdx.x] = moment_tab[64 + threadIdx.x];
-    s_tab[64 + threadIdx.x] = reinterpret_cast<const uint4 *>(pattern_f)[threadIdx.x];
+    // (every load of the prologue is issued before the first of them is waited for: the stores to LDS stand together in front of the barrier.  All four waves
+    // fetch the tap table and wave 0 stores it -- behind a test of the thread index the load was waited for before the next one was issued)
+    const uint4 tap_v = moment_tab[64 + lane], pair_v = reinterpret_cast<const uint4 *>(pattern_f)[threadIdx.x];
     const uint4 dm = moment_tab[lane];                       // disc mask of the lane's four patch dwords
     const uint32_t dmask[4] = {dm.x, dm.y, dm.z, dm.w};
-    const uint32_t wpack = reinterpret_cast<const uint32_t *>(moment_tab + 128)[lane];   // (row, byte) of the lane's first three window pieces (describe_lanes::win_pack)
-    // the frame's keypoint total and this wave's table entry (k_slots): both addresses are known from the block index, one round trip
+    const uint32_t wpack_w = reinterpret_cast<const uint32_t *>(moment_tab + 128)[lane];   // (row, byte) of the lane's first three window pieces (describe_lanes::win_pack)
+    __shared__ __attribute__((aligned(16))) uint32_t s_patch[4][describe_lanes::kSlabDwords];   // a wave's slab: see below
+    uint32_t *const win = &s_patch[wv][0], *const geo = win + kDescGeoDword, *const rec = win + kDescRecDword;
+    // Everything a strip's keypoints need from memory is requested here, together, from addresses that depend on the block index and the kernel
+    // arguments alone (one round trip in front of the barrier, none per keypoint): the frame's totals; the strip's table entries (k_slots), lane j
+    // the entry of the wave's j-th keypoint (the lanes behind the strip read its last entry once more), with the tracker's fields wherever the slot CAN
+    // be a tracker point (slot < max_tracks: whether it is one, slot < trk_count[f], is known only when the loads are back); and the geometry of all
+    // levels, lane l that of level l, into the wave's table (a lane-indexed read of the kernel arguments).  Level 0 is entered as the other levels are:
+    // its pitch, and its plane as an offset from the frame's part of the slab (a 64-bit difference; the sum below wraps back to the caller's pointer).
     const int total = out_count[f], nt = trk_count[f];
-    const uint2 ent = slot_tab[(uint64_t)f * capacity + min(slot0, capacity - 1)];
-    __syncthreads();                                         // the tables are in LDS (every wave of the block is still here)
-    if (slot0 >= total) return;
-    DescKp K[kDescPerWave];
-#pragma unroll
-    for (int k = 0; k < kDescPerWave; ++k) {
-        const int slot = slot0 + k;
-        K[k].valid = slot < total;
-        const int sl = K[k].valid ? slot : slot0;            // an absent second keypoint mirrors the first (its results are not stored)
-        if (sl < nt) {
-            const uint64_t s2 = (uint64_t)f * max_tracks + sl;
-            K[k].x = trk_x[s2]; K[k].y = trk_y[s2]; K[k].ox = trk_px[s2]; K[k].oy = trk_py[s2]; K[k].oct = lk_level; K[k].tid_out = trk_id[s2];
-        } else {
-            const uint2 e2 = k == 0 ? ent : slot_tab[(uint64_t)f * capacity + sl];
-            const int level = (int)e2.y;
-            K[k].x = (int)(e2.x & 0xFFFFu); K[k].y = (int)(e2.x >> 16); K[k].oct = level; K[k].tid_out = -1;
-            K[k].ox = __fmul_rn((float)K[k].x, TL.L[level].scale);     // orb_extractor.cpp:156
-            K[k].oy = __fmul_rn((float)K[k].y, TL.L[level].scale);
-        }
+    const uint8_t *const slab_f = src.slab + (uint64_t)f * TL.slab_stride;
+    const int myslot = slot0 + 4 * min(lane, R - 1);
+    const uint2 ent = slot_tab[(uint64_t)f * capacity + min(myslot, capacity - 1)];
+    int tx = 0, ty = 0, tid = -1;
+    float tpx = 0.f, tpy = 0.f;
+    if (myslot < max_tracks) {
+        const uint64_t s2 = (uint64_t)f * max_tracks + myslot;
+        tx = trk_x[s2]; ty = trk_y[s2]; tpx = trk_px[s2]; tpy = trk_py[s2]; tid = trk_id[s2];
     }
+    const TileLevel &GL = TL.L[lane & (MS_MAX_LEVELS - 1)];
+    const int g_pitch = GL.pitch, g_w = GL.w, g_h = GL.h;
+    const float g_scale = GL.scale;
+    const uint64_t g_off = GL.img_off;
+    if (threadIdx.x < 64) s_tab[threadIdx.x] = tap_v;
+    s_tab[64 + threadIdx.x] = pair_v;
+    if (lane < MS_MAX_LEVELS) {
+        const uint64_t off = lane == 0 ? (uint64_t)(uintptr_t)src.lvl0 + (uint64_t)f * src.lvl0_frame_stride - (uint64_t)(uintptr_t)slab_f : g_off;
+        uint32_t *g = geo + kDescGeoStride * lane;
+        g[0] = (uint32_t)(lane == 0 ? src.lvl0_pitch : g_pitch); g[1] = (uint32_t)g_w; g[2] = (uint32_t)g_h; g[3] = __float_as_uint(g_scale);
+        g[4] = (uint32_t)off; g[5] = (uint32_t)(off >> 32);
+    }
+    __syncthreads();                                         // the tables are in LDS (every wave of the block is still here); the ONLY block barrier: the waves finish independently
+    const int trips = describe_strips::trips(strip.slot0, wv, R, total);
+    if (trips <= 0) return;                                  // a strip wholly at or beyond the frame's total
+    // lane j resolves the strip's j-th keypoint -- coordinates, level, geometry, whether its window lies inside the level and where the window starts --
+    // and leaves it in the wave's table: the loop reads one record per keypoint back as scalars, and a keypoint's level selects its geometry without
+    // a memory load that depends on the level
+    if (lane < R) {
+        const bool trk = myslot < nt;
+        const int level = trk ? lk_level : (int)min(ent.y, (uint32_t)(MS_MAX_LEVELS - 1));      // (an entry beyond the total is stale, not wild; its record is not read)
+        const uint32_t *g = geo + kDescGeoStride * level;
+        const int pitch = (int)g[0], w = (int)g[1], h = (int)g[2];
+        const float scale = __uint_as_float(g[3]);
+        const int x = trk ? tx : (int)(ent.x & 0xFFFFu), y = trk ? ty : (int)(ent.x >> 16);
+        const float ox = trk ? tpx : __fmul_rn((float)x, scale), oy = trk ? tpy : __fmul_rn((float)y, scale);     // orb_extractor.cpp:156
+        const bool inner = x >= 23 && x + 24 < w && y >= 22 && y + 22 < h;          // the whole window lies inside the level
+        // the plane's offset in the frame's slab; for an inner keypoint the window's corner at once
+        const uint64_t off = ((uint64_t)g[4] | ((uint64_t)g[5] << 32)) + (inner ? (uint64_t)((int64_t)(y - 22) * pitch + (x - 23)) : 0ull);
+        uint32_t *r = rec + kDescRecStride * lane;
+        *reinterpret_cast<uint4 *>(r) = uint4{(uint32_t)x, (uint32_t)y, (uint32_t)level | (inner ? 256u : 0u), (uint32_t)(trk ? tid : -1)};
+        *reinterpret_cast<uint4 *>(r + 4) = uint4{__float_as_uint(ox), __float_as_uint(oy), (uint32_t)pitch, (uint32_t)w};
+        *reinterpret_cast<uint4 *>(r + 8) = uint4{(uint32_t)h, (uint32_t)off, (uint32_t)(off >> 32), 0u};
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    DescKp K = desc_scalars(desc_read(rec));
     // ONE window of the (unblurred) level is copied into the wave's LDS slab with coalesced row loads: 45 rows x 48 B around the keypoint
     // (x-23 .. x+24, y-22 .. y+22; 9 wave-wide dword loads).  It holds the 31 x 31 orientation patch (each lane takes four of its dwords, with everything
     // outside the radius-15 disc zeroed, into registers for the moments) AND everything the 39 x 39 BLURRED patch of the BRIEF tests depends on (19 + 3 pixels each way),
@@ -1117,23 +1180,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // vertical pass on packed 16-bit lanes, horizontal pass with v_dot2 and one rounding -- and the blurred pyramid is no longer
     // written and read back for every frame (2 P bytes and a 0.49 ms kernel per 256-frame step; round 1 fetched 31 x 32 B of the level plus
     // 39 x 40 B of its blurred twin = 70 row pieces per keypoint, now 45).  k_blur still exists: ImagePyramid::getBlurredLevel runs it on demand.
-    __shared__ __attribute__((aligned(16))) uint32_t s_patch[4][kDescPerWave][45 * 12 + 32 * 8 + 4];   // the window (a whole number of 16-byte units: its rows are read as ds_read_b128); the blurred patch takes its place.  The 32 x 8 dwords behind it held a masked copy of the orientation patch until the moments were taken from registers: pass 1 of the blur still reads window "rows" 45 .. 47 there (zero weights), and the slab keeps its size and bank layout
-    const int wv = threadIdx.x >> 6;
-    int m10[kDescPerWave], m01[kDescPerWave];
-#pragma unroll
-    for (int k = 0; k < kDescPerWave; ++k) {
-        const TileLevel GL = TL.L[K[k].oct];               // (kernel arguments: no load from the geometry table behind the level)
-        const int pitch = K[k].oct == 0 ? src.lvl0_pitch : GL.pitch;
-        const uint8_t *img = K[k].oct == 0 ? src.lvl0 + (uint64_t)f * src.lvl0_frame_stride : src.slab + (uint64_t)f * TL.slab_stride + GL.img_off;
-        const int w = GL.w, h = GL.h, kx = K[k].x, ky = K[k].y;
-        uint32_t *win = &s_patch[wv][k][0], *pb = win;      // (pass 1 of the blur has read the whole window into registers before pass 2 writes the first blurred dword)
-        if (kx >= 23 && kx + 24 < w && ky >= 22 && ky + 22 < h) {          // wave-uniform: the whole window lies inside the level
+    // The slab (s_patch, above): the window (a whole number of 16-byte units: its rows are read as ds_read_b128); the blurred patch takes its place.  The 32 x 8
+    // dwords behind it held a masked copy of the orientation patch until the moments were taken from registers: pass 1 of the blur still reads window "rows" 45 .. 47
+    // there (zero weights), the wave's tables lie behind those, and the slab keeps its size and bank layout.
+    // The strip walk: the wave's keypoints one after another in the same registers and the same slab.  Wave-level fences only -- nothing in the loop waits for
+    // another wave, and its bound (trips) depends on the kernel arguments and the frame's total alone.
+    typedef __attribute__((address_space(3))) uint8_t lds_u8_t;
+    const uint32_t pbase = (uint32_t)(uintptr_t)(const lds_u8_t *)win + describe_brief_index::kIndexBias;   // the blurred patch's LDS address and the index's constant in one (wave-uniform)
+    const int lane_w = lane;
+    // (every load of the prologue is waited for HERE, vmcnt(0): left to the loop's first use of the lane tables, the wait stands at the head of the loop and
+    // there also waits for the stores of the previous keypoint)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#pragma unroll 1
+    for (int k = 0; k < trips; ++k) {
+        // What depends on the lane alone is formed anew for every keypoint, as a wave of one keypoint formed it once: carried around the loop in registers
+        // (the compiler's choice when it sees that it does not change) it costs the kernel its eighth wave per SIMD.  The empty statements hide that from it.
+        int lane_k = lane_w;
+        uint32_t wpack = wpack_w;
+        asm volatile("" : "+v"(lane_k), "+v"(wpack));
+        const int lane = lane_k;
+        const int pitch = K.pitch, w = K.w, h = K.h, kx = K.x, ky = K.y;
+        uint32_t *pb = win;                                  // (pass 1 of the blur has read the whole window into registers before pass 2 writes the first blurred dword)
+        // the next keypoint's record is requested here and read back behind the window's fence, which waits for LDS anyway: from the second keypoint of a
+        // strip on, no wait on scalar or vector memory stands between a keypoint's record and its window loads (the last trip reads its own record once more)
+        const DescRec next = desc_read(rec + kDescRecStride * min(k + 1, trips - 1));
+        if (K.inner) {                                       // wave-uniform: the whole window lies inside the level
             // piece t = 3 a + b is window dword lane + 64 t: the dword column of piece b, 16 a rows further down (describe_lanes.h).  Three lane offsets from
             // the packed table (all >= 0: the uniform part of each address is the minimum of what the piece reads, §11 of DESIGN.md), three uniform row bases.
             // The last piece exists for lanes 0 .. 27 only; the others fetch the first dword of its row base once more and park it behind the window (dwords
             // 540 .. 575 of the slab, which nothing reads as data), so that all nine loads are in flight together: behind a lane test the ninth load was
             // issued only after the first eight had returned -- one more round trip in every keypoint's chain.
-            const uint8_t *corner = img + (int64_t)(ky - 22) * pitch + (kx - 23);
+            const uint8_t *corner = slab_f + K.off;   // (the record of an inner keypoint holds its window's corner)
             uint32_t off[3];
 #pragma unroll
             for (int b = 0; b < 3; ++b) off[b] = __umul24((wpack >> (10 * b)) & 15u, (uint32_t)pitch) + ((wpack >> (10 * b + 4)) & 63u);
@@ -1143,6 +1220,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 win[lane + 64 * t] = reinterpret_cast<const U32u *>(rows + (describe_lanes::win_active(lane, t) ? off[t % 3] : 0u))->v;
             }
         } else {                                                          // a keypoint within 24 pixels of the border (a few per cent): BORDER_REFLECT_101 byte by byte
+            const uint8_t *img = slab_f + K.off;
 #pragma unroll 1
             for (int t = 0; t < 9; ++t) {
                 const int i = lane + 64 * t, r = i / 12, c = i - 12 * r;
@@ -1156,6 +1234,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        const DescKp Kn = desc_scalars(next);
+        int m10, m01;
         {   // orientation patch: rows y-15 .. y+15 = window rows 7 .., columns x-15 .. = window dword 2 ..; everything outside the radius-15 disc zeroed (the mask of
             // the 32nd row is zero).  Patch dword lane + 64 t is 8 window rows below dword lane + 64 (t - 1): one lane base, four reads at constant offsets.
             // O1: moments m10 = sum u I, m01 = sum v I over the disc (orb_extractor.cpp:245-275; integer sums, any order) on the lane's own four masked dwords,
@@ -1166,7 +1246,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             for (int t = 0; t < 4; ++t) d[t] = (describe_lanes::ori_active(lane, t) ? ob[8 * describe_lanes::kWinDwords * t] : 0u) & dmask[t];
             int p10, p01;
             describe_lanes::lane_moments(d, describe_lanes::moment_col_weights(lane), describe_lanes::moment_row_bias(lane), p10, p01);
-            m10[k] = wave_sum(p10); m01[k] = wave_sum(p01);
+            m10 = wave_sum(p10); m01 = wave_sum(p01);
         }
         {   // blurred patch rows y-19 .. y+19 (output row ro <- window rows ro .. ro+6), columns x-19 .. x+19 = window bytes 4 .. 42, ON THE MATRIX CORES (round 3):
             // a separable 7-tap filter is two products with banded constant matrices, out = V (P Hh), and every quantity of k_blur's fixed-point arithmetic is an
@@ -1221,54 +1301,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 }
             }
         }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    float angle_deg[kDescPerWave], ca[kDescPerWave], sa[kDescPerWave], nsa[kDescPerWave];
-#pragma unroll
-    for (int k = 0; k < kDescPerWave; ++k) {
-        angle_deg[k] = describe_steer::fast_atan2((float)m01[k], (float)m10[k]);
-        const float angle = describe_steer::deg_to_rad(angle_deg[k]);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const float angle_deg = describe_steer::fast_atan2((float)m01, (float)m10);
+        const float angle = describe_steer::deg_to_rad(angle_deg);
         // sin(v) is cos(pi / 2 - v): lane 1 evaluates the shifted argument while lane 0 evaluates v, one cos_approx for both; every lane reads the two
         // results back as scalars
         const float cs = describe_steer::cos_approx(lane == 1 ? describe_steer::sin_argument(angle) : angle);
-        ca[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 0));
-        sa[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 1));
+        const float ca = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 0));
+        const float sa = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), 1));
         // the column is x cos - y sin = x cos + y (-sin), the same float bit for bit (a product's sign is exact): with the sign turned once per keypoint, row and
         // column of a point are the same two multiplies and one add, and the compiler packs each step of the pair into one v_pk_*_f32.  The empty statement
         // keeps it from folding the negation back into a subtraction.
-        nsa[k] = -sa[k];
-        asm volatile("" : "+s"(nsa[k]));
-    }
-    // O2: steered BRIEF on the blurred patch; the lane's point pairs are shared by the wave's keypoints
-    unsigned long long bits[kDescPerWave][4];
-    typedef __attribute__((address_space(3))) uint8_t lds_u8_t;
-    uint32_t pbase[kDescPerWave];                            // the blurred patch's LDS address and the index's constant in one (wave-uniform)
+        float nsa = -sa;
+        asm volatile("" : "+s"(nsa));
+        // O2: steered BRIEF on the blurred patch
+        unsigned long long bits[4];
 #pragma unroll
-    for (int k = 0; k < kDescPerWave; ++k) pbase[k] = (uint32_t)(uintptr_t)(const lds_u8_t *)&s_patch[wv][k][0] + describe_brief_index::kIndexBias;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 pt = __builtin_bit_cast(float4, s_tab[64 + q * 64 + lane]);             // the test's two points, already float
-        const float x1 = pt.x, y1 = pt.y, x2 = pt.z, y2 = pt.w;
-#pragma unroll
-        for (int k = 0; k < kDescPerWave; ++k) {
+        for (int q = 0; q < 4; ++q) {
+            const float4 pt = __builtin_bit_cast(float4, s_tab[64 + q * 64 + lane]);             // the test's two points, already float
+            const float x1 = pt.x, y1 = pt.y, x2 = pt.z, y2 = pt.w;
             // rows and columns + 19 lie in 0 .. 38 (the pattern stays inside the 39 x 39 patch under every rotation).  The products and the add / sub are the
             // reference's, one rounding each; rounding to the integer is one more float add, and the conversion, both + 19 and the patch's LDS address are one
             // constant behind one 24-bit multiply-add (describe_brief_index.h: 6 instructions per point where v_rndne + v_cvt per coordinate made it 11)
-            const uint32_t r1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, sa[k]), __fmul_rn(y1, ca[k])));
-            const uint32_t c1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, ca[k]), __fmul_rn(y1, nsa[k])));
-            const uint32_t r2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, sa[k]), __fmul_rn(y2, ca[k])));
-            const uint32_t c2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, ca[k]), __fmul_rn(y2, nsa[k])));
-            const uint32_t i1 = describe_brief_index::index_from_bits(r1, c1, pbase[k]), i2 = describe_brief_index::index_from_bits(r2, c2, pbase[k]);
-            bits[k][q] = __ballot(*(const lds_u8_t *)(uintptr_t)i1 < *(const lds_u8_t *)(uintptr_t)i2);
+            const uint32_t r1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, sa), __fmul_rn(y1, ca)));
+            const uint32_t c1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, ca), __fmul_rn(y1, nsa)));
+            const uint32_t r2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, sa), __fmul_rn(y2, ca)));
+            const uint32_t c2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, ca), __fmul_rn(y2, nsa)));
+            const uint32_t i1 = describe_brief_index::index_from_bits(r1, c1, pbase), i2 = describe_brief_index::index_from_bits(r2, c2, pbase);
+            bits[q] = __ballot(*(const lds_u8_t *)(uintptr_t)i1 < *(const lds_u8_t *)(uintptr_t)i2);
         }
-    }
-#pragma unroll
-    for (int k = 0; k < kDescPerWave; ++k) {
-        if (!K[k].valid) continue;                              // wave-uniform
-        const uint64_t o = (uint64_t)f * capacity + slot0 + k;
-        if (lane < 8) out_desc[o * 8 + lane] = (uint32_t)(bits[k][lane >> 1] >> ((lane & 1) * 32));
-        if (lane == 0) { out_x[o] = K[k].ox; out_y[o] = K[k].oy; out_angle[o] = angle_deg[k]; out_octave[o] = K[k].oct; out_track[o] = K[k].tid_out; }
+        const uint64_t o = (uint64_t)f * capacity + slot0 + 4 * k;
+        if (lane < 8) out_desc[o * 8 + lane] = (uint32_t)(bits[lane >> 1] >> ((lane & 1) * 32));
+        if (lane == 0) { out_x[o] = K.ox; out_y[o] = K.oy; out_angle[o] = angle_deg; out_octave[o] = K.oct; out_track[o] = K.tid_out; }
+        // the last BRIEF read of the patch has been consumed (the ballots): the next keypoint's window may take the slab
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        K = Kn;
     }
 }
 
@@ -1305,6 +1374,7 @@ struct ms_orb {
     bool wide[MS_MAX_LEVELS] = {false};
     uint4 *d_moment_tab = nullptr;            // k_describe: disc mask of the orientation patch, four dwords per lane
     float4 *d_pattern_f = nullptr;            // k_describe: the 256 BRIEF point pairs as floats
+    int describe_strip = 0;                   // k_describe: 0 = the automatic launch plan (describe_strips.h), 1 .. 8 = every wave walks that many keypoints (ms_orb_set_describe_strip)
     // optional per-stage HIP events (ms_orb_set_profiling)
     bool profiling = false;
     bool blur_valid = false;           // the blurred planes of the slab hold the last batch (k_blur runs on demand only)
@@ -1544,6 +1614,12 @@ void ms_orb_destroy(ms_orb *o) {
 
 int ms_orb_capacity(const ms_orb *o) { return o ? o->geom.capacity : MS_ERR_INVALID; }
 
+int ms_orb_set_describe_strip(ms_orb *o, int r) {
+    if (!o || r < 0 || r > describe_strips::kMaxStrip) return MS_ERR_INVALID;
+    o->describe_strip = r;
+    return MS_OK;
+}
+
 int ms_orb_set_profiling(ms_orb *o, int enable) {
     if (!o) return MS_ERR_INVALID;
     ms_ctx *c = o->ctx;
@@ -1667,7 +1743,11 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     const size_t C = (size_t)G.capacity;
     hipLaunchKernelGGL(k_slots, dim3(G.levels, nf), dim3(256), 0, st, det_x, det_y, det_count, trk_count, o->d_slot_tab + F * C, o->d_count + F, o->tile_levels, G.det_stride, G.capacity);
     MS_KERNEL_CHECK(c, "k_slots");
-    hipLaunchKernelGGL(k_describe, dim3(ms_div_up(G.capacity, 4 * kDescPerWave), nf), dim3(256), 0, st, src, o->tile_levels, o->d_moment_tab, o->d_pattern_f,
+    // which block describes which slots: long strips first, a tail of one-keypoint blocks twice what the device holds at once (8 blocks per CU); a launch
+    // without more blocks than that tail -- a single frame, the frame-by-frame legs -- is one keypoint per wave throughout
+    describe_strips::Plan plan;
+    if (!describe_strips::build(nf, G.capacity, 8ll * std::max(c->n_cu, 1), o->describe_strip, plan)) return ms_fail(c, MS_ERR_CAPACITY, "k_describe: %d frames of %d slots exceed the grid", nf, G.capacity);
+    hipLaunchKernelGGL(k_describe, dim3(plan.blocks), dim3(256), 0, st, src, o->tile_levels, plan, o->d_moment_tab, o->d_pattern_f,
                        o->d_slot_tab + F * C, G.capacity, G.max_tracks, G.lk_level, o->d_trk_x + F * T, o->d_trk_y + F * T, o->d_trk_px + F * T, o->d_trk_py + F * T, o->d_trk_id + F * T, trk_count, o->d_x + F * C, o->d_y + F * C,
                        o->d_angle + F * C, o->d_octave + F * C, o->d_desc + F * C * 8, o->d_track + F * C, o->d_count + F);
     MS_KERNEL_CHECK(c, "k_describe");

@@ -324,6 +324,11 @@ class OrbExtractor:
         self.ctx.check(lib().ms_keypoints_pack(self.ctx._h, C.byref(v), frame, n, _vp(db), _vp(out)), "ms_keypoints_pack")
         return out
 
+    def set_describe_strip(self, r):
+        """Keypoints a wave of the describe kernel walks in sequence: 0 = the automatic launch plan (default), 1 .. 8 = every workgroup uses r.
+        A test hook: the outputs are the same for every value."""
+        self.ctx.check(lib().ms_orb_set_describe_strip(self._h, int(r)), "ms_orb_set_describe_strip")
+
     def set_profiling(self, enable=True):
         self.ctx.check(lib().ms_orb_set_profiling(self._h, int(enable)), "ms_orb_set_profiling")
 
