@@ -12,6 +12,7 @@
 #include <fstream>
 #include <map>
 #include <sstream>
+#include <utility>
 #include "common.hpp"
 
 namespace mi355slam {
@@ -81,7 +82,7 @@ public:
         ctx_.check(ms_bow_vocab_create(ctx_.get(), (int)tree.size(), tree.parent.data(), tree.descriptor.data(), tree.weight.data(), tree.wordId.data(),
                                        tree.depthLevels, &vocab_), "ms_bow_vocab_create");
     }
-    ~BowIndex() { ms_bow_db_destroy(db_); ms_bow_vocab_destroy(vocab_); for (void *p : {d_desc_, d_word_, d_weight_, d_node_}) if (p) ms_dev_free(ctx_.get(), p); }
+    ~BowIndex() { ms_bow_db_destroy(db_); ms_bow_vocab_destroy(vocab_); }
     BowIndex(const BowIndex &) = delete;
 
     // bow_index.cpp:59-93
@@ -93,13 +94,12 @@ public:
         reserve(n);
         host_desc_.resize(8 * n);
         for (std::size_t i = 0; i < n; ++i) for (int k = 0; k < 8; ++k) host_desc_[8 * i + k] = keypoints[i].descriptor[k];
-        ctx_.check(ms_dev_upload(ctx_.get(), d_desc_, host_desc_.data(), 32 * n), "ms_dev_upload");
-        ctx_.check(ms_bow_transform(ctx_.get(), vocab_, static_cast<const std::uint32_t *>(d_desc_), (int)n, levelsUp,
-                                    static_cast<std::int32_t *>(d_word_), static_cast<double *>(d_weight_), static_cast<std::int32_t *>(d_node_)), "ms_bow_transform");
-        word_.resize(n); weight_.resize(n); node_.resize(n);
-        ctx_.check(ms_dev_download(ctx_.get(), word_.data(), d_word_, 4 * n), "ms_dev_download");
-        ctx_.check(ms_dev_download(ctx_.get(), weight_.data(), d_weight_, 8 * n), "ms_dev_download");
-        ctx_.check(ms_dev_download(ctx_.get(), node_.data(), d_node_, 4 * n), "ms_dev_download");
+        d_desc_.upload(0, 8 * n, host_desc_.data());
+        ctx_.check(ms_bow_transform(ctx_.get(), vocab_, d_desc_.data(), (int)n, levelsUp, d_word_.data(), d_weight_.data(), d_node_.data()), "ms_bow_transform");
+        word_.resize(n); weight_.resize(n); node_.resize(n);                      // host buffers reused across calls
+        ctx_.check(ms_dev_download(ctx_.get(), word_.data(), d_word_.data(), 4 * n), "ms_dev_download");
+        ctx_.check(ms_dev_download(ctx_.get(), weight_.data(), d_weight_.data(), 8 * n), "ms_dev_download");
+        ctx_.check(ms_dev_download(ctx_.get(), node_.data(), d_node_.data(), 4 * n), "ms_dev_download");
         assemble(word_, weight_, node_, bowVector, bowFeatureVector);
     }
 
@@ -159,12 +159,16 @@ private:
     }
     void reserve(std::size_t n) {
         if (n <= cap_) return;
-        for (void **p : {&d_desc_, &d_word_, &d_weight_, &d_node_}) if (*p) { ms_dev_free(ctx_.get(), *p); *p = nullptr; }
-        cap_ = n + n / 2 + 64;
-        ctx_.check(ms_dev_alloc(ctx_.get(), 32 * cap_, &d_desc_), "ms_dev_alloc");
-        ctx_.check(ms_dev_alloc(ctx_.get(), 4 * cap_, &d_word_), "ms_dev_alloc");
-        ctx_.check(ms_dev_alloc(ctx_.get(), 8 * cap_, &d_weight_), "ms_dev_alloc");
-        ctx_.check(ms_dev_alloc(ctx_.get(), 4 * cap_, &d_node_), "ms_dev_alloc");
+        // free, forget the capacity, allocate, and only then record it (the order of Context::workspace): a failed allocation leaves no buffers and capacity 0
+        d_desc_.reset(); d_word_.reset(); d_weight_.reset(); d_node_.reset();
+        cap_ = 0;
+        const std::size_t cap = n + n / 2 + 64;
+        DeviceArray<std::uint32_t> desc(ctx_, 8 * cap);
+        DeviceArray<std::int32_t> word(ctx_, cap);
+        DeviceArray<double> weight(ctx_, cap);
+        DeviceArray<std::int32_t> node(ctx_, cap);
+        d_desc_ = std::move(desc); d_word_ = std::move(word); d_weight_ = std::move(weight); d_node_ = std::move(node);
+        cap_ = cap;
     }
     Context &ctx_;
     int scoring_ = 0, nWords_ = 0;
@@ -174,8 +178,10 @@ private:
     std::vector<double> qValues_;
     std::vector<float> outScore_;
     std::size_t outCap_ = 64;
-    void *d_desc_ = nullptr, *d_word_ = nullptr, *d_weight_ = nullptr, *d_node_ = nullptr;
-    std::size_t cap_ = 0;
+    DeviceArray<std::uint32_t> d_desc_;
+    DeviceArray<std::int32_t> d_word_, d_node_;
+    DeviceArray<double> d_weight_;
+    std::size_t cap_ = 0;                                                         // keypoints the four buffers hold
     std::vector<std::uint32_t> host_desc_;
     std::vector<std::int32_t> word_, node_;
     std::vector<double> weight_;

@@ -106,11 +106,55 @@ public:
         return static_cast<unsigned char *>(ws_);
     }
     std::vector<unsigned char> &staging() { return stage_; }          // host side of the same tables, reused across calls
+    // a host copy of n elements of device memory (results in the workspace, a table); nothing is copied for n == 0
+    template <class T> std::vector<T> download(const T *dev, std::size_t n) const {
+        std::vector<T> out(n);
+        if (n) check(ms_dev_download(ctx_, out.data(), dev, n * sizeof(T)), "ms_dev_download");
+        return out;
+    }
 private:
     ms_ctx *ctx_ = nullptr;
     void *ws_ = nullptr;
     std::size_t wsBytes_ = 0;
     std::vector<unsigned char> stage_;
+};
+
+// n elements of device memory on a context: allocated by the constructor, freed by the destructor, moved but never copied.  What every
+// device-resident table of the mirrors is made of, so a constructor that throws half-way gives back what it had allocated.
+template <class T> class DeviceArray {
+public:
+    DeviceArray() = default;
+    DeviceArray(Context &ctx, std::size_t n) : ctx_(&ctx), n_(n) {
+        void *p = nullptr;
+        ctx.check(ms_dev_alloc(ctx.get(), n * sizeof(T) + 16, &p), "ms_dev_alloc");     // 16 bytes of tail: a zero-length table still has a non-null pointer
+        p_ = static_cast<T *>(p);
+    }
+    ~DeviceArray() { reset(); }
+    DeviceArray(DeviceArray &&o) noexcept : ctx_(o.ctx_), p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DeviceArray &operator=(DeviceArray &&o) noexcept {
+        if (this != &o) { reset(); ctx_ = o.ctx_; p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    void reset() { if (p_) ms_dev_free(ctx_->get(), p_); p_ = nullptr; n_ = 0; }       // frees now: for an owner that must free before it allocates
+    T *data() { return p_; }
+    const T *data() const { return p_; }
+    std::size_t size() const { return n_; }
+    void upload(std::size_t first, std::size_t count, const T *src) {
+        if (first + count > n_) throw std::runtime_error("DeviceArray::upload: range outside the array");
+        if (count) ctx_->check(ms_dev_upload(ctx_->get(), p_ + first, src, count * sizeof(T)), "ms_dev_upload");
+    }
+    void fill(const T &value) { const std::vector<T> host(n_, value); upload(0, n_, host.data()); }
+    std::vector<T> download(std::size_t first, std::size_t count) const {
+        if (first + count > n_) throw std::runtime_error("DeviceArray::download: range outside the array");
+        return count ? ctx_->download(p_ + first, count) : std::vector<T>();
+    }
+    std::vector<T> download() const { return download(0, n_); }
+private:
+    Context *ctx_ = nullptr;
+    T *p_ = nullptr;
+    std::size_t n_ = 0;
 };
 
 }  // namespace mi355slam

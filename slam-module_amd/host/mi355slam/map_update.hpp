@@ -1,0 +1,427 @@
+// map_update.hpp -- the operations of the host mirror on the device-resident map (map_tables.hpp), with their argument and result structs:
+// loop correction (correctLoop), triangulation (triangulateMapPoints), covisibility (getNeighbors, computeAdjacentKeyframes, localMapPoints),
+// culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent) and matchTrackedFeatures.
+// Results come back through Context::workspace and Context::download; nothing here owns device memory.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <stdexcept>
+#include "map_tables.hpp"
+#include "optimize_transform.hpp"
+
+namespace mi355slam {
+
+// The keyframes LoopCloser::correctLoop moves (loop_closer.cpp:420-470), as slots of DeviceKeyframePoses: rigid = a member of
+// rigidlyTransformedKfIds (:427, T itself), otherwise lambda = (t - t0) / (t1 - t0) of :458.
+struct LoopCorrections {
+    std::vector<std::int32_t> slot;
+    std::vector<std::uint8_t> rigid;
+    std::vector<double> lambda;
+};
+// localMapPoints (:418, :429-433, :465-469) as table rows: row[j] moves with the keyframe at position reference[j] of LoopCorrections::slot.
+struct LoopPoints {
+    std::vector<std::int32_t> row, reference;
+};
+// What DeviceMapPoints::refresh takes for the moved points (:504-505).
+struct RefreshArgs {
+    std::vector<std::int32_t> rows;
+    std::vector<std::vector<MapObservation>> observations;
+    std::vector<std::int32_t> firstOctave;
+    const DeviceDescriptorPool *pool = nullptr;
+};
+
+// LoopCloser::correctLoop from the pose correction to the refresh of the moved map points (loop_closer.cpp:398-506) on the device tables:
+// ms_loop_correct (poses, then points), then DeviceMapPoints::refresh of refreshArgs.rows.  T = the Sim3 of :405.  Re-triangulation (:508-523)
+// stays with the caller.  Returns refresh's medoids.
+inline std::vector<int> correctLoop(Context &ctx, DeviceMapPoints &table, DeviceKeyframePoses &poses, const Sim3 &T, const LoopCorrections &corrections,
+                                    const LoopPoints &points, const RefreshArgs &refreshArgs, const StaticSettings &settings) {
+    if (corrections.rigid.size() != corrections.slot.size() || corrections.lambda.size() != corrections.slot.size() || points.reference.size() != points.row.size())
+        throw std::invalid_argument("correctLoop: the correction lists have different lengths");
+    const double t8[8] = {T.q[0], T.q[1], T.q[2], T.q[3], T.t[0], T.t[1], T.t[2], T.s};
+    ctx.check(ms_loop_correct(ctx.get(), poses.pose(), (int)poses.size(), table.mutablePosition(), (int)table.size(), t8, corrections.slot.data(),
+                              corrections.rigid.data(), corrections.lambda.data(), (int)corrections.slot.size(), points.row.data(), points.reference.data(),
+                              (int)points.row.size()), "ms_loop_correct");
+    return table.refresh(ctx, poses, refreshArgs.rows, refreshArgs.observations, refreshArgs.firstOctave, settings, refreshArgs.pool);
+}
+
+// ---- the map-point triangulator (ms_triangulate) ------------------------------------------------------------------------------------
+// TriangulationMethod of mapper_helpers.hpp plus the first / last variant (triangulateMapPointFirstLastObs).
+enum class TriangulationMethod { TME = MS_TRI_TME, MIDPOINT = MS_TRI_MIDPOINT, FIRST_LAST = MS_TRI_FIRST_LAST };
+// Per keyframe slot of DeviceKeyframePoses: the pinhole stand-in of kf.shared->camera and its getFocalLength().
+struct KeyframeCameras {
+    std::vector<ms_pinhole> camera;
+    std::vector<std::int32_t> focalLength;
+};
+// The map points to triangulate and MapPoint::observations of each, flattened in the reference's iteration order (ascending KfId):
+// row r's observations are [obsStart[r], obsStart[r + 1]); obsKf = the keyframe's slot, obsX / obsY / obsOctave = kp.pt and kp.octave,
+// obsDepth = keyPointDepth (empty: no depth anywhere); wasTriangulated = status != NOT_TRIANGULATED on entry (mapper_helpers.cpp:607).
+struct TriangulateArgs {
+    std::vector<std::int32_t> rows;
+    std::vector<std::uint8_t> wasTriangulated;
+    std::vector<std::int32_t> obsStart, obsKf, obsOctave;
+    std::vector<float> obsX, obsY, obsDepth;
+};
+// Per entry of TriangulateArgs::rows: status (0 NOT_TRIANGULATED, 1 UNSURE, 2 TRIANGULATED), the first gate that stopped the point (the reason
+// codes of ms_triangulate) and nNew of triangulateMapPointFirstLastObs.
+struct TriangulateResult {
+    std::vector<std::uint8_t> status, reason;
+    std::vector<std::int32_t> passCount;
+};
+
+// triangulateMapPoint / triangulateMapPointFirstLastObs (mapper_helpers.cpp:600-812) for args.rows, on the device: positions are written into
+// `table`, the status flags (DeviceMapPointFlags encoding) into `flags` when given.  The debug counters of loop_closer.cpp:516-521 follow from
+// the result and the entry state: `failed` = the entry status was TRIANGULATED and status != 2; `changed` (a comparison of position values in
+// the reference) = the position was written: status != 0, or the depth branch of :621 ran (not wasTriangulated, a positive depth, reason != 1).
+inline TriangulateResult triangulateMapPoints(Context &ctx, DeviceMapPoints &table, DeviceMapPointFlags *flags, const DeviceKeyframePoses &poses,
+                                              const KeyframeCameras &cams, const TriangulateArgs &args, const StaticSettings &settings, TriangulationMethod method) {
+    const std::size_t n = args.rows.size();
+    if (args.wasTriangulated.size() != n || args.obsStart.size() != n + 1) throw std::invalid_argument("triangulateMapPoints: one flag and one list per row");
+    const std::size_t nObs = (std::size_t)std::max<std::int32_t>(args.obsStart.back(), 0);
+    if (args.obsKf.size() < nObs || args.obsOctave.size() < nObs || args.obsX.size() < nObs || args.obsY.size() < nObs || (!args.obsDepth.empty() && args.obsDepth.size() < nObs))
+        throw std::invalid_argument("triangulateMapPoints: the observation arrays are shorter than obsStart says");
+    if (cams.camera.size() != poses.size() || cams.focalLength.size() != poses.size()) throw std::invalid_argument("triangulateMapPoints: one camera per keyframe slot");
+    if (flags && flags->size() < table.size()) throw std::invalid_argument("triangulateMapPoints: fewer flags than map points");
+    const Parameters &p = settings.parameters;
+    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    TriangulateResult out;
+    out.status.assign(n, 0); out.reason.assign(n, 0); out.passCount.assign(n, 0);
+    ctx.check(ms_triangulate(ctx.get(), table.mutablePosition(), flags ? flags->mutableFlags() : nullptr, (int)table.size(), poses.pose(), (int)poses.size(),
+                             cams.camera.data(), cams.focalLength.data(), args.rows.data(), args.wasTriangulated.data(), (int)n, args.obsStart.data(), args.obsKf.data(),
+                             args.obsX.data(), args.obsY.data(), args.obsOctave.data(), args.obsDepth.empty() ? nullptr : args.obsDepth.data(), &s, (int)method,
+                             out.status.data(), out.reason.data(), out.passCount.data()), "ms_triangulate");
+    return out;
+}
+
+// ---- set queries over the map graph (ms_covisibility, ms_map_point_union) ---------------------------------------------------------
+// One call of Keyframe::getNeighbors (keyframe.cpp:192-230): the keyframe's slot, its previousKfId / nextKfId as slots (-1 for none).
+struct NeighborQuery {
+    std::int32_t slot = 0, previous = -1, next = -1;
+    int minCovisibilities = 1;
+    bool triangulatedOnly = false;
+};
+
+// getNeighbors for every query in one device call: per query the neighbour slots, ascending (the order of the reference's std::map walk).
+inline std::vector<std::vector<std::int32_t>> getNeighbors(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags,
+                                                           const std::vector<NeighborQuery> &queries) {
+    std::vector<std::vector<std::int32_t>> out(queries.size());
+    if (queries.empty()) return out;
+    if (flags && flags->size() < table.mapPointCount()) throw std::invalid_argument("getNeighbors: fewer flags than map points");
+    std::vector<ms_covis_query> q(queries.size());
+    for (std::size_t i = 0; i < queries.size(); ++i)
+        q[i] = ms_covis_query{queries[i].slot, queries[i].previous, queries[i].next, (std::int32_t)queries[i].minCovisibilities,
+                              (std::uint8_t)(queries[i].triangulatedOnly ? DeviceMapPointFlags::TRIANGULATED : 0)};
+    const std::size_t nKf = table.size(), bytes = 4 * queries.size() * nKf;
+    std::int32_t *packed = reinterpret_cast<std::int32_t *>(ctx.workspace(bytes));
+    std::vector<std::int32_t> n(queries.size(), 0);
+    ctx.check(ms_covisibility(ctx.get(), table.table(), (int)nKf, (int)table.stride(), flags ? flags->flags() : nullptr, (int)table.mapPointCount(), q.data(), (int)q.size(),
+                              nullptr, packed, n.data()), "ms_covisibility");
+    std::vector<std::int32_t> host(queries.size() * nKf);
+    ctx.check(ms_dev_download(ctx.get(), host.data(), packed, bytes), "ms_dev_download");
+    for (std::size_t i = 0; i < queries.size(); ++i) out[i].assign(host.begin() + i * nKf, host.begin() + i * nKf + n[i]);
+    return out;
+}
+
+// What computeAdjacentKeyframes reads of the map besides the covisibilities: per slot the previousKfId / nextKfId links (as slots, -1 for
+// none) and Keyframe::cameraCenter().
+struct KeyframeChain {
+    std::vector<std::int32_t> previous, next;
+    std::vector<std::array<double, 3>> cameraCenter;
+    // what observationCounts and cullMap read in addition: per slot the KfId (-1 for an empty slot) and Keyframe::t
+    std::vector<std::int32_t> id;
+    std::vector<double> t;
+};
+
+// computeAdjacentKeyframes (mapper_helpers.cpp:144-229): the getNeighbors calls of every second keyframe of the chain behind `current`
+// (:160-176) are ONE ms_covisibility call; the chain walks from the parents and the squared-distance sort (:178-216) stay on the host.
+inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, std::int32_t current,
+                                                          int minCovisibilities, int maxKeyframes, const KeyframeChain &chain) {
+    if (chain.previous.size() != table.size() || chain.next.size() != table.size() || chain.cameraCenter.size() != table.size())
+        throw std::invalid_argument("computeAdjacentKeyframes: one link pair and one camera centre per slot");
+    auto inTable = [&](std::int32_t s) { return s >= 0 && (std::size_t)s < table.size(); };
+    if (!inTable(current)) throw std::invalid_argument("computeAdjacentKeyframes: current keyframe outside the table");
+    std::vector<char> adjacentSet(table.size(), 0);          // std::set<KfId> over slots: walked in ascending order below
+    std::vector<NeighborQuery> queries;
+    int i = 0;
+    for (std::int32_t backwards = current; backwards != -1; backwards = chain.previous[backwards]) {
+        if (!inTable(backwards)) throw std::invalid_argument("computeAdjacentKeyframes: a link leaves the table");
+        adjacentSet[backwards] = 1;
+        if (i % 2 == 0) queries.push_back({backwards, chain.previous[backwards], chain.next[backwards], minCovisibilities, false});
+        if (++i >= maxKeyframes) break;
+    }
+    std::vector<char> parents(table.size(), 0);
+    for (const std::vector<std::int32_t> &nb : getNeighbors(ctx, table, flags, queries))
+        for (std::int32_t k : nb) parents[k] = 1;
+    for (std::size_t parent = 0; parent < parents.size(); ++parent) {
+        if (!parents[parent]) continue;
+        for (const std::vector<std::int32_t> *link : {&chain.previous, &chain.next}) {
+            i = 0;
+            for (std::int32_t at = (std::int32_t)parent; at != -1; at = (*link)[at]) {
+                if (!inTable(at)) throw std::invalid_argument("computeAdjacentKeyframes: a link leaves the table");
+                adjacentSet[at] = 1;
+                if (++i >= maxKeyframes / 2) break;
+            }
+        }
+    }
+    adjacentSet[current] = 0;
+    std::vector<std::int32_t> adjacent;
+    for (std::size_t k = 0; k < adjacentSet.size(); ++k) if (adjacentSet[k]) adjacent.push_back((std::int32_t)k);
+    const std::array<double, 3> &c = chain.cameraCenter[current];
+    auto dist2 = [&](std::int32_t k) {                       // squaredNorm of a 3-vector, Eigen's unrolled redux: x^2 + (y^2 + z^2)
+        const std::array<double, 3> &p = chain.cameraCenter[k];
+        const double x = p[0] - c[0], y = p[1] - c[1], z = p[2] - c[2];
+        return x * x + (y * y + z * z);
+    };
+    std::sort(adjacent.begin(), adjacent.end(), [&](std::int32_t a, std::int32_t b) { return dist2(a) < dist2(b); });
+    if ((int)adjacent.size() > maxKeyframes) adjacent.erase(adjacent.begin() + maxKeyframes, adjacent.end());
+    return adjacent;
+}
+
+// The ordered union of the map points of a list of keyframes: rows ascending (the std::set / std::map walk) and, for each, the first
+// position of the list whose keyframe lists it (localMapPoints.emplace of loop_closer.cpp:430-432) -- LoopPoints as it stands.
+//   matchLocalMapPoints (mapper_helpers.cpp:241-261)   localMapPoints(ctx, table, &flags, adjacentSlots, currentSlot, DeviceMapPointFlags::USABLE).row
+//                                                      is GateView::indices in front of isInFrustum
+//   deduplicateMapPoints (:337-345), searchAndDeduplicate (loop_closer.cpp:569-584)   exclude = -1, require = 0
+//   correctLoop (:418-433, :465-469)                   keyframes = LoopCorrections::slot; the result is its LoopPoints
+inline LoopPoints localMapPoints(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &keyframes,
+                                 std::int32_t excludeSlot = -1, std::uint8_t require = 0, bool withOwner = true) {
+    LoopPoints out;
+    const std::size_t nMp = table.mapPointCount();
+    if (flags && flags->size() < nMp) throw std::invalid_argument("localMapPoints: fewer flags than map points");
+    const ms_union_problem problem{0, (std::int32_t)keyframes.size(), excludeSlot, require};
+    std::int32_t *rows = reinterpret_cast<std::int32_t *>(ctx.workspace(8 * nMp + 256)), *owner = rows + (nMp + 63) / 64 * 64;
+    std::int32_t n = 0;
+    ctx.check(ms_map_point_union(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), flags ? flags->flags() : nullptr, (int)nMp, keyframes.data(),
+                                 (int)keyframes.size(), &problem, 1, rows, withOwner ? owner : nullptr, &n), "ms_map_point_union");
+    out.row = ctx.download(rows, (std::size_t)n);
+    if (withOwner) out.reference = ctx.download(owner, (std::size_t)n);
+    return out;
+}
+
+// ---- observation counts and culling on the map tables (ms_observation_count, ms_map_cull) -----------------------------------------
+// Per table row: mp.observations.size(), getFirstObservation() and getLastObservation() as slots (-1 for a row nobody observes).
+struct ObservationCounts {
+    std::vector<std::int32_t> count, first, last;
+};
+
+// The transpose of the keyframe table, computed where it lies: what the status promotion of mapper_helpers.cpp:1072 and the row selection of
+// :1088 read, without a std::map of observations per point on the host.  kfIds: per slot the KfId, -1 for an empty slot.
+inline ObservationCounts observationCounts(Context &ctx, const DeviceKeyframeMapPoints &table, const std::vector<std::int32_t> &kfIds) {
+    if (kfIds.size() != table.size()) throw std::invalid_argument("observationCounts: one KfId per slot");
+    const std::size_t nMp = table.mapPointCount(), pitch = (nMp + 63) / 64 * 64;
+    std::int32_t *dev = reinterpret_cast<std::int32_t *>(ctx.workspace(12 * pitch + 256));
+    ctx.check(ms_observation_count(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), (int)nMp, kfIds.data(), dev, dev + pitch, dev + 2 * pitch),
+              "ms_observation_count");
+    ObservationCounts out;
+    out.count = ctx.download(dev, nMp); out.first = ctx.download(dev + pitch, nMp); out.last = ctx.download(dev + 2 * pitch, nMp);
+    return out;
+}
+
+// The three ParametersSlam fields the culling step reads.  Their types are not in the reference tree: ratioFloat32 says whether
+// keyframeCullMaxCriticalRatio is a float there (the product of :476 is then rounded to float32); see INTEGRATION.md.
+struct CullSettings {
+    double minMapPointCullingAge = 0.0;
+    int minObservationsForBA = 0;
+    double keyframeCullMaxCriticalRatio = 0.0;
+    bool cullPoints = true;             // false: cullKeyframes alone
+    bool ratioFloat32 = false;
+};
+
+// What the host side of the map still has to do after a cull: the removed rows (ascending) with the reason of each (1 no observation left,
+// 2 aged and not triangulated, 3 orphaned by a removed keyframe) -- trackIdToMapPoint.erase and the host copies of those points -- and the
+// removed keyframes as slots, in the order of removal (descending KfId) -- bowIndex->remove, the `uncertainty` accumulation onto the next
+// keyframe and re-pointing referenceKeyframe to the previous one (mapper_helpers.cpp:384, :408-426), with the links as they were before.
+struct CullResult {
+    std::vector<std::int32_t> removedRows;
+    std::vector<std::uint8_t> removedWhy;
+    std::vector<std::int32_t> removedKeyframes, removedPrevious, removedNext;
+};
+
+// cullMapPoints + cullKeyframes (mapper_helpers.cpp:1095-1096) in ONE device call on the tables in place.  `current` and adjacentKfIds /
+// loopClosureKeyframes are slots; a candidate without a previous keyframe (:453) or named by a loop-closure edge (:455-464) is kept.  The
+// previous / next links of `chain` are relinked as removeKeyframe does (:414-420) and a removed slot's id becomes -1.
+inline CullResult cullMap(Context &ctx, DeviceKeyframeMapPoints &table, DeviceMapPointFlags *flags, DeviceMapPointLive &live, KeyframeChain &chain, std::int32_t current,
+                          const std::vector<std::int32_t> &adjacentKfIds, const std::vector<std::int32_t> &loopClosureKeyframes, const CullSettings &settings) {
+    const std::size_t nKf = table.size(), nMp = table.mapPointCount();
+    if (chain.previous.size() != nKf || chain.next.size() != nKf || chain.id.size() != nKf || chain.t.size() != nKf)
+        throw std::invalid_argument("cullMap: one link pair, one KfId and one time per slot");
+    if (live.size() < nMp || (flags && flags->size() < nMp)) throw std::invalid_argument("cullMap: fewer live bytes or flags than map points");
+    if (settings.cullPoints && !flags) throw std::invalid_argument("cullMap: cullMapPoints reads the flags");
+    std::vector<std::uint8_t> keep(adjacentKfIds.size(), 0), removed(adjacentKfIds.size(), 0);
+    for (std::size_t i = 0; i < adjacentKfIds.size(); ++i) {
+        const std::int32_t k = adjacentKfIds[i];
+        if (k < 0 || (std::size_t)k >= nKf) throw std::invalid_argument("cullMap: adjacent keyframe outside the table");
+        keep[i] = chain.previous[k] < 0 || std::find(loopClosureKeyframes.begin(), loopClosureKeyframes.end(), k) != loopClosureKeyframes.end();
+    }
+    const ms_cull_settings s{current, settings.cullPoints ? 1 : 0, settings.minMapPointCullingAge, (std::int32_t)settings.minObservationsForBA,
+                             settings.keyframeCullMaxCriticalRatio, settings.ratioFloat32 ? 1 : 0};
+    const std::size_t pitch = (nMp + 63) / 64 * 64;
+    std::int32_t *rows = reinterpret_cast<std::int32_t *>(ctx.workspace(5 * pitch + 256));
+    std::uint8_t *why = reinterpret_cast<std::uint8_t *>(rows + pitch);
+    std::int32_t nRows = 0, nKfs = 0;
+    ctx.check(ms_map_cull(ctx.get(), table.mutableTable(), (int)nKf, (int)table.stride(), flags ? flags->mutableFlags() : nullptr, live.mutableLive(), (int)nMp, chain.id.data(),
+                          chain.t.data(), adjacentKfIds.data(), keep.data(), (int)adjacentKfIds.size(), &s, nullptr, rows, why, removed.data(), &nRows, &nKfs), "ms_map_cull");
+    CullResult out;
+    out.removedRows = ctx.download(rows, (std::size_t)nRows); out.removedWhy = ctx.download(why, (std::size_t)nRows);
+    for (std::size_t i = 0; i < adjacentKfIds.size(); ++i) if (removed[i]) out.removedKeyframes.push_back(adjacentKfIds[i]);
+    std::sort(out.removedKeyframes.begin(), out.removedKeyframes.end(), [&](std::int32_t a, std::int32_t b) { return chain.id[a] > chain.id[b]; });
+    for (std::int32_t k : out.removedKeyframes) {            // :414-420, in the order of removal
+        const std::int32_t prev = chain.previous[k], next = chain.next[k];
+        out.removedPrevious.push_back(prev); out.removedNext.push_back(next);
+        if (next != -1) chain.previous[next] = prev;
+        if (prev != -1) chain.next[prev] = next;
+        chain.previous[k] = chain.next[k] = -1;
+        chain.id[k] = -1;
+    }
+    return out;
+}
+
+// ---- the passes over device observation lists (DeviceObservationLists, ms_map_refresh_lists, ms_triangulate_lists) -------------------
+// The map-point update of a new keyframe, mapper_helpers.cpp:1062-1077, without a per-point host structure: the observation lists of the
+// current keyframe's usable map points (status neither NOT_TRIANGULATED nor BAD, :1066) are built on the device, then updateDescriptor +
+// updateDistanceAndNorm (:1069-1070) and the status promotion of :1072-1076 run on them where they lie.  `pool` may be null (descriptors stay).
+// Returns the number of refreshed map points; `lists` holds them afterwards.
+inline std::size_t updateMapPoints(Context &ctx, DeviceObservationLists &lists, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags, const DeviceKeyframeMapPoints &table,
+                                   const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses, const std::vector<std::int32_t> &kfIds,
+                                   const std::vector<std::int32_t> &descBase, const DeviceDescriptorPool *pool, std::int32_t currentSlot, int minObservationsForBA,
+                                   const StaticSettings &settings) {
+    ObservationSelection sel;
+    sel.slot = currentSlot; sel.filter = MS_OBS_REFRESH; sel.dropEmpty = true;
+    const int levels = (int)settings.scaleFactors.size();
+    lists.build(table, keypoints, &flags, kfIds, pool ? descBase : std::vector<std::int32_t>(), sel, levels);
+    const ms_obs_lists l = lists.lists();
+    ctx.check(ms_map_refresh_lists(ctx.get(), mapPoints.position(), mapPoints.mutableNorm(), mapPoints.mutableMinDistance(), mapPoints.mutableMaxDistance(),
+                                   mapPoints.mutableDescriptor(), (int)mapPoints.size(), poses.pose(),
+                                   (int)poses.size(), pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, &l, (int)lists.rowCount(), (int)lists.observationCount(),
+                                   settings.scaleFactors.data(), levels, std::max(minObservationsForBA, 1), flags.mutableFlags(), nullptr), "ms_map_refresh_lists");
+    return lists.rowCount();
+}
+
+// The re-triangulation after local BA, mapper_helpers.cpp:1085-1092: the current keyframe's map points that are not TRIANGULATED or have at
+// least two observations (:1088), triangulated from device lists.  The per-point results come back as from triangulateMapPoints, in the
+// order of the keyframe's keypoints.
+inline TriangulateResult retriangulateCurrent(Context &ctx, DeviceObservationLists &lists, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags,
+                                              const DeviceKeyframeMapPoints &table, const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses,
+                                              const KeyframeCameras &cams, const std::vector<std::int32_t> &kfIds, std::int32_t currentSlot, const StaticSettings &settings,
+                                              TriangulationMethod method) {
+    if (cams.camera.size() != poses.size() || cams.focalLength.size() != poses.size()) throw std::invalid_argument("retriangulateCurrent: one camera per keyframe slot");
+    ObservationSelection sel;
+    sel.slot = currentSlot; sel.filter = MS_OBS_RETRIANGULATE;
+    lists.build(table, keypoints, &flags, kfIds, {}, sel, (int)settings.levelSigmaSq.size());
+    const Parameters &p = settings.parameters;
+    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    const std::size_t n = lists.rowCount();
+    TriangulateResult out;
+    out.status.assign(n, 0); out.reason.assign(n, 0); out.passCount.assign(n, 0);
+    const ms_obs_lists l = lists.lists();
+    ctx.check(ms_triangulate_lists(ctx.get(), mapPoints.mutablePosition(), flags.mutableFlags(), (int)mapPoints.size(), poses.pose(), (int)poses.size(), cams.camera.data(),
+                                   cams.focalLength.data(), &l, (int)n, (int)lists.observationCount(), &s, (int)method, out.status.data(), out.reason.data(),
+                                   out.passCount.data()), "ms_triangulate_lists");
+    return out;
+}
+
+// ---- matchTrackedFeatures on the device tables (ms_match_tracked, ms_match_tracked_finish) ----------------------------------------------
+// The current frame as matchTrackedFeatures reads it: its keyframe slot (the keypoints are in DeviceKeypointTable, the pose in
+// DeviceKeyframePoses; poseCW is the same pose on the host) and keyPointToTrackId per keypoint, -1 for none.
+struct TrackedFrame {
+    std::int32_t slot = 0;
+    DeviceKeyframePoses::Pose poseCW{};
+    std::vector<std::int32_t> keyPointToTrackId;
+};
+// Per keypoint the outcome (0 no track | 1 created | 2 just tracked | 3 bound after isInFrustum and checkReprojectionError | 4 outside the
+// frustum | 5 reprojection error | 6 absent track, no descriptors), the rows of the created map points with their keypoints (in keypoint
+// order: what nextMpId, the host MapPoint objects and their colours are derived from), the reference's debug counters, and FIRST_LAST's
+// result per just-tracked point.
+struct MatchTrackedResult {
+    std::vector<std::uint8_t> outcome;
+    std::vector<std::int32_t> createdRows, createdKeyPoints;
+    std::size_t newPoints = 0, justTriangulated = 0, checked = 0, frustumFail = 0, reproFail = 0, success = 0;
+    TriangulateResult firstLast;
+};
+
+// matchTrackedFeatures (mapper_helpers.cpp:67-142) for one frame on the device tables, nothing per keypoint on the host:
+//   ms_match_tracked (the walk: bind, gate, create) -> ms_observation_lists of the just-tracked rows -> ms_triangulate_lists FIRST_LAST (:90)
+//   -> ms_match_tracked_finish (the descriptor of the points that are now UNSURE, :811; the rows of :121) -> the refresh of :121-124: one pass
+//   when the frame has descriptors, otherwise the just-tracked TRIANGULATED rows with the descriptor half and the checked rows without it.
+// freeRows: table rows the caller offers to new map points, at least as many as the frame can create (the k-th created point takes the
+// k-th); `pool` must hold the frame's descriptors at descBase[slot] when that is >= 0.  `lists` is scratch and holds the last refresh's rows.
+inline MatchTrackedResult matchTrackedFeatures(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &table, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags,
+                                               DeviceMapPointLive &live, DeviceTrackTable &tracks, const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses,
+                                               const KeyframeCameras &cams, const std::vector<std::int32_t> &kfIds, const std::vector<std::int32_t> &descBase,
+                                               const DeviceDescriptorPool *pool, const TrackedFrame &frame, const std::vector<std::int32_t> &freeRows,
+                                               const StaticSettings &settings, float viewAngleLimitCos = 0.5f) {
+    const std::size_t nKf = table.size(), nMp = table.mapPointCount(), nKp = frame.keyPointToTrackId.size(), nNew = freeRows.size();
+    if (frame.slot < 0 || (std::size_t)frame.slot >= nKf) throw std::invalid_argument("matchTrackedFeatures: slot outside the table");
+    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || kfIds.size() != nKf || descBase.size() != nKf || poses.size() != nKf)
+        throw std::invalid_argument("matchTrackedFeatures: one camera, focal length, KfId, descriptor base and pose per slot");
+    if (mapPoints.size() != nMp || flags.size() < nMp || live.size() < nMp || tracks.mapPointCount() != nMp) throw std::invalid_argument("matchTrackedFeatures: the map-point tables differ in size");
+    if (keypoints.size() != nKf || keypoints.stride() != table.stride()) throw std::invalid_argument("matchTrackedFeatures: the keypoint table does not match the keyframe table");
+    const bool hasDescriptors = descBase[frame.slot] >= 0;
+    if (hasDescriptors && !pool) throw std::invalid_argument("matchTrackedFeatures: the frame has descriptors and there is no pool");
+    for (std::int32_t t : frame.keyPointToTrackId) if (t >= 0) tracks.ensureTrack(t);
+    const int levels = (int)settings.levelSigmaSq.size();
+    const Parameters &p = settings.parameters;
+    ms_tracked_frame f{};
+    f.slot = frame.slot;
+    std::copy(frame.poseCW.begin(), frame.poseCW.end(), f.pose);
+    f.cam = cams.camera[frame.slot]; f.focal = cams.focalLength[frame.slot];
+    f.desc_base = descBase[frame.slot]; f.track_base = tracks.trackBase();
+    f.level_sigma_sq = settings.levelSigmaSq.data(); f.n_levels = levels;
+    f.rel_reprojection_threshold = p.relativeReprojectionErrorThreshold; f.view_cos_limit = viewAngleLimitCos;
+    // device scratch: created rows | created keypoints | just-tracked rows | checked rows | refresh rows | outcomes
+    const std::size_t pitchKp = (nKp + 63) / 64 * 64 + 64, pitchNew = (nNew + 63) / 64 * 64 + 64;
+    std::int32_t *createdRows = reinterpret_cast<std::int32_t *>(ctx.workspace(4 * (2 * pitchNew + 4 * pitchKp) + pitchKp + 256));
+    std::int32_t *createdKp = createdRows + pitchNew, *trackedRows = createdKp + pitchNew, *checkedRows = trackedRows + pitchKp, *refreshRows = checkedRows + pitchKp;
+    std::uint8_t *outcome = reinterpret_cast<std::uint8_t *>(refreshRows + 2 * pitchKp);
+    std::int32_t counts[5] = {0, 0, 0, 0, 0};
+    ctx.check(ms_match_tracked(ctx.get(), table.mutableTable(), (int)nKf, (int)table.stride(), flags.mutableFlags(), live.mutableLive(), mapPoints.position(), mapPoints.norm(),
+                               mapPoints.minDistance(), mapPoints.maxDistance(), mapPoints.mutableDescriptor(), tracks.mpTrack(), (int)nMp, keypoints.x(), keypoints.y(),
+                               keypoints.octave(), pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, tracks.trackRow(), (int)tracks.window(), &f,
+                               frame.keyPointToTrackId.data(), (int)nKp, freeRows.data(), (int)nNew, outcome, createdRows, createdKp, trackedRows, checkedRows, counts),
+              "ms_match_tracked");
+    MatchTrackedResult out;
+    out.newPoints = (std::size_t)counts[0]; out.justTriangulated = (std::size_t)counts[1]; out.checked = (std::size_t)counts[2];
+    out.frustumFail = (std::size_t)counts[3]; out.reproFail = (std::size_t)counts[4];
+    out.outcome = ctx.download(outcome, nKp);
+    out.createdRows = ctx.download(createdRows, out.newPoints); out.createdKeyPoints = ctx.download(createdKp, out.newPoints);
+    const std::vector<std::int32_t> noBase;
+    auto listsOf = [&](const std::int32_t *rows, std::size_t n, bool dropEmpty) {
+        ObservationSelection sel;
+        sel.deviceRows = rows; sel.rowCount = n; sel.dropEmpty = dropEmpty;
+        lists.build(table, keypoints, &flags, kfIds, pool ? descBase : noBase, sel, levels);
+    };
+    std::size_t nTracked = 0;
+    if (out.justTriangulated) {                              // :90
+        listsOf(trackedRows, out.justTriangulated, false);
+        nTracked = lists.rowCount();
+        const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)levels, p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                                p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+        out.firstLast.status.assign(nTracked, 0); out.firstLast.reason.assign(nTracked, 0); out.firstLast.passCount.assign(nTracked, 0);
+        const ms_obs_lists l = lists.lists();
+        ctx.check(ms_triangulate_lists(ctx.get(), mapPoints.mutablePosition(), flags.mutableFlags(), (int)nMp, poses.pose(), (int)nKf, cams.camera.data(), cams.focalLength.data(), &l,
+                                       (int)nTracked, (int)lists.observationCount(), &s, MS_TRI_FIRST_LAST, out.firstLast.status.data(), out.firstLast.reason.data(),
+                                       out.firstLast.passCount.data()), "ms_triangulate_lists");
+    }
+    ms_obs_lists l = lists.lists();
+    if (!pool) l.obs_desc = nullptr;
+    std::int32_t nRefresh = 0;
+    ctx.check(ms_match_tracked_finish(ctx.get(), &l, (int)nTracked, flags.flags(), pool ? pool->descriptor() : nullptr, mapPoints.mutableDescriptor(), (int)nMp, checkedRows,
+                                      (int)out.checked, hasDescriptors ? 1 : 0, refreshRows, (int)(2 * pitchKp), &nRefresh), "ms_match_tracked_finish");
+    auto refresh = [&](const std::int32_t *rows, std::size_t n, bool descriptors) {                      // :121-124
+        if (n == 0) return;
+        listsOf(rows, n, true);
+        const ms_obs_lists r = lists.lists();
+        const bool withPool = descriptors && pool;
+        ctx.check(ms_map_refresh_lists(ctx.get(), mapPoints.position(), mapPoints.mutableNorm(), mapPoints.mutableMinDistance(), mapPoints.mutableMaxDistance(),
+                                       mapPoints.mutableDescriptor(), (int)nMp, poses.pose(), (int)nKf, withPool ? pool->descriptor() : nullptr, withPool ? (int)pool->size() : 0, &r,
+                                       (int)lists.rowCount(), (int)lists.observationCount(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(), 0, nullptr, nullptr),
+                  "ms_map_refresh_lists");
+    };
+    refresh(refreshRows, (std::size_t)nRefresh, true);
+    if (!hasDescriptors) refresh(checkedRows, out.checked, false);
+    out.success = (std::size_t)nRefresh + (hasDescriptors ? 0 : out.checked);
+    return out;
+}
+
+}  // namespace mi355slam

@@ -1,5 +1,5 @@
 // Compile + link check of the map-graph queries of the host mirror (DeviceKeyframeMapPoints, getNeighbors, computeAdjacentKeyframes,
-// localMapPoints in mi355slam/keyframe_matcher.hpp) against libmi355slam.so (tests/test_covis_abi.py), their comparison with a sequential
+// localMapPoints in mi355slam/map_tables.hpp and map_update.hpp) against libmi355slam.so (tests/test_covis_abi.py), their comparison with a sequential
 // std::map / std::set restatement of the reference's loops, and the one-core baseline tools/covis_probe.py times the device path against.
 //   covis_smoke --no-gpu                 every MS_ERR_INVALID case of ms_covisibility / ms_map_point_union through their _check halves (no
 //                                        context, no device), and the restatement below on a hand-computed map
@@ -17,7 +17,7 @@
 #include <random>
 #include <set>
 #include <vector>
-#include "mi355slam/keyframe_matcher.hpp"
+#include "mi355slam/map_update.hpp"
 
 using namespace mi355slam;
 

@@ -1,5 +1,5 @@
 // Compile + link check of the culling step of the host mirror (DeviceMapPointLive, observationCounts, cullMap in
-// mi355slam/keyframe_matcher.hpp) against libmi355slam.so (tests/test_map_cull_abi.py), its comparison with a sequential std::map
+// mi355slam/map_tables.hpp and map_update.hpp) against libmi355slam.so (tests/test_map_cull_abi.py), its comparison with a sequential std::map
 // restatement of the reference's loops (mapper_helpers.cpp:349-482, mapdb.cpp:161-174), and the one-core baseline tools/cull_probe.py times
 // the device path against.
 //   map_cull_smoke --no-gpu               every MS_ERR_INVALID case of ms_map_cull through ms_map_cull_check (no context, no device), and the
@@ -25,7 +25,7 @@
 #include <random>
 #include <set>
 #include <vector>
-#include "mi355slam/keyframe_matcher.hpp"
+#include "mi355slam/map_update.hpp"
 
 using namespace mi355slam;
 

@@ -1,5 +1,5 @@
 // Compile + link check of the table writers of the host mirror (DeviceKeyframePoses, DeviceMapPoints::refresh, mi355slam::correctLoop in
-// mi355slam/keyframe_matcher.hpp) against libmi355slam.so (tests/test_map_refresh_abi.py), their comparison with a sequential C++ restatement
+// mi355slam/map_tables.hpp and map_update.hpp) against libmi355slam.so (tests/test_map_refresh_abi.py), their comparison with a sequential C++ restatement
 // of the reference's loops, and the one-core baseline tools/map_refresh_probe.py times the device path against.
 //   map_refresh_smoke --no-gpu            every MS_ERR_INVALID case of ms_map_refresh / ms_loop_correct through their _check halves (no context,
 //                                         no device), and the restatement below on a hand-computed point
@@ -15,7 +15,8 @@
 #include <cstring>
 #include <random>
 #include <vector>
-#include "mi355slam/keyframe_matcher.hpp"
+#include "mi355slam/keyframe_matcher.hpp"       // detail::hamming256, the restatement's distance
+#include "mi355slam/map_update.hpp"
 
 using namespace mi355slam;
 

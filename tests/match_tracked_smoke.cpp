@@ -1,4 +1,4 @@
-// Compile + link check of the matchTrackedFeatures part of the host mirror (mi355slam/keyframe_matcher.hpp: DeviceTrackTable,
+// Compile + link check of the matchTrackedFeatures part of the host mirror (mi355slam/map_tables.hpp and map_update.hpp: DeviceTrackTable,
 // matchTrackedFeatures) against libmi355slam.so, and its run on one small map.
 //   match_tracked_smoke --no-gpu   the symbols link; a few calls of ms_match_tracked_check / ms_match_tracked_finish_check (no context, no device)
 //   match_tracked_smoke            mapper_helpers.cpp:67-142 twice on copies of one seeded map: through mi355slam::matchTrackedFeatures (nothing
@@ -14,7 +14,8 @@
 #include <cstring>
 #include <map>
 #include <vector>
-#include "mi355slam/keyframe_matcher.hpp"
+#include "mi355slam/keyframe_matcher.hpp"       // updateDescriptors, the restatement's medoid
+#include "mi355slam/map_update.hpp"
 
 using namespace mi355slam;
 

@@ -1,4 +1,4 @@
-// Compile + link check of the observation-list part of the host mirror (mi355slam/keyframe_matcher.hpp: DeviceKeypointTable,
+// Compile + link check of the observation-list part of the host mirror (mi355slam/map_tables.hpp and map_update.hpp: DeviceKeypointTable,
 // DeviceObservationLists, updateMapPoints, retriangulateCurrent) against libmi355slam.so, and its run on one small map.
 //   obs_lists_smoke --no-gpu    the symbols link; a few calls of ms_observation_lists_check (no context, no device)
 //   obs_lists_smoke --baseline MAP K S M SLOT   the one-core baseline tools/obs_lists_probe.py times, on the map file of map_cull_smoke
@@ -16,7 +16,7 @@
 #include <cstring>
 #include <map>
 #include <vector>
-#include "mi355slam/keyframe_matcher.hpp"
+#include "mi355slam/map_update.hpp"
 
 using namespace mi355slam;
 

@@ -1,5 +1,5 @@
-"""The matchTrackedFeatures part of the host mirror (DeviceTrackTable and matchTrackedFeatures in slam-module_amd/host/mi355slam/keyframe_matcher.hpp)
-compiles, links against the C ABI and, on the GPU, gives the outcomes, counters and tables of a sequential restatement that walks
+"""The matchTrackedFeatures part of the host mirror (DeviceTrackTable in slam-module_amd/host/mi355slam/map_tables.hpp and matchTrackedFeatures in
+map_update.hpp) compiles, links against the C ABI and, on the GPU, gives the outcomes, counters and tables of a sequential restatement that walks
 keyPointToTrackId and trackIdToMapPoint in std::maps and hands host lists to the host-list entry points (tests/match_tracked_smoke.cpp)."""
 import os
 import re
@@ -26,7 +26,7 @@ def test_mirror_compiles_links_and_the_validation_runs_without_a_device():
 
 
 def test_no_std_map_in_the_mirror():
-    hpp = open(os.path.join(ROOT, "slam-module_amd", "host", "mi355slam", "keyframe_matcher.hpp")).read()
+    hpp = open(os.path.join(ROOT, "slam-module_amd", "host", "mi355slam", "map_update.hpp")).read()
     code = re.sub(r"//[^\n]*", "", hpp)
     body = code[code.index("inline MatchTrackedResult matchTrackedFeatures"):]
     body = body[:body.index("\n}\n")]

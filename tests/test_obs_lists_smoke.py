@@ -1,5 +1,5 @@
-"""The observation-list part of the host mirror (DeviceKeypointTable, DeviceObservationLists, updateMapPoints, retriangulateCurrent in
-slam-module_amd/host/mi355slam/keyframe_matcher.hpp) compiles, links against the C ABI and, on the GPU, gives the tables of a sequential
+"""The observation-list part of the host mirror (DeviceKeypointTable, DeviceObservationLists in slam-module_amd/host/mi355slam/map_tables.hpp,
+updateMapPoints, retriangulateCurrent in map_update.hpp) compiles, links against the C ABI and, on the GPU, gives the tables of a sequential
 restatement that keeps std::map<KfId, KpId> observations per map point (tests/obs_lists_smoke.cpp)."""
 import os
 import re
@@ -26,7 +26,7 @@ def test_mirror_compiles_links_and_the_validation_runs_without_a_device():
 
 
 def test_no_std_map_of_observations_in_the_mirror():
-    hpp = open(os.path.join(ROOT, "slam-module_amd", "host", "mi355slam", "keyframe_matcher.hpp")).read()
+    hpp = open(os.path.join(ROOT, "slam-module_amd", "host", "mi355slam", "map_update.hpp")).read()
     code = re.sub(r"//[^\n]*", "", hpp)
     for name in ("updateMapPoints", "retriangulateCurrent"):
         body = code[code.index("inline", code.index(name) - 80):]

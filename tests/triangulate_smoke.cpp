@@ -1,4 +1,4 @@
-// Compile + link check of the triangulator of the host mirror (mi355slam::triangulateMapPoints in mi355slam/keyframe_matcher.hpp) against
+// Compile + link check of the triangulator of the host mirror (mi355slam::triangulateMapPoints in mi355slam/map_update.hpp) against
 // libmi355slam.so (tests/test_triangulate_abi.py) and its run on one small scene (tests/test_gpu_triangulate.py).
 //   triangulate_smoke --no-gpu       the MS_ERR_INVALID cases of ms_triangulate through ms_triangulate_check (no context, no device); this is
 //                                    also the stand-alone program the host validation runs under the sanitizers with
@@ -10,7 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "mi355slam/keyframe_matcher.hpp"
+#include "mi355slam/map_update.hpp"
 
 using namespace mi355slam;
 
