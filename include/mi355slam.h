@@ -187,6 +187,12 @@ int ms_keypoints_unpack(const uint8_t *records, int n, float *x, float *y, float
  * 1 .. 8 = every workgroup uses r, no taper.  MS_ERR_INVALID for anything else.  Holds for the calls that follow. */
 int ms_orb_set_describe_strip(ms_orb *orb, int r);
 
+/* Which workgroup of the describe kernel describes which keypoint, and when (a test hook; outputs are bit for bit the same for every value).
+ * Bit 0: the workgroups dealt to one XCD take a contiguous run of the launch plan's blocks (whole frames through one L2).
+ * Bit 1: a level's detections are visited in a spatial order (row bands, x inside a band) instead of score order; each still lands in its slot.
+ * The default is 1 (the visit order costs the slot kernel what it saves the describe kernel).  MS_ERR_INVALID for anything outside 0 .. 3.  Holds for the calls that follow. */
+int ms_orb_set_describe_order(ms_orb *orb, int mode);
+
 /* Per-kernel timing of ms_orb_extract with HIP events on the context stream (off by default).
  * Stage order: 0 resize (all levels), 1 blur, 2 fast, 3 select, 4 tracks, 5 describe.
  * ms_orb_stage_ms synchronises and returns the durations of the LAST ms_orb_extract call. */

@@ -1,5 +1,6 @@
 // The launch plan of k_describe (orb.hip): which workgroup describes which output slots.  Plain C++, no HIP: the library builds the
-// plan from it, the kernel decodes its block index with it, and tests/describe_strips_check.cpp checks both on the CPU.
+// plan from it, the kernel decodes its block index with it, and tests/describe_strips_check.cpp checks both on the CPU
+// (remap, which deals the logical blocks to the physical ones: tests/describe_order_check.cpp).
 //
 // A workgroup is four waves.  A wave pays its setup once (tables to LDS, lane tables, the frame's counts and pointers, one block barrier)
 // and then walks a STRIP of r keypoints, 1 <= r <= 8, one after another in the same registers and the same LDS slab: wave wv of the block
@@ -11,7 +12,8 @@
 // halved r down to 2 with as many frames as give one device-full of blocks each, and at the end frames with r = 1 whose blocks number
 // at least twice what the device holds at once.  A block of the long region that starts last still has (4 +) 2 + 2 keypoint durations of
 // shorter work behind it.  A launch that has no more than those two device-fulls of blocks at r = 1 is all r = 1.
-// Long strips are not free: the slots the device works on at one time span r times as many frames, and their pyramids share the caches.
+// Long strips are not free: the slots the device works on at one time span r times as many frames, and their pyramids share the caches
+// (remap, below, keeps a frame's blocks on one L2, which is what lets the long region run at 8).
 #pragma once
 #include <cstdint>
 
@@ -20,7 +22,7 @@ namespace describe_strips {
 constexpr int kWaves = 4;            // waves of a workgroup = slots between two keypoints of a wave
 constexpr int kMaxStrip = 8;         // longest strip (the kernel's per-wave tables hold this many keypoints)
 constexpr int kMaxRegions = 4;
-constexpr int kLongStrip = 4;        // r of the automatic plan's first region (measured: 4 beats 8 and 2)
+constexpr int kLongStrip = 8;        // r of the automatic plan's first region (measured: with remap 8 beats 4 and 2; without it 4 beat 8)
 constexpr int64_t kGridLimit = 0x7FFFFFFF;
 
 // Blocks [block0, next region's block0) describe frames frame0 .., bpf blocks each.  inv = (2^32 - 1) / bpf: the quotient by one
@@ -84,6 +86,32 @@ constexpr Strip decode(const Plan &p, uint32_t block) {
     uint32_t q = (uint32_t)(((uint64_t)local * inv) >> 32), s = local - q * bpf;
     if (s >= bpf) { ++q; s -= bpf; }
     return Strip{frame0 + (int32_t)q, (int32_t)(s * (uint32_t)(kWaves * r)), r};
+}
+
+// Physical block index -> logical block index (the one decode takes): which workgroup describes which strip, for the caches' sake alone.
+// The dispatcher deals consecutive workgroups round robin to the device's eight XCDs, each with an L2 of its own, so with the identity the
+// blocks of a frame land on all eight L2s and every L2 pulls every frame's pyramid.  Here each region of the plan is permuted within itself:
+// the blocks whose index inside the region is x modulo kXcds get ONE contiguous run of logical blocks -- whole frames one after another -- and
+// walk it in rising order.  With n = 8 q + rem blocks in the region the run of label x starts at x (q + 1) for x < rem and at
+// rem (q + 1) + (x - rem) q behind them; it holds q + (x < rem) blocks, one for every physical block of that label.  A bijection of every
+// region onto itself for every n >= 1 (n < 8: the identity), so the regions still run in plan order and the taper keeps its meaning.
+// Nothing depends on where a block really runs: a dispatcher that deals otherwise only loses the reuse.
+constexpr int kXcds = 8;
+constexpr uint32_t remap(const Plan &p, uint32_t block) {
+    // (field by field, as in decode.  A region ends where the next one starts; the last one of the plan at the block count -- an unused record's
+    // block0 is not below it)
+    uint32_t block0 = (uint32_t)p.reg[0].block0, end = (uint32_t)p.reg[1].block0;
+    for (int k = 1; k < kMaxRegions; ++k) {
+        const bool in = block >= (uint32_t)p.reg[k].block0;
+        block0 = in ? (uint32_t)p.reg[k].block0 : block0;
+        const uint32_t next = k + 1 < kMaxRegions ? (uint32_t)p.reg[k + 1 < kMaxRegions ? k + 1 : k].block0 : (uint32_t)p.blocks;
+        end = in ? next : end;
+    }
+    end = end < (uint32_t)p.blocks ? end : (uint32_t)p.blocks;
+    const uint32_t local = block - block0, n = end - block0;
+    const uint32_t x = local % kXcds, j = local / kXcds, q = n / kXcds, rem = n % kXcds;
+    const uint32_t start = x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q;
+    return block0 + start + j;
 }
 
 // Trips of wave wv of a strip that starts at slot0 in a frame of `total` keypoints: its slots slot0 + wv + 4 k < total, k < r.

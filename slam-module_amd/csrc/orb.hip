@@ -19,6 +19,7 @@
 // x86-64 SSE2 scalar build (CMakeLists.txt:4-5: -O2, no -march).
 #include "ms_internal.h"
 #include "fast_tiles.h"
+#include "describe_order.h"
 #include "describe_strips.h"
 #include "describe_lanes.h"
 #include "describe_steer.h"
@@ -1030,23 +1031,72 @@ __device__ __forceinline__ int wave_sum(int v) {      // DPP inclusive scan, tot
     return __builtin_amdgcn_readlane(wave_scan_add(v), 63);
 }
 
-// Output slot -> detection, two dwords per slot (x | y << 16, level: coordinates up to the 32767 ms_orb_create admits), and the frame's keypoint total: k_describe's waves found their keypoint through a chain
+// Visit position -> detection, two dwords per position (x | y << 16, level | output slot << 8: coordinates up to the 32767 ms_orb_create admits), and the frame's keypoint total: k_describe's waves found their keypoint through a chain
 // of dependent loads (the counts of all levels -> a 16-step search for the level -> the level's base in the geometry table -> the coordinates), ~150 scalar
 // instructions and three round trips in front of the window fetch of EVERY wave.  One block per (level, frame) writes the level's run of the table once.
+// SPATIAL: the level's run is visited in the order of describe_order::key instead of k_select's score order (the outputs stay in their slots).
+template <bool SPATIAL>            // (a kernel of its own: the plain table needs no LDS)
 __global__ __launch_bounds__(256) void k_slots(const int16_t *__restrict__ det_x, const int16_t *__restrict__ det_y, const int32_t *__restrict__ det_count,
                                                const int32_t *__restrict__ trk_count, uint2 *__restrict__ slot_tab, int32_t *__restrict__ out_count,
                                                TileLevels TL, int det_stride, int capacity) {
-    const int l = blockIdx.x, f = blockIdx.y;
+    __shared__ uint32_t s_key[SPATIAL ? kMaxQuota : 1];                              // a detection's key below the band (describe_order::in_band_key), grouped by band
+    __shared__ uint16_t s_y[SPATIAL ? kMaxQuota : 1];
+    __shared__ int s_start[SPATIAL ? describe_order::kMaxBands : 1], s_cur[SPATIAL ? describe_order::kMaxBands : 1], s_w[4];
+    const int l = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
     int base = trk_count[f];
     for (int k = 0; k < l; ++k) base += det_count[f * TL.levels + k];
     const int cnt = det_count[f * TL.levels + l];
+    const int n = max(min(min(cnt, capacity - base), kMaxQuota), 0);       // the level's detections that have an output slot
     const uint64_t s0 = (uint64_t)f * det_stride + TL.L[l].det_base;
-    for (int i = threadIdx.x; i < cnt; i += 256)
-        if (base + i < capacity) slot_tab[(uint64_t)f * capacity + base + i] = uint2{(uint32_t)(uint16_t)det_x[s0 + i] | ((uint32_t)(uint16_t)det_y[s0 + i] << 16), (uint32_t)l};
-    if (l == TL.levels - 1 && threadIdx.x == 0) out_count[f] = min(base + cnt, capacity);
+    uint2 *const tab = slot_tab + (uint64_t)f * capacity + base;
+    // (the output slot of detection i of the level is base + i whatever position visits it)
+    if constexpr (!SPATIAL) {
+        for (int i = tid; i < n; i += 256) tab[i] = uint2{(uint32_t)(uint16_t)det_x[s0 + i] | ((uint32_t)(uint16_t)det_y[s0 + i] << 16), describe_order::pack(l, base + i)};
+    } else {
+        // Visit position of a detection = how many of the level's keys (describe_order.h: row band, x along the band, index) are smaller than its own.  The
+        // band is the key's top, so that is the count of the bands above plus the count of smaller keys INSIDE its band: a histogram of the bands, its running
+        // sum, the keys grouped by band (in whatever order the appends land: the keys are distinct, a rank does not depend on it), and one walk over the own
+        // band's keys per detection -- n * n / bands compares for a level spread over its bands where a sort network's log^2 n steps each wait for LDS
+        // (a bitonic sort of 64-bit keys here: 0.040 ms per 256 x 720p launch against 0.005 ms for the plain table; this: 0.013 ms).  A level whose detections all lie
+        // in ONE band pays n * n (estimated, not measured: 4096 of them ~0.5 ms in its block; a quota of 600 ~4 us).
+        for (int b = tid; b < describe_order::kMaxBands; b += 256) s_cur[b] = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) atomicAdd(&s_cur[min(describe_order::band_of(det_y[s0 + i] & 0x7FFF), (uint32_t)describe_order::kMaxBands - 1)], 1);
+        __syncthreads();
+        {   // exclusive running sum over the bands: four bands per thread, wave scan, the waves' totals
+            int c[4], sum = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { c[k] = s_cur[4 * tid + k]; sum += c[k]; }
+            const int incl = wave_scan_add(sum);
+            if ((tid & 63) == 63) s_w[tid >> 6] = incl;
+            __syncthreads();
+            int at = incl - sum;
+            for (int w = 0; w < (tid >> 6); ++w) at += s_w[w];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { s_start[4 * tid + k] = at; s_cur[4 * tid + k] = at; at += c[k]; }
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            const int x = det_x[s0 + i] & 0x7FFF, y = det_y[s0 + i] & 0x7FFF;           // (coordinates are 0 .. 32767)
+            const uint32_t band = describe_order::band_of(y);
+            const int p = atomicAdd(&s_cur[band], 1);                                   // < n: the bands' counts sum to n
+            s_key[p] = describe_order::in_band_key(x, band, i); s_y[p] = (uint16_t)y;
+        }
+        __syncthreads();                                                                // s_cur[band] is now the band's end
+        for (int p = tid; p < n; p += 256) {
+            const uint32_t mine = s_key[p], y = s_y[p], band = describe_order::band_of((int)y);
+            const int lo = s_start[band], hi = s_cur[band];
+            int pos = lo;
+            for (int q = lo; q < hi; ++q) pos += s_key[q] < mine;
+            const int i = (int)(mine & ((1u << describe_order::kIndexBits) - 1));
+            const uint32_t along = mine >> describe_order::kIndexBits, x = (band & 1u) ? (uint32_t)((1 << describe_order::kCoordBits) - 1) - along : along;
+            tab[pos] = uint2{x | (y << 16), describe_order::pack(l, base + i)};
+        }
+    }
+    if (l == TL.levels - 1 && tid == 0) out_count[f] = min(base + cnt, capacity);
 }
 
-// Keypoints per wave.  A wave of k_describe walks a STRIP of keypoints one after another (describe_strips.h: 4 in the long region of a large launch, then 2, then 1;
+// Keypoints per wave.  A wave of k_describe walks a STRIP of keypoints one after another (describe_strips.h: 8 in the long region of a large launch, then 4, 2 and 1;
 // 1 throughout for a launch without more than two device-fulls of blocks), in the same registers and the same LDS slab, and pays once per strip what a wave of one
 // keypoint paid per keypoint: the tables to LDS, the lane tables, the frame's counts, the block barrier, and the chain of dependent scalar loads slot entry ->
 // level -> geometry -> frame pointers (13 s_waitcnt lgkmcnt(0), 5 vmcnt and the barrier in the 197 instructions in front of the first window load; now 31
@@ -1054,7 +1104,10 @@ __global__ __launch_bounds__(256) void k_slots(const int16_t *__restrict__ det_x
 //     one keypoint per wave (the parent)         0.4376 .. 0.4437
 //     long strips of 2 / 4 / 8                   0.436  / 0.4168 .. 0.4188 / 0.4394 .. 0.4416
 // Longer is not better: the slots in flight at one time span r times as many frames, whose pyramids share the caches (FETCH_SIZE + 17 % at r = 4, + 24 % at
-// r = 8), and that eats what the setup saves.  With the next keypoint's window fetched under the BRIEF tests of the current one (64 VGPRs, no scratch, the
+// r = 8), and that eats what the setup saves -- while the blocks of a frame are dealt to all eight L2s.  With each XCD's blocks on a contiguous run of the
+// plan (describe_strips::remap; profiles/r09_a_ab_describe_order.txt) FETCH_SIZE falls to 31 % at strips of 4 and to 57 % at 8, and 8 is the fastest:
+//     remap, long strips of 2 / 4 / 8            0.4320 .. 0.4329 / 0.4105 .. 0.4127 / 0.4009 .. 0.4039      (same session: without remap, 4: 0.4191 .. 0.4215)
+// With the next keypoint's window fetched under the BRIEF tests of the current one (64 VGPRs, no scratch, the
 // same LDS) the kernel took 0.4185 .. 0.4196 ms against 0.4168 .. 0.4188 without: not kept.
 // What round 1 measured on ITS kernel (separate blurred patch, a level search per wave, 7 waves per SIMD, the blur on the vector pipe) does not carry over:
 // "four one after another with the next one's patches prefetched" was 0.63 of 0.60 ms there, and of the same list the per-slot table (0.583 -> 0.542 ms)
@@ -1062,7 +1115,7 @@ __global__ __launch_bounds__(256) void k_slots(const int16_t *__restrict__ det_x
 // cost registers (100 VGPRs, 30 KB LDS, slower: DESIGN section 10); 16-byte row pieces and one scattered store for all outputs did nothing.
 
 // A keypoint of a wave's strip as the loop wants it: everything a lane resolved in front of the loop (k_describe), read back as scalars
-struct DescKp { int x, y, oct, tid_out, pitch, w, h; float ox, oy; bool inner; uint64_t off; };
+struct DescKp { int x, y, oct, tid_out, pitch, w, h, slot; float ox, oy; bool inner; uint64_t off; };
 // The per-wave tables live in the dwords of the wave's slab that neither the window (0 .. 575, with the parked ninth piece) nor pass 1 of the
 // blur (row 47's fourth 16-byte unit ends at dword 579) touches: the geometry of the 16 levels, 6 dwords each, and the strip's keypoints, 12 each
 constexpr int kDescGeoDword = 584, kDescGeoStride = 6, kDescRecDword = kDescGeoDword + kDescGeoStride * MS_MAX_LEVELS, kDescRecStride = 12;
@@ -1077,7 +1130,7 @@ __device__ __forceinline__ DescKp desc_scalars(const DescRec &r) {
     DescKp K;
     K.x = (int)s(a.x); K.y = (int)s(a.y); K.oct = (int)(s(a.z) & 0xFFu); K.inner = (s(a.z) >> 8) != 0; K.tid_out = (int)s(a.w);
     K.ox = __uint_as_float(s(b.x)); K.oy = __uint_as_float(s(b.y)); K.pitch = (int)s(b.z); K.w = (int)s(b.w);
-    K.h = (int)s(c.x); K.off = (uint64_t)s(c.y) | ((uint64_t)s(c.z) << 32);
+    K.h = (int)s(c.x); K.off = (uint64_t)s(c.y) | ((uint64_t)s(c.z) << 32); K.slot = (int)s(c.w);
     return K;
 }
 typedef int v4i_t __attribute__((ext_vector_type(4)));
@@ -1093,15 +1146,16 @@ __device__ __forceinline__ void transpose4_rows(uint32_t (&r)[4]) {
 
 // amdgpu_waves_per_eu(8, 8): the register allocation aims at 8 waves per SIMD (the kernel is bound by how many keypoints are in flight)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_describe(FrameSrc src, TileLevels TL, describe_strips::Plan plan, const uint4 *__restrict__ moment_tab, const float4 *__restrict__ pattern_f,
-                                                  const uint2 *__restrict__ slot_tab, int capacity, int max_tracks, int lk_level,
+                                                  const uint2 *__restrict__ slot_tab, int capacity, int max_tracks, int lk_level, int xcd_runs,
                                                   const int16_t *__restrict__ trk_x, const int16_t *__restrict__ trk_y, const float *__restrict__ trk_px,
                                                   const float *__restrict__ trk_py, const int32_t *__restrict__ trk_id, const int32_t *__restrict__ trk_count,
                                                   float *__restrict__ out_x, float *__restrict__ out_y, float *__restrict__ out_angle,
                                                   int32_t *__restrict__ out_octave, uint32_t *__restrict__ out_desc, int32_t *__restrict__ out_track,
                                                   const int32_t *__restrict__ out_count) {
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // block -> (frame, first slot of the block's strips, strip length): scalar arithmetic on the plan's region records (describe_strips.h), no load
-    const describe_strips::Strip strip = describe_strips::decode(plan, blockIdx.x);
+    // block -> (frame, first slot of the block's strips, strip length): scalar arithmetic on the plan's region records (describe_strips.h), no load.
+    // xcd_runs: the blocks that the dispatcher deals to one XCD take a contiguous run of the plan's blocks, whole frames through one L2 (remap)
+    const describe_strips::Strip strip = describe_strips::decode(plan, xcd_runs ? describe_strips::remap(plan, blockIdx.x) : blockIdx.x);
     const int f = strip.frame, R = min(strip.r, describe_strips::kMaxStrip);
     const int slot0 = strip.slot0 + wv;                      // the wave's first slot; its k-th keypoint is slot0 + 4 k.  Wave-uniform: everything derived from it is scalar
     // A keypoint is a chain of dependent memory round trips (its slot -> coordinates -> patch -> angle -> BRIEF samples) and the
@@ -1156,7 +1210,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // a memory load that depends on the level
     if (lane < R) {
         const bool trk = myslot < nt;
-        const int level = trk ? lk_level : (int)min(ent.y, (uint32_t)(MS_MAX_LEVELS - 1));      // (an entry beyond the total is stale, not wild; its record is not read)
+        const int level = trk ? lk_level : min(describe_order::level_of(ent.y), MS_MAX_LEVELS - 1);      // (an entry beyond the total is stale, not wild; its record is not read)
         const uint32_t *g = geo + kDescGeoStride * level;
         const int pitch = (int)g[0], w = (int)g[1], h = (int)g[2];
         const float scale = __uint_as_float(g[3]);
@@ -1168,7 +1222,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         uint32_t *r = rec + kDescRecStride * lane;
         *reinterpret_cast<uint4 *>(r) = uint4{(uint32_t)x, (uint32_t)y, (uint32_t)level | (inner ? 256u : 0u), (uint32_t)(trk ? tid : -1)};
         *reinterpret_cast<uint4 *>(r + 4) = uint4{__float_as_uint(ox), __float_as_uint(oy), (uint32_t)pitch, (uint32_t)w};
-        *reinterpret_cast<uint4 *>(r + 8) = uint4{(uint32_t)h, (uint32_t)off, (uint32_t)(off >> 32), 0u};
+        *reinterpret_cast<uint4 *>(r + 8) = uint4{(uint32_t)h, (uint32_t)off, (uint32_t)(off >> 32), (uint32_t)(trk ? myslot : describe_order::slot_of(ent.y))};   // the output slot: a detection's is its table entry's (k_slots)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1331,7 +1385,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const uint32_t i1 = describe_brief_index::index_from_bits(r1, c1, pbase), i2 = describe_brief_index::index_from_bits(r2, c2, pbase);
             bits[q] = __ballot(*(const lds_u8_t *)(uintptr_t)i1 < *(const lds_u8_t *)(uintptr_t)i2);
         }
-        const uint64_t o = (uint64_t)f * capacity + slot0 + 4 * k;
+        const uint64_t o = (uint64_t)f * capacity + K.slot;        // (slot0 + 4 k is the VISIT position)
         if (lane < 8) out_desc[o * 8 + lane] = (uint32_t)(bits[lane >> 1] >> ((lane & 1) * 32));
         if (lane == 0) { out_x[o] = K.ox; out_y[o] = K.oy; out_angle[o] = angle_deg; out_octave[o] = K.oct; out_track[o] = K.tid_out; }
         // the last BRIEF read of the patch has been consumed (the ballots): the next keypoint's window may take the slab
@@ -1374,6 +1428,7 @@ struct ms_orb {
     bool wide[MS_MAX_LEVELS] = {false};
     uint4 *d_moment_tab = nullptr;            // k_describe: disc mask of the orientation patch, four dwords per lane
     float4 *d_pattern_f = nullptr;            // k_describe: the 256 BRIEF point pairs as floats
+    int describe_order = describe_order::kDefaultMode;   // bit 0: XCD-contiguous blocks (describe_strips::remap), bit 1: spatial visit order (k_slots) (ms_orb_set_describe_order)
     int describe_strip = 0;                   // k_describe: 0 = the automatic launch plan (describe_strips.h), 1 .. 8 = every wave walks that many keypoints (ms_orb_set_describe_strip)
     // optional per-stage HIP events (ms_orb_set_profiling)
     bool profiling = false;
@@ -1494,6 +1549,10 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
     }
     G.det_stride = std::max(cfg->max_kpts, det_base);       // the reference keeps per-level vectors, so a frame can hold sum(quota) > maxKeypoints points
     G.capacity = G.det_stride + cfg->max_tracks;
+    if (G.capacity >= (1 << (32 - describe_order::kSlotShift))) {      // a slot-table entry holds the output slot beside the level
+        delete o;
+        return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: %d output slots per frame (max %d)", G.capacity, (1 << (32 - describe_order::kSlotShift)) - 1);
+    }
     for (int l = 0; l < cfg->levels; ++l) {
         const LevelGeom &L = G.L[l];
         const int sel_k = (cfg->min_distance > 0.f && L.min_dist >= 2) ? std::min(4 * L.quota, kMaxQuota) : L.quota;     // k_select's `want`
@@ -1620,6 +1679,12 @@ int ms_orb_set_describe_strip(ms_orb *o, int r) {
     return MS_OK;
 }
 
+int ms_orb_set_describe_order(ms_orb *o, int mode) {
+    if (!o || mode < 0 || (mode & ~describe_order::kModeMask)) return MS_ERR_INVALID;
+    o->describe_order = mode;
+    return MS_OK;
+}
+
 int ms_orb_set_profiling(ms_orb *o, int enable) {
     if (!o) return MS_ERR_INVALID;
     ms_ctx *c = o->ctx;
@@ -1741,14 +1806,17 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     detect_range.end();
     MsRange describe_range("describe");
     const size_t C = (size_t)G.capacity;
-    hipLaunchKernelGGL(k_slots, dim3(G.levels, nf), dim3(256), 0, st, det_x, det_y, det_count, trk_count, o->d_slot_tab + F * C, o->d_count + F, o->tile_levels, G.det_stride, G.capacity);
+    if (o->describe_order & describe_order::kSpatial)
+        hipLaunchKernelGGL(k_slots<true>, dim3(G.levels, nf), dim3(256), 0, st, det_x, det_y, det_count, trk_count, o->d_slot_tab + F * C, o->d_count + F, o->tile_levels, G.det_stride, G.capacity);
+    else
+        hipLaunchKernelGGL(k_slots<false>, dim3(G.levels, nf), dim3(256), 0, st, det_x, det_y, det_count, trk_count, o->d_slot_tab + F * C, o->d_count + F, o->tile_levels, G.det_stride, G.capacity);
     MS_KERNEL_CHECK(c, "k_slots");
     // which block describes which slots: long strips first, a tail of one-keypoint blocks twice what the device holds at once (8 blocks per CU); a launch
     // without more blocks than that tail -- a single frame, the frame-by-frame legs -- is one keypoint per wave throughout
     describe_strips::Plan plan;
     if (!describe_strips::build(nf, G.capacity, 8ll * std::max(c->n_cu, 1), o->describe_strip, plan)) return ms_fail(c, MS_ERR_CAPACITY, "k_describe: %d frames of %d slots exceed the grid", nf, G.capacity);
     hipLaunchKernelGGL(k_describe, dim3(plan.blocks), dim3(256), 0, st, src, o->tile_levels, plan, o->d_moment_tab, o->d_pattern_f,
-                       o->d_slot_tab + F * C, G.capacity, G.max_tracks, G.lk_level, o->d_trk_x + F * T, o->d_trk_y + F * T, o->d_trk_px + F * T, o->d_trk_py + F * T, o->d_trk_id + F * T, trk_count, o->d_x + F * C, o->d_y + F * C,
+                       o->d_slot_tab + F * C, G.capacity, G.max_tracks, G.lk_level, o->describe_order & describe_order::kRemap, o->d_trk_x + F * T, o->d_trk_y + F * T, o->d_trk_px + F * T, o->d_trk_py + F * T, o->d_trk_id + F * T, trk_count, o->d_x + F * C, o->d_y + F * C,
                        o->d_angle + F * C, o->d_octave + F * C, o->d_desc + F * C * 8, o->d_track + F * C, o->d_count + F);
     MS_KERNEL_CHECK(c, "k_describe");
     MS_STAGE_MARK();

@@ -329,6 +329,11 @@ class OrbExtractor:
         A test hook: the outputs are the same for every value."""
         self.ctx.check(lib().ms_orb_set_describe_strip(self._h, int(r)), "ms_orb_set_describe_strip")
 
+    def set_describe_order(self, mode):
+        """Which workgroup of the describe kernel takes which keypoint: bit 0 = XCD-contiguous blocks, bit 1 = spatial visit order (default 1).
+        A test hook: the outputs are the same for every value."""
+        self.ctx.check(lib().ms_orb_set_describe_order(self._h, int(mode)), "ms_orb_set_describe_order")
+
     def set_profiling(self, enable=True):
         self.ctx.check(lib().ms_orb_set_profiling(self._h, int(enable)), "ms_orb_set_profiling")
 
