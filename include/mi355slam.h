@@ -973,6 +973,98 @@ int ms_match_tracked_finish_check(const ms_obs_lists *lists, int n_rows, const u
     int n_mp, const int32_t *checked_rows, int n_checked, int append_checked, const int32_t *refresh_rows, int cap_refresh,
     const int32_t *n_refresh, char *why, size_t why_bytes);
 
+/* ---- fusing duplicate map points on the device map tables ------------------------------------------------------------------
+ * ms_map_fuse: the walk of replaceDuplication (keyframe_matcher.cpp:424-526) behind its gates and its descriptor search, on the tables of
+ * 9.6 / 9.8 / 9.11 in place: kf_mp, mp_flags (the 9.6 encoding), mp_live, n_obs (DEVICE int32 [n_mp], in / out: the caller passes what
+ * ms_observation_count gave and the walk keeps it current) and, both or neither, mp_track / track_row with track_base and n_track.
+ * mp_index (HOST [n_entries]) is the array given to ms_project_gate; views[v] = {slot, first, count} are the gate's slices plus the walked
+ * keyframe's slot; n_kept (HOST [n_views]) and kept_entry / top_idx / top_dist (DEVICE, packed per view at views[v].first) are what
+ * ms_project_gate (MS_GATE_FUSE) and ms_projection_topk left.  The candidate of kept query q is top_idx[4q] when it is >= 0 and
+ * top_dist[4q] <= max_dist (50 in the reference), else none; an entry the gate dropped has none.
+ * The graph filters of :429-440 are part of the walk: the caller gates every valid row of its list without pre-filtering, which is legal
+ * because replaceDuplication changes no position, normal, distance or descriptor, and a filter is a `continue` without side effects.
+ * Views are walked in order, the entries of a view in slice order.  Entry e, row m = mp_index[e], K = views[v].slot; the first rule that
+ * matches the CURRENT state of the tables gives outcome[e]:
+ *   1  mp_live[m] == 0 (:429: erased earlier in this call, or before it)                       nothing
+ *   2  m is a valid entry of slot K (:434)                                                     nothing
+ *   3  (mp_flags[m] & 2) == 0 (:438)                                                           nothing
+ *   0  no candidate                                                                            nothing
+ *   4  candidate k, kf_mp[K][k] not valid (:502-505)                                           kf_mp[K][k] = m, n_obs[m] += 1
+ *   5  x = kf_mp[K][k], n_obs[m] < n_obs[x] and (mp_flags[x] & 2) == 0 (:511-514)              n_obs[x] -= 1, kf_mp[K][k] = m, n_obs[m] += 1
+ *   6  the same comparison, any other x (:516)                                                 replace(loser m, winner x)
+ *   7  n_obs[m] >= n_obs[x] (:520)                                                             replace(loser x, winner m)
+ * replace(l, w) = MapPoint::replaceWith (map_point.cpp:118-156): in every slot s that lists l at keypoint p, kf_mp[s][p] = -1 when w is a
+ * valid entry of s before this replace, else kf_mp[s][p] = w and n_obs[w] += 1.  Then mp_live[l] = 0, mp_flags[l] = 0, n_obs[l] = 0 (the
+ * state ms_map_cull leaves).  With track tables and t = mp_track[l] != -1: when mp_track[w] == -1, mp_track[w] = t and, for t inside the
+ * window, track_row[t - track_base] = w; otherwise nothing (l is no longer live, so 9.11's PRESENT rule reads its track as erased).
+ * mp_track[l] stays.
+ * Per entry (DEVICE [n_entries], each may be NULL): outcome; kp = the candidate keypoint for codes 4-7, else -1; other = x for codes 5-7,
+ * else -1.  Every entry of [0, n_entries) gets the defaults 0 / -1 / -1 first, also the entries of no slice and of views behind an early
+ * stop (n_views = 0 writes nothing on the device).  In walk order (DEVICE [n_entries], each may be NULL): erased_rows = the losers, erased_into = their winners.  HOST: n_erased,
+ * counts[8] (one per code, over the views walked), views_done.  Left to the caller, who derives them from erased_rows / erased_into and the
+ * per-entry outputs: keyPointToTrackId.erase (:142-144), the host MapPoint objects, fusedCount (the entries with codes 4-7).
+ * source_slot >= 0 (deduplicateMapPoints reads currentKeyframe.mapPoints live, mapper_helpers.cpp:331-334): when a replace in view v wrote
+ * a new valid row into slot source_slot, the walk finishes view v and stops with views_done = v + 1; the caller reads that slot back,
+ * rebuilds and gates the remaining views and calls again.  Inside one view the list cannot gain a row that matters: the loser of a code 6
+ * is the entry itself, a code 7 turns a later entry into a dead row (code 1).  source_slot = -1 walks every view (searchAndDeduplicate's
+ * std::set is a copy).
+ * Three launches whatever n_views and n_entries are (fill; scatter the candidates and run the pre-pass; ONE workgroup of 1024 lanes walks:
+ * the slice in trips of 1024 entries, the entries with a candidate compacted and stepped through in order, a replace as one pass of the
+ * workgroup's 16 waves over the slots).  Integer work; atomics only as adds (and one exchange to zero) on n_obs; the same input gives the
+ * same bits on every call.  Synchronous: one upload, one download; the workspace belongs to the context and only grows.
+ * MS_ERR_INVALID from the pre-pass, with the tables untouched (the per-entry outputs hold their defaults): a valid entry of a walked slot
+ * whose row is not live (mapDB.mapPoints.at would throw at :507), a kept_entry outside its view's slice, a top_idx[4q] outside
+ * [-1, stride).  The walk preserves "the valid entries of every slot are live".
+ * MS_ERR_INVALID, with nothing written and before any device call: a slot, row or slice out of range; overlapping slices; a row listed twice
+ * within a view; n_kept[v] outside [0, count]; max_dist outside [0, 256]; source_slot outside [-1, n_kf); one track table without the
+ * other; stride < 1; a negative size; a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps, MS_GATE_MAX_VIEWS,
+ * MS_GATE_MAX_ENTRIES (n_entries stays below it) and MS_TRACKED_MAX_WINDOW.  n_entries = 0, n_views = 0 and empty views are fine.
+ * Not checked: the reference's invariant that a slot lists a row at most once.  Under its violation the result is unspecified; every index
+ * is still compared against n_mp and stride before it is used.
+ *
+ * ms_map_replace_pairs: the "merge moved map points" loop of loop_closer.cpp:531-546 with the same replace.  pairs (HOST [n_pairs][2]) =
+ * (first, second) in order; outcome (HOST uint8 [n_pairs]): 0 replaced (loser first, winner second) | 1 equal (:534) | 2 skipped because
+ * first or second was the first row of a pair replaced earlier (:537-541; the rule depends on the list alone and is applied on the host).
+ * Chains (a -> b, then b -> c) run in order.  erased_rows / erased_into (DEVICE [n_pairs], each may be NULL): the replaced pairs in order;
+ * n_erased (HOST) their number.  Two launches and one clear (check that every listed row is live; ONE workgroup walks the pairs).
+ * MS_ERR_INVALID with the tables untouched for a listed row that is not live; before any device call for a row out of range and the table
+ * conditions above; MS_ERR_CAPACITY for n_pairs >= MS_GATE_MAX_ENTRIES.  n_pairs = 0 is fine.
+ * The *_check twins are the host validation alone (no context, no device; `why` receives the message). */
+typedef struct {
+    int32_t slot;                        /* the walked keyframe */
+    int32_t first, count;                /* its slice of mp_index: the ms_gate_view's */
+} ms_fuse_view;
+int ms_map_fuse(ms_ctx *ctx,
+    /* DEVICE tables, updated in place; mp_track / track_row both or neither */
+    int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, int32_t *n_obs, int n_mp,
+    int32_t *mp_track, int32_t *track_row, int track_base, int n_track,
+    /* DEVICE, read */
+    const int32_t *kept_entry, const int32_t *top_idx, const uint16_t *top_dist,
+    /* HOST */
+    const int32_t *mp_index, int n_entries, const ms_fuse_view *views, const int32_t *n_kept, int n_views, int max_dist, int source_slot,
+    /* DEVICE [n_entries], each may be NULL */
+    uint8_t *outcome, int32_t *kp, int32_t *other, int32_t *erased_rows, int32_t *erased_into,
+    /* HOST: one, [8], one */
+    int32_t *n_erased, int32_t *counts, int32_t *views_done);
+int ms_map_fuse_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const int32_t *n_obs, int n_mp,
+    const int32_t *mp_track, const int32_t *track_row, int track_base, int n_track,
+    const int32_t *kept_entry, const int32_t *top_idx, const uint16_t *top_dist,
+    const int32_t *mp_index, int n_entries, const ms_fuse_view *views, const int32_t *n_kept, int n_views, int max_dist, int source_slot,
+    const int32_t *n_erased, const int32_t *counts, const int32_t *views_done, char *why, size_t why_bytes);
+int ms_map_replace_pairs(ms_ctx *ctx,
+    /* DEVICE tables, updated in place */
+    int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, int32_t *n_obs, int n_mp,
+    int32_t *mp_track, int32_t *track_row, int track_base, int n_track,
+    /* HOST */
+    const int32_t *pairs, int n_pairs, uint8_t *outcome,
+    /* DEVICE [n_pairs], each may be NULL */
+    int32_t *erased_rows, int32_t *erased_into,
+    /* HOST */
+    int32_t *n_erased);
+int ms_map_replace_pairs_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const int32_t *n_obs, int n_mp,
+    const int32_t *mp_track, const int32_t *track_row, int track_base, int n_track,
+    const int32_t *pairs, int n_pairs, const uint8_t *outcome, const int32_t *n_erased, char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

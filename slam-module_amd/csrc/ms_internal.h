@@ -23,6 +23,7 @@ enum MsWorkspaceId {
     MS_WS_MAP_CULL,         // ms_observation_count and ms_map_cull (map_cull.hip): device KfId order / walk / first and last positions / marks / block counts
     MS_WS_OBS_LISTS,        // ms_observation_lists (obs_lists.hip): device KfId order / descriptor bases / lengths / marks / block counts / cursors / sort keys
     MS_WS_MATCH_TRACKED,    // ms_match_tracked and ms_match_tracked_finish (match_tracked.hip): device frame record / track ids / new rows / per-keypoint rows and positions
+    MS_WS_MAP_FUSE,         // ms_map_fuse and ms_map_replace_pairs (map_fuse.hip): device entry rows / views / pairs / candidates / "listed by K" marks / results
     MS_WS_COUNT
 };
 

@@ -496,6 +496,45 @@ inline GatedLists gate_and_score(Context &ctx, const DeviceMapPoints &table, con
     }
     return g;
 }
+
+// gate_and_score's sibling for ms_map_fuse (map_update.hpp): the same gate and the same scoring per view, but the lists stay where the kernels
+// left them -- nothing but nKept comes back.  keptEntry / topIdx / topDist are DEVICE pointers into Context::workspace, packed per view at
+// first[v]; `extra` = extraBytesPerEntry bytes per entry behind them for the caller's own device outputs.  The pointers hold until the next
+// request for workspace.
+struct DeviceGatedLists {
+    std::vector<std::int32_t> index, first, count, nKept;    // index: mp_index as ms_project_gate got it
+    const std::int32_t *keptEntry = nullptr, *topIdx = nullptr;
+    const std::uint16_t *topDist = nullptr;
+    unsigned char *extra = nullptr;
+};
+
+inline DeviceGatedLists gate_and_score_device(Context &ctx, const DeviceMapPoints &table, const std::vector<GateView> &views, const std::vector<const DeviceKeyframe *> &kfs,
+                                              const StaticSettings &settings, std::size_t extraBytesPerEntry) {
+    std::vector<ms_gate_view> V;
+    DeviceGatedLists g;
+    pack_views(views, V, g.index);
+    const std::size_t ne = g.index.size(), sec = pad16(4 * ne);
+    g.nKept.assign(views.size(), 0);
+    for (const ms_gate_view &v : V) { g.first.push_back(v.first); g.count.push_back(v.count); }
+    const std::size_t oX = 0, oY = oX + sec, oR = oY + sec, oLo = oR + sec, oHi = oLo + sec, oD = oHi + sec, oE = oD + 32 * ne;
+    const std::size_t oTi = oE + sec, oTo = oTi + 16 * ne, oN = oTo + 16 * ne, oTd = oN + sec, oX2 = oTd + pad16(8 * ne), total = oX2 + pad16(extraBytesPerEntry * ne);
+    unsigned char *ws = ctx.workspace(total + 16);
+    auto F = [&](std::size_t o) { return reinterpret_cast<float *>(ws + o); };
+    auto I = [&](std::size_t o) { return reinterpret_cast<std::int32_t *>(ws + o); };
+    g.keptEntry = I(oE); g.topIdx = I(oTi); g.topDist = reinterpret_cast<const std::uint16_t *>(ws + oTd); g.extra = ws + oX2;
+    ctx.check(ms_project_gate(ctx.get(), table.position(), table.norm(), table.minDistance(), table.maxDistance(), table.descriptor(), (int)table.size(),
+                              g.index.data(), (int)ne, V.data(), (int)V.size(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(),
+                              settings.parameters.orbScaleFactor, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, I(oE), F(oX), F(oY), F(oR), I(oLo), I(oHi),
+                              reinterpret_cast<std::uint32_t *>(ws + oD), g.nKept.data()), "ms_project_gate");
+    for (std::size_t v = 0; v < V.size() && ne; ++v) {
+        const std::size_t f = (std::size_t)V[v].first;
+        const ms_match_frame &fr = kfs[v]->frame();
+        ctx.check(ms_projection_topk(ctx.get(), kfs[v]->sortedX(), kfs[v]->sortedY(), kfs[v]->sortedIndex(), fr.n, fr.desc, fr.octave, nullptr,
+                                     F(oX) + f, F(oY) + f, F(oR) + f, I(oLo) + f, I(oHi) + f, reinterpret_cast<const std::uint32_t *>(ws + oD) + 8 * f, g.nKept[v],
+                                     I(oTi) + 4 * f, reinterpret_cast<std::uint16_t *>(ws + oTd) + 4 * f, I(oTo) + 4 * f, I(oN) + f, nullptr), "ms_projection_topk");
+    }
+    return g;
+}
 }  // namespace detail
 
 // Keyframe::isInFrustum (keyframe.cpp:247-262) for many map points at once: reprojection, viewing distance and viewing angle of the table rows

@@ -1,11 +1,13 @@
 // map_update.hpp -- the operations of the host mirror on the device-resident map (map_tables.hpp), with their argument and result structs:
 // loop correction (correctLoop), triangulation (triangulateMapPoints), covisibility (getNeighbors, computeAdjacentKeyframes, localMapPoints),
-// culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent) and matchTrackedFeatures.
+// culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
+// fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints).
 // Results come back through Context::workspace and Context::download; nothing here owns device memory.
 #pragma once
 #include <algorithm>
 #include <array>
 #include <stdexcept>
+#include "keyframe_matcher.hpp"
 #include "map_tables.hpp"
 #include "optimize_transform.hpp"
 
@@ -421,6 +423,139 @@ inline MatchTrackedResult matchTrackedFeatures(Context &ctx, DeviceObservationLi
     refresh(refreshRows, (std::size_t)nRefresh, true);
     if (!hasDescriptors) refresh(checkedRows, out.checked, false);
     out.success = (std::size_t)nRefresh + (hasDescriptors ? 0 : out.checked);
+    return out;
+}
+
+// ---- fusing duplicate map points on the device tables (ms_map_fuse, ms_map_replace_pairs) ----------------------------------------------
+// The tables the fuse steps update in place.  observationCount: DEVICE [mapPointCount], mp.observations.size() of every row as
+// ms_observation_count leaves it (observationCountsOnDevice); the walk keeps it current, so one count serves a whole new-keyframe chain.
+struct FuseTables {
+    DeviceKeyframeMapPoints &table;
+    DeviceMapPointFlags &flags;
+    DeviceMapPointLive &live;
+    std::int32_t *observationCount;
+    DeviceTrackTable *tracks = nullptr;
+};
+// One keyframe as replaceDuplication reads it: its slot, its matcher features, poseCW (p_c = R p + t, row-major) and camera.
+struct FuseKeyframe {
+    std::int32_t slot = 0;
+    const DeviceKeyframe *features = nullptr;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+    ms_pinhole camera{};
+};
+// The erased rows with their winners in the order of erasure -- what the caller's keyPointToTrackId.erase, its host MapPoint objects and
+// trackIdToMapPoint bookkeeping are derived from -- the entries per outcome code of ms_map_fuse, fusedCount (codes 4-7) and how often
+// direction 1 of deduplicateMapPoints gated again after an early stop.
+struct FuseResult {
+    std::vector<std::int32_t> erasedRows, erasedInto;
+    std::array<std::int32_t, 8> counts{};
+    unsigned fusedCount = 0, regates = 0;
+};
+
+// mp.observations.size() of every row into DEVICE memory (counts: [table.mapPointCount()]), for FuseTables::observationCount
+inline void observationCountsOnDevice(Context &ctx, const DeviceKeyframeMapPoints &table, const std::vector<std::int32_t> &kfIds, std::int32_t *counts) {
+    if (kfIds.size() != table.size()) throw std::invalid_argument("observationCountsOnDevice: one KfId per slot");
+    ctx.check(ms_observation_count(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), (int)table.mapPointCount(), kfIds.data(), counts, nullptr, nullptr),
+              "ms_observation_count");
+}
+
+namespace detail {
+inline void check_fuse_tables(const FuseTables &T, const char *who) {
+    const std::size_t nMp = T.table.mapPointCount();
+    if (T.flags.size() < nMp || T.live.size() < nMp || (T.tracks && T.tracks->mapPointCount() != nMp) || !T.observationCount)
+        throw std::invalid_argument(std::string(who) + ": the map-point tables differ in size or the observation counts are missing");
+}
+
+// replaceDuplication of `rows` against each of `keyframes`, in order, as ONE gate call, one scoring launch per keyframe and ONE ms_map_fuse
+// on the lists where they lie.  Returns views_done.
+inline std::size_t fuse_batch(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables &T, const FuseKeyframe *keyframes, std::size_t n, const std::vector<std::int32_t> &rows,
+                              float margin, std::int32_t sourceSlot, const StaticSettings &settings, FuseResult &out) {
+    std::vector<GateView> views(n);
+    std::vector<const DeviceKeyframe *> kfs(n);
+    for (std::size_t v = 0; v < n; ++v) {
+        std::copy(keyframes[v].R, keyframes[v].R + 9, views[v].R); std::copy(keyframes[v].t, keyframes[v].t + 3, views[v].t);
+        views[v].camera = keyframes[v].camera; views[v].threshold = margin; views[v].mode = MS_GATE_FUSE; views[v].indices = rows;
+        kfs[v] = keyframes[v].features;
+    }
+    const DeviceGatedLists g = gate_and_score_device(ctx, mapPoints, views, kfs, settings, 8);
+    std::vector<ms_fuse_view> fv(n);
+    for (std::size_t v = 0; v < n; ++v) fv[v] = ms_fuse_view{keyframes[v].slot, g.first[v], g.count[v]};
+    const std::size_t ne = g.index.size();
+    std::int32_t *erasedRows = reinterpret_cast<std::int32_t *>(g.extra), *erasedInto = erasedRows + ne;
+    std::int32_t nErased = 0, counts[8] = {0}, viewsDone = 0;
+    ctx.check(ms_map_fuse(ctx.get(), T.table.mutableTable(), (int)T.table.size(), (int)T.table.stride(), T.flags.mutableFlags(), T.live.mutableLive(), T.observationCount,
+                          (int)T.table.mapPointCount(), T.tracks ? T.tracks->mpTrack() : nullptr, T.tracks ? T.tracks->trackRow() : nullptr,
+                          T.tracks ? T.tracks->trackBase() : 0, T.tracks ? (int)T.tracks->window() : 0, g.keptEntry, g.topIdx, g.topDist, g.index.data(), (int)ne, fv.data(),
+                          g.nKept.data(), (int)n, (int)HAMMING_DIST_THR_LOW, sourceSlot, nullptr, nullptr, nullptr, erasedRows, erasedInto, &nErased, counts, &viewsDone),
+              "ms_map_fuse");
+    const std::vector<std::int32_t> rowsDown = ctx.download(erasedRows, (std::size_t)nErased), intoDown = ctx.download(erasedInto, (std::size_t)nErased);
+    out.erasedRows.insert(out.erasedRows.end(), rowsDown.begin(), rowsDown.end());
+    out.erasedInto.insert(out.erasedInto.end(), intoDown.begin(), intoDown.end());
+    for (int c = 0; c < 8; ++c) { out.counts[c] += counts[c]; if (c >= 4) out.fusedCount += (unsigned)counts[c]; }
+    return (std::size_t)viewsDone;
+}
+}  // namespace detail
+
+// deduplicateMapPoints (mapper_helpers.cpp:320-347) on the device tables; nothing of the map graph is on the host between its steps.
+//   direction 1 (:330-334)  the current keyframe's valid rows, in keypoint order, against ALL remaining adjacent keyframes in one gate + score
+//                           batch and one ms_map_fuse with source_slot = current.  The reference reads currentKeyframe.mapPoints live: when a
+//                           replace put a new row into that slot the walk stops behind the view, the slot is read back (one row of kf_mp)
+//                           and the rest is gated again.  A row an earlier view of a batch erased ends as outcome 1 in the later ones.
+//   the union (:337-345)    ms_map_point_union over the adjacent slots as the tables are then, rows ascending
+//   direction 2 (:346)      one view: the union against the current keyframe
+// margin = getFocalLength(currentKeyframe) * relativeReprojectionErrorThreshold (:328), computed by the caller.  The graph filters of
+// keyframe_matcher.cpp:429-440 run inside the walk, so every valid row is gated.
+inline FuseResult deduplicateMapPoints(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables T, const FuseKeyframe &current, const std::vector<FuseKeyframe> &adjacent,
+                                       float margin, const StaticSettings &settings) {
+    detail::check_fuse_tables(T, "deduplicateMapPoints");
+    const std::size_t nMp = T.table.mapPointCount(), stride = T.table.stride();
+    if (current.slot < 0 || (std::size_t)current.slot >= T.table.size()) throw std::invalid_argument("deduplicateMapPoints: current keyframe outside the table");
+    FuseResult out;
+    std::vector<std::int32_t> rows, adjacentSlots;
+    for (std::size_t done = 0; done < adjacent.size();) {
+        const std::vector<std::int32_t> slotRow = ctx.download(T.table.table() + (std::size_t)current.slot * stride, stride);
+        rows.clear();
+        for (std::int32_t r : slotRow) if (r >= 0 && (std::size_t)r < nMp) rows.push_back(r);
+        if (rows.empty()) break;
+        if (done) ++out.regates;
+        done += detail::fuse_batch(ctx, mapPoints, T, adjacent.data() + done, adjacent.size() - done, rows, margin, current.slot, settings, out);
+    }
+    for (const FuseKeyframe &k : adjacent) adjacentSlots.push_back(k.slot);
+    rows = localMapPoints(ctx, T.table, nullptr, adjacentSlots, -1, 0, false).row;
+    if (!rows.empty()) detail::fuse_batch(ctx, mapPoints, T, &current, 1, rows, margin, -1, settings, out);
+    return out;
+}
+
+// searchAndDeduplicate (loop_closer.cpp:567-591): loopMapPoints = the usable rows (neither BAD nor NOT_TRIANGULATED, :575-578) of the
+// candidate keyframe's neighbours (slots; the caller's getNeighbors), a std::set and therefore a copy: every rigidly transformed keyframe
+// is walked against the same list (source_slot = -1), margin 4.
+inline FuseResult searchAndDeduplicate(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables T, const std::vector<std::int32_t> &neighbourSlots,
+                                       const std::vector<FuseKeyframe> &rigidlyTransformed, const StaticSettings &settings) {
+    detail::check_fuse_tables(T, "searchAndDeduplicate");
+    FuseResult out;
+    const std::vector<std::int32_t> rows = localMapPoints(ctx, T.table, &T.flags, neighbourSlots, -1, DeviceMapPointFlags::USABLE, false).row;
+    if (!rows.empty() && !rigidlyTransformed.empty())
+        detail::fuse_batch(ctx, mapPoints, T, rigidlyTransformed.data(), rigidlyTransformed.size(), rows, 4.0f, -1, settings, out);
+    return out;
+}
+
+// "Merge moved map points", loop_closer.cpp:531-546: loopClosure.mapPointMatches as (first, second) table rows, in order.  outcome per pair:
+// 0 replaced (first by second) | 1 equal | 2 skipped by the `merged` rule.  counts stays zero; fusedCount = the replaced pairs.
+inline FuseResult mergeMatchedMapPoints(Context &ctx, FuseTables T, const std::vector<std::pair<std::int32_t, std::int32_t>> &matches, std::vector<std::uint8_t> *outcome = nullptr) {
+    detail::check_fuse_tables(T, "mergeMatchedMapPoints");
+    FuseResult out;
+    const std::size_t n = matches.size();
+    std::vector<std::int32_t> pairs(2 * n);
+    for (std::size_t i = 0; i < n; ++i) { pairs[2 * i] = matches[i].first; pairs[2 * i + 1] = matches[i].second; }
+    std::vector<std::uint8_t> oc(n, 0);
+    std::int32_t *erasedRows = reinterpret_cast<std::int32_t *>(ctx.workspace(8 * n + 64)), *erasedInto = erasedRows + n, nErased = 0;
+    ctx.check(ms_map_replace_pairs(ctx.get(), T.table.mutableTable(), (int)T.table.size(), (int)T.table.stride(), T.flags.mutableFlags(), T.live.mutableLive(),
+                                   T.observationCount, (int)T.table.mapPointCount(), T.tracks ? T.tracks->mpTrack() : nullptr, T.tracks ? T.tracks->trackRow() : nullptr,
+                                   T.tracks ? T.tracks->trackBase() : 0, T.tracks ? (int)T.tracks->window() : 0, pairs.data(), (int)n, oc.data(), erasedRows, erasedInto,
+                                   &nErased), "ms_map_replace_pairs");
+    out.erasedRows = ctx.download(erasedRows, (std::size_t)nErased); out.erasedInto = ctx.download(erasedInto, (std::size_t)nErased);
+    out.fusedCount = (unsigned)nErased;
+    if (outcome) *outcome = oc;
     return out;
 }
 

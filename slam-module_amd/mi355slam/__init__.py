@@ -1182,6 +1182,18 @@ class CullSettingsC(C.Structure):
                 ("max_critical_ratio", C.c_double), ("ratio_float32", C.c_int32)]
 
 
+class FuseViewC(C.Structure):
+    """ms_fuse_view (ms_map_fuse)."""
+    _fields_ = [("slot", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
+
+
+def _download_i32_at(buf, byte_offset, n):
+    """n int32 from byte_offset of a DevBuf."""
+    a = np.zeros(max(n, 1), np.int32)
+    buf.ctx.check(lib().ms_dev_download(buf.ctx._h, _vp(a), C.c_void_p(buf.ptr + byte_offset), C.c_size_t(4 * n)), "ms_dev_download")
+    return a[:n]
+
+
 def _download_i32(buf, shape):
     return buf.download(np.int32, shape) if shape[0] * shape[1] else np.zeros(shape, np.int32)
 
@@ -1339,6 +1351,166 @@ class KeyframeTable:
             for b in (d_n, d_rows, d_why, own_f, own_l):
                 if b is not None:
                     b.free()
+        return out
+
+    def _fuse_tables(self, tables, n_mp):
+        """Uploads mp_flags / mp_live / n_obs and, when given, mp_track / track_row of a dict of arrays; returns (bufs, n_track)."""
+        some = lambda a, dtype: self.ctx.upload(a if len(a) else np.zeros(1, dtype))
+        bufs = dict(mp_flags=some(np.ascontiguousarray(tables["mp_flags"], np.uint8).reshape(-1), np.uint8),
+                    mp_live=some(np.ascontiguousarray(tables["mp_live"], np.uint8).reshape(-1), np.uint8), n_obs=some(_i32(tables["n_obs"]), np.int32))
+        for name in ("mp_flags", "mp_live", "n_obs"):
+            if len(np.asarray(tables[name]).reshape(-1)) != n_mp:
+                raise ValueError("%s describes %d map points, n_mp is %d" % (name, len(np.asarray(tables[name]).reshape(-1)), n_mp))
+        n_track = 0
+        for name in ("mp_track", "track_row"):
+            bufs[name] = some(_i32(tables[name]), np.int32) if tables.get(name) is not None else None
+        if tables.get("track_row") is not None:
+            n_track = len(_i32(tables["track_row"]))
+        return bufs, n_track
+
+    def _fuse_download(self, bufs, tables, n_mp, n_track):
+        some = lambda b, dtype, n: b.download(dtype, (n,)) if n else np.zeros(0, dtype)
+        out = dict(kf_mp=self.download() if self.n_kf else np.zeros((0, self.stride), np.int32), mp_flags=some(bufs["mp_flags"], np.uint8, n_mp),
+                   mp_live=some(bufs["mp_live"], np.uint8, n_mp), n_obs=some(bufs["n_obs"], np.int32, n_mp))
+        if bufs["mp_track"] is not None:
+            out["mp_track"] = some(bufs["mp_track"], np.int32, n_mp)
+        if bufs["track_row"] is not None:
+            out["track_row"] = some(bufs["track_row"], np.int32, n_track)
+        return out
+
+    def fuse(self, tables, mp_index, views, n_kept, kept_entry, top_idx, top_dist, max_dist=50, source_slot=-1,
+             want=("outcome", "kp", "other", "erased_rows", "erased_into")):
+        """The walk of replaceDuplication on this table in place (ms_map_fuse); for the tests: every array is uploaded for the call.  tables: a
+        dict of mp_flags, mp_live, n_obs and optionally mp_track, track_row, track_base; views: (slot, first, count).  Returns a dict of the
+        tables after the walk, the outputs named in `want`, counts [8] and views_done."""
+        n_mp = len(np.asarray(tables["mp_live"]).reshape(-1))
+        mp_index, n_kept, kept_entry, top_idx = _i32(mp_index), _i32(n_kept), _i32(kept_entry), _i32(top_idx)
+        top_dist = np.ascontiguousarray(top_dist, np.uint16).reshape(-1)
+        n, n_views = len(mp_index), len(views)
+        if len(n_kept) != n_views or len(kept_entry) != n or len(top_idx) != 4 * n or len(top_dist) != 4 * n:
+            raise ValueError("fuse: the lists do not describe %d entries in %d views" % (n, n_views))
+        bufs, n_track = self._fuse_tables(tables, n_mp)
+        ins = [self.ctx.upload(a if len(a) else np.zeros(1, a.dtype)) for a in (kept_entry, top_idx, top_dist)]
+        outs = {name: self.ctx.alloc((1 if name == "outcome" else 4) * max(n, 1)) if name in want else None
+                for name in ("outcome", "kp", "other", "erased_rows", "erased_into")}
+        n_erased, views_done, counts = 0, 0, np.zeros(8, np.int32)
+        try:
+            n_erased, counts, views_done = self.fuse_device(bufs, n_mp, int(tables.get("track_base", 0)), n_track, mp_index, views, n_kept, ins[0], ins[1], ins[2],
+                                                            max_dist, source_slot, outs)
+        finally:
+            self._fuse_last = self._fuse_download(bufs, tables, n_mp, n_track)   # the tables as the call left them, also when it was turned away
+            for name, b in outs.items():
+                if b is not None:
+                    k = n_erased if name.startswith("erased") else n
+                    self._fuse_last[name] = (b.download(np.uint8 if name == "outcome" else np.int32, (k,)) if k
+                                             else np.zeros(0, np.uint8 if name == "outcome" else np.int32))
+            for b in list(bufs.values()) + ins + list(outs.values()):
+                if b is not None:
+                    b.free()
+        out = self._fuse_last
+        out.update(counts=counts, views_done=views_done, n_erased=n_erased)
+        return out
+
+    def fuse_device(self, bufs, n_mp, track_base, n_track, mp_index, views, n_kept, d_kept_entry, d_top_idx, d_top_dist, max_dist, source_slot, outs):
+        """ms_map_fuse with the tables, the lists and the outputs left on the device.  bufs: DevBufs mp_flags, mp_live, n_obs, mp_track /
+        track_row (or None); outs: DevBufs or None for outcome, kp, other, erased_rows, erased_into.  Returns (n_erased, counts [8], views_done)."""
+        mp_index, n_kept = _i32(mp_index), _i32(n_kept)
+        V = (FuseViewC * max(len(views), 1))(*[FuseViewC(*[int(x) for x in v]) for v in views])
+        n_erased, views_done, counts = C.c_int32(0), C.c_int32(0), np.zeros(8, np.int32)
+        self.ctx.check(lib().ms_map_fuse(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(bufs["mp_flags"]), _vp(bufs["mp_live"]), _vp(bufs["n_obs"]), int(n_mp),
+                                         _vp(bufs.get("mp_track")), _vp(bufs.get("track_row")), int(track_base), int(n_track), _vp(d_kept_entry), _vp(d_top_idx),
+                                         _vp(d_top_dist), _vp(mp_index), len(mp_index), V, _vp(n_kept), len(views), int(max_dist), int(source_slot),
+                                         *[_vp(outs.get(k)) for k in ("outcome", "kp", "other", "erased_rows", "erased_into")], C.byref(n_erased), _vp(counts),
+                                         C.byref(views_done)), "ms_map_fuse")
+        return n_erased.value, counts, views_done.value
+
+    def download_slot(self, slot):
+        return _download_i32_at(self.kf_mp, 4 * self.stride * slot, self.stride)
+
+    def deduplicate(self, table, kfs, views_of, tables, current, adjacent, margin, scale_factors_, scale_factor, max_dist=50, device_tables=None):
+        """deduplicateMapPoints (mapper_helpers.cpp:320-347) as a device-resident chain; for the tests.  table: a MapPointTable; kfs[slot]: a
+        ProjectionKeyframe; views_of[slot]: dict(R, t, cam) of the slot's pose and camera; tables: as for fuse (arrays, uploaded once).
+        Direction 1: the current slot's valid rows, in keypoint order, gated and scored against all remaining adjacent keyframes in one
+        batch and walked with source_slot = current; whenever the walk stops early the slot is read back and the rest is gated again.  Then
+        the union of the adjacent slots' rows (ms_map_point_union, ascending) against the current keyframe.  Returns the tables after it,
+        erased (rows, winners) in order, counts [8], and regates = how often direction 1 gated again.  device_tables = (bufs, n_track) of an
+        earlier _fuse_tables call: the tables are then neither uploaded nor downloaded nor freed here (tools/map_fuse_probe.py)."""
+        n_mp = len(np.asarray(tables["mp_live"]).reshape(-1))
+        bufs, n_track = device_tables if device_tables is not None else self._fuse_tables(tables, n_mp)
+        erased_rows, erased_into, counts, regates = [], [], np.zeros(8, np.int64), -1
+        gate = lambda slot, rows: dict(views_of[slot], threshold=float(margin), mode=GATE_FUSE, indices=rows)
+
+        def batch(slots, rows, source_slot):
+            views = [gate(k, rows) for k in slots]
+            ne = len(rows) * len(views)
+            dev, n_kept, V = project_gate_device(self.ctx, table, views, scale_factors_, scale_factor, per_entry=False)
+            ti, td, to, ns = self.ctx.alloc(16 * ne + 16), self.ctx.alloc(8 * ne + 16), self.ctx.alloc(16 * ne + 16), self.ctx.alloc(4 * ne + 16)
+            at = lambda b, size, f: C.c_void_p(b.ptr + size * f)
+            for v, k in enumerate(slots):
+                f, kf = V[v].first, kfs[k]
+                self.ctx.check(lib().ms_projection_topk(self.ctx._h, _vp(kf.d_sx), _vp(kf.d_sy), _vp(kf.d_si), kf.n, _vp(kf.d_desc), _vp(kf.d_oct), None,
+                                                        at(dev["q_x"], 4, f), at(dev["q_y"], 4, f), at(dev["q_radius"], 4, f), at(dev["q_min_octave"], 4, f),
+                                                        at(dev["q_max_octave"], 4, f), at(dev["q_desc"], 32, f), int(n_kept[v]), at(ti, 16, f), at(td, 8, f),
+                                                        at(to, 16, f), at(ns, 4, f), None), "ms_projection_topk")
+            er, ei = self.ctx.alloc(4 * ne + 16), self.ctx.alloc(4 * ne + 16)
+            try:
+                n, c, done = self.fuse_device(bufs, n_mp, int(tables.get("track_base", 0)), n_track, np.tile(_i32(rows), len(views)),
+                                              [(k, V[v].first, V[v].count) for v, k in enumerate(slots)], n_kept, dev["kept_entry"], ti, td, max_dist, source_slot,
+                                              dict(erased_rows=er, erased_into=ei))
+                if n:
+                    erased_rows.extend(er.download(np.int32, (n,)).tolist()); erased_into.extend(ei.download(np.int32, (n,)).tolist())
+            finally:
+                for b in list(dev.values()) + [ti, td, to, ns, er, ei]:
+                    b.free()
+            counts[:] += c
+            return done
+
+        try:
+            remaining = [int(k) for k in adjacent]
+            while remaining:                                 # direction 1, :330-334
+                row = self.download_slot(current)
+                rows = row[(row >= 0) & (row < n_mp)]
+                regates += 1
+                if not len(rows):
+                    break
+                remaining = remaining[batch(remaining, rows, current):]
+            d_rows = self.ctx.alloc(4 * max(n_mp, 1))
+            n_rows = self.map_point_union_device(adjacent, [(0, len(adjacent), -1, 0)], n_mp, None, d_rows, None)
+            rows = d_rows.download(np.int32, (n_mp,))[:n_rows[0]] if n_mp else np.zeros(0, np.int32)
+            d_rows.free()
+            if len(rows):
+                batch([int(current)], rows, -1)             # direction 2, :346
+            out = self._fuse_download(bufs, tables, n_mp, n_track) if device_tables is None else {}
+        finally:
+            for b in bufs.values():
+                if b is not None and device_tables is None:
+                    b.free()
+        out.update(erased_rows=np.array(erased_rows, np.int32), erased_into=np.array(erased_into, np.int32), counts=counts.astype(np.int32), regates=max(regates, 0))
+        return out
+
+    def replace_pairs(self, tables, pairs, want=("erased_rows", "erased_into")):
+        """The "merge moved map points" loop of loop_closer.cpp:531-546 on this table in place (ms_map_replace_pairs); for the tests.  pairs
+        [n, 2] = (first, second).  Returns the tables after it, outcome [n] (0 replaced, 1 equal, 2 skipped) and the erased rows / winners."""
+        n_mp = len(np.asarray(tables["mp_live"]).reshape(-1))
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = len(pairs)
+        bufs, n_track = self._fuse_tables(tables, n_mp)
+        outs = {name: self.ctx.alloc(4 * max(n, 1)) if name in want else None for name in ("erased_rows", "erased_into")}
+        outcome, n_erased = np.zeros(max(n, 1), np.uint8), C.c_int32(0)
+        try:
+            self.ctx.check(lib().ms_map_replace_pairs(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(bufs["mp_flags"]), _vp(bufs["mp_live"]), _vp(bufs["n_obs"]),
+                                                      n_mp, _vp(bufs["mp_track"]), _vp(bufs["track_row"]), int(tables.get("track_base", 0)), n_track, _vp(pairs), n,
+                                                      _vp(outcome), _vp(outs["erased_rows"]), _vp(outs["erased_into"]), C.byref(n_erased)), "ms_map_replace_pairs")
+        finally:
+            self._fuse_last = self._fuse_download(bufs, tables, n_mp, n_track)
+            for name, b in outs.items():
+                if b is not None:
+                    self._fuse_last[name] = b.download(np.int32, (n_erased.value,)) if n_erased.value else np.zeros(0, np.int32)
+            for b in list(bufs.values()) + list(outs.values()):
+                if b is not None:
+                    b.free()
+        out = self._fuse_last
+        out.update(outcome=outcome[:n], n_erased=n_erased.value)
         return out
 
     def observation_lists_device(self, lists, kf_id, n_mp, select, kp=None, desc_base=None, flags=None, n_levels=0, cap_rows=None, cap_obs=None):
