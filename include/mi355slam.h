@@ -187,6 +187,14 @@ int ms_keypoints_unpack(const uint8_t *records, int n, float *x, float *y, float
  * 1 .. 8 = every workgroup uses r, no taper.  MS_ERR_INVALID for anything else.  Holds for the calls that follow. */
 int ms_orb_set_describe_strip(ms_orb *orb, int r);
 
+/* Which resize kernel builds the pyramid, and which workgroup takes which tile (a test hook; outputs are bit for bit the same for every value).
+ * px: 0 = automatic (8 destination pixels per lane on every level whose tables allow it, for launches that fill the device; a frame or a
+ * few run the 4-pixel kernel), 4 = the 4-pixel kernel everywhere, 8 = the 8-pixel kernel on every eligible level whatever the launch's size
+ * (levels that are not eligible run the 4-pixel kernel).  map, for the 8-pixel kernel: 0 = automatic (by frame for batches of
+ * 32 frames and more), 1 = tiles dealt across the whole device, 2 = by frame (all tiles of a frame on one XCD).
+ * MS_ERR_INVALID for anything else.  Holds for the calls that follow. */
+int ms_orb_set_resize_plan(ms_orb *orb, int px, int map);
+
 /* Which workgroup of the describe kernel describes which keypoint, and when (a test hook; outputs are bit for bit the same for every value).
  * Bit 0: the workgroups dealt to one XCD take a contiguous run of the launch plan's blocks (whole frames through one L2).
  * Bit 1: a level's detections are visited in a spatial order (row bands, x inside a band) instead of score order; each still lands in its slot.

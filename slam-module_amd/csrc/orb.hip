@@ -25,6 +25,7 @@
 #include "describe_steer.h"
 #include "describe_brief_index.h"
 #include "resize_vpass.h"
+#include "resize_plan.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -108,7 +109,9 @@ __global__ __launch_bounds__(256) void k_copy_level0(const uint8_t *src, uint64_
 // row addresses, resize_row; three instructions per pixel in the vertical pass, resize_vpass.h) while the scalar count rose from 81.8 M to 101.9 M
 // bought 3.6 % (0.2935 -> 0.2830 ms for the seven launches).  The time followed the SUM of vector and scalar instructions (-3.4 %), not the vector
 // count: neither "HBM-bound by design" nor "bound by vector issue" describes it.  The step's 1.0 .. 1.5 GB (counter as read .. corrected) pass at
-// 3.6 .. 5.4 TB/s.
+// 3.6 .. 5.4 TB/s.  Since then: the levels whose tables allow it (every level of a 1.1 or 1.2 pyramid) run k_resize8 below, and this kernel keeps the
+// rest (other ratios, WIDE) and px = 4 of ms_orb_set_resize_plan.  Halving the waves there moved the time by under 5 % while the L2s' misses fell from
+// 1.39 x to 1.0 x the source bytes: this kernel's short row segments (2.4 lines of 128 bytes, 3.4 touched, the neighbours on other XCDs) are part of its cost.
 // unaligned dword / qword accesses (global memory takes them)
 struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
 struct __attribute__((packed, aligned(1))) U64u { uint32_t lo, hi; };
@@ -322,6 +325,97 @@ __global__ __launch_bounds__(256) void k_resize(ResizeArgs R, ResizeTab T) {
             if (dy0 + r < D.h) *reinterpret_cast<uint32_t *>(dst + (uint64_t)(dy0 + r) * D.pitch + dx0) = packed;
         }
     }
+}
+
+// k_resize8: the shared-row form of k_resize<false> with 8 destination pixels per lane (resize_plan.h), for the levels whose tables pass the
+// plan's eligibility test (every chunk inside its 16-byte window, every row group on 6 or 7 consecutive source rows).  Per source row a lane
+// loads 16 bytes (global_load_dwordx4) and stores 8 per destination row; the horizontal pass is one v_perm + v_dot2 + mask per pixel from
+// three byte funnels per row, the vertical pass, the rounding and the packing are resize_vpass.h's: the pixels are k_resize's bit for bit.
+// A wave's row segment is twice as long (about 614 source bytes at ratio 1.2), so fewer of the 128-byte lines it touches are shared with the
+// neighbouring tile, and from resize_plan::kByFrameMinFrames frames on a frame's tiles all run on one XCD, whose L2 then serves those shared
+// lines (the tile borders, the source row two row groups share) instead of every L2 fetching its own copy.  Halving the waves (and with
+// them the scalar and vector-memory instructions) is NOT what the time follows: see DESIGN section 10.
+struct Resize8Tab {
+    const uint32_t *xtab;  // [chunks][8] : resize_plan::entry
+    const int16_t *ytab;   // as ResizeTab's
+};
+typedef u32x4_t u4a_t __attribute__((aligned(4)));       // a 16-byte load from a dword-aligned address
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+
+template <int NROWS>
+__device__ __forceinline__ void resize8_shared_rows(const uint8_t *S, int spitch, int s0, int sh, uint32_t sx0, uint32_t from, int shift, bool edge,
+                                                    const uint32_t (&A)[resize_plan::kPx], const uint32_t (&sel)[resize_plan::kPx],
+                                                    const short4 (&yt)[kResizeRows], uint8_t *dst, int dy0, uint32_t doff, int dh, int dpitch) {
+    resize_plan::Window W[NROWS];
+#pragma unroll
+    for (int i = 0; i < NROWS; ++i) {
+        const u32x4_t a = *(const __attribute__((address_space(1))) u4a_t *)(resize_row(S, min(s0 + i, sh - 1), spitch) + from);
+        W[i] = {a.x, a.y, a.z, a.w};
+    }
+    if (edge) {                                        // a branch of its own (the empty statement cannot be hoisted): as selects the shift costs every wave six instructions per row
+#pragma unroll
+        for (int i = 0; i < NROWS; ++i) {
+            uint32_t d0 = W[i].d0, d1 = W[i].d1, d2 = W[i].d2, d3 = W[i].d3;
+            asm volatile("" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
+            W[i] = resize_plan::shift_down(d0, d1, d2, d3, shift);
+        }
+    }
+    uint32_t F[NROWS][resize_plan::kPx];
+#pragma unroll
+    for (int i = 0; i < NROWS; ++i) {
+        const resize_plan::Funnels fn = resize_plan::funnels(W[i], sx0);
+#pragma unroll
+        for (int c = 0; c < resize_plan::kPx; ++c) {
+            F[i][c] = resize_vpass::f8(__builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, resize_plan::tap_pair(fn, c, sel[c])), __builtin_bit_cast(us2_t, A[c]), 0u, false));
+            asm volatile("" : "+v"(F[i][c]));          // the mask happens here, once (as in resize_shared_rows)
+        }
+    }
+    // two bodies behind a scalar branch, kept apart as in resize_shared_rows
+    auto emit = [&](int r, bool upper, const uint32_t (&f0)[resize_plan::kPx], const uint32_t (&f1)[resize_plan::kPx]) {
+        const uint32_t b0 = resize_vpass::row_tap((uint32_t)yt[r].z), b1 = resize_vpass::row_tap((uint32_t)yt[r].w);      // scalar
+        uint32_t v[resize_plan::kPx];
+#pragma unroll
+        for (int c = 0; c < resize_plan::kPx; ++c) {
+            v[c] = resize_vpass::vsum(b0, f0[c], b1, f1[c]);
+            asm("" : "+v"(v[c]));                      // one v_add3_u32
+        }
+        u32x2_t packed = {resize_vpass::pack4(v[0], v[1], v[2], v[3]), resize_vpass::pack4(v[4], v[5], v[6], v[7])};
+        if (upper) asm volatile("; rows d + 1, d + 2" : "+v"(packed)); else asm volatile("; rows d, d + 1" : "+v"(packed));
+        *(__attribute__((address_space(1))) u32x2_t *)(resize_row(dst, dy0 + r, dpitch) + doff) = packed;       // 8-byte aligned: rows start 64-byte aligned
+    };
+#pragma unroll
+    for (int r = 0; r < kResizeRows; ++r) {
+        if (dy0 + r >= dh) continue;                                 // rows of the padded last group (wave-uniform, like every branch here)
+        if (r + 2 >= NROWS || yt[r].x - s0 == r) emit(r, false, F[r], F[r + 1]);      // NROWS = 6: the caller has seen d_4 = 4
+        else emit(r, true, F[r + 1], F[min(r + 2, NROWS - 1)]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_resize8(ResizeArgs R, Resize8Tab T, resize_plan::Launch P) {
+    const resize_plan::Tile tl = resize_plan::decode(P, blockIdx.x, blockIdx.y, blockIdx.z);                 // wave-uniform (SGPRs)
+    const int dy0 = (tl.ty * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * kResizeRows;             // wave-uniform: row addresses stay scalar
+    const int chunk = tl.tx * 64 + (int)(threadIdx.x & 63);
+    if (tl.frame >= P.nf || dy0 >= R.dh || chunk >= P.nchunks) return;       // from here on a ballot counts working lanes only
+    const uint8_t *S = R.src + (uint64_t)tl.frame * R.src_frame_stride;
+    uint8_t *dst = R.dst + (uint64_t)tl.frame * R.dst_frame_stride;
+    const uint32_t doff = (uint32_t)chunk * resize_plan::kPx;              // 8 chunk + 7 < pitch
+    const uint4 xa = reinterpret_cast<const uint4 *>(T.xtab)[2 * chunk], xb = reinterpret_cast<const uint4 *>(T.xtab)[2 * chunk + 1];
+    const uint32_t e[resize_plan::kPx] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+    uint32_t A[resize_plan::kPx], sel[resize_plan::kPx];
+#pragma unroll
+    for (int c = 0; c < resize_plan::kPx; ++c) { A[c] = resize_plan::entry_taps(e[c]); sel[c] = resize_plan::entry_sel(e[c]); }
+    const uint32_t sx0 = resize_plan::chunk_sx0(e[0], e[1], e[2], e[3]);
+    short4 yt[kResizeRows];
+#pragma unroll
+    for (int r = 0; r < kResizeRows; ++r) yt[r] = reinterpret_cast<const short4 *>(T.ytab)[dy0 + r];
+    const int last = (R.sw - 1) & ~3, base = (int)(sx0 & ~3u);
+    const bool edge = __ballot(resize_plan::lane_is_edge(base, last)) != 0;        // wave-uniform
+    const resize_plan::Fetch ft = resize_plan::fetch(base, last, edge);             // 0 <= from <= last - 12 on an edge wave, from = base <= last - 12 otherwise
+    uint32_t from = (uint32_t)ft.from;               // < pitch: an unsigned 32-bit lane offset beside each row's scalar base
+    asm volatile("" : "+v"(from));
+    const int s0 = yt[0].x, sh = R.sh;
+    if (dy0 + 4 < R.dh && yt[4].x - s0 == 5) resize8_shared_rows<7>(S, R.src_pitch, s0, sh, sx0, from, ft.shift, edge, A, sel, yt, dst, dy0, doff, R.dh, R.dst_pitch);
+    else resize8_shared_rows<6>(S, R.src_pitch, s0, sh, sx0, from, ft.shift, edge, A, sel, yt, dst, dy0, doff, R.dh, R.dst_pitch);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1426,6 +1520,8 @@ struct ms_orb {
     // resize tables per level (device)
     int16_t *d_xtab[MS_MAX_LEVELS] = {nullptr}, *d_ytab[MS_MAX_LEVELS] = {nullptr};
     bool wide[MS_MAX_LEVELS] = {false};
+    uint32_t *d_xtab8[MS_MAX_LEVELS] = {nullptr};    // k_resize8's column table, on the levels it may take (resize_plan.h); nullptr elsewhere
+    int resize_px = 0, resize_map = 0;                // ms_orb_set_resize_plan: 0 = automatic
     uint4 *d_moment_tab = nullptr;            // k_describe: disc mask of the orientation patch, four dwords per lane
     float4 *d_pattern_f = nullptr;            // k_describe: the 256 BRIEF point pairs as floats
     int describe_order = describe_order::kDefaultMode;   // bit 0: XCD-contiguous blocks (describe_strips::remap), bit 1: spatial visit order (k_slots) (ms_orb_set_describe_order)
@@ -1608,6 +1704,11 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
                 hipMemcpy(*d, v.data(), v.size() * 2, hipMemcpyHostToDevice) != hipSuccess) rc = MS_ERR_HIP;
         };
         up(&o->d_xtab[l], xt); up(&o->d_ytab[l], yt);
+        std::vector<uint32_t> x8;                        // the 8-pixel kernel takes the level iff its real tables pass both tests
+        if (rc == MS_OK && !o->wide[l] && resize_plan::rows_shared(yt.data(), h[l], h[l - 1]) && resize_plan::build_columns(xo.data(), xc.data(), w[l - 1], w[l], x8)) {
+            if (hipMalloc(reinterpret_cast<void **>(&o->d_xtab8[l]), x8.size() * 4) != hipSuccess ||
+                hipMemcpy(o->d_xtab8[l], x8.data(), x8.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = MS_ERR_HIP;
+        }
     }
     if (rc == MS_OK && (hipMalloc(reinterpret_cast<void **>(&o->d_ftile_tab), ftab.size() * sizeof(uint2) + 16) != hipSuccess ||
                         hipMemcpy(o->d_ftile_tab, ftab.data(), ftab.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)) rc = MS_ERR_HIP;
@@ -1667,6 +1768,7 @@ void ms_orb_destroy(ms_orb *o) {
     for (int l = 0; l < MS_MAX_LEVELS; ++l) {
         if (o->d_xtab[l]) (void)hipFree(o->d_xtab[l]);
         if (o->d_ytab[l]) (void)hipFree(o->d_ytab[l]);
+        if (o->d_xtab8[l]) (void)hipFree(o->d_xtab8[l]);
     }
     delete o;
 }
@@ -1676,6 +1778,12 @@ int ms_orb_capacity(const ms_orb *o) { return o ? o->geom.capacity : MS_ERR_INVA
 int ms_orb_set_describe_strip(ms_orb *o, int r) {
     if (!o || r < 0 || r > describe_strips::kMaxStrip) return MS_ERR_INVALID;
     o->describe_strip = r;
+    return MS_OK;
+}
+
+int ms_orb_set_resize_plan(ms_orb *o, int px, int map) {
+    if (!o || (px != 0 && px != 4 && px != 8) || map < resize_plan::kMapAuto || map > resize_plan::kMapByFrame) return MS_ERR_INVALID;
+    o->resize_px = px; o->resize_map = map;
     return MS_OK;
 }
 
@@ -1769,7 +1877,11 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
         else { RA.src = src.slab + G.L[l - 1].img_off; RA.src_frame_stride = G.slab_stride; RA.src_pitch = G.L[l - 1].pitch; }
         RA.sw = G.L[l - 1].w; RA.sh = G.L[l - 1].h;
         RA.dst = src.slab + G.L[l].img_off; RA.dst_frame_stride = G.slab_stride; RA.dst_pitch = G.L[l].pitch; RA.dw = G.L[l].w; RA.dh = G.L[l].h;
-        if (o->wide[l]) hipLaunchKernelGGL(k_resize<true>, grid, dim3(256), 0, st, RA, RT);
+        // the 8-pixel kernel on the levels whose tables allow it, for launches that fill the device (a frame or a few: the 4-pixel kernel, resize_plan.h)
+        const resize_plan::Launch P = resize_plan::launch(RA.dw, RA.dh, nf, o->resize_map);
+        if (o->d_xtab8[l] && (o->resize_px == 8 || (o->resize_px == 0 && resize_plan::fills_device(P))))
+            hipLaunchKernelGGL(k_resize8, dim3(P.grid_x, P.grid_y, P.grid_z), dim3(256), 0, st, RA, Resize8Tab{o->d_xtab8[l], o->d_ytab[l]}, P);
+        else if (o->wide[l]) hipLaunchKernelGGL(k_resize<true>, grid, dim3(256), 0, st, RA, RT);
         else hipLaunchKernelGGL(k_resize<false>, grid, dim3(256), 0, st, RA, RT);
         MS_KERNEL_CHECK(c, "k_resize");
     }

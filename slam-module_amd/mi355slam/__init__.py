@@ -329,6 +329,12 @@ class OrbExtractor:
         A test hook: the outputs are the same for every value."""
         self.ctx.check(lib().ms_orb_set_describe_strip(self._h, int(r)), "ms_orb_set_describe_strip")
 
+    def set_resize_plan(self, px=0, map=0):
+        """The resize kernel of the pyramid: px 0 = automatic (eight pixels per lane on eligible levels when the launch fills the device), 4 = four everywhere, 8 = eight on every eligible level; map = which
+        workgroup of the 8-pixel kernel takes which tile, 0 = automatic, 1 = tiles across the device, 2 = a frame's tiles on one XCD.
+        A test hook: the outputs are the same for every value."""
+        self.ctx.check(lib().ms_orb_set_resize_plan(self._h, int(px), int(map)), "ms_orb_set_resize_plan")
+
     def set_describe_order(self, mode):
         """Which workgroup of the describe kernel takes which keypoint: bit 0 = XCD-contiguous blocks, bit 1 = spatial visit order (default 1).
         A test hook: the outputs are the same for every value."""

@@ -1,5 +1,5 @@
 """Extended differential fuzz of the front end against the CPU oracle: N random configurations (sizes biased towards tile edges),
-bit-exact keypoints, angles, descriptors and pyramid pixels.  usage: python tools/frontend_fuzz.py [N] [seed]"""
+bit-exact keypoints, angles, descriptors and pyramid pixels.  usage: python tools/frontend_fuzz.py [N] [seed] [px [map]]"""
 import os, sys
 R = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in ("slam-module_amd", "oracle"): sys.path.insert(0, os.path.join(R, p))
@@ -21,6 +21,7 @@ while done < N:
     img = np.ascontiguousarray(img)
     ocfg = mso.cfg(levels=levels, scale_factor=sf, max_kpts=kp, fast_threshold=thr)
     ex = mi355slam.OrbExtractor(ctx, w, h, levels=levels, scale_factor=sf, max_kpts=kp, fast_threshold=thr, max_batch=1)
+    if len(sys.argv) > 3: ex.set_resize_plan(int(sys.argv[3]), int(sys.argv[4]) if len(sys.argv) > 4 else 0)      # [px [map]]: force the resize kernel / its grid mapping
     ex.extract(img[None])
     got = ex.download(0); want = mso.orb_extract(ocfg, img)
     ok = len(got["x"]) == len(want["x"]) and all(np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)) for k in ("x", "y", "angle")) \

@@ -2,7 +2,7 @@
 raised threshold prunes only when a frame's tiles run at different times, i.e. with many frames per call.  N random configurations,
 64 .. 160 frames per call (a few different frames, each at many places of the batch, so the oracle runs once per different frame), small quotas as well as
 large ones, with and without a minimum distance; every frame's keypoints, angles and descriptors bit for bit, and the detector's candidate counts never above
-the unpruned ones of a one-frame call.  usage: python tools/frontend_fuzz_batch.py [N] [seed]"""
+the unpruned ones of a one-frame call.  usage: python tools/frontend_fuzz_batch.py [N] [seed] [px [map]]"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("slam-module_amd", "oracle"): sys.path.insert(0, os.path.join(R, p))
@@ -30,6 +30,7 @@ while done < N:
     ocfg = mso.cfg(levels=levels, scale_factor=sf, max_kpts=kp, fast_threshold=thr, min_distance=md)
     want = [mso.orb_extract(ocfg, img) for img in imgs]
     ex = mi355slam.OrbExtractor(ctx, w, h, levels=levels, scale_factor=sf, max_kpts=kp, fast_threshold=thr, max_batch=n_frames + int(rng.integers(0, 3)), min_distance=md)
+    if len(sys.argv) > 3: ex.set_resize_plan(int(sys.argv[3]), int(sys.argv[4]) if len(sys.argv) > 4 else 0)      # [px [map]]: force the resize kernel / its grid mapping
     full = []
     for img in imgs:                                 # a one-frame call prunes nothing: its counts are the unpruned ones
         ex.extract(img[None]); full.append(ex.last_candidate_counts()[0])

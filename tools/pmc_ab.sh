@@ -14,7 +14,7 @@ for f in glob.glob(os.path.join(sys.argv[1], "**", "*counter_collection.csv"), r
     for r in csv.DictReader(open(f)):
         m = re.search(r"k_[a-z0-9_]+", r["Kernel_Name"])
         if m: acc[m.group(0)][r["Counter_Name"]] += float(r["Counter_Value"]) / 3
-for k in ("k_fast", "k_describe"):
+for k in os.environ.get("PMC_KERNELS", "k_fast k_describe").split():      # e.g. PMC_KERNELS="k_resize k_resize8": summed over a step's launches
     print(sys.argv[2], k, {c: round(v) for c, v in sorted(acc[k].items())})
 PY
 done
