@@ -1073,6 +1073,101 @@ int ms_map_replace_pairs_check(const int32_t *kf_mp, int n_kf, int stride, const
     const int32_t *mp_track, const int32_t *track_row, int track_base, int n_track,
     const int32_t *pairs, int n_pairs, const uint8_t *outcome, const int32_t *n_erased, char *why, size_t why_bytes);
 
+/* ---- createNewMapPoints on the device map tables -------------------------------------------------------------------------
+ * The loop body of mapper_helpers.cpp:271-318 for one adjacent keyframe, between ms_match_triangulation and the next adjacent.  The tables
+ * are those of 9.6 / 9.8 / 9.9 / 9.11.  cur = the slot of the current keyframe (kf1 of the matcher), adj = the adjacent one's.
+ *
+ * ms_create_points_lists: matched (DEVICE int32 [n_kp1], what ms_match_triangulation wrote for the pair: -1 none, else a keypoint of adj)
+ * is walked in ascending keypoint index of cur (the order of :282-290).  The i-th match (j, m = matched[j]) takes the provisional row
+ * new_rows[i] (HOST [n_new]) and becomes entry i of `lists` (:293-301): rows[i] = new_rows[i], was_triangulated[i] = 0, obs_start[i] = 2i,
+ * n_obs_row[i] = 2, obs_start[n_matches] = 2 n_matches; the two observations (cur, j) and (adj, m) in ascending kf_id of their slots
+ * (MapPoint::observations is a std::map<KfId, KpId>), each with obs_kf, obs_kp, obs_x, obs_y, obs_octave, obs_depth and obs_desc =
+ * kf_desc_base[slot] + keypoint (-1 for a negative base) as ms_observation_lists gathers them; first_octave[i] = the first one's octave.
+ * match_kp1 / match_kp2 (DEVICE [cap_rows], each may be NULL) = j / m.  n_matches goes to the HOST.  The lists are a valid input of
+ * ms_triangulate_lists (n_rows = n_matches, n_obs = 2 n_matches; MS_TRI_TME or MS_TRI_MIDPOINT), which writes mp_pos and mp_flags of the
+ * provisional rows (:308).  No table is written here: a provisional row stays mp_live = 0.  All of `lists` but rows and obs_start may be
+ * NULL, and the keypoint-table array or kf_desc_base an output reads may be NULL when that output is.
+ * One launch: ONE workgroup of 256 lanes walks the keypoints in trips of 256, decides and counts (phase A, which writes nothing) and writes
+ * behind a barrier (phase B), unless phase A counted a violation: MS_ERR_INVALID with nothing written for a matched[j] outside
+ * [0, n_kp2) other than -1, a keypoint of adj named twice, a matched keypoint of either slot whose kf_mp entry is already valid
+ * (keyframe.cpp:275), a used new_rows entry that is live and, for n_levels > 0, a matched keypoint's octave outside [0, n_levels) (no
+ * clamped copy is written; n_levels = 0 gathers octaves as they are).  MS_ERR_CAPACITY when n_matches > n_new, > cap_rows or 2 n_matches >
+ * cap_obs: nothing is written and n_matches is the needed count, so the caller can call again.
+ * Synchronous: one upload (new_rows), one download (the count and the violation counters); the workspace belongs to the context and only grows.
+ * MS_ERR_INVALID, with nothing written and before any device call: cur or adj outside [0, n_kf) or with kf_id < 0 (or the same kf_id);
+ * cur == adj; new_rows out of range or listed twice; n_kp1 or n_kp2 > stride; n_levels outside [0, MS_TRI_MAX_LEVELS]; stride < 1; a
+ * negative size; a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps.  n_kp1 = 0 returns n_matches = 0 without a launch (the
+ * lists are not touched); a matched array of -1 returns 0 and obs_start = {0}.
+ *
+ * ms_create_points_bind: after ms_triangulate_lists.  For every entry i with mp_flags[rows[i]] != 0 (:309; two observations give UNSURE = 2
+ * or NOT_TRIANGULATED = 0, :629-636): kf_mp[cur][match_kp1[i]] = kf_mp[adj][match_kp2[i]] = rows[i] (:310-311), mp_live[row] = 1,
+ * mp_desc[row] = the pool descriptor of the FIRST observation with obs_desc != -1 (updateDescriptor of two observations, the rule of
+ * ms_match_tracked_finish; skipped when desc_pool or lists->obs_desc is NULL), n_obs[row] = 2 and mp_track[row] = -1 (DEVICE int32 [n_mp],
+ * each may be NULL), usable1[match_kp1[i]] = 0 and usable2[match_kp2[i]] = 0 (the DEVICE `usable` masks of the two ms_match_frame, each
+ * may be NULL).  A failed entry writes nothing: its row stays mp_live = 0 and mp_flags = 0 and free, its keypoints stay unbound and usable,
+ * so they are offered to the next adjacent keyframe; the position ms_triangulate_lists may have left in the row means nothing.
+ * Packed in match order (DEVICE [n_matches], each may be NULL): created_rows, created_kp1, created_kp2; n_created goes to the HOST.
+ * One launch in the same trip shape, one download.  The lists are read where they lie; every row (n_mp), keypoint (n_kp1, n_kp2) and
+ * descriptor index (n_pool) is compared with its table first, and MS_ERR_INVALID with nothing written is returned for one outside.
+ * MS_ERR_INVALID before any device call: cur, adj as above; n_kp1 or n_kp2 > stride; descriptor arrays not 16-byte aligned; stride < 1; a
+ * negative size; a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_matches: MS_COVIS_MAX_STRIDE).  n_matches = 0 is fine.
+ *
+ * ms_unbound_mask: usable[s][j] = !((uint32)kf_mp[slots[s] * stride + j] < n_mp) for j < n_kp[s], for n_slots slots in one launch -- the
+ * M2 mask of ms_match_frame (keyframe_matcher.cpp:205-221) taken from the table.  slots, n_kp (HOST int32 [n_slots]); usable (HOST
+ * [n_slots] of DEVICE uint8 pointers, [n_kp[s]] each).  MS_ERR_INVALID for a slot outside [0, n_kf), n_kp[s] outside [0, stride], a
+ * missing array; MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_slots: MS_COVIS_MAX_QUERIES).
+ *
+ * All three give the same bits on every call and at every capacity: integer work, one LDS atomicOr per match in ms_create_points_lists
+ * and no other atomic.  The *_check twins are the host validation alone (no context, no device; `why` receives the message). */
+int ms_create_points_lists(ms_ctx *ctx,
+    /* DEVICE tables, read */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int n_mp,
+    /* HOST [n_kf] */
+    const int32_t *kf_id,
+    /* DEVICE keypoint table; see above for which may be NULL */
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth,
+    /* HOST [n_kf], may be NULL when lists->obs_desc is */
+    const int32_t *kf_desc_base,
+    int cur, int adj,
+    /* DEVICE [n_kp1]; n_kp1 / n_kp2 = the keypoints of cur / adj */
+    const int32_t *matched, int n_kp1, int n_kp2,
+    /* HOST */
+    const int32_t *new_rows, int n_new, int n_levels,
+    /* HOST struct of DEVICE pointers, and their capacities */
+    const ms_obs_lists *lists, int cap_rows, int cap_obs,
+    /* DEVICE [cap_rows], each may be NULL */
+    int32_t *match_kp1, int32_t *match_kp2,
+    /* HOST */
+    int32_t *n_matches);
+int ms_create_points_lists_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int n_mp, const int32_t *kf_id,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, int cur, int adj,
+    const int32_t *matched, int n_kp1, int n_kp2, const int32_t *new_rows, int n_new, int n_levels,
+    const ms_obs_lists *lists, int cap_rows, int cap_obs, const int32_t *match_kp1, const int32_t *match_kp2,
+    const int32_t *n_matches, char *why, size_t why_bytes);
+int ms_create_points_bind(ms_ctx *ctx,
+    /* DEVICE tables, updated in place (mp_flags is read); n_obs and mp_track may be NULL */
+    int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, uint8_t *mp_live, uint32_t *mp_desc, int32_t *n_obs, int32_t *mp_track, int n_mp,
+    const uint32_t *desc_pool, int n_pool,
+    int cur, int adj,
+    /* HOST struct of DEVICE pointers (rows, obs_desc are read); DEVICE [n_matches], what ms_create_points_lists left */
+    const ms_obs_lists *lists, const int32_t *match_kp1, const int32_t *match_kp2, int n_matches,
+    /* the keypoints of cur / adj; DEVICE masks of the two frames [n_kp1] / [n_kp2], each may be NULL */
+    int n_kp1, int n_kp2, uint8_t *usable1, uint8_t *usable2,
+    /* DEVICE [n_matches], each may be NULL */
+    int32_t *created_rows, int32_t *created_kp1, int32_t *created_kp2,
+    /* HOST */
+    int32_t *n_created);
+int ms_create_points_bind_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const uint32_t *mp_desc,
+    const int32_t *n_obs, const int32_t *mp_track, int n_mp, const uint32_t *desc_pool, int n_pool, int cur, int adj,
+    const ms_obs_lists *lists, const int32_t *match_kp1, const int32_t *match_kp2, int n_matches,
+    int n_kp1, int n_kp2, const uint8_t *usable1, const uint8_t *usable2, const int32_t *created_rows, const int32_t *created_kp1, const int32_t *created_kp2,
+    const int32_t *n_created, char *why, size_t why_bytes);
+int ms_unbound_mask(ms_ctx *ctx, const int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    /* HOST [n_slots]: the slots, their keypoint counts, their DEVICE masks */
+    const int32_t *slots, const int32_t *n_kp, uint8_t *const *usable, int n_slots);
+int ms_unbound_mask_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *slots, const int32_t *n_kp,
+    uint8_t *const *usable, int n_slots, char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

@@ -75,6 +75,9 @@ public:
     const float *sortedY() const { return sy_.data(); }
     const std::int32_t *sortedIndex() const { return si_.data(); }
     const ms_match_frame &frame() const { return f_; }
+    // the DEVICE `usable` mask [keypoints]: what createNewMapPoints clears as it binds keypoints, and unboundMasks rewrites from the keyframe table
+    std::uint8_t *mutableUsable() { return usable_.data(); }
+    std::size_t keyPointCount() const { return (std::size_t)f_.n; }
 private:
     ms_match_frame f_{};                     // pointers into the arrays below
     DeviceArray<std::uint32_t> desc_;

@@ -243,6 +243,14 @@ public:
             return;
         }
     }
+    // room for at least `rows` rows and `observations` observations (the contents are not kept when the buffers grow), and the counts a
+    // caller that filled the lists itself (createNewMapPoints) found
+    void ensure(std::size_t rows, std::size_t observations) {
+        if (rows > capRows_ || observations > capObs_ || !buf_.obsStart.data()) reserve(std::max(rows, capRows_), std::max(observations, capObs_));
+    }
+    void setCounts(std::size_t rows, std::size_t observations, bool hasDescriptors) { nRows_ = rows; nObs_ = observations; hasDesc_ = hasDescriptors; }
+    std::size_t rowCapacity() const { return capRows_; }
+    std::size_t observationCapacity() const { return capObs_; }
     std::size_t rowCount() const { return nRows_; }
     std::size_t observationCount() const { return nObs_; }
     bool hasDescriptors() const { return hasDesc_; }

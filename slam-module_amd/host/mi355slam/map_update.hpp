@@ -426,6 +426,137 @@ inline MatchTrackedResult matchTrackedFeatures(Context &ctx, DeviceObservationLi
     return out;
 }
 
+// ---- createNewMapPoints on the device tables (ms_create_points_lists, ms_create_points_bind, ms_unbound_mask) --------------------------
+// The `usable` masks of the triangulation matcher ("the keypoint has no map point", keyframe_matcher.cpp:205-221) of the listed slots, written
+// from the keyframe table in one launch.  frames[slot] = the DeviceKeyframe of that slot.
+inline void unboundMasks(Context &ctx, const DeviceKeyframeMapPoints &kfTable, const std::vector<std::int32_t> &slots, const std::vector<DeviceKeyframe *> &frames) {
+    std::vector<std::int32_t> counts;
+    std::vector<std::uint8_t *> masks;
+    for (std::int32_t s : slots) {
+        if (s < 0 || (std::size_t)s >= frames.size() || !frames[s]) throw std::invalid_argument("unboundMasks: no frame for slot " + std::to_string(s));
+        counts.push_back((std::int32_t)frames[s]->keyPointCount());
+        masks.push_back(frames[s]->mutableUsable());
+    }
+    ctx.check(ms_unbound_mask(ctx.get(), kfTable.table(), (int)kfTable.size(), (int)kfTable.stride(), (int)kfTable.mapPointCount(), slots.data(), counts.data(), masks.data(),
+                              (int)slots.size()), "ms_unbound_mask");
+}
+
+// What one adjacent keyframe gave: per match (ascending keypoint of the current keyframe) the provisional row, the two keypoints and the
+// triangulator's status / reason; the created points packed in the same order -- what nextMpId, the host MapPoint objects and their colours
+// are derived from.  skipped = the slot was the current keyframe's (mapper_helpers.cpp:281).
+struct CreatedPoints {
+    std::int32_t slot = -1;
+    bool skipped = false;
+    std::vector<std::int32_t> rows, keyPoints1, keyPoints2;
+    std::vector<std::uint8_t> status, reason;
+    std::vector<std::int32_t> createdRows, createdKeyPoints1, createdKeyPoints2;
+};
+
+// createNewMapPoints (mapper_helpers.cpp:271-318) for the keyframe in currentSlot, nothing per match on the host.  Per adjacent slot, in the
+// given order:  create_E_21 -> ms_match_triangulation -> ms_create_points_lists -> ms_triangulate_lists (TME or MIDPOINT, :308) ->
+// ms_create_points_bind.  frames[slot] = the slot's DeviceKeyframe, whose `usable` mask says "no map point" (unboundMasks) and is kept
+// current by the bind step, so the next adjacent's matcher sees this adjacent's binds.  freeRows: free table rows, at least as many as one
+// adjacent can match; an adjacent takes the first ones and hands back those whose triangulation failed.  `lists` is scratch.
+// observationCount / mpTrack: DEVICE [mapPointCount] arrays of the cull / fuse / track steps to keep current (2 and -1 for a created row), or null.
+// hostPoses: the poses DeviceKeyframePoses holds (downloaded when null).
+inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &kfTable, DeviceMapPoints &table, DeviceMapPointFlags &flags,
+                                                     DeviceMapPointLive &live, const DeviceKeypointTable &kpTable, const DeviceKeyframePoses &poses, const KeyframeCameras &cams,
+                                                     const std::vector<std::int32_t> &kfIds, const std::vector<std::int32_t> &descBase, const DeviceDescriptorPool *pool,
+                                                     std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots, const std::vector<DeviceKeyframe *> &frames,
+                                                     const std::vector<std::int32_t> &freeRows, const StaticSettings &settings, TriangulationMethod method,
+                                                     std::int32_t *observationCount = nullptr, std::int32_t *mpTrack = nullptr,
+                                                     const std::vector<DeviceKeyframePoses::Pose> *hostPoses = nullptr) {
+    const std::size_t nKf = kfTable.size(), nMp = kfTable.mapPointCount();
+    if (currentSlot < 0 || (std::size_t)currentSlot >= nKf) throw std::invalid_argument("createNewMapPoints: slot outside the table");
+    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || kfIds.size() != nKf || descBase.size() != nKf || poses.size() != nKf || frames.size() != nKf)
+        throw std::invalid_argument("createNewMapPoints: one camera, focal length, KfId, descriptor base, pose and frame per slot");
+    if (table.size() != nMp || flags.size() < nMp || live.size() < nMp) throw std::invalid_argument("createNewMapPoints: the map-point tables differ in size");
+    if (kpTable.size() != nKf || kpTable.stride() != kfTable.stride()) throw std::invalid_argument("createNewMapPoints: the keypoint table does not match the keyframe table");
+    if (method == TriangulationMethod::FIRST_LAST) throw std::invalid_argument("createNewMapPoints: TME or MIDPOINT");
+    if (!frames[currentSlot]) throw std::invalid_argument("createNewMapPoints: no frame for the current slot");
+    const std::vector<DeviceKeyframePoses::Pose> downloaded = hostPoses ? std::vector<DeviceKeyframePoses::Pose>() : poses.download();
+    const std::vector<DeviceKeyframePoses::Pose> &P = hostPoses ? *hostPoses : downloaded;
+    if (P.size() != nKf) throw std::invalid_argument("createNewMapPoints: one host pose per slot");
+    auto rotation = [](const DeviceKeyframePoses::Pose &p, double R[9], double t[3]) {
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) R[3 * i + j] = p[4 * i + j]; t[i] = p[4 * i + 3]; }
+    };
+    DeviceKeyframe &kf1 = *frames[currentSlot];
+    const std::size_t n1 = kf1.keyPointCount();
+    const int levels = (int)settings.levelSigmaSq.size();
+    const Parameters &p = settings.parameters;
+    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)levels, p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    // device scratch: E and the scale factors | match count | matched | the matches' keypoints | the created points
+    const std::size_t pitch = (n1 + 63) / 64 * 64 + 64, oS = 128, oCount = oS + detail::pad16(4 * settings.scaleFactors.size()) + 64, oInts = oCount + 64;
+    unsigned char *ws = ctx.workspace(oInts + 4 * 6 * pitch);
+    std::int32_t *matched = reinterpret_cast<std::int32_t *>(ws + oInts), *kp1 = matched + pitch, *kp2 = kp1 + pitch, *createdRows = kp2 + pitch,
+                 *createdKp1 = createdRows + pitch, *createdKp2 = createdKp1 + pitch;
+    std::vector<std::int32_t> free = freeRows;
+    std::vector<CreatedPoints> out;
+    for (std::int32_t adj : adjacentSlots) {
+        CreatedPoints r;
+        r.slot = adj;
+        if (adj == currentSlot) {                            // :281
+            r.skipped = true;
+            out.push_back(std::move(r));
+            continue;
+        }
+        if (adj < 0 || (std::size_t)adj >= nKf || !frames[adj]) throw std::invalid_argument("createNewMapPoints: no frame for slot " + std::to_string(adj));
+        DeviceKeyframe &kf2 = *frames[adj];
+        double R1[9], t1[3], R2[9], t2[3], E[9];
+        rotation(P[currentSlot], R1, t1); rotation(P[adj], R2, t2);
+        create_E_21(R2, t2, R1, t1, E);                      // keyframe_matcher.cpp:171-175
+        std::vector<unsigned char> &st = ctx.staging();
+        st.assign(oCount, 0);
+        std::memcpy(st.data(), E, 72);
+        std::memcpy(st.data() + oS, settings.scaleFactors.data(), 4 * settings.scaleFactors.size());
+        ctx.check(ms_dev_upload(ctx.get(), ws, st.data(), st.size()), "ms_dev_upload");
+        const ms_match_frame f1 = kf1.frame(), f2 = kf2.frame();
+        ctx.check(ms_match_triangulation(ctx.get(), &f1, &f2, 1, reinterpret_cast<const double *>(ws), reinterpret_cast<const float *>(ws + oS), p.epipolarCheckThresholdDegrees, 1,
+                                         &matched, reinterpret_cast<std::int32_t *>(ws + oCount)), "ms_match_triangulation");
+        std::int32_t nMatches = 0;
+        for (int attempt = 0;; ++attempt) {
+            ms_obs_lists l = lists.lists();
+            if (!pool) l.obs_desc = nullptr;
+            const int rc = ms_create_points_lists(ctx.get(), kfTable.table(), (int)nKf, (int)kfTable.stride(), live.live(), (int)nMp, kfIds.data(), kpTable.x(), kpTable.y(),
+                                                  kpTable.octave(), kpTable.depth(), pool ? descBase.data() : nullptr, currentSlot, adj, matched, (int)n1, (int)kf2.keyPointCount(),
+                                                  free.data(), (int)free.size(), levels, &l, (int)lists.rowCapacity(), (int)lists.observationCapacity(), kp1, kp2, &nMatches);
+            if (rc == MS_ERR_CAPACITY && attempt == 0 && (std::size_t)nMatches <= free.size() &&
+                ((std::size_t)nMatches > lists.rowCapacity() || 2 * (std::size_t)nMatches > lists.observationCapacity())) {
+                lists.ensure((std::size_t)nMatches, 2 * (std::size_t)nMatches);      // the needed count came back: once is enough
+                continue;
+            }
+            ctx.check(rc, "ms_create_points_lists");
+            break;
+        }
+        const std::size_t n = (std::size_t)nMatches;
+        lists.setCounts(n, 2 * n, pool != nullptr);
+        r.rows.assign(free.begin(), free.begin() + (std::ptrdiff_t)n);
+        r.keyPoints1 = ctx.download(kp1, n); r.keyPoints2 = ctx.download(kp2, n);
+        r.status.assign(n, 0); r.reason.assign(n, 0);
+        ms_obs_lists l = lists.lists();
+        if (!pool) l.obs_desc = nullptr;
+        ctx.check(ms_triangulate_lists(ctx.get(), table.mutablePosition(), flags.mutableFlags(), (int)nMp, poses.pose(), (int)nKf, cams.camera.data(), cams.focalLength.data(), &l,
+                                       (int)n, (int)(2 * n), &s, (int)method, r.status.data(), r.reason.data(), nullptr), "ms_triangulate_lists");      // :308
+        std::int32_t nCreated = 0;
+        ctx.check(ms_create_points_bind(ctx.get(), kfTable.mutableTable(), (int)nKf, (int)kfTable.stride(), flags.flags(), live.mutableLive(), table.mutableDescriptor(),
+                                        observationCount, mpTrack, (int)nMp, pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, currentSlot, adj, &l, kp1, kp2,
+                                        (int)n, (int)n1, (int)kf2.keyPointCount(), kf1.mutableUsable(), kf2.mutableUsable(), createdRows, createdKp1, createdKp2, &nCreated), "ms_create_points_bind");      // :309-316
+        r.createdRows = ctx.download(createdRows, (std::size_t)nCreated);
+        r.createdKeyPoints1 = ctx.download(createdKp1, (std::size_t)nCreated); r.createdKeyPoints2 = ctx.download(createdKp2, (std::size_t)nCreated);
+        std::vector<std::int32_t> left;                      // the rows of the failed matches go back to the front, in order
+        left.reserve(free.size());
+        std::size_t c = 0;
+        for (std::size_t i = 0; i < free.size(); ++i) {
+            if (i < n && c < r.createdRows.size() && r.createdRows[c] == free[i]) { ++c; continue; }
+            left.push_back(free[i]);
+        }
+        free.swap(left);
+        out.push_back(std::move(r));
+    }
+    return out;
+}
+
 // ---- fusing duplicate map points on the device tables (ms_map_fuse, ms_map_replace_pairs) ----------------------------------------------
 // The tables the fuse steps update in place.  observationCount: DEVICE [mapPointCount], mp.observations.size() of every row as
 // ms_observation_count leaves it (observationCountsOnDevice); the walk keeps it current, so one count serves a whole new-keyframe chain.

@@ -1681,6 +1681,140 @@ class KeyframeTable:
         res = self.match_tracked_bind(table, flags, live, tracks, kp, pool, poses, kf_id, cams, focal, desc_base, frame, new_rows, settings, view_cos_limit)
         return self.match_tracked_refresh(res, scale_factors_)
 
+    def create_points_lists_device(self, lists, live, n_mp, kf_id, kp, desc_base, cur, adj, matched, n_kp1, n_kp2, new_rows, n_levels=0, match_kp1=None, match_kp2=None,
+                                   cap_rows=None, cap_obs=None):
+        """ms_create_points_lists into an ObservationLists, everything left on the device: the matches of `matched` (a DevBuf of [n_kp1]
+        int32, what ms_match_triangulation wrote for the pair cur / adj) as provisional rows new_rows[i] with their two observations.
+        live = a DevBuf of [n_mp] uint8, kp = a KeypointTable, desc_base [n_kf] int32 or None, match_kp1 / match_kp2 = DevBufs of cap_rows
+        int32 or None.  Returns (rc, n_matches) without raising: MS_ERR_CAPACITY still reports the needed count."""
+        kf_id, new_rows = _i32(kf_id), _i32(new_rows)
+        if len(kf_id) != self.n_kf or (kp.n_kf, kp.stride) != (self.n_kf, self.stride):
+            raise ValueError("kf_id or the keypoint table do not describe the table's %d x %d" % (self.n_kf, self.stride))
+        base = None if desc_base is None else _i32(desc_base)
+        if base is not None and len(base) != self.n_kf:
+            raise ValueError("desc_base describes %d slots, the table has %d" % (len(base), self.n_kf))
+        L = lists.struct(True, base is not None, True)
+        n = C.c_int32(0)
+        rc = lib().ms_create_points_lists(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(live), int(n_mp), _vp(kf_id), _vp(kp.x), _vp(kp.y), _vp(kp.octave),
+                                          _vp(kp.depth), _vp(base), int(cur), int(adj), _vp(matched), int(n_kp1), int(n_kp2), _vp(new_rows), len(new_rows), int(n_levels),
+                                          C.byref(L), lists.cap_rows if cap_rows is None else int(cap_rows), lists.cap_obs if cap_obs is None else int(cap_obs),
+                                          _vp(match_kp1), _vp(match_kp2), C.byref(n))
+        return rc, n.value
+
+    def create_points_bind_device(self, table, flags, live, pool, cur, adj, lists, match_kp1, match_kp2, n_matches, n_kp1, n_kp2, usable1=None, usable2=None, n_obs=None,
+                                  mp_track=None, created=None):
+        """ms_create_points_bind on the first n_matches entries of `lists` after their triangulation: the entries whose flags are not 0 are
+        bound in both keyframes, made live, given the descriptor of their first observation in `pool` (a DevBuf; None: descriptors stay)
+        and cleared in the two `usable` masks (DevBufs or None).  n_obs / mp_track = DevBufs of [n_mp] int32 or None; created = dict of
+        DevBufs created_rows / created_kp1 / created_kp2 of n_matches int32 (each may be absent).  Returns (rc, n_created) without raising."""
+        created = created or {}
+        n_pool = int(np.prod(pool.shape)) // 8 if pool is not None else 0
+        L = lists.struct(True, True, True)
+        n = C.c_int32(0)
+        rc = lib().ms_create_points_bind(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(flags), _vp(live), _vp(table.desc), _vp(n_obs), _vp(mp_track), table.n,
+                                         _vp(pool), n_pool, int(cur), int(adj), C.byref(L), _vp(match_kp1), _vp(match_kp2), int(n_matches), int(n_kp1), int(n_kp2),
+                                         _vp(usable1), _vp(usable2), *[_vp(created.get(k)) for k in ("created_rows", "created_kp1", "created_kp2")], C.byref(n))
+        return rc, n.value
+
+    def unbound_mask(self, slots, n_kp, n_mp, masks):
+        """ms_unbound_mask: masks[s] (a DevBuf of n_kp[s] bytes) = 1 where keypoint j of slot slots[s] has no map point -- the M2 `usable`
+        mask of the triangulation matcher, from this table, for all listed slots in one launch."""
+        slots, n_kp = _i32(slots), _i32(n_kp)
+        if len(n_kp) != len(slots) or len(masks) != len(slots):
+            raise ValueError("one keypoint count and one mask per slot")
+        ptrs = (C.c_void_p * max(len(slots), 1))(*[m.ptr for m in masks])
+        self.ctx.check(lib().ms_unbound_mask(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, int(n_mp), _vp(slots), _vp(n_kp), ptrs, len(slots)), "ms_unbound_mask")
+
+    def create_points(self, table, flags, live, kp, pool, poses, kf_id, cams, focal, desc_base, current, adjacent, frames, free_rows, settings, scale_factors_, thr_deg,
+                      mode=TRI_TME, n_obs=None, mp_track=None, lists=None, check_orientation=True, exact_capacity=False, pose_host=None):
+        """createNewMapPoints (mapper_helpers.cpp:271-318) for the keyframe in slot `current` on the device tables, in place: this
+        KeyframeTable, the MapPointTable `table`, flags / live (DevBufs) and the `usable` masks of `frames` (slot -> FrameOnDevice with
+        octave and bearing, whose masks hold "has no map point": see unbound_mask).  Per adjacent slot, in the given order and skipping
+        `current` (:281): create_E21, ms_match_triangulation, ms_create_points_lists, ms_triangulate_lists (mode = TRI_TME or
+        TRI_MIDPOINT), ms_create_points_bind.  free_rows = free table rows; an adjacent takes the first ones and gives back those whose
+        triangulation failed.  pose_host [n_kf, 12] = the poses as the pose table holds them (downloaded when None).  `lists` (an
+        ObservationLists; allocated here when None) is regrown when an adjacent reports MS_ERR_CAPACITY; exact_capacity regrows it for
+        every adjacent to exactly its number of matches (tests).  Returns one dict per adjacent slot: slot, n_matches, match_kp1,
+        match_kp2, rows, status, reason, created_rows, created_kp1, created_kp2 (None for the skipped slot).
+        nextMpId, the host MapPoint objects and their colours stay with the caller, who derives them from the created lists."""
+        ctx = self.ctx
+        kf_id, desc_base, free = _i32(kf_id), _i32(desc_base), [int(r) for r in _i32(free_rows)]
+        P = np.asarray(poses.download() if pose_host is None else pose_host, np.float64).reshape(-1, 3, 4)
+        sf = ctx.upload(np.ascontiguousarray(scale_factors_, np.float32))
+        n_levels = len(settings["level_sigma_sq"])
+        own_lists = lists is None
+        if own_lists:
+            lists = ObservationLists(ctx, 256, 512)
+        f1 = frames[current]
+        n1 = f1.n
+        d_E, d_matched, d_count = ctx.alloc(72), ctx.alloc(4 * max(n1, 1)), ctx.alloc(16)
+        bufs = {k: ctx.alloc(4 * max(n1, 1)) for k in ("match_kp1", "match_kp2", "created_rows", "created_kp1", "created_kp2")}
+        some = lambda b, n: b.download(np.int32, (n,)) if n else np.zeros(0, np.int32)
+        out = []
+        try:
+            for adj in adjacent:
+                if adj == current:                           # :281
+                    out.append(None)
+                    continue
+                f2 = frames[adj]
+                E = create_E21(P[adj][:, :3], P[adj][:, 3], P[current][:, :3], P[current][:, 3])
+                ctx.check(lib().ms_dev_upload(ctx._h, C.c_void_p(d_E.ptr), _vp(E), C.c_size_t(72)), "ms_dev_upload")
+                A1, A2 = (MatchFrame * 1)(f1.struct), (MatchFrame * 1)(f2.struct)
+                ptrs = (C.c_void_p * 1)(d_matched.ptr)
+                ctx.check(lib().ms_match_triangulation(ctx._h, A1, A2, 1, _vp(d_E), _vp(sf), C.c_float(thr_deg), int(check_orientation), ptrs, _vp(d_count)),
+                          "ms_match_triangulation")
+                call = lambda *caps: self.create_points_lists_device(lists, live, table.n, kf_id, kp, desc_base, current, adj, d_matched, n1, f2.n, free, n_levels,
+                                                                     bufs["match_kp1"], bufs["match_kp2"], *caps)
+                rc, n = call(0, 0) if exact_capacity else call()
+                if rc == MS_ERR_CAPACITY and n <= len(free) and (exact_capacity or n > lists.cap_rows or 2 * n > lists.cap_obs):
+                    lists.grow(n, 2 * n)                     # the needed count came back: once is enough
+                    rc, n = call()
+                ctx.check(rc, "ms_create_points_lists")
+                res = dict(slot=int(adj), n_matches=n, match_kp1=some(bufs["match_kp1"], n), match_kp2=some(bufs["match_kp2"], n), rows=np.array(free[:n], np.int32))
+                res["status"], res["reason"], _ = table.triangulate_lists(poses, cams, focal, lists, n, 2 * n, settings, mode, flags=flags)
+                rc, n_created = self.create_points_bind_device(table, flags, live, pool, current, adj, lists, bufs["match_kp1"], bufs["match_kp2"], n, n1, f2.n,
+                                                               f1.bufs["usable"], f2.bufs["usable"], n_obs, mp_track, bufs)
+                ctx.check(rc, "ms_create_points_bind")
+                for k in ("created_rows", "created_kp1", "created_kp2"):
+                    res[k] = some(bufs[k], n_created)
+                taken = set(res["created_rows"].tolist())
+                free = [r for r in free if r not in taken]
+                out.append(res)
+        finally:
+            for b in [d_E, d_matched, d_count, sf] + list(bufs.values()):
+                b.free()
+            if own_lists:
+                lists.free()
+        return out
+
+
+def create_E21(R1, t1, R2, t2):
+    """create_E_21 (openvslam/essential_solver.cc:157-162) with the host mirror's order of operations: [t21]x R21, R21 = R2 R1^T,
+    t21 = t2 - R21 t1; float64 [9], row-major."""
+    R1, R2 = [[float(v) for v in np.asarray(R, np.float64).reshape(9)] for R in (R1, R2)]
+    t1, t2 = [[float(v) for v in np.asarray(t, np.float64).reshape(3)] for t in (t1, t2)]
+    R21, t21 = [0.0] * 9, [0.0] * 3
+    for i in range(3):
+        for j in range(3):
+            s = 0.0
+            for k in range(3):
+                s += R2[3 * i + k] * R1[3 * j + k]
+            R21[3 * i + j] = s
+    for i in range(3):
+        s = 0.0
+        for k in range(3):
+            s += -R21[3 * i + k] * t1[k]
+        t21[i] = s + t2[i]
+    S = [0.0, -t21[2], t21[1], t21[2], 0.0, -t21[0], -t21[1], t21[0], 0.0]
+    E = np.zeros(9, np.float64)
+    for i in range(3):
+        for j in range(3):
+            s = 0.0
+            for k in range(3):
+                s += S[3 * i + k] * R21[3 * k + j]
+            E[3 * i + j] = s
+    return E
+
 
 class TrackedFrameC(C.Structure):
     """ms_tracked_frame."""
