@@ -1168,6 +1168,103 @@ int ms_unbound_mask(ms_ctx *ctx, const int32_t *kf_mp, int n_kf, int stride, int
 int ms_unbound_mask_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *slots, const int32_t *n_kp,
     uint8_t *const *usable, int n_slots, char *why, size_t why_bytes);
 
+/* ---- the local BA window on the device map tables ------------------------------------------------------------------------
+ * The two steps of localBundleAdjust (bundle_adjuster.cpp:141-394) around the solve that walk MapPoint::observations and Keyframe::mapPoints:
+ * building the graph's vertices and projection edges (:245-290) and writing the result back (:376-390, or :326-331 when the neighbourhood
+ * stage is skipped).  kf_mp, mp_flags, n_obs, mp_pos, kf_pose and the validity rule are those of 9.5 - 9.8; tests/ba_window_ref.py restates
+ * both steps and is their specification.
+ *
+ * ms_ba_window_lists: `lists` (n_rows, n_obs) is what ms_observation_lists left for the rows of an ms_map_point_union over the local slots
+ * with require = 1 (localMapPoints: ascending row, TRIANGULATED only; every observation of each, ascending KfId); rows, obs_start, obs_kf,
+ * obs_kp, obs_x, obs_y and obs_octave are read.  local_slot (HOST [n_local]) = the local keyframes in POSE ORDER: the caller sorts them by
+ * descending KfId, the std::set<KfId, std::greater<>> walk of :245; distinct slots, each holding a keyframe.  current_index = the position
+ * of the current keyframe in local_slot.  kf_cam / kf_focal (HOST, per slot) as ms_triangulate takes them; level_sigma_sq (HOST [n_levels]).
+ * HOST outputs, the arrays of an ms_ba_problem (the caller's: pose holds n_local * 7, point cap_point * 3, the obs_* arrays cap_edge entries):
+ *   pose [n_local * 7]   matrixToPose(poseCW) = g2o::SE3Quat(R, t) of kf_pose[local_slot[k]]: Eigen's quaternion of a rotation matrix (its
+ *                        four branches in its operation order), then normalizeRotation (flipped to w >= 0, divided by its norm); qx, qy,
+ *                        qz, qw, tx, ty, tz
+ *   point [n_rows * 3]   mp_pos[rows[p]], bit for bit; a row without a kept observation is a point like any other
+ *   per kept observation, in list order (rows ascending, inside a row ascending KfId, then keypoint: the order of :259-290):
+ *   obs_point            the position p of the row in `rows`;   obs_pose   the position k of the observing slot in local_slot
+ *   obs_uv               ((x - cx) / fx, (y - cy) / fy) of the float32 pixel in float64: bearing.xy / bearing.z of the ms_pinhole stand-in (:52)
+ *   obs_info             (double)focal * (double)focal / (double)level_sigma_sq[octave] (:51)
+ * An observation from a slot that is not in local_slot is dropped (:275).  n_edge = the kept observations; n_current = those with obs_pose ==
+ * current_index (nCurrentFrameMapPoints of :219, which the thresholds of :236 and :326 read).
+ * DEVICE outputs, kept for ms_ba_window_apply: window->edge_slot / edge_kp / edge_point ([cap_edge] each) = the table entry (slot, keypoint)
+ * and the point index of every edge.
+ * One thread per listed observation; keep / drop from a per-slot pose index (int32 [n_kf], -1 for a slot that is not local) that is uploaded
+ * with the cameras; ranks and offsets from the shared block rank / offsets scan.  One clear of the result head and four launches whatever the sizes (count,
+ * offsets, pack, vertices), one upload, one download: the host outputs lie side by side in the context's workspace and come down in one copy through the
+ * context's pinned block.  Synchronous on the context stream.  Integer arithmetic decides every position, there is no atomic, and the float64
+ * expressions are evaluated as written without contraction: the same input gives the same bits on every call and at any capacity.
+ * MS_ERR_INVALID, with nothing written and before any device call: a local slot out of range or listed twice, current_index outside
+ * [0, n_local), a local slot's camera with fx or fy not positive and finite (or cx, cy not finite), n_levels outside [1, MS_TRI_MAX_LEVELS],
+ * a level_sigma_sq that is not positive and finite, a negative size, a missing array, observations without a row.  MS_ERR_CAPACITY when
+ * n_rows > cap_point or n_edge > cap_edge: nothing is written to the caller's arrays or to `window`, and n_edge / n_current are returned, so
+ * the caller regrows and calls again (n_edge <= n_obs always); also beyond MS_COVIS_MAX_KF / MS_COVIS_MAX_MP / MS_TRI_MAX_ROWS / MS_TRI_MAX_OBS.
+ * n_rows = 0 is fine: poses only, n_edge = 0.  The lists are valid by construction when they come from ms_observation_lists (built with
+ * n_levels); a row outside [0, n_mp) gives a zero point and an octave outside [0, n_levels) reads the nearest level.
+ *
+ * ms_ba_window_apply: the solver's answer into the tables, in place.  HOST inputs, the arrays ms_ba_download returned: pose [n_pose * 7] with
+ * n_pose >= n_local (the fixed extra vertex of stage 2 is ignored), point [n_rows * 3], chi2 [n_edge] (NULL for MS_BA_APPLY_NEIGHBOR).  The
+ * window: `window` and n_edge as ms_ba_window_lists left them, rows (DEVICE [n_rows]: lists->rows), local_slot, current_index.
+ * MS_BA_APPLY_LOCAL (:376-390): every edge with chi2 > 5.991 (float64, strict; a NaN keeps the edge) is erased in both directions:
+ * kf_mp[edge_slot * stride + edge_kp] = -1 and n_obs[row] -= 1.  Then every row that lost at least one observation and whose n_obs is now
+ * <= 2 gets mp_flags = 2, UNSURE (the reference tests after each erase; the count only falls, so the test on the final count is the same);
+ * a row that lost nothing keeps its flags whatever its count.  Then mp_pos[rows[p]] = point[p] for every point, and kf_pose[local_slot[k]] =
+ * rows 0-2 of to_homogeneous_matrix() for every k < n_local: Eigen's toRotationMatrix of the quaternion as given, t copied.
+ * MS_BA_APPLY_NEIGHBOR (:326-331): the positions, and the pose of local_slot[current_index] alone; kf_mp, mp_flags and n_obs (each may be
+ * NULL) keep their bits.
+ * n_obs holds the whole-map counts, as ms_observation_count gives them and the chain keeps them current.  The tables must not change between
+ * the two calls: an edge whose table entry no longer names its row is skipped and counted (n_stale), and a non-zero count returns
+ * MS_ERR_INVALID AFTER the pass, every other effect in place, as the octave rule of ms_observation_lists does.
+ * HOST outputs: n_erased and erased_edge [n_erased], the erased edges' indices, ascending.  The application derives
+ * keyPointToTrackId.erase (keyframe.cpp:285) and its host copies from them; the matcher's "no map point" masks of the touched slots are the
+ * caller's to renew with ms_unbound_mask.  MS_ERR_CAPACITY when n_erased > cap_erased: NOTHING is written, to no table, and n_erased is the
+ * needed count (n_erased <= n_edge always).
+ * LOCAL: one clear and four launches whatever the sizes (count, offsets, erase, vertices); NEIGHBOR: one launch.  One upload, one download;
+ * synchronous.  The only atomic is the integer decrement of n_obs: the same input gives the same bits on every call.
+ * MS_ERR_INVALID before any device call: a bad mode, n_pose < n_local, local_slot / current_index as above, stride < 1, a negative size, a
+ * missing array.  The *_check twins are the host validation alone (no context, no device; `why` receives the message). */
+#define MS_BA_APPLY_LOCAL    0   /* BaStats::Ba::LOCAL: both stages ran */
+#define MS_BA_APPLY_NEIGHBOR 1   /* BaStats::Ba::NEIGHBOR: the neighbourhood stage was skipped */
+typedef struct {
+    int32_t *edge_slot, *edge_kp, *edge_point;   /* DEVICE [cap_edge] each */
+} ms_ba_window_dev;
+int ms_ba_window_lists(ms_ctx *ctx,
+    /* DEVICE tables, read */
+    const double *kf_pose, int n_kf, const double *mp_pos, int n_mp,
+    /* HOST struct of DEVICE pointers, and the counts ms_observation_lists returned */
+    const ms_obs_lists *lists, int n_rows, int n_obs,
+    /* HOST */
+    const int32_t *local_slot, int n_local, int current_index, const ms_pinhole *kf_cam, const int32_t *kf_focal,
+    const float *level_sigma_sq, int n_levels,
+    /* HOST outputs and their capacities */
+    double *pose, double *point, int32_t *obs_point, int32_t *obs_pose, double *obs_uv, double *obs_info, int cap_point, int cap_edge,
+    /* HOST struct of DEVICE pointers, written */
+    const ms_ba_window_dev *window,
+    /* HOST */
+    int32_t *n_edge, int32_t *n_current);
+int ms_ba_window_lists_check(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const ms_obs_lists *lists, int n_rows, int n_obs,
+    const int32_t *local_slot, int n_local, int current_index, const ms_pinhole *kf_cam, const int32_t *kf_focal,
+    const float *level_sigma_sq, int n_levels, const double *pose, const double *point, const int32_t *obs_point, const int32_t *obs_pose,
+    const double *obs_uv, const double *obs_info, int cap_point, int cap_edge, const ms_ba_window_dev *window,
+    const int32_t *n_edge, const int32_t *n_current, char *why, size_t why_bytes);
+int ms_ba_window_apply(ms_ctx *ctx,
+    /* DEVICE tables, updated in place; kf_mp, mp_flags and n_obs may be NULL for MS_BA_APPLY_NEIGHBOR */
+    int32_t *kf_mp, int n_kf, int stride, double *mp_pos, uint8_t *mp_flags, int32_t *n_obs, int n_mp, double *kf_pose,
+    /* HOST, what ms_ba_download returned */
+    const double *pose, int n_pose, const double *point, const double *chi2,
+    /* the window: HOST struct of DEVICE pointers, DEVICE rows, HOST local_slot */
+    const ms_ba_window_dev *window, int n_edge, const int32_t *rows, int n_rows, const int32_t *local_slot, int n_local, int current_index,
+    int mode,
+    /* HOST */
+    int32_t *erased_edge, int cap_erased, int32_t *n_erased, int32_t *n_stale);
+int ms_ba_window_apply_check(const int32_t *kf_mp, int n_kf, int stride, const double *mp_pos, const uint8_t *mp_flags, const int32_t *n_obs, int n_mp,
+    const double *kf_pose, const double *pose, int n_pose, const double *point, const double *chi2,
+    const ms_ba_window_dev *window, int n_edge, const int32_t *rows, int n_rows, const int32_t *local_slot, int n_local, int current_index,
+    int mode, const int32_t *erased_edge, int cap_erased, const int32_t *n_erased, const int32_t *n_stale, char *why, size_t why_bytes);
+
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).
  * Writes the ids of invalid entries (bin order, then insertion order) and returns their count. */

@@ -25,6 +25,7 @@ enum MsWorkspaceId {
     MS_WS_MATCH_TRACKED,    // ms_match_tracked and ms_match_tracked_finish (match_tracked.hip): device frame record / track ids / new rows / per-keypoint rows and positions
     MS_WS_MAP_FUSE,         // ms_map_fuse and ms_map_replace_pairs (map_fuse.hip): device entry rows / views / pairs / candidates / "listed by K" marks / results
     MS_WS_CREATE_POINTS,    // ms_create_points_lists, ms_create_points_bind and ms_unbound_mask (create_points.hip): device new rows / per-keypoint positions / results / slot records
+    MS_WS_BA_WINDOW,        // ms_ba_window_lists and ms_ba_window_apply (ba_window.hip): device pose index / cameras / results in; block counts / marks / the block that goes down
     MS_WS_COUNT
 };
 

@@ -30,6 +30,7 @@ struct Parameters {
     float epipolarCheckThresholdDegrees = 2.0f;
     double odometryPriorStrengthRotation = 100.0, odometryPriorStrengthPosition = 50.0;
     unsigned minVisibleMapPointsInNeighborhoodBA = 0;
+    unsigned minVisibleMapPointsInCurrentFrameBA = 0, minKeyframesInBA = 0;       // the early-outs of bundle_adjuster.cpp:235-240 (stand-in defaults)
     // loop_closer.cpp:230, loop_ransac.cpp:50, :85: set by the parent project, whose defaults are not in the reference tree
     unsigned loopClosureRansacIterations = 300;
     unsigned loopClosureRansacMinInliers = 10;

@@ -1,12 +1,16 @@
 // map_update.hpp -- the operations of the host mirror on the device-resident map (map_tables.hpp), with their argument and result structs:
 // loop correction (correctLoop), triangulation (triangulateMapPoints), covisibility (getNeighbors, computeAdjacentKeyframes, localMapPoints),
 // culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
-// fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints).
+// fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), createNewMapPoints and the local
+// bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables).
 // Results come back through Context::workspace and Context::download; nothing here owns device memory.
 #pragma once
 #include <algorithm>
 #include <array>
+#include <functional>
+#include <limits>
 #include <stdexcept>
+#include "bundle_adjuster.hpp"
 #include "keyframe_matcher.hpp"
 #include "map_tables.hpp"
 #include "optimize_transform.hpp"
@@ -553,6 +557,123 @@ inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, DeviceObserva
         }
         free.swap(left);
         out.push_back(std::move(r));
+    }
+    return out;
+}
+
+// ---- local bundle adjustment on the device tables (ms_ba_window_lists, ms_ba_window_apply) ---------------------------------------------
+// The EdgeSE3Expmap edges of a window (the odometry chain of bundle_adjuster.cpp:296-311 and the loop closures of :314-319): they read odometry
+// data that no table holds, so the caller fills edgeI / edgeJ / edgeMeas / edgeInfo of the window, given the local keyframes' slots in pose
+// order (descending KfId; vertex k of the window is localSlots[k]).
+using PoseEdgeBuilder = std::function<void(const std::vector<std::int32_t> &localSlots, BaWindow &window)>;
+
+// What localBundleAdjustOnTables did: which stage ended it (NONE: one of the early-outs of :235-240, nothing solved and nothing written),
+// the local keyframes' slots in pose order, localMapPoints as table rows (the reference's return value, :393) and the erased observations in
+// edge order -- what keyPointToTrackId.erase (keyframe.cpp:285) and the host copies are derived from.
+struct LocalBaOnTables {
+    BaStats::Ba stage = BaStats::Ba::NONE;
+    BaOutcome outcome;
+    std::vector<std::int32_t> localSlots, localRows;
+    std::size_t currentFrameMapPoints = 0, edgeCount = 0;
+    struct Erased { std::int32_t edge, slot, keyPoint, row; };
+    std::vector<Erased> erased;
+};
+
+namespace detail {
+// localKeyframes of :177-193 as slots, descending KfId: the current keyframe, the adjacent ones and the seven newest of the map (the loop
+// inserts, then breaks at i > 5)
+inline std::vector<std::int32_t> local_keyframes(const std::vector<std::int32_t> &kfIds, std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots) {
+    const std::size_t nKf = kfIds.size();
+    std::vector<char> local(nKf, 0);
+    auto insert = [&](std::int32_t s) {
+        if (s < 0 || (std::size_t)s >= nKf || kfIds[s] < 0) throw std::invalid_argument("localBundleAdjustOnTables: slot " + std::to_string(s) + " holds no keyframe");
+        local[s] = 1;
+    };
+    insert(currentSlot);
+    for (std::int32_t s : adjacentSlots) insert(s);
+    std::vector<std::int32_t> byId;
+    for (std::size_t s = 0; s < nKf; ++s) if (kfIds[s] >= 0) byId.push_back((std::int32_t)s);
+    std::sort(byId.begin(), byId.end(), [&](std::int32_t a, std::int32_t b) { return kfIds[a] > kfIds[b]; });
+    for (std::size_t i = 0; i < byId.size() && i < 7; ++i) local[byId[i]] = 1;
+    std::vector<std::int32_t> out;
+    for (std::int32_t s : byId) if (local[s]) out.push_back(s);
+    return out;
+}
+}  // namespace detail
+
+// localBundleAdjust (bundle_adjuster.cpp:141-394) for the keyframe in currentSlot with nothing walked on the host: the local keyframes
+// (:177-193), ms_map_point_union -> ms_observation_lists -> ms_ba_window_lists for the window (:214-290), the early-outs of :235-240, the
+// existing two-stage localBundleAdjust on the gathered window, then ms_ba_window_apply in the mode the stage dictates (:326-331 or :376-390).
+// adjacentSlots = computeAdjacentKeyframes(minCovisibilities 15, problemMaxSize) as slots; chain.id = the KfId per slot, -1 for an empty one.
+// observationCount: DEVICE [mapPointCount], the whole-map counts the chain keeps current (observationCountsOnDevice).  `lists` is scratch and
+// holds the window's lists afterwards.  The mirror's localBundleAdjust reports the outliers, not their chi2, so the apply step is handed
+// +inf for an outlier and 0 otherwise.  frames (slot -> DeviceKeyframe, may be null): the "no map point" masks of the slots that lost an
+// observation are renewed with unboundMasks.
+inline LocalBaOnTables localBundleAdjustOnTables(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &kfTable, DeviceMapPoints &table, DeviceMapPointFlags &flags,
+                                                 const DeviceKeypointTable &kpTable, DeviceKeyframePoses &poses, const KeyframeCameras &cams, const KeyframeChain &chain,
+                                                 std::int32_t *observationCount, std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots,
+                                                 const PoseEdgeBuilder &edges, int problemMaxSize, const Parameters &parameters, const StaticSettings &settings,
+                                                 WorkspaceBA *workspace = nullptr, const std::vector<DeviceKeyframe *> *frames = nullptr) {
+    const std::size_t nKf = kfTable.size(), nMp = kfTable.mapPointCount();
+    if (chain.id.size() != nKf || cams.camera.size() != nKf || cams.focalLength.size() != nKf || poses.size() != nKf)
+        throw std::invalid_argument("localBundleAdjustOnTables: one KfId, camera, focal length and pose per slot");
+    if (table.size() != nMp || flags.size() < nMp || !observationCount) throw std::invalid_argument("localBundleAdjustOnTables: the map-point tables differ in size or the observation counts are missing");
+    LocalBaOnTables out;
+    out.localSlots = detail::local_keyframes(chain.id, currentSlot, adjacentSlots);
+    const std::vector<std::int32_t> &local = out.localSlots;
+    const std::int32_t current = (std::int32_t)(std::find(local.begin(), local.end(), currentSlot) - local.begin());
+    // localMapPoints and their observations, on the device
+    std::int32_t *unionRows = reinterpret_cast<std::int32_t *>(ctx.workspace(4 * nMp + 256));
+    const ms_union_problem problem{0, (std::int32_t)local.size(), -1, DeviceMapPointFlags::TRIANGULATED};
+    std::int32_t nUnion = 0;
+    ctx.check(ms_map_point_union(ctx.get(), kfTable.table(), (int)nKf, (int)kfTable.stride(), flags.flags(), (int)nMp, local.data(), (int)local.size(), &problem, 1, unionRows, nullptr,
+                                 &nUnion), "ms_map_point_union");
+    ObservationSelection sel;
+    sel.deviceRows = unionRows; sel.rowCount = (std::size_t)nUnion;
+    const int levels = (int)settings.levelSigmaSq.size();
+    lists.build(kfTable, kpTable, &flags, chain.id, {}, sel, levels);
+    const std::size_t nRows = lists.rowCount(), nObs = lists.observationCount();
+    const ms_obs_lists l = lists.lists();
+    out.localRows = lists.download(l.rows, nRows);
+    // the window: the edge arrays stay on the device for the apply step
+    const std::size_t pitch = (nObs + 63) / 64 * 64 + 64;
+    std::int32_t *edgeArrays = reinterpret_cast<std::int32_t *>(ctx.workspace(12 * pitch));
+    const ms_ba_window_dev window{edgeArrays, edgeArrays + pitch, edgeArrays + 2 * pitch};
+    BaWindow w;
+    w.poses.resize(local.size()); w.points.resize(nRows); w.obsPose.resize(nObs); w.obsPoint.resize(nObs); w.obsUv.resize(nObs); w.obsInfo.resize(nObs);
+    std::int32_t nEdge = 0, nCurrent = 0;
+    ctx.check(ms_ba_window_lists(ctx.get(), poses.pose(), (int)nKf, table.position(), (int)nMp, &l, (int)nRows, (int)nObs, local.data(), (int)local.size(), current,
+                                 cams.camera.data(), cams.focalLength.data(), settings.levelSigmaSq.data(), levels, w.poses[0].data(), nRows ? w.points[0].data() : nullptr,
+                                 w.obsPoint.data(), w.obsPose.data(), nObs ? w.obsUv[0].data() : nullptr, w.obsInfo.data(), (int)nRows, (int)nObs, &window, &nEdge, &nCurrent),
+              "ms_ba_window_lists");
+    out.currentFrameMapPoints = (std::size_t)nCurrent; out.edgeCount = (std::size_t)nEdge;
+    if (local.empty() || (unsigned)nCurrent < parameters.minVisibleMapPointsInCurrentFrameBA || local.size() < parameters.minKeyframesInBA) return out;      // :235-240
+    w.obsPose.resize((std::size_t)nEdge); w.obsPoint.resize((std::size_t)nEdge); w.obsUv.resize((std::size_t)nEdge); w.obsInfo.resize((std::size_t)nEdge);
+    w.currentKeyframe = current;
+    if (edges) edges(local, w);
+    const bool neighbourhood = !((unsigned)nCurrent < parameters.minVisibleMapPointsInNeighborhoodBA);         // :326
+    out.outcome = localBundleAdjust(ctx, w, problemMaxSize, parameters, neighbourhood, workspace);
+    out.stage = neighbourhood ? BaStats::Ba::LOCAL : BaStats::Ba::NEIGHBOR;
+    std::vector<double> chi2;
+    if (neighbourhood) {
+        chi2.resize((std::size_t)nEdge);
+        for (std::size_t e = 0; e < chi2.size(); ++e) chi2[e] = out.outcome.outlier[e] ? std::numeric_limits<double>::infinity() : 0.0;
+    }
+    std::vector<std::int32_t> erased((std::size_t)nEdge + 1);
+    std::int32_t nErased = 0, nStale = 0;
+    ctx.check(ms_ba_window_apply(ctx.get(), kfTable.mutableTable(), (int)nKf, (int)kfTable.stride(), table.mutablePosition(), flags.mutableFlags(), observationCount, (int)nMp,
+                                 poses.pose(), w.poses[0].data(), (int)w.poses.size(), nRows ? w.points[0].data() : nullptr, neighbourhood ? chi2.data() : nullptr, &window, nEdge,
+                                 l.rows, (int)nRows, local.data(), (int)local.size(), current, neighbourhood ? MS_BA_APPLY_LOCAL : MS_BA_APPLY_NEIGHBOR, erased.data(), nEdge,
+                                 &nErased, &nStale), "ms_ba_window_apply");
+    if (nErased > 0) {
+        const std::vector<std::int32_t> keyPoints = ctx.download(window.edge_kp, (std::size_t)nEdge);
+        std::vector<std::int32_t> touched;
+        for (std::int32_t i = 0; i < nErased; ++i) {
+            const std::int32_t e = erased[(std::size_t)i], slot = local[(std::size_t)w.obsPose[(std::size_t)e]];
+            out.erased.push_back({e, slot, keyPoints[(std::size_t)e], out.localRows[(std::size_t)w.obsPoint[(std::size_t)e]]});
+            if (std::find(touched.begin(), touched.end(), slot) == touched.end()) touched.push_back(slot);
+        }
+        if (frames) unboundMasks(ctx, kfTable, touched, *frames);
     }
     return out;
 }

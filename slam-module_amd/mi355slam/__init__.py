@@ -1787,6 +1787,129 @@ class KeyframeTable:
                 lists.free()
         return out
 
+    def ba_window_lists_device(self, table, poses, lists, n_rows, n_obs, local_slot, current_index, cams, focal, level_sigma_sq, edges, out, cap_point=None,
+                               cap_edge=None):
+        """ms_ba_window_lists: the observation lists `lists` (n_rows, n_obs; an ObservationLists as observation_lists_device left it for the
+        rows of a map_point_union over the local slots with require = 1) as the arrays of a BA problem.  table = the MapPointTable, poses =
+        the KeyframePoseTable; local_slot = the local keyframes' slots by descending KfId, current_index the current one's position among
+        them; cams [n_kf, 6], focal [n_kf] per slot.  edges = a BaWindowEdges (the edges' table entries, left on the device for
+        ba_window_apply); out = dict of HOST arrays pose [n_local, 7], point [cap_point, 3], obs_uv [cap_edge, 2], obs_info float64 and
+        obs_point, obs_pose int32 [cap_edge] (the capacities default to the arrays' and the edge buffers' sizes).  Returns
+        (rc, n_edge, n_current) without raising: MS_ERR_CAPACITY still reports the needed counts."""
+        local_slot, focal = _i32(local_slot), _i32(focal)
+        cam_rows = np.asarray(cams, np.float64).reshape(-1, 6)
+        if len(cam_rows) != poses.n or len(focal) != poses.n or poses.n != self.n_kf:
+            raise ValueError("ba_window_lists: one pose, one camera and one focal length per keyframe slot")
+        K = (Pinhole * max(poses.n, 1))(*[Pinhole(c[0], c[1], c[2], c[3], int(c[4]), int(c[5])) for c in cam_rows])
+        sig = np.ascontiguousarray(level_sigma_sq, np.float32).reshape(-1)
+        for k, dt in (("pose", np.float64), ("point", np.float64), ("obs_uv", np.float64), ("obs_info", np.float64), ("obs_point", np.int32), ("obs_pose", np.int32)):
+            if out[k].dtype != dt or not out[k].flags["C_CONTIGUOUS"]:
+                raise ValueError("ba_window_lists: out[%r] must be a contiguous %s array" % (k, np.dtype(dt).name))
+        if out["pose"].size < 7 * len(local_slot):
+            raise ValueError("ba_window_lists: out['pose'] holds fewer than %d poses" % len(local_slot))
+        cap_point = out["point"].size // 3 if cap_point is None else int(cap_point)
+        cap_edge = min(edges.cap_edge, out["obs_point"].size, out["obs_pose"].size, out["obs_uv"].size // 2, out["obs_info"].size) if cap_edge is None else int(cap_edge)
+        L, Wd = lists.struct(True, True, True), edges.struct()
+        n_edge, n_current = C.c_int32(0), C.c_int32(0)
+        rc = lib().ms_ba_window_lists(self.ctx._h, _vp(poses.pose), poses.n, _vp(table.pos), table.n, C.byref(L), int(n_rows), int(n_obs), _vp(local_slot), len(local_slot),
+                                      int(current_index), K, _vp(focal), _vp(sig), len(sig), _vp(out["pose"]), _vp(out["point"]), _vp(out["obs_point"]), _vp(out["obs_pose"]),
+                                      _vp(out["obs_uv"]), _vp(out["obs_info"]), cap_point, cap_edge, C.byref(Wd), C.byref(n_edge), C.byref(n_current))
+        return rc, n_edge.value, n_current.value
+
+    def ba_window(self, table, poses, flags, kp, kf_id, local_slot, current_index, cams, focal, level_sigma_sq, lists=None, edges=None):
+        """The local BA window of localBundleAdjust (bundle_adjuster.cpp:214-290) from the device tables: map_point_union over local_slot
+        with require = 1, observation_lists of its rows, ms_ba_window_lists.  flags = a DevBuf of [n_mp] uint8; kp = the KeypointTable;
+        lists / edges (an ObservationLists / a BaWindowEdges) are allocated here when None and regrown when a call reports
+        MS_ERR_CAPACITY.  Returns a dict: pose, point, obs_point, obs_pose, obs_uv, obs_info (the arrays of the BA problem), n_rows, n_obs,
+        n_edge, n_current, local_slot, current_index, and lists / edges, which ba_window_apply reads on the device."""
+        local_slot = _i32(local_slot)
+        n_mp = table.n
+        d_rows = self.ctx.alloc(4 * max(n_mp, 1))
+        try:
+            n_in = int(self.map_point_union_device(local_slot, [(0, len(local_slot), -1, 1)], n_mp, flags, d_rows, None)[0])
+            if lists is None:
+                lists = ObservationLists(self.ctx, max(n_in, 1), max(4 * n_in, 1))
+            sel = dict(source=OBS_FROM_ROWS, rows_in=d_rows, n_in=n_in)
+            n_rows, n_obs = self._lists_of(lists, kf_id, n_mp, sel, kp, None, flags, len(np.asarray(level_sigma_sq).reshape(-1)))
+        finally:
+            d_rows.free()
+        if edges is None:
+            edges = BaWindowEdges(self.ctx, max(n_obs, 1))
+        elif edges.cap_edge < n_obs:
+            edges.grow(n_obs)                                # n_edge <= n_obs: once is enough
+        out = dict(pose=np.zeros((len(local_slot), 7)), point=np.zeros((n_rows, 3)), obs_point=np.zeros(n_obs, np.int32), obs_pose=np.zeros(n_obs, np.int32),
+                   obs_uv=np.zeros((n_obs, 2)), obs_info=np.zeros(n_obs))
+        rc, n_edge, n_current = self.ba_window_lists_device(table, poses, lists, n_rows, n_obs, local_slot, current_index, cams, focal, level_sigma_sq, edges, out,
+                                                            cap_point=n_rows, cap_edge=n_obs)
+        self.ctx.check(rc, "ms_ba_window_lists")
+        for k in ("obs_point", "obs_pose", "obs_uv", "obs_info"):
+            out[k] = out[k][:n_edge]
+        out.update(n_rows=n_rows, n_obs=n_obs, n_edge=n_edge, n_current=n_current, local_slot=local_slot, current_index=int(current_index), lists=lists, edges=edges)
+        return out
+
+    def ba_window_apply(self, table, poses, flags, n_obs, window, pose, point, chi2, mode, cap_erased=None, erased_edge=None):
+        """ms_ba_window_apply: the arrays ms_ba_download returned (pose [n_pose, 7], point [n_rows, 3], chi2 [n_edge] or None) into the
+        tables, in place -- this KeyframeTable, the MapPointTable's positions, the KeyframePoseTable, flags (uint8) and n_obs (int32)
+        DevBufs of [n_mp].  window = what ba_window returned (or a dict with lists, edges, n_rows, n_edge, local_slot, current_index).
+        mode = BA_APPLY_LOCAL (outliers erased, UNSURE demotion, every position and every local pose) or BA_APPLY_NEIGHBOR (the positions
+        and the current keyframe's pose).  erased_edge = the caller's int32 array (tests) or None.  Returns (rc, erased_edge [n_erased],
+        n_stale) without raising; on MS_ERR_CAPACITY the second is the needed count."""
+        pose, point = np.ascontiguousarray(pose, np.float64).reshape(-1, 7), np.ascontiguousarray(point, np.float64).reshape(-1, 3)
+        chi2 = None if chi2 is None else np.ascontiguousarray(chi2, np.float64).reshape(-1)
+        n_edge, n_rows, local_slot = int(window["n_edge"]), int(window["n_rows"]), _i32(window["local_slot"])
+        if len(point) != n_rows or (chi2 is not None and len(chi2) != n_edge):
+            raise ValueError("ba_window_apply: %d points and %s chi2 values for a window of %d rows and %d edges" % (len(point), "no" if chi2 is None else len(chi2), n_rows, n_edge))
+        if erased_edge is None:
+            erased_edge = np.zeros(max(n_edge if cap_erased is None else int(cap_erased), 1), np.int32)
+        cap_erased = min(n_edge, len(erased_edge)) if cap_erased is None else int(cap_erased)
+        Wd = window["edges"].struct()
+        n_erased, n_stale = C.c_int32(0), C.c_int32(0)
+        rc = lib().ms_ba_window_apply(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(table.pos), _vp(flags), _vp(n_obs), table.n, _vp(poses.pose), _vp(pose),
+                                      len(pose), _vp(point), _vp(chi2), C.byref(Wd), n_edge, _vp(window["lists"]["rows"]), n_rows, _vp(local_slot), len(local_slot),
+                                      int(window["current_index"]), int(mode), _vp(erased_edge), cap_erased, C.byref(n_erased), C.byref(n_stale))
+        if rc == MS_ERR_CAPACITY:
+            return rc, n_erased.value, n_stale.value
+        return rc, erased_edge[:n_erased.value], n_stale.value
+
+
+BA_APPLY_LOCAL, BA_APPLY_NEIGHBOR = 0, 1
+
+
+class BaWindowDevC(C.Structure):
+    """ms_ba_window_dev: device pointers."""
+    _fields_ = [(k, C.c_void_p) for k in ("edge_slot", "edge_kp", "edge_point")]
+
+
+class BaWindowEdges:
+    """The device buffers of ms_ba_window_dev for up to cap_edge edges (reusable across windows; grow() reallocates)."""
+    _NAMES = ("edge_slot", "edge_kp", "edge_point")
+
+    def __init__(self, ctx, cap_edge, guard=0):
+        self.ctx, self.guard = ctx, int(guard)               # guard: bytes kept behind every buffer (tests look at them)
+        self.cap_edge = 0
+        self._bufs = {}
+        self.grow(cap_edge)
+
+    def grow(self, cap_edge):
+        self.free()
+        self.cap_edge = int(cap_edge)
+        for name in self._NAMES:
+            self._bufs[name] = self.ctx.alloc(4 * self.cap_edge + self.guard + 16)
+
+    def __getitem__(self, name):
+        return self._bufs[name]
+
+    def struct(self):
+        return BaWindowDevC(*[self._bufs[k].ptr for k in self._NAMES])
+
+    def download(self, n_edge):
+        return {k: self._bufs[k].download(np.int32, (n_edge,)) if n_edge else np.zeros(0, np.int32) for k in self._NAMES}
+
+    def free(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
+
 
 def create_E21(R1, t1, R2, t2):
     """create_E_21 (openvslam/essential_solver.cc:157-162) with the host mirror's order of operations: [t21]x R21, R21 = R2 R1^T,
