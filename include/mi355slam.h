@@ -1168,6 +1168,61 @@ int ms_unbound_mask(ms_ctx *ctx, const int32_t *kf_mp, int n_kf, int stride, int
 int ms_unbound_mask_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *slots, const int32_t *n_kp,
     uint8_t *const *usable, int n_slots, char *why, size_t why_bytes);
 
+/* ---- matchLocalMapPoints on the device map tables -------------------------------------------------------------------------
+ * The walk of searchByProjection (keyframe_matcher.cpp:349-389) behind ms_project_gate (MS_GATE_SEARCH) and ms_projection_topk, with both
+ * addObservations (:388-389) written where the tables lie.  tests/search_bind_ref.py restates it twice and is its specification.
+ *
+ * ms_bound_mask: skip[j] = ((uint32)kf_mp[slot * stride + j] < n_mp) for j < n_kp -- the keypoints of the slot that carry a map point
+ * (:358; a valid entry of the tables always has n_obs >= 1, so the reference's second condition is implied).  One launch on a DEVICE uint8
+ * array, in stream order: it is the t_skip of ms_projection_topk, and the complement of ms_unbound_mask for one slot.
+ *
+ * ms_search_bind: kept_entry, q_*, top_*, n_scored are what ms_project_gate and ms_projection_topk left for ONE view, given as the scoring got
+ * them (element 0 = the view's first kept query; kept_entry holds positions of mp_index, inside [first, first + count)); skip is the mask that
+ * scoring used; sorted_x .. t_octave, n_kp are the keyframe as the scoring got it; mp_index (HOST) is the gate's array, of which entries
+ * [first, first + count) are read; slot = K, the keyframe's slot.  q_min_octave and q_max_octave may each be NULL (no window on that side).
+ * Walk the kept queries q = 0 .. n_kept - 1 in order, e = kept_entry[q], m = mp_index[e], `taken` = the keypoints bound earlier in this call:
+ *   an empty list (top_idx[4q] < 0) is outcome 0 and top_dist[4q] > 100 is outcome 1 without looking further (every candidate is at least that far);
+ *   else best and second = the first two entries of top_idx[4q ..] that are >= 0 and not taken, with their top_dist and top_octave;
+ *   fewer than two and n_scored[q] > 4: the radius query of ms_projection_topk again (same float32 arithmetic), over the keypoints not in skip,
+ *     not taken and inside the octave window; best and second = the two smallest by (distance, position in the sorted array);
+ *   no best -> 0; bestDist > 100 -> 1; bestLevel == bestLevel2 && bestDist > 0.8 * bestDist2 (float64) -> 2; else bind: kf_mp[K][best] = m,
+ *     n_obs[m] += 1, match_kp[e - first] = best, best is taken, usable[best] = 0: outcome 3 from the list, 4 after a rescan.  A rescan that
+ *     binds nothing reports 0, 1 or 2 with bit 3 set (8, 9, 10).
+ * Outputs: match_kp (DEVICE int32 [count], per ENTRY of the slice, -1 for none), outcome (DEVICE uint8 [count], per kept QUERY; entries from
+ * n_kept on are 0), usable (DEVICE uint8 [n_kp], K's matcher mask, cleared at each bound keypoint as ms_create_points_bind does) -- each may be
+ * NULL; n_matched and counts[6] (HOST): counts[c] for c < 5 = the queries with outcome & 7 == c, counts[5] = the rescans.
+ * A pre-pass on the device counts violations: a kept_entry outside the slice; a top_idx outside [-1, n_kp) or marked by skip; skip[j]
+ * disagreeing with kf_mp[K][j]; a row m that is not live, that K already lists, or that two kept queries name.  Any of them returns
+ * MS_ERR_INVALID with kf_mp and n_obs bit-identical (match_kp and outcome hold their defaults).  MS_ERR_INVALID before any device call: slot
+ * outside [0, n_kf); n_kp > stride; n_kept > count; an mp_index of the slice outside [0, n_mp); descriptors not 16-byte aligned; stride < 1; a
+ * negative size; a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps and for a slice that ends at or beyond MS_GATE_MAX_ENTRIES.
+ * n_kept = 0 and count = 0 are fine.  Four launches, one upload (the slice of mp_index), one download; synchronous.  The same input gives the
+ * same bits on every call; the workspace belongs to the context and only grows (ms_debug_host_allocs).  The *_check twins are the host
+ * validation alone (no context, no device; `why` receives the message). */
+int ms_bound_mask(ms_ctx *ctx, const int32_t *kf_mp, int n_kf, int stride, int n_mp, int slot, int n_kp,
+    /* DEVICE [n_kp] */
+    uint8_t *skip);
+int ms_bound_mask_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, int slot, int n_kp, const uint8_t *skip, char *why, size_t why_bytes);
+int ms_search_bind(ms_ctx *ctx,
+    /* DEVICE tables: kf_mp and n_obs are updated in place, mp_live is read */
+    int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int32_t *n_obs, int n_mp,
+    /* DEVICE, one view's lists where the gate and the scoring left them, and the mask that scoring used */
+    const int32_t *kept_entry, const float *q_x, const float *q_y, const float *q_radius, const int32_t *q_min_octave, const int32_t *q_max_octave,
+    const uint32_t *q_desc, const int32_t *top_idx, const uint16_t *top_dist, const int32_t *top_octave, const int32_t *n_scored, const uint8_t *skip,
+    /* DEVICE, the keyframe */
+    const float *sorted_x, const float *sorted_y, const int32_t *sorted_idx, const uint32_t *t_desc, const int32_t *t_octave, int n_kp,
+    /* HOST */
+    const int32_t *mp_index, int first, int count, int n_kept, int slot,
+    /* DEVICE, each may be NULL */
+    int32_t *match_kp, uint8_t *outcome, uint8_t *usable,
+    /* HOST */
+    int32_t *n_matched, int32_t *counts);
+int ms_search_bind_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const int32_t *n_obs, int n_mp,
+    const int32_t *kept_entry, const float *q_x, const float *q_y, const float *q_radius, const int32_t *q_min_octave, const int32_t *q_max_octave,
+    const uint32_t *q_desc, const int32_t *top_idx, const uint16_t *top_dist, const int32_t *top_octave, const int32_t *n_scored, const uint8_t *skip,
+    const float *sorted_x, const float *sorted_y, const int32_t *sorted_idx, const uint32_t *t_desc, const int32_t *t_octave, int n_kp,
+    const int32_t *mp_index, int first, int count, int n_kept, int slot, const int32_t *n_matched, const int32_t *counts, char *why, size_t why_bytes);
+
 /* ---- the local BA window on the device map tables ------------------------------------------------------------------------
  * The two steps of localBundleAdjust (bundle_adjuster.cpp:141-394) around the solve that walk MapPoint::observations and Keyframe::mapPoints:
  * building the graph's vertices and projection edges (:245-290) and writing the result back (:376-390, or :326-331 when the neighbourhood

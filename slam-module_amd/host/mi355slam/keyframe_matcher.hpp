@@ -509,10 +509,23 @@ struct DeviceGatedLists {
     const std::int32_t *keptEntry = nullptr, *topIdx = nullptr;
     const std::uint16_t *topDist = nullptr;
     unsigned char *extra = nullptr;
+    // the rest of what the two kernels left, for ms_search_bind (searchByProjectionOnTables)
+    const float *qX = nullptr, *qY = nullptr, *qRadius = nullptr;
+    const std::int32_t *qMinOctave = nullptr, *qMaxOctave = nullptr, *topOctave = nullptr, *nScored = nullptr;
+    const std::uint32_t *qDesc = nullptr;
+    const std::uint8_t *skip = nullptr;                      // the mask the scoring used (BoundMaskSource), or null
+};
+// searchByProjection's bound mask taken from the DEVICE keyframe table: slot's row of kfMp [nKf x stride] over nMp map points (ms_bound_mask)
+struct BoundMaskSource {
+    const std::int32_t *kfMp = nullptr;
+    std::size_t nKf = 0, stride = 0, nMp = 0;
+    std::int32_t slot = 0;
 };
 
+// bound (optional) = where searchByProjection's skip mask comes from: it is written into the same block by ms_bound_mask, in stream order in
+// front of the scoring, and the scoring of every view reads it (used with one view, whose keyframe sits in bound->slot).
 inline DeviceGatedLists gate_and_score_device(Context &ctx, const DeviceMapPoints &table, const std::vector<GateView> &views, const std::vector<const DeviceKeyframe *> &kfs,
-                                              const StaticSettings &settings, std::size_t extraBytesPerEntry) {
+                                              const StaticSettings &settings, std::size_t extraBytesPerEntry, const BoundMaskSource *bound = nullptr) {
     std::vector<ms_gate_view> V;
     DeviceGatedLists g;
     pack_views(views, V, g.index);
@@ -520,11 +533,18 @@ inline DeviceGatedLists gate_and_score_device(Context &ctx, const DeviceMapPoint
     g.nKept.assign(views.size(), 0);
     for (const ms_gate_view &v : V) { g.first.push_back(v.first); g.count.push_back(v.count); }
     const std::size_t oX = 0, oY = oX + sec, oR = oY + sec, oLo = oR + sec, oHi = oLo + sec, oD = oHi + sec, oE = oD + 32 * ne;
-    const std::size_t oTi = oE + sec, oTo = oTi + 16 * ne, oN = oTo + 16 * ne, oTd = oN + sec, oX2 = oTd + pad16(8 * ne), total = oX2 + pad16(extraBytesPerEntry * ne);
+    const std::size_t oTi = oE + sec, oTo = oTi + 16 * ne, oN = oTo + 16 * ne, oTd = oN + sec, oX2 = oTd + pad16(8 * ne);
+    const std::size_t nSkip = bound && !kfs.empty() ? (std::size_t)kfs[0]->frame().n : 0, oK = oX2 + pad16(extraBytesPerEntry * ne), total = oK + pad16(nSkip);
     unsigned char *ws = ctx.workspace(total + 16);
     auto F = [&](std::size_t o) { return reinterpret_cast<float *>(ws + o); };
     auto I = [&](std::size_t o) { return reinterpret_cast<std::int32_t *>(ws + o); };
     g.keptEntry = I(oE); g.topIdx = I(oTi); g.topDist = reinterpret_cast<const std::uint16_t *>(ws + oTd); g.extra = ws + oX2;
+    g.qX = F(oX); g.qY = F(oY); g.qRadius = F(oR); g.qMinOctave = I(oLo); g.qMaxOctave = I(oHi); g.qDesc = reinterpret_cast<const std::uint32_t *>(ws + oD);
+    g.topOctave = I(oTo); g.nScored = I(oN);
+    if (bound) {
+        g.skip = ws + oK;
+        ctx.check(ms_bound_mask(ctx.get(), bound->kfMp, (int)bound->nKf, (int)bound->stride, (int)bound->nMp, bound->slot, (int)nSkip, ws + oK), "ms_bound_mask");
+    }
     ctx.check(ms_project_gate(ctx.get(), table.position(), table.norm(), table.minDistance(), table.maxDistance(), table.descriptor(), (int)table.size(),
                               g.index.data(), (int)ne, V.data(), (int)V.size(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(),
                               settings.parameters.orbScaleFactor, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, I(oE), F(oX), F(oY), F(oR), I(oLo), I(oHi),
@@ -532,13 +552,44 @@ inline DeviceGatedLists gate_and_score_device(Context &ctx, const DeviceMapPoint
     for (std::size_t v = 0; v < V.size() && ne; ++v) {
         const std::size_t f = (std::size_t)V[v].first;
         const ms_match_frame &fr = kfs[v]->frame();
-        ctx.check(ms_projection_topk(ctx.get(), kfs[v]->sortedX(), kfs[v]->sortedY(), kfs[v]->sortedIndex(), fr.n, fr.desc, fr.octave, nullptr,
+        ctx.check(ms_projection_topk(ctx.get(), kfs[v]->sortedX(), kfs[v]->sortedY(), kfs[v]->sortedIndex(), fr.n, fr.desc, fr.octave, g.skip,
                                      F(oX) + f, F(oY) + f, F(oR) + f, I(oLo) + f, I(oHi) + f, reinterpret_cast<const std::uint32_t *>(ws + oD) + 8 * f, g.nKept[v],
                                      I(oTi) + 4 * f, reinterpret_cast<std::uint16_t *>(ws + oTd) + 4 * f, I(oTo) + 4 * f, I(oN) + f, nullptr), "ms_projection_topk");
     }
     return g;
 }
 }  // namespace detail
+
+// What searchByProjectionOnTables returns: the match count, the queries per outcome code of ms_search_bind (counts[5] = the rescans) and, on
+// request, per entry of view.indices the matched keypoint or -1.
+struct SearchBindResult {
+    unsigned matched = 0;
+    std::array<std::int32_t, 6> counts{};
+    std::vector<std::int32_t> matchKp;
+};
+
+// searchByProjection (keyframe_matcher.cpp:295-414) over table rows with the walk and both addObservations (:388-389) on the device tables:
+// ms_bound_mask (slot's row of kfMp -> the scoring's skip mask) -> gates -> scoring -> ms_search_bind on the lists where they lie.  kfMp
+// [nKf x stride], mpLive, nObs [nMp] are the DEVICE tables; kf is the keyframe in `slot`; usable (optional) = its DEVICE matcher mask
+// (DeviceKeyframe::mutableUsable), cleared at each bound keypoint.  view as for searchByProjection.  Nothing comes down but the gate's n_kept
+// and the result block (and match_kp when asked for).
+inline SearchBindResult searchByProjectionOnTables(Context &ctx, const DeviceKeyframe &kf, const DeviceMapPoints &table, const GateView &view, std::int32_t *kfMp,
+                                                   std::size_t nKf, std::size_t stride, const std::uint8_t *mpLive, std::int32_t *nObs, std::size_t nMp, std::int32_t slot,
+                                                   const StaticSettings &settings, std::uint8_t *usable = nullptr, bool wantMatches = false) {
+    SearchBindResult out;
+    const std::size_t nKp = (std::size_t)kf.frame().n, ne = view.indices.size();
+    const detail::BoundMaskSource bound{kfMp, nKf, stride, nMp, slot};
+    const detail::DeviceGatedLists g = detail::gate_and_score_device(ctx, table, {view}, {&kf}, settings, wantMatches ? 4 : 0, &bound);
+    std::int32_t *matchKp = wantMatches && ne ? reinterpret_cast<std::int32_t *>(g.extra) : nullptr;
+    std::int32_t n = 0;
+    const ms_match_frame &f = kf.frame();
+    ctx.check(ms_search_bind(ctx.get(), kfMp, (int)nKf, (int)stride, mpLive, nObs, (int)nMp, g.keptEntry, g.qX, g.qY, g.qRadius, g.qMinOctave, g.qMaxOctave, g.qDesc, g.topIdx,
+                             g.topDist, g.topOctave, g.nScored, g.skip, kf.sortedX(), kf.sortedY(), kf.sortedIndex(), f.desc, f.octave, (int)nKp, g.index.data(),
+                             g.first[0], g.count[0], g.nKept[0], slot, matchKp, nullptr, usable, &n, out.counts.data()), "ms_search_bind");
+    out.matched = (unsigned)n;
+    if (matchKp) out.matchKp = ctx.download(matchKp, ne);
+    return out;
+}
 
 // Keyframe::isInFrustum (keyframe.cpp:247-262) for many map points at once: reprojection, viewing distance and viewing angle of the table rows
 // `indices` against one pose and camera.

@@ -1,7 +1,7 @@
 // map_update.hpp -- the operations of the host mirror on the device-resident map (map_tables.hpp), with their argument and result structs:
 // loop correction (correctLoop), triangulation (triangulateMapPoints), covisibility (getNeighbors, computeAdjacentKeyframes, localMapPoints),
 // culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
-// fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), createNewMapPoints and the local
+// fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), matchLocalMapPoints, createNewMapPoints and the local
 // bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables).
 // Results come back through Context::workspace and Context::download; nothing here owns device memory.
 #pragma once
@@ -186,7 +186,8 @@ inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, const De
 // The ordered union of the map points of a list of keyframes: rows ascending (the std::set / std::map walk) and, for each, the first
 // position of the list whose keyframe lists it (localMapPoints.emplace of loop_closer.cpp:430-432) -- LoopPoints as it stands.
 //   matchLocalMapPoints (mapper_helpers.cpp:241-261)   localMapPoints(ctx, table, &flags, adjacentSlots, currentSlot, DeviceMapPointFlags::USABLE).row
-//                                                      is GateView::indices in front of isInFrustum
+//                                                      is GateView::indices of the SEARCH view that matchLocalMapPoints (below) gates, scores
+//                                                      and binds on the device (searchByProjectionOnTables)
 //   deduplicateMapPoints (:337-345), searchAndDeduplicate (loop_closer.cpp:569-584)   exclude = -1, require = 0
 //   correctLoop (:418-433, :465-469)                   keyframes = LoopCorrections::slot; the result is its LoopPoints
 inline LoopPoints localMapPoints(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &keyframes,
@@ -789,6 +790,27 @@ inline FuseResult searchAndDeduplicate(Context &ctx, const DeviceMapPoints &mapP
     if (!rows.empty() && !rigidlyTransformed.empty())
         detail::fuse_batch(ctx, mapPoints, T, rigidlyTransformed.data(), rigidlyTransformed.size(), rows, 4.0f, -1, settings, out);
     return out;
+}
+
+// ---- matchLocalMapPoints on the device tables (ms_bound_mask, ms_search_bind) ----------------------------------------------------------
+// matchLocalMapPoints (mapper_helpers.cpp:231-269) for the keyframe `current`: the usable rows of the adjacent keyframes that the current one
+// does not list yet (:241-261; they come down once, as the gate takes its rows from the host), then ONE MS_GATE_SEARCH view with
+// viewAngleLimitCos 0.5 (:304) and searchByProjection with the walk and both addObservations on the tables (searchByProjectionOnTables): the
+// top-4 lists and the query arrays stay on the device, and neither the current keyframe's row of kf_mp nor n_obs is uploaded afterwards.
+// T.observationCount stays current.  usable (optional) = current.features' DEVICE matcher mask (DeviceKeyframe::mutableUsable), cleared at each
+// bound keypoint.  Returns at once on an empty list (:263).
+inline SearchBindResult matchLocalMapPoints(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables T, const FuseKeyframe &current,
+                                            const std::vector<std::int32_t> &adjacentSlots, float threshold, const StaticSettings &settings, std::uint8_t *usable = nullptr,
+                                            bool wantMatches = false) {
+    detail::check_fuse_tables(T, "matchLocalMapPoints");
+    if (current.slot < 0 || (std::size_t)current.slot >= T.table.size() || !current.features) throw std::invalid_argument("matchLocalMapPoints: current keyframe outside the table");
+    GateView view;
+    view.indices = localMapPoints(ctx, T.table, &T.flags, adjacentSlots, current.slot, DeviceMapPointFlags::USABLE, false).row;
+    if (view.indices.empty()) return SearchBindResult{};
+    std::copy(current.R, current.R + 9, view.R); std::copy(current.t, current.t + 3, view.t);
+    view.camera = current.camera; view.threshold = threshold; view.cosLimit = 0.5f; view.mode = MS_GATE_SEARCH;
+    return searchByProjectionOnTables(ctx, *current.features, mapPoints, view, T.table.mutableTable(), T.table.size(), T.table.stride(), T.live.live(), T.observationCount,
+                                      T.table.mapPointCount(), current.slot, settings, usable, wantMatches);
 }
 
 // "Merge moved map points", loop_closer.cpp:531-546: loopClosure.mapPointMatches as (first, second) table rows, in order.  outcome per pair:

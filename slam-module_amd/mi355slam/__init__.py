@@ -1193,6 +1193,30 @@ class FuseViewC(C.Structure):
     _fields_ = [("slot", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
 
 
+class SearchBindArgs:
+    """The arguments of KeyframeTable.search_bind (ms_search_bind).  Device arrays are DevBufs, device addresses (int) or None:
+    mp_live, n_obs [n_mp]; kept_entry, q_x, q_y, q_radius, q_min_octave, q_max_octave, q_desc, top_idx, top_dist, top_octave, n_scored as
+    ms_project_gate and ms_projection_topk left them for ONE view (element 0 = its first kept query); skip = the mask that scoring used;
+    kf = the view's ProjectionKeyframe; match_kp, outcome [count], usable [kf.n] = the optional outputs.  Host: mp_index (the gate's
+    array), first, count, n_kept, slot, n_mp."""
+    FIELDS = ("mp_live", "n_obs", "n_mp", "kept_entry", "q_x", "q_y", "q_radius", "q_min_octave", "q_max_octave", "q_desc", "top_idx", "top_dist", "top_octave",
+              "n_scored", "skip", "kf", "mp_index", "first", "count", "n_kept", "slot", "match_kp", "outcome", "usable")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.pop(k, None))
+        if kw:
+            raise TypeError("SearchBindArgs: unknown fields %s" % sorted(kw))
+
+
+class SearchBindResult:
+    """n_matched and counts [6] of ms_search_bind: counts[c] for c < 5 = the kept queries with outcome & 7 == c (0 no candidate, 1 too far,
+    2 ratio, 3 bound from the list, 4 bound after a rescan), counts[5] = the rescans."""
+
+    def __init__(self, n_matched, counts):
+        self.n_matched, self.counts = int(n_matched), counts
+
+
 def _download_i32_at(buf, byte_offset, n):
     """n int32 from byte_offset of a DevBuf."""
     a = np.zeros(max(n, 1), np.int32)
@@ -1724,6 +1748,24 @@ class KeyframeTable:
             raise ValueError("one keypoint count and one mask per slot")
         ptrs = (C.c_void_p * max(len(slots), 1))(*[m.ptr for m in masks])
         self.ctx.check(lib().ms_unbound_mask(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, int(n_mp), _vp(slots), _vp(n_kp), ptrs, len(slots)), "ms_unbound_mask")
+
+    def bound_mask(self, slot, n_kp, n_mp, skip):
+        """ms_bound_mask: skip (a DevBuf or device address of n_kp bytes) = 1 where keypoint j of `slot` carries a map point -- the t_skip of
+        ms_projection_topk for searchByProjection, from this table, in stream order."""
+        self.ctx.check(lib().ms_bound_mask(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, int(n_mp), int(slot), int(n_kp), _vp(skip)), "ms_bound_mask")
+
+    def search_bind(self, a):
+        """ms_search_bind on this table in place: the walk of searchByProjection over one view's gated and scored queries with both
+        addObservations.  a: a SearchBindArgs.  Returns a SearchBindResult; raises MsError when the call is turned away."""
+        mp_index = _i32(a.mp_index)
+        n, counts = C.c_int32(0), np.zeros(6, np.int32)
+        kf = a.kf
+        self.ctx.check(lib().ms_search_bind(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(a.mp_live), _vp(a.n_obs), int(a.n_mp), _vp(a.kept_entry), _vp(a.q_x),
+                                            _vp(a.q_y), _vp(a.q_radius), _vp(a.q_min_octave), _vp(a.q_max_octave), _vp(a.q_desc), _vp(a.top_idx), _vp(a.top_dist),
+                                            _vp(a.top_octave), _vp(a.n_scored), _vp(a.skip), _vp(kf.d_sx), _vp(kf.d_sy), _vp(kf.d_si), _vp(kf.d_desc), _vp(kf.d_oct),
+                                            int(kf.n), _vp(mp_index) if len(mp_index) else None, int(a.first), int(a.count), int(a.n_kept), int(a.slot),
+                                            _vp(a.match_kp), _vp(a.outcome), _vp(a.usable), C.byref(n), _vp(counts)), "ms_search_bind")
+        return SearchBindResult(n.value, counts)
 
     def create_points(self, table, flags, live, kp, pool, poses, kf_id, cams, focal, desc_base, current, adjacent, frames, free_rows, settings, scale_factors_, thr_deg,
                       mode=TRI_TME, n_obs=None, mp_track=None, lists=None, check_orientation=True, exact_capacity=False, pose_host=None):
