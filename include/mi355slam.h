@@ -609,6 +609,7 @@ int ms_loop_correct_check(const double *kf_pose, int n_kf, const double *mp_pos,
 #define MS_COVIS_MAX_STRIDE 8192
 #define MS_COVIS_MAX_QUERIES 4096               /* queries of ms_covisibility, problems of ms_map_point_union */
 #define MS_COVIS_MAX_MP (1 << 24)               /* n_mp stays BELOW this */
+#define MS_LOOP_MAX_CANDIDATES 4096             /* candidates of ms_loop_pairs and ms_loop_sim3_lists */
 #define MS_UNION_MAX_ENTRIES (1 << 20)          /* the problems' list slices together */
 typedef struct {
     int32_t slot, force_a, force_b, min_covis;
@@ -1319,6 +1320,99 @@ int ms_ba_window_apply_check(const int32_t *kf_mp, int n_kf, int stride, const d
     const double *kf_pose, const double *pose, int n_pose, const double *point, const double *chi2,
     const ms_ba_window_dev *window, int n_edge, const int32_t *rows, int n_rows, const int32_t *local_slot, int n_local, int current_index,
     int mode, const int32_t *erased_edge, int cap_erased, const int32_t *n_erased, const int32_t *n_stale, char *why, size_t why_bytes);
+
+/* ---- the loop closer's candidates on the device map tables -----------------------------------------------------------------
+ * The three pieces of LoopCloser::tryLoopClosure (loop_closer.cpp:126-378) between its batched solvers (ms_match_loop_closure, ms_loop_ransac,
+ * matchMapPointsSim3 on table rows, ms_sim3_optimize) that read MapDB::mapPoints, MapPoint::observations and Keyframe::mapPoints.  kf_mp,
+ * mp_flags, mp_live, mp_pos, kf_pose and the keypoint table kp_x / kp_y / kp_octave ([n_kf * stride], parallel to kf_mp) are those of
+ * 9.5 - 9.9: row r is PRESENT iff (uint32)r < n_mp and mp_live[r] != 0 (mp_live == NULL: every row is live); bit 0 of mp_flags is
+ * TRIANGULATED; kf_pose [n_kf * 12] = rows 0-2 of poseCW, row-major 3 x 4.  tests/loop_chain_ref.py restates all three and is their
+ * specification.  The camera-frame point of row r in slot k is, in float64 and evaluated as written (no contraction),
+ *   x_i = ((R[i][0] * p0 + R[i][1] * p1) + R[i][2] * p2) + t_i        R, t = kf_pose[k], p = mp_pos[r]
+ *
+ * ms_loop_usable_mask (keyframe_matcher.cpp:79-84, :94-96; :568-571): for n_slots slots in one launch, with r = kf_mp[slots[s] * stride + k]
+ * for k < n_kp[s]:   usable[s][k] = 1 iff r is present and (require_triangulated[s] == 0 or mp_flags[r] & 1), else 0;
+ *                    tri_row[s][k] = r iff r is present and mp_flags[r] & 1, else -1.
+ * usable is the M1 mask of ms_match_frame: the current keyframe's with require = requireTringulationForLoopClosures, a candidate's with
+ * require = 1 (:95); tri_row is the mps1 / mps2 argument of the table form of matchMapPointsSim3.  slots, n_kp, require_triangulated: HOST
+ * int32 [n_slots]; usable: HOST [n_slots] of DEVICE uint8 [n_kp[s]]; tri_row: HOST [n_slots] of DEVICE int32 [n_kp[s]], the array or any
+ * entry may be NULL.  Errors and caps are those of ms_unbound_mask; in addition mp_flags == NULL is MS_ERR_INVALID when any require is set
+ * or any tri_row is asked for.  One upload, one launch, synchronous.
+ *
+ * ms_loop_pairs (loop_closer.cpp:203-213, loop_ransac.cpp:17-41): the RANSAC problems of all candidates in one call.  cur / n_kp_cur = the
+ * current keyframe's slot and keypoints; cand_slot, n_kp_cand (HOST [n_cand]); matched (HOST [n_cand] of DEVICE int32 [n_kp_cur]) = what
+ * ms_match_loop_closure wrote for the pair (cur, candidate c); level_sigma_sq (HOST [n_levels]).  For candidate c, keypoint i = 0 ..
+ * n_kp_cur - 1 in ascending order yields a pair iff m = matched[c][i] >= 0, r1 = kf_mp[cur][i] is present, r2 = kf_mp[cand_slot[c]][m] is
+ * present and r1 != r2.  HOST outputs, CSR over candidates through pair_start [n_cand + 1], cap_pairs entries each:
+ *   kp1, kp2, row1, row2   i, m, r1, r2
+ *   pts1, pts2 [3 each]    poseCW(cur) * mp_pos[r1], poseCW(cand) * mp_pos[r2] (commonPtsInKeyframe1 / 2)
+ *   thr1, thr2             the float product 9.21034f * level_sigma_sq[octave], octave = kp_octave at (cur, i) / (cand, m): on consistent
+ *                          tables the keypoints observations.at(kf.id) names (chiSqSigmaSq1 / 2)
+ *   cur_pose [12], cand_pose [n_cand * 12]   the poses as read, for the accept gates of :279-338;   n_pairs   the total
+ * They are the arrays of ms_loop_ransac_problem.  Three launches whatever n_cand is: a count pass (ONE workgroup per candidate walks the
+ * keypoints in trips of 256 and writes nothing but counts), the offsets scan over the candidates (a second trip beyond 256 candidates),
+ * the pack pass.  MS_ERR_INVALID with nothing written when the count pass met a matched value outside [-1, n_kp_cand[c]) or a kept pair's
+ * octave outside [0, n_levels).  MS_ERR_CAPACITY when n_pairs > cap_pairs: nothing is written to the arrays or the poses, and n_pairs and
+ * pair_start hold the needed sizes.  MS_ERR_INVALID before any device call: a slot outside [0, n_kf), cur among the candidates, a
+ * candidate listed twice, a keypoint count outside [0, stride], n_levels outside [1, MS_TRI_MAX_LEVELS], a level_sigma_sq that is not
+ * positive and finite, stride < 1, a negative size, a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps and
+ * MS_LOOP_MAX_CANDIDATES.  n_cand = 0 and n_kp_cur = 0 return n_pairs = 0 and pair_start = {0} without a launch (the poses are not
+ * written); a candidate with n_kp_cand = 0 or a matched array of -1 has no pair.
+ *
+ * ms_loop_sim3_lists (optimize_transform.cpp:44-59, :101-142): the arrays of ms_sim3_opt_problem for the final match lists (the inlier
+ * pairs plus what matchMapPointsSim3 appended), given as keypoint pairs kp1 / kp2 (HOST) in CSR over candidates, match_start [n_cand + 1];
+ * entry e of candidate c names the rows kf_mp[cur][kp1[e]] and kf_mp[cand_slot[c]][kp2[e]].  kf_cam (HOST, per slot) as
+ * ms_ba_window_lists takes it.  HOST outputs, aligned with the lists:
+ *   pts1, pts2 [3 each]   as in ms_loop_pairs;   row1, row2   the rows
+ *   obs1, obs2 [2 each]   ((x - cx) / fx, (y - cy) / fy) of the float32 pixel in float64, the obs_uv rule of ms_ba_window_lists
+ *   info1, info2          level_sigma_sq[octave] (the reference multiplies by it, :122, :137; that is kept)
+ * One launch, one thread per entry.  MS_ERR_INVALID with nothing written for a keypoint outside its keyframe (n_kp_cur, n_kp_cand), an
+ * entry whose row is not present, an octave outside the levels (all three found on the device), a camera with fx or fy not positive and
+ * finite (or cx, cy not finite), a match_start that does not start at 0 or descends, and the cases of ms_loop_pairs.  MS_ERR_CAPACITY
+ * beyond the table caps, MS_LOOP_MAX_CANDIDATES, and for a candidate's list longer than the stride.  No match: no launch.
+ *
+ * All three: the same input gives the same bits on every call, at every capacity and at every position of a batch (integer arithmetic
+ * decides every position, the compaction keeps keypoint order, the only atomics are integer violation counters); the number of launches
+ * does not depend on n_cand; synchronous on the context stream with one upload and one download through the context's pinned block; the
+ * workspace belongs to the context and only grows (ms_debug_host_allocs).  The *_check twins are the host validation alone (no context,
+ * no device; `why` receives the message, prefixed "loop mask: ", "loop pairs: ", "loop sim3 lists: "). */
+int ms_loop_usable_mask(ms_ctx *ctx,
+    /* DEVICE tables, read; mp_live may be NULL */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, int n_mp,
+    /* HOST [n_slots]: the slots, their keypoint counts, their require flags, their DEVICE masks and row arrays */
+    const int32_t *slots, const int32_t *n_kp, const int32_t *require_triangulated, uint8_t *const *usable, int32_t *const *tri_row, int n_slots);
+int ms_loop_usable_mask_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, int n_mp,
+    const int32_t *slots, const int32_t *n_kp, const int32_t *require_triangulated, uint8_t *const *usable, int32_t *const *tri_row, int n_slots,
+    char *why, size_t why_bytes);
+int ms_loop_pairs(ms_ctx *ctx,
+    /* DEVICE tables, read; mp_live may be NULL */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose, const int32_t *kp_octave,
+    /* HOST; matched [n_cand] of DEVICE int32 [n_kp_cur] */
+    int cur, int n_kp_cur, const int32_t *cand_slot, const int32_t *n_kp_cand, const int32_t *const *matched, int n_cand,
+    const float *level_sigma_sq, int n_levels,
+    /* HOST outputs and their capacity */
+    int cap_pairs, int32_t *pair_start, int32_t *kp1, int32_t *kp2, int32_t *row1, int32_t *row2, double *pts1, double *pts2, float *thr1, float *thr2,
+    double *cur_pose, double *cand_pose, int32_t *n_pairs);
+int ms_loop_pairs_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose, const int32_t *kp_octave,
+    int cur, int n_kp_cur, const int32_t *cand_slot, const int32_t *n_kp_cand, const int32_t *const *matched, int n_cand,
+    const float *level_sigma_sq, int n_levels,
+    int cap_pairs, const int32_t *pair_start, const int32_t *kp1, const int32_t *kp2, const int32_t *row1, const int32_t *row2, const double *pts1, const double *pts2, const float *thr1, const float *thr2,
+    const double *cur_pose, const double *cand_pose, const int32_t *n_pairs, char *why, size_t why_bytes);
+int ms_loop_sim3_lists(ms_ctx *ctx,
+    /* DEVICE tables, read; mp_live may be NULL */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave,
+    /* HOST */
+    int cur, int n_kp_cur, const int32_t *cand_slot, const int32_t *n_kp_cand, int n_cand, const ms_pinhole *kf_cam,
+    const float *level_sigma_sq, int n_levels, const int32_t *kp1, const int32_t *kp2, const int32_t *match_start,
+    /* HOST outputs [match_start[n_cand]] */
+    double *pts1, double *pts2, double *obs1, double *obs2, float *info1, float *info2, int32_t *row1, int32_t *row2);
+int ms_loop_sim3_lists_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave,
+    int cur, int n_kp_cur, const int32_t *cand_slot, const int32_t *n_kp_cand, int n_cand, const ms_pinhole *kf_cam,
+    const float *level_sigma_sq, int n_levels, const int32_t *kp1, const int32_t *kp2, const int32_t *match_start,
+    const double *pts1, const double *pts2, const double *obs1, const double *obs2, const float *info1, const float *info2, const int32_t *row1, const int32_t *row2,
+    char *why, size_t why_bytes);
 
 /* Rotation-consistency histogram (openvslam/match_angle_checker.h:60-134), host arithmetic: 30 bins of
  * cvRound(delta/30), everything outside the 3 fullest bins is invalid (ties between bins go to the lower bin).

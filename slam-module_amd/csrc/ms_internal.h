@@ -27,6 +27,7 @@ enum MsWorkspaceId {
     MS_WS_CREATE_POINTS,    // ms_create_points_lists, ms_create_points_bind and ms_unbound_mask (create_points.hip): device new rows / per-keypoint positions / results / slot records
     MS_WS_BA_WINDOW,        // ms_ba_window_lists and ms_ba_window_apply (ba_window.hip): device pose index / cameras / results in; block counts / marks / the block that goes down
     MS_WS_SEARCH_BIND,      // ms_search_bind (search_bind.hip): device slice of mp_index / results / row marks
+    MS_WS_LOOP_CHAIN,       // ms_loop_usable_mask, ms_loop_pairs and ms_loop_sim3_lists (loop_chain.hip): device slot / candidate records, sigmas, match lists; counts; the block that goes down
     MS_WS_COUNT
 };
 

@@ -41,6 +41,10 @@ struct Parameters {
     double minTriangulationAngleTwoObs = 1.0, minTriangulationAngleMultipleObs = 3.0;       // degrees
     float relativeReprojectionErrorThreshold = 0.004f;
     bool computeDenseStereoDepth = false;         // tracker.computeDenseStereoDepth
+    // loop_closer.cpp:215, :321-337 (tryLoopClosure): set by the parent project (stand-in defaults)
+    unsigned minLoopClosureFeatureMatches = 20;
+    double maximumDriftMetersPerSecond = 1.0, maximumDriftMetersPerTraveled = 1.0;
+    double maximumDriftRadiansPerSecond = 1.0, maximumDriftRadiansPerTraveled = 1.0;
 };
 
 // slam::StaticSettings (static_settings.hpp:9-21)

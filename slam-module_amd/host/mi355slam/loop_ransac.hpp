@@ -69,6 +69,18 @@ public:
         reprojected2 = reprojectToSameImage(commonPtsInKeyframe2, camera2, visibleSame2);
     }
 
+    // the same object from thresholds that are already CHI_SQ_2D * levelSigmaSq[octave] (what ms_loop_pairs gathers from the device tables)
+    LoopRansac(const std::vector<Vec3> &pts1, const std::vector<Vec3> &pts2, const std::vector<float> &thresholds1, const std::vector<float> &thresholds2,
+               const PinholeCamera &camera1, const PinholeCamera &camera2, const StaticSettings &settings)
+        : camera1(camera1), camera2(camera2), commonPtsInKeyframe1(pts1), commonPtsInKeyframe2(pts2), chiSqSigmaSq1(thresholds1), chiSqSigmaSq2(thresholds2),
+          settings(settings) {
+        if (pts2.size() != pts1.size() || thresholds1.size() != pts1.size() || thresholds2.size() != pts1.size())
+            throw std::invalid_argument("LoopRansac: points and thresholds must describe the same matches");
+        matchCount = (unsigned)pts1.size();
+        reprojected1 = reprojectToSameImage(commonPtsInKeyframe1, camera1, visibleSame1);
+        reprojected2 = reprojectToSameImage(commonPtsInKeyframe2, camera2, visibleSame2);
+    }
+
     // :52-54
     bool earlyReturn() const { return matchCount < 3 || matchCount < settings.parameters.loopClosureRansacMinInliers; }
 

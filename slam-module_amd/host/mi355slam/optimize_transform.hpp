@@ -94,6 +94,7 @@ struct Sim3Matches {
     std::vector<Vec3> pts1, pts2;          // kf1.poseCW * mp1.position, kf2.poseCW * mp2.position
     std::vector<Vec2> obs1, obs2;          // keyPoint.bearing.xy / keyPoint.bearing.z in kf1, kf2
     std::vector<int> octaves1, octaves2;   // keyPoint.octave in kf1, kf2
+    std::vector<float> info1, info2;       // when not empty: levelSigmaSq[octave] as ms_loop_sim3_lists gathered it, used in place of the octaves
     std::size_t size() const { return pts1.size(); }
 };
 
@@ -117,9 +118,12 @@ inline std::vector<unsigned> OptimizeSim3TransformAll(Context &ctx, const std::v
     for (std::size_t k = 0; k < n; ++k) {
         const Sim3Matches &m = *matches[k];
         const std::size_t c = m.size();
-        if (m.pts2.size() != c || m.obs1.size() != c || m.obs2.size() != c || m.octaves1.size() != c || m.octaves2.size() != c)
+        const bool gathered = !m.info1.empty() || !m.info2.empty();
+        if (m.pts2.size() != c || m.obs1.size() != c || m.obs2.size() != c ||
+            (gathered ? m.info1.size() != c || m.info2.size() != c : m.octaves1.size() != c || m.octaves2.size() != c))
             throw std::invalid_argument("OptimizeSim3Transform: points, observations and octaves must describe the same matches");
-        for (std::size_t i = 0; i < c; ++i) {
+        if (gathered) { info1[k] = m.info1; info2[k] = m.info2; }
+        for (std::size_t i = 0; i < c && !gathered; ++i) {
             info1[k].push_back(settings.levelSigmaSq.at((std::size_t)m.octaves1[i]));               // :122 (levelSigmaSq, not its inverse)
             info2[k].push_back(settings.levelSigmaSq.at((std::size_t)m.octaves2[i]));               // :137
         }

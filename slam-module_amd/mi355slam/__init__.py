@@ -1217,6 +1217,60 @@ class SearchBindResult:
         self.n_matched, self.counts = int(n_matched), counts
 
 
+class _Args:
+    """Keyword arguments checked against FIELDS; a field that is not given is None."""
+    FIELDS = ()
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw.pop(k, None))
+        if kw:
+            raise TypeError("%s: unknown fields %s" % (type(self).__name__, sorted(kw)))
+
+
+class LoopMaskArgs(_Args):
+    """The arguments of KeyframeTable.loop_usable_mask (ms_loop_usable_mask).  mp_flags, mp_live: DevBufs of [n_mp] uint8 (mp_live may be
+    None: every row is live); slots, n_kp, require_triangulated: int32 [n_slots] on the host; usable: one DevBuf of n_kp[s] bytes per
+    slot; tri_row: None, or per slot a DevBuf of n_kp[s] int32 or None."""
+    FIELDS = ("mp_flags", "mp_live", "n_mp", "slots", "n_kp", "require_triangulated", "usable", "tri_row")
+
+
+class LoopPairsArgs(_Args):
+    """The arguments of KeyframeTable.loop_pairs (ms_loop_pairs).  Device arrays (DevBufs, device addresses or None): mp_live [n_mp] (may be
+    None), mp_pos [n_mp * 3] float64, kf_pose [n_kf * 12] float64, kp_octave [n_kf * stride] int32, matched: one int32 [n_kp_cur] array per
+    candidate as ms_match_loop_closure left it.  Host: n_mp, cur, n_kp_cur, cand_slot, n_kp_cand, level_sigma_sq, cap_pairs, and `out`,
+    None or a dict of the output arrays (see LOOP_PAIRS_OUT) that are handed to the call as they are."""
+    FIELDS = ("mp_live", "mp_pos", "n_mp", "kf_pose", "kp_octave", "cur", "n_kp_cur", "cand_slot", "n_kp_cand", "matched", "level_sigma_sq", "cap_pairs", "out")
+
+
+class LoopSim3ListsArgs(_Args):
+    """The arguments of KeyframeTable.loop_sim3_lists (ms_loop_sim3_lists).  Device arrays as LoopPairsArgs plus kp_x, kp_y [n_kf * stride]
+    float32.  Host: cams [n_kf, 6] (fx, fy, cx, cy, width, height per slot), level_sigma_sq, the match lists kp1, kp2 in CSR over the
+    candidates through match_start [n_cand + 1], and `out`, None or a dict of the output arrays (see LOOP_SIM3_OUT)."""
+    FIELDS = ("mp_live", "mp_pos", "n_mp", "kf_pose", "kp_x", "kp_y", "kp_octave", "cur", "n_kp_cur", "cand_slot", "n_kp_cand", "cams", "level_sigma_sq", "kp1", "kp2",
+              "match_start", "out")
+
+
+# the HOST outputs of ms_loop_pairs / ms_loop_sim3_lists: name, dtype, values per entry
+LOOP_PAIRS_OUT = (("kp1", np.int32, 1), ("kp2", np.int32, 1), ("row1", np.int32, 1), ("row2", np.int32, 1), ("pts1", np.float64, 3), ("pts2", np.float64, 3),
+                  ("thr1", np.float32, 1), ("thr2", np.float32, 1))
+LOOP_SIM3_OUT = (("pts1", np.float64, 3), ("pts2", np.float64, 3), ("obs1", np.float64, 2), ("obs2", np.float64, 2), ("info1", np.float32, 1), ("info2", np.float32, 1),
+                 ("row1", np.int32, 1), ("row2", np.int32, 1))
+
+
+def _loop_out(spec, out, n, extra=()):
+    """The output arrays of a loop-chain call: the caller's (checked) or fresh ones of n entries."""
+    if out is None:
+        out = {k: np.zeros((n, w) if w > 1 else n, dt) for k, dt, w in spec}
+        out.update({k: np.zeros(shape, dt) for k, dt, shape in extra})
+    for k, dt, w in tuple(spec) + tuple((k, dt, 0) for k, dt, _ in extra):
+        if out[k].dtype != dt or not out[k].flags["C_CONTIGUOUS"]:
+            raise ValueError("out[%r] must be a contiguous %s array" % (k, np.dtype(dt).name))
+        if w and out[k].size < w * n:
+            raise ValueError("out[%r] holds fewer than %d entries" % (k, n))
+    return out
+
+
 def _download_i32_at(buf, byte_offset, n):
     """n int32 from byte_offset of a DevBuf."""
     a = np.zeros(max(n, 1), np.int32)
@@ -1766,6 +1820,68 @@ class KeyframeTable:
                                             int(kf.n), _vp(mp_index) if len(mp_index) else None, int(a.first), int(a.count), int(a.n_kept), int(a.slot),
                                             _vp(a.match_kp), _vp(a.outcome), _vp(a.usable), C.byref(n), _vp(counts)), "ms_search_bind")
         return SearchBindResult(n.value, counts)
+
+    def loop_usable_mask(self, a):
+        """ms_loop_usable_mask: the M1 masks of matchForLoopClosures (usable[s][k] = keypoint k of slots[s] has a present map point, a
+        TRIANGULATED one where require_triangulated[s]) and the TRIANGULATED rows tri_row[s] of matchMapPointsSim3, from this table, for all
+        listed slots in one launch.  a: a LoopMaskArgs.  Raises MsError when the call is turned away."""
+        slots, n_kp, req = _i32(a.slots), _i32(a.n_kp), _i32(a.require_triangulated)
+        n = len(slots)
+        if len(n_kp) != n or len(req) != n or len(a.usable) != n or (a.tri_row is not None and len(a.tri_row) != n):
+            raise ValueError("one keypoint count, one require flag, one mask and (with tri_row) one row array per slot")
+        masks = (C.c_void_p * max(n, 1))(*[_vp(m).value for m in a.usable])
+        rows = None if a.tri_row is None else (C.c_void_p * max(n, 1))(*[_vp(r).value for r in a.tri_row])
+        self.ctx.check(lib().ms_loop_usable_mask(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(a.mp_flags), _vp(a.mp_live), int(a.n_mp), _vp(slots), _vp(n_kp),
+                                                 _vp(req), masks, rows, n), "ms_loop_usable_mask")
+
+    def loop_pairs(self, a):
+        """ms_loop_pairs: the RANSAC problems of all loop-closure candidates of keyframe a.cur from this table (loop_closer.cpp:203-213,
+        loop_ransac.cpp:17-41).  a: a LoopPairsArgs.  Returns (rc, n_pairs, out): out holds pair_start [n_cand + 1], cur_pose [12],
+        cand_pose [n_cand, 12] and the arrays of LOOP_PAIRS_OUT with cap_pairs entries, of which the first n_pairs are written.  rc is 0 or
+        MS_ERR_CAPACITY, which still reports n_pairs and pair_start so that the caller can call again; every other code raises MsError (its
+        `rc` attribute holds the code), as the other methods do."""
+        cand, nk = _i32(a.cand_slot), _i32(a.n_kp_cand)
+        n = len(cand)
+        if len(nk) != n or len(a.matched) != n:
+            raise ValueError("one keypoint count and one matched array per candidate")
+        sig = np.ascontiguousarray(a.level_sigma_sq, np.float32).reshape(-1)
+        cap = int(a.cap_pairs)
+        out = _loop_out(LOOP_PAIRS_OUT, a.out, cap, (("pair_start", np.int32, n + 1), ("cur_pose", np.float64, 12), ("cand_pose", np.float64, (max(n, 1), 12))))
+        ptrs = (C.c_void_p * max(n, 1))(*[_vp(m).value for m in a.matched])
+        total = C.c_int32(0)
+        rc = lib().ms_loop_pairs(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(a.mp_live), _vp(a.mp_pos), int(a.n_mp), _vp(a.kf_pose), _vp(a.kp_octave),
+                                 int(a.cur), int(a.n_kp_cur), _vp(cand), _vp(nk), ptrs, n, _vp(sig), len(sig), cap, _vp(out["pair_start"]),
+                                 *[_vp(out[k]) for k, _, _ in LOOP_PAIRS_OUT], _vp(out["cur_pose"]), _vp(out["cand_pose"]), C.byref(total))
+        if rc not in (0, MS_ERR_CAPACITY):
+            self._raise(rc, "ms_loop_pairs")
+        return rc, total.value, out
+
+    def loop_sim3_lists(self, a):
+        """ms_loop_sim3_lists: the arrays of the Sim3 refinement's problems for the final match lists of all candidates
+        (optimize_transform.cpp:44-59, :101-142).  a: a LoopSim3ListsArgs.  Returns the dict of the arrays of LOOP_SIM3_OUT, aligned with the
+        lists; raises MsError (with the code in its `rc` attribute) when the call is turned away."""
+        cand, nk, start = _i32(a.cand_slot), _i32(a.n_kp_cand), _i32(a.match_start)
+        kp1, kp2 = _i32(a.kp1), _i32(a.kp2)
+        n = len(cand)
+        if len(nk) != n or len(start) != n + 1 or len(kp1) != len(kp2) or (len(start) and start[-1] > len(kp1)):
+            raise ValueError("one keypoint count per candidate, match_start of n_cand + 1 entries, kp1 and kp2 of match_start[n_cand] entries")
+        cam_rows = np.asarray(a.cams, np.float64).reshape(-1, 6)
+        if len(cam_rows) != self.n_kf:
+            raise ValueError("loop_sim3_lists: one camera per keyframe slot")
+        K = (Pinhole * max(self.n_kf, 1))(*[Pinhole(c[0], c[1], c[2], c[3], int(c[4]), int(c[5])) for c in cam_rows])
+        sig = np.ascontiguousarray(a.level_sigma_sq, np.float32).reshape(-1)
+        out = _loop_out(LOOP_SIM3_OUT, a.out, len(kp1))
+        rc = lib().ms_loop_sim3_lists(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(a.mp_live), _vp(a.mp_pos), int(a.n_mp), _vp(a.kf_pose), _vp(a.kp_x),
+                                      _vp(a.kp_y), _vp(a.kp_octave), int(a.cur), int(a.n_kp_cur), _vp(cand), _vp(nk), n, K, _vp(sig), len(sig), _vp(kp1), _vp(kp2),
+                                      _vp(start), *[_vp(out[k]) for k, _, _ in LOOP_SIM3_OUT])
+        if rc != 0:
+            self._raise(rc, "ms_loop_sim3_lists")
+        return out
+
+    def _raise(self, rc, what):
+        err = MsError("%s failed (%d): %s" % (what, rc, lib().ms_last_error(self.ctx._h).decode()))
+        err.rc = rc
+        raise err
 
     def create_points(self, table, flags, live, kp, pool, poses, kf_id, cams, focal, desc_base, current, adjacent, frames, free_rows, settings, scale_factors_, thr_deg,
                       mode=TRI_TME, n_obs=None, mp_track=None, lists=None, check_orientation=True, exact_capacity=False, pose_host=None):
