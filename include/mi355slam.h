@@ -1580,6 +1580,85 @@ int ms_ba_download(ms_ba *ba, int i, double *pose, double *point, double *chi2_p
 int ms_ba_solve_host(ms_ctx *ctx, const ms_ba_problem *problem, double *pose_out, double *point_out,
                      double *chi2_per_obs, ms_ba_result *res);
 
+/* ---- poseBundleAdjust on the device map tables ---------------------------------------------------------------------------
+ * poseBundleAdjust (bundle_adjuster.cpp:396-491) runs on every frame that is not a keyframe (mapper_helpers.cpp:1043-1050), behind
+ * ms_match_tracked.  kf_mp, mp_flags, mp_live, mp_pos, kf_pose and the keypoint table kp_x / kp_y / kp_octave are those of 9.5 - 9.9: row r
+ * is PRESENT iff (uint32)r < n_mp and mp_live[r] != 0 (mp_live == NULL: every row is live); bit 0 of mp_flags is TRIANGULATED.
+ * tests/pose_tables_ref.py restates the gather and the apply and is their specification.
+ *
+ * ms_pose_tables_create: a persistent handle, created once per context and used for every frame.  It owns a pose-only solver handle with two
+ * poses, up to cap_obs fixed points / observations and one SE3 edge, whose device input arrays are written by a kernel, never uploaded;
+ * level_sigma_sq (HOST float [n_levels]) goes to the device once, here.  MS_ERR_INVALID for cap_obs outside [0, MS_COVIS_MAX_STRIDE],
+ * n_levels outside [1, MS_TRI_MAX_LEVELS], a level_sigma_sq that is not positive and finite.
+ *
+ * ms_pose_tables_solve, frame f (HOST):
+ *   Gather (:403-407, :453-480).  For keypoint j = 0 .. n_kp - 1 in ascending order, r = kf_mp[slot * stride + j] yields one observation iff r
+ *   is PRESENT and mp_flags[r] & 1.  Observation k, the k-th kept keypoint: point[k] = mp_pos[r] bit for bit; obs_point[k] = k; obs_pose[k] =
+ *   0; obs_uv and obs_info by the expressions of ms_ba_window_lists (the float32 pixel in float64, (x - cx) / fx; (double)focal *
+ *   (double)focal / (double)level_sigma_sq[octave]), through the same device code.  Pose 0 = matrixToPose(kf_pose[slot]), free; pose 1 =
+ *   matrixToPose(kf_pose[prev_slot]), fixed; both by the four-branch conversion ms_ba_window_lists documents.  The one SE3 edge is
+ *   makeOdometryEdge(kf, prev): vertex 0 = pose 0, vertex 1 = pose 1, edge_meas / edge_info as INTEGRATION.md 4 fills them.
+ *   n_triangulated = the number kept.
+ *   Solve: the pose-only kernel of ms_ba_solve, unchanged, on that problem with max_iters and huber_delta; a frame the apply is not going to
+ *   write (below) is evaluated once and not iterated on.
+ *   Apply (:485-489).  Iff n_triangulated >= min_visible and the solve ended in a finite state, kf_pose[slot] = rows 0-2 of the returned
+ *   pose's matrix by the conversion of ms_ba_window_apply, on the device, and out->ran = 1.  Otherwise kf_pose keeps its bits and out->ran = 0
+ *   (the reference's `return false`, :410-412).  The decision is the apply kernel's: the host learns the count only with the results.  No
+ *   other table is written.
+ * out (HOST): ran; n_triangulated; pose [7] = pose 0 as the solver returned it (as gathered when ran = 0); result, the solver's ms_ba_result
+ * (of the single evaluation when the frame was not iterated on).  chi2 (HOST [cap_obs], may be NULL) receives the chi2 per observation in
+ * gather order, n_triangulated values, when ran = 1.
+ * Per call: NO host-to-device copy (f travels as kernel arguments); three launches whatever the sizes -- the gather (ONE workgroup of 256
+ * lanes walks the keypoints in trips of 256; order-preserving compaction through the shared block rank, the count carried across trips;
+ * the descriptor's n_obs / n_point are written on the device), the solver, the apply (which also writes the small result record) -- ONE
+ * device-to-host copy of that record through the context's pinned block and ONE polite host wait for the handle's event.  Synchronous on
+ * the context stream.  Nothing is allocated after the first call of a handle (ms_debug_host_allocs).  Integer arithmetic decides every
+ * position and there is no atomic: the same tables give the same bits on every call, and the same bits as ms_ba_solve_host on the restated
+ * problem.
+ * prev_slot == -1 (:430-432): ran = 0, n_triangulated = 0 and MS_OK before any device call.  MS_ERR_INVALID before any device call: slot
+ * outside [0, n_kf), prev_slot outside [-1, n_kf) or equal to slot, n_kp > stride, stride < 1, a negative size, a missing array, a camera
+ * ms_triangulate_check rejects, a non-finite edge_meas / edge_info / huber_delta, max_iters < 0.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_*
+ * caps.  After the gather, with kf_pose untouched and n_triangulated returned: MS_ERR_INVALID when a KEPT keypoint's octave lies outside
+ * [0, n_levels) (the rule of ms_match_tracked; a dropped keypoint's octave is never read); MS_ERR_CAPACITY when n_triangulated > cap_obs.
+ * MS_ERR_NUMERIC, kf_pose untouched and out->pose not written, when the solve ended in a non-finite state (as ms_ba_download).
+ *
+ * ms_pose_tables_problem: a diagnostic for tests and probes, not on the per-frame path: the arrays the last gather wrote, HOST outputs, any
+ * may be NULL: pose [2 * 7], point [n * 3], obs_point [n], obs_pose [n], obs_uv [n * 2], obs_info [n]; n = its count (0 before the first
+ * call and after one that returned early or with an error).
+ * ms_pose_tables_solve_check is the host validation of ms_pose_tables_solve alone (no context, no device; `why` receives the message). */
+typedef struct ms_pose_tables ms_pose_tables;
+typedef struct {
+    int32_t slot, prev_slot;             /* the frame's keyframe slot; its previous keyframe's, -1 for none */
+    int32_t n_kp;                        /* the frame's keypoints, <= stride */
+    ms_pinhole cam;
+    int32_t focal;                       /* getFocalLength */
+    double edge_meas[7];                 /* makeOdometryEdge(kf, prev): the measurement SE3, qx, qy, qz, qw, tx, ty, tz */
+    double edge_info[36];                /* its 6 x 6 information, row-major */
+    int32_t min_visible;                 /* minVisibleMapPointsInCurrentFrameBA */
+    int32_t max_iters;                   /* poseBAIterations */
+    double huber_delta;                  /* as ms_ba_problem's */
+} ms_pose_tables_frame;
+typedef struct {
+    int32_t ran;                         /* the reference's return value */
+    int32_t n_triangulated;
+    double pose[7];
+    ms_ba_result result;
+} ms_pose_tables_out;
+int ms_pose_tables_create(ms_ctx *ctx, int cap_obs, const float *level_sigma_sq, int n_levels, ms_pose_tables **out);
+void ms_pose_tables_destroy(ms_pose_tables *h);
+int ms_pose_tables_solve(ms_pose_tables *h,
+    /* DEVICE tables, read; mp_live may be NULL */
+    const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const double *mp_pos, int n_mp,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave,
+    /* DEVICE, updated in place */
+    double *kf_pose,
+    /* HOST */
+    const ms_pose_tables_frame *frame, ms_pose_tables_out *out, double *chi2);
+int ms_pose_tables_solve_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const double *mp_pos, int n_mp,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const double *kf_pose,
+    const ms_pose_tables_frame *frame, const ms_pose_tables_out *out, char *why, size_t why_bytes);
+int ms_pose_tables_problem(ms_pose_tables *h, double *pose, double *point, int32_t *obs_point, int32_t *obs_pose, double *obs_uv, double *obs_info, int32_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3390,6 +3390,76 @@ int ms_ba_solve_host(ms_ctx *c, const ms_ba_problem *problem, double *pose_out, 
 
 }  // extern "C"
 
+// ---------------------------------------------------------------- a pose-only handle whose inputs a kernel writes (pose_tables.hip)
+// The block of ba_lay_out for the poseBundleAdjust shape at capacity cap_obs: pose 0 free, pose 1 fixed, every point fixed and seen once from pose 0, one SE3
+// edge.  No host array is staged: the input range is cleared (free2pose[0] = 0 is all k_ba_pose_only reads of the index arrays), pidx and the two descriptors
+// go up once, here; every later value -- the descriptor's n_point / n_obs / max_iters / huber included -- is written on the device.  No eager result block:
+// the caller's apply kernel reads stats / pose / chi2_obs where the solver leaves them.
+int ms_ba_pose_tables_create(ms_ctx *c, int cap_obs, ms_ba **out, MsBaPoseIo *io) {
+    if (!c || !out || !io || cap_obs < 0) return MS_ERR_INVALID;
+    *out = nullptr;
+    MS_HIP(c, hipSetDevice(c->device));
+    tl_ba_arena.begin();
+    struct ArenaEnd { ~ArenaEnd() { tl_ba_arena.end(); } } arena_end;
+    ms_ba_problem Q{};                                     // sizes only
+    Q.n_pose = 2; Q.n_point = cap_obs; Q.n_obs = cap_obs; Q.n_pose_edge = 1;
+    Prep R;
+    R.np_free = 1; R.pidx.assign(2, -1); R.pidx[0] = 0; R.free2pose.push_back(0);
+    R.pose_only = true; R.fused = true; R.auto_team = 1;
+    BaLayout L;
+    BaProb H{};
+    ms_ba::AltPtrs A{};
+    ba_lay_out(Q, R, true, 0, L, H, A);
+    ms_ba *B = nullptr;
+    for (void *&slot : c->ba_handle_pool) if (slot) { B = static_cast<ms_ba *>(slot); slot = nullptr; break; }
+    if (!B) { B = new ms_ba(); ++g_ba_host_allocs; }
+    B->ctx = c; B->n = 1;
+    const int rc = ba_take_block(c, B, ms_align_up(L.total, 256));
+    if (rc != MS_OK) { ba_delete_object(B); return rc; }
+    B->d_probs = reinterpret_cast<BaProb *>(B->d_arena + L.desc_at);
+    B->d_probs_alt = B->d_probs + 1;
+    B->pack_doubles = 0; B->d_pack = nullptr;
+    B->pose_only = true; B->one_pose = false; B->work_dirty = true;
+    B->work_lo.push_back(R.in_hi); B->work_hi.push_back(L.total); B->chol_tiles.push_back(0.0);
+    L.relocate(B->d_arena);
+    B->host.assign(1, H); B->alt_ptrs.assign(1, A); B->dims.assign(1, Q);
+    ba_make_alt(B);
+    const hipStream_t st = c->stream;
+    hipError_t e = hipMemsetAsync(B->d_arena + R.in_lo, 0, R.in_hi - R.in_lo, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<int32_t *>(B->host[0].pidx), R.pidx.data(), 2 * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(B->d_probs, B->host.data(), sizeof(BaProb), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(B->d_probs_alt, B->host_alt.data(), sizeof(BaProb), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);     // (the sources are this call's)
+    if (e == hipSuccess) e = ba_set_lds_attributes(c);
+    if (e != hipSuccess) { (void)hipGetLastError(); ms_ba_destroy(B); return ms_fail(c, MS_ERR_HIP, "pose tables: device setup failed: %s", hipGetErrorString(e)); }
+    const BaProb &P = B->host[0];
+    io->pose0 = const_cast<double *>(P.pose0); io->point0 = const_cast<double *>(P.point0);
+    io->obs_uv = const_cast<double *>(P.obs_uv); io->obs_info = const_cast<double *>(P.obs_info);
+    io->edge_meas = const_cast<double *>(P.edge_meas); io->edge_info = const_cast<double *>(P.edge_info);
+    io->obs_pose = const_cast<int32_t *>(P.obs_pose); io->obs_point = const_cast<int32_t *>(P.obs_point);
+    io->edge_i = const_cast<int32_t *>(P.edge_i); io->edge_j = const_cast<int32_t *>(P.edge_j);
+    io->n_point = &B->d_probs->n_point; io->n_obs = &B->d_probs->n_obs; io->max_iters = &B->d_probs->max_iters; io->huber = &B->d_probs->huber;
+    io->pose = P.pose; io->chi2_obs = P.chi2_obs; io->stats = P.stats;
+    *out = B;
+    return MS_OK;
+}
+
+int ms_ba_pose_tables_launch(ms_ba *B) {
+    if (!B || !B->pose_only || B->n != 1) return MS_ERR_INVALID;
+    ms_ctx *c = B->ctx;
+    hipLaunchKernelGGL(k_ba_pose_only, dim3(1), dim3(PO_NT), kPoLdsBytes, c->stream, B->d_probs);
+    MS_KERNEL_CHECK(c, "k_ba_pose_only");
+    B->launched_team = 1; B->team_checked = true; B->last_one_pose = false; ++B->solves;
+    B->eager = false; B->verdict_eager = false; B->self_packed = false; B->quiet = false;
+    return MS_OK;
+}
+
+int ms_ba_pose_tables_wait(ms_ba *B) {
+    if (!B) return MS_ERR_INVALID;
+    MS_TRY_BA(ba_launch_done(B->ctx, B));
+    return ba_wait_pending(B);
+}
+
 void ms_ba_release_pool(ms_ctx *c) {
     for (void *&sl : c->ba_handle_pool) if (sl) { ba_delete_object(static_cast<ms_ba *>(sl)); sl = nullptr; }
     if (c->ba_stage) { if (c->ba_stage_busy) (void)hipEventSynchronize(c->ba_stage_ev); (void)hipHostFree(c->ba_stage); c->ba_stage = nullptr; c->ba_stage_bytes = 0; }

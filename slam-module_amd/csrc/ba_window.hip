@@ -12,6 +12,7 @@
 // The only atomic is the integer decrement of n_obs in the apply; the float64 expressions are evaluated as written (no contraction).
 #include "ms_internal.h"
 #include "ms_scan.h"
+#include "ba_window_dev.h"
 #include <cmath>
 #include <cstring>
 
@@ -80,57 +81,21 @@ __global__ __launch_bounds__(kBlock) void k_window_pack(const GatherArgs A) {
     A.o_point[e] = lo;
     A.o_pose[e] = k;
     const double fx = A.cam[4 * k], fy = A.cam[4 * k + 1], cx = A.cam[4 * k + 2], cy = A.cam[4 * k + 3];
-    A.uv[2 * (size_t)e] = ((double)A.lists.obs_x[o] - cx) / fx;                  // normalizePixel of the pinhole stand-in, bundle_adjuster.cpp:52
-    A.uv[2 * (size_t)e + 1] = ((double)A.lists.obs_y[o] - cy) / fy;
+    A.uv[2 * (size_t)e] = obs_normalised(A.lists.obs_x[o], cx, fx);
+    A.uv[2 * (size_t)e + 1] = obs_normalised(A.lists.obs_y[o], cy, fy);
     int32_t octave = A.lists.obs_octave[o];
     octave = octave < 0 ? 0 : (octave >= A.n_levels ? A.n_levels - 1 : octave);  // ms_observation_lists stores them inside the range already
-    const double focal = (double)A.focal[k];
-    A.info[e] = focal * focal / (double)A.sigma[octave];                         // :51
+    A.info[e] = obs_information(A.focal[k], A.sigma[octave]);
     A.win.edge_slot[e] = slot;
     A.win.edge_kp[e] = A.lists.obs_kp[o];
     A.win.edge_point[e] = lo;
-}
-
-// g2o::SE3Quat(R, t): Eigen's quaternion of a rotation matrix (Quaternion.h, quaternionbase_assign_impl<Other, 3, 3>), then
-// normalizeRotation (w >= 0, unit length).  R row-major; q = x, y, z, w
-__device__ void quat_of_matrix(const double *R, double *q) {
-    double t = R[0] + R[4] + R[8];
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t;
-        q[1] = (R[2] - R[6]) * t;
-        q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (R[3 * k + j] - R[3 * j + k]) * t;
-        q[j] = (R[3 * j + i] + R[3 * i + j]) * t;
-        q[k] = (R[3 * k + i] + R[3 * i + k]) * t;
-    }
-    if (q[3] < 0.0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
 }
 
 // thread i: the pose of local keyframe i (i < n_local) and the position of listed row i (i < n_rows, 0 when the points do not fit)
 __global__ __launch_bounds__(kBlock) void k_window_vertices(const GatherArgs A, int n_rows) {
     const int i = blockIdx.x * kBlock + (int)threadIdx.x;
     if (i < A.n_local) {
-        const double *P = A.kf_pose + 12 * (size_t)A.local_slot[i];
-        double R[9], q[4];
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) R[3 * a + b] = P[4 * a + b];
-        quat_of_matrix(R, q);
-        double *out = A.pose + 7 * (size_t)i;
-        out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; out[3] = q[3];
-        out[4] = P[3]; out[5] = P[7]; out[6] = P[11];
+        pose_of_table(A.kf_pose + 12 * (size_t)A.local_slot[i], A.pose + 7 * (size_t)i);
     }
     if (i < n_rows) {
         const int32_t r = A.lists.rows[i];
@@ -190,16 +155,6 @@ __global__ __launch_bounds__(kEdgeBlock) void k_apply_erase(const ApplyArgs A) {
     atomicSub(&A.n_obs[row], 1);                             // MapPoint::eraseObservation, :382
     A.lost[p] = 1;
     A.erased[dst] = e;
-}
-
-// Eigen's QuaternionBase::toRotationMatrix of the quaternion as given, rows 0-2 of to_homogeneous_matrix()
-__device__ __forceinline__ void write_pose(const double *s, double *P) {
-    const double x = s[0], y = s[1], z = s[2], w = s[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    P[0] = 1.0 - (tyy + tzz); P[1] = txy - twz; P[2] = txz + twy; P[3] = s[4];
-    P[4] = txy + twz; P[5] = 1.0 - (txx + tzz); P[6] = tyz - twx; P[7] = s[5];
-    P[8] = txz - twy; P[9] = tyz + twx; P[10] = 1.0 - (txx + tyy); P[11] = s[6];
 }
 
 __global__ __launch_bounds__(kBlock) void k_apply_vertices(const ApplyArgs A) {

@@ -70,6 +70,20 @@ struct ms_ctx {
 extern std::atomic<long long> g_ms_host_allocs;
 void ms_ba_release_pool(ms_ctx *ctx);      // ba.hip: deletes the pooled handle objects (ms_ctx_destroy)
 
+// ba.hip, for pose_tables.hip: a pose-only handle of capacity cap_obs -- two poses (0 free, 1 fixed), up to cap_obs fixed points with
+// one observation each from pose 0, one SE3 edge -- whose inputs are WRITTEN BY A KERNEL: the device block ms_ba_create lays out for that shape, with
+// no host array staged.  MsBaPoseIo names what the gather writes and what the apply reads, all DEVICE pointers into the handle's block.
+struct MsBaPoseIo {
+    double *pose0, *point0, *obs_uv, *obs_info, *edge_meas, *edge_info;    // [2 * 7], [cap * 3], [cap * 2], [cap], [7], [36]
+    int32_t *obs_pose, *obs_point, *edge_i, *edge_j;                       // [cap], [cap], [1], [1]
+    int32_t *n_point, *n_obs, *max_iters;                                  // fields of the descriptor k_ba_pose_only reads
+    double *huber;
+    const double *pose, *chi2_obs, *stats;                                 // the solver's state [2 * 7], chi2 per observation [cap], status record [16]
+};
+int ms_ba_pose_tables_create(ms_ctx *ctx, int cap_obs, ms_ba **out, MsBaPoseIo *io);
+int ms_ba_pose_tables_launch(ms_ba *ba);   // k_ba_pose_only on the handle's problem as the device holds it: one launch, nothing else
+int ms_ba_pose_tables_wait(ms_ba *ba);     // records the handle's event behind everything enqueued so far and waits for it politely (ba_wait_event)
+
 // page-locked host staging of at least `bytes` in ctx->pinned (contents are valid until the next call that uses it)
 int ms_pinned(ms_ctx *ctx, size_t bytes);
 

@@ -31,6 +31,7 @@ struct Parameters {
     double odometryPriorStrengthRotation = 100.0, odometryPriorStrengthPosition = 50.0;
     unsigned minVisibleMapPointsInNeighborhoodBA = 0;
     unsigned minVisibleMapPointsInCurrentFrameBA = 0, minKeyframesInBA = 0;       // the early-outs of bundle_adjuster.cpp:235-240 (stand-in defaults)
+    unsigned poseBAIterations = 10;               // bundle_adjuster.cpp:483 (a stand-in default)
     // loop_closer.cpp:230, loop_ransac.cpp:50, :85: set by the parent project, whose defaults are not in the reference tree
     unsigned loopClosureRansacIterations = 300;
     unsigned loopClosureRansacMinInliers = 10;

@@ -679,6 +679,59 @@ inline LocalBaOnTables localBundleAdjustOnTables(Context &ctx, DeviceObservation
     return out;
 }
 
+// ---- poseBundleAdjust on the device tables (ms_pose_tables_solve) ----------------------------------------------------------------------
+// makeOdometryEdge(keyframe, previous) (bundle_adjuster.cpp:65-112): it reads odometry data that no table holds, so the caller fills it as
+// it fills edgeMeas / edgeInfo of a BaWindow.  Vertex 0 = the frame, vertex 1 = its previous keyframe.
+struct PoseOdometryEdge {
+    std::array<double, 7> measurement{{0, 0, 0, 1, 0, 0, 0}};
+    std::array<double, 36> information{};
+};
+
+// The persistent handle of poseBundleAdjustOnTables: one per context, for frames of up to maxMapPoints triangulated map points.
+class DevicePoseAdjuster {
+public:
+    DevicePoseAdjuster(Context &ctx, std::size_t maxMapPoints, const StaticSettings &settings) {
+        ctx.check(ms_pose_tables_create(ctx.get(), (int)maxMapPoints, settings.levelSigmaSq.data(), (int)settings.levelSigmaSq.size(), &h_), "ms_pose_tables_create");
+    }
+    ~DevicePoseAdjuster() { ms_pose_tables_destroy(h_); }
+    DevicePoseAdjuster(const DevicePoseAdjuster &) = delete;
+    DevicePoseAdjuster &operator=(const DevicePoseAdjuster &) = delete;
+    ms_pose_tables *get() const { return h_; }
+    ms_pose_tables_out last{};               // what the last poseBundleAdjustOnTables on this handle returned
+private:
+    ms_pose_tables *h_ = nullptr;
+};
+
+// poseBundleAdjust (bundle_adjuster.cpp:396-491) for the frame in `slot` with nothing walked on the host: the frame's TRIANGULATED map points
+// are gathered from the tables, solved and the pose written back into `poses` on the device.  Returns the reference's bool: false, with
+// nothing written, for a frame with fewer than minVisibleMapPointsInCurrentFrameBA such points (:410-412) or without a previous keyframe
+// (prevSlot = -1, :430-432).  live may be null (every row holds a map point).  keyPointCount defaults to the stride: the entries behind a
+// keyframe's keypoints are -1 (DeviceKeyframeMapPoints::update pads them).
+inline bool poseBundleAdjustOnTables(Context &ctx, DevicePoseAdjuster &handle, const DeviceKeyframeMapPoints &kfTable, const DeviceMapPointFlags &flags,
+                                     const DeviceMapPointLive *live, const DeviceMapPoints &table, const DeviceKeypointTable &kpTable, DeviceKeyframePoses &poses,
+                                     const KeyframeCameras &cams, std::int32_t slot, std::int32_t prevSlot, const PoseOdometryEdge &odometryEdge, const Parameters &parameters,
+                                     const StaticSettings &settings, std::size_t keyPointCount = ~(std::size_t)0) {
+    detail::TraceRange range("poseBundleAdjust");                             // mapper_helpers.cpp:1044
+    const std::size_t nKf = kfTable.size(), nMp = kfTable.mapPointCount();
+    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || poses.size() != nKf || kpTable.size() != nKf || kpTable.stride() != kfTable.stride())
+        throw std::invalid_argument("poseBundleAdjustOnTables: one camera, focal length, pose and keypoint row per slot");
+    if (table.size() != nMp || flags.size() < nMp || (live && live->size() < nMp)) throw std::invalid_argument("poseBundleAdjustOnTables: the map-point tables differ in size");
+    if (slot < 0 || (std::size_t)slot >= nKf) throw std::invalid_argument("poseBundleAdjustOnTables: slot " + std::to_string(slot) + " outside the table");
+    (void)settings;                                                            // (its level sigmas went to the device with the handle)
+    ms_pose_tables_frame f{};
+    f.slot = slot; f.prev_slot = prevSlot;
+    f.n_kp = (std::int32_t)std::min(keyPointCount, kfTable.stride());
+    f.cam = cams.camera[(std::size_t)slot]; f.focal = cams.focalLength[(std::size_t)slot];
+    std::copy(odometryEdge.measurement.begin(), odometryEdge.measurement.end(), f.edge_meas);
+    std::copy(odometryEdge.information.begin(), odometryEdge.information.end(), f.edge_info);
+    f.min_visible = (std::int32_t)parameters.minVisibleMapPointsInCurrentFrameBA;
+    f.max_iters = (std::int32_t)parameters.poseBAIterations;
+    f.huber_delta = std::sqrt(CHI2_THRESHOLD);                                 // rk->setDelta(std::sqrt(CHI2_THRESHOLD)) (:56), as detail::as_problem
+    ctx.check(ms_pose_tables_solve(handle.get(), kfTable.table(), (int)nKf, (int)kfTable.stride(), flags.flags(), live ? live->live() : nullptr, table.position(), (int)nMp,
+                                   kpTable.x(), kpTable.y(), kpTable.octave(), poses.pose(), &f, &handle.last, nullptr), "ms_pose_tables_solve");
+    return handle.last.ran != 0;
+}
+
 // ---- fusing duplicate map points on the device tables (ms_map_fuse, ms_map_replace_pairs) ----------------------------------------------
 // The tables the fuse steps update in place.  observationCount: DEVICE [mapPointCount], mp.observations.size() of every row as
 // ms_observation_count leaves it (observationCountsOnDevice); the walk keeps it current, so one count serves a whole new-keyframe chain.

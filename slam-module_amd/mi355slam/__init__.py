@@ -2069,6 +2069,85 @@ class BaWindowEdges:
         self._bufs = {}
 
 
+class PoseTablesFrameC(C.Structure):
+    """ms_pose_tables_frame"""
+    _fields_ = [("slot", C.c_int32), ("prev_slot", C.c_int32), ("n_kp", C.c_int32), ("cam", Pinhole), ("focal", C.c_int32), ("edge_meas", C.c_double * 7),
+                ("edge_info", C.c_double * 36), ("min_visible", C.c_int32), ("max_iters", C.c_int32), ("huber_delta", C.c_double)]
+
+
+class PoseTablesOutC(C.Structure):
+    """ms_pose_tables_out"""
+    _fields_ = [("ran", C.c_int32), ("n_triangulated", C.c_int32), ("pose", C.c_double * 7), ("result", BaResultC)]
+
+
+def pose_tables_frame(frame):
+    """dict(slot, prev_slot, n_kp, cam (fx, fy, cx, cy, width, height), focal, edge_meas [7], edge_info [36], min_visible, max_iters,
+    huber_delta) -> PoseTablesFrameC"""
+    cam = frame["cam"]
+    meas = np.ascontiguousarray(frame["edge_meas"], np.float64).reshape(7)
+    info = np.ascontiguousarray(frame["edge_info"], np.float64).reshape(36)
+    return PoseTablesFrameC(int(frame["slot"]), int(frame["prev_slot"]), int(frame["n_kp"]), Pinhole(cam[0], cam[1], cam[2], cam[3], int(cam[4]), int(cam[5])),
+                            int(frame["focal"]), (C.c_double * 7)(*meas), (C.c_double * 36)(*info), int(frame["min_visible"]), int(frame["max_iters"]),
+                            float(frame["huber_delta"]))
+
+
+class PoseAdjuster:
+    """poseBundleAdjust on the device map tables (ms_pose_tables_*): a persistent handle for up to cap_obs triangulated map points per frame,
+    created once per context and used for every frame."""
+
+    def __init__(self, ctx, cap_obs, level_sigma_sq):
+        self.ctx, self.cap_obs = ctx, int(cap_obs)
+        sig = np.ascontiguousarray(level_sigma_sq, np.float32).reshape(-1)
+        self._h = C.c_void_p()
+        ctx.check(lib().ms_pose_tables_create(ctx._h, self.cap_obs, _vp(sig), len(sig), C.byref(self._h)), "ms_pose_tables_create")
+        ctx._adopt(self)
+        self._chi2 = np.zeros(max(self.cap_obs, 1))
+
+    def solve_device(self, kf, flags, live, table, kp, poses, frame, want_chi2=True):
+        """ms_pose_tables_solve on a KeyframeTable, flags / live DevBufs of [n_mp] uint8 (live may be None), a MapPointTable, a
+        KeypointTable and a KeyframePoseTable, which is updated in place.  frame: see pose_tables_frame.  Returns (rc, dict(ran,
+        n_triangulated, pose [7], chi2 [n_triangulated] when ran, stats)) without raising."""
+        if (kp.n_kf, kp.stride) != (kf.n_kf, kf.stride) or poses.n != kf.n_kf:
+            raise ValueError("the keypoint table is %d x %d, the pose table has %d slots, kf_mp is %d x %d" % (kp.n_kf, kp.stride, poses.n, kf.n_kf, kf.stride))
+        F, O = pose_tables_frame(frame), PoseTablesOutC()
+        rc = lib().ms_pose_tables_solve(self._h, _vp(kf.kf_mp), kf.n_kf, kf.stride, _vp(flags), _vp(live), _vp(table.pos), table.n, _vp(kp.x), _vp(kp.y), _vp(kp.octave),
+                                        _vp(poses.pose), C.byref(F), C.byref(O), _vp(self._chi2 if want_chi2 else None))
+        r = O.result
+        n = O.n_triangulated if (rc == 0 and O.ran and want_chi2) else 0
+        return rc, dict(ran=bool(O.ran), n_triangulated=O.n_triangulated, pose=np.array(list(O.pose)), chi2=self._chi2[:n].copy(),
+                        stats=dict(iters=r.iterations, trials=r.trials, stop=r.stopped_early, lam=r.final_lambda, chi2_init=r.chi2_initial, chi2_final=r.chi2_final))
+
+    def solve(self, kf, flags, live, table, kp, poses, frame, want_chi2=True):
+        """solve_device, raising on an error; returns its dict."""
+        rc, res = self.solve_device(kf, flags, live, table, kp, poses, frame, want_chi2)
+        self.ctx.check(rc, "ms_pose_tables_solve")
+        return res
+
+    def problem(self):
+        """ms_pose_tables_problem: the arrays the last gather wrote, as the dict of a BA problem without its edge (a diagnostic)."""
+        cap = max(self.cap_obs, 1)
+        out = dict(pose=np.zeros((2, 7)), point=np.zeros((cap, 3)), obs_point=np.zeros(cap, np.int32), obs_pose=np.zeros(cap, np.int32), obs_uv=np.zeros((cap, 2)),
+                   obs_info=np.zeros(cap))
+        n = C.c_int32(0)
+        self.ctx.check(lib().ms_pose_tables_problem(self._h, _vp(out["pose"]), _vp(out["point"]), _vp(out["obs_point"]), _vp(out["obs_pose"]), _vp(out["obs_uv"]),
+                                                    _vp(out["obs_info"]), C.byref(n)), "ms_pose_tables_problem")
+        for k in ("point", "obs_point", "obs_pose", "obs_uv", "obs_info"):
+            out[k] = out[k][:n.value]
+        out["n"] = n.value
+        return out
+
+    def close(self):
+        if self._h and self.ctx._h:
+            lib().ms_pose_tables_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def create_E21(R1, t1, R2, t2):
     """create_E_21 (openvslam/essential_solver.cc:157-162) with the host mirror's order of operations: [t21]x R21, R21 = R2 R1^T,
     t21 = t2 - R21 t1; float64 [9], row-major."""
@@ -2125,7 +2204,7 @@ class TrackTable:
 
 
 # ---- observation lists on the device (ms_observation_lists) ----
-MS_ERR_INVALID, MS_ERR_CAPACITY = -1, -4
+MS_ERR_INVALID, MS_ERR_CAPACITY, MS_ERR_NUMERIC = -1, -4, -5
 OBS_FROM_ROWS, OBS_FROM_SLOT = 0, 1
 OBS_ALL, OBS_REFRESH, OBS_RETRIANGULATE = 0, 1, 2
 
