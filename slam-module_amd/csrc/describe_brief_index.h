@@ -39,6 +39,8 @@ DBRIEF_HD uint32_t round_bits(float v) {
 }
 
 // byte index + base from the two coordinates' round_bits(); `base` = kIndexBias + whatever the caller adds to every index (the patch's address)
+// (k_describe stores its patch COLUMN-major, 39 columns of 40 bytes, and passes (column, row): the same sum with the roles swapped, and kIndexBias is
+// symmetric in the two -- both coordinates carry the same radius and the same magic bits)
 DBRIEF_HD uint32_t index_from_bits(uint32_t row_bits, uint32_t col_bits, uint32_t base) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __umul24(row_bits, kRowBytes) + col_bits + base;

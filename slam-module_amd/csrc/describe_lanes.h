@@ -88,10 +88,12 @@ DESCRIBE_LANES_FN void lane_moments(const uint32_t (&d)[4], uint32_t col_weights
 }
 #undef DESCRIBE_LANES_FN
 
-// ---- blur taps: s_tab[0 .. 31] horizontal taps [dt][n], s_tab[32 .. 63] vertical taps [dt][n], 16 bytes each (B operands of the i8 MFMA) ----
+// ---- blur taps, pass 1: s_tab[0 .. 31] horizontal taps [dt][n], 16 bytes each (B operands of the i8 MFMA) ----
 // Tile t's operand of lane (n = lane & 15, kg = lane >> 4) is entry [dt = kg - t][n] when dt is 0 or 1 (and, in the last tile, the column
 // 32 + n is one of the patch's 39), all zero otherwise.  [dt][n] = 16 dt + n = lane - 16 t, and entry [1][0] holds no tap at all (its
 // 16 rows start 16 - 0 - 1 >= 15 past the column), in both tables: it is the zero operand, so the lane selects an INDEX and reads once.
+// (tap_table still writes the vertical taps in the same B form behind the horizontal ones; the kernel takes the first half only: pass 2
+// has the taps as its A operand, vert_operand below.)
 constexpr int kTapZeroSlot = 16;
 constexpr int tap_slot(int lane, int t) {
     return ((unsigned)(lane - 16 * t) < 32u && (t < 2 || (lane & 15) <= 6)) ? lane - 16 * t : kTapZeroSlot;
@@ -110,5 +112,31 @@ inline void tap_table(uint32_t *out /* 64 * 4 dwords */) {
                     out[((tab * 2 + dt) * 16 + n) * 4 + j / 4] |= v << (8 * (j % 4));
                 }
 }
+
+// ---- blur taps, pass 2: out = V T' with the vertical taps as the A operand and pass 1's result, as it leaves the accumulators, as B ----
+// Pass 1 leaves T' in the C layout: lane (n, q), accumulator tile m, element r is T' row 16 m + 4 q + r of column n, so the lane's dword m (one byte
+// plane of the four elements) is K bytes 16 q + 4 m .. + 3 of a B operand {dword 0, dword 1, dword 2, 0} whose K index is ordered
+//     k' = 16 q + 4 m + r   <->   T' row 16 m + 4 q + r                     (q = the K group, m = the dword, r = the byte)
+// The order of K is free as long as A is permuted the same way: lane (i = lane & 15, kg = lane >> 4) of A holds, for output row 16 yt + i, at dword m
+// byte r the tap of T' row 16 m + 4 kg + r, w7[16 (m - yt) + 4 kg + r - i] -- non-zero for m - yt = 0 or 1 only, and dependent on (lane, m - yt)
+// alone.  So a lane carries two dwords D0, D1 (vert_operand) and output row tile yt takes them at dword positions yt and yt + 1, zero elsewhere:
+// {D0, D1, 0, 0}, {0, D0, D1, 0}, {0, 0, D0, D1}.  In the last one D1 stands at dword 3 = T' rows 48 .. 63, where B is zero.
+constexpr uint32_t vert_operand(int lane, int dm) {
+    const int w7[7] = {18, 34, 48, 56, 48, 34, 18};
+    const int i = lane & 15, kg = lane >> 4;
+    uint32_t d = 0;
+    for (int r = 0; r < 4; ++r) {
+        const int tap = 16 * dm + 4 * kg + r - i;
+        if (tap >= 0 && tap <= 6) d |= (uint32_t)w7[tap] << (8 * r);
+    }
+    return d;
+}
+constexpr uint32_t vert_operand_dword(int lane, int yt, int m) { return (m == yt || m == yt + 1) ? vert_operand(lane, m - yt) : 0u; }   // dword m of A for row tile yt
+constexpr int vert_k_row(int kg, int m, int r) { return 16 * m + 4 * kg + r; }      // the T' row that K byte 16 kg + 4 m + r stands for
+// The result's C layout: lane (n, q) holds patch rows 16 yt + 4 q .. + 3 of column 16 t + n, one dword of a COLUMN-major patch (39 columns of 40 bytes)
+constexpr int kBlurCols = 39, kBlurColDwords = 10;
+// (16 t + n < 39 and 4 yt + q < 10 for t, yt in 0 .. 2 and a lane of 0 .. 63, written so that the tiles that are valid in every lane carry no test)
+constexpr bool blur_store_valid(int lane, int t, int yt) { return (t < 2 || (lane & 15) < kBlurCols - 32) && (yt < 2 || (lane >> 4) < kBlurColDwords - 8); }
+constexpr int blur_store_dword(int lane, int t, int yt) { return (16 * t + (lane & 15)) * kBlurColDwords + 4 * yt + (lane >> 4); }
 
 }   // namespace describe_lanes

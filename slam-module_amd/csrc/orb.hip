@@ -1228,16 +1228,6 @@ __device__ __forceinline__ DescKp desc_scalars(const DescRec &r) {
     return K;
 }
 typedef int v4i_t __attribute__((ext_vector_type(4)));
-// r[m] in lane row q (the wave's four rows of 16 lanes)  ->  r[q] of lane row m: the 2 x 2 blocks trade places across the wave's halves
-// (v_permlane32_swap: lanes 32-63 of the first operand <-> lanes 0-31 of the second), then each block is transposed across neighbouring rows
-// (v_permlane16_swap: odd rows of the first <-> even rows of the second); lane maps checked on the device by tools/mfma_i8_probe.hip
-__device__ __forceinline__ void transpose4_rows(uint32_t (&r)[4]) {
-    auto s = __builtin_amdgcn_permlane32_swap(r[0], r[2], false, false); r[0] = s[0]; r[2] = s[1];
-    s = __builtin_amdgcn_permlane32_swap(r[1], r[3], false, false); r[1] = s[0]; r[3] = s[1];
-    s = __builtin_amdgcn_permlane16_swap(r[0], r[1], false, false); r[0] = s[0]; r[1] = s[1];
-    s = __builtin_amdgcn_permlane16_swap(r[2], r[3], false, false); r[2] = s[0]; r[3] = s[1];
-}
-
 // amdgpu_waves_per_eu(8, 8): the register allocation aims at 8 waves per SIMD (the kernel is bound by how many keypoints are in flight)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_describe(FrameSrc src, TileLevels TL, describe_strips::Plan plan, const uint4 *__restrict__ moment_tab, const float4 *__restrict__ pattern_f,
                                                   const uint2 *__restrict__ slot_tab, int capacity, int max_tracks, int lk_level, int xcd_runs,
@@ -1259,13 +1249,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // orientation) -- was fetched from global memory where it was needed, behind the LDS fences no load may cross: two exposed round trips in the middle of every
     // wave's chain, and this kernel is bound by the LENGTH of that chain (ablation: prologue + window fetch alone 0.35 of 0.60 ms, no prologue chain -0.07 ms,
     // a quarter fewer vector instructions 0.00 ms).  They are block-wide tables in LDS now, loaded first thing, under the count loads.
-    __shared__ uint4 s_tab[64 + 256];                        // [0..31] horizontal taps (dt, n), [32..63] vertical taps, [64..319] the point pairs [q][lane]
+    __shared__ uint4 s_tab[32 + 256];                        // [0..31] horizontal taps (dt, n), [32..287] the point pairs [q][lane]
     // (every load of the prologue is issued before the first of them is waited for: the stores to LDS stand together in front of the barrier.  All four waves
-    // fetch the tap table and wave 0 stores it -- behind a test of the thread index the load was waited for before the next one was issued)
-    const uint4 tap_v = moment_tab[64 + lane], pair_v = reinterpret_cast<const uint4 *>(pattern_f)[threadIdx.x];
+    // fetch the tap table and half of wave 0 stores it -- behind a test of the thread index the load was waited for before the next one was issued)
+    const uint4 tap_v = moment_tab[64 + (lane & 31)], pair_v = reinterpret_cast<const uint4 *>(pattern_f)[threadIdx.x];
     const uint4 dm = moment_tab[lane];                       // disc mask of the lane's four patch dwords
     const uint32_t dmask[4] = {dm.x, dm.y, dm.z, dm.w};
-    const uint32_t wpack_w = reinterpret_cast<const uint32_t *>(moment_tab + 128)[lane];   // (row, byte) of the lane's first three window pieces (describe_lanes::win_pack)
+    const uint32_t wpack_w = reinterpret_cast<const uint32_t *>(moment_tab + 96)[lane];    // (row, byte) of the lane's first three window pieces (describe_lanes::win_pack)
+    const uint2 vert_w = reinterpret_cast<const uint2 *>(moment_tab + 112)[lane];          // the lane's two dwords of pass 2's A operand, the vertical taps (describe_lanes::vert_operand)
     __shared__ __attribute__((aligned(16))) uint32_t s_patch[4][describe_lanes::kSlabDwords];   // a wave's slab: see below
     uint32_t *const win = &s_patch[wv][0], *const geo = win + kDescGeoDword, *const rec = win + kDescRecDword;
     // Everything a strip's keypoints need from memory is requested here, together, from addresses that depend on the block index and the kernel
@@ -1288,8 +1279,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const int g_pitch = GL.pitch, g_w = GL.w, g_h = GL.h;
     const float g_scale = GL.scale;
     const uint64_t g_off = GL.img_off;
-    if (threadIdx.x < 64) s_tab[threadIdx.x] = tap_v;
-    s_tab[64 + threadIdx.x] = pair_v;
+    if (threadIdx.x < 32) s_tab[threadIdx.x] = tap_v;
+    s_tab[32 + threadIdx.x] = pair_v;
     if (lane < MS_MAX_LEVELS) {
         const uint64_t off = lane == 0 ? (uint64_t)(uintptr_t)src.lvl0 + (uint64_t)f * src.lvl0_frame_stride - (uint64_t)(uintptr_t)slab_f : g_off;
         uint32_t *g = geo + kDescGeoStride * lane;
@@ -1344,8 +1335,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         // What depends on the lane alone is formed anew for every keypoint, as a wave of one keypoint formed it once: carried around the loop in registers
         // (the compiler's choice when it sees that it does not change) it costs the kernel its eighth wave per SIMD.  The empty statements hide that from it.
         int lane_k = lane_w;
-        uint32_t wpack = wpack_w;
-        asm volatile("" : "+v"(lane_k), "+v"(wpack));
+        uint32_t wpack = wpack_w, vd0 = vert_w.x, vd1 = vert_w.y;
+        asm volatile("" : "+v"(lane_k), "+v"(wpack), "+v"(vd0), "+v"(vd1));
         const int lane = lane_k;
         const int pitch = K.pitch, w = K.w, h = K.h, kx = K.x, ky = K.y;
         uint32_t *pb = win;                                  // (pass 1 of the blur has read the whole window into registers before pass 2 writes the first blurred dword)
@@ -1402,30 +1393,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             //   pass 1   T' = (P - 128) Hh: A = window rows as they lie in LDS (lane (i, kg): row 16 m + i, bytes 16 kg .. + 15, one ds_read_b128, xor 0x80 = -128
             //            as signed bytes; the bytes past column 47 and the rows past 44 meet zero weights), B = the taps by column (host table).  T' = T - 32768 fits 16 bits
             //   between  T' leaves the accumulators as its high and low bytes (4 v_perm per tile for both planes); the C layout holds 4 consecutive ROWS of a column per
-            //            lane, the next A operand wants 16 -- a 4 x 4 transpose of dwords across the wave's four 16-lane rows: two v_permlane32_swap + two
-            //            v_permlane16_swap per plane and column tile, no trip through LDS
-            //   pass 2   out^T = T'^T V^T as 256 x (high bytes) + (low bytes - 128): two chained products per 16 x 16 tile (the first starts from 33024 =
-            //            (rounding + the offsets' share) / 256, is shifted up by 8 and becomes the second's C), byte 2 of each sum is the blurred pixel; the
-            //            C layout now holds 4 consecutive pixels of a ROW per lane = one dword of the patch
-            // 27 v_mfma_i32_16x16x64_i8 + ~150 vector instructions per keypoint, where the packed-16-bit form (k_blur's, 60 lanes x 8 rows) took ~350: the kernel sits at
+            //            lane -- and so does a B operand, up to the order of its K index.  No lane exchanges anything: the lane's three dwords of a byte plane ARE
+            //            its B operand of pass 2, {d[0], d[1], d[2], 0}, with K byte 16 q + 4 m + r standing for T' row 16 m + 4 q + r (describe_lanes.h)
+            //   pass 2   out = V T' as 256 x (high bytes) + (low bytes - 128): A = the vertical taps in the same K order, two dwords per lane from the host's table at
+            //            dword positions yt and yt + 1; two chained products per 16 x 16 tile (the first starts from 33024 = (rounding + the offsets' share) / 256,
+            //            is shifted up by 8 and becomes the second's C), byte 2 of each sum is the blurred pixel; the C layout holds 4 consecutive pixels of a
+            //            COLUMN per lane = one dword of the patch, which is stored column-major (39 columns of 40 bytes; the BRIEF index swaps its arguments)
+            // 27 v_mfma_i32_16x16x64_i8 + ~155 vector instructions per keypoint (~195 with the transposes of the A form), where the packed-16-bit form (k_blur's, 60 lanes x 8 rows) took ~350: the kernel sits at
             // the VALU issue limit and the matrix pipe was idle.
             const int n = lane & 15, q = lane >> 4;
-            // B operands of tile t: lane (n, kg) holds rows 16 kg .. + 15 of column 16 t + n -- non-zero only for kg - t = 0 or 1, and for columns <= 38
+            // B operands of pass 1, tile t: lane (n, kg) holds rows 16 kg .. + 15 of column 16 t + n -- non-zero only for kg - t = 0 or 1, and for columns <= 38
             // -- entry lane - 16 t of the table, or the table's all-zero entry: the lane selects the index, not the four dwords (describe_lanes::tap_slot)
-            auto taps = [&](int base, int t) { return __builtin_bit_cast(v4i_t, s_tab[base + describe_lanes::tap_slot(lane, t)]); };
-            v4i_t Aw[3], Vb[3];                              // the window rows as pass 1's A operands (read BEFORE the first blurred dword takes the window's place), the vertical taps
+            auto taps = [&](int t) { return __builtin_bit_cast(v4i_t, s_tab[describe_lanes::tap_slot(lane, t)]); };
+            v4i_t Aw[3];                                     // the window rows as pass 1's A operands (read BEFORE the first blurred dword takes the window's place)
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 uint4 a4 = *reinterpret_cast<const uint4 *>(win + (16 * m + n) * 12 + 4 * q);
                 a4.x ^= 0x80808080u; a4.y ^= 0x80808080u; a4.z ^= 0x80808080u; a4.w ^= 0x80808080u;
                 Aw[m] = __builtin_bit_cast(v4i_t, a4);
-                Vb[m] = taps(32, m);
             }
-            // one column tile at a time (pass 1 -> bytes -> transposes -> pass 2 -> store): the three tiles' intermediates side by side cost the kernel its eighth wave per SIMD
+            const int d0 = (int)vd0, d1 = (int)vd1;
+            const v4i_t Va[3] = {{d0, d1, 0, 0}, {0, d0, d1, 0}, {0, 0, d0, d1}};     // the vertical taps of row tiles 0 .. 2 (in the last, d1 meets B's zero dword)
+            // one column tile at a time (pass 1 -> bytes -> pass 2 -> store): the three tiles' intermediates side by side cost the kernel its eighth wave per SIMD
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                const v4i_t Hb = taps(0, t), zero = {0, 0, 0, 0};
-                uint32_t hd[4], ld[4];
+                const v4i_t Hb = taps(t), zero = {0, 0, 0, 0};
+                uint32_t hd[3], ld[3];
 #pragma unroll
                 for (int m = 0; m < 3; ++m) {
                     const v4i_t T = __builtin_amdgcn_mfma_i32_16x16x64_i8(Aw[m], Hb, zero, 0, 0, 0);
@@ -1434,18 +1427,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                     hd[m] = __builtin_amdgcn_perm(x23, x01, 0x05040100u);
                     ld[m] = __builtin_amdgcn_perm(x23, x01, 0x07060302u) ^ 0x80808080u;
                 }
-                hd[3] = 0; ld[3] = 0;                                   // rows 48 .. 63: zero weights AND zero data
-                transpose4_rows(hd); transpose4_rows(ld);
-                const v4i_t A2h = {(int)hd[0], (int)hd[1], (int)hd[2], (int)hd[3]}, A2l = {(int)ld[0], (int)ld[1], (int)ld[2], (int)ld[3]};
+                const v4i_t B2h = {(int)hd[0], (int)hd[1], (int)hd[2], 0}, B2l = {(int)ld[0], (int)ld[1], (int)ld[2], 0};   // K bytes 12 .. 15 of a group = T' rows 48 .. 63: zero data
 #pragma unroll
                 for (int yt = 0; yt < 3; ++yt) {
-                    v4i_t acc = {33024, 33024, 33024, 33024};
-                    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A2h, Vb[yt], acc, 0, 0, 0);
-                    acc <<= 8;
-                    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A2l, Vb[yt], acc, 0, 0, 0);
-                    const int y = 16 * yt + n;
-                    if (y < 39 && 4 * t + q < 10)                       // lane (n, q): pixels 16 t + 4 q .. + 3 of patch row y (byte 2 of each sum; the sums stay below 2^24)
-                        pb[y * 10 + 4 * t + q] = __builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x0C0C0602u) | __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x06020C0Cu);
+                    // (33024 + the high sums) << 8 with the start value behind the product, in the shift's own instruction (v_lshl_add_u32): the first product
+                    // starts from the inline zero, and no four registers hold the constant
+                    v4i_t acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(Va[yt], B2h, zero, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[r] = (int)(((uint32_t)acc[r] << 8) + (33024u << 8));
+                    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(Va[yt], B2l, acc, 0, 0, 0);
+                    if (describe_lanes::blur_store_valid(lane, t, yt))      // lane (n, q): rows 16 yt + 4 q .. + 3 of patch column 16 t + n (byte 2 of each sum; the sums stay below 2^24)
+                        pb[describe_lanes::blur_store_dword(lane, t, yt)] = __builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x0C0C0602u) | __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x06020C0Cu);
                 }
             }
         }
@@ -1467,7 +1459,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         unsigned long long bits[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float4 pt = __builtin_bit_cast(float4, s_tab[64 + q * 64 + lane]);             // the test's two points, already float
+            const float4 pt = __builtin_bit_cast(float4, s_tab[32 + q * 64 + lane]);             // the test's two points, already float
             const float x1 = pt.x, y1 = pt.y, x2 = pt.z, y2 = pt.w;
             // rows and columns + 19 lie in 0 .. 38 (the pattern stays inside the 39 x 39 patch under every rotation).  The products and the add / sub are the
             // reference's, one rounding each; rounding to the integer is one more float add, and the conversion, both + 19 and the patch's LDS address are one
@@ -1476,7 +1468,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const uint32_t c1 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x1, ca), __fmul_rn(y1, nsa)));
             const uint32_t r2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, sa), __fmul_rn(y2, ca)));
             const uint32_t c2 = describe_brief_index::round_bits(__fadd_rn(__fmul_rn(x2, ca), __fmul_rn(y2, nsa)));
-            const uint32_t i1 = describe_brief_index::index_from_bits(r1, c1, pbase), i2 = describe_brief_index::index_from_bits(r2, c2, pbase);
+            const uint32_t i1 = describe_brief_index::index_from_bits(c1, r1, pbase), i2 = describe_brief_index::index_from_bits(c2, r2, pbase);     // (column, row): the patch is column-major
             bits[q] = __ballot(*(const lds_u8_t *)(uintptr_t)i1 < *(const lds_u8_t *)(uintptr_t)i2);
         }
         const uint64_t o = (uint64_t)f * capacity + K.slot;        // (slot0 + 4 k is the VISIT position)
@@ -1718,16 +1710,20 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
         };
         // disc mask of the 31 x 31 orientation patch as k_describe's lanes hold it: dword i = lane + 64 t (the t-th of the lane) covers columns 4 (i & 7) .. + 3 of row
         // i >> 3; a byte is kept when |u| <= u_max[|v|] (orb_extractor.cpp:174-186, :259-271), the 32nd column and row are cleared
-        std::vector<uint32_t> mt(64 * 4 + 64 * 4 + 64, 0u);
+        std::vector<uint32_t> mt(64 * 4 + 32 * 4 + 64 + 64 * 2, 0u);
         for (int lane = 0; lane < 64; ++lane)
             for (int t = 0; t < 4; ++t) mt[lane * 4 + t] = describe_lanes::disc_mask(lane, t, G.umax);
-        // behind it, k_describe's blur as matrix operands (B of v_mfma_i32_16x16x64_i8: lane (n, kg) holds rows k = 16 kg .. + 15 of column 16 t + n, one byte each): the taps
-        // 18 34 48 56 48 34 18 by patch column x -- window byte k contributes to x when 0 <= k - x - 1 <= 6 -- and by patch row y (window row k, 0 <= k - y <= 6).  Only
-        // dt = kg - t = 0 and 1 can be non-zero, and the pattern depends on (dt, n) alone: [table 0 = horizontal, 1 = vertical][dt][n][4 dwords]
-        // (describe_lanes::tap_table; entry [1][0] of either table is all zero and serves as the zero operand), and behind that the packed (row, byte) of every lane's
-        // first three window pieces
-        describe_lanes::tap_table(&mt[64 * 4]);
-        for (int lane = 0; lane < 64; ++lane) mt[64 * 4 + 64 * 4 + lane] = describe_lanes::win_pack(lane);
+        // behind it, pass 1 of k_describe's blur as matrix operands (B of v_mfma_i32_16x16x64_i8: lane (n, kg) holds rows k = 16 kg .. + 15 of column 16 t + n, one byte each):
+        // the taps 18 34 48 56 48 34 18 by patch column x -- window byte k contributes to x when 0 <= k - x - 1 <= 6.  Only dt = kg - t = 0 and 1 can be non-zero, and the
+        // pattern depends on (dt, n) alone: [dt][n][4 dwords], the horizontal half of describe_lanes::tap_table (entry [1][0] is all zero and serves as the zero operand);
+        // behind that the packed (row, byte) of every lane's first three window pieces, and the lane's two dwords of pass 2's A operand (the vertical taps)
+        uint32_t taps[64 * 4];
+        describe_lanes::tap_table(taps);
+        std::copy(taps, taps + 32 * 4, &mt[64 * 4]);
+        for (int lane = 0; lane < 64; ++lane) {
+            mt[64 * 4 + 32 * 4 + lane] = describe_lanes::win_pack(lane);
+            for (int dm = 0; dm < 2; ++dm) mt[64 * 4 + 32 * 4 + 64 + 2 * lane + dm] = describe_lanes::vert_operand(lane, dm);
+        }
         std::vector<float> pf(1024);
         for (int i = 0; i < 1024; ++i) pf[i] = (float)pattern[i];
         if (hipMalloc(reinterpret_cast<void **>(&o->d_moment_tab), mt.size() * 4) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&o->d_pattern_f), pf.size() * 4) != hipSuccess ||
