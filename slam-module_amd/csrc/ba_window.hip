@@ -171,88 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_apply_vertices(const ApplyArgs A) {
     if (i < A.n_local && (local || i == A.current)) write_pose(A.pose + 7 * (size_t)i, A.kf_pose + 12 * (size_t)A.local_slot[i]);
 }
 
-// ------------------------------------------------------------------------------------------------ validation
-#define WL_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "ba window lists: " __VA_ARGS__)
-
-// the local keyframes: in range, distinct, the current one among them.  `what` = the message prefix.
-int check_local(const char *what, const int32_t *local_slot, int n_local, int n_kf, int current_index, char *why, size_t bytes) {
-    if (n_local > 0 && !local_slot) return ms_why(MS_ERR_INVALID, why, bytes, "%s: missing array (local_slot)", what);
-    int bad = 0;
-    if (!ms_distinct_in_range(local_slot, n_local, n_kf, &bad)) {
-        if (bad < 0) return ms_why(MS_ERR_INVALID, why, bytes, "%s: local slot %d is listed twice", what, -1 - bad);
-        return ms_why(MS_ERR_INVALID, why, bytes, "%s: local slot %d outside [0, %d)", what, local_slot[bad], n_kf);
-    }
-    if (current_index < 0 || current_index >= n_local) return ms_why(MS_ERR_INVALID, why, bytes, "%s: current index %d outside [0, %d)", what, current_index, n_local);
-    return MS_OK;
-}
-
-int check_lists_args(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const ms_obs_lists *lists, int n_rows, int n_obs, const int32_t *local_slot, int n_local,
-                     int current_index, const ms_pinhole *kf_cam, const int32_t *kf_focal, const float *level_sigma_sq, int n_levels, const double *pose, const double *point,
-                     const int32_t *obs_point, const int32_t *obs_pose, const double *obs_uv, const double *obs_info, int cap_point, int cap_edge,
-                     const ms_ba_window_dev *window, const int32_t *n_edge, const int32_t *n_current, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_rows < 0 || n_obs < 0 || n_local < 0 || cap_point < 0 || cap_edge < 0)
-        WL_INVALID("negative size (%d slots, %d map points, %d rows, %d observations, %d local keyframes, capacities %d / %d)", n_kf, n_mp, n_rows, n_obs, n_local, cap_point,
-                   cap_edge);
-    if (n_levels < 1 || n_levels > MS_TRI_MAX_LEVELS) WL_INVALID("%d levels outside [1, %d]", n_levels, MS_TRI_MAX_LEVELS);
-    if (!n_edge || !n_current) WL_INVALID("missing array (n_edge or n_current)");
-    if (!kf_pose || !kf_cam || !kf_focal || !level_sigma_sq || !pose) WL_INVALID("missing array (kf_pose, kf_cam, kf_focal, level_sigma_sq or pose)");
-    if (n_rows > 0 && (!mp_pos || !lists || !lists->rows || !lists->obs_start)) WL_INVALID("missing array (mp_pos, rows or obs_start)");
-    if (n_obs > 0 && (n_rows == 0 || !lists->obs_kf || !lists->obs_kp || !lists->obs_x || !lists->obs_y || !lists->obs_octave))
-        WL_INVALID("missing array (obs_kf, obs_kp, obs_x, obs_y or obs_octave)");
-    if (cap_point > 0 && !point) WL_INVALID("missing array (point)");
-    if (cap_edge > 0 && (!obs_point || !obs_pose || !obs_uv || !obs_info || !window || !window->edge_slot || !window->edge_kp || !window->edge_point))
-        WL_INVALID("missing array (obs_point, obs_pose, obs_uv, obs_info or the window's edge arrays)");
-    int rc;
-    if ((rc = check_local("ba window lists", local_slot, n_local, n_kf, current_index, why, bytes))) return rc;
-    for (int k = 0; k < n_local; ++k) {
-        const ms_pinhole &K = kf_cam[local_slot[k]];
-        if (!(std::isfinite(K.fx) && K.fx > 0.0 && std::isfinite(K.fy) && K.fy > 0.0)) WL_INVALID("the camera of local slot %d has fx %g, fy %g", local_slot[k], K.fx, K.fy);
-        if (!std::isfinite(K.cx) || !std::isfinite(K.cy)) WL_INVALID("the camera of local slot %d has cx %g, cy %g", local_slot[k], K.cx, K.cy);
-    }
-    for (int l = 0; l < n_levels; ++l)
-        if (!(std::isfinite(level_sigma_sq[l]) && level_sigma_sq[l] > 0.f)) WL_INVALID("level_sigma_sq[%d] = %g", l, (double)level_sigma_sq[l]);
-    return MS_OK;
-}
-
-#define WA_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "ba window apply: " __VA_ARGS__)
-
-int check_apply_args(const int32_t *kf_mp, int n_kf, int stride, const double *mp_pos, const uint8_t *mp_flags, const int32_t *n_obs, int n_mp, const double *kf_pose,
-                     const double *pose, int n_pose, const double *point, const double *chi2, const ms_ba_window_dev *window, int n_edge, const int32_t *rows, int n_rows,
-                     const int32_t *local_slot, int n_local, int current_index, int mode, const int32_t *erased_edge, int cap_erased, const int32_t *n_erased,
-                     const int32_t *n_stale, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_pose < 0 || n_edge < 0 || n_rows < 0 || n_local < 0 || cap_erased < 0)
-        WA_INVALID("negative size (%d slots, %d map points, %d poses, %d edges, %d rows, %d local keyframes, capacity %d)", n_kf, n_mp, n_pose, n_edge, n_rows, n_local, cap_erased);
-    if (stride < 1) WA_INVALID("stride %d", stride);
-    if (mode != MS_BA_APPLY_LOCAL && mode != MS_BA_APPLY_NEIGHBOR) WA_INVALID("mode %d", mode);
-    if (!n_erased || !n_stale) WA_INVALID("missing array (n_erased or n_stale)");
-    if (!kf_pose || !pose) WA_INVALID("missing array (kf_pose or pose)");
-    if (n_rows > 0 && (!mp_pos || !point || !rows)) WA_INVALID("missing array (mp_pos, point or rows)");
-    if (n_pose < n_local) WA_INVALID("%d poses for %d local keyframes", n_pose, n_local);
-    if (mode == MS_BA_APPLY_LOCAL) {
-        if (!kf_mp || !mp_flags || !n_obs) WA_INVALID("missing array (kf_mp, mp_flags or n_obs)");
-        if (n_edge > 0 && (!chi2 || !window || !window->edge_slot || !window->edge_kp || !window->edge_point)) WA_INVALID("missing array (chi2 or the window's edge arrays)");
-        if (n_edge > 0 && n_rows == 0) WA_INVALID("%d edges without a row", n_edge);
-        if (cap_erased > 0 && !erased_edge) WA_INVALID("missing array (erased_edge)");
-    }
-    return check_local("ba window apply", local_slot, n_local, n_kf, current_index, why, bytes);
-}
-
 }  // namespace
-
-extern "C" int ms_ba_window_lists_check(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const ms_obs_lists *lists, int n_rows, int n_obs,
-                                        const int32_t *local_slot, int n_local, int current_index, const ms_pinhole *kf_cam, const int32_t *kf_focal,
-                                        const float *level_sigma_sq, int n_levels, const double *pose, const double *point, const int32_t *obs_point, const int32_t *obs_pose,
-                                        const double *obs_uv, const double *obs_info, int cap_point, int cap_edge, const ms_ba_window_dev *window, const int32_t *n_edge,
-                                        const int32_t *n_current, char *why, size_t why_bytes) {
-    int rc;
-    if ((rc = check_lists_args(kf_pose, n_kf, mp_pos, n_mp, lists, n_rows, n_obs, local_slot, n_local, current_index, kf_cam, kf_focal, level_sigma_sq, n_levels, pose, point,
-                               obs_point, obs_pose, obs_uv, obs_info, cap_point, cap_edge, window, n_edge, n_current, why, why_bytes)))
-        return rc;
-    if (n_kf > MS_COVIS_MAX_KF || n_mp >= MS_COVIS_MAX_MP || n_rows > MS_TRI_MAX_ROWS || n_obs > MS_TRI_MAX_OBS)
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "ba window lists: %d slots / %d map points / %d rows / %d observations, caps %d / below %d / %d / %d", n_kf, n_mp, n_rows,
-                      n_obs, MS_COVIS_MAX_KF, MS_COVIS_MAX_MP, MS_TRI_MAX_ROWS, MS_TRI_MAX_OBS);
-    return MS_OK;
-}
 
 extern "C" int ms_ba_window_lists(ms_ctx *c, const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const ms_obs_lists *lists, int n_rows, int n_obs,
                                   const int32_t *local_slot, int n_local, int current_index, const ms_pinhole *kf_cam, const int32_t *kf_focal, const float *level_sigma_sq,
@@ -332,20 +251,6 @@ extern "C" int ms_ba_window_lists(ms_ctx *c, const double *kf_pose, int n_kf, co
     l_point.get(hd, 0, point, 3 * (size_t)n_rows);
     const size_t ne = (size_t)head[0];
     l_opoint.get(hd, 0, obs_point, ne); l_opose.get(hd, 0, obs_pose, ne); l_uv.get(hd, 0, obs_uv, 2 * ne); l_info.get(hd, 0, obs_info, ne);
-    return MS_OK;
-}
-
-extern "C" int ms_ba_window_apply_check(const int32_t *kf_mp, int n_kf, int stride, const double *mp_pos, const uint8_t *mp_flags, const int32_t *n_obs, int n_mp,
-                                        const double *kf_pose, const double *pose, int n_pose, const double *point, const double *chi2, const ms_ba_window_dev *window,
-                                        int n_edge, const int32_t *rows, int n_rows, const int32_t *local_slot, int n_local, int current_index, int mode,
-                                        const int32_t *erased_edge, int cap_erased, const int32_t *n_erased, const int32_t *n_stale, char *why, size_t why_bytes) {
-    int rc;
-    if ((rc = check_apply_args(kf_mp, n_kf, stride, mp_pos, mp_flags, n_obs, n_mp, kf_pose, pose, n_pose, point, chi2, window, n_edge, rows, n_rows, local_slot, n_local,
-                               current_index, mode, erased_edge, cap_erased, n_erased, n_stale, why, why_bytes)))
-        return rc;
-    if (ms_map_over_capacity(n_kf, stride, n_mp, 0) || n_rows > MS_TRI_MAX_ROWS || n_edge > MS_TRI_MAX_OBS)
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "ba window apply: %d slots / stride %d / %d map points / %d rows / %d edges, caps %d / %d / below %d / %d / %d", n_kf,
-                      stride, n_mp, n_rows, n_edge, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_TRI_MAX_ROWS, MS_TRI_MAX_OBS);
     return MS_OK;
 }
 

@@ -191,22 +191,6 @@ __global__ __launch_bounds__(kBlock) void k_union_pack(const UnionArgs A) {
 
 }  // namespace
 
-extern "C" int ms_covisibility_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const ms_covis_query *queries, int n_q,
-                                     const int32_t *neighbours, const int32_t *n_neighbours, char *why, size_t why_bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_q < 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: negative count (%d slots, %d map points, %d queries)", n_kf, n_mp, n_q);
-    if (stride < 1) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: stride %d", stride);
-    if (n_q == 0) return MS_OK;
-    if (!kf_mp || !queries || !neighbours || !n_neighbours) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: missing array");
-    for (int q = 0; q < n_q; ++q) {
-        const ms_covis_query &Q = queries[q];
-        if (Q.slot < 0 || Q.slot >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: query %d: slot %d outside [0, %d)", q, Q.slot, n_kf);
-        if (Q.force_a < -1 || Q.force_a >= n_kf || Q.force_b < -1 || Q.force_b >= n_kf)
-            return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: query %d: forced slots %d, %d outside [-1, %d)", q, Q.force_a, Q.force_b, n_kf);
-        if (Q.require && !mp_flags) return ms_why(MS_ERR_INVALID, why, why_bytes, "covisibility: query %d requires flags 0x%x and there is no mp_flags", q, (unsigned)Q.require);
-    }
-    return MS_OK;
-}
-
 extern "C" int ms_covisibility(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const ms_covis_query *queries, int n_q,
                                int32_t *count, int32_t *neighbours, int32_t *n_neighbours) {
     if (!c) return MS_ERR_INVALID;
@@ -258,25 +242,6 @@ extern "C" int ms_covisibility(ms_ctx *c, const int32_t *kf_mp, int n_kf, int st
     MS_HIP(c, hipMemcpyAsync(l_down.at(hs), l_nn.at(ds), l_nn.bytes(), hipMemcpyDeviceToHost, c->stream));
     MS_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(n_neighbours, l_down.at(hs), l_down.bytes());
-    return MS_OK;
-}
-
-extern "C" int ms_map_point_union_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, int n_mp, const int32_t *kf_list, int n_list,
-                                        const ms_union_problem *problems, int n_u, const int32_t *rows, const int32_t *n_rows, char *why, size_t why_bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_list < 0 || n_u < 0)
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: negative count (%d slots, %d map points, %d list entries, %d problems)", n_kf, n_mp, n_list, n_u);
-    if (stride < 1) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: stride %d", stride);
-    if (n_u == 0) return MS_OK;
-    if (!kf_mp || !problems || !rows || !n_rows || (n_list > 0 && !kf_list)) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: missing array");
-    for (int u = 0; u < n_u; ++u) {
-        const ms_union_problem &P = problems[u];
-        if (P.count < 0 || P.first < 0 || (long long)P.first + P.count > n_list)
-            return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: problem %d: slice [%d, %d + %d) outside [0, %d)", u, P.first, P.first, P.count, n_list);
-        if (P.exclude_slot < -1 || P.exclude_slot >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: problem %d: exclude slot %d outside [-1, %d)", u, P.exclude_slot, n_kf);
-        if (P.require && !mp_flags) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: problem %d requires flags 0x%x and there is no mp_flags", u, (unsigned)P.require);
-        for (int i = P.first; i < P.first + P.count; ++i)       // list entries in no slice are never read, so only the slices are checked
-            if (kf_list[i] < 0 || kf_list[i] >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "map point union: list entry %d: slot %d outside [0, %d)", i, kf_list[i], n_kf);
-    }
     return MS_OK;
 }
 

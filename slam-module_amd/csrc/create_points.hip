@@ -208,89 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_unbound_mask(const int32_t *kf_mp, c
     if (j < S.n_kp) S.usable[j] = (uint8_t)!((uint32_t)kf_mp[(size_t)S.slot * stride + j] < (uint32_t)n_mp);
 }
 
-#define CL_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "create points lists: " __VA_ARGS__)
-
-int check_lists_args(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int n_mp, const int32_t *kf_id, const float *kp_x, const float *kp_y,
-                     const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, int cur, int adj, const int32_t *matched, int n_kp1, int n_kp2,
-                     const int32_t *new_rows, int n_new, int n_levels, const ms_obs_lists *out, int cap_rows, int cap_obs, const int32_t *n_matches, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_kp1 < 0 || n_kp2 < 0 || n_new < 0 || cap_rows < 0 || cap_obs < 0 || n_levels < 0)
-        CL_INVALID("negative size (%d slots, %d map points, %d and %d keypoints, %d new rows, capacities %d / %d, %d levels)", n_kf, n_mp, n_kp1, n_kp2, n_new, cap_rows, cap_obs, n_levels);
-    if (stride < 1) CL_INVALID("stride %d", stride);
-    if (!n_matches || !kf_id) CL_INVALID("missing array (n_matches or kf_id)");
-    if (cur < 0 || cur >= n_kf) CL_INVALID("slot %d outside [0, %d)", cur, n_kf);
-    if (adj < 0 || adj >= n_kf) CL_INVALID("slot %d outside [0, %d)", adj, n_kf);
-    if (cur == adj) CL_INVALID("the current and the adjacent keyframe are both slot %d", cur);
-    if (kf_id[cur] < 0) CL_INVALID("slot %d has kf_id %d", cur, kf_id[cur]);
-    if (kf_id[adj] < 0) CL_INVALID("slot %d has kf_id %d", adj, kf_id[adj]);
-    if (kf_id[cur] == kf_id[adj]) CL_INVALID("slots %d and %d both have kf_id %d", cur, adj, kf_id[cur]);
-    if (n_kp1 > stride || n_kp2 > stride) CL_INVALID("%d keypoints in a table of stride %d", n_kp1 > stride ? n_kp1 : n_kp2, stride);
-    if (n_levels > MS_TRI_MAX_LEVELS) CL_INVALID("%d levels outside [0, %d]", n_levels, MS_TRI_MAX_LEVELS);
-    if (!kf_mp || (n_mp > 0 && !mp_live)) CL_INVALID("missing array (kf_mp or mp_live)");
-    if (n_kp1 > 0 && !matched) CL_INVALID("missing array (matched)");
-    if (n_new > 0 && !new_rows) CL_INVALID("missing array (new_rows)");
-    if (!out || !out->rows || !out->obs_start) CL_INVALID("missing array (rows or obs_start)");
-    if ((out->obs_x && !kp_x) || (out->obs_y && !kp_y) || ((out->obs_octave || out->first_octave || n_levels > 0) && !kp_octave) || (out->obs_depth && !kp_depth) ||
-        (out->obs_desc && !kf_desc_base))
-        CL_INVALID("missing array (an output is asked for whose table is missing)");
-    int bad = 0;
-    if (!ms_distinct_in_range(new_rows, n_new, n_mp, &bad)) {
-        if (bad < 0) CL_INVALID("new row %d is listed twice", -1 - bad);
-        CL_INVALID("new row %d outside [0, %d)", new_rows[bad], n_mp);
-    }
-    return MS_OK;
-}
-
-#define CB_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "create points bind: " __VA_ARGS__)
-
-int check_bind_args(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const uint32_t *mp_desc, int n_mp, const uint32_t *desc_pool,
-                    int n_pool, int cur, int adj, const ms_obs_lists *lists, const int32_t *match_kp1, const int32_t *match_kp2, int n_matches, int n_kp1, int n_kp2,
-                    const int32_t *n_created, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_pool < 0 || n_matches < 0 || n_kp1 < 0 || n_kp2 < 0)
-        CB_INVALID("negative size (%d slots, %d map points, %d pool descriptors, %d matches, %d and %d keypoints)", n_kf, n_mp, n_pool, n_matches, n_kp1, n_kp2);
-    if (stride < 1) CB_INVALID("stride %d", stride);
-    if (n_kp1 > stride || n_kp2 > stride) CB_INVALID("%d keypoints in a table of stride %d", n_kp1 > stride ? n_kp1 : n_kp2, stride);
-    if (!n_created) CB_INVALID("missing array (n_created)");
-    if (cur < 0 || cur >= n_kf) CB_INVALID("slot %d outside [0, %d)", cur, n_kf);
-    if (adj < 0 || adj >= n_kf) CB_INVALID("slot %d outside [0, %d)", adj, n_kf);
-    if (cur == adj) CB_INVALID("the current and the adjacent keyframe are both slot %d", cur);
-    if (!kf_mp || !mp_flags || !mp_live) CB_INVALID("missing array (kf_mp, mp_flags or mp_live)");
-    if (n_matches > 0 && (!lists || !lists->rows || !match_kp1 || !match_kp2)) CB_INVALID("missing array (rows, match_kp1 or match_kp2)");
-    if (n_matches > 0 && desc_pool && lists->obs_desc && !mp_desc) CB_INVALID("missing array (mp_desc)");
-    if ((reinterpret_cast<uintptr_t>(mp_desc) | reinterpret_cast<uintptr_t>(desc_pool)) & 15u) CB_INVALID("descriptor arrays must be 16-byte aligned");
-    return MS_OK;
-}
-
-#define UM_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "unbound mask: " __VA_ARGS__)
-
-int check_mask_args(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *slots, const int32_t *n_kp, uint8_t *const *usable, int n_slots, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_slots < 0) UM_INVALID("negative size (%d slots, %d map points, %d listed slots)", n_kf, n_mp, n_slots);
-    if (stride < 1) UM_INVALID("stride %d", stride);
-    if (n_slots > 0 && (!kf_mp || !slots || !n_kp || !usable)) UM_INVALID("missing array (kf_mp, slots, n_kp or usable)");
-    for (int s = 0; s < n_slots; ++s) {
-        if (slots[s] < 0 || slots[s] >= n_kf) UM_INVALID("slot %d outside [0, %d)", slots[s], n_kf);
-        if (n_kp[s] < 0 || n_kp[s] > stride) UM_INVALID("%d keypoints in a table of stride %d", n_kp[s], stride);
-        if (n_kp[s] > 0 && !usable[s]) UM_INVALID("missing array (usable of slot %d)", slots[s]);
-    }
-    return MS_OK;
-}
-
 }  // namespace
-
-extern "C" int ms_create_points_lists_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int n_mp, const int32_t *kf_id, const float *kp_x,
-                                            const float *kp_y, const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, int cur, int adj,
-                                            const int32_t *matched, int n_kp1, int n_kp2, const int32_t *new_rows, int n_new, int n_levels, const ms_obs_lists *lists,
-                                            int cap_rows, int cap_obs, const int32_t *match_kp1, const int32_t *match_kp2, const int32_t *n_matches, char *why,
-                                            size_t why_bytes) {
-    int rc;
-    if ((rc = check_lists_args(kf_mp, n_kf, stride, mp_live, n_mp, kf_id, kp_x, kp_y, kp_octave, kp_depth, kf_desc_base, cur, adj, matched, n_kp1, n_kp2, new_rows, n_new,
-                               n_levels, lists, cap_rows, cap_obs, n_matches, why, why_bytes)))
-        return rc;
-    (void)match_kp1; (void)match_kp2;                        // each may be NULL
-    if (ms_map_over_capacity(n_kf, stride, n_mp, 0))
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "create points lists: %d slots / stride %d / %d map points, caps %d / %d / below %d", n_kf, stride, n_mp, MS_COVIS_MAX_KF,
-                      MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP);
-    return MS_OK;
-}
 
 extern "C" int ms_create_points_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int n_mp, const int32_t *kf_id, const float *kp_x,
                                       const float *kp_y, const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, int cur, int adj,
@@ -338,22 +256,6 @@ extern "C" int ms_create_points_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf,
     return MS_OK;
 }
 
-extern "C" int ms_create_points_bind_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const uint32_t *mp_desc,
-                                           const int32_t *n_obs, const int32_t *mp_track, int n_mp, const uint32_t *desc_pool, int n_pool, int cur, int adj,
-                                           const ms_obs_lists *lists, const int32_t *match_kp1, const int32_t *match_kp2, int n_matches, int n_kp1, int n_kp2,
-                                           const uint8_t *usable1, const uint8_t *usable2, const int32_t *created_rows, const int32_t *created_kp1,
-                                           const int32_t *created_kp2, const int32_t *n_created, char *why, size_t why_bytes) {
-    int rc;
-    if ((rc = check_bind_args(kf_mp, n_kf, stride, mp_flags, mp_live, mp_desc, n_mp, desc_pool, n_pool, cur, adj, lists, match_kp1, match_kp2, n_matches, n_kp1, n_kp2, n_created,
-                              why, why_bytes)))
-        return rc;
-    (void)n_obs; (void)mp_track; (void)usable1; (void)usable2; (void)created_rows; (void)created_kp1; (void)created_kp2;      // each may be NULL
-    if (ms_map_over_capacity(n_kf, stride, n_mp, 0) || n_matches > MS_COVIS_MAX_STRIDE)
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "create points bind: %d slots / stride %d / %d map points / %d matches, caps %d / %d / below %d / %d", n_kf, stride, n_mp,
-                      n_matches, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_STRIDE);
-    return MS_OK;
-}
-
 extern "C" int ms_create_points_bind(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, uint8_t *mp_live, uint32_t *mp_desc, int32_t *n_obs,
                                      int32_t *mp_track, int n_mp, const uint32_t *desc_pool, int n_pool, int cur, int adj, const ms_obs_lists *lists,
                                      const int32_t *match_kp1, const int32_t *match_kp2, int n_matches, int n_kp1, int n_kp2, uint8_t *usable1, uint8_t *usable2,
@@ -384,16 +286,6 @@ extern "C" int ms_create_points_bind(ms_ctx *c, int32_t *kf_mp, int n_kf, int st
     const int32_t *down = l_down.at(W.host);
     if (down[1]) return ms_fail(c, MS_ERR_INVALID, "create points bind: %d entries name a row, a keypoint or a descriptor outside the tables (nothing written)", down[1]);
     *n_created = down[0];
-    return MS_OK;
-}
-
-extern "C" int ms_unbound_mask_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *slots, const int32_t *n_kp, uint8_t *const *usable, int n_slots,
-                                     char *why, size_t why_bytes) {
-    int rc;
-    if ((rc = check_mask_args(kf_mp, n_kf, stride, n_mp, slots, n_kp, usable, n_slots, why, why_bytes))) return rc;
-    if (ms_map_over_capacity(n_kf, stride, n_mp, n_slots))
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "unbound mask: %d slots / stride %d / %d map points / %d listed slots, caps %d / %d / below %d / %d", n_kf, stride, n_mp,
-                      n_slots, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_QUERIES);
     return MS_OK;
 }
 

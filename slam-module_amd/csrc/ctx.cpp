@@ -62,8 +62,6 @@ int ms_scratch(ms_ctx *c, size_t bytes, void **out) {
     return MS_OK;
 }
 
-std::atomic<long long> g_ms_host_allocs{0};
-
 int ms_grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
     if (bytes <= cap) return MS_OK;
     if (p) {
@@ -78,18 +76,6 @@ int ms_grow(ms_ctx *c, void *&p, size_t &cap, size_t bytes, bool pinned) {
     cap = want;
     ++g_ms_host_allocs;
     return MS_OK;
-}
-
-bool ms_distinct_in_range(const int32_t *idx, int n, int limit, int *bad) {
-    for (int i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= limit) { *bad = i; return false; }
-    thread_local std::vector<int32_t> tmp;
-    if (tmp.capacity() < (size_t)n) { tmp.reserve((size_t)n + (size_t)n / 2); ++g_ms_host_allocs; }
-    tmp.assign(idx, idx + n);
-    std::sort(tmp.begin(), tmp.end());
-    for (int i = 1; i < n; ++i)
-        if (tmp[i - 1] == tmp[i]) { *bad = -1 - tmp[i]; return false; }
-    return true;
 }
 
 extern "C" {

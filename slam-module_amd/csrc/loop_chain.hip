@@ -19,7 +19,6 @@
 // expressions are written with *_rn intrinsics in the order the header pins.  The stores are plain vector stores.
 #include "ms_internal.h"
 #include "ms_scan.h"
-#include "loop_chain_check.h"
 #include <cstring>
 
 namespace {
@@ -199,12 +198,6 @@ __global__ __launch_bounds__(kBlock) void k_sim3_lists(const SimArgs A) {
 
 }  // namespace
 
-extern "C" int ms_loop_usable_mask_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, int n_mp, const int32_t *slots,
-                                         const int32_t *n_kp, const int32_t *require_triangulated, uint8_t *const *usable, int32_t *const *tri_row, int n_slots, char *why,
-                                         size_t why_bytes) {
-    return ms_loopc::check_mask(kf_mp, n_kf, stride, mp_flags, mp_live, n_mp, slots, n_kp, require_triangulated, usable, tri_row, n_slots, why, why_bytes);
-}
-
 extern "C" int ms_loop_usable_mask(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, int n_mp, const int32_t *slots,
                                    const int32_t *n_kp, const int32_t *require_triangulated, uint8_t *const *usable, int32_t *const *tri_row, int n_slots) {
     if (!c) return MS_ERR_INVALID;
@@ -231,15 +224,6 @@ extern "C" int ms_loop_usable_mask(ms_ctx *c, const int32_t *kf_mp, int n_kf, in
     MS_KERNEL_CHECK(c, "k_loop_mask");
     MS_HIP(c, hipStreamSynchronize(c->stream));                // the staging block is written again by the next call
     return MS_OK;
-}
-
-extern "C" int ms_loop_pairs_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose,
-                                   const int32_t *kp_octave, int cur, int n_kp_cur, const int32_t *cand_slot, const int32_t *n_kp_cand, const int32_t *const *matched,
-                                   int n_cand, const float *level_sigma_sq, int n_levels, int cap_pairs, const int32_t *pair_start, const int32_t *kp1, const int32_t *kp2,
-                                   const int32_t *row1, const int32_t *row2, const double *pts1, const double *pts2, const float *thr1, const float *thr2,
-                                   const double *cur_pose, const double *cand_pose, const int32_t *n_pairs, char *why, size_t why_bytes) {
-    return ms_loopc::check_pairs(kf_mp, n_kf, stride, mp_live, mp_pos, n_mp, kf_pose, kp_octave, cur, n_kp_cur, cand_slot, n_kp_cand, matched, n_cand, level_sigma_sq, n_levels,
-                                 cap_pairs, pair_start, kp1, kp2, row1, row2, pts1, pts2, thr1, thr2, cur_pose, cand_pose, n_pairs, why, why_bytes);
 }
 
 extern "C" int ms_loop_pairs(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose,
@@ -311,15 +295,6 @@ extern "C" int ms_loop_pairs(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stri
     l_pts1.get(hd, 0, pts1, 3 * n); l_pts2.get(hd, 0, pts2, 3 * n); l_thr1.get(hd, 0, thr1, n); l_thr2.get(hd, 0, thr2, n);
     l_cur.get(hd, 0, cur_pose, 12); l_pose.get(hd, 0, cand_pose, 12 * (size_t)n_cand);
     return MS_OK;
-}
-
-extern "C" int ms_loop_sim3_lists_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose,
-                                        const float *kp_x, const float *kp_y, const int32_t *kp_octave, int cur, int n_kp_cur, const int32_t *cand_slot,
-                                        const int32_t *n_kp_cand, int n_cand, const ms_pinhole *kf_cam, const float *level_sigma_sq, int n_levels, const int32_t *kp1,
-                                        const int32_t *kp2, const int32_t *match_start, const double *pts1, const double *pts2, const double *obs1, const double *obs2,
-                                        const float *info1, const float *info2, const int32_t *row1, const int32_t *row2, char *why, size_t why_bytes) {
-    return ms_loopc::check_sim3_lists(kf_mp, n_kf, stride, mp_live, mp_pos, n_mp, kf_pose, kp_x, kp_y, kp_octave, cur, n_kp_cur, cand_slot, n_kp_cand, n_cand, kf_cam,
-                                      level_sigma_sq, n_levels, kp1, kp2, match_start, pts1, pts2, obs1, obs2, info1, info2, row1, row2, why, why_bytes);
 }
 
 extern "C" int ms_loop_sim3_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const double *mp_pos, int n_mp, const double *kf_pose,

@@ -26,7 +26,6 @@
 // `uncertainty` accumulation, re-pointing referenceKeyframe, trackIdToMapPoint and bowIndex->remove.
 #include "ms_internal.h"
 #include "ms_scan.h"
-#include "map_cull_check.h"
 #include <algorithm>
 #include <cstring>
 
@@ -187,21 +186,15 @@ __global__ __launch_bounds__(kBlock) void k_cull_pack(const CullArgs A) {
     if (A.removed_why) A.removed_why[dst] = why;
 }
 
-// the per-thread vectors of the validation (slots in KfId order, sorted candidates): they only grow
-std::vector<int32_t> &tl_order() { thread_local std::vector<int32_t> v; return v; }
-std::vector<int32_t> &tl_sorted() { thread_local std::vector<int32_t> v; return v; }
-
 }  // namespace
 
 extern "C" int ms_observation_count(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *kf_id, int32_t *n_obs, int32_t *first_slot,
                                     int32_t *last_slot) {
     if (!c) return MS_ERR_INVALID;
     int rc;
-    std::vector<int32_t> &order = tl_order();
-    if ((rc = ms_cull::check_table("observation count", kf_mp, n_kf, stride, n_mp, kf_id, order, c->err, sizeof(c->err)))) return rc;
-    if (ms_map_over_capacity(n_kf, stride, n_mp, 0))
-        return ms_fail(c, MS_ERR_CAPACITY, "observation count: %d slots / stride %d / %d map points, caps %d / %d / below %d", n_kf, stride, n_mp, MS_COVIS_MAX_KF,
-                       MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP);
+    if ((rc = ms_kf_table_check("observation count", kf_mp, n_kf, stride, n_mp, kf_id, c->err, sizeof(c->err)))) return rc;
+    if (ms_map_over_capacity(n_kf, stride, n_mp, 0)) return ms_why_table_caps("observation count", n_kf, stride, n_mp, c->err, sizeof(c->err));
+    const std::vector<int32_t> &order = ms_slots_by_id();    // the slots in KfId order, left by the validation
     if (n_mp == 0 || (!n_obs && !first_slot && !last_slot)) return MS_OK;
     MsRange range("observationCount");
     const size_t nk = (size_t)n_kf, nm = (size_t)n_mp;
@@ -216,7 +209,7 @@ extern "C" int ms_observation_count(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
     if ((rc = ms_grow(c, W.host, W.host_bytes, up.end, true))) return rc;
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
-    ms_cull::fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
+    ms_fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
     if (up.end) MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     CullArgs A{};
     A.kf_mp = const_cast<int32_t *>(kf_mp);                  // read only here
@@ -240,13 +233,6 @@ extern "C" int ms_observation_count(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
     return MS_OK;
 }
 
-extern "C" int ms_map_cull_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, int n_mp, const int32_t *kf_id, const double *kf_t,
-                                 const int32_t *cand, const uint8_t *cand_keep, int n_cand, const ms_cull_settings *settings, const int32_t *removed_rows,
-                                 const uint8_t *cand_removed, const int32_t *n_removed_rows, const int32_t *n_removed_kf, char *why, size_t why_bytes) {
-    return ms_cull::check_cull(kf_mp, n_kf, stride, mp_flags, mp_live, n_mp, kf_id, kf_t, cand, cand_keep, n_cand, settings, removed_rows, cand_removed, n_removed_rows,
-                               n_removed_kf, tl_order(), tl_sorted(), why, why_bytes);
-}
-
 extern "C" int ms_map_cull(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, int n_mp, const int32_t *kf_id, const double *kf_t,
                            const int32_t *cand, const uint8_t *cand_keep, int n_cand, const ms_cull_settings *s, int32_t *n_obs, int32_t *removed_rows, uint8_t *removed_why,
                            uint8_t *cand_removed, int32_t *n_removed_rows, int32_t *n_removed_kf) {
@@ -264,7 +250,7 @@ extern "C" int ms_map_cull(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint
         return MS_OK;
     }
     MsRange range("mapCull");
-    const std::vector<int32_t> &order = tl_order();          // the slots in KfId order, left by the validation
+    const std::vector<int32_t> &order = ms_slots_by_id();    // the slots in KfId order, left by the validation
     const size_t nk = (size_t)n_kf, nm = (size_t)n_mp, nc = (size_t)n_cand, n_blk = (nm + kBlock - 1) / kBlock;
     // upload block: slot -> position in KfId order | position -> slot | kf_t | the walk; then (host only) the results
     MsLayout up;
@@ -284,7 +270,7 @@ extern "C" int ms_map_cull(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint
     if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
-    ms_cull::fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
+    ms_fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
     l_t.fill(hs, kf_t);
     // :445: descending KfId; :453-464: the kept ones never reach the device
     int2 *walk = l_walk.at(hs);

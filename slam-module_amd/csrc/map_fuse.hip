@@ -25,7 +25,6 @@
 // MapPoint objects, fusedCount (codes 4-7).
 #include "ms_internal.h"
 #include "ms_scan.h"
-#include "map_fuse_check.h"
 #include <cstring>
 
 namespace {
@@ -239,18 +238,7 @@ __global__ __launch_bounds__(kWalk) void k_pairs_walk(const FuseArgs A) {
     if (threadIdx.x == 0) A.down[0] = A.n_pairs;
 }
 
-std::vector<int32_t> &tl_sorted() { thread_local std::vector<int32_t> v; return v; }
-
 }  // namespace
-
-extern "C" int ms_map_fuse_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const int32_t *n_obs, int n_mp,
-                                 const int32_t *mp_track, const int32_t *track_row, int track_base, int n_track, const int32_t *kept_entry, const int32_t *top_idx,
-                                 const uint16_t *top_dist, const int32_t *mp_index, int n_entries, const ms_fuse_view *views, const int32_t *n_kept, int n_views,
-                                 int max_dist, int source_slot, const int32_t *n_erased, const int32_t *counts, const int32_t *views_done, char *why, size_t why_bytes) {
-    (void)track_base;                                        // any base is fine: a track outside the window writes no track_row
-    return ms_fuse::check_fuse(kf_mp, n_kf, stride, mp_flags, mp_live, n_obs, n_mp, mp_track, track_row, n_track, kept_entry, top_idx, top_dist, mp_index, n_entries, views,
-                               n_kept, n_views, max_dist, source_slot, n_erased, counts, views_done, tl_sorted(), why, why_bytes);
-}
 
 extern "C" int ms_map_fuse(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, int32_t *n_obs, int n_mp, int32_t *mp_track,
                            int32_t *track_row, int track_base, int n_track, const int32_t *kept_entry, const int32_t *top_idx, const uint16_t *top_dist,
@@ -318,13 +306,6 @@ extern "C" int ms_map_fuse(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint
     return MS_OK;
 }
 
-extern "C" int ms_map_replace_pairs_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const int32_t *n_obs, int n_mp,
-                                          const int32_t *mp_track, const int32_t *track_row, int track_base, int n_track, const int32_t *pairs, int n_pairs,
-                                          const uint8_t *outcome, const int32_t *n_erased, char *why, size_t why_bytes) {
-    (void)track_base;
-    return ms_fuse::check_pairs(kf_mp, n_kf, stride, mp_flags, mp_live, n_obs, n_mp, mp_track, track_row, n_track, pairs, n_pairs, outcome, n_erased, why, why_bytes);
-}
-
 extern "C" int ms_map_replace_pairs(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, int32_t *n_obs, int n_mp, int32_t *mp_track,
                                     int32_t *track_row, int track_base, int n_track, const int32_t *pairs, int n_pairs, uint8_t *outcome, int32_t *erased_rows,
                                     int32_t *erased_into, int32_t *n_erased) {
@@ -350,7 +331,7 @@ extern "C" int ms_map_replace_pairs(ms_ctx *c, int32_t *kf_mp, int n_kf, int str
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
     l_rows.fill(hs, pairs);
-    const int n_run = ms_fuse::pair_outcomes(pairs, n_pairs, outcome, tl_sorted());
+    const int n_run = ms_pair_outcomes(pairs, n_pairs, outcome);
     int2 *run = l_pairs.at(hs);
     for (int i = 0, k = 0; i < n_pairs; ++i)
         if (outcome[i] == 0) run[k++] = make_int2(pairs[2 * i], pairs[2 * i + 1]);

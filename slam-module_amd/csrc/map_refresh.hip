@@ -304,42 +304,6 @@ __global__ __launch_bounds__(kBlock) void k_loop_points(const LoopArgs A) {
     p[2] = s * (X[6] * x + X[7] * y + X[8] * z) + X[11];
 }
 
-}  // namespace
-
-extern "C" int ms_map_refresh_check(const double *mp_pos, const float *mp_norm, const float *mp_min_dist, const float *mp_max_dist, const uint32_t *mp_desc, int n_mp,
-                                    const double *kf_pose, int n_kf, const uint32_t *desc_pool, int n_pool, const int32_t *rows, int n_rows,
-                                    const int32_t *obs_start, const int32_t *obs_kf, const int32_t *obs_desc, const int32_t *first_octave,
-                                    const float *scale_factors, int n_levels, char *why, size_t why_bytes) {
-    if (n_mp < 0 || n_kf < 0 || n_pool < 0 || n_rows < 0 || n_levels < 1 || !scale_factors) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: bad arguments");
-    if (n_rows == 0) return MS_OK;
-    if (!mp_pos || !mp_norm || !mp_min_dist || !mp_max_dist || !kf_pose || !rows || !obs_start || !obs_kf || !first_octave)
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: missing array");
-    const bool with_desc = desc_pool != nullptr && obs_desc != nullptr;
-    if (with_desc && !mp_desc) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: a descriptor pool without the table's descriptors");
-    if (with_desc && ((reinterpret_cast<uintptr_t>(mp_desc) | reinterpret_cast<uintptr_t>(desc_pool)) & 15u))
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: descriptor arrays must be 16-byte aligned");
-    if (obs_start[0] != 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: obs_start[0] = %d", obs_start[0]);
-    for (int r = 0; r < n_rows; ++r) {
-        if (obs_start[r + 1] < obs_start[r]) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: obs_start decreases at row entry %d", r);
-        if (obs_start[r + 1] == obs_start[r]) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row entry %d has no observations", r);
-        if (first_octave[r] < 0 || first_octave[r] >= n_levels)
-            return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row entry %d: octave %d outside [0, %d)", r, first_octave[r], n_levels);
-    }
-    for (int o = 0; o < obs_start[n_rows]; ++o) {
-        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: observation %d: keyframe slot %d outside [0, %d)", o, obs_kf[o], n_kf);
-        if (with_desc && (obs_desc[o] < -1 || obs_desc[o] >= n_pool))
-            return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: observation %d: descriptor %d outside [0, %d)", o, obs_desc[o], n_pool);
-    }
-    int bad = 0;
-    if (!ms_distinct_in_range(rows, n_rows, n_mp, &bad)) {
-        if (bad >= 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row entry %d: row %d outside [0, %d)", bad, rows[bad], n_mp);
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "map refresh: row %d is listed twice", -1 - bad);
-    }
-    return MS_OK;
-}
-
-namespace {
-
 // The lists of one call: HOST arrays that are uploaded (ms_map_refresh), or DEVICE arrays the kernels read where they lie (ms_map_refresh_lists).
 struct RefreshLists {
     const int32_t *rows, *obs_start, *obs_kf, *obs_desc, *first_octave;
@@ -496,30 +460,6 @@ extern "C" int ms_map_refresh_lists(ms_ctx *c, const double *mp_pos, float *mp_n
     const RefreshLists L{lists->rows, lists->obs_start, lists->obs_kf, lists->obs_desc, lists->first_octave, true};
     return refresh_run(c, mp_pos, mp_norm, mp_min_dist, mp_max_dist, mp_desc, kf_pose, n_kf, desc_pool, L, n_rows, n_obs, scale_factors, n_levels, promote_min_obs, mp_flags,
                        medoid);
-}
-
-extern "C" int ms_loop_correct_check(const double *kf_pose, int n_kf, const double *mp_pos, int n_mp, const double *T, const int32_t *kf_slot, const uint8_t *kf_rigid,
-                                     const double *kf_lambda, int n_corr, const int32_t *mp_row, const int32_t *mp_ref, int n_pts, char *why, size_t why_bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_corr < 0 || n_pts < 0 || !T) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: bad arguments");
-    for (int k = 0; k < 8; ++k)
-        if (!std::isfinite(T[k])) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: T[%d] is not finite", k);
-    if ((n_corr > 0 && (!kf_pose || !kf_slot || !kf_rigid || !kf_lambda)) || (n_pts > 0 && (!mp_pos || !mp_row || !mp_ref)))
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: missing array");
-    for (int i = 0; i < n_corr; ++i)                         // a rigid member's lambda is not read
-        if (!kf_rigid[i] && !(kf_lambda[i] >= 0.0 && kf_lambda[i] <= 1.0))
-            return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: keyframe entry %d: lambda %g outside [0, 1]", i, kf_lambda[i]);
-    for (int j = 0; j < n_pts; ++j)
-        if (mp_ref[j] < 0 || mp_ref[j] >= n_corr) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: point entry %d: reference %d outside [0, %d)", j, mp_ref[j], n_corr);
-    int bad = 0;
-    if (!ms_distinct_in_range(kf_slot, n_corr, n_kf, &bad)) {
-        if (bad >= 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: keyframe entry %d: slot %d outside [0, %d)", bad, kf_slot[bad], n_kf);
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: keyframe slot %d is listed twice", -1 - bad);
-    }
-    if (!ms_distinct_in_range(mp_row, n_pts, n_mp, &bad)) {
-        if (bad >= 0) return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: point entry %d: row %d outside [0, %d)", bad, mp_row[bad], n_mp);
-        return ms_why(MS_ERR_INVALID, why, why_bytes, "loop correct: map-point row %d is listed twice", -1 - bad);
-    }
-    return MS_OK;
 }
 
 extern "C" int ms_loop_correct(ms_ctx *c, double *kf_pose, int n_kf, double *mp_pos, int n_mp, const double *T, const int32_t *kf_slot,

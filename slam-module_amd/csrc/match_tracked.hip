@@ -217,88 +217,7 @@ __global__ __launch_bounds__(kBlock) void k_match_finish(const FinishArgs A) {
     if (threadIdx.x == 0) A.down[0] = n_kept + A.n_checked;
 }
 
-std::vector<int32_t> &tl_ids() { thread_local std::vector<int32_t> v; return v; }
-
-#define MT_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "match tracked: " __VA_ARGS__)
-
-int check_tracked_args(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const double *mp_pos, const float *mp_norm,
-                       const float *mp_min_dist, const float *mp_max_dist, const uint32_t *mp_desc, const int32_t *mp_track, int n_mp, const float *kp_x, const float *kp_y,
-                       const int32_t *kp_octave, const uint32_t *desc_pool, int n_pool, const int32_t *track_row, int n_track, const ms_tracked_frame *f,
-                       const int32_t *kp_track, int n_kp, const int32_t *new_rows, int n_new, const uint8_t *outcome, const int32_t *counts, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0 || n_pool < 0 || n_track < 0 || n_kp < 0 || n_new < 0)
-        MT_INVALID("negative size (%d slots, %d map points, %d pool descriptors, %d tracks, %d keypoints, %d new rows)", n_kf, n_mp, n_pool, n_track, n_kp, n_new);
-    if (stride < 1) MT_INVALID("stride %d", stride);
-    if (!f || !counts) MT_INVALID("missing array (frame or counts)");
-    if (f->slot < 0 || f->slot >= n_kf) MT_INVALID("slot %d outside [0, %d)", f->slot, n_kf);
-    if (n_kp > stride) MT_INVALID("%d keypoints in a table of stride %d", n_kp, stride);
-    if (!kf_mp || !kp_x || !kp_y || !kp_octave) MT_INVALID("missing array (kf_mp or the keypoint table)");
-    if (n_mp > 0 && (!mp_flags || !mp_live || !mp_pos || !mp_norm || !mp_min_dist || !mp_max_dist || !mp_desc || !mp_track)) MT_INVALID("missing array (the map-point table)");
-    if (n_track > 0 && !track_row) MT_INVALID("missing array (track_row)");
-    if (n_kp > 0 && (!kp_track || !outcome)) MT_INVALID("missing array (kp_track or outcome)");
-    if (n_new > 0 && !new_rows) MT_INVALID("missing array (new_rows)");
-    if (!f->level_sigma_sq) MT_INVALID("missing array (level_sigma_sq)");
-    if (f->n_levels < 1 || f->n_levels > MS_TRI_MAX_LEVELS) MT_INVALID("%d levels outside [1, %d]", f->n_levels, MS_TRI_MAX_LEVELS);
-    for (int l = 0; l < f->n_levels; ++l)
-        if (!std::isfinite(f->level_sigma_sq[l])) MT_INVALID("level_sigma_sq[%d] is not finite", l);
-    if (!std::isfinite(f->rel_reprojection_threshold) || !std::isfinite(f->view_cos_limit))
-        MT_INVALID("rel_reprojection_threshold %g or view_cos_limit %g is not finite", (double)f->rel_reprojection_threshold, (double)f->view_cos_limit);
-    if (f->cam.width < 1 || f->cam.height < 1 || !(f->cam.fx > 0.0) || !(f->cam.fy > 0.0) || !std::isfinite(f->cam.fx) || !std::isfinite(f->cam.fy) ||
-        !std::isfinite(f->cam.cx) || !std::isfinite(f->cam.cy))
-        MT_INVALID("bad camera");
-    if (f->desc_base >= 0 && (!desc_pool || (long long)f->desc_base + n_kp > n_pool))
-        MT_INVALID("descriptors [%d, %d + %d) outside the pool of %d", f->desc_base, f->desc_base, n_kp, desc_pool ? n_pool : 0);
-    if ((reinterpret_cast<uintptr_t>(mp_desc) | reinterpret_cast<uintptr_t>(desc_pool)) & 15u) MT_INVALID("descriptor arrays must be 16-byte aligned");
-    std::vector<int32_t> &ids = tl_ids();
-    ids.clear();
-    if (ids.capacity() < (size_t)n_kp) { ids.reserve((size_t)n_kp + (size_t)n_kp / 2); ++g_ms_host_allocs; }
-    for (int j = 0; j < n_kp; ++j) {
-        const int32_t t = kp_track[j];
-        if (t < 0) continue;
-        if (t < f->track_base || (long long)t - f->track_base >= n_track)
-            MT_INVALID("keypoint %d: track id %d outside the window [%d, %d + %d)", j, t, f->track_base, f->track_base, n_track);
-        ids.push_back(t);
-    }
-    std::sort(ids.begin(), ids.end());
-    for (size_t i = 1; i < ids.size(); ++i)
-        if (ids[i - 1] == ids[i]) MT_INVALID("track id %d is listed twice", ids[i]);
-    int bad = 0;
-    if (!ms_distinct_in_range(new_rows, n_new, n_mp, &bad)) {
-        if (bad < 0) MT_INVALID("new row %d is listed twice", -1 - bad);
-        MT_INVALID("new row %d outside [0, %d)", new_rows[bad], n_mp);
-    }
-    return MS_OK;
-}
-
-#define MF_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "match tracked finish: " __VA_ARGS__)
-
-int check_finish_args(const ms_obs_lists *lists, int n_rows, const uint8_t *mp_flags, const uint32_t *desc_pool, const uint32_t *mp_desc, int n_mp,
-                      const int32_t *checked_rows, int n_checked, const int32_t *refresh_rows, int cap_refresh, const int32_t *n_refresh, char *why, size_t bytes) {
-    if (n_rows < 0 || n_checked < 0 || n_mp < 0 || cap_refresh < 0) MF_INVALID("negative size (%d rows, %d checked rows, %d map points, capacity %d)", n_rows, n_checked, n_mp, cap_refresh);
-    if (!n_refresh) MF_INVALID("missing array (n_refresh)");
-    if (n_rows > 0 && (!lists || !lists->rows || !lists->obs_start || !mp_flags)) MF_INVALID("missing array (rows, obs_start or mp_flags)");
-    if (n_rows > 0 && desc_pool && lists->obs_desc && !mp_desc) MF_INVALID("missing array (mp_desc)");
-    if (n_checked > 0 && !checked_rows) MF_INVALID("missing array (checked_rows)");
-    if (n_rows + n_checked > 0 && !refresh_rows) MF_INVALID("missing array (refresh_rows)");
-    if ((reinterpret_cast<uintptr_t>(mp_desc) | reinterpret_cast<uintptr_t>(desc_pool)) & 15u) MF_INVALID("descriptor arrays must be 16-byte aligned");
-    return MS_OK;
-}
-
 }  // namespace
-
-extern "C" int ms_match_tracked_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const double *mp_pos, const float *mp_norm,
-                                      const float *mp_min_dist, const float *mp_max_dist, const uint32_t *mp_desc, const int32_t *mp_track, int n_mp, const float *kp_x,
-                                      const float *kp_y, const int32_t *kp_octave, const uint32_t *desc_pool, int n_pool, const int32_t *track_row, int n_track,
-                                      const ms_tracked_frame *frame, const int32_t *kp_track, int n_kp, const int32_t *new_rows, int n_new, const uint8_t *outcome,
-                                      const int32_t *counts, char *why, size_t why_bytes) {
-    int rc;
-    if ((rc = check_tracked_args(kf_mp, n_kf, stride, mp_flags, mp_live, mp_pos, mp_norm, mp_min_dist, mp_max_dist, mp_desc, mp_track, n_mp, kp_x, kp_y, kp_octave, desc_pool,
-                                 n_pool, track_row, n_track, frame, kp_track, n_kp, new_rows, n_new, outcome, counts, why, why_bytes)))
-        return rc;
-    if (ms_map_over_capacity(n_kf, stride, n_mp, 0) || n_track > MS_TRACKED_MAX_WINDOW)
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "match tracked: %d slots / stride %d / %d map points / %d tracks, caps %d / %d / below %d / %d", n_kf, stride, n_mp,
-                      n_track, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_TRACKED_MAX_WINDOW);
-    return MS_OK;
-}
 
 extern "C" int ms_match_tracked(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live, const double *mp_pos, const float *mp_norm,
                                 const float *mp_min_dist, const float *mp_max_dist, uint32_t *mp_desc, int32_t *mp_track, int n_mp, const float *kp_x, const float *kp_y,
@@ -362,18 +281,6 @@ extern "C" int ms_match_tracked(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride,
         return ms_fail(c, MS_ERR_INVALID, "match tracked: %d bound keypoints whose kf_mp entry is already valid, %d new rows that are live, %d octaves outside [0, %d) (nothing written)",
                        down[5], down[6], down[7], f->n_levels);
     if (down[0] > n_new) return ms_fail(c, MS_ERR_CAPACITY, "match tracked: the frame creates %d map points, new_rows holds %d (nothing written)", down[0], n_new);
-    return MS_OK;
-}
-
-extern "C" int ms_match_tracked_finish_check(const ms_obs_lists *lists, int n_rows, const uint8_t *mp_flags, const uint32_t *desc_pool, const uint32_t *mp_desc, int n_mp,
-                                             const int32_t *checked_rows, int n_checked, int append_checked, const int32_t *refresh_rows, int cap_refresh,
-                                             const int32_t *n_refresh, char *why, size_t why_bytes) {
-    int rc;
-    if ((rc = check_finish_args(lists, n_rows, mp_flags, desc_pool, mp_desc, n_mp, checked_rows, n_checked, refresh_rows, cap_refresh, n_refresh, why, why_bytes))) return rc;
-    const long long need = (long long)n_rows + (append_checked ? n_checked : 0);
-    if (n_rows > MS_COVIS_MAX_STRIDE || n_checked > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || need > cap_refresh)
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "match tracked finish: %d rows / %d checked rows / %d map points, caps %d / %d / below %d; refresh_rows holds %d of up to %lld",
-                      n_rows, n_checked, n_mp, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, cap_refresh, need);
     return MS_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "../../include/mi355slam.h"
+#include "ms_check.h"
 #include "ms_layout.h"
 
 struct MsWorkspace {
@@ -64,10 +65,6 @@ struct ms_ctx {
     char err[512] = {0};
 };
 
-// every allocation the library makes on the host or the device after a context exists (handle objects, host scratch growth, device blocks, pinned staging, events):
-// a per-keyframe path must leave it unchanged after warm-up (ms_debug_host_allocs)
-#include <atomic>
-extern std::atomic<long long> g_ms_host_allocs;
 void ms_ba_release_pool(ms_ctx *ctx);      // ba.hip: deletes the pooled handle objects (ms_ctx_destroy)
 
 // ba.hip, for pose_tables.hip: a pose-only handle of capacity cap_obs -- two poses (0 free, 1 fixed), up to cap_obs fixed points with
@@ -97,26 +94,11 @@ int ms_scratch(ms_ctx *ctx, size_t bytes, void **out);
 // for the context stream, frees the block and allocates half as much again as asked for; the contents are not kept.
 int ms_grow(ms_ctx *ctx, void *&p, size_t &cap, size_t bytes, bool pinned);
 
-// true when idx[0 .. n) are distinct values of [0, limit).  Otherwise *bad = the first entry outside the range, or -1 - v for a value v that is
-// listed twice (entries are ranged before duplicates are looked for).  The sorted copy lives in a per-thread vector that only grows.
-bool ms_distinct_in_range(const int32_t *idx, int n, int limit, int *bad);
-
 inline int ms_fail(ms_ctx *ctx, int code, const char *fmt, ...) {
     if (ctx) {
         va_list ap;
         va_start(ap, fmt);
         vsnprintf(ctx->err, sizeof(ctx->err), fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
-// ms_fail for the *_check entry points, which report into the caller's buffer (may be null)
-inline int ms_why(int code, char *why, size_t bytes, const char *fmt, ...) {
-    if (why && bytes) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(why, bytes, fmt, ap);
         va_end(ap);
     }
     return code;
@@ -162,8 +144,3 @@ struct MsRange {
 };
 
 inline int ms_div_up(int a, int b) { return (a + b - 1) / b; }
-
-// the sizes every entry point over the keyframe table kf_mp accepts; n = its queries, problems or candidates
-inline bool ms_map_over_capacity(int n_kf, int stride, int n_mp, int n) {
-    return n_kf > MS_COVIS_MAX_KF || stride > MS_COVIS_MAX_STRIDE || n_mp >= MS_COVIS_MAX_MP || n > MS_COVIS_MAX_QUERIES;
-}

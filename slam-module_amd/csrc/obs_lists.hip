@@ -21,7 +21,6 @@
 // still computed and nothing behind the block scan writes.
 #include "ms_internal.h"
 #include "ms_scan.h"
-#include "map_cull_check.h"
 #include <algorithm>
 #include <cstring>
 
@@ -222,54 +221,17 @@ __global__ __launch_bounds__(kBlock) void k_ol_gather(const ListArgs A) {
     }
 }
 
-std::vector<int32_t> &tl_order() { thread_local std::vector<int32_t> v; return v; }
-
-int check_lists(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *kf_id, const uint8_t *mp_flags, const float *kp_x, const float *kp_y,
-                const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, const ms_obs_select *sel, int n_levels, const ms_obs_lists *out,
-                int cap_rows, int cap_obs, const int32_t *n_rows, const int32_t *n_obs, std::vector<int32_t> &order, char *why, size_t bytes) {
-    using ms_cull::why_is;
-    if (!sel || !out || !n_rows || !n_obs) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: missing array (selection, outputs or counts)");
-    if (cap_rows < 0 || cap_obs < 0 || n_levels < 0 || sel->n_in < 0)
-        return why_is(MS_ERR_INVALID, why, bytes, "observation lists: negative size (capacities %d / %d, %d levels, %d rows_in)", cap_rows, cap_obs, n_levels, sel->n_in);
-    int rc;
-    if ((rc = ms_cull::check_table("observation lists", kf_mp, n_kf, stride, n_mp, kf_id, order, why, bytes))) return rc;
-    if (sel->source != MS_OBS_FROM_ROWS && sel->source != MS_OBS_FROM_SLOT) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: source %d", sel->source);
-    if (sel->filter != MS_OBS_ALL && sel->filter != MS_OBS_REFRESH && sel->filter != MS_OBS_RETRIANGULATE)
-        return why_is(MS_ERR_INVALID, why, bytes, "observation lists: filter %d", sel->filter);
-    if (sel->filter != MS_OBS_ALL && !mp_flags) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: filter %d reads flags and there is no mp_flags", sel->filter);
-    if (sel->source == MS_OBS_FROM_SLOT) {
-        if (sel->slot < 0 || sel->slot >= n_kf) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: slot %d outside [0, %d)", sel->slot, n_kf);
-        if (kf_id[sel->slot] < 0) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: slot %d is empty (kf_id %d)", sel->slot, kf_id[sel->slot]);
-    } else if (sel->n_in > 0 && !sel->rows_in) {
-        return why_is(MS_ERR_INVALID, why, bytes, "observation lists: missing array (rows_in)");
-    }
-    if ((cap_rows > 0 && !out->rows) || !out->obs_start) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: missing array (rows or obs_start)");
-    if ((out->obs_x && !kp_x) || (out->obs_y && !kp_y) || ((out->obs_octave || out->first_octave) && !kp_octave) || (out->obs_depth && !kp_depth) ||
-        (out->obs_desc && !kf_desc_base))
-        return why_is(MS_ERR_INVALID, why, bytes, "observation lists: missing array (an output is asked for without its keypoint table)");
-    if (out->was_triangulated && !mp_flags) return why_is(MS_ERR_INVALID, why, bytes, "observation lists: missing array (was_triangulated without mp_flags)");
-    return MS_OK;
-}
-
 }  // namespace
-
-extern "C" int ms_observation_lists_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *kf_id, const uint8_t *mp_flags, const float *kp_x,
-                                          const float *kp_y, const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, const ms_obs_select *sel,
-                                          int n_levels, const ms_obs_lists *out, int cap_rows, int cap_obs, const int32_t *n_rows, const int32_t *n_obs, char *why,
-                                          size_t why_bytes) {
-    return check_lists(kf_mp, n_kf, stride, n_mp, kf_id, mp_flags, kp_x, kp_y, kp_octave, kp_depth, kf_desc_base, sel, n_levels, out, cap_rows, cap_obs, n_rows, n_obs,
-                       tl_order(), why, why_bytes);
-}
 
 extern "C" int ms_observation_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, int n_mp, const int32_t *kf_id, const uint8_t *mp_flags, const float *kp_x,
                                     const float *kp_y, const int32_t *kp_octave, const float *kp_depth, const int32_t *kf_desc_base, const ms_obs_select *sel, int n_levels,
                                     const ms_obs_lists *out, int cap_rows, int cap_obs, int32_t *n_rows, int32_t *n_obs) {
     if (!c) return MS_ERR_INVALID;
     int rc;
-    std::vector<int32_t> &order = tl_order();
-    if ((rc = check_lists(kf_mp, n_kf, stride, n_mp, kf_id, mp_flags, kp_x, kp_y, kp_octave, kp_depth, kf_desc_base, sel, n_levels, out, cap_rows, cap_obs, n_rows, n_obs,
-                          order, c->err, sizeof(c->err))))
+    if ((rc = ms_observation_lists_check(kf_mp, n_kf, stride, n_mp, kf_id, mp_flags, kp_x, kp_y, kp_octave, kp_depth, kf_desc_base, sel, n_levels, out, cap_rows, cap_obs,
+                                         n_rows, n_obs, c->err, sizeof(c->err))))
         return rc;
+    const std::vector<int32_t> &order = ms_slots_by_id();    // the slots in KfId order, left by the validation
     const bool from_slot = sel->source == MS_OBS_FROM_SLOT;
     if (ms_map_over_capacity(n_kf, stride, n_mp, 0) || sel->n_in > kMaxIn)
         return ms_fail(c, MS_ERR_CAPACITY, "observation lists: %d slots / stride %d / %d map points / %d rows_in, caps %d / %d / below %d / %d", n_kf, stride, n_mp,
@@ -301,7 +263,7 @@ extern "C" int ms_observation_lists(ms_ctx *c, const int32_t *kf_mp, int n_kf, i
     if ((rc = ms_grow(c, W.host, W.host_bytes, host.end, true))) return rc;
     if ((rc = ms_grow(c, W.dev, W.dev_bytes, dev.end, false))) return rc;
     void *hs = W.host, *ds = W.dev;
-    ms_cull::fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
+    ms_fill_ranks(order, n_kf, l_sr.at(hs), l_rs.at(hs));
     l_base.fill(hs, kf_desc_base);
     if (up.end) MS_HIP(c, hipMemcpyAsync(ds, hs, up.end, hipMemcpyHostToDevice, c->stream));
     ListArgs A{};

@@ -117,45 +117,7 @@ __global__ __launch_bounds__(kBlock) void k_pose_apply(const ApplyArgs A) {
         for (int i = tid; i < n; i += kBlock) A.rec[kRecChi2 + i] = A.io.chi2_obs[i];
 }
 
-#define PT_INVALID(...) return ms_why(MS_ERR_INVALID, why, bytes, "pose tables: " __VA_ARGS__)
-
-int check_solve_args(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const double *mp_pos, int n_mp, const float *kp_x, const float *kp_y,
-                     const int32_t *kp_octave, const double *kf_pose, const ms_pose_tables_frame *f, const ms_pose_tables_out *out, char *why, size_t bytes) {
-    if (n_kf < 0 || n_mp < 0) PT_INVALID("negative size (%d slots, %d map points)", n_kf, n_mp);
-    if (stride < 1) PT_INVALID("stride %d", stride);
-    if (!f || !out) PT_INVALID("missing array (frame or out)");
-    if (f->n_kp < 0) PT_INVALID("negative size (%d keypoints)", f->n_kp);
-    if (f->n_kp > stride) PT_INVALID("%d keypoints in a table of stride %d", f->n_kp, stride);
-    if (f->slot < 0 || f->slot >= n_kf) PT_INVALID("slot %d outside [0, %d)", f->slot, n_kf);
-    if (f->prev_slot < -1 || f->prev_slot >= n_kf) PT_INVALID("previous slot %d outside [-1, %d)", f->prev_slot, n_kf);
-    if (f->prev_slot == f->slot) PT_INVALID("slot %d is its own previous keyframe", f->slot);
-    if (!kf_mp || !kp_x || !kp_y || !kp_octave || !kf_pose) PT_INVALID("missing array (kf_mp, the keypoint table or kf_pose)");
-    if (n_mp > 0 && (!mp_flags || !mp_pos)) PT_INVALID("missing array (mp_flags or mp_pos)");
-    const ms_pinhole &K = f->cam;
-    if (K.width < 1 || K.height < 1 || !(K.fx > 0.0) || !(K.fy > 0.0) || !std::isfinite(K.fx) || !std::isfinite(K.fy) || !std::isfinite(K.cx) || !std::isfinite(K.cy))
-        PT_INVALID("bad camera (%d x %d, fx %g, fy %g)", K.width, K.height, K.fx, K.fy);
-    for (int i = 0; i < 7; ++i)
-        if (!std::isfinite(f->edge_meas[i])) PT_INVALID("edge_meas[%d] is not finite", i);
-    for (int i = 0; i < 36; ++i)
-        if (!std::isfinite(f->edge_info[i])) PT_INVALID("edge_info[%d] is not finite", i);
-    if (!std::isfinite(f->huber_delta)) PT_INVALID("huber_delta is not finite");
-    if (f->max_iters < 0) PT_INVALID("max_iters %d", f->max_iters);
-    return MS_OK;
-}
-
 }  // namespace
-
-extern "C" int ms_pose_tables_solve_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const double *mp_pos, int n_mp,
-                                          const float *kp_x, const float *kp_y, const int32_t *kp_octave, const double *kf_pose, const ms_pose_tables_frame *frame,
-                                          const ms_pose_tables_out *out, char *why, size_t why_bytes) {
-    (void)mp_live;                                           // may be NULL: every row is live
-    int rc;
-    if ((rc = check_solve_args(kf_mp, n_kf, stride, mp_flags, mp_pos, n_mp, kp_x, kp_y, kp_octave, kf_pose, frame, out, why, why_bytes))) return rc;
-    if (ms_map_over_capacity(n_kf, stride, n_mp, 0))
-        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "pose tables: %d slots / stride %d / %d map points, caps %d / %d / below %d", n_kf, stride, n_mp, MS_COVIS_MAX_KF,
-                      MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP);
-    return MS_OK;
-}
 
 extern "C" int ms_pose_tables_create(ms_ctx *c, int cap_obs, const float *level_sigma_sq, int n_levels, ms_pose_tables **out) {
     if (!c || !out) return MS_ERR_INVALID;

@@ -25,7 +25,6 @@
 // total.  n_obs is touched only by an agent-scope atomic add.  Integer and correctly rounded float32 work: the same input gives the same bits on every call.
 #include "ms_internal.h"
 #include "ms_scan.h"
-#include "search_bind_check.h"
 #include <cstring>
 
 namespace {
@@ -243,10 +242,6 @@ __global__ __launch_bounds__(kWalk) void k_sbind_walk(const BindArgs A) {
 
 }  // namespace
 
-extern "C" int ms_bound_mask_check(const int32_t *kf_mp, int n_kf, int stride, int n_mp, int slot, int n_kp, const uint8_t *skip, char *why, size_t why_bytes) {
-    return ms_sbind::check_mask(kf_mp, n_kf, stride, n_mp, slot, n_kp, skip, why, why_bytes);
-}
-
 extern "C" int ms_bound_mask(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stride, int n_mp, int slot, int n_kp, uint8_t *skip) {
     if (!c) return MS_ERR_INVALID;
     int rc;
@@ -257,17 +252,6 @@ extern "C" int ms_bound_mask(ms_ctx *c, const int32_t *kf_mp, int n_kf, int stri
     hipLaunchKernelGGL(k_bound_mask, dim3((unsigned)ms_div_up(n_kp, kBlock)), dim3(kBlock), 0, c->stream, kf_mp + (size_t)slot * stride, n_kp, n_mp, skip);
     MS_KERNEL_CHECK(c, "k_bound_mask");
     return MS_OK;                                            // in stream order with the scoring that reads it
-}
-
-extern "C" int ms_search_bind_check(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, const int32_t *n_obs, int n_mp, const int32_t *kept_entry,
-                                    const float *q_x, const float *q_y, const float *q_radius, const int32_t *q_min_octave, const int32_t *q_max_octave,
-                                    const uint32_t *q_desc, const int32_t *top_idx, const uint16_t *top_dist, const int32_t *top_octave, const int32_t *n_scored,
-                                    const uint8_t *skip, const float *sorted_x, const float *sorted_y, const int32_t *sorted_idx, const uint32_t *t_desc,
-                                    const int32_t *t_octave, int n_kp, const int32_t *mp_index, int first, int count, int n_kept, int slot, const int32_t *n_matched,
-                                    const int32_t *counts, char *why, size_t why_bytes) {
-    (void)q_min_octave; (void)q_max_octave;                  // each may be NULL: no window on that side
-    return ms_sbind::check_bind(kf_mp, n_kf, stride, mp_live, n_obs, n_mp, kept_entry, q_x, q_y, q_radius, q_desc, top_idx, top_dist, top_octave, n_scored, skip, sorted_x,
-                                sorted_y, sorted_idx, t_desc, t_octave, n_kp, mp_index, first, count, n_kept, slot, n_matched, counts, why, why_bytes);
 }
 
 extern "C" int ms_search_bind(ms_ctx *c, int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_live, int32_t *n_obs, int n_mp, const int32_t *kept_entry,

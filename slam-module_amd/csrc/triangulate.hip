@@ -435,48 +435,6 @@ __global__ __launch_bounds__(kBlock) void k_tri_points(const TriArgs A) {
     A.out[2 * (size_t)r + 1] = res.n_pass;
 }
 
-}  // namespace
-
-#define TRI_INVALID(...) return ms_why(MS_ERR_INVALID, why, why_bytes, "triangulate: " __VA_ARGS__)
-
-extern "C" int ms_triangulate_check(const double *mp_pos, int n_mp, const double *kf_pose, int n_kf, const ms_pinhole *kf_cam, const int32_t *kf_focal,
-                                    const int32_t *rows, const uint8_t *was_triangulated, int n_rows, const int32_t *obs_start, const int32_t *obs_kf,
-                                    const float *obs_x, const float *obs_y, const int32_t *obs_octave, const ms_tri_settings *settings, int mode, char *why,
-                                    size_t why_bytes) {
-    if (n_mp < 0 || n_kf < 0 || n_rows < 0) TRI_INVALID("bad arguments");
-    if (mode != MS_TRI_TME && mode != MS_TRI_MIDPOINT && mode != MS_TRI_FIRST_LAST) TRI_INVALID("mode %d", mode);
-    if (!settings || !settings->level_sigma_sq) TRI_INVALID("missing settings");
-    if (settings->n_levels < 1 || settings->n_levels > MS_TRI_MAX_LEVELS) TRI_INVALID("n_levels %d outside [1, %d]", settings->n_levels, MS_TRI_MAX_LEVELS);
-    if (!std::isfinite(settings->min_angle_two_obs) || !std::isfinite(settings->min_angle_multiple_obs) || !std::isfinite(settings->rel_reprojection_threshold))
-        TRI_INVALID("a setting is not finite");
-    for (int l = 0; l < settings->n_levels; ++l)
-        if (!std::isfinite(settings->level_sigma_sq[l])) TRI_INVALID("level_sigma_sq[%d] is not finite", l);
-    if (n_rows == 0) return MS_OK;
-    if (n_rows > MS_TRI_MAX_ROWS) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d rows, at most %d per call", n_rows, MS_TRI_MAX_ROWS);
-    if (!mp_pos || !kf_pose || !kf_cam || !kf_focal || !rows || !was_triangulated || !obs_start) TRI_INVALID("missing array");
-    if (obs_start[0] != 0) TRI_INVALID("obs_start[0] = %d", obs_start[0]);
-    for (int r = 0; r < n_rows; ++r)
-        if (obs_start[r + 1] < obs_start[r]) TRI_INVALID("obs_start decreases at row entry %d", r);
-    const int n_obs = obs_start[n_rows];
-    if (n_obs > MS_TRI_MAX_OBS) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "triangulate: %d observations, at most %d per call", n_obs, MS_TRI_MAX_OBS);
-    if (n_obs > 0 && (!obs_kf || !obs_x || !obs_y || !obs_octave)) TRI_INVALID("missing array");
-    for (int o = 0; o < n_obs; ++o) {
-        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) TRI_INVALID("observation %d: keyframe slot %d outside [0, %d)", o, obs_kf[o], n_kf);
-        if (obs_octave[o] < 0 || obs_octave[o] >= settings->n_levels) TRI_INVALID("observation %d: octave %d outside [0, %d)", o, obs_octave[o], settings->n_levels);
-        const ms_pinhole &c = kf_cam[obs_kf[o]];
-        if (c.width < 1 || c.height < 1 || !(c.fx > 0.0) || !(c.fy > 0.0) || !std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy))
-            TRI_INVALID("keyframe slot %d: bad camera (%d x %d, fx %g, fy %g)", obs_kf[o], c.width, c.height, c.fx, c.fy);
-    }
-    int bad = 0;
-    if (!ms_distinct_in_range(rows, n_rows, n_mp, &bad)) {
-        if (bad >= 0) TRI_INVALID("row entry %d: row %d outside [0, %d)", bad, rows[bad], n_mp);
-        TRI_INVALID("row %d is listed twice", -1 - bad);
-    }
-    return MS_OK;
-}
-
-namespace {
-
 // The lists of one call: HOST arrays that are uploaded (ms_triangulate), or DEVICE arrays the kernels read where they lie (ms_triangulate_lists).
 struct TriLists {
     const int32_t *rows;
@@ -576,6 +534,8 @@ extern "C" int ms_triangulate(ms_ctx *c, double *mp_pos, uint8_t *mp_flags, int 
     const TriLists L{rows, was_triangulated, obs_start, obs_kf, obs_octave, obs_x, obs_y, obs_depth, false};
     return tri_run(c, mp_pos, mp_flags, kf_pose, n_kf, kf_cam, kf_focal, L, n_rows, obs_start[n_rows], settings, mode, status, reason, n_pass);
 }
+
+#define TRI_INVALID(...) return ms_why(MS_ERR_INVALID, why, why_bytes, "triangulate: " __VA_ARGS__)
 
 // The lists are DEVICE arrays here, so only the host arguments can be looked at: the settings and the mode as ms_triangulate_check does, the
 // sizes and the pointers.  What the lists hold is the caller's: ms_observation_lists makes them valid by construction.

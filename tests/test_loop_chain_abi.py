@@ -39,7 +39,11 @@ def test_library_exports_the_calls_and_python_binds_them():
     assert not re.search(r"^loop_chain\.o\s*:.*FLAGS", mk, flags=re.M)                           # the default -ffp-contract=off
     src = open(os.path.join(ROOT, "slam-module_amd", "csrc", "loop_chain.hip")).read()
     assert '#include "ms_scan.h"' in src and "block_rank<kBlock>" in src and "block_offsets<kBlock>" in src and "MS_WS_LOOP_CHAIN" in src and "ms_pinned(" in src
-    assert '#include "loop_chain_check.h"' in src
+    internal = open(os.path.join(ROOT, "slam-module_amd", "csrc", "ms_internal.h")).read()
+    checks = open(os.path.join(ROOT, "slam-module_amd", "csrc", "map_checks.cpp")).read()
+    assert '#include "ms_internal.h"' in src and '#include "ms_check.h"' in internal and '#include "ms_check.h"' in checks     # the validation is one host-only unit
+    for name in CALLS:
+        assert 'extern "C" int %s_check(' % name not in src and 'extern "C" int %s_check(' % name in checks, name
     assert "MS_WS_LOOP_CHAIN" in open(os.path.join(ROOT, "slam-module_amd", "csrc", "ms_internal.h")).read()
 
 
@@ -66,9 +70,9 @@ def test_caps_match_the_header(tmp_path):
 
 
 def test_the_check_header_compiles_alone_and_clean_under_sanitizers(tmp_path):
-    """loop_chain_check.h is plain C++: a program with its own main carries the three checks and runs under ASan and UBSan."""
+    """map_checks.cpp is plain C++: a program with its own main links the three checks and runs under ASan and UBSan."""
     src, exe = tmp_path / "alone.cpp", tmp_path / "alone"
-    src.write_text('#define LOOP_CHAIN_HOST_ONLY\n#include "loop_chain_check.h"\n#include <cstring>\nint main() {\n'
+    src.write_text('#include "mi355slam.h"\n#include <cstring>\nint main() {\n'
                    "  char why[64]; int32_t kf_mp[8] = {0}, slots[2] = {1, 0}, n_kp[2] = {4, 0}, req[2] = {1, 0}, row[4]; uint8_t flags[3] = {0}, mask[4];\n"
                    "  uint8_t *usable[2] = {mask, nullptr}; int32_t *tri[2] = {row, nullptr};\n"
                    "  if (ms_loop_usable_mask_check(kf_mp, 2, 4, flags, nullptr, 3, slots, n_kp, req, usable, tri, 2, why, sizeof why)) return 1;\n"
@@ -76,7 +80,7 @@ def test_the_check_header_compiles_alone_and_clean_under_sanitizers(tmp_path):
                    "  if (ms_loop_usable_mask_check(kf_mp, 2, 4, flags, nullptr, 3, slots, n_kp, req, usable, tri, 2, why, sizeof why) != MS_ERR_INVALID) return 2;\n"
                    '  return std::strncmp(why, "loop mask: slot 2", 17) ? 3 : 0;\n}\n')
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I",
-                           os.path.join(ROOT, "slam-module_amd", "csrc"), str(src), "-o", str(exe)])
+                           os.path.join(ROOT, "include"), str(src), os.path.join(ROOT, "slam-module_amd", "csrc", "map_checks.cpp"), "-o", str(exe)])
     subprocess.check_call([str(exe)])
 
 
