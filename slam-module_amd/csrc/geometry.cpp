@@ -5,7 +5,10 @@
 // half-width table (orb_extractor.cpp:174-186) and the fixed-point coefficient tables of
 // cv::resize(INTER_LINEAR) on 8U (OpenCV semantics, restated; SURVEY 8a "OpenCV semantics").
 // Everything here runs once per extractor on the host; the per-frame arithmetic is all on the GPU.
-#include "ms_internal.h"
+// Plain C++17, no HIP: tests/orb_geom_check.cpp compiles this file alone.
+#include "ms_geometry.h"
+#include "../../include/mi355slam.h"
+#include <algorithm>
 #include <cmath>
 
 namespace msgeo {

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/mi355slam.h"
 #include "ms_check.h"
+#include "ms_geometry.h"      // msgeo::* (geometry.cpp), ms_div_up
 #include "ms_layout.h"
 
 struct MsWorkspace {
@@ -119,17 +120,6 @@ inline int ms_fail(ms_ctx *ctx, int code, const char *fmt, ...) {
             return ms_fail((ctx), MS_ERR_HIP, "launch of %s failed: %s", name, hipGetErrorString(e__)); \
     } while (0)
 
-// host geometry (geometry.cpp) -- restates static_settings.cpp:9-60 and image_pyramid.cpp:76-78
-namespace msgeo {
-void scale_factors(int levels, float f, float *out);
-void level_sigma_sq(int levels, float f, float *out);
-void level_quotas(int levels, float f, int max_kpts, int32_t *out);
-void level_sizes(int levels, float f, int w0, int h0, int32_t *w, int32_t *h);
-void umax(int32_t *u16);
-// cv::resize INTER_LINEAR 8U coefficient tables (11-bit fixed point)
-void resize_tables(int src_n, int dst_n, bool is_x, std::vector<int16_t> &ofs, std::vector<int16_t> &coef);
-}  // namespace msgeo
-
 // Stage ranges for a profiler's marker trace (ms_set_trace_ranges): roctxRangePushA / roctxRangePop, resolved at run time from
 // librocprofiler-sdk-roctx / libroctx64 -- no link dependency, nothing happens (one relaxed load) while they are off.
 void ms_range_push(const char *name);
@@ -142,5 +132,3 @@ struct MsRange {
     MsRange(const MsRange &) = delete;
     MsRange &operator=(const MsRange &) = delete;
 };
-
-inline int ms_div_up(int a, int b) { return (a + b - 1) / b; }

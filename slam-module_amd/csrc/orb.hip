@@ -26,41 +26,16 @@
 #include "describe_brief_index.h"
 #include "resize_vpass.h"
 #include "resize_plan.h"
+#include "orb_geom.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
 namespace {
 
-constexpr int kPatchRadius = MS_ORB_PATCH_RADIUS;   // 19
 using describe_lanes::kHalfPatch;                    // 15, ORB_FAST_PATCH_HALF_SIZE
-constexpr int kMaxQuota = 4096;                      // per-level selection capacity (LDS sort)
 
-struct LevelGeom {
-    int32_t w, h, pitch, quota;
-    int32_t min_dist;                 // per-level minimum keypoint distance (0/1 = none), feature_detector.cpp:79-82
-    int32_t det_base;                 // first slot of this level in det arrays (prefix of quotas)
-    int32_t cand_cap;                 // capacity of this level's candidate list (entries)
-    int32_t btiles_x, btile_base;     // k_blur tile table (248 x 72 tiles: 4 waves x kBlurRows rows)
-    uint32_t btiles_inv;              // ceil(2^32 / tiles_x): row of a tile = mulhi(t, inv), exact for t < 2^16
-    uint64_t img_off, blur_off;       // byte offsets inside a frame slab
-    uint64_t cand_off;                // entry offset inside a frame's candidate buffer
-    float scale;                      // scaleFactors[l] (float32 chain)
-};
-
-struct PyrGeom {
-    int32_t levels, lk_level, fast_threshold, max_kpts, max_tracks, capacity;
-    int32_t det_stride;               // per-frame stride of the det arrays = max(max_kpts, sum of the level quotas): the quotas are rounded per level
-                                      // (static_settings.cpp:52) and can add up to more than max_kpts (e.g. 15 levels / 160 keypoints -> 161)
-    int32_t width, height, btiles_total, ftiles_total;      // ftiles_total: entries of k_fast's tile table (fast_tiles.h)
-    uint64_t slab_stride, cand_stride;     // per frame: bytes / entries
-    int32_t umax[16];
-    LevelGeom L[MS_MAX_LEVELS];
-};
-
-// first tile id of every level, passed BY VALUE (kernel-argument SGPRs): finding a block's level must not be a chain of
-// dependent loads from the geometry table (that chain was a third of k_fast's wave time)
-struct TileMap { int32_t base[MS_MAX_LEVELS + 1]; };
+// (LevelGeom, PyrGeom, TileMap, TileLevel, TileLevels and the constants kPatchRadius, kMaxQuota, kResizeRows, kBlurSeg, kBlurRows: orb_geom.h)
 __device__ __forceinline__ int tile_level(const TileMap &tm, int levels, int t) {
     int l = 0;
 #pragma unroll
@@ -68,27 +43,12 @@ __device__ __forceinline__ int tile_level(const TileMap &tm, int levels, int t) 
     return l;
 }
 
-// What the tiled kernels (k_blur, k_fast) need about a level, also BY VALUE in the kernel arguments: one batch of scalar loads from the
-// kernel-argument segment once the block knows its level, instead of a chain of dependent loads from the geometry table behind branches.
-struct TileLevel { int32_t w, h, pitch, btiles_x, cand_cap; uint32_t btiles_inv; uint64_t img_off, blur_off, cand_off; float scale; int32_t det_base;
-                   int32_t sel_k; };     // sel_k: how many of the level's strongest candidates k_select looks at (its `want`)
-struct TileLevels { TileLevel L[MS_MAX_LEVELS]; uint64_t slab_stride, cand_stride; int32_t levels, fast_threshold; };
-
 struct FrameSrc {          // where pyramid level 0 lives for this call
     const uint8_t *lvl0;
     uint64_t lvl0_frame_stride;
     int32_t lvl0_pitch;
     uint8_t *slab;
 };
-
-__device__ __forceinline__ const uint8_t *level_ptr(const FrameSrc &s, const PyrGeom *g, int f, int l, int &pitch) {
-    if (l == 0) { pitch = s.lvl0_pitch; return s.lvl0 + (uint64_t)f * s.lvl0_frame_stride; }
-    pitch = g->L[l].pitch;
-    return s.slab + (uint64_t)f * g->slab_stride + g->L[l].img_off;
-}
-__device__ __forceinline__ uint8_t *blur_ptr(const FrameSrc &s, const PyrGeom *g, int f, int l) {
-    return s.slab + (uint64_t)f * g->slab_stride + g->L[l].blur_off;
-}
 
 // ------------------------------------------------------------------------------------------------
 // copy a non-aligned caller image into the slab's level-0 plane (only when in-place use is impossible)
@@ -137,8 +97,6 @@ __device__ __forceinline__ int resize_px(uint64_t w0, uint64_t w1, int k, int a0
     const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
     return min(max(v, 0), 255);
 }
-
-constexpr int kResizeRows = 5;   // destination rows per lane: the table fetch is paid once and 10 source windows (30 dwords) are in flight per lane
 
 struct Window3 { uint32_t d0, d1, d2; };
 typedef uint32_t u3_t __attribute__((ext_vector_type(3)));
@@ -466,10 +424,6 @@ __device__ __forceinline__ int wave_scan_add(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x143 /*row_bcast:31*/, 0xc, 0xf, false);
     return v;
 }
-
-constexpr int kBlurSeg = 248;   // outputs per wave row segment
-constexpr int kBlurRows = 18;   // output rows per wave (+ 6 halo rows loaded).  Measured in one session: 8 -> 0.61 ms, 14 -> 0.53, 16 -> 0.67 (64-row tiles: row starts collide), 18 -> 0.51, 28 -> 0.51
-// (8 pixels per lane with 8-byte loads and stores -- half the memory instructions per pixel -- was built and measured: 0.60 ms against 0.51, at 6..10 rows per wave)
 
 __global__ __launch_bounds__(256) void k_blur(FrameSrc src, TileLevels TL, TileMap tm) {
     int t = blockIdx.x;
@@ -1490,32 +1444,20 @@ struct ms_orb {
     ms_ctx *ctx = nullptr;
     ms_orb_config cfg{};
     PyrGeom geom{};
-    PyrGeom *d_geom = nullptr;
     TileMap blur_tiles{};
-    uint2 *d_ftile_tab = nullptr;      // k_fast: (level | S << 4, X0 | Y0 << 16) of every tile
     TileLevels tile_levels{};          // per-level geometry of the tiled kernels, passed by value
-    uint8_t *d_slab = nullptr;
-    uint32_t *d_cand = nullptr;
-    int32_t *d_cand_count = nullptr, *d_det_count = nullptr, *d_trk_count = nullptr;
+    // the device block and the pointers into it, one d_<name> per array of orb_geom.h's lists (a per-level one is null where the level has no such table)
+    uint8_t *d_block = nullptr;
+#define ORB_X_MEMBER(T, name, n) T *d_##name = nullptr;
+#define ORB_XL_MEMBER(T, name, n) T *d_##name[MS_MAX_LEVELS] = {nullptr};
+    ORB_BLOCK_CONSTANTS(ORB_X_MEMBER, ORB_XL_MEMBER)
+    ORB_BLOCK_WORK(ORB_X_MEMBER)
+#undef ORB_X_MEMBER
+#undef ORB_XL_MEMBER
     size_t cand_count_bytes = 0, score_hist_bytes = 0;
-    uint32_t *d_score_hist = nullptr;  // k_fast: 256 score bins per (frame, level) of the candidates found so far in the launch; zero between calls
-    int32_t *d_last_count = nullptr;   // candidates k_fast appended per (frame, level) in the last call (ms_orb_last_candidate_counts)
-    int16_t *d_det_x = nullptr, *d_det_y = nullptr, *d_trk_x = nullptr, *d_trk_y = nullptr;
-    uint8_t *d_det_score = nullptr, *d_mask = nullptr;
-    float *d_trk_px = nullptr, *d_trk_py = nullptr, *d_track_xy = nullptr;
-    int32_t *d_trk_id = nullptr, *d_track_id = nullptr, *d_n_tracks = nullptr;
-    // outputs
-    float *d_x = nullptr, *d_y = nullptr, *d_angle = nullptr;
-    int32_t *d_octave = nullptr, *d_track = nullptr, *d_count = nullptr;
-    uint2 *d_slot_tab = nullptr;              // k_slots: output slot -> (x | y << 16, level)
-    uint32_t *d_desc = nullptr;
-    // resize tables per level (device)
-    int16_t *d_xtab[MS_MAX_LEVELS] = {nullptr}, *d_ytab[MS_MAX_LEVELS] = {nullptr};
+    uint8_t *d_mask = nullptr;         // ms_orb_set_valid_mask: an allocation of its own, it comes and goes
     bool wide[MS_MAX_LEVELS] = {false};
-    uint32_t *d_xtab8[MS_MAX_LEVELS] = {nullptr};    // k_resize8's column table, on the levels it may take (resize_plan.h); nullptr elsewhere
     int resize_px = 0, resize_map = 0;                // ms_orb_set_resize_plan: 0 = automatic
-    uint4 *d_moment_tab = nullptr;            // k_describe: disc mask of the orientation patch, four dwords per lane
-    float4 *d_pattern_f = nullptr;            // k_describe: the 256 BRIEF point pairs as floats
     int describe_order = describe_order::kDefaultMode;   // bit 0: XCD-contiguous blocks (describe_strips::remap), bit 1: spatial visit order (k_slots) (ms_orb_set_describe_order)
     int describe_strip = 0;                   // k_describe: 0 = the automatic launch plan (describe_strips.h), 1 .. 8 = every wave walks that many keypoints (ms_orb_set_describe_strip)
     // optional per-stage HIP events (ms_orb_set_profiling)
@@ -1540,12 +1482,6 @@ struct ms_orb {
     int lvl0_pitch = 0;
 };
 
-template <typename T>
-static int dev_calloc(ms_ctx *c, T **p, size_t n) {
-    MS_HIP(c, hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T) ? n * sizeof(T) : 1));
-    MS_HIP(c, hipMemsetAsync(*p, 0, n * sizeof(T) ? n * sizeof(T) : 1, c->stream));
-    return MS_OK;
-}
 #define MS_TRY(x) do { int rc__ = (x); if (rc__ != MS_OK) return rc__; } while (0)
 
 // KeyPoint::serialize (key_point.hpp:22-25): ar(pt.x, pt.y, angle, octave, octave, bearing, descriptor) -- 19 dwords per keypoint
@@ -1567,180 +1503,61 @@ __global__ __launch_bounds__(256) void k_pack_keypoints(const float *__restrict_
     out[i] = v;
 }
 
+// lays the device block out, allocates it, points the handle's d_<name> into it, uploads the constants in one copy and zeroes the rest
+static int orb_take_block(ms_orb *o, const OrbGeom &R, const OrbTables &C) {
+    ms_ctx *c = o->ctx;
+    const OrbBlock K = orb_block_layout(o->cfg, R, C);
+    MS_HIP(c, hipMalloc(reinterpret_cast<void **>(&o->d_block), K.end));
+#define ORB_X_BIND(T, name, n) o->d_##name = K.name.at(o->d_block);
+#define ORB_XL_BIND(T, name, n) for (int l = 0; l < MS_MAX_LEVELS; ++l) o->d_##name[l] = K.name[l].count ? K.name[l].at(o->d_block) : nullptr;
+    ORB_BLOCK_CONSTANTS(ORB_X_BIND, ORB_XL_BIND)
+    ORB_BLOCK_WORK(ORB_X_BIND)
+#undef ORB_X_BIND
+#undef ORB_XL_BIND
+    o->cand_count_bytes = K.cand_count.bytes(); o->score_hist_bytes = K.score_hist.bytes();
+    std::vector<uint8_t> stage;
+    orb_stage_constants(K, R, C, stage);
+    MS_HIP(c, hipMemcpyAsync(o->d_block, stage.data(), K.const_end, hipMemcpyHostToDevice, c->stream));
+    MS_HIP(c, hipMemsetAsync(o->d_block + K.const_end, 0, K.end - K.const_end, c->stream));
+    MS_HIP(c, hipStreamSynchronize(c->stream));          // `stage` goes out of scope
+    return MS_OK;
+}
+
+// the copy stream and its events (batches of host frames only; a one-frame extractor never uses them)
+static int orb_create_streams(ms_orb *o) {
+    ms_ctx *c = o->ctx;
+    MS_HIP(c, hipEventCreateWithFlags(&o->ev_end, hipEventDisableTiming));
+    if (o->cfg.max_batch < 32) return MS_OK;
+    MS_HIP(c, hipStreamCreateWithFlags(&o->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 4; ++i) {
+        MS_HIP(c, hipEventCreateWithFlags(&o->ev_copied[i], hipEventDisableTiming));
+        MS_HIP(c, hipEventCreateWithFlags(&o->ev_free[i], hipEventDisableTiming));
+    }
+    return MS_OK;
+}
+
 extern "C" {
 
 int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
     if (!ctx || !cfg || !out) return MS_ERR_INVALID;
     *out = nullptr;
-    if (cfg->levels < 1 || cfg->levels > MS_MAX_LEVELS || cfg->max_kpts < 1 || cfg->max_batch < 1 || cfg->max_tracks < 0 ||
-        cfg->lk_track_level < 0 || cfg->lk_track_level >= cfg->levels || cfg->fast_threshold < 1 || cfg->fast_threshold > 254 ||
-        !(cfg->scale_factor > 1.0f) || !(cfg->min_distance >= 0.f) || cfg->width > 32767 || cfg->height > 32767 ||
-        (int64_t)cfg->width * cfg->height >= (1 << 24))
-        return ms_fail(ctx, MS_ERR_INVALID, "ms_orb_create: unsupported configuration");
+    // on the host, nothing allocated: the geometry (which is also the check of the configuration) and the constant tables
+    OrbGeom R;
+    char why[256];
+    const int bad = orb_geometry(*cfg, R, why, sizeof(why));
+    if (bad != MS_OK) return ms_fail(ctx, bad, "ms_orb_create: %s", why);
+    OrbTables C;
+    orb_tables(R.geom, C);
     MS_HIP(ctx, hipSetDevice(ctx->device));
     ms_orb *o = new ms_orb();
     o->ctx = ctx;
     o->cfg = *cfg;
-    PyrGeom &G = o->geom;
-    G.levels = cfg->levels; G.lk_level = cfg->lk_track_level; G.fast_threshold = cfg->fast_threshold;
-    G.max_kpts = cfg->max_kpts; G.max_tracks = cfg->max_tracks;
-    G.width = cfg->width; G.height = cfg->height;
-    int32_t w[MS_MAX_LEVELS], h[MS_MAX_LEVELS], quota[MS_MAX_LEVELS];
-    float sf[MS_MAX_LEVELS];
-    msgeo::level_sizes(cfg->levels, cfg->scale_factor, cfg->width, cfg->height, w, h);
-    msgeo::level_quotas(cfg->levels, cfg->scale_factor, cfg->max_kpts, quota);
-    msgeo::scale_factors(cfg->levels, cfg->scale_factor, sf);
-    msgeo::umax(G.umax);
-    uint64_t off = 0, coff = 0;
-    int det_base = 0, bt = 0;
-    for (int l = 0; l < cfg->levels; ++l) {
-        if (w[l] < 2 * kPatchRadius + 2 || h[l] < 2 * kPatchRadius + 2 || quota[l] > kMaxQuota) {
-            delete o;
-            return ms_fail(ctx, MS_ERR_INVALID, "ms_orb_create: level %d is %dx%d (min 40x40) / quota %d (max %d)", l, w[l], h[l], quota[l], kMaxQuota);
-        }
-        if ((int64_t)ms_div_up(w[l], kBlurSeg) * ms_div_up(h[l], 4 * kBlurRows) >= 65536) {      // k_blur's mulhi tile division is exact below 2^16 tiles per level
-            delete o;
-            return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: level %d (%dx%d) needs more than 65535 blur tiles", l, w[l], h[l]);
-        }
-        LevelGeom &L = G.L[l];
-        L.w = w[l]; L.h = h[l]; L.pitch = (int)ms_align_up(w[l], 64); L.quota = quota[l]; L.scale = sf[l];
-        {   // feature_detector.cpp:79-82: minDist = floor(gfttMinDistance * (min(w,h) / 720 * 0.8) + 0.5)
-            const double su = std::min(w[l], h[l]) / 720.0 * 0.8;
-            L.min_dist = (int)std::floor(cfg->min_distance * su + 0.5);
-        }
-        L.det_base = det_base; det_base += quota[l];
-        L.img_off = off; off += (uint64_t)L.pitch * L.h;
-        L.blur_off = off; off += (uint64_t)L.pitch * L.h;
-        L.cand_cap = (int32_t)ms_align_up((size_t)(((w[l] + 1) / 2) * ((h[l] + 1) / 2) + 256), 4);   // strict 3x3 maxima: <= one per 2x2 block; a multiple of 4 so that every level's list starts 16-byte aligned (k_select reads it as uint4)
-        L.cand_off = coff; coff += L.cand_cap;
-        L.btiles_x = ms_div_up(w[l], kBlurSeg); L.btile_base = bt; bt += L.btiles_x * ms_div_up(h[l], 4 * kBlurRows);
-        L.btiles_inv = (uint32_t)(((1ull << 32) + L.btiles_x - 1) / L.btiles_x);
-    }
-    G.btiles_total = bt;
-    std::vector<uint2> ftab;                             // k_fast's tile table (the cover of fast_tiles.h): level | S << 4,  X0 | Y0 << 16
-    {
-        std::vector<fast_tiles::Tile> cover;
-        for (int l = 0; l < cfg->levels; ++l) {
-            cover.clear();
-            fast_tiles::cover(w[l], h[l], cover);
-            for (const fast_tiles::Tile &t : cover) ftab.push_back(make_uint2((uint32_t)l | ((uint32_t)t.S << 4), (uint32_t)t.X0 | ((uint32_t)t.Y0 << 16)));
-            if (!cover.empty() && (cover.back().X0 > 0xFFFF || cover.back().Y0 > 0xFFFF)) {      // 16 bits each in the entry; the last tile of a level has the largest of both
-                delete o;
-                return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: level %d (%dx%d) is beyond the detector's tile table (65535 px)", l, w[l], h[l]);
-            }
-        }
-    }
-    G.ftiles_total = (int)ftab.size();
-    if (ftab.size() > 65535) {                           // the tile index is k_fast's grid y
-        delete o;
-        return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: %zu detector tiles per frame (max 65535)", ftab.size());
-    }
-    G.det_stride = std::max(cfg->max_kpts, det_base);       // the reference keeps per-level vectors, so a frame can hold sum(quota) > maxKeypoints points
-    G.capacity = G.det_stride + cfg->max_tracks;
-    if (G.capacity >= (1 << (32 - describe_order::kSlotShift))) {      // a slot-table entry holds the output slot beside the level
-        delete o;
-        return ms_fail(ctx, MS_ERR_CAPACITY, "ms_orb_create: %d output slots per frame (max %d)", G.capacity, (1 << (32 - describe_order::kSlotShift)) - 1);
-    }
-    for (int l = 0; l < cfg->levels; ++l) {
-        const LevelGeom &L = G.L[l];
-        const int sel_k = (cfg->min_distance > 0.f && L.min_dist >= 2) ? std::min(4 * L.quota, kMaxQuota) : L.quota;     // k_select's `want`
-        o->tile_levels.L[l] = TileLevel{L.w, L.h, L.pitch, L.btiles_x, L.cand_cap, L.btiles_inv, L.img_off, L.blur_off, L.cand_off, L.scale, L.det_base, sel_k};
-    }
-    for (int l = 0; l <= MS_MAX_LEVELS; ++l) o->blur_tiles.base[l] = l < cfg->levels ? G.L[l].btile_base : bt;
-    G.slab_stride = ms_align_up(off, 256); G.cand_stride = coff;
-    o->tile_levels.slab_stride = G.slab_stride; o->tile_levels.cand_stride = G.cand_stride; o->tile_levels.levels = G.levels; o->tile_levels.fast_threshold = G.fast_threshold;
-    o->lvl0_off = G.L[0].img_off; o->lvl0_pitch = G.L[0].pitch;
-    const size_t B = cfg->max_batch, cap = G.capacity;
-    int rc = MS_OK;
-    auto A = [&](int r) { if (rc == MS_OK) rc = r; };
-    A(dev_calloc(ctx, &o->d_geom, 1));
-    A(dev_calloc(ctx, &o->d_slab, B * G.slab_stride + 256));   // + slack (round 1's k_describe could touch one byte past the last plane; today's window loads stay inside the level)
-    A(dev_calloc(ctx, &o->d_cand, B * G.cand_stride));
-    A(dev_calloc(ctx, &o->d_cand_count, B * MS_MAX_LEVELS));
-    o->cand_count_bytes = sizeof(int32_t) * B * MS_MAX_LEVELS;
-    A(dev_calloc(ctx, &o->d_score_hist, B * MS_MAX_LEVELS * 256));
-    o->score_hist_bytes = sizeof(uint32_t) * B * MS_MAX_LEVELS * 256;
-    A(dev_calloc(ctx, &o->d_last_count, B * MS_MAX_LEVELS));
-    A(dev_calloc(ctx, &o->d_det_count, B * MS_MAX_LEVELS));
-    A(dev_calloc(ctx, &o->d_trk_count, B));
-    A(dev_calloc(ctx, &o->d_det_x, B * (size_t)G.det_stride));
-    A(dev_calloc(ctx, &o->d_det_y, B * (size_t)G.det_stride));
-    A(dev_calloc(ctx, &o->d_det_score, B * (size_t)G.det_stride));
-    const size_t T = (size_t)std::max(cfg->max_tracks, 1);
-    A(dev_calloc(ctx, &o->d_trk_x, B * T)); A(dev_calloc(ctx, &o->d_trk_y, B * T));
-    A(dev_calloc(ctx, &o->d_trk_px, B * T)); A(dev_calloc(ctx, &o->d_trk_py, B * T));
-    A(dev_calloc(ctx, &o->d_trk_id, B * T)); A(dev_calloc(ctx, &o->d_track_xy, B * T * 2));
-    A(dev_calloc(ctx, &o->d_track_id, B * T)); A(dev_calloc(ctx, &o->d_n_tracks, B));
-    A(dev_calloc(ctx, &o->d_x, B * cap)); A(dev_calloc(ctx, &o->d_y, B * cap)); A(dev_calloc(ctx, &o->d_angle, B * cap));
-    A(dev_calloc(ctx, &o->d_octave, B * cap)); A(dev_calloc(ctx, &o->d_track, B * cap)); A(dev_calloc(ctx, &o->d_count, B)); A(dev_calloc(ctx, &o->d_slot_tab, B * cap));
-    A(dev_calloc(ctx, &o->d_desc, B * cap * 8));
-    if (rc == MS_OK && hipMemcpyAsync(o->d_geom, &o->geom, sizeof(PyrGeom), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = MS_ERR_HIP;
-    for (int l = 1; l < cfg->levels && rc == MS_OK; ++l) {
-        std::vector<int16_t> xo, xc, yo, yc;
-        msgeo::resize_tables(w[l - 1], w[l], true, xo, xc);
-        msgeo::resize_tables(h[l - 1], h[l], false, yo, yc);
-        const int wpad = ms_div_up(w[l], 4) * 4, hpad = ms_div_up(h[l], kResizeRows) * kResizeRows;     // whole groups, last entry repeated
-        std::vector<int16_t> xt(4 * (size_t)wpad), yt(4 * (size_t)hpad);
-        for (int d = 0; d < w[l]; ++d) { xt[4 * d] = xo[d]; xt[4 * d + 1] = xc[2 * d]; xt[4 * d + 2] = xc[2 * d + 1]; xt[4 * d + 3] = 0; }
-        for (int d = 0; d < h[l]; ++d) {      // clip(sy, 0, ssize.height) applied to both tap rows
-            yt[4 * d] = (int16_t)std::min(std::max((int)yo[d], 0), h[l - 1] - 1);
-            yt[4 * d + 1] = (int16_t)std::min(std::max((int)yo[d] + 1, 0), h[l - 1] - 1);
-            yt[4 * d + 2] = yc[2 * d]; yt[4 * d + 3] = yc[2 * d + 1];
-        }
-        for (int d = w[l]; d < wpad; ++d) for (int k = 0; k < 4; ++k) xt[4 * d + k] = xt[4 * (w[l] - 1) + k];
-        for (int d = h[l]; d < hpad; ++d) for (int k = 0; k < 4; ++k) yt[4 * d + k] = yt[4 * (h[l] - 1) + k];
-        for (int d = 0; d + 3 < w[l]; d += 4) if (xo[d + 3] + 1 - xo[d] > 7) o->wide[l] = true;   // taps beyond an 8-byte window
-        auto up = [&](int16_t **d, const std::vector<int16_t> &v) {
-            if (rc != MS_OK) return;
-            if (hipMalloc(reinterpret_cast<void **>(d), v.size() * 2) != hipSuccess ||
-                hipMemcpy(*d, v.data(), v.size() * 2, hipMemcpyHostToDevice) != hipSuccess) rc = MS_ERR_HIP;
-        };
-        up(&o->d_xtab[l], xt); up(&o->d_ytab[l], yt);
-        std::vector<uint32_t> x8;                        // the 8-pixel kernel takes the level iff its real tables pass both tests
-        if (rc == MS_OK && !o->wide[l] && resize_plan::rows_shared(yt.data(), h[l], h[l - 1]) && resize_plan::build_columns(xo.data(), xc.data(), w[l - 1], w[l], x8)) {
-            if (hipMalloc(reinterpret_cast<void **>(&o->d_xtab8[l]), x8.size() * 4) != hipSuccess ||
-                hipMemcpy(o->d_xtab8[l], x8.data(), x8.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = MS_ERR_HIP;
-        }
-    }
-    if (rc == MS_OK && (hipMalloc(reinterpret_cast<void **>(&o->d_ftile_tab), ftab.size() * sizeof(uint2) + 16) != hipSuccess ||
-                        hipMemcpy(o->d_ftile_tab, ftab.data(), ftab.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)) rc = MS_ERR_HIP;
-    if (rc == MS_OK) {                                   // k_describe's lane tables
-        static const int8_t pattern[1024] = {
-#include "orb_pattern.inc"
-        };
-        // disc mask of the 31 x 31 orientation patch as k_describe's lanes hold it: dword i = lane + 64 t (the t-th of the lane) covers columns 4 (i & 7) .. + 3 of row
-        // i >> 3; a byte is kept when |u| <= u_max[|v|] (orb_extractor.cpp:174-186, :259-271), the 32nd column and row are cleared
-        std::vector<uint32_t> mt(64 * 4 + 32 * 4 + 64 + 64 * 2, 0u);
-        for (int lane = 0; lane < 64; ++lane)
-            for (int t = 0; t < 4; ++t) mt[lane * 4 + t] = describe_lanes::disc_mask(lane, t, G.umax);
-        // behind it, pass 1 of k_describe's blur as matrix operands (B of v_mfma_i32_16x16x64_i8: lane (n, kg) holds rows k = 16 kg .. + 15 of column 16 t + n, one byte each):
-        // the taps 18 34 48 56 48 34 18 by patch column x -- window byte k contributes to x when 0 <= k - x - 1 <= 6.  Only dt = kg - t = 0 and 1 can be non-zero, and the
-        // pattern depends on (dt, n) alone: [dt][n][4 dwords], the horizontal half of describe_lanes::tap_table (entry [1][0] is all zero and serves as the zero operand);
-        // behind that the packed (row, byte) of every lane's first three window pieces, and the lane's two dwords of pass 2's A operand (the vertical taps)
-        uint32_t taps[64 * 4];
-        describe_lanes::tap_table(taps);
-        std::copy(taps, taps + 32 * 4, &mt[64 * 4]);
-        for (int lane = 0; lane < 64; ++lane) {
-            mt[64 * 4 + 32 * 4 + lane] = describe_lanes::win_pack(lane);
-            for (int dm = 0; dm < 2; ++dm) mt[64 * 4 + 32 * 4 + 64 + 2 * lane + dm] = describe_lanes::vert_operand(lane, dm);
-        }
-        std::vector<float> pf(1024);
-        for (int i = 0; i < 1024; ++i) pf[i] = (float)pattern[i];
-        if (hipMalloc(reinterpret_cast<void **>(&o->d_moment_tab), mt.size() * 4) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&o->d_pattern_f), pf.size() * 4) != hipSuccess ||
-            hipMemcpy(o->d_moment_tab, mt.data(), mt.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(o->d_pattern_f, pf.data(), pf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = MS_ERR_HIP;
-    }
-    if (rc == MS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = MS_ERR_HIP;
-    if (rc != MS_OK) { ms_orb_destroy(o); return ms_fail(ctx, rc, "ms_orb_create: device allocation failed"); }
-    {   // the copy stream and its events (batches of host frames only; a one-frame extractor never uses them)
-        bool ok = hipEventCreateWithFlags(&o->ev_end, hipEventDisableTiming) == hipSuccess;
-        if (cfg->max_batch >= 32) {
-            ok = ok && hipStreamCreateWithFlags(&o->copy_stream, hipStreamNonBlocking) == hipSuccess;
-            for (int i = 0; i < 4 && ok; ++i)
-                ok = hipEventCreateWithFlags(&o->ev_copied[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&o->ev_free[i], hipEventDisableTiming) == hipSuccess;
-        }
-        if (!ok) { ms_orb_destroy(o); return ms_fail(ctx, MS_ERR_HIP, "ms_orb_create: stream / event creation failed"); }
-    }
+    o->geom = R.geom; o->tile_levels = R.tile_levels; o->blur_tiles = R.blur_tiles;
+    o->lvl0_off = R.lvl0_off; o->lvl0_pitch = R.lvl0_pitch;
+    for (int l = 1; l < cfg->levels; ++l) o->wide[l] = C.level[l].wide;
+    // from here on one way out: ms_orb_destroy takes whatever exists
+    if (orb_take_block(o, R, C) != MS_OK) { ms_orb_destroy(o); return ms_fail(ctx, MS_ERR_HIP, "ms_orb_create: device allocation failed"); }
+    if (orb_create_streams(o) != MS_OK) { ms_orb_destroy(o); return ms_fail(ctx, MS_ERR_HIP, "ms_orb_create: stream / event creation failed"); }
     *out = o;
     return MS_OK;
 }
@@ -1749,23 +1566,12 @@ void ms_orb_destroy(ms_orb *o) {
     if (!o) return;
     (void)hipSetDevice(o->ctx->device);
     (void)hipStreamSynchronize(o->ctx->stream);
-    void *ptrs[] = {o->d_geom, o->d_slab, o->d_cand, o->d_cand_count, o->d_score_hist, o->d_last_count, o->d_det_count, o->d_trk_count, o->d_det_x, o->d_det_y,
-                    o->d_det_score, o->d_mask, o->d_trk_x, o->d_trk_y, o->d_trk_px, o->d_trk_py, o->d_trk_id, o->d_track_xy,
-                    o->d_track_id, o->d_n_tracks, o->d_x, o->d_y, o->d_angle, o->d_octave, o->d_track, o->d_count, o->d_desc, o->d_slot_tab};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (o->d_moment_tab) (void)hipFree(o->d_moment_tab);
-    if (o->d_pattern_f) (void)hipFree(o->d_pattern_f);
-    if (o->d_ftile_tab) (void)hipFree(o->d_ftile_tab);
+    if (o->d_block) (void)hipFree(o->d_block);
+    if (o->d_mask) (void)hipFree(o->d_mask);
     for (auto &set : o->evr) for (int i = 0; i <= MS_ORB_STAGES; ++i) if (set[i]) (void)hipEventDestroy(set[i]);
     if (o->copy_stream) { (void)hipStreamSynchronize(o->copy_stream); (void)hipStreamDestroy(o->copy_stream); }
     for (int i = 0; i < 4; ++i) { if (o->ev_copied[i]) (void)hipEventDestroy(o->ev_copied[i]); if (o->ev_free[i]) (void)hipEventDestroy(o->ev_free[i]); }
     if (o->ev_end) (void)hipEventDestroy(o->ev_end);
-
-    for (int l = 0; l < MS_MAX_LEVELS; ++l) {
-        if (o->d_xtab[l]) (void)hipFree(o->d_xtab[l]);
-        if (o->d_ytab[l]) (void)hipFree(o->d_ytab[l]);
-        if (o->d_xtab8[l]) (void)hipFree(o->d_xtab8[l]);
-    }
     delete o;
 }
 
