@@ -92,6 +92,7 @@ private:
 
 namespace detail {
 inline std::size_t pad16(std::size_t n) { return (n + 15) / 16 * 16; }
+inline std::size_t padded(std::size_t n) { return (n + 63) / 64 * 64 + 64; }      // the pitch of a scratch array of n entries
 
 inline unsigned run_greedy(Context &ctx, bool triangulation, const DeviceKeyframe &kf1, const DeviceKeyframe &kf2, std::vector<int> &out,
                            float ratio, const double *E12, const std::vector<float> *scaleFactors, float thrDeg) {
@@ -569,22 +570,23 @@ struct SearchBindResult {
 };
 
 // searchByProjection (keyframe_matcher.cpp:295-414) over table rows with the walk and both addObservations (:388-389) on the device tables:
-// ms_bound_mask (slot's row of kfMp -> the scoring's skip mask) -> gates -> scoring -> ms_search_bind on the lists where they lie.  kfMp
-// [nKf x stride], mpLive, nObs [nMp] are the DEVICE tables; kf is the keyframe in `slot`; usable (optional) = its DEVICE matcher mask
+// ms_bound_mask (slot's row of M.keyframes -> the scoring's skip mask) -> gates -> scoring -> ms_search_bind on the lists where they lie.  Writes
+// M.keyframes and M.observationCount, reads M.points and M.live; kf is the keyframe in `slot`; usable (optional) = its DEVICE matcher mask
 // (DeviceKeyframe::mutableUsable), cleared at each bound keypoint.  view as for searchByProjection.  Nothing comes down but the gate's n_kept
 // and the result block (and match_kp when asked for).
-inline SearchBindResult searchByProjectionOnTables(Context &ctx, const DeviceKeyframe &kf, const DeviceMapPoints &table, const GateView &view, std::int32_t *kfMp,
-                                                   std::size_t nKf, std::size_t stride, const std::uint8_t *mpLive, std::int32_t *nObs, std::size_t nMp, std::int32_t slot,
-                                                   const StaticSettings &settings, std::uint8_t *usable = nullptr, bool wantMatches = false) {
+inline SearchBindResult searchByProjectionOnTables(Context &ctx, MapTables M, const DeviceKeyframe &kf, const GateView &view, std::int32_t slot, const StaticSettings &settings,
+                                                   std::uint8_t *usable = nullptr, bool wantMatches = false) {
+    M.require("searchByProjectionOnTables", M.POINTS | M.FLAGS | M.LIVE | M.COUNTS);
     SearchBindResult out;
-    const std::size_t nKp = (std::size_t)kf.frame().n, ne = view.indices.size();
+    std::int32_t *kfMp = M.keyframes.mutableTable();
+    const std::size_t nKp = (std::size_t)kf.frame().n, ne = view.indices.size(), nKf = M.keyframes.size(), stride = M.keyframes.stride(), nMp = M.keyframes.mapPointCount();
     const detail::BoundMaskSource bound{kfMp, nKf, stride, nMp, slot};
-    const detail::DeviceGatedLists g = detail::gate_and_score_device(ctx, table, {view}, {&kf}, settings, wantMatches ? 4 : 0, &bound);
+    const detail::DeviceGatedLists g = detail::gate_and_score_device(ctx, *M.points, {view}, {&kf}, settings, wantMatches ? 4 : 0, &bound);
     std::int32_t *matchKp = wantMatches && ne ? reinterpret_cast<std::int32_t *>(g.extra) : nullptr;
     std::int32_t n = 0;
     const ms_match_frame &f = kf.frame();
-    ctx.check(ms_search_bind(ctx.get(), kfMp, (int)nKf, (int)stride, mpLive, nObs, (int)nMp, g.keptEntry, g.qX, g.qY, g.qRadius, g.qMinOctave, g.qMaxOctave, g.qDesc, g.topIdx,
-                             g.topDist, g.topOctave, g.nScored, g.skip, kf.sortedX(), kf.sortedY(), kf.sortedIndex(), f.desc, f.octave, (int)nKp, g.index.data(),
+    ctx.check(ms_search_bind(ctx.get(), kfMp, (int)nKf, (int)stride, M.live->live(), M.observationCount, (int)nMp, g.keptEntry, g.qX, g.qY, g.qRadius, g.qMinOctave, g.qMaxOctave,
+                             g.qDesc, g.topIdx, g.topDist, g.topOctave, g.nScored, g.skip, kf.sortedX(), kf.sortedY(), kf.sortedIndex(), f.desc, f.octave, (int)nKp, g.index.data(),
                              g.first[0], g.count[0], g.nKept[0], slot, matchKp, nullptr, usable, &n, out.counts.data()), "ms_search_bind");
     out.matched = (unsigned)n;
     if (matchKp) out.matchKp = ctx.download(matchKp, ne);

@@ -33,16 +33,6 @@ struct LoopClosureResult {
     std::vector<LoopCandidateOutcome> candidates;            // in candidate order, up to and including the one the loop stopped at
 };
 
-// the device tables the loop closer reads
-struct LoopCloserTables {
-    const DeviceKeyframeMapPoints &keyframes;
-    const DeviceMapPointFlags &flags;
-    const DeviceMapPointLive *live;                          // may be null: every row is live
-    const DeviceMapPoints &points;
-    const DeviceKeyframePoses &poses;
-    const DeviceKeypointTable &keypoints;
-};
-
 namespace detail {
 using Pose = std::array<double, 12>;
 inline std::array<double, 3> cameraCenterOf(const Pose &P) {                 // worldToCameraMatrixCameraCenter: -R^T t
@@ -92,14 +82,14 @@ inline LoopCode acceptGates(const Sim3 &candToCurr, const Pose &curPose, const P
     return LoopCode::OK;
 }
 // :164-187: TOO_CLOSE_TIME, UNNECESSARY_EARLY or UNKNOWN (the candidate goes on to the heavy computations)
-inline LoopCode cheapRejection(const KeyframeChain &chain, std::int32_t current, std::int32_t cand, double previousClosureT, bool isAdjacent) {
+inline LoopCode cheapRejection(const KeyframeSlots &chain, std::int32_t current, std::int32_t cand, double previousClosureT, bool isAdjacent) {
     const double correctionLength = chain.t[current] - std::max(chain.t[cand], previousClosureT);
     if (correctionLength < 5.0) return LoopCode::TOO_CLOSE_TIME;
     if (chain.t[current] - chain.t[cand] < 2.15) return LoopCode::TOO_CLOSE_TIME;
     if (isAdjacent && distance(chain.cameraCenter[cand], chain.cameraCenter[current]) < 0.5) return LoopCode::UNNECESSARY_EARLY;
     return LoopCode::UNKNOWN;
 }
-inline double distanceTraveled(const KeyframeChain &chain, std::int32_t current, std::int32_t cand) {        // :312-319
+inline double distanceTraveled(const KeyframeSlots &chain, std::int32_t current, std::int32_t cand) {        // :312-319
     double d = 0;
     for (std::int32_t at = current; at != cand;) {
         const std::int32_t before = chain.previous.at((std::size_t)at);
@@ -112,16 +102,16 @@ inline double distanceTraveled(const KeyframeChain &chain, std::int32_t current,
 }  // namespace detail
 
 // The candidate loop of tryLoopClosure (:132-357) for the keyframe in slot `current`.  candidates = getBowSimilar's keyframes of the current
-// map as slots, in its order; adjacent = the adjacent keyframes' slots; chain: previous links, camera centres, ids and times per slot;
-// frames[slot] = the keyframe's matcher inputs on the device (its `usable` mask is rewritten here); cameras per slot.
-inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTables &T, std::int32_t current, const std::vector<std::int32_t> &candidates,
-                                                const std::vector<std::int32_t> &adjacent, const KeyframeChain &chain, const std::vector<DeviceKeyframe *> &frames,
-                                                const std::vector<ms_pinhole> &cameras, double previousClosureT, const StaticSettings &settings) {
+// map as slots, in its order; adjacent = the adjacent keyframes' slots.  Of M.slots it reads the previous links, camera centres, ids, times and
+// cameras, and frames[slot] = the keyframe's matcher inputs on the device, whose `usable` mask is the one thing written here.  M.live may be
+// null: every row is live.
+inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, MapTables M, std::int32_t current, const std::vector<std::int32_t> &candidates, const std::vector<std::int32_t> &adjacent,
+                                                double previousClosureT, const StaticSettings &settings) {
+    M.require("tryLoopClosureOnTables", M.POINTS | M.FLAGS | M.POSES | M.KEYPOINTS | M.FRAMES | M.CAMERAS | M.TIMES | M.IDS | M.CENTRES | M.LINKS);
     const Parameters &P = settings.parameters;
-    const int nKf = (int)T.keyframes.size(), stride = (int)T.keyframes.stride(), nMp = (int)T.keyframes.mapPointCount();
-    if ((int)frames.size() != nKf || (int)cameras.size() != nKf || (int)chain.t.size() != nKf || (int)chain.id.size() != nKf || (int)chain.cameraCenter.size() != nKf ||
-        (int)chain.previous.size() != nKf || current < 0 || current >= nKf)
-        throw std::invalid_argument("tryLoopClosureOnTables: one frame, camera, time, id, centre and link per slot, and a current keyframe among them");
+    const KeyframeSlots &chain = M.slots;
+    const int nKf = (int)M.keyframes.size(), stride = (int)M.keyframes.stride(), nMp = (int)M.keyframes.mapPointCount();
+    if (current < 0 || current >= nKf) throw std::invalid_argument("tryLoopClosureOnTables: the current keyframe lies outside the table");
     LoopClosureResult out;
     // 1. the cheap rejections, in candidate order, with the stop of :149
     std::vector<std::size_t> heavy;                          // positions in out.candidates
@@ -138,9 +128,9 @@ inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTa
     }
     const int n = (int)heavy.size();
     if (n == 0) return out;
-    const int nKpCur = (int)frames[(std::size_t)current]->keyPointCount();
+    const int nKpCur = (int)chain.frames[(std::size_t)current]->keyPointCount();
     std::vector<std::int32_t> slot(n), nKp(n);
-    for (int c = 0; c < n; ++c) { slot[c] = out.candidates[heavy[c]].slot; nKp[c] = (int)frames[(std::size_t)slot[c]]->keyPointCount(); }
+    for (int c = 0; c < n; ++c) { slot[c] = out.candidates[heavy[c]].slot; nKp[c] = (int)chain.frames[(std::size_t)slot[c]]->keyPointCount(); }
     // 2. the matcher's masks and the TRIANGULATED rows of the current keyframe and of every survivor, one call
     std::vector<std::int32_t> mSlot{current}, mKp{nKpCur}, mReq{P.requireTringulationForLoopClosures ? 1 : 0};
     for (int c = 0; c < n; ++c) { mSlot.push_back(slot[c]); mKp.push_back(nKp[c]); mReq.push_back(1); }
@@ -149,18 +139,18 @@ inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTa
     std::vector<std::int32_t *> tri;
     for (int s = 0; s <= n; ++s) {
         triRow.emplace_back(ctx, (std::size_t)mKp[s]);
-        usable.push_back(frames[(std::size_t)mSlot[s]]->mutableUsable());
+        usable.push_back(chain.frames[(std::size_t)mSlot[s]]->mutableUsable());
         tri.push_back(triRow.back().data());
     }
-    const std::uint8_t *live = T.live ? T.live->live() : nullptr;
-    ctx.check(ms_loop_usable_mask(ctx.get(), T.keyframes.table(), nKf, stride, T.flags.flags(), live, nMp, mSlot.data(), mKp.data(), mReq.data(), usable.data(), tri.data(), n + 1),
+    const std::uint8_t *live = M.live ? M.live->live() : nullptr;
+    ctx.check(ms_loop_usable_mask(ctx.get(), M.keyframes.table(), nKf, stride, M.flags->flags(), live, nMp, mSlot.data(), mKp.data(), mReq.data(), usable.data(), tri.data(), n + 1),
               "ms_loop_usable_mask");
     // 3. matchForLoopClosures of the current keyframe against every survivor, one call; `matched` stays on the device
-    std::vector<ms_match_frame> f1((std::size_t)n, frames[(std::size_t)current]->frame()), f2;
+    std::vector<ms_match_frame> f1((std::size_t)n, chain.frames[(std::size_t)current]->frame()), f2;
     std::vector<DeviceArray<std::int32_t>> matched;
     std::vector<std::int32_t *> matchedPtr;
     for (int c = 0; c < n; ++c) {
-        f2.push_back(frames[(std::size_t)slot[c]]->frame());
+        f2.push_back(chain.frames[(std::size_t)slot[c]]->frame());
         matched.emplace_back(ctx, (std::size_t)std::max(nKpCur, 1));
         matchedPtr.push_back(matched.back().data());
     }
@@ -174,7 +164,7 @@ inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTa
     detail::Pose curPose{};
     std::vector<detail::Pose> candPose((std::size_t)n);
     std::int32_t nPairs = 0;
-    ctx.check(ms_loop_pairs(ctx.get(), T.keyframes.table(), nKf, stride, live, T.points.position(), nMp, T.poses.pose(), T.keypoints.octave(), current, nKpCur, slot.data(),
+    ctx.check(ms_loop_pairs(ctx.get(), M.keyframes.table(), nKf, stride, live, M.points->position(), nMp, M.poses->pose(), M.keypoints->octave(), current, nKpCur, slot.data(),
                             nKp.data(), matchedPtr.data(), n, settings.levelSigmaSq.data(), (int)settings.levelSigmaSq.size(), (int)cap, pairStart.data(), kp1.data(), kp2.data(),
                             row1.data(), row2.data(), cap ? pts1[0].data() : nullptr, cap ? pts2[0].data() : nullptr, thr1.data(), thr2.data(), curPose.data(),
                             candPose[0].data(), &nPairs), "ms_loop_pairs");
@@ -188,7 +178,7 @@ inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTa
     for (int c = 0; c < n; ++c) {
         const std::size_t a = (std::size_t)pairStart[c], b = (std::size_t)pairStart[c + 1];
         if (b - a < P.minLoopClosureFeatureMatches) { out.candidates[heavy[c]].code = LoopCode::TOO_FEW_FEATURE_MATCHES; continue; }
-        const ms_pinhole &k1 = cameras[(std::size_t)current], &k2 = cameras[(std::size_t)slot[c]];
+        const ms_pinhole &k1 = chain.camera[(std::size_t)current], &k2 = chain.camera[(std::size_t)slot[c]];
         ransac[c].reset(new LoopRansac(std::vector<LoopRansac::Vec3>(pts1.begin() + a, pts1.begin() + b), std::vector<LoopRansac::Vec3>(pts2.begin() + a, pts2.begin() + b),
                                        std::vector<float>(thr1.begin() + a, thr1.begin() + b), std::vector<float>(thr2.begin() + a, thr2.begin() + b),
                                        PinholeCamera{k1.fx, k1.fy, k1.cx, k1.cy, k1.width, k1.height}, PinholeCamera{k2.fx, k2.fy, k2.cx, k2.cy, k2.width, k2.height}, settings));
@@ -211,8 +201,8 @@ inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTa
         const std::vector<std::int32_t> mps2 = triRow[(std::size_t)c + 1].download();
         double R1in2[9], t1in2[3], R2in1[9], t2in1[3];
         detail::sim3ViewPoses(r.bestR12, r.bestT12, (double)r.bestScale12, curPose, candPose[c], R1in2, t1in2, R2in1, t2in1);
-        matchMapPointsSim3(ctx, *frames[(std::size_t)current], *frames[(std::size_t)slot[c]], T.points, mps1, mps2, R1in2, t1in2, R2in1, t2in1, cameras[(std::size_t)current],
-                           cameras[(std::size_t)slot[c]], lists[c], settings);
+        matchMapPointsSim3(ctx, *chain.frames[(std::size_t)current], *chain.frames[(std::size_t)slot[c]], *M.points, mps1, mps2, R1in2, t1in2, R2in1, t2in1,
+                           chain.camera[(std::size_t)current], chain.camera[(std::size_t)slot[c]], lists[c], settings);
         left.push_back(c);
     }
     if (left.empty()) return out;
@@ -228,8 +218,8 @@ inline LoopClosureResult tryLoopClosureOnTables(Context &ctx, const LoopCloserTa
     std::vector<Sim3Matches::Vec2> o1(nm), o2(nm);
     std::vector<float> i1(nm), i2(nm);
     std::vector<std::int32_t> r1(nm), r2(nm);
-    ctx.check(ms_loop_sim3_lists(ctx.get(), T.keyframes.table(), nKf, stride, live, T.points.position(), nMp, T.poses.pose(), T.keypoints.x(), T.keypoints.y(), T.keypoints.octave(),
-                                 current, nKpCur, lSlot.data(), lKp.data(), (int)left.size(), cameras.data(), settings.levelSigmaSq.data(), (int)settings.levelSigmaSq.size(),
+    ctx.check(ms_loop_sim3_lists(ctx.get(), M.keyframes.table(), nKf, stride, live, M.points->position(), nMp, M.poses->pose(), M.keypoints->x(), M.keypoints->y(), M.keypoints->octave(),
+                                 current, nKpCur, lSlot.data(), lKp.data(), (int)left.size(), chain.camera.data(), settings.levelSigmaSq.data(), (int)settings.levelSigmaSq.size(),
                                  a1.data(), a2.data(), start.data(), nm ? q1[0].data() : nullptr, nm ? q2[0].data() : nullptr, nm ? o1[0].data() : nullptr,
                                  nm ? o2[0].data() : nullptr, i1.data(), i2.data(), r1.data(), r2.data()), "ms_loop_sim3_lists");
     // 11. OptimizeSim3Transform of all of them, one call

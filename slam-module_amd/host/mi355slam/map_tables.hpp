@@ -11,6 +11,8 @@
 
 namespace mi355slam {
 
+class DeviceKeyframe;                        // keyframe_matcher.hpp
+
 // Keyframe poses on the device, one slot per keyframe: rows 0-2 of poseCW, row-major (12 doubles).  What ms_map_refresh reads the camera
 // centres from and ms_loop_correct corrects in place.  update() re-uploads a range after the host changed poses (bundle adjustment).
 class DeviceKeyframePoses {
@@ -200,6 +202,8 @@ private:
     DeviceArray<float> depth_;
 };
 
+struct MapTables;
+
 // Which rows an observation-list call takes: the map points of one keyframe slot (the loops of mapper_helpers.cpp:1062 / :1085), or rows
 // that already lie on the device (the output of a map-point union, removed rows), and the filter of the loop (MS_OBS_*).
 struct ObservationSelection {
@@ -215,34 +219,9 @@ struct ObservationSelection {
 class DeviceObservationLists {
 public:
     explicit DeviceObservationLists(Context &ctx, std::size_t rows = 256, std::size_t observations = 2048) : ctx_(ctx) { reserve(rows, observations); }
-    // kfIds: per slot the KfId, -1 for an empty slot; descBase: per slot the DeviceDescriptorPool index of its keypoint 0, -1 for none
-    // (empty: no descriptor indices); levels: octaves outside [0, levels) are an error (0: not looked at).
-    void build(const DeviceKeyframeMapPoints &table, const DeviceKeypointTable &keypoints, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &kfIds,
-               const std::vector<std::int32_t> &descBase, const ObservationSelection &selection, int levels) {
-        if (kfIds.size() != table.size() || (!descBase.empty() && descBase.size() != table.size())) throw std::invalid_argument("DeviceObservationLists::build: one KfId and one base per slot");
-        if (keypoints.size() != table.size() || keypoints.stride() != table.stride()) throw std::invalid_argument("DeviceObservationLists::build: the keypoint table does not match the keyframe table");
-        if (flags && flags->size() < table.mapPointCount()) throw std::invalid_argument("DeviceObservationLists::build: fewer flags than map points");
-        const ms_obs_select sel{selection.slot >= 0 ? MS_OBS_FROM_SLOT : MS_OBS_FROM_ROWS, selection.filter, selection.dropEmpty ? 1 : 0, selection.slot, selection.deviceRows,
-                                (std::int32_t)selection.rowCount};
-        if (!buf_.obsStart.data()) reserve(0, 0);            // a regrow that failed left nothing behind: start again from the smallest buffers
-        for (int attempt = 0;; ++attempt) {
-            ms_obs_lists l = lists();
-            if (descBase.empty()) l.obs_desc = nullptr;
-            if (!flags) l.was_triangulated = nullptr;
-            std::int32_t nRows = 0, nObs = 0;
-            const int rc = ms_observation_lists(ctx_.get(), table.table(), (int)table.size(), (int)table.stride(), (int)table.mapPointCount(), kfIds.data(),
-                                                flags ? flags->flags() : nullptr, keypoints.x(), keypoints.y(), keypoints.octave(), keypoints.depth(),
-                                                descBase.empty() ? nullptr : descBase.data(), &sel, levels, &l, (int)capRows_, (int)capObs_, &nRows, &nObs);
-            if (rc == MS_ERR_CAPACITY && attempt == 0 && ((std::size_t)nRows > capRows_ || (std::size_t)nObs > capObs_)) {
-                reserve(std::max<std::size_t>(nRows, capRows_), std::max<std::size_t>(nObs, capObs_));      // the needed counts came back: once is enough
-                continue;
-            }
-            ctx_.check(rc, "ms_observation_lists");
-            nRows_ = (std::size_t)nRows; nObs_ = (std::size_t)nObs;
-            hasDesc_ = !descBase.empty();
-            return;
-        }
-    }
+    // The lists of `selection` over M.keyframes / M.keypoints / M.flags (may be null) with M.slots.id (per slot the KfId, -1 for an empty slot);
+    // withDescriptors: M.slots.descBase gives the descriptor indices; levels: octaves outside [0, levels) are an error (0: not looked at).
+    void build(const MapTables &M, bool withDescriptors, const ObservationSelection &selection, int levels);
     // room for at least `rows` rows and `observations` observations (the contents are not kept when the buffers grow), and the counts a
     // caller that filled the lists itself (createNewMapPoints) found
     void ensure(std::size_t rows, std::size_t observations) {
@@ -254,10 +233,10 @@ public:
     std::size_t rowCount() const { return nRows_; }
     std::size_t observationCount() const { return nObs_; }
     bool hasDescriptors() const { return hasDesc_; }
-    ms_obs_lists lists() const {
+    ms_obs_lists lists(bool withDescriptors = true) const {                   // false: obs_desc = nullptr, for a call without a pool
         Buffers &b = buf_;
         return ms_obs_lists{b.rows.data(), b.obsStart.data(), b.nObsRow.data(), b.firstOctave.data(), b.wasTriangulated.data(), b.obsKf.data(), b.obsKp.data(),
-                            b.obsOctave.data(), b.obsDesc.data(), b.obsX.data(), b.obsY.data(), b.obsDepth.data()};
+                            b.obsOctave.data(), withDescriptors ? b.obsDesc.data() : nullptr, b.obsX.data(), b.obsY.data(), b.obsDepth.data()};
     }
     // a copy for the host (tests, debugging): `count` int32 from a row array (rows, obs_start, n_obs_row, first_octave) or an observation array
     std::vector<std::int32_t> download(const std::int32_t *deviceArray, std::size_t count) const { return ctx_.download(deviceArray, count); }
@@ -336,5 +315,84 @@ private:
     std::int32_t base_;
     mutable DeviceArray<std::int32_t> mpTrack_, trackRow_;      // mpTrack() / trackRow() const hand out the pointers the kernels write through
 };
+
+// ---- the view every map-table entry point takes ------------------------------------------------------------------------------------------
+// What the host keeps per keyframe slot, one entry per slot of DeviceKeyframeMapPoints in each vector a step reads (MapTables::require).
+struct KeyframeSlots {
+    std::vector<std::int32_t> id;                            // KfId, -1 for an empty slot
+    std::vector<double> t;                                   // Keyframe::t
+    std::vector<std::int32_t> previous, next;                // previousKfId / nextKfId as slots, -1 for none
+    std::vector<std::array<double, 3>> cameraCenter;         // Keyframe::cameraCenter()
+    std::vector<ms_pinhole> camera;                          // the pinhole stand-in of kf.shared->camera
+    std::vector<std::int32_t> focalLength;                   // its getFocalLength()
+    std::vector<std::int32_t> descBase;                      // DeviceDescriptorPool index of the slot's keypoint 0, -1 for none
+    std::vector<DeviceKeyframe *> frames;                    // the slot's matcher inputs on the device, null for none
+};
+
+// The map tables as one non-owning view: references for what every step reads, pointers for what only some do.  Built once and passed down a
+// chain of steps; each step names the parts it needs in one require() line and says in its comment which tables it writes.
+struct MapTables {
+    enum Part : unsigned { POINTS = 1, FLAGS = 2, LIVE = 4, KEYPOINTS = 8, POSES = 16, TRACKS = 32, COUNTS = 64, LISTS = 128, CAMERAS = 256, FOCALS = 512, IDS = 1024,
+                           TIMES = 2048, LINKS = 4096, CENTRES = 8192, DESC_BASES = 16384, FRAMES = 32768 };
+    DeviceKeyframeMapPoints &keyframes;
+    KeyframeSlots &slots;
+    DeviceMapPoints *points = nullptr;
+    DeviceMapPointFlags *flags = nullptr;
+    DeviceMapPointLive *live = nullptr;
+    DeviceKeypointTable *keypoints = nullptr;
+    DeviceKeyframePoses *poses = nullptr;
+    DeviceTrackTable *tracks = nullptr;
+    DeviceDescriptorPool *pool = nullptr;
+    std::int32_t *observationCount = nullptr;                // DEVICE [mapPointCount]: mp.observations.size() of every row (observationCountsOnDevice)
+    DeviceObservationLists *lists = nullptr;                 // scratch of the steps that build observation lists
+
+    // Throws std::invalid_argument(who + ": ...") when a part of `parts` is absent, when a table that is present disagrees in size with the
+    // keyframe table, or when a per-slot vector of `parts` does not have one entry per slot.
+    void require(const char *who, unsigned parts) const {
+        const std::size_t nKf = keyframes.size(), nMp = keyframes.mapPointCount();
+        auto fail = [&](const std::string &what) { throw std::invalid_argument(std::string(who) + ": " + what); };
+        const void *const present[] = {points, flags, live, keypoints, poses, tracks, observationCount, lists};
+        const std::size_t perSlot[] = {slots.camera.size(), slots.focalLength.size(), slots.id.size(), slots.t.size(), std::min(slots.previous.size(), slots.next.size()),
+                                       slots.cameraCenter.size(), slots.descBase.size(), slots.frames.size()};
+        static const char *const name[] = {"map points", "flags", "live bytes", "keypoint table", "poses", "track table", "observation counts", "observation lists", "camera", "focal length",
+                                           "KfId", "time", "link pair", "camera centre", "descriptor base", "frame"};
+        for (unsigned i = 0; i < 8; ++i) if ((parts >> i & 1) && !present[i]) fail(std::string("no ") + name[i]);
+        if ((points && points->size() != nMp) || (flags && flags->size() < nMp) || (live && live->size() < nMp) || (tracks && tracks->mapPointCount() != nMp))
+            fail("the map-point tables differ in size");
+        if (keypoints && (keypoints->size() != nKf || keypoints->stride() != keyframes.stride())) fail("the keypoint table does not match the keyframe table");
+        if (poses && poses->size() != nKf) fail("one pose per slot");
+        for (unsigned i = 8; i < 16; ++i) if ((parts >> i & 1) && perSlot[i - 8] != nKf) fail(std::string("one ") + name[i] + " per slot");
+        if ((parts & LINKS) && slots.previous.size() != slots.next.size()) fail("one link pair per slot");
+    }
+    const std::uint32_t *poolDescriptor() const { return pool ? pool->descriptor() : nullptr; }
+    int poolSize() const { return pool ? (int)pool->size() : 0; }
+    // the four track arguments of ms_map_fuse / ms_map_replace_pairs (nulls and zeros without a track table)
+    struct TrackWindow { std::int32_t *mpTrack, *trackRow, base; int window; };
+    TrackWindow trackWindow() const { return tracks ? TrackWindow{tracks->mpTrack(), tracks->trackRow(), tracks->trackBase(), (int)tracks->window()} : TrackWindow{nullptr, nullptr, 0, 0}; }
+};
+
+inline void DeviceObservationLists::build(const MapTables &M, bool withDescriptors, const ObservationSelection &selection, int levels) {
+    M.require("DeviceObservationLists::build", M.KEYPOINTS | M.IDS | (withDescriptors ? M.DESC_BASES : 0u));
+    const DeviceKeyframeMapPoints &table = M.keyframes;
+    const ms_obs_select sel{selection.slot >= 0 ? MS_OBS_FROM_SLOT : MS_OBS_FROM_ROWS, selection.filter, selection.dropEmpty ? 1 : 0, selection.slot, selection.deviceRows,
+                            (std::int32_t)selection.rowCount};
+    if (!buf_.obsStart.data()) reserve(0, 0);                // a regrow that failed left nothing behind: start again from the smallest buffers
+    for (int attempt = 0;; ++attempt) {
+        ms_obs_lists l = lists(withDescriptors);
+        if (!M.flags) l.was_triangulated = nullptr;
+        std::int32_t nRows = 0, nObs = 0;
+        const int rc = ms_observation_lists(ctx_.get(), table.table(), (int)table.size(), (int)table.stride(), (int)table.mapPointCount(), M.slots.id.data(),
+                                            M.flags ? M.flags->flags() : nullptr, M.keypoints->x(), M.keypoints->y(), M.keypoints->octave(), M.keypoints->depth(),
+                                            withDescriptors ? M.slots.descBase.data() : nullptr, &sel, levels, &l, (int)capRows_, (int)capObs_, &nRows, &nObs);
+        if (rc == MS_ERR_CAPACITY && attempt == 0 && ((std::size_t)nRows > capRows_ || (std::size_t)nObs > capObs_)) {
+            reserve(std::max<std::size_t>(nRows, capRows_), std::max<std::size_t>(nObs, capObs_));      // the needed counts came back: once is enough
+            continue;
+        }
+        ctx_.check(rc, "ms_observation_lists");
+        nRows_ = (std::size_t)nRows; nObs_ = (std::size_t)nObs;
+        hasDesc_ = withDescriptors;
+        return;
+    }
+}
 
 }  // namespace mi355slam

@@ -39,25 +39,27 @@ struct RefreshArgs {
 // LoopCloser::correctLoop from the pose correction to the refresh of the moved map points (loop_closer.cpp:398-506) on the device tables:
 // ms_loop_correct (poses, then points), then DeviceMapPoints::refresh of refreshArgs.rows.  T = the Sim3 of :405.  Re-triangulation (:508-523)
 // stays with the caller.  Returns refresh's medoids.
-inline std::vector<int> correctLoop(Context &ctx, DeviceMapPoints &table, DeviceKeyframePoses &poses, const Sim3 &T, const LoopCorrections &corrections,
-                                    const LoopPoints &points, const RefreshArgs &refreshArgs, const StaticSettings &settings) {
-    if (corrections.rigid.size() != corrections.slot.size() || corrections.lambda.size() != corrections.slot.size() || points.reference.size() != points.row.size())
+inline std::vector<int> correctLoop(Context &ctx, DeviceMapPoints &points, DeviceKeyframePoses &poses, const Sim3 &T, const LoopCorrections &corrections,
+                                    const LoopPoints &moved, const RefreshArgs &refreshArgs, const StaticSettings &settings) {
+    if (corrections.rigid.size() != corrections.slot.size() || corrections.lambda.size() != corrections.slot.size() || moved.reference.size() != moved.row.size())
         throw std::invalid_argument("correctLoop: the correction lists have different lengths");
     const double t8[8] = {T.q[0], T.q[1], T.q[2], T.q[3], T.t[0], T.t[1], T.t[2], T.s};
-    ctx.check(ms_loop_correct(ctx.get(), poses.pose(), (int)poses.size(), table.mutablePosition(), (int)table.size(), t8, corrections.slot.data(),
-                              corrections.rigid.data(), corrections.lambda.data(), (int)corrections.slot.size(), points.row.data(), points.reference.data(),
-                              (int)points.row.size()), "ms_loop_correct");
-    return table.refresh(ctx, poses, refreshArgs.rows, refreshArgs.observations, refreshArgs.firstOctave, settings, refreshArgs.pool);
+    ctx.check(ms_loop_correct(ctx.get(), poses.pose(), (int)poses.size(), points.mutablePosition(), (int)points.size(), t8, corrections.slot.data(),
+                              corrections.rigid.data(), corrections.lambda.data(), (int)corrections.slot.size(), moved.row.data(), moved.reference.data(),
+                              (int)moved.row.size()), "ms_loop_correct");
+    return points.refresh(ctx, poses, refreshArgs.rows, refreshArgs.observations, refreshArgs.firstOctave, settings, refreshArgs.pool);
 }
 
 // ---- the map-point triangulator (ms_triangulate) ------------------------------------------------------------------------------------
 // TriangulationMethod of mapper_helpers.hpp plus the first / last variant (triangulateMapPointFirstLastObs).
 enum class TriangulationMethod { TME = MS_TRI_TME, MIDPOINT = MS_TRI_MIDPOINT, FIRST_LAST = MS_TRI_FIRST_LAST };
-// Per keyframe slot of DeviceKeyframePoses: the pinhole stand-in of kf.shared->camera and its getFocalLength().
-struct KeyframeCameras {
-    std::vector<ms_pinhole> camera;
-    std::vector<std::int32_t> focalLength;
-};
+namespace detail {
+inline ms_tri_settings tri_settings(const StaticSettings &settings) {
+    const Parameters &p = settings.parameters;
+    return ms_tri_settings{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
+                           p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+}
+}  // namespace detail
 // The map points to triangulate and MapPoint::observations of each, flattened in the reference's iteration order (ascending KfId):
 // row r's observations are [obsStart[r], obsStart[r + 1]); obsKf = the keyframe's slot, obsX / obsY / obsOctave = kp.pt and kp.octave,
 // obsDepth = keyPointDepth (empty: no depth anywhere); wasTriangulated = status != NOT_TRIANGULATED on entry (mapper_helpers.cpp:607).
@@ -75,25 +77,24 @@ struct TriangulateResult {
 };
 
 // triangulateMapPoint / triangulateMapPointFirstLastObs (mapper_helpers.cpp:600-812) for args.rows, on the device: positions are written into
-// `table`, the status flags (DeviceMapPointFlags encoding) into `flags` when given.  The debug counters of loop_closer.cpp:516-521 follow from
-// the result and the entry state: `failed` = the entry status was TRIANGULATED and status != 2; `changed` (a comparison of position values in
-// the reference) = the position was written: status != 0, or the depth branch of :621 ran (not wasTriangulated, a positive depth, reason != 1).
-inline TriangulateResult triangulateMapPoints(Context &ctx, DeviceMapPoints &table, DeviceMapPointFlags *flags, const DeviceKeyframePoses &poses,
-                                              const KeyframeCameras &cams, const TriangulateArgs &args, const StaticSettings &settings, TriangulationMethod method) {
+// `points`, the status flags (DeviceMapPointFlags encoding) into `flags` when given; slots.camera / slots.focalLength per slot of `poses`.  The
+// debug counters of loop_closer.cpp:516-521 follow from the result and the entry state: `failed` = the entry status was TRIANGULATED and
+// status != 2; `changed` (a comparison of position values in the reference) = the position was written: status != 0, or the depth branch of
+// :621 ran (not wasTriangulated, a positive depth, reason != 1).
+inline TriangulateResult triangulateMapPoints(Context &ctx, DeviceMapPoints &points, DeviceMapPointFlags *flags, const DeviceKeyframePoses &poses,
+                                              const KeyframeSlots &slots, const TriangulateArgs &args, const StaticSettings &settings, TriangulationMethod method) {
     const std::size_t n = args.rows.size();
     if (args.wasTriangulated.size() != n || args.obsStart.size() != n + 1) throw std::invalid_argument("triangulateMapPoints: one flag and one list per row");
     const std::size_t nObs = (std::size_t)std::max<std::int32_t>(args.obsStart.back(), 0);
     if (args.obsKf.size() < nObs || args.obsOctave.size() < nObs || args.obsX.size() < nObs || args.obsY.size() < nObs || (!args.obsDepth.empty() && args.obsDepth.size() < nObs))
         throw std::invalid_argument("triangulateMapPoints: the observation arrays are shorter than obsStart says");
-    if (cams.camera.size() != poses.size() || cams.focalLength.size() != poses.size()) throw std::invalid_argument("triangulateMapPoints: one camera per keyframe slot");
-    if (flags && flags->size() < table.size()) throw std::invalid_argument("triangulateMapPoints: fewer flags than map points");
-    const Parameters &p = settings.parameters;
-    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
-                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    if (slots.camera.size() != poses.size() || slots.focalLength.size() != poses.size()) throw std::invalid_argument("triangulateMapPoints: one camera per keyframe slot");
+    if (flags && flags->size() < points.size()) throw std::invalid_argument("triangulateMapPoints: fewer flags than map points");
+    const ms_tri_settings s = detail::tri_settings(settings);
     TriangulateResult out;
     out.status.assign(n, 0); out.reason.assign(n, 0); out.passCount.assign(n, 0);
-    ctx.check(ms_triangulate(ctx.get(), table.mutablePosition(), flags ? flags->mutableFlags() : nullptr, (int)table.size(), poses.pose(), (int)poses.size(),
-                             cams.camera.data(), cams.focalLength.data(), args.rows.data(), args.wasTriangulated.data(), (int)n, args.obsStart.data(), args.obsKf.data(),
+    ctx.check(ms_triangulate(ctx.get(), points.mutablePosition(), flags ? flags->mutableFlags() : nullptr, (int)points.size(), poses.pose(), (int)poses.size(),
+                             slots.camera.data(), slots.focalLength.data(), args.rows.data(), args.wasTriangulated.data(), (int)n, args.obsStart.data(), args.obsKf.data(),
                              args.obsX.data(), args.obsY.data(), args.obsOctave.data(), args.obsDepth.empty() ? nullptr : args.obsDepth.data(), &s, (int)method,
                              out.status.data(), out.reason.data(), out.passCount.data()), "ms_triangulate");
     return out;
@@ -108,45 +109,36 @@ struct NeighborQuery {
 };
 
 // getNeighbors for every query in one device call: per query the neighbour slots, ascending (the order of the reference's std::map walk).
-inline std::vector<std::vector<std::int32_t>> getNeighbors(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags,
+inline std::vector<std::vector<std::int32_t>> getNeighbors(Context &ctx, const DeviceKeyframeMapPoints &keyframes, const DeviceMapPointFlags *flags,
                                                            const std::vector<NeighborQuery> &queries) {
     std::vector<std::vector<std::int32_t>> out(queries.size());
     if (queries.empty()) return out;
-    if (flags && flags->size() < table.mapPointCount()) throw std::invalid_argument("getNeighbors: fewer flags than map points");
+    if (flags && flags->size() < keyframes.mapPointCount()) throw std::invalid_argument("getNeighbors: fewer flags than map points");
     std::vector<ms_covis_query> q(queries.size());
     for (std::size_t i = 0; i < queries.size(); ++i)
         q[i] = ms_covis_query{queries[i].slot, queries[i].previous, queries[i].next, (std::int32_t)queries[i].minCovisibilities,
                               (std::uint8_t)(queries[i].triangulatedOnly ? DeviceMapPointFlags::TRIANGULATED : 0)};
-    const std::size_t nKf = table.size(), bytes = 4 * queries.size() * nKf;
+    const std::size_t nKf = keyframes.size(), bytes = 4 * queries.size() * nKf;
     std::int32_t *packed = reinterpret_cast<std::int32_t *>(ctx.workspace(bytes));
     std::vector<std::int32_t> n(queries.size(), 0);
-    ctx.check(ms_covisibility(ctx.get(), table.table(), (int)nKf, (int)table.stride(), flags ? flags->flags() : nullptr, (int)table.mapPointCount(), q.data(), (int)q.size(),
-                              nullptr, packed, n.data()), "ms_covisibility");
+    ctx.check(ms_covisibility(ctx.get(), keyframes.table(), (int)nKf, (int)keyframes.stride(), flags ? flags->flags() : nullptr, (int)keyframes.mapPointCount(), q.data(),
+                              (int)q.size(), nullptr, packed, n.data()), "ms_covisibility");
     std::vector<std::int32_t> host(queries.size() * nKf);
     ctx.check(ms_dev_download(ctx.get(), host.data(), packed, bytes), "ms_dev_download");
     for (std::size_t i = 0; i < queries.size(); ++i) out[i].assign(host.begin() + i * nKf, host.begin() + i * nKf + n[i]);
     return out;
 }
 
-// What computeAdjacentKeyframes reads of the map besides the covisibilities: per slot the previousKfId / nextKfId links (as slots, -1 for
-// none) and Keyframe::cameraCenter().
-struct KeyframeChain {
-    std::vector<std::int32_t> previous, next;
-    std::vector<std::array<double, 3>> cameraCenter;
-    // what observationCounts and cullMap read in addition: per slot the KfId (-1 for an empty slot) and Keyframe::t
-    std::vector<std::int32_t> id;
-    std::vector<double> t;
-};
-
 // computeAdjacentKeyframes (mapper_helpers.cpp:144-229): the getNeighbors calls of every second keyframe of the chain behind `current`
-// (:160-176) are ONE ms_covisibility call; the chain walks from the parents and the squared-distance sort (:178-216) stay on the host.
-inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, std::int32_t current,
-                                                          int minCovisibilities, int maxKeyframes, const KeyframeChain &chain) {
-    if (chain.previous.size() != table.size() || chain.next.size() != table.size() || chain.cameraCenter.size() != table.size())
-        throw std::invalid_argument("computeAdjacentKeyframes: one link pair and one camera centre per slot");
-    auto inTable = [&](std::int32_t s) { return s >= 0 && (std::size_t)s < table.size(); };
+// (:160-176) are ONE ms_covisibility call; the chain walks from the parents and the squared-distance sort (:178-216) stay on the host, on the
+// links and camera centres of M.slots.  Writes nothing.
+inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, MapTables M, std::int32_t current, int minCovisibilities, int maxKeyframes) {
+    M.require("computeAdjacentKeyframes", M.LINKS | M.CENTRES);
+    const KeyframeSlots &chain = M.slots;
+    const std::size_t nKf = M.keyframes.size();
+    auto inTable = [&](std::int32_t s) { return s >= 0 && (std::size_t)s < nKf; };
     if (!inTable(current)) throw std::invalid_argument("computeAdjacentKeyframes: current keyframe outside the table");
-    std::vector<char> adjacentSet(table.size(), 0);          // std::set<KfId> over slots: walked in ascending order below
+    std::vector<char> adjacentSet(nKf, 0);          // std::set<KfId> over slots: walked in ascending order below
     std::vector<NeighborQuery> queries;
     int i = 0;
     for (std::int32_t backwards = current; backwards != -1; backwards = chain.previous[backwards]) {
@@ -155,8 +147,8 @@ inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, const De
         if (i % 2 == 0) queries.push_back({backwards, chain.previous[backwards], chain.next[backwards], minCovisibilities, false});
         if (++i >= maxKeyframes) break;
     }
-    std::vector<char> parents(table.size(), 0);
-    for (const std::vector<std::int32_t> &nb : getNeighbors(ctx, table, flags, queries))
+    std::vector<char> parents(nKf, 0);
+    for (const std::vector<std::int32_t> &nb : getNeighbors(ctx, M.keyframes, M.flags, queries))
         for (std::int32_t k : nb) parents[k] = 1;
     for (std::size_t parent = 0; parent < parents.size(); ++parent) {
         if (!parents[parent]) continue;
@@ -185,21 +177,21 @@ inline std::vector<std::int32_t> computeAdjacentKeyframes(Context &ctx, const De
 
 // The ordered union of the map points of a list of keyframes: rows ascending (the std::set / std::map walk) and, for each, the first
 // position of the list whose keyframe lists it (localMapPoints.emplace of loop_closer.cpp:430-432) -- LoopPoints as it stands.
-//   matchLocalMapPoints (mapper_helpers.cpp:241-261)   localMapPoints(ctx, table, &flags, adjacentSlots, currentSlot, DeviceMapPointFlags::USABLE).row
+//   matchLocalMapPoints (mapper_helpers.cpp:241-261)   localMapPoints(ctx, keyframes, &flags, adjacentSlots, currentSlot, DeviceMapPointFlags::USABLE).row
 //                                                      is GateView::indices of the SEARCH view that matchLocalMapPoints (below) gates, scores
 //                                                      and binds on the device (searchByProjectionOnTables)
 //   deduplicateMapPoints (:337-345), searchAndDeduplicate (loop_closer.cpp:569-584)   exclude = -1, require = 0
-//   correctLoop (:418-433, :465-469)                   keyframes = LoopCorrections::slot; the result is its LoopPoints
-inline LoopPoints localMapPoints(Context &ctx, const DeviceKeyframeMapPoints &table, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &keyframes,
+//   correctLoop (:418-433, :465-469)                   slots = LoopCorrections::slot; the result is its LoopPoints
+inline LoopPoints localMapPoints(Context &ctx, const DeviceKeyframeMapPoints &keyframes, const DeviceMapPointFlags *flags, const std::vector<std::int32_t> &slots,
                                  std::int32_t excludeSlot = -1, std::uint8_t require = 0, bool withOwner = true) {
     LoopPoints out;
-    const std::size_t nMp = table.mapPointCount();
+    const std::size_t nMp = keyframes.mapPointCount();
     if (flags && flags->size() < nMp) throw std::invalid_argument("localMapPoints: fewer flags than map points");
-    const ms_union_problem problem{0, (std::int32_t)keyframes.size(), excludeSlot, require};
+    const ms_union_problem problem{0, (std::int32_t)slots.size(), excludeSlot, require};
     std::int32_t *rows = reinterpret_cast<std::int32_t *>(ctx.workspace(8 * nMp + 256)), *owner = rows + (nMp + 63) / 64 * 64;
     std::int32_t n = 0;
-    ctx.check(ms_map_point_union(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), flags ? flags->flags() : nullptr, (int)nMp, keyframes.data(),
-                                 (int)keyframes.size(), &problem, 1, rows, withOwner ? owner : nullptr, &n), "ms_map_point_union");
+    ctx.check(ms_map_point_union(ctx.get(), keyframes.table(), (int)keyframes.size(), (int)keyframes.stride(), flags ? flags->flags() : nullptr, (int)nMp, slots.data(),
+                                 (int)slots.size(), &problem, 1, rows, withOwner ? owner : nullptr, &n), "ms_map_point_union");
     out.row = ctx.download(rows, (std::size_t)n);
     if (withOwner) out.reference = ctx.download(owner, (std::size_t)n);
     return out;
@@ -213,11 +205,11 @@ struct ObservationCounts {
 
 // The transpose of the keyframe table, computed where it lies: what the status promotion of mapper_helpers.cpp:1072 and the row selection of
 // :1088 read, without a std::map of observations per point on the host.  kfIds: per slot the KfId, -1 for an empty slot.
-inline ObservationCounts observationCounts(Context &ctx, const DeviceKeyframeMapPoints &table, const std::vector<std::int32_t> &kfIds) {
-    if (kfIds.size() != table.size()) throw std::invalid_argument("observationCounts: one KfId per slot");
-    const std::size_t nMp = table.mapPointCount(), pitch = (nMp + 63) / 64 * 64;
+inline ObservationCounts observationCounts(Context &ctx, const DeviceKeyframeMapPoints &keyframes, const std::vector<std::int32_t> &kfIds) {
+    if (kfIds.size() != keyframes.size()) throw std::invalid_argument("observationCounts: one KfId per slot");
+    const std::size_t nMp = keyframes.mapPointCount(), pitch = (nMp + 63) / 64 * 64;
     std::int32_t *dev = reinterpret_cast<std::int32_t *>(ctx.workspace(12 * pitch + 256));
-    ctx.check(ms_observation_count(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), (int)nMp, kfIds.data(), dev, dev + pitch, dev + 2 * pitch),
+    ctx.check(ms_observation_count(ctx.get(), keyframes.table(), (int)keyframes.size(), (int)keyframes.stride(), (int)nMp, kfIds.data(), dev, dev + pitch, dev + 2 * pitch),
               "ms_observation_count");
     ObservationCounts out;
     out.count = ctx.download(dev, nMp); out.first = ctx.download(dev + pitch, nMp); out.last = ctx.download(dev + 2 * pitch, nMp);
@@ -244,16 +236,15 @@ struct CullResult {
     std::vector<std::int32_t> removedKeyframes, removedPrevious, removedNext;
 };
 
-// cullMapPoints + cullKeyframes (mapper_helpers.cpp:1095-1096) in ONE device call on the tables in place.  `current` and adjacentKfIds /
-// loopClosureKeyframes are slots; a candidate without a previous keyframe (:453) or named by a loop-closure edge (:455-464) is kept.  The
-// previous / next links of `chain` are relinked as removeKeyframe does (:414-420) and a removed slot's id becomes -1.
-inline CullResult cullMap(Context &ctx, DeviceKeyframeMapPoints &table, DeviceMapPointFlags *flags, DeviceMapPointLive &live, KeyframeChain &chain, std::int32_t current,
-                          const std::vector<std::int32_t> &adjacentKfIds, const std::vector<std::int32_t> &loopClosureKeyframes, const CullSettings &settings) {
-    const std::size_t nKf = table.size(), nMp = table.mapPointCount();
-    if (chain.previous.size() != nKf || chain.next.size() != nKf || chain.id.size() != nKf || chain.t.size() != nKf)
-        throw std::invalid_argument("cullMap: one link pair, one KfId and one time per slot");
-    if (live.size() < nMp || (flags && flags->size() < nMp)) throw std::invalid_argument("cullMap: fewer live bytes or flags than map points");
-    if (settings.cullPoints && !flags) throw std::invalid_argument("cullMap: cullMapPoints reads the flags");
+// cullMapPoints + cullKeyframes (mapper_helpers.cpp:1095-1096) in ONE device call on the tables in place: writes M.keyframes, M.flags and
+// M.live.  `current` and adjacentKfIds / loopClosureKeyframes are slots; a candidate without a previous keyframe (:453) or named by a
+// loop-closure edge (:455-464) is kept.  The previous / next links of M.slots are relinked as removeKeyframe does (:414-420) and a removed
+// slot's id becomes -1.
+inline CullResult cullMap(Context &ctx, MapTables M, std::int32_t current, const std::vector<std::int32_t> &adjacentKfIds, const std::vector<std::int32_t> &loopClosureKeyframes,
+                          const CullSettings &settings) {
+    M.require("cullMap", M.LIVE | M.LINKS | M.IDS | M.TIMES | (settings.cullPoints ? M.FLAGS : 0u));
+    KeyframeSlots &chain = M.slots;
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount();
     std::vector<std::uint8_t> keep(adjacentKfIds.size(), 0), removed(adjacentKfIds.size(), 0);
     for (std::size_t i = 0; i < adjacentKfIds.size(); ++i) {
         const std::int32_t k = adjacentKfIds[i];
@@ -266,8 +257,8 @@ inline CullResult cullMap(Context &ctx, DeviceKeyframeMapPoints &table, DeviceMa
     std::int32_t *rows = reinterpret_cast<std::int32_t *>(ctx.workspace(5 * pitch + 256));
     std::uint8_t *why = reinterpret_cast<std::uint8_t *>(rows + pitch);
     std::int32_t nRows = 0, nKfs = 0;
-    ctx.check(ms_map_cull(ctx.get(), table.mutableTable(), (int)nKf, (int)table.stride(), flags ? flags->mutableFlags() : nullptr, live.mutableLive(), (int)nMp, chain.id.data(),
-                          chain.t.data(), adjacentKfIds.data(), keep.data(), (int)adjacentKfIds.size(), &s, nullptr, rows, why, removed.data(), &nRows, &nKfs), "ms_map_cull");
+    ctx.check(ms_map_cull(ctx.get(), M.keyframes.mutableTable(), (int)nKf, (int)M.keyframes.stride(), M.flags ? M.flags->mutableFlags() : nullptr, M.live->mutableLive(), (int)nMp,
+                          chain.id.data(), chain.t.data(), adjacentKfIds.data(), keep.data(), (int)adjacentKfIds.size(), &s, nullptr, rows, why, removed.data(), &nRows, &nKfs), "ms_map_cull");
     CullResult out;
     out.removedRows = ctx.download(rows, (std::size_t)nRows); out.removedWhy = ctx.download(why, (std::size_t)nRows);
     for (std::size_t i = 0; i < adjacentKfIds.size(); ++i) if (removed[i]) out.removedKeyframes.push_back(adjacentKfIds[i]);
@@ -286,45 +277,38 @@ inline CullResult cullMap(Context &ctx, DeviceKeyframeMapPoints &table, DeviceMa
 // ---- the passes over device observation lists (DeviceObservationLists, ms_map_refresh_lists, ms_triangulate_lists) -------------------
 // The map-point update of a new keyframe, mapper_helpers.cpp:1062-1077, without a per-point host structure: the observation lists of the
 // current keyframe's usable map points (status neither NOT_TRIANGULATED nor BAD, :1066) are built on the device, then updateDescriptor +
-// updateDistanceAndNorm (:1069-1070) and the status promotion of :1072-1076 run on them where they lie.  `pool` may be null (descriptors stay).
-// Returns the number of refreshed map points; `lists` holds them afterwards.
-inline std::size_t updateMapPoints(Context &ctx, DeviceObservationLists &lists, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags, const DeviceKeyframeMapPoints &table,
-                                   const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses, const std::vector<std::int32_t> &kfIds,
-                                   const std::vector<std::int32_t> &descBase, const DeviceDescriptorPool *pool, std::int32_t currentSlot, int minObservationsForBA,
-                                   const StaticSettings &settings) {
+// updateDistanceAndNorm (:1069-1070) and the status promotion of :1072-1076 run on them where they lie: writes M.points and M.flags->  M.pool
+// may be null (descriptors stay).  Returns the number of refreshed map points; M.lists holds them afterwards.
+inline std::size_t updateMapPoints(Context &ctx, MapTables M, std::int32_t currentSlot, int minObservationsForBA, const StaticSettings &settings) {
+    M.require("updateMapPoints", M.POINTS | M.FLAGS | M.LISTS | M.KEYPOINTS | M.POSES | M.IDS);
     ObservationSelection sel;
     sel.slot = currentSlot; sel.filter = MS_OBS_REFRESH; sel.dropEmpty = true;
     const int levels = (int)settings.scaleFactors.size();
-    lists.build(table, keypoints, &flags, kfIds, pool ? descBase : std::vector<std::int32_t>(), sel, levels);
-    const ms_obs_lists l = lists.lists();
-    ctx.check(ms_map_refresh_lists(ctx.get(), mapPoints.position(), mapPoints.mutableNorm(), mapPoints.mutableMinDistance(), mapPoints.mutableMaxDistance(),
-                                   mapPoints.mutableDescriptor(), (int)mapPoints.size(), poses.pose(),
-                                   (int)poses.size(), pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, &l, (int)lists.rowCount(), (int)lists.observationCount(),
-                                   settings.scaleFactors.data(), levels, std::max(minObservationsForBA, 1), flags.mutableFlags(), nullptr), "ms_map_refresh_lists");
-    return lists.rowCount();
+    M.lists->build(M, M.pool != nullptr, sel, levels);
+    const ms_obs_lists l = M.lists->lists();
+    ctx.check(ms_map_refresh_lists(ctx.get(), M.points->position(), M.points->mutableNorm(), M.points->mutableMinDistance(), M.points->mutableMaxDistance(),
+                                   M.points->mutableDescriptor(), (int)M.points->size(), M.poses->pose(), (int)M.poses->size(), M.poolDescriptor(), M.poolSize(), &l,
+                                   (int)M.lists->rowCount(), (int)M.lists->observationCount(), settings.scaleFactors.data(), levels, std::max(minObservationsForBA, 1),
+                                   M.flags->mutableFlags(), nullptr), "ms_map_refresh_lists");
+    return M.lists->rowCount();
 }
 
 // The re-triangulation after local BA, mapper_helpers.cpp:1085-1092: the current keyframe's map points that are not TRIANGULATED or have at
-// least two observations (:1088), triangulated from device lists.  The per-point results come back as from triangulateMapPoints, in the
-// order of the keyframe's keypoints.
-inline TriangulateResult retriangulateCurrent(Context &ctx, DeviceObservationLists &lists, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags,
-                                              const DeviceKeyframeMapPoints &table, const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses,
-                                              const KeyframeCameras &cams, const std::vector<std::int32_t> &kfIds, std::int32_t currentSlot, const StaticSettings &settings,
-                                              TriangulationMethod method) {
-    if (cams.camera.size() != poses.size() || cams.focalLength.size() != poses.size()) throw std::invalid_argument("retriangulateCurrent: one camera per keyframe slot");
+// least two observations (:1088), triangulated from device lists: writes M.points and M.flags->  The per-point results come back as from
+// triangulateMapPoints, in the order of the keyframe's keypoints.
+inline TriangulateResult retriangulateCurrent(Context &ctx, MapTables M, std::int32_t currentSlot, const StaticSettings &settings, TriangulationMethod method) {
+    M.require("retriangulateCurrent", M.POINTS | M.FLAGS | M.LISTS | M.KEYPOINTS | M.POSES | M.IDS | M.CAMERAS | M.FOCALS);
     ObservationSelection sel;
     sel.slot = currentSlot; sel.filter = MS_OBS_RETRIANGULATE;
-    lists.build(table, keypoints, &flags, kfIds, {}, sel, (int)settings.levelSigmaSq.size());
-    const Parameters &p = settings.parameters;
-    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)settings.levelSigmaSq.size(), p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
-                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
-    const std::size_t n = lists.rowCount();
+    M.lists->build(M, false, sel, (int)settings.levelSigmaSq.size());
+    const ms_tri_settings s = detail::tri_settings(settings);
+    const std::size_t n = M.lists->rowCount();
     TriangulateResult out;
     out.status.assign(n, 0); out.reason.assign(n, 0); out.passCount.assign(n, 0);
-    const ms_obs_lists l = lists.lists();
-    ctx.check(ms_triangulate_lists(ctx.get(), mapPoints.mutablePosition(), flags.mutableFlags(), (int)mapPoints.size(), poses.pose(), (int)poses.size(), cams.camera.data(),
-                                   cams.focalLength.data(), &l, (int)n, (int)lists.observationCount(), &s, (int)method, out.status.data(), out.reason.data(),
-                                   out.passCount.data()), "ms_triangulate_lists");
+    const ms_obs_lists l = M.lists->lists();
+    ctx.check(ms_triangulate_lists(ctx.get(), M.points->mutablePosition(), M.flags->mutableFlags(), (int)M.points->size(), M.poses->pose(), (int)M.poses->size(),
+                                   M.slots.camera.data(), M.slots.focalLength.data(), &l, (int)n, (int)M.lists->observationCount(), &s, (int)method, out.status.data(),
+                                   out.reason.data(), out.passCount.data()), "ms_triangulate_lists");
     return out;
 }
 
@@ -352,78 +336,68 @@ struct MatchTrackedResult {
 //   -> ms_match_tracked_finish (the descriptor of the points that are now UNSURE, :811; the rows of :121) -> the refresh of :121-124: one pass
 //   when the frame has descriptors, otherwise the just-tracked TRIANGULATED rows with the descriptor half and the checked rows without it.
 // freeRows: table rows the caller offers to new map points, at least as many as the frame can create (the k-th created point takes the
-// k-th); `pool` must hold the frame's descriptors at descBase[slot] when that is >= 0.  `lists` is scratch and holds the last refresh's rows.
-inline MatchTrackedResult matchTrackedFeatures(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &table, DeviceMapPoints &mapPoints, DeviceMapPointFlags &flags,
-                                               DeviceMapPointLive &live, DeviceTrackTable &tracks, const DeviceKeypointTable &keypoints, const DeviceKeyframePoses &poses,
-                                               const KeyframeCameras &cams, const std::vector<std::int32_t> &kfIds, const std::vector<std::int32_t> &descBase,
-                                               const DeviceDescriptorPool *pool, const TrackedFrame &frame, const std::vector<std::int32_t> &freeRows,
-                                               const StaticSettings &settings, float viewAngleLimitCos = 0.5f) {
-    const std::size_t nKf = table.size(), nMp = table.mapPointCount(), nKp = frame.keyPointToTrackId.size(), nNew = freeRows.size();
+// k-th); M.pool must hold the frame's descriptors at descBase[slot] when that is >= 0.  Writes M.keyframes, M.points, M.flags, M.live and
+// M.tracks; M.lists is scratch and holds the last refresh's rows.
+inline MatchTrackedResult matchTrackedFeatures(Context &ctx, MapTables M, const TrackedFrame &frame, const std::vector<std::int32_t> &freeRows, const StaticSettings &settings,
+                                               float viewAngleLimitCos = 0.5f) {
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount(), nKp = frame.keyPointToTrackId.size(), nNew = freeRows.size();
     if (frame.slot < 0 || (std::size_t)frame.slot >= nKf) throw std::invalid_argument("matchTrackedFeatures: slot outside the table");
-    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || kfIds.size() != nKf || descBase.size() != nKf || poses.size() != nKf)
-        throw std::invalid_argument("matchTrackedFeatures: one camera, focal length, KfId, descriptor base and pose per slot");
-    if (mapPoints.size() != nMp || flags.size() < nMp || live.size() < nMp || tracks.mapPointCount() != nMp) throw std::invalid_argument("matchTrackedFeatures: the map-point tables differ in size");
-    if (keypoints.size() != nKf || keypoints.stride() != table.stride()) throw std::invalid_argument("matchTrackedFeatures: the keypoint table does not match the keyframe table");
-    const bool hasDescriptors = descBase[frame.slot] >= 0;
-    if (hasDescriptors && !pool) throw std::invalid_argument("matchTrackedFeatures: the frame has descriptors and there is no pool");
-    for (std::int32_t t : frame.keyPointToTrackId) if (t >= 0) tracks.ensureTrack(t);
+    M.require("matchTrackedFeatures", M.POINTS | M.FLAGS | M.LISTS | M.LIVE | M.TRACKS | M.KEYPOINTS | M.POSES | M.CAMERAS | M.FOCALS | M.IDS | M.DESC_BASES);
+    DeviceObservationLists &lists = *M.lists;
+    DeviceMapPoints &points = *M.points;
+    const bool hasDescriptors = M.slots.descBase[frame.slot] >= 0;
+    if (hasDescriptors && !M.pool) throw std::invalid_argument("matchTrackedFeatures: the frame has descriptors and there is no pool");
+    for (std::int32_t t : frame.keyPointToTrackId) if (t >= 0) M.tracks->ensureTrack(t);
     const int levels = (int)settings.levelSigmaSq.size();
-    const Parameters &p = settings.parameters;
     ms_tracked_frame f{};
     f.slot = frame.slot;
     std::copy(frame.poseCW.begin(), frame.poseCW.end(), f.pose);
-    f.cam = cams.camera[frame.slot]; f.focal = cams.focalLength[frame.slot];
-    f.desc_base = descBase[frame.slot]; f.track_base = tracks.trackBase();
+    f.cam = M.slots.camera[frame.slot]; f.focal = M.slots.focalLength[frame.slot];
+    f.desc_base = M.slots.descBase[frame.slot]; f.track_base = M.tracks->trackBase();
     f.level_sigma_sq = settings.levelSigmaSq.data(); f.n_levels = levels;
-    f.rel_reprojection_threshold = p.relativeReprojectionErrorThreshold; f.view_cos_limit = viewAngleLimitCos;
+    f.rel_reprojection_threshold = settings.parameters.relativeReprojectionErrorThreshold; f.view_cos_limit = viewAngleLimitCos;
     // device scratch: created rows | created keypoints | just-tracked rows | checked rows | refresh rows | outcomes
-    const std::size_t pitchKp = (nKp + 63) / 64 * 64 + 64, pitchNew = (nNew + 63) / 64 * 64 + 64;
+    const std::size_t pitchKp = detail::padded(nKp), pitchNew = detail::padded(nNew);
     std::int32_t *createdRows = reinterpret_cast<std::int32_t *>(ctx.workspace(4 * (2 * pitchNew + 4 * pitchKp) + pitchKp + 256));
     std::int32_t *createdKp = createdRows + pitchNew, *trackedRows = createdKp + pitchNew, *checkedRows = trackedRows + pitchKp, *refreshRows = checkedRows + pitchKp;
     std::uint8_t *outcome = reinterpret_cast<std::uint8_t *>(refreshRows + 2 * pitchKp);
     std::int32_t counts[5] = {0, 0, 0, 0, 0};
-    ctx.check(ms_match_tracked(ctx.get(), table.mutableTable(), (int)nKf, (int)table.stride(), flags.mutableFlags(), live.mutableLive(), mapPoints.position(), mapPoints.norm(),
-                               mapPoints.minDistance(), mapPoints.maxDistance(), mapPoints.mutableDescriptor(), tracks.mpTrack(), (int)nMp, keypoints.x(), keypoints.y(),
-                               keypoints.octave(), pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, tracks.trackRow(), (int)tracks.window(), &f,
-                               frame.keyPointToTrackId.data(), (int)nKp, freeRows.data(), (int)nNew, outcome, createdRows, createdKp, trackedRows, checkedRows, counts),
-              "ms_match_tracked");
+    ctx.check(ms_match_tracked(ctx.get(), M.keyframes.mutableTable(), (int)nKf, (int)M.keyframes.stride(), M.flags->mutableFlags(), M.live->mutableLive(), points.position(),
+                               points.norm(), points.minDistance(), points.maxDistance(), points.mutableDescriptor(), M.tracks->mpTrack(), (int)nMp, M.keypoints->x(), M.keypoints->y(),
+                               M.keypoints->octave(), M.poolDescriptor(), M.poolSize(), M.tracks->trackRow(), (int)M.tracks->window(), &f, frame.keyPointToTrackId.data(), (int)nKp,
+                               freeRows.data(), (int)nNew, outcome, createdRows, createdKp, trackedRows, checkedRows, counts), "ms_match_tracked");
     MatchTrackedResult out;
     out.newPoints = (std::size_t)counts[0]; out.justTriangulated = (std::size_t)counts[1]; out.checked = (std::size_t)counts[2];
     out.frustumFail = (std::size_t)counts[3]; out.reproFail = (std::size_t)counts[4];
     out.outcome = ctx.download(outcome, nKp);
     out.createdRows = ctx.download(createdRows, out.newPoints); out.createdKeyPoints = ctx.download(createdKp, out.newPoints);
-    const std::vector<std::int32_t> noBase;
     auto listsOf = [&](const std::int32_t *rows, std::size_t n, bool dropEmpty) {
         ObservationSelection sel;
         sel.deviceRows = rows; sel.rowCount = n; sel.dropEmpty = dropEmpty;
-        lists.build(table, keypoints, &flags, kfIds, pool ? descBase : noBase, sel, levels);
+        lists.build(M, M.pool != nullptr, sel, levels);
     };
     std::size_t nTracked = 0;
     if (out.justTriangulated) {                              // :90
         listsOf(trackedRows, out.justTriangulated, false);
         nTracked = lists.rowCount();
-        const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)levels, p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
-                                p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+        const ms_tri_settings s = detail::tri_settings(settings);
         out.firstLast.status.assign(nTracked, 0); out.firstLast.reason.assign(nTracked, 0); out.firstLast.passCount.assign(nTracked, 0);
         const ms_obs_lists l = lists.lists();
-        ctx.check(ms_triangulate_lists(ctx.get(), mapPoints.mutablePosition(), flags.mutableFlags(), (int)nMp, poses.pose(), (int)nKf, cams.camera.data(), cams.focalLength.data(), &l,
-                                       (int)nTracked, (int)lists.observationCount(), &s, MS_TRI_FIRST_LAST, out.firstLast.status.data(), out.firstLast.reason.data(),
-                                       out.firstLast.passCount.data()), "ms_triangulate_lists");
+        ctx.check(ms_triangulate_lists(ctx.get(), points.mutablePosition(), M.flags->mutableFlags(), (int)nMp, M.poses->pose(), (int)nKf, M.slots.camera.data(),
+                                       M.slots.focalLength.data(), &l, (int)nTracked, (int)lists.observationCount(), &s, MS_TRI_FIRST_LAST, out.firstLast.status.data(),
+                                       out.firstLast.reason.data(), out.firstLast.passCount.data()), "ms_triangulate_lists");
     }
-    ms_obs_lists l = lists.lists();
-    if (!pool) l.obs_desc = nullptr;
+    const ms_obs_lists l = lists.lists(M.pool != nullptr);
     std::int32_t nRefresh = 0;
-    ctx.check(ms_match_tracked_finish(ctx.get(), &l, (int)nTracked, flags.flags(), pool ? pool->descriptor() : nullptr, mapPoints.mutableDescriptor(), (int)nMp, checkedRows,
-                                      (int)out.checked, hasDescriptors ? 1 : 0, refreshRows, (int)(2 * pitchKp), &nRefresh), "ms_match_tracked_finish");
+    ctx.check(ms_match_tracked_finish(ctx.get(), &l, (int)nTracked, M.flags->flags(), M.poolDescriptor(), points.mutableDescriptor(), (int)nMp, checkedRows, (int)out.checked,
+                                      hasDescriptors ? 1 : 0, refreshRows, (int)(2 * pitchKp), &nRefresh), "ms_match_tracked_finish");
     auto refresh = [&](const std::int32_t *rows, std::size_t n, bool descriptors) {                      // :121-124
         if (n == 0) return;
         listsOf(rows, n, true);
         const ms_obs_lists r = lists.lists();
-        const bool withPool = descriptors && pool;
-        ctx.check(ms_map_refresh_lists(ctx.get(), mapPoints.position(), mapPoints.mutableNorm(), mapPoints.mutableMinDistance(), mapPoints.mutableMaxDistance(),
-                                       mapPoints.mutableDescriptor(), (int)nMp, poses.pose(), (int)nKf, withPool ? pool->descriptor() : nullptr, withPool ? (int)pool->size() : 0, &r,
-                                       (int)lists.rowCount(), (int)lists.observationCount(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(), 0, nullptr, nullptr),
-                  "ms_map_refresh_lists");
+        ctx.check(ms_map_refresh_lists(ctx.get(), points.position(), points.mutableNorm(), points.mutableMinDistance(), points.mutableMaxDistance(), points.mutableDescriptor(),
+                                       (int)nMp, M.poses->pose(), (int)nKf, descriptors ? M.poolDescriptor() : nullptr, descriptors ? M.poolSize() : 0, &r, (int)lists.rowCount(),
+                                       (int)lists.observationCount(), settings.scaleFactors.data(), (int)settings.scaleFactors.size(), 0, nullptr, nullptr), "ms_map_refresh_lists");
     };
     refresh(refreshRows, (std::size_t)nRefresh, true);
     if (!hasDescriptors) refresh(checkedRows, out.checked, false);
@@ -433,8 +407,9 @@ inline MatchTrackedResult matchTrackedFeatures(Context &ctx, DeviceObservationLi
 
 // ---- createNewMapPoints on the device tables (ms_create_points_lists, ms_create_points_bind, ms_unbound_mask) --------------------------
 // The `usable` masks of the triangulation matcher ("the keypoint has no map point", keyframe_matcher.cpp:205-221) of the listed slots, written
-// from the keyframe table in one launch.  frames[slot] = the DeviceKeyframe of that slot.
-inline void unboundMasks(Context &ctx, const DeviceKeyframeMapPoints &kfTable, const std::vector<std::int32_t> &slots, const std::vector<DeviceKeyframe *> &frames) {
+// from the keyframe table in one launch into M.slots.frames[slot], the DeviceKeyframe of that slot.
+inline void unboundMasks(Context &ctx, MapTables M, const std::vector<std::int32_t> &slots) {
+    const std::vector<DeviceKeyframe *> &frames = M.slots.frames;
     std::vector<std::int32_t> counts;
     std::vector<std::uint8_t *> masks;
     for (std::int32_t s : slots) {
@@ -442,8 +417,8 @@ inline void unboundMasks(Context &ctx, const DeviceKeyframeMapPoints &kfTable, c
         counts.push_back((std::int32_t)frames[s]->keyPointCount());
         masks.push_back(frames[s]->mutableUsable());
     }
-    ctx.check(ms_unbound_mask(ctx.get(), kfTable.table(), (int)kfTable.size(), (int)kfTable.stride(), (int)kfTable.mapPointCount(), slots.data(), counts.data(), masks.data(),
-                              (int)slots.size()), "ms_unbound_mask");
+    ctx.check(ms_unbound_mask(ctx.get(), M.keyframes.table(), (int)M.keyframes.size(), (int)M.keyframes.stride(), (int)M.keyframes.mapPointCount(), slots.data(), counts.data(),
+                              masks.data(), (int)slots.size()), "ms_unbound_mask");
 }
 
 // What one adjacent keyframe gave: per match (ascending keypoint of the current keyframe) the provisional row, the two keypoints and the
@@ -459,27 +434,23 @@ struct CreatedPoints {
 
 // createNewMapPoints (mapper_helpers.cpp:271-318) for the keyframe in currentSlot, nothing per match on the host.  Per adjacent slot, in the
 // given order:  create_E_21 -> ms_match_triangulation -> ms_create_points_lists -> ms_triangulate_lists (TME or MIDPOINT, :308) ->
-// ms_create_points_bind.  frames[slot] = the slot's DeviceKeyframe, whose `usable` mask says "no map point" (unboundMasks) and is kept
+// ms_create_points_bind.  M.slots.frames[slot] = the slot's DeviceKeyframe, whose `usable` mask says "no map point" (unboundMasks) and is kept
 // current by the bind step, so the next adjacent's matcher sees this adjacent's binds.  freeRows: free table rows, at least as many as one
-// adjacent can match; an adjacent takes the first ones and hands back those whose triangulation failed.  `lists` is scratch.
-// observationCount / mpTrack: DEVICE [mapPointCount] arrays of the cull / fuse / track steps to keep current (2 and -1 for a created row), or null.
+// adjacent can match; an adjacent takes the first ones and hands back those whose triangulation failed.  Writes M.keyframes, M.points, M.flags,
+// M.live and, where given, M.observationCount and M.tracks' mp_track (2 and -1 for a created row); M.lists is scratch.
 // hostPoses: the poses DeviceKeyframePoses holds (downloaded when null).
-inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &kfTable, DeviceMapPoints &table, DeviceMapPointFlags &flags,
-                                                     DeviceMapPointLive &live, const DeviceKeypointTable &kpTable, const DeviceKeyframePoses &poses, const KeyframeCameras &cams,
-                                                     const std::vector<std::int32_t> &kfIds, const std::vector<std::int32_t> &descBase, const DeviceDescriptorPool *pool,
-                                                     std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots, const std::vector<DeviceKeyframe *> &frames,
+inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, MapTables M, std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots,
                                                      const std::vector<std::int32_t> &freeRows, const StaticSettings &settings, TriangulationMethod method,
-                                                     std::int32_t *observationCount = nullptr, std::int32_t *mpTrack = nullptr,
                                                      const std::vector<DeviceKeyframePoses::Pose> *hostPoses = nullptr) {
-    const std::size_t nKf = kfTable.size(), nMp = kfTable.mapPointCount();
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount();
     if (currentSlot < 0 || (std::size_t)currentSlot >= nKf) throw std::invalid_argument("createNewMapPoints: slot outside the table");
-    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || kfIds.size() != nKf || descBase.size() != nKf || poses.size() != nKf || frames.size() != nKf)
-        throw std::invalid_argument("createNewMapPoints: one camera, focal length, KfId, descriptor base, pose and frame per slot");
-    if (table.size() != nMp || flags.size() < nMp || live.size() < nMp) throw std::invalid_argument("createNewMapPoints: the map-point tables differ in size");
-    if (kpTable.size() != nKf || kpTable.stride() != kfTable.stride()) throw std::invalid_argument("createNewMapPoints: the keypoint table does not match the keyframe table");
+    M.require("createNewMapPoints", M.POINTS | M.FLAGS | M.LISTS | M.LIVE | M.KEYPOINTS | M.POSES | M.CAMERAS | M.FOCALS | M.IDS | M.DESC_BASES | M.FRAMES);
+    DeviceObservationLists &lists = *M.lists;
+    const std::vector<DeviceKeyframe *> &frames = M.slots.frames;
+    const bool pool = M.pool != nullptr;
     if (method == TriangulationMethod::FIRST_LAST) throw std::invalid_argument("createNewMapPoints: TME or MIDPOINT");
     if (!frames[currentSlot]) throw std::invalid_argument("createNewMapPoints: no frame for the current slot");
-    const std::vector<DeviceKeyframePoses::Pose> downloaded = hostPoses ? std::vector<DeviceKeyframePoses::Pose>() : poses.download();
+    const std::vector<DeviceKeyframePoses::Pose> downloaded = hostPoses ? std::vector<DeviceKeyframePoses::Pose>() : M.poses->download();
     const std::vector<DeviceKeyframePoses::Pose> &P = hostPoses ? *hostPoses : downloaded;
     if (P.size() != nKf) throw std::invalid_argument("createNewMapPoints: one host pose per slot");
     auto rotation = [](const DeviceKeyframePoses::Pose &p, double R[9], double t[3]) {
@@ -488,11 +459,9 @@ inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, DeviceObserva
     DeviceKeyframe &kf1 = *frames[currentSlot];
     const std::size_t n1 = kf1.keyPointCount();
     const int levels = (int)settings.levelSigmaSq.size();
-    const Parameters &p = settings.parameters;
-    const ms_tri_settings s{settings.levelSigmaSq.data(), (std::int32_t)levels, p.minTriangulationAngleTwoObs, p.minTriangulationAngleMultipleObs,
-                            p.relativeReprojectionErrorThreshold, p.computeDenseStereoDepth ? 1 : 0};
+    const ms_tri_settings s = detail::tri_settings(settings);
     // device scratch: E and the scale factors | match count | matched | the matches' keypoints | the created points
-    const std::size_t pitch = (n1 + 63) / 64 * 64 + 64, oS = 128, oCount = oS + detail::pad16(4 * settings.scaleFactors.size()) + 64, oInts = oCount + 64;
+    const std::size_t pitch = detail::padded(n1), oS = 128, oCount = oS + detail::pad16(4 * settings.scaleFactors.size()) + 64, oInts = oCount + 64;
     unsigned char *ws = ctx.workspace(oInts + 4 * 6 * pitch);
     std::int32_t *matched = reinterpret_cast<std::int32_t *>(ws + oInts), *kp1 = matched + pitch, *kp2 = kp1 + pitch, *createdRows = kp2 + pitch,
                  *createdKp1 = createdRows + pitch, *createdKp2 = createdKp1 + pitch;
@@ -517,15 +486,15 @@ inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, DeviceObserva
         std::memcpy(st.data() + oS, settings.scaleFactors.data(), 4 * settings.scaleFactors.size());
         ctx.check(ms_dev_upload(ctx.get(), ws, st.data(), st.size()), "ms_dev_upload");
         const ms_match_frame f1 = kf1.frame(), f2 = kf2.frame();
-        ctx.check(ms_match_triangulation(ctx.get(), &f1, &f2, 1, reinterpret_cast<const double *>(ws), reinterpret_cast<const float *>(ws + oS), p.epipolarCheckThresholdDegrees, 1,
-                                         &matched, reinterpret_cast<std::int32_t *>(ws + oCount)), "ms_match_triangulation");
+        ctx.check(ms_match_triangulation(ctx.get(), &f1, &f2, 1, reinterpret_cast<const double *>(ws), reinterpret_cast<const float *>(ws + oS),
+                                         settings.parameters.epipolarCheckThresholdDegrees, 1, &matched, reinterpret_cast<std::int32_t *>(ws + oCount)), "ms_match_triangulation");
         std::int32_t nMatches = 0;
         for (int attempt = 0;; ++attempt) {
-            ms_obs_lists l = lists.lists();
-            if (!pool) l.obs_desc = nullptr;
-            const int rc = ms_create_points_lists(ctx.get(), kfTable.table(), (int)nKf, (int)kfTable.stride(), live.live(), (int)nMp, kfIds.data(), kpTable.x(), kpTable.y(),
-                                                  kpTable.octave(), kpTable.depth(), pool ? descBase.data() : nullptr, currentSlot, adj, matched, (int)n1, (int)kf2.keyPointCount(),
-                                                  free.data(), (int)free.size(), levels, &l, (int)lists.rowCapacity(), (int)lists.observationCapacity(), kp1, kp2, &nMatches);
+            const ms_obs_lists l = lists.lists(pool);
+            const int rc = ms_create_points_lists(ctx.get(), M.keyframes.table(), (int)nKf, (int)M.keyframes.stride(), M.live->live(), (int)nMp, M.slots.id.data(), M.keypoints->x(),
+                                                  M.keypoints->y(), M.keypoints->octave(), M.keypoints->depth(), pool ? M.slots.descBase.data() : nullptr, currentSlot, adj, matched,
+                                                  (int)n1, (int)kf2.keyPointCount(), free.data(), (int)free.size(), levels, &l, (int)lists.rowCapacity(), (int)lists.observationCapacity(),
+                                                  kp1, kp2, &nMatches);
             if (rc == MS_ERR_CAPACITY && attempt == 0 && (std::size_t)nMatches <= free.size() &&
                 ((std::size_t)nMatches > lists.rowCapacity() || 2 * (std::size_t)nMatches > lists.observationCapacity())) {
                 lists.ensure((std::size_t)nMatches, 2 * (std::size_t)nMatches);      // the needed count came back: once is enough
@@ -535,18 +504,18 @@ inline std::vector<CreatedPoints> createNewMapPoints(Context &ctx, DeviceObserva
             break;
         }
         const std::size_t n = (std::size_t)nMatches;
-        lists.setCounts(n, 2 * n, pool != nullptr);
+        lists.setCounts(n, 2 * n, pool);
         r.rows.assign(free.begin(), free.begin() + (std::ptrdiff_t)n);
         r.keyPoints1 = ctx.download(kp1, n); r.keyPoints2 = ctx.download(kp2, n);
         r.status.assign(n, 0); r.reason.assign(n, 0);
-        ms_obs_lists l = lists.lists();
-        if (!pool) l.obs_desc = nullptr;
-        ctx.check(ms_triangulate_lists(ctx.get(), table.mutablePosition(), flags.mutableFlags(), (int)nMp, poses.pose(), (int)nKf, cams.camera.data(), cams.focalLength.data(), &l,
-                                       (int)n, (int)(2 * n), &s, (int)method, r.status.data(), r.reason.data(), nullptr), "ms_triangulate_lists");      // :308
+        const ms_obs_lists l = lists.lists(pool);
+        ctx.check(ms_triangulate_lists(ctx.get(), M.points->mutablePosition(), M.flags->mutableFlags(), (int)nMp, M.poses->pose(), (int)nKf, M.slots.camera.data(),
+                                       M.slots.focalLength.data(), &l, (int)n, (int)(2 * n), &s, (int)method, r.status.data(), r.reason.data(), nullptr), "ms_triangulate_lists");      // :308
         std::int32_t nCreated = 0;
-        ctx.check(ms_create_points_bind(ctx.get(), kfTable.mutableTable(), (int)nKf, (int)kfTable.stride(), flags.flags(), live.mutableLive(), table.mutableDescriptor(),
-                                        observationCount, mpTrack, (int)nMp, pool ? pool->descriptor() : nullptr, pool ? (int)pool->size() : 0, currentSlot, adj, &l, kp1, kp2,
-                                        (int)n, (int)n1, (int)kf2.keyPointCount(), kf1.mutableUsable(), kf2.mutableUsable(), createdRows, createdKp1, createdKp2, &nCreated), "ms_create_points_bind");      // :309-316
+        ctx.check(ms_create_points_bind(ctx.get(), M.keyframes.mutableTable(), (int)nKf, (int)M.keyframes.stride(), M.flags->flags(), M.live->mutableLive(),
+                                        M.points->mutableDescriptor(), M.observationCount, M.trackWindow().mpTrack, (int)nMp, M.poolDescriptor(), M.poolSize(), currentSlot, adj, &l, kp1,
+                                        kp2, (int)n, (int)n1, (int)kf2.keyPointCount(), kf1.mutableUsable(), kf2.mutableUsable(), createdRows, createdKp1, createdKp2, &nCreated),
+                  "ms_create_points_bind");      // :309-316
         r.createdRows = ctx.download(createdRows, (std::size_t)nCreated);
         r.createdKeyPoints1 = ctx.download(createdKp1, (std::size_t)nCreated); r.createdKeyPoints2 = ctx.download(createdKp2, (std::size_t)nCreated);
         std::vector<std::int32_t> left;                      // the rows of the failed matches go back to the front, in order
@@ -605,46 +574,42 @@ inline std::vector<std::int32_t> local_keyframes(const std::vector<std::int32_t>
 // localBundleAdjust (bundle_adjuster.cpp:141-394) for the keyframe in currentSlot with nothing walked on the host: the local keyframes
 // (:177-193), ms_map_point_union -> ms_observation_lists -> ms_ba_window_lists for the window (:214-290), the early-outs of :235-240, the
 // existing two-stage localBundleAdjust on the gathered window, then ms_ba_window_apply in the mode the stage dictates (:326-331 or :376-390).
-// adjacentSlots = computeAdjacentKeyframes(minCovisibilities 15, problemMaxSize) as slots; chain.id = the KfId per slot, -1 for an empty one.
-// observationCount: DEVICE [mapPointCount], the whole-map counts the chain keeps current (observationCountsOnDevice).  `lists` is scratch and
-// holds the window's lists afterwards.  The mirror's localBundleAdjust reports the outliers, not their chi2, so the apply step is handed
-// +inf for an outlier and 0 otherwise.  frames (slot -> DeviceKeyframe, may be null): the "no map point" masks of the slots that lost an
-// observation are renewed with unboundMasks.
-inline LocalBaOnTables localBundleAdjustOnTables(Context &ctx, DeviceObservationLists &lists, DeviceKeyframeMapPoints &kfTable, DeviceMapPoints &table, DeviceMapPointFlags &flags,
-                                                 const DeviceKeypointTable &kpTable, DeviceKeyframePoses &poses, const KeyframeCameras &cams, const KeyframeChain &chain,
-                                                 std::int32_t *observationCount, std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots,
-                                                 const PoseEdgeBuilder &edges, int problemMaxSize, const Parameters &parameters, const StaticSettings &settings,
-                                                 WorkspaceBA *workspace = nullptr, const std::vector<DeviceKeyframe *> *frames = nullptr) {
-    const std::size_t nKf = kfTable.size(), nMp = kfTable.mapPointCount();
-    if (chain.id.size() != nKf || cams.camera.size() != nKf || cams.focalLength.size() != nKf || poses.size() != nKf)
-        throw std::invalid_argument("localBundleAdjustOnTables: one KfId, camera, focal length and pose per slot");
-    if (table.size() != nMp || flags.size() < nMp || !observationCount) throw std::invalid_argument("localBundleAdjustOnTables: the map-point tables differ in size or the observation counts are missing");
+// adjacentSlots = computeAdjacentKeyframes(minCovisibilities 15, problemMaxSize) as slots; M.slots.id = the KfId per slot, -1 for an empty one.
+// M.observationCount: the whole-map counts the chain keeps current (observationCountsOnDevice).  Writes M.keyframes, M.points, M.flags, M.poses
+// and M.observationCount; M.lists is scratch and holds the window's lists afterwards.  The mirror's localBundleAdjust reports the outliers, not
+// their chi2, so the apply step is handed +inf for an outlier and 0 otherwise.  With M.slots.frames filled, the "no map point" masks of the slots that lost
+// an observation are renewed with unboundMasks.
+inline LocalBaOnTables localBundleAdjustOnTables(Context &ctx, MapTables M, std::int32_t currentSlot, const std::vector<std::int32_t> &adjacentSlots, const PoseEdgeBuilder &edges,
+                                                 int problemMaxSize, const Parameters &parameters, const StaticSettings &settings, WorkspaceBA *workspace = nullptr) {
+    M.require("localBundleAdjustOnTables", M.POINTS | M.FLAGS | M.LISTS | M.KEYPOINTS | M.POSES | M.COUNTS | M.CAMERAS | M.FOCALS | M.IDS);
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount();
+    DeviceObservationLists &lists = *M.lists;
     LocalBaOnTables out;
-    out.localSlots = detail::local_keyframes(chain.id, currentSlot, adjacentSlots);
+    out.localSlots = detail::local_keyframes(M.slots.id, currentSlot, adjacentSlots);
     const std::vector<std::int32_t> &local = out.localSlots;
     const std::int32_t current = (std::int32_t)(std::find(local.begin(), local.end(), currentSlot) - local.begin());
     // localMapPoints and their observations, on the device
     std::int32_t *unionRows = reinterpret_cast<std::int32_t *>(ctx.workspace(4 * nMp + 256));
     const ms_union_problem problem{0, (std::int32_t)local.size(), -1, DeviceMapPointFlags::TRIANGULATED};
     std::int32_t nUnion = 0;
-    ctx.check(ms_map_point_union(ctx.get(), kfTable.table(), (int)nKf, (int)kfTable.stride(), flags.flags(), (int)nMp, local.data(), (int)local.size(), &problem, 1, unionRows, nullptr,
+    ctx.check(ms_map_point_union(ctx.get(), M.keyframes.table(), (int)nKf, (int)M.keyframes.stride(), M.flags->flags(), (int)nMp, local.data(), (int)local.size(), &problem, 1, unionRows, nullptr,
                                  &nUnion), "ms_map_point_union");
     ObservationSelection sel;
     sel.deviceRows = unionRows; sel.rowCount = (std::size_t)nUnion;
     const int levels = (int)settings.levelSigmaSq.size();
-    lists.build(kfTable, kpTable, &flags, chain.id, {}, sel, levels);
+    lists.build(M, false, sel, levels);
     const std::size_t nRows = lists.rowCount(), nObs = lists.observationCount();
     const ms_obs_lists l = lists.lists();
     out.localRows = lists.download(l.rows, nRows);
     // the window: the edge arrays stay on the device for the apply step
-    const std::size_t pitch = (nObs + 63) / 64 * 64 + 64;
+    const std::size_t pitch = detail::padded(nObs);
     std::int32_t *edgeArrays = reinterpret_cast<std::int32_t *>(ctx.workspace(12 * pitch));
     const ms_ba_window_dev window{edgeArrays, edgeArrays + pitch, edgeArrays + 2 * pitch};
     BaWindow w;
     w.poses.resize(local.size()); w.points.resize(nRows); w.obsPose.resize(nObs); w.obsPoint.resize(nObs); w.obsUv.resize(nObs); w.obsInfo.resize(nObs);
     std::int32_t nEdge = 0, nCurrent = 0;
-    ctx.check(ms_ba_window_lists(ctx.get(), poses.pose(), (int)nKf, table.position(), (int)nMp, &l, (int)nRows, (int)nObs, local.data(), (int)local.size(), current,
-                                 cams.camera.data(), cams.focalLength.data(), settings.levelSigmaSq.data(), levels, w.poses[0].data(), nRows ? w.points[0].data() : nullptr,
+    ctx.check(ms_ba_window_lists(ctx.get(), M.poses->pose(), (int)nKf, M.points->position(), (int)nMp, &l, (int)nRows, (int)nObs, local.data(), (int)local.size(), current,
+                                 M.slots.camera.data(), M.slots.focalLength.data(), settings.levelSigmaSq.data(), levels, w.poses[0].data(), nRows ? w.points[0].data() : nullptr,
                                  w.obsPoint.data(), w.obsPose.data(), nObs ? w.obsUv[0].data() : nullptr, w.obsInfo.data(), (int)nRows, (int)nObs, &window, &nEdge, &nCurrent),
               "ms_ba_window_lists");
     out.currentFrameMapPoints = (std::size_t)nCurrent; out.edgeCount = (std::size_t)nEdge;
@@ -662,8 +627,8 @@ inline LocalBaOnTables localBundleAdjustOnTables(Context &ctx, DeviceObservation
     }
     std::vector<std::int32_t> erased((std::size_t)nEdge + 1);
     std::int32_t nErased = 0, nStale = 0;
-    ctx.check(ms_ba_window_apply(ctx.get(), kfTable.mutableTable(), (int)nKf, (int)kfTable.stride(), table.mutablePosition(), flags.mutableFlags(), observationCount, (int)nMp,
-                                 poses.pose(), w.poses[0].data(), (int)w.poses.size(), nRows ? w.points[0].data() : nullptr, neighbourhood ? chi2.data() : nullptr, &window, nEdge,
+    ctx.check(ms_ba_window_apply(ctx.get(), M.keyframes.mutableTable(), (int)nKf, (int)M.keyframes.stride(), M.points->mutablePosition(), M.flags->mutableFlags(), M.observationCount,
+                                 (int)nMp, M.poses->pose(), w.poses[0].data(), (int)w.poses.size(), nRows ? w.points[0].data() : nullptr, neighbourhood ? chi2.data() : nullptr, &window, nEdge,
                                  l.rows, (int)nRows, local.data(), (int)local.size(), current, neighbourhood ? MS_BA_APPLY_LOCAL : MS_BA_APPLY_NEIGHBOR, erased.data(), nEdge,
                                  &nErased, &nStale), "ms_ba_window_apply");
     if (nErased > 0) {
@@ -674,7 +639,7 @@ inline LocalBaOnTables localBundleAdjustOnTables(Context &ctx, DeviceObservation
             out.erased.push_back({e, slot, keyPoints[(std::size_t)e], out.localRows[(std::size_t)w.obsPoint[(std::size_t)e]]});
             if (std::find(touched.begin(), touched.end(), slot) == touched.end()) touched.push_back(slot);
         }
-        if (frames) unboundMasks(ctx, kfTable, touched, *frames);
+        if (!M.slots.frames.empty()) unboundMasks(ctx, M, touched);
     }
     return out;
 }
@@ -705,43 +670,32 @@ private:
 // poseBundleAdjust (bundle_adjuster.cpp:396-491) for the frame in `slot` with nothing walked on the host: the frame's TRIANGULATED map points
 // are gathered from the tables, solved and the pose written back into `poses` on the device.  Returns the reference's bool: false, with
 // nothing written, for a frame with fewer than minVisibleMapPointsInCurrentFrameBA such points (:410-412) or without a previous keyframe
-// (prevSlot = -1, :430-432).  live may be null (every row holds a map point).  keyPointCount defaults to the stride: the entries behind a
-// keyframe's keypoints are -1 (DeviceKeyframeMapPoints::update pads them).
-inline bool poseBundleAdjustOnTables(Context &ctx, DevicePoseAdjuster &handle, const DeviceKeyframeMapPoints &kfTable, const DeviceMapPointFlags &flags,
-                                     const DeviceMapPointLive *live, const DeviceMapPoints &table, const DeviceKeypointTable &kpTable, DeviceKeyframePoses &poses,
-                                     const KeyframeCameras &cams, std::int32_t slot, std::int32_t prevSlot, const PoseOdometryEdge &odometryEdge, const Parameters &parameters,
-                                     const StaticSettings &settings, std::size_t keyPointCount = ~(std::size_t)0) {
+// (prevSlot = -1, :430-432).  M.live may be null (every row holds a map point).  Writes M.poses alone.  keyPointCount defaults to the stride:
+// the entries behind a keyframe's keypoints are -1 (DeviceKeyframeMapPoints::update pads them).
+inline bool poseBundleAdjustOnTables(Context &ctx, MapTables M, DevicePoseAdjuster &handle, std::int32_t slot, std::int32_t prevSlot, const PoseOdometryEdge &odometryEdge,
+                                     const Parameters &parameters, const StaticSettings &settings, std::size_t keyPointCount = ~(std::size_t)0) {
     detail::TraceRange range("poseBundleAdjust");                             // mapper_helpers.cpp:1044
-    const std::size_t nKf = kfTable.size(), nMp = kfTable.mapPointCount();
-    if (cams.camera.size() != nKf || cams.focalLength.size() != nKf || poses.size() != nKf || kpTable.size() != nKf || kpTable.stride() != kfTable.stride())
-        throw std::invalid_argument("poseBundleAdjustOnTables: one camera, focal length, pose and keypoint row per slot");
-    if (table.size() != nMp || flags.size() < nMp || (live && live->size() < nMp)) throw std::invalid_argument("poseBundleAdjustOnTables: the map-point tables differ in size");
+    M.require("poseBundleAdjustOnTables", M.POINTS | M.FLAGS | M.KEYPOINTS | M.POSES | M.CAMERAS | M.FOCALS);
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount();
     if (slot < 0 || (std::size_t)slot >= nKf) throw std::invalid_argument("poseBundleAdjustOnTables: slot " + std::to_string(slot) + " outside the table");
     (void)settings;                                                            // (its level sigmas went to the device with the handle)
     ms_pose_tables_frame f{};
     f.slot = slot; f.prev_slot = prevSlot;
-    f.n_kp = (std::int32_t)std::min(keyPointCount, kfTable.stride());
-    f.cam = cams.camera[(std::size_t)slot]; f.focal = cams.focalLength[(std::size_t)slot];
+    f.n_kp = (std::int32_t)std::min(keyPointCount, M.keyframes.stride());
+    f.cam = M.slots.camera[(std::size_t)slot]; f.focal = M.slots.focalLength[(std::size_t)slot];
     std::copy(odometryEdge.measurement.begin(), odometryEdge.measurement.end(), f.edge_meas);
     std::copy(odometryEdge.information.begin(), odometryEdge.information.end(), f.edge_info);
     f.min_visible = (std::int32_t)parameters.minVisibleMapPointsInCurrentFrameBA;
     f.max_iters = (std::int32_t)parameters.poseBAIterations;
     f.huber_delta = std::sqrt(CHI2_THRESHOLD);                                 // rk->setDelta(std::sqrt(CHI2_THRESHOLD)) (:56), as detail::as_problem
-    ctx.check(ms_pose_tables_solve(handle.get(), kfTable.table(), (int)nKf, (int)kfTable.stride(), flags.flags(), live ? live->live() : nullptr, table.position(), (int)nMp,
-                                   kpTable.x(), kpTable.y(), kpTable.octave(), poses.pose(), &f, &handle.last, nullptr), "ms_pose_tables_solve");
+    ctx.check(ms_pose_tables_solve(handle.get(), M.keyframes.table(), (int)nKf, (int)M.keyframes.stride(), M.flags->flags(), M.live ? M.live->live() : nullptr, M.points->position(),
+                                   (int)nMp, M.keypoints->x(), M.keypoints->y(), M.keypoints->octave(), M.poses->pose(), &f, &handle.last, nullptr), "ms_pose_tables_solve");
     return handle.last.ran != 0;
 }
 
 // ---- fusing duplicate map points on the device tables (ms_map_fuse, ms_map_replace_pairs) ----------------------------------------------
-// The tables the fuse steps update in place.  observationCount: DEVICE [mapPointCount], mp.observations.size() of every row as
-// ms_observation_count leaves it (observationCountsOnDevice); the walk keeps it current, so one count serves a whole new-keyframe chain.
-struct FuseTables {
-    DeviceKeyframeMapPoints &table;
-    DeviceMapPointFlags &flags;
-    DeviceMapPointLive &live;
-    std::int32_t *observationCount;
-    DeviceTrackTable *tracks = nullptr;
-};
+// The fuse steps update M.keyframes, M.flags, M.live, M.observationCount (mp.observations.size() of every row as ms_observation_count leaves
+// it, observationCountsOnDevice; the walk keeps it current, so one count serves a whole new-keyframe chain) and, when given, M.tracks.
 // One keyframe as replaceDuplication reads it: its slot, its matcher features, poseCW (p_c = R p + t, row-major) and camera.
 struct FuseKeyframe {
     std::int32_t slot = 0;
@@ -758,23 +712,19 @@ struct FuseResult {
     unsigned fusedCount = 0, regates = 0;
 };
 
-// mp.observations.size() of every row into DEVICE memory (counts: [table.mapPointCount()]), for FuseTables::observationCount
-inline void observationCountsOnDevice(Context &ctx, const DeviceKeyframeMapPoints &table, const std::vector<std::int32_t> &kfIds, std::int32_t *counts) {
-    if (kfIds.size() != table.size()) throw std::invalid_argument("observationCountsOnDevice: one KfId per slot");
-    ctx.check(ms_observation_count(ctx.get(), table.table(), (int)table.size(), (int)table.stride(), (int)table.mapPointCount(), kfIds.data(), counts, nullptr, nullptr),
-              "ms_observation_count");
+// mp.observations.size() of every row, written into M.observationCount
+inline void observationCountsOnDevice(Context &ctx, MapTables M) {
+    M.require("observationCountsOnDevice", M.COUNTS | M.IDS);
+    ctx.check(ms_observation_count(ctx.get(), M.keyframes.table(), (int)M.keyframes.size(), (int)M.keyframes.stride(), (int)M.keyframes.mapPointCount(), M.slots.id.data(),
+                                   M.observationCount, nullptr, nullptr), "ms_observation_count");
 }
 
 namespace detail {
-inline void check_fuse_tables(const FuseTables &T, const char *who) {
-    const std::size_t nMp = T.table.mapPointCount();
-    if (T.flags.size() < nMp || T.live.size() < nMp || (T.tracks && T.tracks->mapPointCount() != nMp) || !T.observationCount)
-        throw std::invalid_argument(std::string(who) + ": the map-point tables differ in size or the observation counts are missing");
-}
+constexpr unsigned FUSE_PARTS = MapTables::FLAGS | MapTables::LIVE | MapTables::COUNTS;      // what every fuse step needs of the view
 
 // replaceDuplication of `rows` against each of `keyframes`, in order, as ONE gate call, one scoring launch per keyframe and ONE ms_map_fuse
 // on the lists where they lie.  Returns views_done.
-inline std::size_t fuse_batch(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables &T, const FuseKeyframe *keyframes, std::size_t n, const std::vector<std::int32_t> &rows,
+inline std::size_t fuse_batch(Context &ctx, MapTables M, const FuseKeyframe *keyframes, std::size_t n, const std::vector<std::int32_t> &rows,
                               float margin, std::int32_t sourceSlot, const StaticSettings &settings, FuseResult &out) {
     std::vector<GateView> views(n);
     std::vector<const DeviceKeyframe *> kfs(n);
@@ -783,15 +733,15 @@ inline std::size_t fuse_batch(Context &ctx, const DeviceMapPoints &mapPoints, Fu
         views[v].camera = keyframes[v].camera; views[v].threshold = margin; views[v].mode = MS_GATE_FUSE; views[v].indices = rows;
         kfs[v] = keyframes[v].features;
     }
-    const DeviceGatedLists g = gate_and_score_device(ctx, mapPoints, views, kfs, settings, 8);
+    const DeviceGatedLists g = gate_and_score_device(ctx, *M.points, views, kfs, settings, 8);
     std::vector<ms_fuse_view> fv(n);
     for (std::size_t v = 0; v < n; ++v) fv[v] = ms_fuse_view{keyframes[v].slot, g.first[v], g.count[v]};
     const std::size_t ne = g.index.size();
     std::int32_t *erasedRows = reinterpret_cast<std::int32_t *>(g.extra), *erasedInto = erasedRows + ne;
     std::int32_t nErased = 0, counts[8] = {0}, viewsDone = 0;
-    ctx.check(ms_map_fuse(ctx.get(), T.table.mutableTable(), (int)T.table.size(), (int)T.table.stride(), T.flags.mutableFlags(), T.live.mutableLive(), T.observationCount,
-                          (int)T.table.mapPointCount(), T.tracks ? T.tracks->mpTrack() : nullptr, T.tracks ? T.tracks->trackRow() : nullptr,
-                          T.tracks ? T.tracks->trackBase() : 0, T.tracks ? (int)T.tracks->window() : 0, g.keptEntry, g.topIdx, g.topDist, g.index.data(), (int)ne, fv.data(),
+    const MapTables::TrackWindow tw = M.trackWindow();
+    ctx.check(ms_map_fuse(ctx.get(), M.keyframes.mutableTable(), (int)M.keyframes.size(), (int)M.keyframes.stride(), M.flags->mutableFlags(), M.live->mutableLive(), M.observationCount,
+                          (int)M.keyframes.mapPointCount(), tw.mpTrack, tw.trackRow, tw.base, tw.window, g.keptEntry, g.topIdx, g.topDist, g.index.data(), (int)ne, fv.data(),
                           g.nKept.data(), (int)n, (int)HAMMING_DIST_THR_LOW, sourceSlot, nullptr, nullptr, nullptr, erasedRows, erasedInto, &nErased, counts, &viewsDone),
               "ms_map_fuse");
     const std::vector<std::int32_t> rowsDown = ctx.download(erasedRows, (std::size_t)nErased), intoDown = ctx.download(erasedInto, (std::size_t)nErased);
@@ -811,37 +761,35 @@ inline std::size_t fuse_batch(Context &ctx, const DeviceMapPoints &mapPoints, Fu
 //   direction 2 (:346)      one view: the union against the current keyframe
 // margin = getFocalLength(currentKeyframe) * relativeReprojectionErrorThreshold (:328), computed by the caller.  The graph filters of
 // keyframe_matcher.cpp:429-440 run inside the walk, so every valid row is gated.
-inline FuseResult deduplicateMapPoints(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables T, const FuseKeyframe &current, const std::vector<FuseKeyframe> &adjacent,
-                                       float margin, const StaticSettings &settings) {
-    detail::check_fuse_tables(T, "deduplicateMapPoints");
-    const std::size_t nMp = T.table.mapPointCount(), stride = T.table.stride();
-    if (current.slot < 0 || (std::size_t)current.slot >= T.table.size()) throw std::invalid_argument("deduplicateMapPoints: current keyframe outside the table");
+inline FuseResult deduplicateMapPoints(Context &ctx, MapTables M, const FuseKeyframe &current, const std::vector<FuseKeyframe> &adjacent, float margin, const StaticSettings &settings) {
+    M.require("deduplicateMapPoints", detail::FUSE_PARTS | M.POINTS);
+    const std::size_t nMp = M.keyframes.mapPointCount(), stride = M.keyframes.stride();
+    if (current.slot < 0 || (std::size_t)current.slot >= M.keyframes.size()) throw std::invalid_argument("deduplicateMapPoints: current keyframe outside the table");
     FuseResult out;
     std::vector<std::int32_t> rows, adjacentSlots;
     for (std::size_t done = 0; done < adjacent.size();) {
-        const std::vector<std::int32_t> slotRow = ctx.download(T.table.table() + (std::size_t)current.slot * stride, stride);
+        const std::vector<std::int32_t> slotRow = ctx.download(M.keyframes.table() + (std::size_t)current.slot * stride, stride);
         rows.clear();
         for (std::int32_t r : slotRow) if (r >= 0 && (std::size_t)r < nMp) rows.push_back(r);
         if (rows.empty()) break;
         if (done) ++out.regates;
-        done += detail::fuse_batch(ctx, mapPoints, T, adjacent.data() + done, adjacent.size() - done, rows, margin, current.slot, settings, out);
+        done += detail::fuse_batch(ctx, M, adjacent.data() + done, adjacent.size() - done, rows, margin, current.slot, settings, out);
     }
     for (const FuseKeyframe &k : adjacent) adjacentSlots.push_back(k.slot);
-    rows = localMapPoints(ctx, T.table, nullptr, adjacentSlots, -1, 0, false).row;
-    if (!rows.empty()) detail::fuse_batch(ctx, mapPoints, T, &current, 1, rows, margin, -1, settings, out);
+    rows = localMapPoints(ctx, M.keyframes, nullptr, adjacentSlots, -1, 0, false).row;
+    if (!rows.empty()) detail::fuse_batch(ctx, M, &current, 1, rows, margin, -1, settings, out);
     return out;
 }
 
 // searchAndDeduplicate (loop_closer.cpp:567-591): loopMapPoints = the usable rows (neither BAD nor NOT_TRIANGULATED, :575-578) of the
 // candidate keyframe's neighbours (slots; the caller's getNeighbors), a std::set and therefore a copy: every rigidly transformed keyframe
 // is walked against the same list (source_slot = -1), margin 4.
-inline FuseResult searchAndDeduplicate(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables T, const std::vector<std::int32_t> &neighbourSlots,
-                                       const std::vector<FuseKeyframe> &rigidlyTransformed, const StaticSettings &settings) {
-    detail::check_fuse_tables(T, "searchAndDeduplicate");
+inline FuseResult searchAndDeduplicate(Context &ctx, MapTables M, const std::vector<std::int32_t> &neighbourSlots, const std::vector<FuseKeyframe> &rigidlyTransformed,
+                                       const StaticSettings &settings) {
+    M.require("searchAndDeduplicate", detail::FUSE_PARTS | M.POINTS);
     FuseResult out;
-    const std::vector<std::int32_t> rows = localMapPoints(ctx, T.table, &T.flags, neighbourSlots, -1, DeviceMapPointFlags::USABLE, false).row;
-    if (!rows.empty() && !rigidlyTransformed.empty())
-        detail::fuse_batch(ctx, mapPoints, T, rigidlyTransformed.data(), rigidlyTransformed.size(), rows, 4.0f, -1, settings, out);
+    const std::vector<std::int32_t> rows = localMapPoints(ctx, M.keyframes, M.flags, neighbourSlots, -1, DeviceMapPointFlags::USABLE, false).row;
+    if (!rows.empty() && !rigidlyTransformed.empty()) detail::fuse_batch(ctx, M, rigidlyTransformed.data(), rigidlyTransformed.size(), rows, 4.0f, -1, settings, out);
     return out;
 }
 
@@ -850,35 +798,33 @@ inline FuseResult searchAndDeduplicate(Context &ctx, const DeviceMapPoints &mapP
 // does not list yet (:241-261; they come down once, as the gate takes its rows from the host), then ONE MS_GATE_SEARCH view with
 // viewAngleLimitCos 0.5 (:304) and searchByProjection with the walk and both addObservations on the tables (searchByProjectionOnTables): the
 // top-4 lists and the query arrays stay on the device, and neither the current keyframe's row of kf_mp nor n_obs is uploaded afterwards.
-// T.observationCount stays current.  usable (optional) = current.features' DEVICE matcher mask (DeviceKeyframe::mutableUsable), cleared at each
+// M.observationCount stays current.  usable (optional) = current.features' DEVICE matcher mask (DeviceKeyframe::mutableUsable), cleared at each
 // bound keypoint.  Returns at once on an empty list (:263).
-inline SearchBindResult matchLocalMapPoints(Context &ctx, const DeviceMapPoints &mapPoints, FuseTables T, const FuseKeyframe &current,
-                                            const std::vector<std::int32_t> &adjacentSlots, float threshold, const StaticSettings &settings, std::uint8_t *usable = nullptr,
-                                            bool wantMatches = false) {
-    detail::check_fuse_tables(T, "matchLocalMapPoints");
-    if (current.slot < 0 || (std::size_t)current.slot >= T.table.size() || !current.features) throw std::invalid_argument("matchLocalMapPoints: current keyframe outside the table");
+inline SearchBindResult matchLocalMapPoints(Context &ctx, MapTables M, const FuseKeyframe &current, const std::vector<std::int32_t> &adjacentSlots, float threshold,
+                                            const StaticSettings &settings, std::uint8_t *usable = nullptr, bool wantMatches = false) {
+    M.require("matchLocalMapPoints", detail::FUSE_PARTS | M.POINTS);
+    if (current.slot < 0 || (std::size_t)current.slot >= M.keyframes.size() || !current.features) throw std::invalid_argument("matchLocalMapPoints: current keyframe outside the table");
     GateView view;
-    view.indices = localMapPoints(ctx, T.table, &T.flags, adjacentSlots, current.slot, DeviceMapPointFlags::USABLE, false).row;
+    view.indices = localMapPoints(ctx, M.keyframes, M.flags, adjacentSlots, current.slot, DeviceMapPointFlags::USABLE, false).row;
     if (view.indices.empty()) return SearchBindResult{};
     std::copy(current.R, current.R + 9, view.R); std::copy(current.t, current.t + 3, view.t);
     view.camera = current.camera; view.threshold = threshold; view.cosLimit = 0.5f; view.mode = MS_GATE_SEARCH;
-    return searchByProjectionOnTables(ctx, *current.features, mapPoints, view, T.table.mutableTable(), T.table.size(), T.table.stride(), T.live.live(), T.observationCount,
-                                      T.table.mapPointCount(), current.slot, settings, usable, wantMatches);
+    return searchByProjectionOnTables(ctx, M, *current.features, view, current.slot, settings, usable, wantMatches);
 }
 
 // "Merge moved map points", loop_closer.cpp:531-546: loopClosure.mapPointMatches as (first, second) table rows, in order.  outcome per pair:
 // 0 replaced (first by second) | 1 equal | 2 skipped by the `merged` rule.  counts stays zero; fusedCount = the replaced pairs.
-inline FuseResult mergeMatchedMapPoints(Context &ctx, FuseTables T, const std::vector<std::pair<std::int32_t, std::int32_t>> &matches, std::vector<std::uint8_t> *outcome = nullptr) {
-    detail::check_fuse_tables(T, "mergeMatchedMapPoints");
+inline FuseResult mergeMatchedMapPoints(Context &ctx, MapTables M, const std::vector<std::pair<std::int32_t, std::int32_t>> &matches, std::vector<std::uint8_t> *outcome = nullptr) {
+    M.require("mergeMatchedMapPoints", detail::FUSE_PARTS);
     FuseResult out;
     const std::size_t n = matches.size();
     std::vector<std::int32_t> pairs(2 * n);
     for (std::size_t i = 0; i < n; ++i) { pairs[2 * i] = matches[i].first; pairs[2 * i + 1] = matches[i].second; }
     std::vector<std::uint8_t> oc(n, 0);
     std::int32_t *erasedRows = reinterpret_cast<std::int32_t *>(ctx.workspace(8 * n + 64)), *erasedInto = erasedRows + n, nErased = 0;
-    ctx.check(ms_map_replace_pairs(ctx.get(), T.table.mutableTable(), (int)T.table.size(), (int)T.table.stride(), T.flags.mutableFlags(), T.live.mutableLive(),
-                                   T.observationCount, (int)T.table.mapPointCount(), T.tracks ? T.tracks->mpTrack() : nullptr, T.tracks ? T.tracks->trackRow() : nullptr,
-                                   T.tracks ? T.tracks->trackBase() : 0, T.tracks ? (int)T.tracks->window() : 0, pairs.data(), (int)n, oc.data(), erasedRows, erasedInto,
+    const MapTables::TrackWindow tw = M.trackWindow();
+    ctx.check(ms_map_replace_pairs(ctx.get(), M.keyframes.mutableTable(), (int)M.keyframes.size(), (int)M.keyframes.stride(), M.flags->mutableFlags(), M.live->mutableLive(),
+                                   M.observationCount, (int)M.keyframes.mapPointCount(), tw.mpTrack, tw.trackRow, tw.base, tw.window, pairs.data(), (int)n, oc.data(), erasedRows, erasedInto,
                                    &nErased), "ms_map_replace_pairs");
     out.erasedRows = ctx.download(erasedRows, (std::size_t)nErased); out.erasedInto = ctx.download(erasedInto, (std::size_t)nErased);
     out.fusedCount = (unsigned)nErased;

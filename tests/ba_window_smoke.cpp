@@ -115,7 +115,7 @@ struct Map {
     std::vector<std::vector<float>> x, y;
     std::vector<std::vector<std::int32_t>> octave;
     std::vector<DeviceKeyframePoses::Pose> pose;
-    KeyframeCameras cams;
+    KeyframeSlots cams;                      // camera and focalLength; the view's id is kfId above
     std::vector<DeviceMapPoints::Vec3d> position;
     std::vector<std::uint8_t> flags;
     std::vector<std::int32_t> adjacent;
@@ -169,16 +169,23 @@ struct Tables {
     DeviceKeypointTable kp;
     DeviceKeyframePoses poses;
     DeviceArray<std::int32_t> nObs;
+    KeyframeSlots slots;
     Tables(Context &ctx, const Map &m)
         : kf(ctx, Map::nKf, Map::stride, Map::nMp),
           points(ctx, m.position, std::vector<DeviceMapPoints::Vec3f>(Map::nMp, DeviceMapPoints::Vec3f{0, 0, 1}), std::vector<float>(Map::nMp, 0.f), std::vector<float>(Map::nMp, 0.f),
                  std::vector<KeyPoint::Descriptor>(Map::nMp, KeyPoint::Descriptor{})),
-          flags(ctx, m.flags), kp(ctx, Map::nKf, Map::stride), poses(ctx, m.pose), nObs(ctx, Map::nMp) {
+          flags(ctx, m.flags), kp(ctx, Map::nKf, Map::stride), poses(ctx, m.pose), nObs(ctx, Map::nMp), slots(m.cams) {
+        slots.id = m.kfId;
         for (int k = 0; k < Map::nKf; ++k) {
             kf.update((std::size_t)k, m.mapPoints[(std::size_t)k]);
             kp.update((std::size_t)k, m.x[(std::size_t)k], m.y[(std::size_t)k], m.octave[(std::size_t)k], {});
         }
-        observationCountsOnDevice(ctx, kf, m.kfId, nObs.data());
+        observationCountsOnDevice(ctx, view(nullptr));
+    }
+    MapTables view(DeviceObservationLists *lists) {
+        MapTables M{kf, slots};
+        M.flags = &flags; M.points = &points; M.keypoints = &kp; M.poses = &poses; M.observationCount = nObs.data(); M.lists = lists;
+        return M;
     }
 };
 
@@ -205,8 +212,6 @@ int with_gpu() {
     const Map m = make_map();
     Parameters params;
     const StaticSettings settings(params);
-    KeyframeChain chain;
-    chain.id = m.kfId;
     const PoseEdgeBuilder edges = [&](const std::vector<std::int32_t> &local, BaWindow &w) {      // the odometry chain of :296-311 between neighbours in pose order
         for (std::size_t k = 1; k < local.size(); ++k) {
             w.edgeI.push_back((std::int32_t)k - 1); w.edgeJ.push_back((std::int32_t)k);
@@ -248,14 +253,14 @@ int with_gpu() {
         const Snapshot before = snapshot(ctx, t);
         Parameters p = params;
         if (which == 0) p.minVisibleMapPointsInCurrentFrameBA = (unsigned)nCurrentWant + 1; else p.minKeyframesInBA = (unsigned)localWant.size() + 1;
-        const LocalBaOnTables out = localBundleAdjustOnTables(ctx, lists, t.kf, t.points, t.flags, t.kp, t.poses, m.cams, chain, t.nObs.data(), Map::current, m.adjacent, edges, 20,
+        const LocalBaOnTables out = localBundleAdjustOnTables(ctx, t.view(&lists), Map::current, m.adjacent, edges, 20,
                                                               p, settings);
         if (out.stage != BaStats::Ba::NONE || out.outcome.ran) return fail("an early-out ran the solver");
         if (out.localSlots != localWant || out.localRows != std::vector<std::int32_t>(localMapPoints.begin(), localMapPoints.end())) return fail("early-out: local sets");
         if (!(snapshot(ctx, t) == before)) return fail("an early-out wrote to the tables");
         p = params;
         if (which == 0) p.minVisibleMapPointsInCurrentFrameBA = (unsigned)nCurrentWant; else p.minKeyframesInBA = (unsigned)localWant.size();       // at the threshold it runs
-        if (localBundleAdjustOnTables(ctx, lists, t.kf, t.points, t.flags, t.kp, t.poses, m.cams, chain, t.nObs.data(), Map::current, m.adjacent, edges, 20, p, settings).stage !=
+        if (localBundleAdjustOnTables(ctx, t.view(&lists), Map::current, m.adjacent, edges, 20, p, settings).stage !=
             BaStats::Ba::LOCAL)
             return fail("a window at the threshold did not run");
     }
@@ -267,7 +272,7 @@ int with_gpu() {
         Parameters p = params;
         p.minVisibleMapPointsInNeighborhoodBA = (unsigned)nCurrentWant + 1;
         WorkspaceBA workspace(true);
-        const LocalBaOnTables out = localBundleAdjustOnTables(ctx, lists, t.kf, t.points, t.flags, t.kp, t.poses, m.cams, chain, t.nObs.data(), Map::current, m.adjacent, edges, 20,
+        const LocalBaOnTables out = localBundleAdjustOnTables(ctx, t.view(&lists), Map::current, m.adjacent, edges, 20,
                                                               p, settings, &workspace);
         const Snapshot after = snapshot(ctx, t);
         if (out.stage != BaStats::Ba::NEIGHBOR || !out.outcome.ran || workspace.baStats.frameCount(BaStats::Ba::NEIGHBOR) != 1 || !out.erased.empty()) return fail("NEIGHBOR stage");
@@ -284,7 +289,7 @@ int with_gpu() {
     DeviceObservationLists lists(ctx);
     const Snapshot before = snapshot(ctx, t);
     WorkspaceBA workspace(true);
-    const LocalBaOnTables out = localBundleAdjustOnTables(ctx, lists, t.kf, t.points, t.flags, t.kp, t.poses, m.cams, chain, t.nObs.data(), Map::current, m.adjacent, edges, 20, params,
+    const LocalBaOnTables out = localBundleAdjustOnTables(ctx, t.view(&lists), Map::current, m.adjacent, edges, 20, params,
                                                           settings, &workspace);
     const Snapshot after = snapshot(ctx, t);
     if (out.stage != BaStats::Ba::LOCAL || workspace.baStats.frameCount(BaStats::Ba::LOCAL) != 1) return fail("LOCAL stage");

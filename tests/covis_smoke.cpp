@@ -28,7 +28,7 @@ struct HostMap {
     std::vector<std::vector<std::int32_t>> mapPoints;        // Keyframe::mapPoints per slot (-1 = none)
     std::vector<std::map<std::int32_t, int>> observations;   // MapPoint::observations per row: slot -> keypoint
     std::vector<std::uint8_t> flags;
-    KeyframeChain chain;
+    KeyframeSlots chain;
     void link() {
         observations.assign(flags.size(), {});
         for (std::size_t k = 0; k < mapPoints.size(); ++k)
@@ -283,11 +283,13 @@ int gpu() {
     table.update(40, M.mapPoints[40]);
     std::printf("update ok %d turned away\n", turnedAway);
     // computeAdjacentKeyframes from several keyframes, thresholds and sizes
+    MapTables tables{table, M.chain};
+    tables.flags = &flags;
     std::size_t adjacentTotal = 0;
     for (std::int32_t current : {89, 60, 14, 13, 0})
         for (int minCovis : {1, 4})
             for (int maxKeyframes : {20, 7, 1}) {
-                const auto got = computeAdjacentKeyframes(ctx, table, &flags, current, minCovis, maxKeyframes, M.chain);
+                const auto got = computeAdjacentKeyframes(ctx, tables, current, minCovis, maxKeyframes);
                 if (got != compute_adjacent(M, current, minCovis, maxKeyframes)) { std::printf("computeAdjacentKeyframes differs: current %d minCovis %d max %d\n", current, minCovis, maxKeyframes); return 5; }
                 adjacentTotal += got.size();
             }

@@ -76,7 +76,7 @@ struct Map {
     std::vector<std::vector<float>> depth;
     std::vector<std::int32_t> kfId, descBase, adjacent, freeRows;
     std::vector<DeviceKeyframePoses::Pose> pose;
-    KeyframeCameras cams;
+    KeyframeSlots cams;                      // camera and focalLength; the view's id and descBase are kfId and descBase above
     std::vector<DeviceMapPoints::Vec3d> position;
     std::vector<std::uint8_t> flags, live;
     std::vector<KeyPoint::Descriptor> pool;
@@ -205,11 +205,17 @@ int run() {
     DeviceObservationLists lists(ctx, 4, 8);                 // small on purpose: it grows
     std::vector<std::int32_t> all;
     for (int k = 0; k < Map::nKf; ++k) all.push_back(k);
-    unboundMasks(ctx, dev.table, all, dev.framePtr);         // rewrites what the constructor uploaded; must give the same masks
-    DeviceArray<std::int32_t> nObs(ctx, Map::nMp), mpTrack(ctx, Map::nMp);
-    nObs.fill(7); mpTrack.fill(41);
-    const std::vector<CreatedPoints> got = createNewMapPoints(ctx, lists, dev.table, dev.points, dev.flags, dev.live, keypoints, poses, m.cams, m.kfId, m.descBase, &pool, Map::current,
-                                                              m.adjacent, dev.framePtr, m.freeRows, settings, TriangulationMethod::TME, nObs.data(), mpTrack.data(), &m.pose);
+    KeyframeSlots slots = m.cams;
+    slots.id = m.kfId; slots.descBase = m.descBase; slots.frames = dev.framePtr;
+    DeviceArray<std::int32_t> nObs(ctx, Map::nMp);
+    DeviceTrackTable tracks(ctx, Map::nMp, 0, 1);
+    const std::vector<std::int32_t> track41(Map::nMp, 41);
+    nObs.fill(7); ctx.check(ms_dev_upload(ctx.get(), tracks.mpTrack(), track41.data(), 4 * track41.size()), "ms_dev_upload");
+    MapTables tables{dev.table, slots};
+    tables.flags = &dev.flags; tables.points = &dev.points; tables.live = &dev.live; tables.keypoints = &keypoints; tables.poses = &poses; tables.pool = &pool; tables.lists = &lists;
+    tables.observationCount = nObs.data(); tables.tracks = &tracks;
+    unboundMasks(ctx, tables, all);                          // rewrites what the constructor uploaded; must give the same masks
+    const std::vector<CreatedPoints> got = createNewMapPoints(ctx, tables, Map::current, m.adjacent, m.freeRows, settings, TriangulationMethod::TME, &m.pose);
 
     // ---- the restatement: Keyframe::mapPoints and std::map observations on the host, one match after the other
     Tables ref(ctx, m);
@@ -285,7 +291,7 @@ int run() {
         }
     }
     if (dev.bytes(ctx, m) != ref.bytes(ctx, m)) { std::printf("the tables differ\n"); return 5; }
-    if (nObs.download() != wantObs || mpTrack.download() != wantTrack) { std::printf("n_obs or mp_track differ\n"); return 5; }
+    if (nObs.download() != wantObs || tracks.downloadMapPointTracks() != wantTrack) { std::printf("n_obs or mp_track differ\n"); return 5; }
     if (created < 20 || angle < 5 || depthBranch < 3 || secondTrip < 3 || flipped < 5 || emptyOrSkipped < 1 || failedThenCreated < 1) {
         std::printf("the map exercises too little (%zu %zu %zu %zu %zu %zu %zu %zu)\n", created, angle, other, depthBranch, secondTrip, flipped, emptyOrSkipped, failedThenCreated);
         return 6;

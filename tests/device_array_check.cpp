@@ -247,13 +247,17 @@ void keypoint_table(Context &ctx) {
 void observation_lists(Context &ctx) {
     DeviceKeyframeMapPoints table(ctx, 3, 5, 10);
     DeviceKeypointTable kp(ctx, 3, 5);
+    KeyframeSlots slots;
+    slots.id = {0, 1, 2};
+    MapTables tables{table, slots};
+    tables.keypoints = &kp;
     DeviceObservationLists lists(ctx, 2, 4);
     ObservationSelection sel;
     sel.slot = 0;
     g_needRows = 2; g_needObs = 3;
-    lists.build(table, kp, nullptr, {0, 1, 2}, {}, sel, 0);                       // fits
+    lists.build(tables, false, sel, 0);                       // fits
     g_needRows = 5; g_needObs = 9;
-    lists.build(table, kp, nullptr, {0, 1, 2}, {}, sel, 0);                       // regrows once
+    lists.build(tables, false, sel, 0);                       // regrows once
     CHECK(lists.rowCount() == 5 && lists.observationCount() == 9);
     CHECK((lists.download(lists.lists().rows, 5) == std::vector<std::int32_t>{0, 1, 2, 3, 4}));
 }
@@ -344,17 +348,21 @@ void observation_lists_recover(Context &ctx) {
         reset_stand_in();
         DeviceKeyframeMapPoints table(ctx, 3, 5, 10);
         DeviceKeypointTable kp(ctx, 3, 5);
+            KeyframeSlots slots;
+        slots.id = {0, 1, 2};
+        MapTables tables{table, slots};
+        tables.keypoints = &kp;
         const std::size_t others = g_live.size();
         DeviceObservationLists lists(ctx, 2, 4);
         ObservationSelection sel;
         sel.slot = 0;
         g_needRows = 5; g_needObs = 9;
         g_failAt = g_allocs + k;
-        CHECK(throws_runtime_error([&] { lists.build(table, kp, nullptr, {0, 1, 2}, {}, sel, 0); }));
+        CHECK(throws_runtime_error([&] { lists.build(tables, false, sel, 0); }));
         CHECK(g_live.size() == others);
         g_failAt = -1;
         const long before = g_allocs;
-        lists.build(table, kp, nullptr, {0, 1, 2}, {}, sel, 0);
+        lists.build(tables, false, sel, 0);
         CHECK(g_allocs > before && lists.rowCount() == 5 && g_live.size() == others + 12);
         CHECK((lists.download(lists.lists().rows, 5) == std::vector<std::int32_t>{0, 1, 2, 3, 4}));
     }

@@ -36,7 +36,7 @@ struct Scene {
     std::vector<float> maxDistance;
     std::vector<KeyPoint::Descriptor> mpDescriptor;
     std::vector<std::int32_t> candidates, adjacent;
-    KeyframeChain chain;
+    KeyframeSlots chain;
 };
 
 Kind kindOf(int slot) {
@@ -116,11 +116,12 @@ Scene makeScene() {
     }
     S.candidates = {16, 14, 3, 12, 5, 7, 0, 1, 2, 4, 6, 8, 9, 10, 11};
     S.adjacent = {16, 15, 14, 13};
-    KeyframeChain &c = S.chain;
+    KeyframeSlots &c = S.chain;
     for (int s = 0; s < kKf; ++s) {
         c.previous.push_back(s - 1); c.next.push_back(s + 1 < kKf ? s + 1 : -1);
         c.cameraCenter.push_back(detail::cameraCenterOf(S.keyframes[s].poseCW));
         c.id.push_back(S.keyframes[s].id); c.t.push_back(S.keyframes[s].t);
+        c.camera.push_back(kCam);
     }
     return S;
 }
@@ -272,21 +273,24 @@ StaticSettings makeSettings() {
 struct Mirror {
     std::vector<std::unique_ptr<DeviceKeyframe>> owned;
     std::vector<DeviceKeyframe *> frames;
-    Mirror(Context &ctx, const Scene &S) {
+    KeyframeSlots slots;                                     // the scene's chain and cameras with the frames
+    Mirror(Context &ctx, const Scene &S) : slots(S.chain) {
         for (const Keyframe &kf : S.keyframes) {             // the masks start empty: ms_loop_usable_mask writes them
             owned.emplace_back(new DeviceKeyframe(ctx, featuresOf(kf, std::vector<std::uint8_t>(kf.keyPoints.size(), 0))));
             frames.push_back(owned.back().get());
         }
+        slots.frames = frames;
     }
 };
 
-LoopClosureResult mirror(Context &ctx, const Scene &S, const Device &D, Mirror &M, const StaticSettings &settings) {
-    const LoopCloserTables T{D.keyframes, D.flags, &D.live, D.points, D.poses, D.keypoints};
-    return tryLoopClosureOnTables(ctx, T, kCur, S.candidates, S.adjacent, S.chain, M.frames, std::vector<ms_pinhole>(kKf, kCam), -1.0, settings);
+LoopClosureResult mirror(Context &ctx, const Scene &S, Device &D, Mirror &M, const StaticSettings &settings) {
+    MapTables T{D.keyframes, M.slots};
+    T.flags = &D.flags; T.live = &D.live; T.points = &D.points; T.poses = &D.poses; T.keypoints = &D.keypoints;
+    return tryLoopClosureOnTables(ctx, T, kCur, S.candidates, S.adjacent, -1.0, settings);
 }
 
 int no_gpu() {
-    std::printf("link ok %d\n", (int)(sizeof(LoopClosureResult) > 0 && sizeof(LoopCloserTables) > 0 && sizeof(LoopClosure) > 0));
+    std::printf("link ok %d\n", (int)(sizeof(LoopClosureResult) > 0 && sizeof(MapTables) > 0 && sizeof(LoopClosure) > 0));
     char why[256];
     std::int32_t kf[16], slots[2] = {1, 0}, nKp[2] = {4, 3}, req[2] = {0, 1}, row[8], cand[2] = {0, 2}, start[3] = {0, 1, 2}, a[2] = {0, 1}, out[8];
     std::fill(kf, kf + 16, -1);

@@ -5,7 +5,7 @@
 //   map_cull_smoke --no-gpu               every MS_ERR_INVALID case of ms_map_cull through ms_map_cull_check (no context, no device), and the
 //                                         restatement below on a hand-computed map.  The validation itself (csrc/map_checks.cpp) runs under
 //                                         sanitizers in tests/test_map_checks_corpus.py
-//   map_cull_smoke --gpu                  observationCounts and cullMap against the restatement, the relinked KeyframeChain included
+//   map_cull_smoke --gpu                  observationCounts and cullMap against the restatement, the relinked KeyframeSlots included
 //   map_cull_smoke --baseline K S M C [F] the restatement on one core for K slots of S entries over M rows and C candidates: building the
 //                                         observation maps (what ms_observation_count replaces) and the two culling passes; prints the best
 //                                         of three in milliseconds and checksums, and writes the map to the file F (kf_mp int32 [K * S] |
@@ -34,7 +34,7 @@ struct HostMap {
     std::vector<std::map<std::int32_t, int>> observations;   // MapPoint::observations per row: KfId -> entries of that keyframe
     std::vector<std::uint8_t> flags, live;
     std::vector<std::int32_t> cand;
-    KeyframeChain chain;
+    KeyframeSlots chain;
     std::map<std::int32_t, std::int32_t> slotOf;             // mapDB.keyframes: KfId -> slot
     std::vector<std::int32_t> removedRows, removedKeyframes; // in the order of removal
     std::vector<std::uint8_t> removedWhy;
@@ -295,8 +295,10 @@ int gpu() {
         s.ratioFloat32 = f32;
         const std::int32_t current = nKf - 1;
         const std::vector<std::int32_t> loopKeyframes{M.cand[1], 3};
-        KeyframeChain chain = M.chain;
-        const CullResult got = cullMap(ctx, table, &flags, live, chain, current, M.cand, loopKeyframes, s);
+        KeyframeSlots chain = M.chain;
+        MapTables tables{table, chain};
+        tables.flags = &flags; tables.live = &live;
+        const CullResult got = cullMap(ctx, tables, current, M.cand, loopKeyframes, s);
         cull_map_points(M, current, s.minMapPointCullingAge);
         cull_keyframes(M, M.cand, loopKeyframes, s);
         // the restatement lists the rows in the order of removal, the device in row order

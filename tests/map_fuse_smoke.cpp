@@ -165,6 +165,7 @@ struct Device {
     DeviceMapPointLive live;
     DeviceTrackTable tracks;
     DeviceArray<std::int32_t> nObs;
+    KeyframeSlots slots;
     Device(Context &c, const Scene &S) : ctx(c), points(c, S.pos, S.norm, S.dmin, S.dmax, S.desc), table(c, kKf, kStride, kMp), flags(c, S.flags), live(c, S.live),
                                         tracks(c, kMp, kTrackBase, kWindow), nObs(c, kMp) {
         for (int s = 0; s < kKf; ++s) table.update((std::size_t)s, S.kfMp[(std::size_t)s]);
@@ -179,11 +180,15 @@ struct Device {
             const std::int32_t t = S.track[(std::size_t)r];
             if (t != -1 && !(t >= kTrackBase && t < kTrackBase + kWindow)) c.check(ms_dev_upload(c.get(), tracks.mpTrack() + r, &t, 4), "ms_dev_upload");
         }
-        std::vector<std::int32_t> kfIds(kKf);
-        for (int s = 0; s < kKf; ++s) kfIds[(std::size_t)s] = s < kKf - 1 ? 10 + s : -1;
-        observationCountsOnDevice(c, table, kfIds, nObs.data());
+        slots.id.resize(kKf);
+        for (int s = 0; s < kKf; ++s) slots.id[(std::size_t)s] = s < kKf - 1 ? 10 + s : -1;
+        observationCountsOnDevice(c, tables());
     }
-    FuseTables tables() { return FuseTables{table, flags, live, nObs.data(), &tracks}; }
+    MapTables tables() {
+        MapTables M{table, slots};
+        M.flags = &flags; M.points = &points; M.live = &live; M.tracks = &tracks; M.observationCount = nObs.data();
+        return M;
+    }
 };
 
 bool same_tables(Device &D, const Graph &G, const Scene &S, const char *what) {
@@ -219,7 +224,7 @@ bool same_lists(const FuseResult &got, const Graph &G, std::size_t from, const c
 }
 
 int no_gpu() {
-    std::printf("link ok %d\n", (int)(sizeof(FuseTables) > 0 && sizeof(FuseResult) > 0 && sizeof(FuseKeyframe) > 0));
+    std::printf("link ok %d\n", (int)(sizeof(MapTables) > 0 && sizeof(FuseResult) > 0 && sizeof(FuseKeyframe) > 0));
     char why[256];
     std::int32_t kf[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, nObs[4] = {0}, idx[4] = {0, 1, 2, 1}, kept[4] = {0}, top[16] = {0}, nKept[1] = {2}, out[10] = {0};
     std::uint8_t flags[4] = {0}, live[4] = {1, 1, 1, 1}, oc[2] = {0};
@@ -296,7 +301,7 @@ int gpu() {
     const std::vector<std::int32_t> setList(adjacentSet.begin(), adjacentSet.end());
     G.replaceDuplication(0, setList, candidates(0, setList, margin));
     Device D(ctx, S);
-    const FuseResult got = deduplicateMapPoints(ctx, D.points, D.tables(), keyframe(0), {keyframe(1), keyframe(2), keyframe(3), keyframe(4)}, margin, st);
+    const FuseResult got = deduplicateMapPoints(ctx, D.tables(), keyframe(0), {keyframe(1), keyframe(2), keyframe(3), keyframe(4)}, margin, st);
     if (!same_tables(D, G, S, "deduplicateMapPoints") || !same_lists(got, G, 0, "deduplicateMapPoints")) return 2;
     if (got.fusedCount != G.fused || G.fused < 40 || G.erasedRows.size() < 10 || changed < 1 || got.regates < 1) {
         std::printf("deduplicateMapPoints: fused %u against %u, %zu erased, %d list changes, %u regates\n", got.fusedCount, G.fused, G.erasedRows.size(), changed, got.regates);
@@ -313,7 +318,7 @@ int gpu() {
         const unsigned fusedBefore = G.fused;
         // the gates read positions only, which nothing here moves: `scratch` still serves
         for (int k : {4, 0}) G.replaceDuplication(k, list, candidates(k, list, 4.0f));
-        const FuseResult r = searchAndDeduplicate(ctx, D.points, D.tables(), {1, 2, 3}, {keyframe(4), keyframe(0)}, st);
+        const FuseResult r = searchAndDeduplicate(ctx, D.tables(), {1, 2, 3}, {keyframe(4), keyframe(0)}, st);
         if (!same_tables(D, G, S, "searchAndDeduplicate") || !same_lists(r, G, from, "searchAndDeduplicate") || r.fusedCount != G.fused - fusedBefore) return 3;
         std::printf("searchAndDeduplicate ok fused %u\n", r.fusedCount);
     }

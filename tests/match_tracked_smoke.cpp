@@ -73,7 +73,7 @@ struct Map {
     std::vector<std::vector<float>> x, y, depth;
     std::vector<std::vector<std::int32_t>> octave;
     std::vector<DeviceKeyframePoses::Pose> pose;
-    KeyframeCameras cams;
+    KeyframeSlots cams;                      // camera and focalLength; the view's id and descBase are kfId and descBase above
     std::vector<DeviceMapPoints::Vec3d> position;
     std::vector<DeviceMapPoints::Vec3f> norm;
     std::vector<float> minDist, maxDist;
@@ -210,8 +210,11 @@ int run(bool frameHasDescriptors) {
     // ---- the device path
     Tables dev(ctx, m);
     DeviceObservationLists lists(ctx, 4, 8);
-    const MatchTrackedResult got = matchTrackedFeatures(ctx, lists, dev.table, dev.points, dev.flags, dev.live, dev.tracks, keypoints, poses, m.cams, m.kfId, m.descBase, &pool, frame,
-                                                        m.freeRows, settings);
+    KeyframeSlots slots = m.cams;
+    slots.id = m.kfId; slots.descBase = m.descBase;
+    MapTables tables{dev.table, slots};
+    tables.flags = &dev.flags; tables.points = &dev.points; tables.live = &dev.live; tables.tracks = &dev.tracks; tables.keypoints = &keypoints; tables.poses = &poses; tables.pool = &pool; tables.lists = &lists;
+    const MatchTrackedResult got = matchTrackedFeatures(ctx, tables, frame, m.freeRows, settings);
 
     // ---- the restatement: std::maps, one keypoint after the other
     Tables ref(ctx, m);

@@ -128,7 +128,7 @@ struct Map {
     std::vector<std::vector<float>> x, y, depth;
     std::vector<std::vector<std::int32_t>> octave;
     std::vector<DeviceKeyframePoses::Pose> pose;
-    KeyframeCameras cams;
+    KeyframeSlots cams;                      // camera and focalLength; the view's id and descBase are kfId and descBase above
     std::vector<DeviceMapPoints::Vec3d> position;
     std::vector<std::uint8_t> flags;
     std::vector<KeyPoint::Descriptor> pool;
@@ -202,8 +202,12 @@ int gpu() {
     // ---- the device path: no per-point structure on the host
     Tables dev(ctx, m);
     DeviceObservationLists lists(ctx, 4, 8);                 // small on purpose: the first call regrows
-    const std::size_t refreshed = updateMapPoints(ctx, lists, dev.points, dev.flags, table, keypoints, poses, m.kfId, m.descBase, &pool, Map::current, minObservationsForBA, settings);
-    const TriangulateResult devTri = retriangulateCurrent(ctx, lists, dev.points, dev.flags, table, keypoints, poses, m.cams, m.kfId, Map::current, settings, TriangulationMethod::TME);
+    KeyframeSlots slots = m.cams;
+    slots.id = m.kfId; slots.descBase = m.descBase;
+    MapTables tables{table, slots};
+    tables.flags = &dev.flags; tables.points = &dev.points; tables.keypoints = &keypoints; tables.poses = &poses; tables.pool = &pool; tables.lists = &lists;
+    const std::size_t refreshed = updateMapPoints(ctx, tables, Map::current, minObservationsForBA, settings);
+    const TriangulateResult devTri = retriangulateCurrent(ctx, tables, Map::current, settings, TriangulationMethod::TME);
     const std::vector<std::int32_t> devRows = lists.download(lists.lists().rows, lists.rowCount());
 
     // ---- the restatement: std::map<KfId, KpId> observations per map point, built by walking the keyframes as addObservation does

@@ -65,7 +65,7 @@ struct Map {
     std::vector<std::vector<float>> x, y;
     std::vector<std::vector<std::int32_t>> octave;
     std::vector<DeviceKeyframePoses::Pose> pose;
-    KeyframeCameras cams;
+    KeyframeSlots cams;                      // camera and focalLength
     std::vector<DeviceMapPoints::Vec3d> position;
     std::vector<std::uint8_t> flags, live;
     PoseOdometryEdge edge;
@@ -117,15 +117,21 @@ struct Tables {
     DeviceMapPointLive live;
     DeviceKeypointTable kp;
     DeviceKeyframePoses poses;
+    KeyframeSlots slots;
     Tables(Context &ctx, const Map &m)
         : kf(ctx, Map::nKf, Map::stride, Map::nMp),
           points(ctx, m.position, std::vector<DeviceMapPoints::Vec3f>(Map::nMp, DeviceMapPoints::Vec3f{0, 0, 1}), std::vector<float>(Map::nMp, 0.f), std::vector<float>(Map::nMp, 0.f),
                  std::vector<KeyPoint::Descriptor>(Map::nMp, KeyPoint::Descriptor{})),
-          flags(ctx, m.flags), live(ctx, m.live), kp(ctx, Map::nKf, Map::stride), poses(ctx, m.pose) {
+          flags(ctx, m.flags), live(ctx, m.live), kp(ctx, Map::nKf, Map::stride), poses(ctx, m.pose), slots(m.cams) {
         for (int k = 0; k < Map::nKf; ++k) {
             kf.update((std::size_t)k, m.mapPoints[(std::size_t)k]);
             kp.update((std::size_t)k, m.x[(std::size_t)k], m.y[(std::size_t)k], m.octave[(std::size_t)k], {});
         }
+    }
+    MapTables view() {
+        MapTables M{kf, slots};
+        M.flags = &flags; M.points = &points; M.live = &live; M.keypoints = &kp; M.poses = &poses;
+        return M;
     }
 };
 
@@ -192,7 +198,7 @@ int with_gpu() {
     DevicePoseAdjuster adjuster(ctx, 320, settings);
     const Snapshot before = snapshot(ctx, t);
     auto run = [&](std::int32_t prevSlot) {
-        return poseBundleAdjustOnTables(ctx, adjuster, t.kf, t.flags, &t.live, t.points, t.kp, t.poses, m.cams, Map::frame, prevSlot, m.edge, params, settings);
+        return poseBundleAdjustOnTables(ctx, t.view(), adjuster, Map::frame, prevSlot, m.edge, params, settings);
     };
     // false: one point too few, and no previous keyframe; nothing is written
     params.minVisibleMapPointsInCurrentFrameBA = (unsigned)triangulated + 1;
@@ -221,7 +227,7 @@ int with_gpu() {
     if (same_pose(after.poses[Map::frame], before.poses[Map::frame])) return fail("the frame's pose did not move");
     // the whole stride instead of the frame's keypoint count gives the same problem: the entries behind the keypoints are -1
     t.poses.update(0, Map::nKf, before.poses.data());
-    if (!poseBundleAdjustOnTables(ctx, adjuster, t.kf, t.flags, &t.live, t.points, t.kp, t.poses, m.cams, Map::frame, Map::prev, m.edge, params, settings, (std::size_t)Map::nKp))
+    if (!poseBundleAdjustOnTables(ctx, t.view(), adjuster, Map::frame, Map::prev, m.edge, params, settings, (std::size_t)Map::nKp))
         return fail("did not run with the keypoint count given");
     if (std::memcmp(adjuster.last.pose, w.poses[0].data(), 7 * sizeof(double)) != 0) return fail("the pose with the keypoint count given");
     std::printf("poseBundleAdjustOnTables ok: %zu of %d keypoints, chi2 %.1f -> %.1f in %d iterations, both directions of the bool hold\n", triangulated, Map::nKp,

@@ -133,7 +133,7 @@ Graph graph_of(const Scene &S) {
 }
 
 int no_gpu() {
-    std::printf("link ok %d\n", (int)(sizeof(SearchBindResult) > 0 && sizeof(detail::BoundMaskSource) > 0 && sizeof(FuseTables) > 0));
+    std::printf("link ok %d\n", (int)(sizeof(SearchBindResult) > 0 && sizeof(detail::BoundMaskSource) > 0 && sizeof(MapTables) > 0));
     char why[256];
     std::int32_t kf[8] = {-1, 2, -1, -1, -1, -1, 0, -1}, nObs[4] = {1, 0, 1, 0}, idx[4] = {3, 1, 2, 9}, out[8] = {0};
     std::uint8_t live[4] = {1, 1, 1, 1}, skip[4] = {0};
@@ -178,9 +178,12 @@ int gpu() {
     DeviceMapPointLive live(ctx, S.live);
     DeviceArray<std::int32_t> nObs(ctx, kMp);
     for (int s = 0; s < kKf; ++s) table.update((std::size_t)s, S.kfMp[(std::size_t)s]);
-    std::vector<std::int32_t> kfIds(kKf);
-    for (int s = 0; s < kKf; ++s) kfIds[(std::size_t)s] = s < kKf - 1 ? 10 + s : -1;
-    observationCountsOnDevice(ctx, table, kfIds, nObs.data());
+    KeyframeSlots slots;
+    slots.id.resize(kKf);
+    for (int s = 0; s < kKf; ++s) slots.id[(std::size_t)s] = s < kKf - 1 ? 10 + s : -1;
+    MapTables tables{table, slots};
+    tables.flags = &flags; tables.points = &points; tables.live = &live; tables.observationCount = nObs.data();
+    observationCountsOnDevice(ctx, tables);
     const std::vector<std::int32_t> adjacent{0, 2, 3};
     const float threshold = 10.0f;
 
@@ -198,7 +201,7 @@ int gpu() {
     FuseKeyframe current;
     current.slot = kCurrent; current.features = &features; current.camera = kCam;
     std::copy(S.R, S.R + 9, current.R); std::copy(S.t, S.t + 3, current.t);
-    const SearchBindResult got = matchLocalMapPoints(ctx, points, FuseTables{table, flags, live, nObs.data(), nullptr}, current, adjacent, threshold, st, features.mutableUsable(), true);
+    const SearchBindResult got = matchLocalMapPoints(ctx, tables, current, adjacent, threshold, st, features.mutableUsable(), true);
 
     if (got.matched != wantMatched || wantMatched < 30 || list.size() < 100 || got.matchKp != std::vector<std::int32_t>(match.begin(), match.end())) {
         std::printf("matchLocalMapPoints: %u matches against %u over %zu rows\n", got.matched, wantMatched, list.size());
@@ -217,12 +220,12 @@ int gpu() {
     for (int j = 0; j < kKp; ++j)
         if ((usable[(std::size_t)j] != 0) != (G.keyframes[kCurrent][(std::size_t)j] == -1)) { std::printf("usable differs at keypoint %d\n", j); return 2; }
     // a second call finds the rows bound now excluded from the list and binds nothing twice
-    const SearchBindResult again = matchLocalMapPoints(ctx, points, FuseTables{table, flags, live, nObs.data(), nullptr}, current, adjacent, threshold, st);
+    const SearchBindResult again = matchLocalMapPoints(ctx, tables, current, adjacent, threshold, st);
     const std::vector<std::int32_t> kf2 = ctx.download(table.table(), (std::size_t)kKf * kStride);
     for (std::size_t i = 0; i < kf.size(); ++i) if (kf2[i] != kf[i] && kf[i] != -1) { std::printf("the second call moved a bound keypoint\n"); return 3; }
     std::printf("matchLocalMapPoints ok matched %u of %zu rows, rescans %d, then %u\n", got.matched, list.size(), got.counts[5], again.matched);
     // the empty list (:263)
-    const SearchBindResult none = matchLocalMapPoints(ctx, points, FuseTables{table, flags, live, nObs.data(), nullptr}, current, {4}, threshold, st);
+    const SearchBindResult none = matchLocalMapPoints(ctx, tables, current, {4}, threshold, st);
     if (none.matched != 0) return 4;
     std::printf("empty list ok\n");
     return 0;

@@ -109,7 +109,7 @@ int gpu(const char *path) {
     StaticSettings settings(p);
     std::vector<DeviceKeyframePoses::Pose> poses(nKf);
     for (auto &P : poses) for (double &v : P) v = in.d();
-    KeyframeCameras cams;
+    KeyframeSlots cams;
     for (std::size_t k = 0; k < nKf; ++k) {
         ms_pinhole c;
         c.fx = in.d(); c.fy = in.d(); c.cx = in.d(); c.cy = in.d(); c.width = (std::int32_t)in.d(); c.height = (std::int32_t)in.d();
