@@ -1659,6 +1659,59 @@ int ms_pose_tables_solve_check(const int32_t *kf_mp, int n_kf, int stride, const
     const ms_pose_tables_frame *frame, const ms_pose_tables_out *out, char *why, size_t why_bytes);
 int ms_pose_tables_problem(ms_pose_tables *h, double *pose, double *point, int32_t *obs_point, int32_t *obs_pose, double *obs_uv, double *obs_info, int32_t *n);
 
+/* ---- the end of a frame on the device map tables --------------------------------------------------------------------------
+ * What the mapper does with every frame after the pose adjustment: setPointCloudOutput (mapper_helpers.cpp:484-497, called at :1219-1221),
+ * the frame's result point cloud, and removeKeyframe (:375-431) for a frame that did not become a keyframe (:1223-1226) or for keyframes that
+ * dropped out of the odometry pose trail (:1172-1183).  The tables are those of 9.5 - 9.17: row r is PRESENT iff (uint32)r < n_mp and
+ * mp_live[r] != 0 (mp_live == NULL: every row is live); bit 0 of mp_flags is TRIANGULATED; a VALID entry is (uint32)r < n_mp (9.6).
+ * tests/frame_finish_ref.py restates the call and is its specification.
+ *
+ * Cloud (:484-497), the state BEFORE any removal of this call.  For keypoint j = 0 .. n_kp - 1 in ascending order, r = kf_mp[cloud_slot *
+ * stride + j] is kept iff r is PRESENT and mp_flags[r] & 1 -- ms_pose_tables_solve's gather predicate and order.  The k-th kept keypoint
+ * gives cloud_row[k] = r, cloud_kp[k] = j, cloud_track[k] = mp_track[r] (-1 with mp_track == NULL) and cloud_pos[3k ..] = mp_pos[r] bit for
+ * bit.  counts[0] = the number kept.  cloud_slot == -1: no cloud, counts[0] = 0.
+ *
+ * Removal (:375-431), the table part, for the slots of remove_slots in list order.  A REMAINING slot has kf_id >= 0 and is not in the list.
+ * For every row r a removed slot lists (valid entries), remain[r] = the number of valid entries equal to r in the remaining slots, with
+ * multiplicity (ms_observation_count's definition; a stale entry of a slot with kf_id < 0 does not count).  A LIVE row with remain[r] == 0 is
+ * removed as MapDB::removeMapPoint does, the way ms_map_cull does it: mp_live[r] = 0, mp_flags[r] = 0.  A row that is not live is never
+ * reported; its entries are erased like any other.  Every one of the `stride` entries of every removed slot becomes -1.  With n_obs != NULL,
+ * n_obs[r] = remain[r] for every row a removed slot lists (0 for a removed row); other rows are untouched, and the incoming n_obs is never
+ * read (ms_match_tracked leaves it stale).  removed_rows holds each removed row once, in first-claim order: the order of remove_slots, then
+ * keypoint index.  counts[1] = the number of removed rows, counts[2] = the number of valid entries erased.
+ * Left to the caller, as for ms_map_cull: the previous / next links, `uncertainty`, referenceKeyframe, bowIndex->remove and kf_id[slot] = -1;
+ * track_row needs no write (the presence rule of 9.11).
+ *
+ * MS_ERR_INVALID, nothing written, before any device call: cloud_slot outside [-1, n_kf) or with kf_id < 0; n_kp outside [0, stride]; a removed
+ * slot out of range, listed twice or with kf_id < 0; a non-negative kf_id listed twice; mp_live == NULL with n_remove > 0; stride < 1, a
+ * negative size, a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_remove: MS_COVIS_MAX_QUERIES), and when more rows are
+ * removed than cap_removed: then every table keeps its bits, counts holds the needed numbers and the cloud outputs are valid -- every verdict
+ * is taken before a table is written (the rule of ms_ba_window_apply).  n_remove == 0, cloud_slot == -1, n_mp == 0 and n_kp == 0 are fine.
+ * Per call: one upload block (the per-slot list positions and the list; none with n_remove == 0), at most six launches whatever the sizes (one
+ * with n_remove == 0, none when no cloud is wanted either), no host wait between them, ONE download (counts, cloud, removed rows) through the
+ * context's pinned block.  The cloud is launched first and so sees the tables before the removal.  Integer arithmetic decides every position
+ * and every atomic is an integer min or add: the same tables give the same bytes on every call.  Nothing is allocated after warm-up.
+ * ms_frame_finish_validate is the host validation alone (no context, no device; `why` receives the message). */
+typedef struct {
+    int32_t cloud_slot;      /* slot whose point cloud is wanted, -1 for none */
+    int32_t n_kp;            /* its keypoints, <= stride (pose_tables' rule) */
+} ms_frame_finish_args;
+int ms_frame_finish(ms_ctx *ctx,
+    /* DEVICE tables, updated in place; mp_live may be NULL iff n_remove == 0; mp_track, n_obs may be NULL */
+    int32_t *kf_mp, int n_kf, int stride, uint8_t *mp_flags, uint8_t *mp_live,
+    const double *mp_pos, const int32_t *mp_track, int32_t *n_obs, int n_mp,
+    /* HOST */
+    const int32_t *kf_id, const int32_t *remove_slots, int n_remove, const ms_frame_finish_args *args,
+    /* HOST outputs: cloud_* [n_kp] (each may be NULL), removed_rows [cap_removed], counts [3] */
+    int32_t *cloud_row, int32_t *cloud_kp, int32_t *cloud_track, double *cloud_pos,
+    int32_t *removed_rows, int cap_removed, int32_t *counts);
+/* the twin is named _validate: the set of ms_*_check functions is closed at 22 (tests/test_map_checks_corpus.py records them) */
+int ms_frame_finish_validate(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live,
+    const double *mp_pos, const int32_t *mp_track, const int32_t *n_obs, int n_mp,
+    const int32_t *kf_id, const int32_t *remove_slots, int n_remove, const ms_frame_finish_args *args,
+    const int32_t *cloud_row, const int32_t *cloud_kp, const int32_t *cloud_track, const double *cloud_pos,
+    const int32_t *removed_rows, int cap_removed, const int32_t *counts, char *why, size_t why_bytes);
+
 #ifdef __cplusplus
 }
 #endif

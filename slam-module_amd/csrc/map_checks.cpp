@@ -1,5 +1,5 @@
 // map_checks.cpp -- the host validation of every call on the device map tables: the 22 exported ms_*_check functions, in the order of
-// mi355slam.h.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
+// mi355slam.h, and ms_frame_finish_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
 // calls it with the context's error buffer.  Plain C++17, no HIP and no context: the checks read the HOST arguments only and ask of the DEVICE
 // arrays nothing but whether they are there, so this file compiles alone and runs under sanitizers (tests/map_checks_corpus.cpp).  The first
 // failing statement decides the message, so the order of the statements inside a function is part of the interface.
@@ -743,5 +743,36 @@ extern "C" int ms_pose_tables_solve_check(const int32_t *kf_mp, int n_kf, int st
     if (!std::isfinite(f->huber_delta)) INVALID("pose tables: huber_delta is not finite");
     if (f->max_iters < 0) INVALID("pose tables: max_iters %d", f->max_iters);
     if (ms_map_over_capacity(n_kf, stride, n_mp, 0)) return ms_why_table_caps("pose tables", n_kf, stride, n_mp, why, why_bytes);
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ frame_finish.hip
+// (named _validate, not _check: the header says why)
+extern "C" int ms_frame_finish_validate(const int32_t *kf_mp, int n_kf, int stride, const uint8_t *mp_flags, const uint8_t *mp_live, const double *mp_pos,
+                                        const int32_t *mp_track, const int32_t *n_obs, int n_mp, const int32_t *kf_id, const int32_t *remove_slots, int n_remove,
+                                        const ms_frame_finish_args *args, const int32_t *cloud_row, const int32_t *cloud_kp, const int32_t *cloud_track,
+                                        const double *cloud_pos, const int32_t *removed_rows, int cap_removed, const int32_t *counts, char *why, size_t why_bytes) {
+    (void)mp_track; (void)n_obs; (void)cloud_row; (void)cloud_kp; (void)cloud_track; (void)cloud_pos;      // each may be NULL
+    if (n_remove < 0 || cap_removed < 0) INVALID("frame finish: negative size (%d removed slots, capacity %d)", n_remove, cap_removed);
+    if (!args || !counts) INVALID("frame finish: missing array (args or counts)");
+    if (n_remove > 0 && !remove_slots) INVALID("frame finish: missing array (remove_slots)");
+    if (cap_removed > 0 && !removed_rows) INVALID("frame finish: missing array (removed_rows)");
+    int rc;
+    if ((rc = ms_kf_table_check("frame finish", kf_mp, n_kf, stride, n_mp, kf_id, why, why_bytes))) return rc;
+    if (n_mp > 0 && (!mp_flags || !mp_pos)) INVALID("frame finish: missing array (mp_flags or mp_pos)");
+    if (n_remove > 0 && !mp_live) INVALID("frame finish: mp_live == NULL with %d removed slots", n_remove);
+    if (args->cloud_slot < -1 || args->cloud_slot >= n_kf) INVALID("frame finish: cloud slot %d outside [-1, %d)", args->cloud_slot, n_kf);
+    if (args->cloud_slot >= 0 && kf_id[args->cloud_slot] < 0) INVALID("frame finish: cloud slot %d is empty (kf_id %d)", args->cloud_slot, kf_id[args->cloud_slot]);
+    if (args->n_kp < 0 || args->n_kp > stride) INVALID("frame finish: %d keypoints in a table of stride %d", args->n_kp, stride);
+    if (n_remove > MS_COVIS_MAX_QUERIES || ms_map_over_capacity(n_kf, stride, n_mp, 0))
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "frame finish: %d slots / stride %d / %d map points / %d removed slots, caps %d / %d / below %d / %d", n_kf, stride, n_mp,
+                      n_remove, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_QUERIES);
+    int bad = 0;
+    if (!ms_distinct_in_range(remove_slots, n_remove, n_kf, &bad)) {
+        if (bad < 0) INVALID("frame finish: removed slot %d is listed twice", -1 - bad);
+        INVALID("frame finish: removed slot %d outside [0, %d)", remove_slots[bad], n_kf);
+    }
+    for (int i = 0; i < n_remove; ++i)
+        if (kf_id[remove_slots[i]] < 0) INVALID("frame finish: removed slot %d is empty (kf_id %d)", remove_slots[i], kf_id[remove_slots[i]]);
     return MS_OK;
 }

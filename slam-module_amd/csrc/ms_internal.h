@@ -30,6 +30,7 @@ enum MsWorkspaceId {
     MS_WS_BA_WINDOW,        // ms_ba_window_lists and ms_ba_window_apply (ba_window.hip): device pose index / cameras / results in; block counts / marks / the block that goes down
     MS_WS_SEARCH_BIND,      // ms_search_bind (search_bind.hip): device slice of mp_index / results / row marks
     MS_WS_LOOP_CHAIN,       // ms_loop_usable_mask, ms_loop_pairs and ms_loop_sim3_lists (loop_chain.hip): device slot / candidate records, sigmas, match lists; counts; the block that goes down
+    MS_WS_FRAME_FINISH,     // ms_frame_finish (frame_finish.hip): device list positions / list; first claims / remaining entries / block counts; the block that goes down
     MS_WS_COUNT
 };
 

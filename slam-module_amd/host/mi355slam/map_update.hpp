@@ -2,7 +2,8 @@
 // loop correction (correctLoop), triangulation (triangulateMapPoints), covisibility (getNeighbors, computeAdjacentKeyframes, localMapPoints),
 // culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
 // fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), matchLocalMapPoints, createNewMapPoints and the local
-// bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables).
+// bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables), the per-frame pose
+// adjustment (poseBundleAdjustOnTables) and the end of a frame (finishFrame, removeKeyframes).
 // Results come back through Context::workspace and Context::download; nothing here owns device memory.
 #pragma once
 #include <algorithm>
@@ -691,6 +692,71 @@ inline bool poseBundleAdjustOnTables(Context &ctx, MapTables M, DevicePoseAdjust
     ctx.check(ms_pose_tables_solve(handle.get(), M.keyframes.table(), (int)nKf, (int)M.keyframes.stride(), M.flags->flags(), M.live ? M.live->live() : nullptr, M.points->position(),
                                    (int)nMp, M.keypoints->x(), M.keypoints->y(), M.keypoints->octave(), M.poses->pose(), &f, &handle.last, nullptr), "ms_pose_tables_solve");
     return handle.last.ran != 0;
+}
+
+// ---- the end of a frame on the device tables (ms_frame_finish) ---------------------------------------------------------------------------
+// The frame's result point cloud (setPointCloudOutput, mapper_helpers.cpp:484-497: table row, keypoint, trackId, position of every keypoint
+// whose map point is TRIANGULATED, in keypoint order) and what the host side of the map still has to do after removeKeyframe (:375-431):
+// the removed map points in first-claim order -- trackIdToMapPoint.erase and the host copies -- and the removed keyframes' links as they
+// were before -- bowIndex->remove, the `uncertainty` accumulation onto the next keyframe, re-pointing referenceKeyframe to the previous one.
+struct FrameFinish {
+    std::vector<std::int32_t> cloudRows, cloudKeyPoints, cloudTracks;
+    std::vector<double> cloudPositions;
+    std::vector<std::int32_t> removedRows, removedPrevious, removedNext;
+    std::size_t erasedObservations = 0;
+};
+
+namespace detail {
+// ONE ms_frame_finish call: the cloud of cloudSlot (-1: none), then the removal of `slots`.  Writes M.keyframes, M.flags, M.live and, when given,
+// M.observationCount; relinks M.slots.previous / next in list order and empties the removed slots' ids, as cullMap does.
+inline FrameFinish finish_frame(Context &ctx, MapTables &M, const char *who, std::int32_t cloudSlot, std::size_t nKeyPoints, const std::vector<std::int32_t> &slots,
+                                const std::vector<std::int32_t> &loopClosureKeyframes) {
+    M.require(who, M.POINTS | M.FLAGS | M.LIVE | M.LINKS | M.IDS);
+    KeyframeSlots &chain = M.slots;
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount(), stride = M.keyframes.stride();
+    for (std::int32_t k : slots) {
+        if (k < 0 || (std::size_t)k >= nKf) throw std::invalid_argument(std::string(who) + ": slot " + std::to_string(k) + " outside the table");
+        if (chain.previous[k] < 0) throw std::invalid_argument(std::string(who) + ": slot " + std::to_string(k) + " has no previous keyframe (cannot delete the first keyframe)");      // :392
+        if (std::find(loopClosureKeyframes.begin(), loopClosureKeyframes.end(), k) != loopClosureKeyframes.end())
+            throw std::invalid_argument(std::string(who) + ": slot " + std::to_string(k) + " is named by a loop-closure edge");                                                  // :382-385
+    }
+    const ms_frame_finish_args args{cloudSlot, (std::int32_t)std::min(nKeyPoints, stride)};
+    const std::size_t nCloud = cloudSlot >= 0 ? (std::size_t)args.n_kp : 0, cap = std::min(nMp, slots.size() * stride);
+    FrameFinish out;
+    out.cloudRows.resize(nCloud); out.cloudKeyPoints.resize(nCloud); out.cloudTracks.resize(nCloud); out.cloudPositions.resize(3 * nCloud); out.removedRows.resize(cap);
+    std::int32_t counts[3] = {0, 0, 0};
+    ctx.check(ms_frame_finish(ctx.get(), M.keyframes.mutableTable(), (int)nKf, (int)stride, M.flags->mutableFlags(), M.live->mutableLive(), M.points->position(),
+                              M.tracks ? M.tracks->mpTrack() : nullptr, M.observationCount, (int)nMp, chain.id.data(), slots.data(), (int)slots.size(), &args,
+                              out.cloudRows.data(), out.cloudKeyPoints.data(), out.cloudTracks.data(), out.cloudPositions.data(), out.removedRows.data(), (int)cap, counts),
+              "ms_frame_finish");
+    out.cloudRows.resize((std::size_t)counts[0]); out.cloudKeyPoints.resize((std::size_t)counts[0]); out.cloudTracks.resize((std::size_t)counts[0]);
+    out.cloudPositions.resize(3 * (std::size_t)counts[0]); out.removedRows.resize((std::size_t)counts[1]);
+    out.erasedObservations = (std::size_t)counts[2];
+    for (std::int32_t k : slots) {                           // :414-420, in list order
+        const std::int32_t prev = chain.previous[k], next = chain.next[k];
+        out.removedPrevious.push_back(prev); out.removedNext.push_back(next);
+        if (next != -1) chain.previous[next] = prev;
+        if (prev != -1) chain.next[prev] = next;
+        chain.previous[k] = chain.next[k] = -1;
+        chain.id[k] = -1;
+    }
+    return out;
+}
+}  // namespace detail
+
+// The end of addKeyframe, mapper_helpers.cpp:1216-1230, for the frame in `slot`: its point cloud from the tables as they are, then, iff it did
+// not become a keyframe, removeKeyframe (:375-431) on the tables -- one device call, nothing of the map walked on the host.  Throws
+// std::invalid_argument before any device call when the frame is to be removed and has no previous keyframe (:392) or is named by a
+// loop-closure edge (loopClosureKeyframes: slots, :382-385).  M.tracks may be null (cloudTracks = -1), M.observationCount is kept current when given.
+inline FrameFinish finishFrame(Context &ctx, MapTables M, std::int32_t slot, std::size_t nKeyPoints, bool keyframeDecision, const std::vector<std::int32_t> &loopClosureKeyframes) {
+    const std::vector<std::int32_t> slots = keyframeDecision ? std::vector<std::int32_t>{} : std::vector<std::int32_t>{slot};
+    return detail::finish_frame(ctx, M, "finishFrame", slot, nKeyPoints, slots, loopClosureKeyframes);
+}
+
+// removeKeyframe (:375-431) for a list of keyframes, in list order: the keyframes that dropped out of the odometry pose trail (:1172-1183).
+// One device call; no cloud.  The same two refusals as finishFrame, for every slot of the list, before any device call.
+inline FrameFinish removeKeyframes(Context &ctx, MapTables M, const std::vector<std::int32_t> &slots, const std::vector<std::int32_t> &loopClosureKeyframes) {
+    return detail::finish_frame(ctx, M, "removeKeyframes", -1, 0, slots, loopClosureKeyframes);
 }
 
 // ---- fusing duplicate map points on the device tables (ms_map_fuse, ms_map_replace_pairs) ----------------------------------------------

@@ -1282,6 +1282,26 @@ def _download_i32(buf, shape):
     return buf.download(np.int32, shape) if shape[0] * shape[1] else np.zeros(shape, np.int32)
 
 
+class FrameFinishArgsC(C.Structure):
+    """ms_frame_finish_args"""
+    _fields_ = [("cloud_slot", C.c_int32), ("n_kp", C.c_int32)]
+
+
+FRAME_FINISH_ARRAYS = ("kf_mp", "mp_flags", "mp_live", "mp_pos", "mp_track", "n_obs", "kf_id", "remove_slots", "cloud_row", "cloud_kp", "cloud_track", "cloud_pos",
+                       "removed_rows", "counts")
+
+
+def frame_finish_validate(arrays, n_kf, stride, n_mp, n_remove, cloud_slot, n_kp, cap_removed, args=True):
+    """ms_frame_finish_validate, the host half of ms_frame_finish (no context, no device).  arrays: a dict of the names in FRAME_FINISH_ARRAYS
+    (numpy arrays, DevBufs or None; only kf_id and remove_slots are read); args=False passes no ms_frame_finish_args.  Returns (rc, message)."""
+    p = lambda k: _vp(arrays.get(k))
+    A, why = FrameFinishArgsC(int(cloud_slot), int(n_kp)), C.create_string_buffer(512)
+    rc = lib().ms_frame_finish_validate(p("kf_mp"), int(n_kf), int(stride), p("mp_flags"), p("mp_live"), p("mp_pos"), p("mp_track"), p("n_obs"), int(n_mp), p("kf_id"),
+                                        p("remove_slots"), int(n_remove), C.byref(A) if args else None, p("cloud_row"), p("cloud_kp"), p("cloud_track"), p("cloud_pos"),
+                                        p("removed_rows"), int(cap_removed), p("counts"), why, C.c_size_t(512))
+    return rc, why.value.decode()
+
+
 class KeyframeTable:
     """Keyframe::mapPoints of every keyframe on the device: kf_mp [n_kf, stride] int32, entry (k, j) = the map-point table row bound to
     keypoint j of the keyframe in slot k, -1 for none.  The queries take n_mp (rows of the map-point table; an entry outside [0, n_mp)
@@ -1435,6 +1455,33 @@ class KeyframeTable:
             for b in (d_n, d_rows, d_why, own_f, own_l):
                 if b is not None:
                     b.free()
+        return out
+
+    def frame_finish_device(self, flags, live, table, tracks, n_obs, kf_id, remove_slots, cloud_slot, n_kp, cap_removed=None):
+        """ms_frame_finish on this table in place, without raising: flags / live DevBufs of [n_mp] uint8 (live may be None when nothing is
+        removed), table a MapPointTable, tracks a DevBuf of mp_track [n_mp] int32 or None, n_obs a DevBuf of [n_mp] int32 or None.  Returns
+        (rc, dict(cloud_row, cloud_kp, cloud_track, cloud_pos [n, 3], removed_rows, counts [3])); removed_rows is empty when rc != 0."""
+        kf_id, remove_slots = _i32(kf_id), _i32(remove_slots)
+        if len(kf_id) != self.n_kf:
+            raise ValueError("kf_id describes %d slots, the table has %d" % (len(kf_id), self.n_kf))
+        n_mp = table.n
+        cap = int(min(n_mp, len(remove_slots) * self.stride) if cap_removed is None else cap_removed)
+        n = max(int(n_kp), 1)
+        row, kp, track, pos = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3))
+        removed, counts = np.zeros(max(cap, 1), np.int32), np.zeros(3, np.int32)
+        A = FrameFinishArgsC(int(cloud_slot), int(n_kp))
+        rc = lib().ms_frame_finish(self.ctx._h, _vp(self.kf_mp), self.n_kf, self.stride, _vp(flags), _vp(live), _vp(table.pos), _vp(tracks), _vp(n_obs), n_mp, _vp(kf_id),
+                                   _vp(remove_slots), len(remove_slots), C.byref(A), _vp(row), _vp(kp), _vp(track), _vp(pos), _vp(removed), cap, _vp(counts))
+        k = int(counts[0])
+        return rc, dict(cloud_row=row[:k].copy(), cloud_kp=kp[:k].copy(), cloud_track=track[:k].copy(), cloud_pos=pos[:k].copy(),
+                        removed_rows=removed[:int(counts[1]) if rc == 0 else 0].copy(), counts=counts)
+
+    def frame_finish(self, flags, live, table, tracks, n_obs, kf_id, remove_slots, cloud_slot, n_kp, cap_removed=None):
+        """The end of a frame (mapper_helpers.cpp:1216-1230, :1172-1183): setPointCloudOutput of cloud_slot (-1: none) on the tables as they
+        are, then the table part of removeKeyframe for remove_slots (ms_frame_finish).  cap_removed None: room for every row that can be
+        removed.  Returns frame_finish_device's dict; raises MsError on an error."""
+        rc, out = self.frame_finish_device(flags, live, table, tracks, n_obs, kf_id, remove_slots, cloud_slot, n_kp, cap_removed)
+        self.ctx.check(rc, "ms_frame_finish")
         return out
 
     def _fuse_tables(self, tables, n_mp):
