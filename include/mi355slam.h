@@ -1712,6 +1712,97 @@ int ms_frame_finish_validate(const int32_t *kf_mp, int n_kf, int stride, const u
     const int32_t *cloud_row, const int32_t *cloud_kp, const int32_t *cloud_track, const double *cloud_pos,
     const int32_t *removed_rows, int cap_removed, const int32_t *counts, char *why, size_t why_bytes);
 
+/* ---- a new keyframe from the extractor's output to the map tables ----------------------------------------------------------
+ * Keyframe::addFullFeatures / processKeyPoints (keyframe.cpp:34-116, called at mapper_helpers.cpp:1186-1203) without the host in between:
+ * ms_keyframe_admit puts frame `frame` of a DEVICE ms_keypoints view (ms_orb_device_view, or any SoA of device arrays, as ms_keypoints_pack
+ * accepts) into slot `slot` of the tables of 9.4 - 9.18 and completes the DEVICE arrays of an ms_match_frame and of FeatureSearch::create.
+ * n = view->count[frame] is read ON THE DEVICE; the host learns it with the results.  tests/keyframe_admit_ref.py restates the call and is
+ * its specification.
+ *
+ * Written for j < n:
+ *   keypoint table, entry slot * stride + j: kp_x, kp_y, kp_octave copied bit for bit; entries j >= n keep their bytes
+ *   kp_depth (keyframe.cpp:55-64): depth = -1; with view->track_id[j] >= 0 and track_ids given, depth = track_depth[i], i the LAST index with
+ *     track_ids[i] == the id (trackIdToIndex[id] = idx overwrites); then, iff depth < 0 as written (a NaN stays), the sample of depth_image at
+ *     (__float2int_rn(x), __float2int_rn(y)) -- the rounding of the valid mask in ms_orb_set_valid_mask -- or -1 outside the image or with no
+ *     image.  The image is a stand-in for frame->getDepth, which belongs to the external image class, as the valid mask stands in for
+ *     tracker::Camera::isValidPixel
+ *   desc_pool[(desc_base + j) * 8 ..]: the descriptor
+ *   out->desc, angle, octave copied; out->bearing = the unit vector of ((x - cx) / fx, (y - cy) / fy, 1) in float64 without contraction, the
+ *     stand-in of 9.7 (one device function, shared with ms_triangulate); out->usable[j] = 1, what ms_unbound_mask gives for the cleared row
+ *   out->sorted_x / sorted_y / sorted_idx: FeatureSearch::create by ms_feature_search_sort's rule.  The position of j is the number of k with
+ *     y[k] < y[j] || (y[k] == y[j] && k < j): integer ranks, no atomics
+ *   out->node_id / node_start / kp_idx with a vocabulary: the descent of ms_bow_transform on the view's descriptors where they lie, then the
+ *     keypoints with weight > 0 (DBoW2's rule) ranked by (node, index) -- the ms_bow of a FeatureVector.  Without a vocabulary n_nodes = 0.
+ * Written per slot: kf_mp[slot * stride + j] = -1 for ALL stride entries; kf_pose[slot] = pose (it travels as a kernel argument).
+ * HOST outputs (ms_admit_host, the struct and each member may be NULL; each array holds cap_kp elements), one download through the context's
+ * pinned block: kp_track = keyPointTrackIds, what ms_match_tracked takes next; word, weight of the descent (-1 and 0 without a vocabulary)
+ * for the host's BowVector, whose floating-point sums stay in feature order on the host; sorted_x, sorted_y, sorted_idx, octave, desc: the
+ * host copies a keyframe record keeps.  counts (HOST [3]) = n, n_nodes, the keypoints in the node lists.
+ *
+ * Every verdict is taken before any write: a first pass counts into the head of the block that goes down, and the writing kernels return at
+ * once when it is non-zero.  MS_ERR_CAPACITY with the needed n in counts[0] when n > stride, n > cap_kp or desc_base + n > n_pool.
+ * MS_ERR_INVALID for n outside [0, view->capacity], a non-finite x or y among the first n (ranks would collide), a VALID entry
+ * ((uint32)r < n_mp, ms_match_tracked's rule) already in the slot's row, a tracked keypoint whose id is not in track_ids when track_ids is
+ * given (the reference's .at throws).  In every such case each table and frame array keeps its bytes.  Before any device call
+ * (ms_keyframe_admit_validate, the host validation alone: no context, no device; `why` receives the message): MS_ERR_INVALID for slot, frame
+ * or desc_base out of range, descriptor arrays that are not 16-byte aligned, stride < 1, a non-finite pose or camera, a depth image without
+ * a size, a missing array; MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_tracks, cap_kp and view->capacity: MS_COVIS_MAX_STRIDE).
+ * FOUR launches whatever the sizes (descent and head; verdicts; ranks and every write; node lists), at most one upload block (the track
+ * lists; none without them), ONE download, one host wait.  Synchronous on the context stream, behind ms_orb_extract.  The workspace belongs
+ * to the context and only grows: nothing is allocated after warm-up (ms_debug_host_allocs).  The same inputs give the same bytes on every
+ * call.  Not covered: the keypoints of frames that are no keyframe (addTrackerFeatures: host data of the tracker), colours (getPixel),
+ * the BowVector itself (ms_bow_db_add takes host arrays), reuse of pool space when keyframes leave. */
+typedef struct {
+    int32_t slot;                        /* the keyframe's slot in kf_mp, the keypoint table and kf_pose */
+    int32_t desc_base;                   /* index of keypoint 0 in desc_pool */
+    double pose[12];                     /* rows 0-2 of poseCW, row-major */
+    ms_pinhole cam;
+    int32_t levels_up;                   /* of the descent (4 in the reference); read with a vocabulary only */
+    const ms_bow_vocab *vocab;           /* may be NULL */
+    const int32_t *track_ids;            /* HOST [n_tracks] the tracker features' ids, may be NULL */
+    const float *track_depth;            /* HOST [n_tracks] their depth */
+    int32_t n_tracks;
+    const float *depth_image;            /* DEVICE float32, may be NULL */
+    int32_t depth_width, depth_height, depth_stride;     /* row stride in elements */
+} ms_admit_args;
+typedef struct {                         /* DEVICE arrays of one keyframe */
+    int32_t cap_kp;
+    uint32_t *desc;                      /* [cap * 8] */
+    float *angle;                        /* [cap] */
+    int32_t *octave;                     /* [cap] */
+    double *bearing;                     /* [cap * 3] */
+    uint8_t *usable;                     /* [cap] */
+    float *sorted_x, *sorted_y;          /* [cap] */
+    int32_t *sorted_idx;                 /* [cap] */
+    int32_t *node_id;                    /* [cap] */
+    int32_t *node_start;                 /* [cap + 1] */
+    int32_t *kp_idx;                     /* [cap] */
+} ms_admit_frame;
+typedef struct {                         /* HOST outputs, [cap_kp] each, each may be NULL */
+    int32_t *kp_track;
+    int32_t *word;
+    double *weight;
+    float *sorted_x, *sorted_y;
+    int32_t *sorted_idx;
+    int32_t *octave;
+    uint32_t *desc;                      /* [cap_kp * 8] */
+} ms_admit_host;
+int ms_keyframe_admit(ms_ctx *ctx,
+    /* HOST struct of DEVICE arrays */
+    const ms_keypoints *view, int frame,
+    /* DEVICE tables, updated in place */
+    int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    float *kp_x, float *kp_y, int32_t *kp_octave, float *kp_depth,
+    uint32_t *desc_pool, int n_pool, double *kf_pose,
+    /* HOST */
+    const ms_admit_args *args, const ms_admit_frame *out, const ms_admit_host *host, int32_t *counts);
+/* the twin is named _validate: the set of ms_*_check functions is closed at 22 (tests/test_map_checks_corpus.py records them) */
+int ms_keyframe_admit_validate(const ms_keypoints *view, int frame,
+    const int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth,
+    const uint32_t *desc_pool, int n_pool, const double *kf_pose,
+    const ms_admit_args *args, const ms_admit_frame *out, const ms_admit_host *host, const int32_t *counts, char *why, size_t why_bytes);
+
 #ifdef __cplusplus
 }
 #endif

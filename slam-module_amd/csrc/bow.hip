@@ -9,77 +9,17 @@
 // The word/weight/node triple per descriptor is all the device produces; the two std::maps (BowVector with its L1
 // normalisation, FeatureVector) are assembled from it by the host mirror in feature order, which keeps the floating-point sums
 // identical to the reference's.
-#include "ms_internal.h"
+#include "bow_descend.h"      // BowTree and ms_bow_vocab are in ms_internal.h, the walk in bow_descend.h: keyframe_admit.hip runs the same descent
 
 namespace {
 
-struct BowTree {
-    const int32_t *first_child;    // [n] internal index of the first child (children are contiguous)
-    const int32_t *n_children;     // [n]
-    const uint4 *desc;             // [n][2]
-    const int32_t *orig_id;        // [n] node id of the caller's numbering
-    const int32_t *word;           // [n] word id (-1 for inner nodes)
-    const double *weight;          // [n]
-    int depth_levels, max_depth;
-};
-
-__device__ __forceinline__ uint32_t group_min16(uint32_t v) {      // min over each row of 16 lanes, result in every lane
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x121 /*row_ror:1*/, 0xf, 0xf, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x122 /*row_ror:2*/, 0xf, 0xf, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x124 /*row_ror:4*/, 0xf, 0xf, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x128 /*row_ror:8*/, 0xf, 0xf, false));
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_bow_descend(BowTree T, const uint4 *__restrict__ desc, int n, int levels_up,
                                                      int32_t *__restrict__ out_word, double *__restrict__ out_weight, int32_t *__restrict__ out_node) {
-    const int i = blockIdx.x * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;
-    const bool live = i < n;
-    uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
-    if (live) { q0 = desc[2 * (size_t)i]; q1 = desc[2 * (size_t)i + 1]; }
-    const int nid_level = T.depth_levels - levels_up;
-    int cur = 0, level = 0, nid = nid_level <= 0 ? 0 : -1;
-    int nc = live ? T.n_children[0] : 0;
-    const bool empty = nc == 0;
-    // every group walks until its node has no children; max_depth bounds the loop for any tree the host accepted
-    for (int step = 0; step < T.max_depth && __ballot(nc > 0) != 0; ++step) {
-        if (nc > 0) {
-            const int first = T.first_child[cur];
-            uint32_t best = 0xFFFFFFFFu;
-            for (int c0 = 0; c0 < nc; c0 += 16) {
-                const int c = c0 + sub;
-                uint32_t key = 0xFFFFFFFFu;
-                if (c < nc) {
-                    const uint4 a = T.desc[2 * (size_t)(first + c)], b = T.desc[2 * (size_t)(first + c) + 1];
-                    const uint32_t d = __popc(a.x ^ q0.x) + __popc(a.y ^ q0.y) + __popc(a.z ^ q0.z) + __popc(a.w ^ q0.w) +
-                                       __popc(b.x ^ q1.x) + __popc(b.y ^ q1.y) + __popc(b.z ^ q1.z) + __popc(b.w ^ q1.w);
-                    key = (d << 16) | (uint32_t)c;
-                }
-                best = min(best, key);
-            }
-            best = group_min16(best);
-            cur = first + (int)(best & 0xFFFFu);
-            ++level;
-            if (level == nid_level) nid = cur;
-            nc = T.n_children[cur];
-        }
-    }
-    if (live && sub == 0) {
-        if (empty) { out_word[i] = -1; if (out_weight) out_weight[i] = 0.0; if (out_node) out_node[i] = 0; return; }
-        out_word[i] = T.word[cur];
-        if (out_weight) out_weight[i] = T.weight[cur];
-        if (out_node) out_node[i] = nid < 0 ? T.orig_id[cur] : (nid == 0 ? 0 : T.orig_id[nid]);
-    }
+    const int i = blockIdx.x * 16 + (threadIdx.x >> 4);
+    bow_descend(T, desc, i, i < n, levels_up, out_word, out_weight, out_node);
 }
 
 }  // namespace
-
-struct ms_bow_vocab {
-    ms_ctx *ctx = nullptr;
-    void *slab = nullptr;
-    BowTree tree{};
-    int n_nodes = 0, max_children = 0;
-};
 
 extern "C" {
 

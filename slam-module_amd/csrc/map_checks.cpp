@@ -1,5 +1,5 @@
 // map_checks.cpp -- the host validation of every call on the device map tables: the 22 exported ms_*_check functions, in the order of
-// mi355slam.h, and ms_frame_finish_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
+// mi355slam.h, and ms_frame_finish_validate and ms_keyframe_admit_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
 // calls it with the context's error buffer.  Plain C++17, no HIP and no context: the checks read the HOST arguments only and ask of the DEVICE
 // arrays nothing but whether they are there, so this file compiles alone and runs under sanitizers (tests/map_checks_corpus.cpp).  The first
 // failing statement decides the message, so the order of the statements inside a function is part of the interface.
@@ -774,5 +774,48 @@ extern "C" int ms_frame_finish_validate(const int32_t *kf_mp, int n_kf, int stri
     }
     for (int i = 0; i < n_remove; ++i)
         if (kf_id[remove_slots[i]] < 0) INVALID("frame finish: removed slot %d is empty (kf_id %d)", remove_slots[i], kf_id[remove_slots[i]]);
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ keyframe_admit.hip
+// (named _validate, not _check: the header says why)
+extern "C" int ms_keyframe_admit_validate(const ms_keypoints *view, int frame, const int32_t *kf_mp, int n_kf, int stride, int n_mp, const float *kp_x, const float *kp_y,
+                                          const int32_t *kp_octave, const float *kp_depth, const uint32_t *desc_pool, int n_pool, const double *kf_pose,
+                                          const ms_admit_args *args, const ms_admit_frame *out, const ms_admit_host *host, const int32_t *counts, char *why,
+                                          size_t why_bytes) {
+    (void)host;                                              // the struct and each member may be NULL
+    if (n_kf < 0 || n_mp < 0 || n_pool < 0) INVALID("keyframe admit: negative size (%d slots, %d map points, %d pool entries)", n_kf, n_mp, n_pool);
+    if (stride < 1) return ms_why_stride("keyframe admit", stride, why, why_bytes);
+    if (!view || !args || !out || !counts) INVALID("keyframe admit: missing array (view, args, out or counts)");
+    if (!view->count || !view->x || !view->y || !view->angle || !view->octave || !view->desc || !view->track_id)
+        INVALID("keyframe admit: missing array (count, x, y, angle, octave, desc or track_id of the view)");
+    if (!kf_mp || !kp_x || !kp_y || !kp_octave || !kp_depth || !desc_pool || !kf_pose)
+        INVALID("keyframe admit: missing array (kf_mp, the keypoint table, desc_pool or kf_pose)");
+    if (!out->desc || !out->angle || !out->octave || !out->bearing || !out->usable || !out->sorted_x || !out->sorted_y || !out->sorted_idx || !out->node_id ||
+        !out->node_start || !out->kp_idx)
+        INVALID("keyframe admit: missing array (a frame array of out)");
+    if (view->capacity < 0 || out->cap_kp < 0 || args->n_tracks < 0)
+        INVALID("keyframe admit: negative size (view capacity %d, cap_kp %d, %d tracks)", view->capacity, out->cap_kp, args->n_tracks);
+    if (frame < 0 || frame >= MS_COVIS_MAX_KF) INVALID("keyframe admit: frame %d outside [0, %d)", frame, MS_COVIS_MAX_KF);
+    if (args->slot < 0 || args->slot >= n_kf) INVALID("keyframe admit: slot %d outside [0, %d)", args->slot, n_kf);
+    if (args->desc_base < 0 || args->desc_base > n_pool) INVALID("keyframe admit: desc_base %d outside [0, %d]", args->desc_base, n_pool);
+    if ((reinterpret_cast<uintptr_t>(view->desc) | reinterpret_cast<uintptr_t>(desc_pool) | reinterpret_cast<uintptr_t>(out->desc)) & 15u)
+        INVALID("keyframe admit: descriptor arrays must be 16-byte aligned");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(args->pose[i])) INVALID("keyframe admit: pose[%d] is not finite", i);
+    const ms_pinhole &K = args->cam;
+    if (!(K.fx > 0.0) || !(K.fy > 0.0) || !std::isfinite(K.fx) || !std::isfinite(K.fy) || !std::isfinite(K.cx) || !std::isfinite(K.cy))
+        INVALID("keyframe admit: bad camera (fx %g, fy %g, cx %g, cy %g)", K.fx, K.fy, K.cx, K.cy);
+    if (args->vocab && args->levels_up < 0) INVALID("keyframe admit: levels_up %d", args->levels_up);
+    if ((args->track_ids == nullptr) != (args->track_depth == nullptr)) INVALID("keyframe admit: missing array (track_ids or track_depth)");
+    if (args->n_tracks > 0 && !args->track_ids) INVALID("keyframe admit: missing array (track_ids with %d tracks)", args->n_tracks);
+    if (args->depth_image && (args->depth_width < 1 || args->depth_height < 1 || args->depth_stride < args->depth_width))
+        INVALID("keyframe admit: a depth image of %d x %d, row stride %d", args->depth_width, args->depth_height, args->depth_stride);
+    if (view->capacity > MS_COVIS_MAX_STRIDE || out->cap_kp > MS_COVIS_MAX_STRIDE || args->n_tracks > MS_COVIS_MAX_STRIDE)
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "keyframe admit: view capacity %d / cap_kp %d / %d tracks, caps %d each", view->capacity, out->cap_kp, args->n_tracks,
+                      MS_COVIS_MAX_STRIDE);
+    if (args->depth_image && ((long long)args->depth_stride * args->depth_height > 0x7fffffffLL))
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "keyframe admit: a depth image of %d rows of %d elements, caps below 2^31 elements", args->depth_height, args->depth_stride);
+    if (ms_map_over_capacity(n_kf, stride, n_mp, 0)) return ms_why_table_caps("keyframe admit", n_kf, stride, n_mp, why, why_bytes);
     return MS_OK;
 }

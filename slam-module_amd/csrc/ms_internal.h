@@ -31,7 +31,26 @@ enum MsWorkspaceId {
     MS_WS_SEARCH_BIND,      // ms_search_bind (search_bind.hip): device slice of mp_index / results / row marks
     MS_WS_LOOP_CHAIN,       // ms_loop_usable_mask, ms_loop_pairs and ms_loop_sim3_lists (loop_chain.hip): device slot / candidate records, sigmas, match lists; counts; the block that goes down
     MS_WS_FRAME_FINISH,     // ms_frame_finish (frame_finish.hip): device list positions / list; first claims / remaining entries / block counts; the block that goes down
+    MS_WS_KEYFRAME_ADMIT,   // ms_keyframe_admit (keyframe_admit.hip): device track ids / depths; word / weight / node / track index / sorted nodes; the block that goes down
     MS_WS_COUNT
+};
+
+// The vocabulary tree as ms_bow_vocab_create lays it out on the device (bow.hip): breadth-first, every node's children adjacent.  The walk is
+// bow_descend.h's; bow.hip and keyframe_admit.hip run it.
+struct BowTree {
+    const int32_t *first_child;    // [n] internal index of the first child (children are contiguous)
+    const int32_t *n_children;     // [n]
+    const uint4 *desc;             // [n][2]
+    const int32_t *orig_id;        // [n] node id of the caller's numbering
+    const int32_t *word;           // [n] word id (-1 for inner nodes)
+    const double *weight;          // [n]
+    int depth_levels, max_depth;
+};
+struct ms_bow_vocab {
+    ms_ctx *ctx = nullptr;
+    void *slab = nullptr;
+    BowTree tree{};
+    int n_nodes = 0, max_children = 0;
 };
 
 struct ms_ctx {

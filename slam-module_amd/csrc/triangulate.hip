@@ -22,6 +22,7 @@
 // float32 steps of checkReprojectionError are spelt with the *_rn intrinsics).  A butterfly sum gives every lane the same bits because
 // a + b == b + a.  No atomics, no shared memory, no inline assembly.  Everything a kernel indexes with is validated on the host first.
 #include "ms_internal.h"
+#include "ms_bearing.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -65,10 +66,7 @@ __device__ __forceinline__ void load_obs(const TriArgs &A, int o, Obs &ob) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) ob.P[i] = P[i];
     const ms_pinhole c = A.cam[k];
-    ob.xn = ((double)A.obs_x[o] - c.cx) / c.fx;
-    ob.yn = ((double)A.obs_y[o] - c.cy) / c.fy;
-    const double nrm = sqrt(ob.xn * ob.xn + ob.yn * ob.yn + 1.0);
-    ob.b[0] = ob.xn / nrm; ob.b[1] = ob.yn / nrm; ob.b[2] = 1.0 / nrm;
+    ms_pinhole_bearing(c, A.obs_x[o], A.obs_y[o], ob.xn, ob.yn, ob.b);
 }
 __device__ __forceinline__ void ray_of(const Obs &ob, double *r) {       // cameraToWorldRotation() * bearing
 #pragma unroll

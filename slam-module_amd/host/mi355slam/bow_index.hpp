@@ -116,6 +116,19 @@ public:
         if (norm > 0.0) for (auto &kv : v) kv.second /= norm;
     }
 
+    // assemble without the FeatureVector, for a keyframe whose node lists ms_keyframe_admit built on the device (admitKeyframe): the
+    // same sums in the same feature order, so the same bits
+    static void assembleVector(const std::vector<std::int32_t> &word, const std::vector<double> &weight, BowVector &v) {
+        for (std::size_t i = 0; i < word.size(); ++i) {
+            if (!(weight[i] > 0)) continue;
+            v[(unsigned)word[i]] += weight[i];
+        }
+        double norm = 0.0;
+        for (const auto &kv : v) norm += std::fabs(kv.second);
+        if (norm > 0.0) for (auto &kv : v) kv.second /= norm;
+    }
+    const ms_bow_vocab *vocabulary() const { return vocab_; }                     // the device tree, for ms_keyframe_admit
+
     // bow_index.cpp:44-48: the reference passes the keyframe (its shared->bowVec and id) and the map id
     void add(const BowVector &bowVec, MapKf mapKf) {
         requireL1();

@@ -66,6 +66,30 @@ public:
         // instead of a round trip to the device): 48 bytes per keypoint
         hsx_ = std::move(sx); hsy_ = std::move(sy); hsi_ = std::move(si); hdesc_ = std::move(desc); hoct_ = std::move(oct);
     }
+    // Empty arrays for up to `capacity` keypoints that ms_keyframe_admit completes on the device (admitKeyframe, map_update.hpp): nothing is
+    // uploaded, now or later.  Until admitted() the keyframe has no keypoints.
+    DeviceKeyframe(Context &ctx, std::size_t capacity)
+        : desc_(ctx, 8 * capacity), angle_(ctx, capacity), sx_(ctx, capacity), sy_(ctx, capacity), octave_(ctx, capacity), nodeId_(ctx, capacity),
+          nodeStart_(ctx, capacity + 1), kpIdx_(ctx, capacity), si_(ctx, capacity), bearing_(ctx, 3 * capacity), usable_(ctx, capacity), cap_(capacity) {}
+    std::size_t capacity() const { return cap_; }            // 0 for a keyframe built from host features
+    // what ms_keyframe_admit writes on the device, and the host copies it fills from its one download
+    ms_admit_frame admitFrame() {
+        return ms_admit_frame{(std::int32_t)cap_, desc_.data(), angle_.data(), octave_.data(), bearing_.data(), usable_.data(), sx_.data(), sy_.data(), si_.data(), nodeId_.data(),
+                              nodeStart_.data(), kpIdx_.data()};
+    }
+    ms_admit_host admitHost(std::int32_t *keyPointTrackIds, std::int32_t *word, double *weight) {
+        hsx_.resize(cap_); hsy_.resize(cap_); hsi_.resize(cap_); hoct_.resize(cap_); hdesc_.resize(8 * cap_);      // a keyframe admitted again: the vectors keep their storage
+        return ms_admit_host{keyPointTrackIds, word, weight, hsx_.data(), hsy_.data(), hsi_.data(), hoct_.data(), hdesc_.data()};
+    }
+    // completes the ms_match_frame from the call's counts (n, n_nodes, keypoints in the node lists)
+    void admitted(const std::int32_t counts[3]) {
+        const std::size_t n = (std::size_t)counts[0];
+        f_ = ms_match_frame{};
+        f_.n = counts[0];
+        f_.desc = desc_.data(); f_.angle = angle_.data(); f_.octave = octave_.data(); f_.bearing = bearing_.data(); f_.usable = usable_.data();
+        f_.bow.n_nodes = counts[1]; f_.bow.node_id = nodeId_.data(); f_.bow.node_start = nodeStart_.data(); f_.bow.kp_idx = kpIdx_.data();
+        hsx_.resize(n); hsy_.resize(n); hsi_.resize(n); hoct_.resize(n); hdesc_.resize(8 * n);
+    }
     const std::vector<float> &hostSortedX() const { return hsx_; }
     const std::vector<float> &hostSortedY() const { return hsy_; }
     const std::vector<std::int32_t> &hostSortedIndex() const { return hsi_; }
@@ -88,6 +112,7 @@ private:
     std::vector<float> hsx_, hsy_;
     std::vector<std::int32_t> hsi_, hoct_;
     std::vector<std::uint32_t> hdesc_;
+    std::size_t cap_ = 0;
 };
 
 namespace detail {

@@ -31,13 +31,31 @@ private:
 // keyframes arrive).
 class DeviceDescriptorPool {
 public:
-    DeviceDescriptorPool(Context &ctx, const std::vector<KeyPoint::Descriptor> &descriptors) : desc_(ctx, descriptors.size()) {
+    DeviceDescriptorPool(Context &ctx, const std::vector<KeyPoint::Descriptor> &descriptors) : desc_(ctx, descriptors.size()), used_(descriptors.size()) {
         desc_.upload(0, size(), descriptors.data());
     }
+    // An empty pool of `capacity` descriptors that keyframes are admitted into (admitKeyframe, map_update.hpp): append only.  Space is not
+    // reused when keyframes leave.
+    DeviceDescriptorPool(Context &ctx, std::size_t capacity) : desc_(ctx, capacity) {}
+    // room for n more descriptors: the index of the first.  Throws when the pool is full; nothing is reserved then.
+    std::size_t reserve(std::size_t n) {
+        if (n > size() - used_) throw std::length_error("DeviceDescriptorPool::reserve: " + std::to_string(n) + " descriptors, " + std::to_string(size() - used_) + " free");
+        const std::size_t base = used_;
+        used_ += n;
+        return base;
+    }
+    // the last n descriptors of the latest reservation were not needed (admitKeyframe reserves before the device has counted the keypoints)
+    void release(std::size_t n) {
+        if (n > used_) throw std::length_error("DeviceDescriptorPool::release: more than is reserved");
+        used_ -= n;
+    }
+    std::size_t used() const { return used_; }
     std::size_t size() const { return desc_.size(); }
     const std::uint32_t *descriptor() const { return reinterpret_cast<const std::uint32_t *>(desc_.data()); }
+    std::uint32_t *mutableDescriptor() { return reinterpret_cast<std::uint32_t *>(desc_.data()); }      // what admitKeyframe writes
 private:
     DeviceArray<KeyPoint::Descriptor> desc_;
+    std::size_t used_ = 0;
 };
 
 // One entry of MapPoint::observations as the refresh reads it: the observing keyframe's slot in DeviceKeyframePoses and the observing
@@ -195,6 +213,10 @@ public:
     const float *y() const { return y_.data(); }
     const std::int32_t *octave() const { return octave_.data(); }
     const float *depth() const { return depth_.data(); }
+    float *mutableX() { return x_.data(); }                  // what admitKeyframe writes, with the three below
+    float *mutableY() { return y_.data(); }
+    std::int32_t *mutableOctave() { return octave_.data(); }
+    float *mutableDepth() { return depth_.data(); }
 private:
     std::size_t n_, stride_;
     DeviceArray<float> x_, y_;

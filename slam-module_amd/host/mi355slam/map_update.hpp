@@ -3,7 +3,8 @@
 // culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
 // fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), matchLocalMapPoints, createNewMapPoints and the local
 // bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables), the per-frame pose
-// adjustment (poseBundleAdjustOnTables) and the end of a frame (finishFrame, removeKeyframes).
+// adjustment (poseBundleAdjustOnTables), the end of a frame (finishFrame, removeKeyframes) and the arrival of a keyframe from the extractor's
+// device output (admitKeyframe).
 // Results come back through Context::workspace and Context::download; nothing here owns device memory.
 #pragma once
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include <functional>
 #include <limits>
 #include <stdexcept>
+#include "bow_index.hpp"
 #include "bundle_adjuster.hpp"
 #include "keyframe_matcher.hpp"
 #include "map_tables.hpp"
@@ -757,6 +759,87 @@ inline FrameFinish finishFrame(Context &ctx, MapTables M, std::int32_t slot, std
 // One device call; no cloud.  The same two refusals as finishFrame, for every slot of the list, before any device call.
 inline FrameFinish removeKeyframes(Context &ctx, MapTables M, const std::vector<std::int32_t> &slots, const std::vector<std::int32_t> &loopClosureKeyframes) {
     return detail::finish_frame(ctx, M, "removeKeyframes", -1, 0, slots, loopClosureKeyframes);
+}
+
+// ---- a new keyframe from the extractor's output to the device tables (ms_keyframe_admit) ---------------------------------------------------
+// What addKeyframeCommonOuter knows of the frame that becomes a keyframe (mapper_helpers.cpp:1186-1203): its KfId and time, poseCW, the
+// pinhole stand-in of its camera, the tracker features' ids and depths (mapperInput.trackerFeatures) and, optionally, a DEVICE depth image
+// standing in for frame->getDepth (float32, rows depthStride elements apart).
+struct KeyframeAdmission {
+    std::int32_t id = -1;
+    double t = 0.0;
+    DeviceKeyframePoses::Pose poseCW{};
+    ms_pinhole camera{};
+    std::int32_t focalLength = 0;
+    std::vector<std::int32_t> trackIds;
+    std::vector<float> trackDepths;
+    bool hasTrackerFeatures = false;         // false: nobody is looked up, every depth comes from the image or is -1
+    const float *depthImage = nullptr;
+    std::int32_t depthWidth = 0, depthHeight = 0, depthStride = 0;
+};
+
+struct AdmittedKeyframe {
+    std::size_t keyPoints = 0;
+    std::vector<std::int32_t> keyPointTrackIds;              // what matchTrackedFeatures takes next
+    BowVector bowVector;                                     // for BowIndex::add; empty without a BowIndex
+};
+
+// Keyframe::addFullFeatures (keyframe.cpp:95-116) and BowIndex::transform for frame `frame` of a device keypoint view (the extractor's
+// ms_orb_device_view), into `slot`: ONE device call, nothing of the frame is downloaded but the 64 bytes per keypoint the host keeps.  Writes
+// M.keyframes (the slot's row = -1), M.keypoints, M.poses, M.pool (reserve()) and M.slots.frames[slot], which must be a DeviceKeyframe(ctx, capacity);
+// fills the slot's record: id, t, previous / next (the new keyframe follows `previousSlot`, -1 for the first), cameraCenter, camera, focalLength,
+// descBase.  A refusal of the call throws and leaves the tables, the pool's fill and the record as they were.
+inline AdmittedKeyframe admitKeyframe(Context &ctx, MapTables M, const ms_keypoints &view, int frame, std::int32_t slot, std::int32_t previousSlot,
+                                      const KeyframeAdmission &kf, BowIndex *bowIndex) {
+    M.require("admitKeyframe", M.KEYPOINTS | M.POSES | M.IDS | M.TIMES | M.LINKS | M.CENTRES | M.CAMERAS | M.FOCALS | M.DESC_BASES | M.FRAMES);
+    const std::size_t nKf = M.keyframes.size();
+    if (!M.pool) throw std::invalid_argument("admitKeyframe: no descriptor pool");
+    if (slot < 0 || (std::size_t)slot >= nKf || previousSlot < -1 || (std::size_t)(previousSlot + 1) > nKf || previousSlot == slot)
+        throw std::invalid_argument("admitKeyframe: slot " + std::to_string(slot) + " or previous slot " + std::to_string(previousSlot) + " outside the table");
+    KeyframeSlots &S = M.slots;
+    if (S.id[slot] >= 0) throw std::invalid_argument("admitKeyframe: slot " + std::to_string(slot) + " holds keyframe " + std::to_string(S.id[slot]));
+    DeviceKeyframe *dk = S.frames[slot];
+    if (!dk || dk->capacity() == 0) throw std::invalid_argument("admitKeyframe: slot " + std::to_string(slot) + " has no DeviceKeyframe with a capacity");
+    if (kf.trackIds.size() != kf.trackDepths.size()) throw std::invalid_argument("admitKeyframe: one depth per tracker feature");
+    // the device learns n; the pool hands out what the frame arrays could hold at most and gets the rest back
+    const std::size_t room = std::min({dk->capacity(), M.keyframes.stride(), (std::size_t)std::max(view.capacity, 0), M.pool->size() - M.pool->used()});
+    const std::size_t base = M.pool->reserve(room);
+    static const std::int32_t noId = 0;                      // a non-null pointer for an empty list: "no tracker features" is the flag's to say
+    static const float noDepth = 0.f;
+    ms_admit_args args{};
+    args.slot = slot; args.desc_base = (std::int32_t)base;
+    std::copy(kf.poseCW.begin(), kf.poseCW.end(), args.pose);
+    args.cam = kf.camera;
+    args.levels_up = 4;                                      // bow_index.cpp:85
+    args.vocab = bowIndex ? bowIndex->vocabulary() : nullptr;
+    if (kf.hasTrackerFeatures) { args.track_ids = kf.trackIds.empty() ? &noId : kf.trackIds.data(); args.track_depth = kf.trackDepths.empty() ? &noDepth : kf.trackDepths.data(); }
+    args.n_tracks = (std::int32_t)kf.trackIds.size();
+    args.depth_image = kf.depthImage; args.depth_width = kf.depthWidth; args.depth_height = kf.depthHeight; args.depth_stride = kf.depthStride;
+    AdmittedKeyframe out;
+    std::vector<std::int32_t> word(dk->capacity());
+    std::vector<double> weight(dk->capacity());
+    out.keyPointTrackIds.resize(dk->capacity());
+    const ms_admit_frame arrays = dk->admitFrame();
+    const ms_admit_host host = dk->admitHost(out.keyPointTrackIds.data(), word.data(), weight.data());
+    std::int32_t counts[3] = {0, 0, 0};
+    const int rc = ms_keyframe_admit(ctx.get(), &view, frame, M.keyframes.mutableTable(), (int)nKf, (int)M.keyframes.stride(), (int)M.keyframes.mapPointCount(), M.keypoints->mutableX(),
+                                     M.keypoints->mutableY(), M.keypoints->mutableOctave(), M.keypoints->mutableDepth(), M.pool->mutableDescriptor(), (int)(base + room),
+                                     M.poses->pose(), &args, &arrays, &host, counts);
+    if (rc != MS_OK) { M.pool->release(room); ctx.check(rc, "ms_keyframe_admit"); }
+    const std::size_t n = (std::size_t)counts[0];
+    M.pool->release(room - n);                               // the tail of the reservation nobody wrote
+    dk->admitted(counts);
+    out.keyPoints = n;
+    out.keyPointTrackIds.resize(n); word.resize(n); weight.resize(n);
+    if (bowIndex) BowIndex::assembleVector(word, weight, out.bowVector);
+    S.id[slot] = kf.id; S.t[slot] = kf.t;
+    S.previous[slot] = previousSlot; S.next[slot] = -1;      // keyframe.cpp:82-83, then the chain of addKeyframeCommonOuter
+    if (previousSlot >= 0) S.next[previousSlot] = slot;
+    const auto &P = kf.poseCW;                               // cameraCenter() = -R^T t
+    for (int j = 0; j < 3; ++j) S.cameraCenter[slot][j] = -(P[j] * P[3] + P[4 + j] * P[7] + P[8 + j] * P[11]);
+    S.camera[slot] = kf.camera; S.focalLength[slot] = kf.focalLength;
+    S.descBase[slot] = (std::int32_t)base;
+    return out;
 }
 
 // ---- fusing duplicate map points on the device tables (ms_map_fuse, ms_map_replace_pairs) ----------------------------------------------

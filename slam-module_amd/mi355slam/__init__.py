@@ -1302,6 +1302,131 @@ def frame_finish_validate(arrays, n_kf, stride, n_mp, n_remove, cloud_slot, n_kp
     return rc, why.value.decode()
 
 
+# ---- a new keyframe from the extractor's output to the map tables (ms_keyframe_admit) ----
+class AdmitArgsC(C.Structure):
+    """ms_admit_args"""
+    _fields_ = [("slot", C.c_int32), ("desc_base", C.c_int32), ("pose", C.c_double * 12), ("cam", Pinhole), ("levels_up", C.c_int32), ("vocab", C.c_void_p),
+                ("track_ids", C.c_void_p), ("track_depth", C.c_void_p), ("n_tracks", C.c_int32), ("depth_image", C.c_void_p), ("depth_width", C.c_int32),
+                ("depth_height", C.c_int32), ("depth_stride", C.c_int32)]
+
+
+class AdmitFrameC(C.Structure):
+    """ms_admit_frame: device pointers"""
+    _fields_ = [("cap_kp", C.c_int32)] + [(k, C.c_void_p) for k in ("desc", "angle", "octave", "bearing", "usable", "sorted_x", "sorted_y", "sorted_idx", "node_id",
+                                                                     "node_start", "kp_idx")]
+
+
+class AdmitHostC(C.Structure):
+    """ms_admit_host: host pointers"""
+    _fields_ = [(k, C.c_void_p) for k in ("kp_track", "word", "weight", "sorted_x", "sorted_y", "sorted_idx", "octave", "desc")]
+
+
+ADMIT_TABLES = ("kf_mp", "kp_x", "kp_y", "kp_octave", "kp_depth", "desc_pool", "kf_pose")
+_ADMIT_FRAME = (("desc", np.uint32, 8), ("angle", np.float32, 1), ("octave", np.int32, 1), ("bearing", np.float64, 3), ("usable", np.uint8, 1), ("sorted_x", np.float32, 1),
+                ("sorted_y", np.float32, 1), ("sorted_idx", np.int32, 1), ("node_id", np.int32, 1), ("node_start", np.int32, 1), ("kp_idx", np.int32, 1))
+_ADMIT_HOST = (("kp_track", np.int32, 1), ("word", np.int32, 1), ("weight", np.float64, 1), ("sorted_x", np.float32, 1), ("sorted_y", np.float32, 1),
+               ("sorted_idx", np.int32, 1), ("octave", np.int32, 1), ("desc", np.uint32, 8))
+
+
+def keypoints_view(capacity, count, x, y, angle, octave, desc, track_id):
+    """An ms_keypoints of caller-owned DEVICE arrays (DevBufs or pointers), laid out as ms_orb_device_view's: frame f's keypoint i is element
+    f * capacity + i."""
+    p = lambda b: _vp(b).value
+    return KeypointsView(int(capacity), p(count), p(x), p(y), p(angle), p(octave), p(desc), p(track_id))
+
+
+class AdmitFrame:
+    """The device arrays of one keyframe that ms_keyframe_admit completes (ms_admit_frame, capacity cap_kp): what an ms_match_frame and
+    FeatureSearch::create need.  After a call, n / n_nodes are the call's counts and match_frame() is the struct the matchers take."""
+
+    def __init__(self, ctx, cap_kp):
+        self.ctx, self.cap_kp, self.n, self.n_nodes, self.n_listed = ctx, int(cap_kp), 0, 0, 0
+        self.bufs = {k: ctx.alloc(max((self.cap_kp + (k == "node_start")) * w * np.dtype(dt).itemsize, 16)) for k, dt, w in _ADMIT_FRAME}
+        self.struct = AdmitFrameC(self.cap_kp, *[self.bufs[k].ptr for k, _, _ in _ADMIT_FRAME])
+
+    def match_frame(self):
+        b = self.bufs
+        return MatchFrame(self.n, b["desc"].ptr, b["angle"].ptr, b["octave"].ptr, b["bearing"].ptr, b["usable"].ptr,
+                          Bow(self.n_nodes, b["node_id"].ptr, b["node_start"].ptr, b["kp_idx"].ptr))
+
+    def on_device(self):
+        """What match_loop_closure / match_triangulation take in place of a FrameOnDevice: the admitted arrays, nothing uploaded."""
+        f = FrameOnDevice.__new__(FrameOnDevice)
+        f.n, f.bufs, f.struct = self.n, self.bufs, self.match_frame()
+        return f
+
+    def download(self):
+        """Every array in full (cap_kp entries; node_start cap_kp + 1)."""
+        shape = lambda k, w: (self.cap_kp + (k == "node_start"),) + ((w,) if w > 1 else ())
+        return {k: self.bufs[k].download(dt, shape(k, w)) for k, dt, w in _ADMIT_FRAME}
+
+    def free(self):
+        for b in self.bufs.values():
+            b.free()
+
+
+def _admit_args(args):
+    """dict(slot, desc_base, pose [12], cam (fx, fy, cx, cy, width, height), levels_up (4), vocab (a BowVocabulary or None), track_ids /
+    track_depth (host arrays or None; n_tracks, when given, overrides their length), depth_image (a DevBuf of float32 or None), depth_width,
+    depth_height, depth_stride (the width when absent)) -> ms_admit_args and what must stay alive while it is used."""
+    pose = np.ascontiguousarray(args["pose"], np.float64).reshape(12)
+    cam = args["cam"]
+    ids = None if args.get("track_ids") is None else _i32(args["track_ids"])
+    dep = None if args.get("track_depth") is None else np.ascontiguousarray(args["track_depth"], np.float32).reshape(-1)
+    vocab = args.get("vocab")
+    n_tracks = int(args["n_tracks"]) if "n_tracks" in args else (len(ids) if ids is not None else 0)
+    w = int(args.get("depth_width", 0))
+    A = AdmitArgsC(int(args["slot"]), int(args["desc_base"]), (C.c_double * 12)(*pose), Pinhole(cam[0], cam[1], cam[2], cam[3], int(cam[4]), int(cam[5])),
+                   int(args.get("levels_up", 4)), vocab._h.value if vocab is not None else None, _vp(ids).value, _vp(dep).value, n_tracks,
+                   _vp(args.get("depth_image")).value, w,
+                   int(args.get("depth_height", 0)), int(args.get("depth_stride", w)))
+    return A, (ids, dep, vocab)
+
+
+def keyframe_admit_validate(view, frame, tables, n_kf, stride, n_mp, n_pool, args, out, host=None, counts=True):
+    """ms_keyframe_admit_validate, the host half of ms_keyframe_admit (no context, no device).  view: a KeypointsView or None; tables: a dict of
+    the names in ADMIT_TABLES (numpy arrays, DevBufs, pointers or None: only their presence and alignment is looked at); args: _admit_args'
+    dict or None; out: an AdmitFrameC / AdmitFrame or None; host: an AdmitHostC or None.  Returns (rc, message)."""
+    p = lambda k: _vp(tables.get(k))
+    A, keep = _admit_args(args) if args is not None else (None, None)
+    out = out.struct if isinstance(out, AdmitFrame) else out
+    why, cnt = C.create_string_buffer(512), np.zeros(3, np.int32)
+    ref = lambda s: C.byref(s) if s is not None else None
+    rc = lib().ms_keyframe_admit_validate(ref(view), int(frame), p("kf_mp"), int(n_kf), int(stride), int(n_mp), p("kp_x"), p("kp_y"), p("kp_octave"), p("kp_depth"),
+                                          p("desc_pool"), int(n_pool), p("kf_pose"), ref(A), ref(out), ref(host), _vp(cnt if counts else None), why, C.c_size_t(512))
+    return rc, why.value.decode()
+
+
+def keyframe_admit_device(ctx, view, frame, tables, n_kf, stride, n_mp, n_pool, args, out, host=True):
+    """ms_keyframe_admit without raising.  view: a KeypointsView of DEVICE arrays (OrbExtractor.device_view() or keypoints_view()); tables: a dict
+    of DevBufs named in ADMIT_TABLES, updated in place; args: _admit_args' dict; out: an AdmitFrame, whose n / n_nodes are set on success;
+    host: True for every host output, False for none, or the names wanted.  Returns (rc, dict(counts [3], and the host outputs cut to n))."""
+    A, keep = _admit_args(args)
+    names = [k for k, _, _ in _ADMIT_HOST] if host is True else ([] if not host else list(host))
+    cap = out.cap_kp
+    arrs = {k: np.zeros((cap, w) if w > 1 else cap, dt) for k, dt, w in _ADMIT_HOST if k in names}
+    H = AdmitHostC(*[arrs[k].ctypes.data if k in arrs else None for k, _, _ in _ADMIT_HOST])
+    counts = np.zeros(3, np.int32)
+    p = lambda k: _vp(tables[k])
+    rc = lib().ms_keyframe_admit(ctx._h, C.byref(view), int(frame), p("kf_mp"), int(n_kf), int(stride), int(n_mp), p("kp_x"), p("kp_y"), p("kp_octave"), p("kp_depth"),
+                                 p("desc_pool"), int(n_pool), p("kf_pose"), C.byref(A), C.byref(out.struct), C.byref(H) if names else None, _vp(counts))
+    res = dict(counts=counts)
+    if rc == 0:
+        out.n, out.n_nodes, out.n_listed = (int(v) for v in counts)
+        res.update({k: a[:out.n].copy() for k, a in arrs.items()})
+    return rc, res
+
+
+def keyframe_admit(ctx, view, frame, kf_table, n_mp, kp, pool, poses, args, out, host=True):
+    """Keyframe::addFullFeatures / processKeyPoints on the device tables (ms_keyframe_admit): frame `frame` of the view goes into slot
+    args["slot"] of kf_table (a KeyframeTable), kp (a KeypointTable), pool (a DevBuf of [n_pool, 8] uint32) and poses (a KeyframePoseTable);
+    `out` (an AdmitFrame) receives the matcher's and the feature search's arrays.  Returns keyframe_admit_device's dict; raises MsError."""
+    tables = dict(kf_mp=kf_table.kf_mp, kp_x=kp.x, kp_y=kp.y, kp_octave=kp.octave, kp_depth=kp.depth, desc_pool=pool, kf_pose=poses.pose)
+    rc, res = keyframe_admit_device(ctx, view, frame, tables, kf_table.n_kf, kf_table.stride, n_mp, pool.nbytes // 32, args, out, host)
+    ctx.check(rc, "ms_keyframe_admit")
+    return res
+
+
 class KeyframeTable:
     """Keyframe::mapPoints of every keyframe on the device: kf_mp [n_kf, stride] int32, entry (k, j) = the map-point table row bound to
     keypoint j of the keyframe in slot k, -1 for none.  The queries take n_mp (rows of the map-point table; an entry outside [0, n_mp)
