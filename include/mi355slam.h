@@ -157,7 +157,11 @@ int ms_orb_set_valid_mask(ms_orb *orb, const uint8_t *mask_host);
  *   track_xy      : optional [n_frames][max_tracks][2] level-0 coords (host), track_id [n_frames][max_tracks],
  *                   n_tracks [n_frames].  NULL = no tracker features.
  * Asynchronous on the context stream; results are read with ms_orb_download / ms_orb_device_view
- * after ms_ctx_sync (ms_orb_download synchronises itself). */
+ * after ms_ctx_sync (ms_orb_download synchronises itself).
+ * Which launches a call issues depends on where its frames live: frames in device memory, and host batches of fewer than 32 frames, are one
+ * piece, and a piece large enough runs level 0's corner detection beside the resize chain (ms_orb_set_fast_overlap).  A HOST batch of 32 frames
+ * or more, pinned or pageable, on an extractor with max_batch >= 32 and profiling off comes in as four pieces on the extractor's copy stream, each
+ * piece's kernels under the next piece's copy; those pieces never split automatically.  The results are the same bit for bit either way. */
 int ms_orb_extract(ms_orb *orb, const uint8_t *images, int images_on_device, int n_frames,
                    size_t frame_stride, size_t row_stride,
                    const float *track_xy, const int32_t *track_id, const int32_t *n_tracks);
@@ -201,9 +205,25 @@ int ms_orb_set_resize_plan(ms_orb *orb, int px, int map);
  * The default is 1 (the visit order costs the slot kernel what it saves the describe kernel).  MS_ERR_INVALID for anything outside 0 .. 3.  Holds for the calls that follow. */
 int ms_orb_set_describe_order(ms_orb *orb, int mode);
 
+/* Whether corner detection on pyramid level 0 (the caller's image, which needs no resized level) runs beside the resize chain, on a side stream of
+ * the extractor (its copy stream where it has one) that forks from the context stream at the start of the call's kernels and joins it in front of
+ * the selection (a test hook; outputs are bit for bit the same for every value).  0 = automatic: only in calls where each of the two detector
+ * launches, level 0 and the other levels, has more workgroups than the detector's pruning rule asks for (17 frames and more at 1280 x 720 x 8
+ * levels), and not in the pieces of a batch of host frames, whose kernels already run beside the next piece's copy; 1 = never: one launch on the
+ * context stream; 2 = always, where the pyramid has more than one level (the side stream is created on this request if the extractor has none); a
+ * one-level pyramid keeps its single launch.  MS_ERR_INVALID for anything else.  Holds for the calls that follow. */
+int ms_orb_set_fast_overlap(ms_orb *orb, int mode);
+/* How the last ms_orb_extract launched the corner detector: *launches = its launches (1 = one launch over all levels, 2 = level 0 beside the
+ * resize chain and the other levels behind it; a host batch that came in as pieces counts every piece's), *pruning = how many of them were the
+ * instantiation that raises its threshold from what the launch has found (launches of more than 2048 workgroups).  Host bookkeeping, no wait. */
+int ms_orb_last_fast_launches(const ms_orb *orb, int32_t *launches, int32_t *pruning);
+
 /* Per-kernel timing of ms_orb_extract with HIP events on the context stream (off by default).
  * Stage order: 0 resize (all levels), 1 blur, 2 fast, 3 select, 4 tracks, 5 describe.
- * ms_orb_stage_ms synchronises and returns the durations of the LAST ms_orb_extract call. */
+ * ms_orb_stage_ms synchronises and returns the durations of the LAST ms_orb_extract call.
+ * The events are all on the context stream, so the six times add up to the call's span.  In a call that runs level 0's detection beside the
+ * resize chain (ms_orb_set_fast_overlap), `resize` therefore contains level 0's detection and `fast` is the other levels plus the wait for the
+ * side stream; the time of each kernel alone is what a kernel trace shows. */
 #define MS_ORB_STAGES 6
 int ms_orb_set_profiling(ms_orb *orb, int enable);
 int ms_orb_stage_ms(ms_orb *orb, float *ms /* [MS_ORB_STAGES] */);

@@ -530,7 +530,6 @@ __global__ __launch_bounds__(256) void k_blur(FrameSrc src, TileLevels TL, TileM
 //             ((255-score)<<24 | y*w+x) with ONE global atomic per tile
 constexpr int kFastWaves = 8, kFastThreads = 64 * kFastWaves;     // waves per tile: 4 position rows each
 constexpr int kFastSeg = 248, kFastRows = 4 * kFastWaves - 2, kFastPosRows = kFastRows + 2, kFastRowsPerWave = 4;
-constexpr int kFastPruneMinBlocks = 2 * 4 * 256;               // launches with more workgroups than this learn a raised threshold (k_fast)
 constexpr int kFastPositions = kFastPosRows * (kFastSeg + 2);   // scored positions of a tile: columns 3..252 of its position rows
 
 __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) {
@@ -1474,6 +1473,13 @@ struct ms_orb {
     hipEvent_t ev_copied[4] = {nullptr}, ev_free[4] = {nullptr}, ev_end = nullptr;
     int chunked_frames = 0;            // n_frames of the last chunked call (its ev_free[] mark the pieces of exactly that split); 0 = none
     bool end_recorded = false;
+    // level 0's k_fast beside the resize chain (orb_enqueue_kernels): on a side stream between a fork and a join event of the context stream
+    int ftiles_level0 = 0;             // the first entries of d_ftile_tab are level 0's
+    int fast_overlap = 0;              // ms_orb_set_fast_overlap: 0 = automatic, 1 = never, 2 = always
+    int fast_launches = 0, fast_pruning = 0;   // k_fast launches of the last call, and how many of them were k_fast<true> (ms_orb_last_fast_launches)
+    hipStream_t side_stream = nullptr; // exists where max_batch can reach the automatic rule, or once mode 2 was asked for: the copy stream where the
+    bool side_owned = false;           // extractor has one (idle in the calls that split automatically), else a stream of its own
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // state of the last call
     FrameSrc last_src{};
     int last_frames = 0;
@@ -1523,16 +1529,37 @@ static int orb_take_block(ms_orb *o, const OrbGeom &R, const OrbTables &C) {
     return MS_OK;
 }
 
-// the copy stream and its events (batches of host frames only; a one-frame extractor never uses them)
+// the side stream of level 0's k_fast with its fork and join events
+static int orb_create_side_stream(ms_orb *o) {
+    ms_ctx *c = o->ctx;
+    if (o->side_stream) return MS_OK;
+    if (!o->ev_fork) MS_HIP(c, hipEventCreateWithFlags(&o->ev_fork, hipEventDisableTiming));
+    if (!o->ev_join) MS_HIP(c, hipEventCreateWithFlags(&o->ev_join, hipEventDisableTiming));
+    // The copy stream does the job where there is one: automatic mode never splits the pieces of a batch of host frames, so that stream is idle in every
+    // call that does.  A stream more per extractor is not free: with one merely EXISTING beside the copy stream (the step itself did not split) the
+    // bench's PCIe-inclusive step, which keeps four streams busy, went from 4.4 to 5.5 ms with four hardware queues and to 5.1 with eight
+    // (DESIGN section 10); with the copy stream in its place it stays where it was.
+    // Default priority: at the lowest one (hipDeviceGetStreamPriorityRange) detection fills in behind the resize blocks and overlaps less -- measured,
+    // +1.8 % on the 256-frame step against +2.2 %.
+    if (o->copy_stream) { o->side_stream = o->copy_stream; return MS_OK; }
+    MS_HIP(c, hipStreamCreateWithFlags(&o->side_stream, hipStreamNonBlocking));      // last: the stream exists only with both its events
+    o->side_owned = true;
+    return MS_OK;
+}
+
+// the copy stream and its events (batches of host frames only; a one-frame extractor never uses them), and the side stream where a call can be
+// large enough for the split k_fast
 static int orb_create_streams(ms_orb *o) {
     ms_ctx *c = o->ctx;
     MS_HIP(c, hipEventCreateWithFlags(&o->ev_end, hipEventDisableTiming));
-    if (o->cfg.max_batch < 32) return MS_OK;
-    MS_HIP(c, hipStreamCreateWithFlags(&o->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 4; ++i) {
-        MS_HIP(c, hipEventCreateWithFlags(&o->ev_copied[i], hipEventDisableTiming));
-        MS_HIP(c, hipEventCreateWithFlags(&o->ev_free[i], hipEventDisableTiming));
+    if (o->cfg.max_batch >= 32) {
+        MS_HIP(c, hipStreamCreateWithFlags(&o->copy_stream, hipStreamNonBlocking));
+        for (int i = 0; i < 4; ++i) {
+            MS_HIP(c, hipEventCreateWithFlags(&o->ev_copied[i], hipEventDisableTiming));
+            MS_HIP(c, hipEventCreateWithFlags(&o->ev_free[i], hipEventDisableTiming));
+        }
     }
+    if (orb_fast_split_auto(o->cfg.max_batch, o->ftiles_level0, o->geom.ftiles_total)) MS_TRY(orb_create_side_stream(o));
     return MS_OK;
 }
 
@@ -1553,7 +1580,7 @@ int ms_orb_create(ms_ctx *ctx, const ms_orb_config *cfg, ms_orb **out) {
     o->ctx = ctx;
     o->cfg = *cfg;
     o->geom = R.geom; o->tile_levels = R.tile_levels; o->blur_tiles = R.blur_tiles;
-    o->lvl0_off = R.lvl0_off; o->lvl0_pitch = R.lvl0_pitch;
+    o->lvl0_off = R.lvl0_off; o->lvl0_pitch = R.lvl0_pitch; o->ftiles_level0 = R.ftiles_level0;
     for (int l = 1; l < cfg->levels; ++l) o->wide[l] = C.level[l].wide;
     // from here on one way out: ms_orb_destroy takes whatever exists
     if (orb_take_block(o, R, C) != MS_OK) { ms_orb_destroy(o); return ms_fail(ctx, MS_ERR_HIP, "ms_orb_create: device allocation failed"); }
@@ -1572,6 +1599,9 @@ void ms_orb_destroy(ms_orb *o) {
     if (o->copy_stream) { (void)hipStreamSynchronize(o->copy_stream); (void)hipStreamDestroy(o->copy_stream); }
     for (int i = 0; i < 4; ++i) { if (o->ev_copied[i]) (void)hipEventDestroy(o->ev_copied[i]); if (o->ev_free[i]) (void)hipEventDestroy(o->ev_free[i]); }
     if (o->ev_end) (void)hipEventDestroy(o->ev_end);
+    if (o->side_owned) { (void)hipStreamSynchronize(o->side_stream); (void)hipStreamDestroy(o->side_stream); }
+    if (o->ev_fork) (void)hipEventDestroy(o->ev_fork);
+    if (o->ev_join) (void)hipEventDestroy(o->ev_join);
     delete o;
 }
 
@@ -1592,6 +1622,16 @@ int ms_orb_set_resize_plan(ms_orb *o, int px, int map) {
 int ms_orb_set_describe_order(ms_orb *o, int mode) {
     if (!o || mode < 0 || (mode & ~describe_order::kModeMask)) return MS_ERR_INVALID;
     o->describe_order = mode;
+    return MS_OK;
+}
+
+int ms_orb_set_fast_overlap(ms_orb *o, int mode) {
+    if (!o || mode < 0 || mode > 2) return MS_ERR_INVALID;
+    if (mode == 2 && o->geom.levels > 1) {          // a small extractor has no side stream yet
+        MS_HIP(o->ctx, hipSetDevice(o->ctx->device));
+        MS_TRY(orb_create_side_stream(o));
+    }
+    o->fast_overlap = mode;
     return MS_OK;
 }
 
@@ -1644,6 +1684,10 @@ int ms_orb_extract(ms_orb *o, const uint8_t *images, int on_device, int n_frames
     const int rc = orb_extract_enqueue(o, images, on_device, n_frames, frame_stride, row_stride, track_xy, track_id, n_tracks, counters_dirty);
     // k_fast fills the candidate counters and k_select puts them back to zero; a call that fails in between must not leave them to the next one
     if (rc != MS_OK && counters_dirty) {
+        if (o->side_stream) {           // a part-launch of k_fast may still be appending on the side stream
+            (void)hipEventRecord(o->ev_join, o->side_stream);
+            (void)hipStreamWaitEvent(o->ctx->stream, o->ev_join, 0);
+        }
         (void)hipMemsetAsync(o->d_cand_count, 0, o->cand_count_bytes, o->ctx->stream);
         (void)hipMemsetAsync(o->d_score_hist, 0, o->score_hist_bytes, o->ctx->stream);
     }
@@ -1651,8 +1695,8 @@ int ms_orb_extract(ms_orb *o, const uint8_t *images, int on_device, int n_frames
 }
 
 // the kernels of one extract over frames [f0, f0 + nf) of the batch: every per-frame array is linear in the frame index, so a piece of the batch
-// is the same launches on offset pointers
-static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool have_tracks, bool have_ids, bool &counters_dirty) {
+// is the same launches on offset pointers (in_pieces: this is such a piece, its frames copied from the host on the copy stream)
+static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool have_tracks, bool have_ids, bool in_pieces, bool &counters_dirty) {
     ms_ctx *c = o->ctx;
     const PyrGeom &G = o->geom;
     hipStream_t st = c->stream;
@@ -1664,12 +1708,37 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     // device holds at once (4 per CU on 256 CUs).  Below that (nearly) all tiles start before any has finished; they run the plain kernel, tile-fastest.
     const bool prune = (long long)nf * G.ftiles_total > kFastPruneMinBlocks;
     uint32_t *score_hist = prune ? o->d_score_hist + F * L * 256 : nullptr;
+    // Level 0 is the caller's image and needs no resized level, and k_fast is bound by vector issue where the resize chain waits on memory: a call
+    // large enough runs level 0's tiles (the first ftiles_level0 entries of the tile table) on the side stream beside the resizes, the other levels'
+    // behind them on the context stream, and joins the two in front of k_select.  Both parts are the same instantiation on the same lists, counters
+    // and bins: the lists are unordered and the raised threshold is exact whatever a tile has seen (k_fast).  A piece of a batch of host frames
+    // (in_pieces) keeps the single launch unless the split is forced: its kernels already run beside the next piece's copy, the step is bound by the
+    // copies, and the side stream is the copy stream, which has the next piece's frames to carry.
+    const int tiles0 = o->ftiles_level0, tiles1 = G.ftiles_total - tiles0;
+    const bool split = o->side_stream && tiles1 > 0 && o->fast_overlap != 1 &&
+                       (o->fast_overlap == 2 || (!in_pieces && orb_fast_split_auto(nf, tiles0, G.ftiles_total)));
+    auto launch_fast = [&](hipStream_t s, int tile0, int tiles) {
+        ++o->fast_launches; o->fast_pruning += prune;
+        if (prune) hipLaunchKernelGGL(k_fast<true>, dim3(nf, tiles), dim3(kFastThreads), 0, s, src, cand, cand_count, score_hist, o->d_ftile_tab + tile0, o->tile_levels);     // frame fastest: see k_fast
+        else hipLaunchKernelGGL(k_fast<false>, dim3(tiles, nf), dim3(kFastThreads), 0, s, src, cand, cand_count, score_hist, o->d_ftile_tab + tile0, o->tile_levels);
+    };
     int16_t *det_x = o->d_det_x + F * G.det_stride, *det_y = o->d_det_y + F * G.det_stride;
     uint8_t *det_score = o->d_det_score + F * G.det_stride;
     int stage = 0;
     if (o->profiling) { o->ev = o->evr[o->prof_calls % ms_orb::kProfRing]; ++o->prof_calls; }
 #define MS_STAGE_MARK() do { if (o->profiling) MS_HIP(c, hipEventRecord(o->ev[stage++], st)); } while (0)
     MS_STAGE_MARK();
+    if (split) {
+        // the fork lies behind all that must precede the call on the context stream: the previous call's kernels (its k_select and k_describe read
+        // what this launch writes), k_copy_level0, a piece's wait for its copy.  The stage marks stay on the context stream: with the split the
+        // `resize` interval holds level 0's detection and `fast` the other levels plus the join.
+        MS_HIP(c, hipEventRecord(o->ev_fork, st));
+        MS_HIP(c, hipStreamWaitEvent(o->side_stream, o->ev_fork, 0));
+        counters_dirty = true;
+        launch_fast(o->side_stream, 0, tiles0);
+        MS_KERNEL_CHECK(c, "k_fast");
+        MS_HIP(c, hipEventRecord(o->ev_join, o->side_stream));
+    }
     MsRange pyramid_range("pyramid");
     for (int l = 1; l < G.levels; ++l) {
         dim3 grid(ms_div_up(G.L[l].w, 256), ms_div_up(G.L[l].h, 4 * kResizeRows), nf);
@@ -1695,9 +1764,9 @@ static int orb_enqueue_kernels(ms_orb *o, FrameSrc src, int f0, int nf, bool hav
     MS_STAGE_MARK();
     MsRange detect_range("detect");
     counters_dirty = true;
-    if (prune) hipLaunchKernelGGL(k_fast<true>, dim3(nf, G.ftiles_total), dim3(kFastThreads), 0, st, src, cand, cand_count, score_hist, o->d_ftile_tab, o->tile_levels);     // frame fastest: see k_fast
-    else hipLaunchKernelGGL(k_fast<false>, dim3(G.ftiles_total, nf), dim3(kFastThreads), 0, st, src, cand, cand_count, score_hist, o->d_ftile_tab, o->tile_levels);
+    if (split) launch_fast(st, tiles0, tiles1); else launch_fast(st, 0, G.ftiles_total);
     MS_KERNEL_CHECK(c, "k_fast");
+    if (split) MS_HIP(c, hipStreamWaitEvent(st, o->ev_join, 0));      // k_select consumes both parts' lists
     MS_STAGE_MARK();
     const bool few = nf * G.levels <= 64;                           // a frame or a handful: one block per level is the whole launch -- give it 1024 threads
     if (o->cfg.min_distance > 0.f) {
@@ -1747,6 +1816,7 @@ static int orb_extract_enqueue(ms_orb *o, const uint8_t *images, int on_device, 
         return ms_fail(c, MS_ERR_INVALID, "ms_orb_extract: strides smaller than the frame");
     MS_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
+    o->fast_launches = o->fast_pruning = 0;
     MS_TRY(ms_ctx_order_after_downloads(c));               // asynchronous downloads of the previous outputs (ms_dev_download_async) finish before they are overwritten
     FrameSrc src{};
     src.slab = o->d_slab;
@@ -1762,7 +1832,7 @@ static int orb_extract_enqueue(ms_orb *o, const uint8_t *images, int on_device, 
     if (aligned) {   // use the caller's frames in place as pyramid level 0 (image_pyramid.cpp:75 without the copy)
         src.lvl0 = images; src.lvl0_frame_stride = frame_stride; src.lvl0_pitch = (int)row_stride;
         o->lvl0_in_slab = false;
-        MS_TRY(orb_enqueue_kernels(o, src, 0, n_frames, have_tracks, track_id != nullptr, counters_dirty));
+        MS_TRY(orb_enqueue_kernels(o, src, 0, n_frames, have_tracks, track_id != nullptr, false, counters_dirty));
     } else {
         uint8_t *dst = o->d_slab + o->lvl0_off;
         src.lvl0 = dst; src.lvl0_frame_stride = G.slab_stride; src.lvl0_pitch = o->lvl0_pitch;
@@ -1789,10 +1859,10 @@ static int orb_extract_enqueue(ms_orb *o, const uint8_t *images, int on_device, 
             hipLaunchKernelGGL(k_copy_level0, grid, dim3(256), 0, st, images, (uint64_t)frame_stride, (uint64_t)row_stride, o->d_slab,
                                G.slab_stride, o->lvl0_off, G.width, G.height, o->lvl0_pitch);
             MS_KERNEL_CHECK(c, "k_copy_level0");
-            MS_TRY(orb_enqueue_kernels(o, src, 0, n_frames, have_tracks, track_id != nullptr, counters_dirty));
+            MS_TRY(orb_enqueue_kernels(o, src, 0, n_frames, have_tracks, track_id != nullptr, false, counters_dirty));
         } else if (!chunked) {
             MS_TRY(copy_frames(0, n_frames, st));
-            MS_TRY(orb_enqueue_kernels(o, src, 0, n_frames, have_tracks, track_id != nullptr, counters_dirty));
+            MS_TRY(orb_enqueue_kernels(o, src, 0, n_frames, have_tracks, track_id != nullptr, false, counters_dirty));
         } else {
             // Piece k's kernels run under piece k+1's copy (the copy engine and the CUs work side by side; the design rule: copies on a stream of their own).
             // A piece of the slab may be overwritten once the PREVIOUS call's kernels on it are done: its ev_free when that call was split the same way,
@@ -1807,7 +1877,7 @@ static int orb_extract_enqueue(ms_orb *o, const uint8_t *images, int on_device, 
                 MS_TRY(copy_frames(f0, nf, o->copy_stream));
                 MS_HIP(c, hipEventRecord(o->ev_copied[k], o->copy_stream));
                 MS_HIP(c, hipStreamWaitEvent(st, o->ev_copied[k], 0));
-                MS_TRY(orb_enqueue_kernels(o, src, f0, nf, have_tracks, track_id != nullptr, counters_dirty));
+                MS_TRY(orb_enqueue_kernels(o, src, f0, nf, have_tracks, track_id != nullptr, true, counters_dirty));
                 MS_HIP(c, hipEventRecord(o->ev_free[k], st));
             }
             o->chunked_frames = n_frames;
@@ -1884,6 +1954,12 @@ int ms_orb_last_candidate_counts(ms_orb *o, int32_t *out) {
     if (o->last_frames < 1) return ms_fail(c, MS_ERR_INVALID, "ms_orb_last_candidate_counts: nothing ran");
     MS_HIP(c, hipStreamSynchronize(c->stream));
     MS_HIP(c, hipMemcpy(out, o->d_last_count, sizeof(int32_t) * (size_t)o->last_frames * o->geom.levels, hipMemcpyDeviceToHost));
+    return MS_OK;
+}
+
+int ms_orb_last_fast_launches(const ms_orb *o, int32_t *launches, int32_t *pruning) {
+    if (!o || !launches || !pruning) return MS_ERR_INVALID;
+    *launches = o->fast_launches; *pruning = o->fast_pruning;
     return MS_OK;
 }
 

@@ -31,6 +31,7 @@ namespace {
 constexpr int kPatchRadius = MS_ORB_PATCH_RADIUS;   // 19
 constexpr int kMaxQuota = 4096;                      // per-level selection capacity (LDS sort)
 constexpr int kResizeRows = 5;   // destination rows per lane: the table fetch is paid once and 10 source windows (30 dwords) are in flight per lane
+constexpr int kFastPruneMinBlocks = 2 * 4 * 256;   // launches with more workgroups than this learn a raised threshold (k_fast)
 constexpr int kBlurSeg = 248;   // outputs per wave row segment
 constexpr int kBlurRows = 18;   // output rows per wave (+ 6 halo rows loaded).  Measured in one session: 8 -> 0.61 ms, 14 -> 0.53, 16 -> 0.67 (64-row tiles: row starts collide), 18 -> 0.51, 28 -> 0.51
 // (8 pixels per lane with 8-byte loads and stores -- half the memory instructions per pixel -- was built and measured: 0.60 ms against 0.51, at 6..10 rows per wave)
@@ -73,6 +74,7 @@ struct OrbGeom {
     TileLevels tile_levels;
     TileMap blur_tiles;
     std::vector<uint32_t> ftile_tab;     // k_fast's tile table (the cover of fast_tiles.h), two dwords per tile: level | S << 4,  X0 | Y0 << 16
+    int32_t ftiles_level0;               // its first entries are level 0's tiles (the table is level-major): how many
     uint64_t lvl0_off;                   // where a caller's level 0 goes when it cannot be used in place
     int32_t lvl0_pitch;
 };
@@ -131,6 +133,7 @@ inline int orb_geometry(const ms_orb_config &cfg, OrbGeom &R, char *why, size_t 
                 R.ftile_tab.push_back((uint32_t)l | ((uint32_t)t.S << 4));
                 R.ftile_tab.push_back((uint32_t)t.X0 | ((uint32_t)t.Y0 << 16));
             }
+            if (l == 0) R.ftiles_level0 = (int32_t)(R.ftile_tab.size() / 2);
             // 16 bits each in the entry; the last tile of a level has the largest of both.  Out of reach: a level is at most 32767 pixels either way.
             if (!cover.empty() && (cover.back().X0 > 0xFFFF || cover.back().Y0 > 0xFFFF))
                 ORB_GEOM_FAIL(MS_ERR_CAPACITY, "level %d (%dx%d) is beyond the detector's tile table (65535 px)", l, w[l], h[l]);
@@ -158,6 +161,14 @@ inline int orb_geometry(const ms_orb_config &cfg, OrbGeom &R, char *why, size_t 
     return MS_OK;
 }
 #undef ORB_GEOM_FAIL
+
+// Whether a call over nf frames runs k_fast as two launches -- level 0's tiles beside the resize chain, the other levels' behind it
+// (orb_enqueue_kernels): only when each part alone is a launch that learns a raised threshold, i.e. has more than kFastPruneMinBlocks
+// workgroups.  A smaller call (a frame, a few frames) keeps its single launch and pays for no event pair; a pyramid of one level has no
+// second part.
+inline bool orb_fast_split_auto(int nf, int ftiles_level0, int ftiles_total) {
+    return (long long)nf * std::min(ftiles_level0, ftiles_total - ftiles_level0) > kFastPruneMinBlocks;
+}
 
 // ------------------------------------------------------------------------------------------------ constant tables
 // The tables of the resize from level l - 1 to level l >= 1: xt [w padded to 4][4] = sx, a0, a1, 0 and yt [h padded to kResizeRows][4] = sy0, sy1

@@ -340,6 +340,18 @@ class OrbExtractor:
         A test hook: the outputs are the same for every value."""
         self.ctx.check(lib().ms_orb_set_describe_order(self._h, int(mode)), "ms_orb_set_describe_order")
 
+    def set_fast_overlap(self, mode):
+        """Level 0's corner detection beside the resize chain on a side stream: 0 = automatic (calls large enough for it), 1 = never, 2 = always
+        where the pyramid has more than one level.  A test hook: the outputs are the same for every value."""
+        self.ctx.check(lib().ms_orb_set_fast_overlap(self._h, int(mode)), "ms_orb_set_fast_overlap")
+
+    def last_fast_launches(self):
+        """(launches, pruning) of the corner detector in the last extract: 2 launches per piece where level 0 ran beside the resize chain, else 1;
+        pruning = how many of them raised their threshold from what the launch had found."""
+        n, p = C.c_int32(), C.c_int32()
+        self.ctx.check(lib().ms_orb_last_fast_launches(self._h, C.byref(n), C.byref(p)), "ms_orb_last_fast_launches")
+        return n.value, p.value
+
     def set_profiling(self, enable=True):
         self.ctx.check(lib().ms_orb_set_profiling(self._h, int(enable)), "ms_orb_set_profiling")
 
