@@ -321,7 +321,8 @@ int ms_descriptor_medoid(ms_ctx *ctx, const uint32_t *desc_pool, const int32_t *
  * node[i] is the node passed at level depth_levels - levels_up (0 = root when that level is <= 0; the leaf's own id when the
  * leaf lies above that level, where DBoW2 leaves the value unset).  word = -1, weight = 0 for a vocabulary without words.
  * weight / node may be NULL.  The BowVector / FeatureVector maps are assembled from these arrays by the host mirror
- * (mi355slam::BowIndex::transform) in feature order, so the sums match the reference's. */
+ * (mi355slam::BowIndex::transform) in feature order, so the sums match the reference's; ms_bow_vector (below) assembles the
+ * BowVector from word / weight on the device with the same sums. */
 typedef struct ms_bow_vocab ms_bow_vocab;
 int ms_bow_vocab_create(ms_ctx *ctx, int n_nodes, const int32_t *parent, const uint32_t *node_desc, const double *node_weight,
                         const int32_t *node_word, int depth_levels, ms_bow_vocab **out);
@@ -335,7 +336,7 @@ int ms_bow_transform(ms_ctx *ctx, const ms_bow_vocab *vocab, const uint32_t *des
  * L1-normalised map the host mirror assembles after ms_bow_transform: words strictly ascending in [0, n_words), finite values).
  * Queries scan the live entries; results are bit-identical to the reference: the same entries in the same order with the same
  * float scores (order among equal scores: (map_id, kf_id) ascending, the std::map order the reference's std::sort starts from).
- * All arguments are HOST pointers.  add / remove enqueue their work and return; a query synchronises once and fills its outputs.
+ * All arguments are HOST pointers (but the descent ms_bow_db_add_words takes).  add / remove enqueue their work and return; a query synchronises once and fills its outputs.
  * Capacity is grow-only; a steady add / remove / query cycle allocates nothing after warm-up (ms_debug_host_allocs). */
 typedef struct ms_bow_db ms_bow_db;
 /* An empty database for a vocabulary of n_words words, sized for initial_entries entries of initial_words words in all (grows as needed). */
@@ -368,6 +369,48 @@ int ms_bow_db_query(ms_bow_db *db, int n, const int32_t *words, const double *va
 int ms_bow_db_query_ids(ms_bow_db *db, int q, const int32_t *map_ids, const int32_t *kf_ids,
                         float min_in_common_ratio, float score_ratio, int max_out_per_query,
                         int32_t *out_map, int32_t *out_kf, float *out_score, int *n_total);
+
+/* ---- the BowVector on the device --------------------------------------------------------------------------
+ * DBoW2's BowVector::addWeight sums and normalize(L1) (the batch transform behind bow_index.cpp:86-92, mirrored by
+ * mi355slam::BowIndex::assembleVector) for a descent that lies on the device.  tests/bow_vector_ref.py restates the rule and is the
+ * specification.  word (int32) / weight (float64) [n] are DEVICE arrays in the form ms_bow_transform and ms_keyframe_admit write them:
+ *   keep       keypoint i is kept iff weight[i] > 0 as written: a NaN, a zero, a negative weight and a stop word are skipped and their
+ *              word is never read (word = -1 with weight = 0 is legal)
+ *   entries    one per distinct word of the kept keypoints, in ascending word order
+ *   value      starts at 0.0 and adds the kept weights of its word one by one in ascending i, float64, no contraction
+ *   norm       starts at 0.0 and adds fabs(value) entry by entry in ascending word order; iff norm > 0.0 every value becomes
+ *              value / norm (IEEE double division)
+ *   n_bad      the kept keypoints whose word lies outside [0, vocab_words), plus the final values that are not finite
+ * ms_bow_vector writes words [cap] (strictly ascending) and values [cap] (DEVICE) and counts (HOST [2]) = n_words, n_bad.
+ * 0 <= n <= MS_COVIS_MAX_STRIDE, 0 <= cap <= MS_COVIS_MAX_STRIDE.  Every verdict is taken before any output byte is written:
+ * MS_ERR_INVALID when n_bad > 0, MS_ERR_CAPACITY with the needed count in counts[0] when n_words > cap; the outputs keep their bytes
+ * in both cases (n_bad is judged first).  Before any device call (ms_bow_vector_validate, the host validation alone: no context, no
+ * device; `why` receives the message): MS_ERR_INVALID for a negative n or cap, vocab_words < 1, a missing array (counts; word or weight
+ * with n > 0; words or values with cap > 0), weight or values not 8-byte aligned; MS_ERR_CAPACITY beyond the caps.
+ * ONE launch whatever n is (k_bow_vector: one workgroup sorts the keys word << 13 | i in LDS, packs the segment heads with the shared
+ * block rank, a head's lane walks its segment, one lane adds the norm), no upload, ONE download of the 8-byte head, one host wait.
+ * Synchronous on the context stream.  Integer arithmetic decides every position, there is no floating-point atomic and no tree
+ * reduction: the same inputs give the same bytes on every call.  The workspace belongs to the context and only grows.  The worst
+ * case, every keypoint on one word, is a serial sum of n terms in one lane; it is accepted (DESIGN 9.20 has its time). */
+int ms_bow_vector(ms_ctx *ctx, const int32_t *word, const double *weight, int n, int vocab_words, int cap,
+                  int32_t *words, double *values, int32_t *counts);
+/* the twin is named _validate: the set of ms_*_check functions is closed at 22 (tests/test_map_checks_corpus.py records them) */
+int ms_bow_vector_validate(const int32_t *word, const double *weight, int n, int vocab_words, int cap,
+                           const int32_t *words, const double *values, const int32_t *counts, char *why, size_t why_bytes);
+/* BowIndex::add (bow_index.cpp:44-48) for a keyframe whose descent lies on the DEVICE (word_dev / weight_dev [n], n <=
+ * MS_COVIS_MAX_STRIDE; ms_keyframe_admit_words hands them out): a duplicate id is refused on the host before any device work; room for
+ * the bound of n words is reserved at the pool top by the code path of ms_bow_db_add (compaction, growth); the launch of ms_bow_vector
+ * on the database's context packs the vector straight into the segment; the 8-byte head comes down in one synchronisation and only
+ * then is the entry committed, with the cells of its real length.  No upload but the 24-byte entry row.  *n_words (may be NULL) = the
+ * entry's length.  MS_ERR_INVALID, database unchanged (a following query is bit-identical to one before the call), when n_bad > 0,
+ * for a duplicate id, a negative n, a missing array; MS_ERR_CAPACITY for n beyond the cap.  n_words = 0 is an entry like
+ * ms_bow_db_add's n = 0.  Synchronous. */
+int ms_bow_db_add_words(ms_bow_db *db, int32_t map_id, int32_t kf_id, const int32_t *word_dev, const double *weight_dev, int n,
+                        int32_t *n_words);
+/* Downloads a live entry's vector (what keyframe.shared->bowVec held, e.g. for serialization) into HOST words_host / values_host
+ * [cap]; *n = its length.  MS_ERR_INVALID when (map_id, kf_id) is not live; MS_ERR_CAPACITY with the length in *n when cap is too
+ * small (nothing is written).  Synchronous. */
+int ms_bow_db_entry(ms_bow_db *db, int32_t map_id, int32_t kf_id, int cap, int32_t *words_host, double *values_host, int *n);
 
 /* ---- N4: loop-closure RANSAC behind LoopRansac::ransacSolve (loop_ransac.cpp:8-314) --------------------------------------
  * Camera stand-in: tracker::Camera lives in the parent project, outside the reference tree, so the reprojection of
@@ -1770,8 +1813,10 @@ int ms_frame_finish_validate(const int32_t *kf_mp, int n_kf, int stride, const u
  * FOUR launches whatever the sizes (descent and head; verdicts; ranks and every write; node lists), at most one upload block (the track
  * lists; none without them), ONE download, one host wait.  Synchronous on the context stream, behind ms_orb_extract.  The workspace belongs
  * to the context and only grows: nothing is allocated after warm-up (ms_debug_host_allocs).  The same inputs give the same bytes on every
- * call.  Not covered: the keypoints of frames that are no keyframe (addTrackerFeatures: host data of the tracker), colours (getPixel),
- * the BowVector itself (ms_bow_db_add takes host arrays), reuse of pool space when keyframes leave. */
+ * call.  The BowVector itself is not built here: ms_bow_db_add takes host arrays, so a caller either takes word / weight down and sums on the
+ * host, or leaves them NULL and hands the descent to ms_bow_db_add_words where it lies (ms_keyframe_admit_words).
+ * Not covered: the keypoints of frames that are no keyframe (addTrackerFeatures: host data of the tracker), colours (getPixel),
+ * reuse of pool space when keyframes leave. */
 typedef struct {
     int32_t slot;                        /* the keyframe's slot in kf_mp, the keypoint table and kf_pose */
     int32_t desc_base;                   /* index of keypoint 0 in desc_pool */
@@ -1822,6 +1867,11 @@ int ms_keyframe_admit_validate(const ms_keypoints *view, int frame,
     const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth,
     const uint32_t *desc_pool, int n_pool, const double *kf_pose,
     const ms_admit_args *args, const ms_admit_frame *out, const ms_admit_host *host, const int32_t *counts, char *why, size_t why_bytes);
+/* The descent of the context's latest successful ms_keyframe_admit where it lies: *word (int32) / *weight (float64) are
+ * DEVICE arrays of that call's workspace, *n = its n (without a vocabulary word = -1, weight = 0).  The pointers are valid until the
+ * next ms_keyframe_admit on that context.  What ms_bow_db_add_words takes: a caller that uses it passes NULL for the admission's host
+ * word / weight.  MS_ERR_INVALID (NULL, NULL, 0) before the first admit and after an admit that returned an error. */
+int ms_keyframe_admit_words(ms_ctx *ctx, const int32_t **word, const double **weight, int32_t *n);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,9 @@
 //   k_bowdb_merge  only when a query has more than 4096 candidates: every kept element's rank is its position in its sorted chunk plus
 //                  the number of elements before it in each other chunk (binary search); ranks are unique because ids are
 //
+//   k_bow_vector   (bow_vector.hip) for ms_bow_db_add_words: the BowVector of a descent that lies on the device, assembled and packed
+//                  straight into the segment reserved at the pool top; the host commits the entry after the 8-byte head has come down
+//
 // Counting and scoring stay two passes: minInCommon depends on the maximum over all entries, so a fused pass would score every
 // entry that shares a single word.  Every step is integer or an ordered double sum, so results do not depend on scheduling.
 #include "ms_internal.h"
@@ -272,6 +275,7 @@ struct ms_bow_db {
     // device scratch of the queries (grow-only)
     struct Buf { void *p = nullptr; size_t bytes = 0; };
     Buf d_qdesc, d_qvec, d_state, d_common, d_cand, d_chunk, d_result, d_moves;
+    Buf d_head;                                  // {n_words, n_bad} of ms_bow_db_add_words
     // page-locked staging: uploads are appended, the arena is reused after the stream has been synchronised; downloads land in `out`
     uint8_t *stage = nullptr;
     size_t stage_cap = 0, stage_pos = 0;
@@ -530,7 +534,7 @@ void ms_bow_db_destroy(ms_bow_db *db) {
     if (!db) return;
     (void)hipStreamSynchronize(db->ctx->stream);
     for (void *p : {(void *)db->d_ent, (void *)db->d_pool[0], (void *)db->d_pool[1], db->d_qdesc.p, db->d_qvec.p, db->d_state.p, db->d_common.p,
-                    db->d_cand.p, db->d_chunk.p, db->d_result.p, db->d_moves.p})
+                    db->d_cand.p, db->d_chunk.p, db->d_result.p, db->d_moves.p, db->d_head.p})
         if (p) (void)hipFree(p);
     if (db->stage) (void)hipHostFree(db->stage);
     if (db->outp) (void)hipHostFree(db->outp);
@@ -564,6 +568,70 @@ int ms_bow_db_add(ms_bow_db *db, int32_t map_id, int32_t kf_id, int n, const int
     db->live_cells += cells;
     ++db->n_live;
     hash_insert(db, key, slot);
+    return MS_OK;
+}
+
+// BowIndex::add for a keyframe whose descent lies on the device: the segment is reserved for the bound of n words, k_bow_vector
+// assembles the vector straight into it, and the host commits the entry only after the head {n_words, n_bad} has come down.
+int ms_bow_db_add_words(ms_bow_db *db, int32_t map_id, int32_t kf_id, const int32_t *word_dev, const double *weight_dev, int n, int32_t *n_words) {
+    if (!db) return MS_ERR_INVALID;
+    ms_ctx *c = db->ctx;
+    if (n_words) *n_words = 0;
+    if (n < 0 || (n > 0 && (!word_dev || !weight_dev))) return ms_fail(c, MS_ERR_INVALID, "bow db add words: n = %d with missing arrays", n);
+    if (n > MS_COVIS_MAX_STRIDE) return ms_fail(c, MS_ERR_CAPACITY, "bow db add words: %d keypoints, cap %d", n, MS_COVIS_MAX_STRIDE);
+    if (reinterpret_cast<uintptr_t>(weight_dev) & 7u) return ms_fail(c, MS_ERR_INVALID, "bow db add words: weight must be 8-byte aligned");
+    const uint64_t key = id_key(map_id, kf_id);
+    if (find_slot(db, key) >= 0) return ms_fail(c, MS_ERR_INVALID, "bow db add words: (%d, %d) is already in the database", map_id, kf_id);
+    MsRange range("bowIndexAddWords");
+    MS_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if (db->n_free == 0 && (rc = reserve_entries(db, db->n_slots + 1))) return rc;
+    if ((rc = reserve_pool(db, seg_cells(n)))) return rc;                         // the bound: at most n words
+    if ((rc = grow_dev(db, db->d_head, 16)) || (rc = grow_pinned(db, db->outp, db->out_cap, 16))) return rc;
+    int32_t *head = static_cast<int32_t *>(db->d_head.p);
+    if ((rc = ms_bow_vector_enqueue(c, word_dev, weight_dev, n, db->n_words, n, nullptr, nullptr, db->d_pool[0] + db->pool_top, head))) return rc;
+    MS_HIP(c, hipMemcpyAsync(db->outp, head, 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = sync_stream(db))) return rc;
+    const int32_t len = reinterpret_cast<const int32_t *>(db->outp)[0], n_bad = reinterpret_cast<const int32_t *>(db->outp)[1];
+    if (n_bad > 0)
+        return ms_fail(c, MS_ERR_INVALID, "bow db add words: %d kept keypoints have a word outside [0, %d) or a value that is not finite (the database is unchanged)", n_bad,
+                       db->n_words);
+    if (len < 0 || len > n) return ms_fail(c, MS_ERR_HIP, "bow db add words: the device counted %d words of %d keypoints", len, n);
+    // ---- the commit: nothing above changed what a query sees
+    const int slot = db->n_free > 0 ? db->free_slots[(size_t)db->n_free - 1] : db->n_slots;
+    const DbEntry e{db->pool_top, len, map_id, kf_id, 1};
+    if ((rc = upload(db, db->d_ent + slot, &e, sizeof(DbEntry)))) return rc;
+    if (db->n_free > 0) --db->n_free; else ++db->n_slots;
+    db->ent[(size_t)slot] = e;
+    const long long cells = seg_cells(len);                                       // the unused tail of the bound is not consumed
+    db->pool_top += cells;
+    db->live_cells += cells;
+    ++db->n_live;
+    hash_insert(db, key, slot);
+    if (n_words) *n_words = len;
+    return MS_OK;
+}
+
+// A live entry's vector, downloaded: what keyframe.shared->bowVec held.
+int ms_bow_db_entry(ms_bow_db *db, int32_t map_id, int32_t kf_id, int cap, int32_t *words_host, double *values_host, int *n) {
+    if (!db) return MS_ERR_INVALID;
+    ms_ctx *c = db->ctx;
+    if (!n || cap < 0 || (cap > 0 && (!words_host || !values_host))) return ms_fail(c, MS_ERR_INVALID, "bow db entry: cap = %d with missing arrays", cap);
+    *n = 0;
+    const int slot = find_slot(db, id_key(map_id, kf_id));
+    if (slot < 0) return ms_fail(c, MS_ERR_INVALID, "bow db entry: (%d, %d) is not in the database", map_id, kf_id);
+    const DbEntry &e = db->ent[(size_t)slot];
+    *n = e.len;
+    if (e.len > cap) return ms_fail(c, MS_ERR_CAPACITY, "bow db entry: (%d, %d) has %d words, the arrays hold %d", map_id, kf_id, e.len, cap);
+    if (e.len == 0) return MS_OK;
+    MS_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = 8 * (size_t)seg_cells(e.len);
+    int rc;
+    if ((rc = grow_pinned(db, db->outp, db->out_cap, bytes))) return rc;
+    MS_HIP(c, hipMemcpyAsync(db->outp, db->d_pool[0] + e.off, bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = sync_stream(db))) return rc;
+    std::memcpy(words_host, db->outp, 4 * (size_t)e.len);
+    std::memcpy(values_host, db->outp + 8 * (size_t)((e.len + 1) >> 1), 8 * (size_t)e.len);
     return MS_OK;
 }
 

@@ -233,6 +233,7 @@ extern "C" int ms_keyframe_admit(ms_ctx *c, const ms_keypoints *view, int frame,
                                  int32_t *kp_octave, float *kp_depth, uint32_t *desc_pool, int n_pool, double *kf_pose, const ms_admit_args *args,
                                  const ms_admit_frame *out, const ms_admit_host *host, int32_t *counts) {
     if (!c) return MS_ERR_INVALID;
+    c->admit_n = -1;                                         // ms_keyframe_admit_words: nothing to hand out until this call has succeeded
     int rc;
     if ((rc = ms_keyframe_admit_validate(view, frame, kf_mp, n_kf, stride, n_mp, kp_x, kp_y, kp_octave, kp_depth, desc_pool, n_pool, kf_pose, args, out, host, counts, c->err,
                                          sizeof(c->err))))
@@ -326,5 +327,16 @@ extern "C" int ms_keyframe_admit(ms_ctx *c, const ms_keypoints *view, int frame,
     if (H.sorted_idx) l_dsidx.get(ps, 0, H.sorted_idx, m);
     if (H.octave) l_doct.get(ps, 0, H.octave, m);
     if (H.desc) l_ddesc.get(ps, 0, H.desc, 8 * m);
+    c->admit_word = A.word; c->admit_weight = A.weight; c->admit_n = n;
+    return MS_OK;
+}
+
+// The descent of the latest successful ms_keyframe_admit where it lies in the workspace: what ms_bow_db_add_words takes.
+extern "C" int ms_keyframe_admit_words(ms_ctx *c, const int32_t **word, const double **weight, int32_t *n) {
+    if (!c) return MS_ERR_INVALID;
+    if (!word || !weight || !n) return ms_fail(c, MS_ERR_INVALID, "keyframe admit words: missing output");
+    *word = nullptr; *weight = nullptr; *n = 0;
+    if (c->admit_n < 0) return ms_fail(c, MS_ERR_INVALID, "keyframe admit words: no successful ms_keyframe_admit on this context since the last one that failed");
+    *word = c->admit_word; *weight = c->admit_weight; *n = c->admit_n;
     return MS_OK;
 }

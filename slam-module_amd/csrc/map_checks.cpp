@@ -1,5 +1,5 @@
 // map_checks.cpp -- the host validation of every call on the device map tables: the 22 exported ms_*_check functions, in the order of
-// mi355slam.h, and ms_frame_finish_validate and ms_keyframe_admit_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
+// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate and ms_bow_vector_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
 // calls it with the context's error buffer.  Plain C++17, no HIP and no context: the checks read the HOST arguments only and ask of the DEVICE
 // arrays nothing but whether they are there, so this file compiles alone and runs under sanitizers (tests/map_checks_corpus.cpp).  The first
 // failing statement decides the message, so the order of the statements inside a function is part of the interface.
@@ -817,5 +817,19 @@ extern "C" int ms_keyframe_admit_validate(const ms_keypoints *view, int frame, c
     if (args->depth_image && ((long long)args->depth_stride * args->depth_height > 0x7fffffffLL))
         return ms_why(MS_ERR_CAPACITY, why, why_bytes, "keyframe admit: a depth image of %d rows of %d elements, caps below 2^31 elements", args->depth_height, args->depth_stride);
     if (ms_map_over_capacity(n_kf, stride, n_mp, 0)) return ms_why_table_caps("keyframe admit", n_kf, stride, n_mp, why, why_bytes);
+    return MS_OK;
+}
+
+// ms_bow_vector.  word / weight / words / values are DEVICE arrays: only their presence and alignment is looked at.
+extern "C" int ms_bow_vector_validate(const int32_t *word, const double *weight, int n, int vocab_words, int cap, const int32_t *words, const double *values,
+                                      const int32_t *counts, char *why, size_t why_bytes) {
+    if (n < 0 || cap < 0) INVALID("bow vector: negative size (%d keypoints, cap %d)", n, cap);
+    if (vocab_words < 1) INVALID("bow vector: a vocabulary of %d words", vocab_words);
+    if (!counts) INVALID("bow vector: missing array (counts)");
+    if (n > 0 && (!word || !weight)) INVALID("bow vector: missing array (word or weight with %d keypoints)", n);
+    if (cap > 0 && (!words || !values)) INVALID("bow vector: missing array (words or values with cap %d)", cap);
+    if ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(values)) & 7u) INVALID("bow vector: weight and values must be 8-byte aligned");
+    if (n > MS_COVIS_MAX_STRIDE || cap > MS_COVIS_MAX_STRIDE)
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "bow vector: %d keypoints / cap %d, caps %d each", n, cap, MS_COVIS_MAX_STRIDE);
     return MS_OK;
 }

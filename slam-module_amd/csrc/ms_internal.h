@@ -32,6 +32,7 @@ enum MsWorkspaceId {
     MS_WS_LOOP_CHAIN,       // ms_loop_usable_mask, ms_loop_pairs and ms_loop_sim3_lists (loop_chain.hip): device slot / candidate records, sigmas, match lists; counts; the block that goes down
     MS_WS_FRAME_FINISH,     // ms_frame_finish (frame_finish.hip): device list positions / list; first claims / remaining entries / block counts; the block that goes down
     MS_WS_KEYFRAME_ADMIT,   // ms_keyframe_admit (keyframe_admit.hip): device track ids / depths; word / weight / node / track index / sorted nodes; the block that goes down
+    MS_WS_BOW_VECTOR,       // ms_bow_vector (bow_vector.hip): the device head {n_words, n_bad} that goes down
     MS_WS_COUNT
 };
 
@@ -83,6 +84,10 @@ struct ms_ctx {
     void *ba_handle_pool[4] = {nullptr, nullptr, nullptr, nullptr};      // destroyed bundle-adjustment handle OBJECTS (their vectors keep their capacity, their event stays): ms_ba_create takes one back
     // grow-only workspaces of the map-side entry points: a device block and its page-locked staging each (ms_grow; laid out with ms_layout.h)
     MsWorkspace ws[MS_WS_COUNT];
+    // the descent of the latest successful ms_keyframe_admit where it lies in that call's workspace (ms_keyframe_admit_words); admit_n = -1: none
+    const int32_t *admit_word = nullptr;
+    const double *admit_weight = nullptr;
+    int32_t admit_n = -1;
     char err[512] = {0};
 };
 
@@ -101,6 +106,12 @@ struct MsBaPoseIo {
 int ms_ba_pose_tables_create(ms_ctx *ctx, int cap_obs, ms_ba **out, MsBaPoseIo *io);
 int ms_ba_pose_tables_launch(ms_ba *ba);   // k_ba_pose_only on the handle's problem as the device holds it: one launch, nothing else
 int ms_ba_pose_tables_wait(ms_ba *ba);     // records the handle's event behind everything enqueued so far and waits for it politely (ba_wait_event)
+
+// bow_vector.hip, for bowdb.hip: enqueues k_bow_vector on the context stream, nothing else.  word / weight [n] and head [2] =
+// {n_words, n_bad} are DEVICE arrays, 0 <= n <= MS_COVIS_MAX_STRIDE.  With seg the vector goes into seg in the word pool's layout (ceil(len / 2)
+// cells of words, then len cells of values; seg holds the cells of n words) and words / values are not used.
+int ms_bow_vector_enqueue(ms_ctx *ctx, const int32_t *word, const double *weight, int n, int vocab_words, int cap, int32_t *words, double *values,
+                          unsigned long long *seg, int32_t *head);
 
 // page-locked host staging of at least `bytes` in ctx->pinned (contents are valid until the next call that uses it)
 int ms_pinned(ms_ctx *ctx, size_t bytes);

@@ -6,7 +6,9 @@
 // maps on the host in feature order, exactly as DBoW2's batch transform does: v[word] += weight and fv[node].push_back(i) for
 // weight > 0, then BowVector::normalize(L1).  add / remove / getBowSimilar (bow_index.cpp:44-57, :95-176) go to the device
 // keyframe database (ms_bow_db), created on the first add: the reference's inverted index std::vector<std::list<MapKf>> and
-// DBoW2's L1 scoring are replaced, and the results are the reference's (ties in score in (mapId, kfId) order).
+// DBoW2's L1 scoring are replaced, and the results are the reference's (ties in score in (mapId, kfId) order).  A keyframe whose
+// descent lies on the device (ms_keyframe_admit) enters the database without a host vector: addAdmitted / addWords have the device
+// do assembleVector's sums in assembleVector's order (ms_bow_db_add_words), bowVector brings an entry back.
 #pragma once
 #include <cmath>
 #include <fstream>
@@ -137,6 +139,42 @@ public:
         ctx_.check(ms_bow_db_add(db_, mapKf.mapId, mapKf.kfId, (int)qWords_.size(), qWords_.data(), qValues_.data()), "ms_bow_db_add");
     }
 
+    // add for a keyframe whose descent lies on the DEVICE (ms_bow_db_add_words): wordDev / weightDev [n] as ms_bow_transform and
+    // ms_keyframe_admit write them.  The device does assembleVector's sums in assembleVector's order and packs the vector into the
+    // database's pool; no host vector exists.  Returns the entry's number of words.
+    int addWords(const std::int32_t *wordDev, const double *weightDev, int n, MapKf mapKf) {
+        requireL1();
+        ensureDatabase();
+        std::int32_t nWords = 0;
+        ctx_.check(ms_bow_db_add_words(db_, mapKf.mapId, mapKf.kfId, wordDev, weightDev, n, &nWords), "ms_bow_db_add_words");
+        return (int)nWords;
+    }
+
+    // add for the keyframe the context's latest ms_keyframe_admit admitted (admitKeyframe, or a direct call that passed NULL for the
+    // admission's host word / weight): the descent is taken where that call left it (ms_keyframe_admit_words)
+    int addAdmitted(MapKf mapKf) {
+        const std::int32_t *word = nullptr;
+        const double *weight = nullptr;
+        std::int32_t n = 0;
+        ctx_.check(ms_keyframe_admit_words(ctx_.get(), &word, &weight, &n), "ms_keyframe_admit_words");
+        return addWords(word, weight, (int)n, mapKf);
+    }
+
+    // a live entry's BowVector, downloaded (ms_bow_db_entry): what keyframe.shared->bowVec held, e.g. for serialization
+    BowVector bowVector(MapKf mapKf) {
+        ensureDatabase();
+        int n = 0;
+        for (;;) {
+            entryWords_.resize(entryCap_); entryValues_.resize(entryCap_);
+            const int rc = ms_bow_db_entry(db_, mapKf.mapId, mapKf.kfId, (int)entryCap_, entryWords_.data(), entryValues_.data(), &n);
+            if (rc != MS_ERR_CAPACITY) { ctx_.check(rc, "ms_bow_db_entry"); break; }
+            entryCap_ = (std::size_t)n;
+        }
+        BowVector v;
+        for (int i = 0; i < n; ++i) v.emplace_hint(v.end(), (unsigned)entryWords_[(std::size_t)i], entryValues_[(std::size_t)i]);
+        return v;
+    }
+
     // bow_index.cpp:50-57
     void remove(MapKf mapKf) {
         if (db_) ctx_.check(ms_bow_db_remove(db_, mapKf.mapId, mapKf.kfId), "ms_bow_db_remove");
@@ -166,6 +204,9 @@ private:
         if (scoring_ != 0)
             throw std::runtime_error("mi355slam: BowIndex add / getBowSimilar support L1 scoring only (vocabulary scoring type " + std::to_string(scoring_) + ")");
     }
+    void ensureDatabase() {                                                       // the sizes add() creates it with
+        if (!db_) ctx_.check(ms_bow_db_create(ctx_.get(), std::max(nWords_, 1), 1024, 1024ll * 500, &db_), "ms_bow_db_create");
+    }
     void flatten(const BowVector &v) {
         qWords_.clear(); qValues_.clear();
         for (const auto &kv : v) { qWords_.push_back((std::int32_t)kv.first); qValues_.push_back(kv.second); }
@@ -191,6 +232,9 @@ private:
     std::vector<double> qValues_;
     std::vector<float> outScore_;
     std::size_t outCap_ = 64;
+    std::vector<std::int32_t> entryWords_;                                        // bowVector's download
+    std::vector<double> entryValues_;
+    std::size_t entryCap_ = 512;
     DeviceArray<std::uint32_t> d_desc_;
     DeviceArray<std::int32_t> d_word_, d_node_;
     DeviceArray<double> d_weight_;

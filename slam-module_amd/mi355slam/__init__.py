@@ -587,6 +587,38 @@ class BowDatabase:
         w, v = self._vec(words, values)
         self.ctx.check(lib().ms_bow_db_add(self._h, int(map_id), int(kf_id), len(w), w.ctypes.data_as(i32p), v.ctypes.data_as(f64p)), "ms_bow_db_add")
 
+    def add_words_device(self, map_id, kf_id, word, weight, n):
+        """ms_bow_db_add_words without raising: word / weight = DEVICE arrays (DevBufs or pointers) of a descent.  Returns (rc, n_words)."""
+        nw = C.c_int32(0)
+        rc = lib().ms_bow_db_add_words(self._h, int(map_id), int(kf_id), _vp(word), _vp(weight), int(n), C.byref(nw))
+        return rc, nw.value
+
+    def add_words(self, map_id, kf_id, word, weight, n=None):
+        """BowIndex::add for a keyframe whose descent lies on the device (ms_bow_db_add_words): word (int32) / weight (float64) per keypoint,
+        DevBufs or pointers with n given (keyframe_admit_words' triple), or host arrays, which are uploaded first.  Returns the entry's length."""
+        if isinstance(word, np.ndarray) or isinstance(weight, np.ndarray) or n is None:
+            word, weight, n = _descent_on_device(self.ctx, word, weight)
+        rc, nw = self.add_words_device(map_id, kf_id, word, weight, n)
+        self.ctx.check(rc, "ms_bow_db_add_words")
+        return nw
+
+    def entry_device(self, map_id, kf_id, cap):
+        """ms_bow_db_entry without raising.  Returns (rc, n, words [cap], values [cap])."""
+        w, v, n = np.full(max(cap, 1), -7, np.int32), np.full(max(cap, 1), -7.0, np.float64), C.c_int(0)
+        rc = lib().ms_bow_db_entry(self._h, int(map_id), int(kf_id), int(cap), w.ctypes.data_as(i32p), v.ctypes.data_as(f64p), C.byref(n))
+        return rc, n.value, w[:cap], v[:cap]
+
+    def entry(self, map_id, kf_id):
+        """A live entry's BowVector, downloaded: (words int32, values float64)."""
+        cap = 512
+        for attempt in range(2):
+            rc, n, w, v = self.entry_device(map_id, kf_id, cap)
+            if rc != MS_ERR_CAPACITY:
+                self.ctx.check(rc, "ms_bow_db_entry")
+                return w[:n].copy(), v[:n].copy()
+            cap = n
+        raise MsError("ms_bow_db_entry: the entry grew between two calls")
+
     def remove(self, map_id, kf_id):
         self.ctx.check(lib().ms_bow_db_remove(self._h, int(map_id), int(kf_id)), "ms_bow_db_remove")
 
@@ -1437,6 +1469,62 @@ def keyframe_admit(ctx, view, frame, kf_table, n_mp, kp, pool, poses, args, out,
     rc, res = keyframe_admit_device(ctx, view, frame, tables, kf_table.n_kf, kf_table.stride, n_mp, pool.nbytes // 32, args, out, host)
     ctx.check(rc, "ms_keyframe_admit")
     return res
+
+
+def keyframe_admit_words_device(ctx):
+    """ms_keyframe_admit_words without raising.  Returns (rc, word pointer, weight pointer, n): DEVICE arrays of the latest successful
+    keyframe_admit on ctx, valid until its next one."""
+    w, wt, n = C.c_void_p(0), C.c_void_p(0), C.c_int32(0)
+    rc = lib().ms_keyframe_admit_words(ctx._h, C.byref(w), C.byref(wt), C.byref(n))
+    return rc, w.value or 0, wt.value or 0, n.value
+
+
+def keyframe_admit_words(ctx):
+    """The descent of the latest successful keyframe_admit where it lies on the device: (word pointer, weight pointer, n), what
+    BowDatabase.add_words and bow_vector take.  Raises MsError before the first admit and after one that failed."""
+    rc, w, wt, n = keyframe_admit_words_device(ctx)
+    ctx.check(rc, "ms_keyframe_admit_words")
+    return w, wt, n
+
+
+def _descent_on_device(ctx, word, weight):
+    """host word / weight -> (DevBuf, DevBuf, n); the buffers are never empty"""
+    w, wt = _i32(word), np.ascontiguousarray(weight, np.float64).reshape(-1)
+    if len(w) != len(wt):
+        raise ValueError("word and weight differ in length")
+    return ctx.upload(w if len(w) else np.zeros(1, np.int32)), ctx.upload(wt if len(wt) else np.zeros(1, np.float64)), len(w)
+
+
+def bow_vector_validate(word, weight, n, vocab_words, cap, words, values, counts=True):
+    """ms_bow_vector_validate, the host half of ms_bow_vector (no context, no device): arrays, DevBufs, pointers or None -- only their presence
+    and alignment is looked at.  Returns (rc, message)."""
+    why, cnt = C.create_string_buffer(512), np.zeros(2, np.int32)
+    rc = lib().ms_bow_vector_validate(_vp(word), _vp(weight), int(n), int(vocab_words), int(cap), _vp(words), _vp(values), _vp(cnt if counts else None), why,
+                                      C.c_size_t(512))
+    return rc, why.value.decode()
+
+
+def bow_vector_device(ctx, word, weight, n, vocab_words, cap, words, values):
+    """ms_bow_vector without raising: every array a DEVICE array (DevBuf or pointer).  Returns (rc, n_words, n_bad)."""
+    counts = np.zeros(2, np.int32)
+    rc = lib().ms_bow_vector(ctx._h, _vp(word), _vp(weight), int(n), int(vocab_words), int(cap), _vp(words), _vp(values), _vp(counts))
+    return rc, int(counts[0]), int(counts[1])
+
+
+def bow_vector(ctx, word, weight, n, vocab_words):
+    """The keyframe's BowVector assembled on the device (ms_bow_vector): word (int32) / weight (float64) per keypoint as DevBufs or pointers
+    (keyframe_admit_words' arrays), or host arrays, which are uploaded first; n of them are read.  Returns (words int32, values float64)."""
+    if isinstance(word, np.ndarray) or isinstance(weight, np.ndarray):
+        word, weight, m = _descent_on_device(ctx, np.asarray(word)[:n], np.asarray(weight)[:n])
+        if m != n:
+            raise ValueError("n = %d, the arrays hold %d" % (n, m))
+    cap = max(int(n), 1)
+    dw, dv = ctx.alloc(4 * cap), ctx.alloc(8 * cap)
+    rc, n_words, n_bad = bow_vector_device(ctx, word, weight, n, vocab_words, min(cap, 8192), dw, dv)
+    ctx.check(rc, "ms_bow_vector")
+    out = dw.download(np.int32, (cap,))[:n_words].copy(), dv.download(np.float64, (cap,))[:n_words].copy()
+    dw.free(); dv.free()
+    return out
 
 
 class KeyframeTable:
