@@ -1873,6 +1873,95 @@ int ms_keyframe_admit_validate(const ms_keypoints *view, int frame,
  * word / weight.  MS_ERR_INVALID (NULL, NULL, 0) before the first admit and after an admit that returned an error. */
 int ms_keyframe_admit_words(ms_ctx *ctx, const int32_t **word, const double **weight, int32_t *n);
 
+/* ---- the partial map copy for the front end on the device map tables -------------------------------------------------------
+ * copyMap (mapper.cpp:281-326) with copyPartialMapToFrontend: MapDB(mapDB, activeKeyframes) (mapdb.cpp:116-159) and MapPoint(mp,
+ * activeKeyframes) (map_point.cpp:22-43).  ms_map_extract gathers the ACTIVE keyframes of a SOURCE set of tables (9.4 - 9.19) into a
+ * DESTINATION set, compacted; the source is never written.  tests/map_extract_ref.py restates the call and is its specification.
+ *
+ * PRESENT and VALID as in 9.18: (uint32)r < n_mp is valid; valid and mp_live[r] != 0 (src->mp_live == NULL: every row is live) is present.
+ * `active` [n_active] (HOST) lists source slots; destination slot i is active[i] (the caller passes ascending KfId, the std::set's order; any
+ * order is taken).  A source row is ACTIVE iff some entry of an active slot names it and it is present.  Active rows are numbered
+ * 0 .. n_rows - 1 in ascending source-row order (the walk of std::set<MpId> activeMapPoints): row_src[d] = the source row of destination
+ * row d, row_dst[r] = d, or -1 for a row that is not active.
+ * Destination row d < n_rows: mp_pos, mp_norm, mp_min_dist, mp_max_dist, mp_desc, mp_flags and mp_track copied bit for bit; mp_live = 1;
+ *   n_obs[d] = the number of valid entries equal to the row in the active slots, with multiplicity (ms_observation_count's definition: the
+ *   size of the observation map after map_point.cpp:32-36).  Rows [n_rows, dst->n_mp): mp_live = 0, mp_flags = 0, mp_track = -1, n_obs = 0;
+ *   their other fields keep their bytes.
+ * Destination slot i < n_active: entry j = row_dst[r] for a present r, else -1 (an entry that is -1, out of range, or valid but not live:
+ *   the reference's mapPoints.at would throw on the last kind; here it is dropped and counted).  kp_x, kp_y, kp_octave, kp_depth (all
+ *   `stride` entries) and the 12 doubles of kf_pose copied bit for bit.  Slots [n_active, dst->n_kf): every entry -1, the keypoint arrays
+ *   0; their poses keep their bytes.  These are empty slots a frame can be admitted into.
+ * Tracks (mapdb.cpp:141-145 under the presence rule of 9.11): dst track_row[t] = row_dst[r] where the source has track_row[t] = r, r
+ *   present, mp_track[r] == track_base + t and r active; otherwise -1.  Both sides share track_base and n_track.
+ * Pool: the n_kp[i] descriptors at desc_base[active[i]] go to dst_desc_base[i], the running sum of the n_kp of the active slots with
+ *   desc_base >= 0, in list order; dst_desc_base[i] = -1 for a slot with desc_base < 0, and for every slot without a pool.
+ * counts [5]: n_rows, entries kept, valid entries dropped because their row is not live, tracks kept, descriptors copied.
+ * Left to the caller, as for ms_map_cull and ms_frame_finish: the previous / next links, referenceKeyframe (map_point.cpp:38-42), the
+ * scalar members of mapdb.cpp:150-158, bowIndex and the per-slot host records.  Ordering between contexts is the caller's: the source
+ * tables must be quiescent while the call runs (the reference's frontendMapMutex).  The call runs on the stream of `ctx`.
+ *
+ * Optional arrays: mp_live (source only), mp_track, the four keypoint arrays (all or none), kf_pose, track_row (requires mp_track),
+ * desc_pool -- each on both sides or on neither; n_obs, row_src, row_dst of the destination may each be NULL.
+ * MS_ERR_INVALID, nothing written, before any device call: an active slot out of range, listed twice or with kf_id < 0; a non-negative
+ * kf_id listed twice; n_active > dst->n_kf; n_kp[i] outside [0, stride]; a pool slice outside src->pool_size; the sum of the slices beyond
+ * dst->pool_size; track_row without mp_track; an optional array on one side only or only some of the keypoint arrays; a destination pointer
+ * equal to its source pointer; descriptor arrays that are not 16-byte aligned; stride < 1, a negative size, a missing array.  MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (both table
+ * sizes; n_track: MS_TRACKED_MAX_WINDOW), and when n_rows > dst->n_mp: then no DEVICE array of the destination
+ * is written, while both HOST outputs are: counts holds the needed numbers (all five) and dst_desc_base the pool offsets, neither of which
+ * depends on the row capacity -- every verdict is taken before a table is written (the rule of ms_ba_window_apply and ms_frame_finish).
+ * n_active == 0 is fine: an empty destination.
+ * Per call: one upload block (the list, the keypoint counts, the pool offsets of both sides), at most NINE launches whatever the sizes
+ * (fill, mark, count, offsets, place, rows, slots, tracks, pool; the last two only with their arrays), no host wait between them, ONE
+ * download (counts) through the context's pinned block.  Every position is a prefix count and every atomic is an integer add: the same
+ * tables give the same bytes on every call.  Nothing is allocated after warm-up.
+ * ms_map_extract_validate is the host validation alone (no context, no device; `why` receives the message). */
+typedef struct {                         /* DEVICE arrays of the source, never written */
+    const int32_t *kf_mp;                /* [n_kf * stride] */
+    const uint8_t *mp_flags, *mp_live;   /* [n_mp]; mp_live may be NULL */
+    const double *mp_pos;                /* [n_mp * 3] */
+    const float *mp_norm;                /* [n_mp * 3] */
+    const float *mp_min_dist, *mp_max_dist;
+    const uint32_t *mp_desc;             /* [n_mp * 8] */
+    const int32_t *mp_track;             /* [n_mp], may be NULL */
+    const float *kp_x, *kp_y;            /* [n_kf * stride], all four or none */
+    const int32_t *kp_octave;
+    const float *kp_depth;
+    const double *kf_pose;               /* [n_kf * 12], may be NULL */
+    const int32_t *track_row;            /* [n_track], may be NULL */
+    const uint32_t *desc_pool;           /* [pool_size * 8], may be NULL */
+    int32_t n_kf, stride, n_mp, track_base, n_track, pool_size;
+} ms_map_extract_src;
+typedef struct {                         /* DEVICE arrays of the destination; stride, track_base and n_track are the source's */
+    int32_t *kf_mp;                      /* [n_kf * stride] */
+    uint8_t *mp_flags, *mp_live;         /* [n_mp] */
+    double *mp_pos;
+    float *mp_norm;
+    float *mp_min_dist, *mp_max_dist;
+    uint32_t *mp_desc;
+    int32_t *mp_track;
+    float *kp_x, *kp_y;
+    int32_t *kp_octave;
+    float *kp_depth;
+    double *kf_pose;
+    int32_t *track_row;
+    uint32_t *desc_pool;
+    int32_t *n_obs;                      /* [n_mp], may be NULL */
+    int32_t *row_src;                    /* [n_mp], may be NULL */
+    int32_t *row_dst;                    /* [src->n_mp], may be NULL */
+    int32_t n_kf, n_mp, pool_size;       /* slots >= n_active, row capacity, pool capacity in descriptors */
+} ms_map_extract_dst;
+int ms_map_extract(ms_ctx *ctx,
+    /* HOST structs of DEVICE arrays */
+    const ms_map_extract_src *src, const ms_map_extract_dst *dst,
+    /* HOST: kf_id [src->n_kf], active [n_active]; with a pool desc_base [src->n_kf] and n_kp [n_active] */
+    const int32_t *kf_id, const int32_t *active, int n_active, const int32_t *desc_base, const int32_t *n_kp,
+    /* HOST outputs: dst_desc_base [n_active], counts [5] */
+    int32_t *dst_desc_base, int32_t *counts);
+/* the twin is named _validate: the set of ms_*_check functions is closed at 22 (tests/test_map_checks_corpus.py records them) */
+int ms_map_extract_validate(const ms_map_extract_src *src, const ms_map_extract_dst *dst,
+    const int32_t *kf_id, const int32_t *active, int n_active, const int32_t *desc_base, const int32_t *n_kp,
+    const int32_t *dst_desc_base, const int32_t *counts, char *why, size_t why_bytes);
+
 #ifdef __cplusplus
 }
 #endif

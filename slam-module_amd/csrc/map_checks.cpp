@@ -1,5 +1,5 @@
 // map_checks.cpp -- the host validation of every call on the device map tables: the 22 exported ms_*_check functions, in the order of
-// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate and ms_bow_vector_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
+// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate, ms_bow_vector_validate and ms_map_extract_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
 // calls it with the context's error buffer.  Plain C++17, no HIP and no context: the checks read the HOST arguments only and ask of the DEVICE
 // arrays nothing but whether they are there, so this file compiles alone and runs under sanitizers (tests/map_checks_corpus.cpp).  The first
 // failing statement decides the message, so the order of the statements inside a function is part of the interface.
@@ -831,5 +831,65 @@ extern "C" int ms_bow_vector_validate(const int32_t *word, const double *weight,
     if ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(values)) & 7u) INVALID("bow vector: weight and values must be 8-byte aligned");
     if (n > MS_COVIS_MAX_STRIDE || cap > MS_COVIS_MAX_STRIDE)
         return ms_why(MS_ERR_CAPACITY, why, why_bytes, "bow vector: %d keypoints / cap %d, caps %d each", n, cap, MS_COVIS_MAX_STRIDE);
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ map_extract.hip
+// (named _validate, not _check: the header says why)
+extern "C" int ms_map_extract_validate(const ms_map_extract_src *src, const ms_map_extract_dst *dst, const int32_t *kf_id, const int32_t *active, int n_active,
+                                       const int32_t *desc_base, const int32_t *n_kp, const int32_t *dst_desc_base, const int32_t *counts, char *why, size_t why_bytes) {
+    if (!src || !dst || !counts) INVALID("map extract: missing array (src, dst or counts)");
+    const ms_map_extract_src &S = *src;
+    const ms_map_extract_dst &D = *dst;
+    if (n_active < 0 || S.n_track < 0 || S.pool_size < 0 || D.n_kf < 0 || D.n_mp < 0 || D.pool_size < 0)
+        INVALID("map extract: negative size (%d active slots, %d tracks, pools of %d and %d, a destination of %d slots and %d map points)", n_active, S.n_track, S.pool_size,
+                D.pool_size, D.n_kf, D.n_mp);
+    int rc;
+    if ((rc = ms_kf_table_check("map extract", S.kf_mp, S.n_kf, S.stride, S.n_mp, kf_id, why, why_bytes))) return rc;
+    if (S.n_mp > 0 && (!S.mp_flags || !S.mp_pos || !S.mp_norm || !S.mp_min_dist || !S.mp_max_dist || !S.mp_desc)) INVALID("map extract: missing array (a source map-point array)");
+    if (D.n_mp > 0 && (!D.mp_flags || !D.mp_live || !D.mp_pos || !D.mp_norm || !D.mp_min_dist || !D.mp_max_dist || !D.mp_desc))
+        INVALID("map extract: missing array (a destination map-point array)");
+    if (D.n_kf > 0 && !D.kf_mp) INVALID("map extract: missing array (the destination's kf_mp)");
+    if (n_active > 0 && (!active || !dst_desc_base)) INVALID("map extract: missing array (active or dst_desc_base)");
+    if (S.track_row && !S.mp_track) INVALID("map extract: track_row without mp_track");
+    const int n_src_kp = (S.kp_x != nullptr) + (S.kp_y != nullptr) + (S.kp_octave != nullptr) + (S.kp_depth != nullptr);
+    const int n_dst_kp = (D.kp_x != nullptr) + (D.kp_y != nullptr) + (D.kp_octave != nullptr) + (D.kp_depth != nullptr);
+    if (n_src_kp % 4 || n_dst_kp % 4) INVALID("map extract: %d of the four keypoint arrays of the %s", n_src_kp % 4 ? n_src_kp : n_dst_kp, n_src_kp % 4 ? "source" : "destination");
+    if (n_src_kp != n_dst_kp) INVALID("map extract: the keypoint arrays are given for the %s only", n_src_kp ? "source" : "destination");
+    const struct { const char *name; const void *s, *d; } pairs[] = {
+        {"mp_track", S.mp_track, D.mp_track}, {"kf_pose", S.kf_pose, D.kf_pose}, {"track_row", S.track_row, D.track_row}, {"desc_pool", S.desc_pool, D.desc_pool}};
+    for (const auto &p : pairs)
+        if ((p.s != nullptr) != (p.d != nullptr)) INVALID("map extract: %s is given for the %s only", p.name, p.s ? "source" : "destination");
+    const struct { const char *name; const void *s, *d; } same[] = {
+        {"kf_mp", S.kf_mp, D.kf_mp}, {"mp_flags", S.mp_flags, D.mp_flags}, {"mp_live", S.mp_live, D.mp_live}, {"mp_pos", S.mp_pos, D.mp_pos}, {"mp_norm", S.mp_norm, D.mp_norm},
+        {"mp_min_dist", S.mp_min_dist, D.mp_min_dist}, {"mp_max_dist", S.mp_max_dist, D.mp_max_dist}, {"mp_desc", S.mp_desc, D.mp_desc}, {"mp_track", S.mp_track, D.mp_track},
+        {"kp_x", S.kp_x, D.kp_x}, {"kp_y", S.kp_y, D.kp_y}, {"kp_octave", S.kp_octave, D.kp_octave}, {"kp_depth", S.kp_depth, D.kp_depth}, {"kf_pose", S.kf_pose, D.kf_pose},
+        {"track_row", S.track_row, D.track_row}, {"desc_pool", S.desc_pool, D.desc_pool}};
+    for (const auto &p : same)
+        if (p.s && p.s == p.d) INVALID("map extract: the destination's %s is the source's", p.name);
+    if ((reinterpret_cast<uintptr_t>(S.mp_desc) | reinterpret_cast<uintptr_t>(D.mp_desc) | reinterpret_cast<uintptr_t>(S.desc_pool) | reinterpret_cast<uintptr_t>(D.desc_pool)) & 15u)
+        INVALID("map extract: descriptor arrays must be 16-byte aligned");
+    if (ms_map_over_capacity(S.n_kf, S.stride, S.n_mp, 0)) return ms_why_table_caps("map extract", S.n_kf, S.stride, S.n_mp, why, why_bytes);
+    if (ms_map_over_capacity(D.n_kf, S.stride, D.n_mp, 0)) return ms_why_table_caps("map extract: destination", D.n_kf, S.stride, D.n_mp, why, why_bytes);
+    if (S.n_track > MS_TRACKED_MAX_WINDOW) return ms_why(MS_ERR_CAPACITY, why, why_bytes, "map extract: a track window of %d, cap %d", S.n_track, MS_TRACKED_MAX_WINDOW);
+    if (n_active > D.n_kf) INVALID("map extract: %d active slots for a destination of %d slots", n_active, D.n_kf);
+    int bad = 0;
+    if (!ms_distinct_in_range(active, n_active, S.n_kf, &bad)) {
+        if (bad < 0) INVALID("map extract: active slot %d is listed twice", -1 - bad);
+        INVALID("map extract: active slot %d outside [0, %d)", active[bad], S.n_kf);
+    }
+    for (int i = 0; i < n_active; ++i)
+        if (kf_id[active[i]] < 0) INVALID("map extract: active slot %d is empty (kf_id %d)", active[i], kf_id[active[i]]);
+    if (!S.desc_pool) return MS_OK;
+    if (n_active > 0 && (!desc_base || !n_kp)) INVALID("map extract: missing array (desc_base or n_kp with a pool)");
+    long long total = 0;
+    for (int i = 0; i < n_active; ++i) {
+        if (n_kp[i] < 0 || n_kp[i] > S.stride) INVALID("map extract: active slot %d: %d keypoints in a table of stride %d", active[i], n_kp[i], S.stride);
+        const int32_t base = desc_base[active[i]];
+        if (base < 0) continue;
+        if ((long long)base + n_kp[i] > S.pool_size) INVALID("map extract: active slot %d: descriptors [%d, %d + %d) outside the pool of %d", active[i], base, base, n_kp[i], S.pool_size);
+        total += n_kp[i];
+    }
+    if (total > D.pool_size) INVALID("map extract: %lld descriptors for a destination pool of %d", total, D.pool_size);
     return MS_OK;
 }

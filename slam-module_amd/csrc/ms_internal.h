@@ -33,6 +33,7 @@ enum MsWorkspaceId {
     MS_WS_FRAME_FINISH,     // ms_frame_finish (frame_finish.hip): device list positions / list; first claims / remaining entries / block counts; the block that goes down
     MS_WS_KEYFRAME_ADMIT,   // ms_keyframe_admit (keyframe_admit.hip): device track ids / depths; word / weight / node / track index / sorted nodes; the block that goes down
     MS_WS_BOW_VECTOR,       // ms_bow_vector (bow_vector.hip): the device head {n_words, n_bad} that goes down
+    MS_WS_MAP_EXTRACT,      // ms_map_extract (map_extract.hip): device list / keypoint counts / pool offsets; entries per row / row maps / block counts; the head that goes down
     MS_WS_COUNT
 };
 

@@ -3,9 +3,9 @@
 // culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
 // fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), matchLocalMapPoints, createNewMapPoints and the local
 // bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables), the per-frame pose
-// adjustment (poseBundleAdjustOnTables), the end of a frame (finishFrame, removeKeyframes) and the arrival of a keyframe from the extractor's
-// device output (admitKeyframe).
-// Results come back through Context::workspace and Context::download; nothing here owns device memory.
+// adjustment (poseBundleAdjustOnTables), the end of a frame (finishFrame, removeKeyframes), the arrival of a keyframe from the extractor's
+// device output (admitKeyframe) and the map copy for the front end (extractMap, copyMapToFrontend).
+// Results come back through Context::workspace and Context::download; nothing here owns device memory but the two row maps of a MapExtract.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -979,6 +979,115 @@ inline FuseResult mergeMatchedMapPoints(Context &ctx, MapTables M, const std::ve
     out.fusedCount = (unsigned)nErased;
     if (outcome) *outcome = oc;
     return out;
+}
+
+// ---- the partial map copy for the front end on the device tables (ms_map_extract) ---------------------------------------------------------
+// What copyMap (mapper.cpp:281-326) hands the front end: the counts of the copy and, as DEVICE arrays this object owns, the source row of
+// every destination row and the destination row of every source row (-1: not copied) -- what a caller translates its own row lists with.
+struct MapExtract {
+    std::size_t mapPoints = 0, observations = 0, droppedObservations = 0, tracks = 0, descriptors = 0;
+    DeviceArray<std::int32_t> rowSource, rowDestination;
+};
+
+// MapDB(mapDB, activeKeyframes) (mapdb.cpp:116-159) from the tables `src` into the tables `dst`, compacted: ONE device call, nothing of either map
+// walked on the host.  activeSlots = source slots in the order the destination gets them (ascending KfId, the std::set's order); destination slot i
+// is activeSlots[i].  Reads src (never written); writes dst.keyframes, dst.points, dst.flags, dst.live, and dst.keypoints, dst.poses, dst.tracks,
+// dst.pool (reserve()), dst.observationCount where both sides have them; fills dst.slots: id, t, cameraCenter, camera, focalLength and frames copied
+// (the frames' matcher arrays are immutable and shared: the pointers are copied as they are, non-owning), previous / next translated to destination
+// slots and cut where the neighbour is not active (mapdb.cpp:124-129), descBase from the call; the slots behind the active ones are emptied.
+// The two row maps of the result are allocated by every call (MapExtract owns them): "nothing is allocated after warm-up" is the C entry point's
+// property, not this function's; a caller that copies the map often and wants none keeps its own arrays and calls ms_map_extract.
+// keyPointCounts (per SOURCE slot) stands in for frames[s]->keyPointCount() where a slot has no frame.  Left to the caller: referenceKeyframe
+// (map_point.cpp:38-42), the scalar members of mapdb.cpp:150-158, bowIndex.  Throws std::invalid_argument before the device call for an active
+// slot outside the table or empty, a destination with fewer slots than active keyframes, a different stride, a part present on one side only.
+inline MapExtract extractMap(Context &ctx, MapTables src, const std::vector<std::int32_t> &activeSlots, MapTables dst, const std::vector<std::int32_t> &keyPointCounts = {}) {
+    const unsigned perSlot = MapTables::IDS | MapTables::TIMES | MapTables::LINKS | MapTables::CENTRES | MapTables::CAMERAS | MapTables::FOCALS | MapTables::DESC_BASES | MapTables::FRAMES;
+    src.require("extractMap", MapTables::POINTS | MapTables::FLAGS | perSlot);
+    dst.require("extractMap (destination)", MapTables::POINTS | MapTables::FLAGS | MapTables::LIVE | perSlot);
+    const std::size_t nKf = src.keyframes.size(), nActive = activeSlots.size(), stride = src.keyframes.stride();
+    auto refuse = [](const std::string &what) { throw std::invalid_argument("extractMap: " + what); };
+    if (dst.keyframes.stride() != stride) refuse("the destination's stride " + std::to_string(dst.keyframes.stride()) + " is not the source's " + std::to_string(stride));
+    if (dst.keyframes.size() < nActive) refuse(std::to_string(nActive) + " active keyframes for a destination of " + std::to_string(dst.keyframes.size()) + " slots");
+    for (std::int32_t s : activeSlots) {
+        if (s < 0 || (std::size_t)s >= nKf) refuse("active slot " + std::to_string(s) + " outside the table");
+        if (src.slots.id[s] < 0) refuse("active slot " + std::to_string(s) + " is empty");
+    }
+    if ((src.keypoints != nullptr) != (dst.keypoints != nullptr)) refuse("a keypoint table on one side only");
+    if ((src.poses != nullptr) != (dst.poses != nullptr)) refuse("poses on one side only");
+    if ((src.tracks != nullptr) != (dst.tracks != nullptr)) refuse("a track table on one side only");
+    if ((src.pool != nullptr) != (dst.pool != nullptr)) refuse("a descriptor pool on one side only");
+    if (src.tracks && (src.tracks->trackBase() != dst.tracks->trackBase() || src.tracks->window() != dst.tracks->window())) refuse("the track windows differ");
+    if (!keyPointCounts.empty() && keyPointCounts.size() != nKf) refuse("one keypoint count per source slot");
+    std::vector<std::int32_t> nKp(nActive, 0), where(nKf, -1);
+    std::size_t total = 0;
+    for (std::size_t i = 0; i < nActive; ++i) {
+        const std::int32_t s = activeSlots[i];
+        where[s] = (std::int32_t)i;
+        if (!src.pool || src.slots.descBase[s] < 0) continue;
+        if (!src.slots.frames[s] && keyPointCounts.empty()) refuse("active slot " + std::to_string(s) + " has descriptors, no frame and no keypoint count");
+        nKp[i] = src.slots.frames[s] ? (std::int32_t)src.slots.frames[s]->keyPointCount() : keyPointCounts[s];
+        total += (std::size_t)std::max(nKp[i], 0);
+    }
+    const std::size_t poolBase = dst.pool ? dst.pool->reserve(total) : 0;
+    MapExtract out;
+    out.rowSource = DeviceArray<std::int32_t>(ctx, dst.keyframes.mapPointCount());
+    out.rowDestination = DeviceArray<std::int32_t>(ctx, src.keyframes.mapPointCount());
+    const DeviceMapPoints &P = *src.points;
+    DeviceMapPoints &Q = *dst.points;
+    const ms_map_extract_src S{src.keyframes.table(), src.flags->flags(), src.live ? src.live->live() : nullptr, P.position(), P.norm(), P.minDistance(), P.maxDistance(), P.descriptor(),
+                               src.tracks ? src.tracks->mpTrack() : nullptr, src.keypoints ? src.keypoints->x() : nullptr, src.keypoints ? src.keypoints->y() : nullptr,
+                               src.keypoints ? src.keypoints->octave() : nullptr, src.keypoints ? src.keypoints->depth() : nullptr, src.poses ? src.poses->pose() : nullptr,
+                               src.tracks ? src.tracks->trackRow() : nullptr, src.poolDescriptor(), (std::int32_t)nKf, (std::int32_t)stride, (std::int32_t)src.keyframes.mapPointCount(),
+                               src.tracks ? src.tracks->trackBase() : 0, src.tracks ? (std::int32_t)src.tracks->window() : 0, src.poolSize()};
+    const ms_map_extract_dst D{dst.keyframes.mutableTable(), dst.flags->mutableFlags(), dst.live->mutableLive(), Q.mutablePosition(), Q.mutableNorm(), Q.mutableMinDistance(),
+                               Q.mutableMaxDistance(), Q.mutableDescriptor(), dst.tracks ? dst.tracks->mpTrack() : nullptr, dst.keypoints ? dst.keypoints->mutableX() : nullptr,
+                               dst.keypoints ? dst.keypoints->mutableY() : nullptr, dst.keypoints ? dst.keypoints->mutableOctave() : nullptr,
+                               dst.keypoints ? dst.keypoints->mutableDepth() : nullptr, dst.poses ? dst.poses->pose() : nullptr, dst.tracks ? dst.tracks->trackRow() : nullptr,
+                               dst.pool ? dst.pool->mutableDescriptor() + 8 * poolBase : nullptr, dst.observationCount, out.rowSource.data(), out.rowDestination.data(),
+                               (std::int32_t)dst.keyframes.size(), (std::int32_t)dst.keyframes.mapPointCount(), (std::int32_t)total};
+    std::vector<std::int32_t> base(std::max<std::size_t>(nActive, 1), -1);
+    std::int32_t counts[5] = {0, 0, 0, 0, 0};
+    const int rc = ms_map_extract(ctx.get(), &S, &D, src.slots.id.data(), activeSlots.data(), (int)nActive, src.pool ? src.slots.descBase.data() : nullptr, src.pool ? nKp.data() : nullptr,
+                                  base.data(), counts);
+    if (rc != MS_OK) { if (dst.pool) dst.pool->release(total); ctx.check(rc, "ms_map_extract"); }
+    out.mapPoints = (std::size_t)counts[0]; out.observations = (std::size_t)counts[1]; out.droppedObservations = (std::size_t)counts[2];
+    out.tracks = (std::size_t)counts[3]; out.descriptors = (std::size_t)counts[4];
+    const KeyframeSlots &A = src.slots;
+    KeyframeSlots &B = dst.slots;
+    auto translated = [&](std::int32_t s) { return s >= 0 && (std::size_t)s < nKf ? where[s] : -1; };      // mapdb.cpp:124-129
+    for (std::size_t i = 0; i < dst.keyframes.size(); ++i) {
+        const bool copied = i < nActive;
+        const std::int32_t s = copied ? activeSlots[i] : 0;
+        B.id[i] = copied ? A.id[s] : -1;
+        B.previous[i] = copied ? translated(A.previous[s]) : -1;
+        B.next[i] = copied ? translated(A.next[s]) : -1;
+        B.descBase[i] = copied && base[i] >= 0 ? (std::int32_t)poolBase + base[i] : -1;
+        B.frames[i] = copied ? A.frames[s] : nullptr;
+        if (!copied) continue;
+        B.t[i] = A.t[s]; B.cameraCenter[i] = A.cameraCenter[s]; B.camera[i] = A.camera[s]; B.focalLength[i] = A.focalLength[s];
+    }
+    return out;
+}
+
+// copyMap, mapper.cpp:281-310: with `partial` (copyPartialMapToFrontend) the keyframes of computeAdjacentKeyframes(latest, 5, adjacentSpaceSize)
+// plus the latest one, by ascending KfId; otherwise, or without a latest keyframe (latestSlot == -1, :289-292), every keyframe of the back end's
+// map (MapDB(mapDB), mapdb.cpp:98-114, through the same call).  Then extractMap.  Exchanging the front end's tables for the new ones under the
+// reference's frontendMapMutex, and fastForward (:317-321), are the caller's.
+inline MapExtract copyMapToFrontend(Context &ctx, MapTables backend, std::int32_t latestSlot, int adjacentSpaceSize, bool partial, MapTables frontend,
+                                    const std::vector<std::int32_t> &keyPointCounts = {}) {
+    backend.require("copyMapToFrontend", MapTables::IDS);
+    std::vector<std::int32_t> active;
+    if (partial && latestSlot != -1) {
+        constexpr int minCovisibilities = 5;                 // :296
+        active = computeAdjacentKeyframes(ctx, backend, latestSlot, minCovisibilities, adjacentSpaceSize);
+        active.push_back(latestSlot);
+    } else {
+        for (std::size_t k = 0; k < backend.slots.id.size(); ++k) if (backend.slots.id[k] >= 0) active.push_back((std::int32_t)k);
+    }
+    for (std::int32_t s : active)
+        if (s < 0 || (std::size_t)s >= backend.slots.id.size()) throw std::invalid_argument("copyMapToFrontend: slot " + std::to_string(s) + " outside the table");
+    std::sort(active.begin(), active.end(), [&](std::int32_t a, std::int32_t b) { return backend.slots.id[a] < backend.slots.id[b]; });      // std::set<KfId>
+    return extractMap(ctx, backend, active, frontend, keyPointCounts);
 }
 
 }  // namespace mi355slam

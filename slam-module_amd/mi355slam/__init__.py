@@ -1346,6 +1346,60 @@ def frame_finish_validate(arrays, n_kf, stride, n_mp, n_remove, cloud_slot, n_kp
     return rc, why.value.decode()
 
 
+# ---- the partial map copy for the front end (ms_map_extract) ----
+# name -> (dtype, what it has one element group per: "entry" n_kf * stride, "row" n_mp, "slot" n_kf, "track" n_track, "pool" pool_size, "src_row" the source's n_mp; width)
+MAP_EXTRACT_FIELDS = dict(
+    kf_mp=(np.int32, "entry", 1), mp_flags=(np.uint8, "row", 1), mp_live=(np.uint8, "row", 1), mp_pos=(np.float64, "row", 3), mp_norm=(np.float32, "row", 3),
+    mp_min_dist=(np.float32, "row", 1), mp_max_dist=(np.float32, "row", 1), mp_desc=(np.uint32, "row", 8), mp_track=(np.int32, "row", 1), kp_x=(np.float32, "entry", 1),
+    kp_y=(np.float32, "entry", 1), kp_octave=(np.int32, "entry", 1), kp_depth=(np.float32, "entry", 1), kf_pose=(np.float64, "slot", 12), track_row=(np.int32, "track", 1),
+    desc_pool=(np.uint32, "pool", 8), n_obs=(np.int32, "row", 1), row_src=(np.int32, "row", 1), row_dst=(np.int32, "src_row", 1))
+MAP_EXTRACT_SRC = tuple(MAP_EXTRACT_FIELDS)[:16]             # the struct's order
+MAP_EXTRACT_DST = tuple(MAP_EXTRACT_FIELDS)
+
+
+class MapExtractSrcC(C.Structure):
+    """ms_map_extract_src: device pointers and the source's sizes"""
+    _fields_ = [(k, C.c_void_p) for k in MAP_EXTRACT_SRC] + [(k, C.c_int32) for k in ("n_kf", "stride", "n_mp", "track_base", "n_track", "pool_size")]
+
+
+class MapExtractDstC(C.Structure):
+    """ms_map_extract_dst: device pointers and the destination's sizes"""
+    _fields_ = [(k, C.c_void_p) for k in MAP_EXTRACT_DST] + [(k, C.c_int32) for k in ("n_kf", "n_mp", "pool_size")]
+
+
+def map_extract_shape(name, sizes, dst=False):
+    """The shape of array `name` of the source (or, with dst, of the destination) of a map extraction with these sizes."""
+    _, per, w = MAP_EXTRACT_FIELDS[name]
+    n_kf, n_mp, pool = (sizes["n_kf_dst"], sizes["n_mp_dst"], sizes["pool_size_dst"]) if dst else (sizes["n_kf"], sizes["n_mp"], sizes["pool_size"])
+    if per == "entry":
+        return (n_kf, sizes["stride"])
+    n = dict(row=n_mp, slot=n_kf, track=sizes["n_track"], pool=pool, src_row=sizes["n_mp"])[per]
+    return (n, w) if w > 1 else (n,)
+
+
+def _map_extract_structs(src, dst, sizes):
+    """dicts of arrays (DevBufs, numpy arrays, pointers or None; a missing name is None) and sizes (n_kf, stride, n_mp, track_base, n_track,
+    pool_size, n_kf_dst, n_mp_dst, pool_size_dst) -> (ms_map_extract_src, ms_map_extract_dst)"""
+    z = lambda k: int(sizes.get(k, 0))
+    S = MapExtractSrcC(*([_vp(src.get(k)).value for k in MAP_EXTRACT_SRC] + [z(k) for k in ("n_kf", "stride", "n_mp", "track_base", "n_track", "pool_size")]))
+    D = MapExtractDstC(*([_vp(dst.get(k)).value for k in MAP_EXTRACT_DST] + [z(k) for k in ("n_kf_dst", "n_mp_dst", "pool_size_dst")]))
+    return S, D
+
+
+def map_extract_validate(src, dst, sizes, kf_id, active, n_active=None, desc_base=None, n_kp=None, dst_desc_base=True, counts=True):
+    """ms_map_extract_validate, the host half of ms_map_extract (no context, no device).  src / dst: dicts of the names in MAP_EXTRACT_SRC /
+    MAP_EXTRACT_DST, or None for no struct (only the presence, identity and alignment of the arrays is looked at); kf_id, active, desc_base,
+    n_kp: host int32 arrays or None.  Returns (rc, message)."""
+    S, D = _map_extract_structs(src or {}, dst or {}, sizes)
+    n_active = (0 if active is None else len(active)) if n_active is None else n_active
+    why, cnt, base = C.create_string_buffer(512), np.zeros(5, np.int32), np.zeros(max(n_active, 1), np.int32)
+    opt = lambda a: None if a is None else _i32(a)
+    kf_id, active, desc_base, n_kp = opt(kf_id), opt(active), opt(desc_base), opt(n_kp)
+    rc = lib().ms_map_extract_validate(C.byref(S) if src is not None else None, C.byref(D) if dst is not None else None, _vp(kf_id), _vp(active), int(n_active),
+                                       _vp(desc_base), _vp(n_kp), _vp(base if dst_desc_base else None), _vp(cnt if counts else None), why, C.c_size_t(512))
+    return rc, why.value.decode()
+
+
 # ---- a new keyframe from the extractor's output to the map tables (ms_keyframe_admit, DESIGN 9.19) ----
 class AdmitArgsC(C.Structure):
     """ms_admit_args"""
@@ -1707,6 +1761,38 @@ class KeyframeTable:
         removed.  Returns frame_finish_device's dict; raises MsError on an error."""
         rc, out = self.frame_finish_device(flags, live, table, tracks, n_obs, kf_id, remove_slots, cloud_slot, n_kp, cap_removed)
         self.ctx.check(rc, "ms_frame_finish")
+        return out
+
+    def map_extract_device(self, src, dst, sizes, kf_id, active, desc_base=None, n_kp=None):
+        """ms_map_extract with this table as the source's kf_mp, without raising: src / dst are dicts of DevBufs under the names of
+        MAP_EXTRACT_SRC / MAP_EXTRACT_DST (a missing name is NULL; src's kf_mp is this table's), sizes a dict of n_mp, track_base, n_track,
+        pool_size, n_kf_dst, n_mp_dst, pool_size_dst (n_kf and stride are this table's).  Nothing comes down but the two host outputs.
+        Returns (rc, dict(counts [5], dst_desc_base [n_active]))."""
+        kf_id, active = _i32(kf_id), _i32(active)
+        if len(kf_id) != self.n_kf:
+            raise ValueError("kf_id describes %d slots, the table has %d" % (len(kf_id), self.n_kf))
+        S, D = _map_extract_structs(dict(src, kf_mp=self.kf_mp), dst, dict(sizes, n_kf=self.n_kf, stride=self.stride))
+        desc_base, n_kp = (None if a is None else _i32(a) for a in (desc_base, n_kp))
+        base, counts = np.zeros(max(len(active), 1), np.int32), np.zeros(5, np.int32)
+        rc = lib().ms_map_extract(self.ctx._h, C.byref(S), C.byref(D), _vp(kf_id), _vp(active), len(active), _vp(desc_base), _vp(n_kp), _vp(base), _vp(counts))
+        return rc, dict(counts=counts, dst_desc_base=base[:len(active)].copy())
+
+    def map_extract(self, src, sizes, kf_id, active, desc_base=None, n_kp=None, outputs=True):
+        """The partial map copy of copyMap (mapper.cpp:281-326; ms_map_extract) into a fresh, zero-filled destination of sizes["n_kf_dst"] slots,
+        sizes["n_mp_dst"] rows and a pool of sizes["pool_size_dst"], with every array the source has (outputs: also n_obs, row_src, row_dst).
+        Returns dict(counts, dst_desc_base, and the destination arrays as numpy); raises MsError on an error."""
+        sizes = dict(sizes, n_kf=self.n_kf, stride=self.stride)
+        names = [k for k in MAP_EXTRACT_DST if k in ("kf_mp", "mp_live") or src.get(k) is not None or (outputs and k in ("n_obs", "row_src", "row_dst"))]
+        shapes = {k: map_extract_shape(k, sizes, dst=True) for k in names}
+        dst = {k: self.ctx.upload(np.zeros(max(int(np.prod(shapes[k])), 4), MAP_EXTRACT_FIELDS[k][0])) for k in names}
+        try:
+            rc, out = self.map_extract_device(src, dst, sizes, kf_id, active, desc_base, n_kp)
+            self.ctx.check(rc, "ms_map_extract")
+            for k in names:
+                out[k] = dst[k].download(MAP_EXTRACT_FIELDS[k][0], shapes[k]) if np.prod(shapes[k]) else np.zeros(shapes[k], MAP_EXTRACT_FIELDS[k][0])
+        finally:
+            for b in dst.values():
+                b.free()
         return out
 
     def _fuse_tables(self, tables, n_mp):
