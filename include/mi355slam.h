@@ -1815,8 +1815,8 @@ int ms_frame_finish_validate(const int32_t *kf_mp, int n_kf, int stride, const u
  * to the context and only grows: nothing is allocated after warm-up (ms_debug_host_allocs).  The same inputs give the same bytes on every
  * call.  The BowVector itself is not built here: ms_bow_db_add takes host arrays, so a caller either takes word / weight down and sums on the
  * host, or leaves them NULL and hands the descent to ms_bow_db_add_words where it lies (ms_keyframe_admit_words).
- * Not covered: the keypoints of frames that are no keyframe (addTrackerFeatures: host data of the tracker), colours (getPixel),
- * reuse of pool space when keyframes leave. */
+ * Not covered: colours (getPixel), reuse of pool space when keyframes leave.  The keypoints of a frame that carries tracker features only
+ * (addTrackerFeatures) come in through ms_frame_admit. */
 typedef struct {
     int32_t slot;                        /* the keyframe's slot in kf_mp, the keypoint table and kf_pose */
     int32_t desc_base;                   /* index of keypoint 0 in desc_pool */
@@ -1961,6 +1961,67 @@ int ms_map_extract(ms_ctx *ctx,
 int ms_map_extract_validate(const ms_map_extract_src *src, const ms_map_extract_dst *dst,
     const int32_t *kf_id, const int32_t *active, int n_active, const int32_t *desc_base, const int32_t *n_kp,
     const int32_t *dst_desc_base, const int32_t *counts, char *why, size_t why_bytes);
+
+/* ---- a frame of tracker features to the map tables --------------------------------------------------------------------------
+ * Keyframe::addTrackerFeatures / processKeyPoints (keyframe.cpp:34-69, :118-133, called at mapper_helpers.cpp:1196) without table rows going
+ * up piece by piece: the arrival of a frame that did not go through the extractor -- every front-end frame (isBackend is false,
+ * mapper_helpers.cpp:1186-1197) and every back-end frame that is no keyframe.  ms_frame_admit puts the HOST list of tracker features
+ * (points[0].x, points[0].y, id, depth) into slot `slot` of the tables of 9.4 - 9.21; after it the frame is ms_match_tracked,
+ * ms_pose_tables_solve and ms_frame_finish with no table upload in between.  tests/frame_admit_ref.py restates the call and is its
+ * specification.
+ *
+ * Kept: feature i is KEPT iff (keep == NULL || keep[i] != 0) and the mask rule holds.  keep is the host's evaluation of
+ * tracker::Camera::isValidPixel (keyframe.cpp:122), the exact form.  The mask rule: valid_mask == NULL, or the rounded position
+ * (__float2int_rn(x), __float2int_rn(y)) lies inside the raster and its byte is non-zero (ms_orb_set_valid_mask's rule; a position outside the
+ * raster is invalid).  Keypoint k is the k-th kept feature in ascending i; n_kp, the number kept, is decided ON THE DEVICE.
+ * Written for k < n_kp, at entry slot * stride + k: kp_x, kp_y = the feature's bits; kp_octave = 0 (keyframe.cpp:127); kp_depth
+ *   (keyframe.cpp:57-64) = depth[i] of the feature itself, or, iff that is < 0 as written (a NaN stays), the sample of depth_image at the
+ *   rounded position -- ms_keyframe_admit's expression, the image being the same stand-in for frame->getDepth -- or -1 outside the image or
+ *   with no image.  Entries k >= n_kp of the keypoint table keep their bytes.
+ * Written per slot: kf_mp[slot * stride + j] = -1 for ALL stride entries; kf_pose[slot] = pose (it travels as a kernel argument).
+ * HOST outputs, one download through the context's pinned block: kp_track[k] = id[i], what ms_match_tracked takes as kp_track next;
+ * kp_feature[k] = i.  counts (HOST [4]) = n_kp, the features dropped by keep, those dropped by the mask alone, the kept features whose
+ * depth was taken from the image (depth[i] < 0 and the rounded position inside a given image).
+ * One deliberate deviation: keyframe.cpp:129 binds the id to KpId(i), the FEATURE index, so that after a dropped feature every later id sits
+ * on the wrong keypoint or on none; this call binds the k-th kept feature's id and depth to keypoint k.  Equal whenever nothing is dropped
+ * (DESIGN section 3).
+ *
+ * Every verdict is taken before any write (the rule of ms_keyframe_admit and ms_ba_window_apply): MS_ERR_CAPACITY with the needed n_kp in
+ * counts[0] when n_kp > stride or n_kp > cap_kp; MS_ERR_INVALID when the slot's row already holds a VALID entry ((uint32)r < n_mp,
+ * keyframe.cpp:275).  In both cases every table keeps its bytes.  Before any device call (ms_frame_admit_validate, the host validation
+ * alone: no context, no device; `why` receives the message): MS_ERR_INVALID for a slot out of range, a non-finite x or y, an id < 0 (it
+ * would read as "no track" downstream), an id listed twice (ms_match_tracked refuses such a frame; the reference lets the last feature win,
+ * keyframe.cpp:51-53), a non-finite pose, an image or a mask without a size, stride < 1, a negative size, a missing array;
+ * MS_ERR_CAPACITY beyond the MS_COVIS_MAX_* caps (n_tracks and cap_kp: MS_COVIS_MAX_STRIDE; an image or a mask of 2^31 elements or more).
+ * n_tracks == 0 is fine: the row is cleared and the pose is written.
+ * TWO launches whatever the sizes (ranks and verdicts in one workgroup; every write), at most one upload block (the features, through the
+ * context's staging; none with n_tracks == 0), ONE download, one host wait behind the last launch.  The workspace belongs to the context
+ * and only grows: nothing is allocated after warm-up (ms_debug_host_allocs).  No atomics; positions are prefix counts: the same inputs
+ * give the same bytes on every call.
+ * Not covered: colours (getPixel), a device-resident kp_track for ms_match_tracked, several frames per call. */
+typedef struct {
+    int32_t slot;                        /* the frame's slot in kf_mp, the keypoint table and kf_pose */
+    double pose[12];                     /* rows 0-2 of poseCW, row-major (insertNewKeyframeCandidate's result: the host computes it) */
+    const float *depth_image;            /* DEVICE float32, may be NULL: the stand-in for frame->getDepth, as in ms_keyframe_admit */
+    int32_t depth_width, depth_height, depth_stride;     /* row stride in elements */
+    const uint8_t *valid_mask;           /* DEVICE bytes, 0 = invalid, may be NULL: the raster stand-in for isValidPixel */
+    int32_t mask_width, mask_height, mask_stride;        /* row stride in bytes */
+} ms_frame_admit_args;
+int ms_frame_admit(ms_ctx *ctx,
+    /* DEVICE tables, updated in place */
+    int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    float *kp_x, float *kp_y, int32_t *kp_octave, float *kp_depth, double *kf_pose,
+    /* HOST: the tracker features [n_tracks]; keep may be NULL */
+    const float *x, const float *y, const int32_t *id, const float *depth, const uint8_t *keep, int n_tracks,
+    const ms_frame_admit_args *args,
+    /* HOST outputs, [cap_kp] each, each may be NULL; counts [4] */
+    int32_t *kp_track, int32_t *kp_feature, int cap_kp, int32_t *counts);
+/* the twin is named _validate: the set of ms_*_check functions is closed at 22 (tests/test_map_checks_corpus.py records them) */
+int ms_frame_admit_validate(const int32_t *kf_mp, int n_kf, int stride, int n_mp,
+    const float *kp_x, const float *kp_y, const int32_t *kp_octave, const float *kp_depth, const double *kf_pose,
+    const float *x, const float *y, const int32_t *id, const float *depth, const uint8_t *keep, int n_tracks,
+    const ms_frame_admit_args *args,
+    const int32_t *kp_track, const int32_t *kp_feature, int cap_kp, const int32_t *counts, char *why, size_t why_bytes);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // map_checks.cpp -- the host validation of every call on the device map tables: the 22 exported ms_*_check functions, in the order of
-// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate, ms_bow_vector_validate and ms_map_extract_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
+// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate, ms_bow_vector_validate, ms_map_extract_validate and ms_frame_admit_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
 // calls it with the context's error buffer.  Plain C++17, no HIP and no context: the checks read the HOST arguments only and ask of the DEVICE
 // arrays nothing but whether they are there, so this file compiles alone and runs under sanitizers (tests/map_checks_corpus.cpp).  The first
 // failing statement decides the message, so the order of the statements inside a function is part of the interface.
@@ -891,5 +891,44 @@ extern "C" int ms_map_extract_validate(const ms_map_extract_src *src, const ms_m
         total += n_kp[i];
     }
     if (total > D.pool_size) INVALID("map extract: %lld descriptors for a destination pool of %d", total, D.pool_size);
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ frame_admit.hip
+// (named _validate, not _check: the header says why)
+extern "C" int ms_frame_admit_validate(const int32_t *kf_mp, int n_kf, int stride, int n_mp, const float *kp_x, const float *kp_y, const int32_t *kp_octave,
+                                       const float *kp_depth, const double *kf_pose, const float *x, const float *y, const int32_t *id, const float *depth, const uint8_t *keep,
+                                       int n_tracks, const ms_frame_admit_args *args, const int32_t *kp_track, const int32_t *kp_feature, int cap_kp, const int32_t *counts,
+                                       char *why, size_t why_bytes) {
+    (void)keep; (void)kp_track; (void)kp_feature;            // each may be NULL
+    if (n_kf < 0 || n_mp < 0 || n_tracks < 0 || cap_kp < 0) INVALID("frame admit: negative size (%d slots, %d map points, %d features, cap_kp %d)", n_kf, n_mp, n_tracks, cap_kp);
+    if (stride < 1) return ms_why_stride("frame admit", stride, why, why_bytes);
+    if (!args || !counts) INVALID("frame admit: missing array (args or counts)");
+    if (!kf_mp || !kp_x || !kp_y || !kp_octave || !kp_depth || !kf_pose) INVALID("frame admit: missing array (kf_mp, the keypoint table or kf_pose)");
+    if (n_tracks > 0 && (!x || !y || !id || !depth)) INVALID("frame admit: missing array (x, y, id or depth with %d features)", n_tracks);
+    if (args->slot < 0 || args->slot >= n_kf) INVALID("frame admit: slot %d outside [0, %d)", args->slot, n_kf);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(args->pose[i])) INVALID("frame admit: pose[%d] is not finite", i);
+    if (args->depth_image && (args->depth_width < 1 || args->depth_height < 1 || args->depth_stride < args->depth_width))
+        INVALID("frame admit: a depth image of %d x %d, row stride %d", args->depth_width, args->depth_height, args->depth_stride);
+    if (args->valid_mask && (args->mask_width < 1 || args->mask_height < 1 || args->mask_stride < args->mask_width))
+        INVALID("frame admit: a valid mask of %d x %d, row stride %d", args->mask_width, args->mask_height, args->mask_stride);
+    if (n_tracks > MS_COVIS_MAX_STRIDE || cap_kp > MS_COVIS_MAX_STRIDE)
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "frame admit: %d features / cap_kp %d, caps %d each", n_tracks, cap_kp, MS_COVIS_MAX_STRIDE);
+    if (args->depth_image && ((long long)args->depth_stride * args->depth_height > 0x7fffffffLL))
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "frame admit: a depth image of %d rows of %d elements, caps below 2^31 elements", args->depth_height, args->depth_stride);
+    if (args->valid_mask && ((long long)args->mask_stride * args->mask_height > 0x7fffffffLL))
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "frame admit: a valid mask of %d rows of %d bytes, caps below 2^31 bytes", args->mask_height, args->mask_stride);
+    if (ms_map_over_capacity(n_kf, stride, n_mp, 0)) return ms_why_table_caps("frame admit", n_kf, stride, n_mp, why, why_bytes);
+    for (int i = 0; i < n_tracks; ++i) {
+        if (!std::isfinite(x[i]) || !std::isfinite(y[i])) INVALID("frame admit: feature %d has a coordinate that is not finite", i);
+        if (id[i] < 0) INVALID("frame admit: feature %d has the id %d (a negative id reads as no track)", i, id[i]);
+    }
+    std::vector<int32_t> &ids = tl_ids();
+    if (ids.capacity() < (size_t)n_tracks) { ids.reserve((size_t)n_tracks + (size_t)n_tracks / 2); ++g_ms_host_allocs; }
+    ids.assign(id, id + n_tracks);
+    std::sort(ids.begin(), ids.end());
+    for (int i = 1; i < n_tracks; ++i)
+        if (ids[i - 1] == ids[i]) INVALID("frame admit: track id %d is listed twice", ids[i]);
     return MS_OK;
 }

@@ -34,6 +34,7 @@ enum MsWorkspaceId {
     MS_WS_KEYFRAME_ADMIT,   // ms_keyframe_admit (keyframe_admit.hip): device track ids / depths; word / weight / node / track index / sorted nodes; the block that goes down
     MS_WS_BOW_VECTOR,       // ms_bow_vector (bow_vector.hip): the device head {n_words, n_bad} that goes down
     MS_WS_MAP_EXTRACT,      // ms_map_extract (map_extract.hip): device list / keypoint counts / pool offsets; entries per row / row maps / block counts; the head that goes down
+    MS_WS_FRAME_ADMIT,      // ms_frame_admit (frame_admit.hip): device features (x / y / depth / id / keep); the keypoint index per feature; the block that goes down
     MS_WS_COUNT
 };
 

@@ -3,12 +3,14 @@
 // culling (observationCounts, cullMap), the observation-list passes (updateMapPoints, retriangulateCurrent), matchTrackedFeatures and the
 // fusing of duplicate map points (deduplicateMapPoints, searchAndDeduplicate, mergeMatchedMapPoints), matchLocalMapPoints, createNewMapPoints and the local
 // bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables), the per-frame pose
-// adjustment (poseBundleAdjustOnTables), the end of a frame (finishFrame, removeKeyframes), the arrival of a keyframe from the extractor's
-// device output (admitKeyframe) and the map copy for the front end (extractMap, copyMapToFrontend).
+// adjustment (poseBundleAdjustOnTables), the end of a frame (finishFrame, removeKeyframes), the arrival of a frame of tracker features
+// (admitTrackerFrame, with makeKeyframeDecision in front of it), the arrival of a keyframe from the extractor's device output (admitKeyframe)
+// and the map copy for the front end (extractMap, copyMapToFrontend).
 // Results come back through Context::workspace and Context::download; nothing here owns device memory but the two row maps of a MapExtract.
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <functional>
 #include <limits>
 #include <stdexcept>
@@ -759,6 +761,104 @@ inline FrameFinish finishFrame(Context &ctx, MapTables M, std::int32_t slot, std
 // One device call; no cloud.  The same two refusals as finishFrame, for every slot of the list, before any device call.
 inline FrameFinish removeKeyframes(Context &ctx, MapTables M, const std::vector<std::int32_t> &slots, const std::vector<std::int32_t> &loopClosureKeyframes) {
     return detail::finish_frame(ctx, M, "removeKeyframes", -1, 0, slots, loopClosureKeyframes);
+}
+
+// ---- a frame of tracker features to the device tables (ms_frame_admit) ------------------------------------------------------------------
+// makeKeyframeDecision (mapper_helpers.cpp:28-65) on what the host already holds: the two times, the two origPoseCameraCenter()s, the previous
+// keyframe's keyPointToTrackId values and the current tracker features' ids.  It stays on the host on purpose: in the back end it decides
+// whether the extractor runs at all, and it is a set lookup over a few hundred ids.  The comparison types are the reference's: maxCovis is a
+// float product and the test is <=.
+struct KeyframeDecisionParameters {
+    double keyframeDecisionMinIntervalSeconds = 0.0;
+    double keyframeDecisionDistanceThreshold = 0.0;
+    float keyframeDecisionCovisibilityRatio = 0.0f;
+};
+inline bool makeKeyframeDecision(bool hasPreviousKeyframe, double currentT, double previousT, const std::array<double, 3> &currentCenter, const std::array<double, 3> &previousCenter,
+                                 const std::vector<std::int32_t> &previousTrackIds, const std::vector<std::int32_t> &currentTrackIds, const KeyframeDecisionParameters &parameters) {
+    if (!hasPreviousKeyframe) return true;                   // :34
+    const double age = currentT - previousT;
+    if (age < parameters.keyframeDecisionMinIntervalSeconds) return false;      // :38
+    double sq = 0.0;
+    for (int j = 0; j < 3; ++j) sq += (currentCenter[j] - previousCenter[j]) * (currentCenter[j] - previousCenter[j]);
+    if (std::sqrt(sq) > parameters.keyframeDecisionDistanceThreshold) return true;      // :40-44
+    std::vector<std::int32_t> previous(previousTrackIds);    // the std::set of :49-51 as a sorted vector
+    std::sort(previous.begin(), previous.end());
+    int prevCovisibilities = 0;
+    unsigned nTracks = 0;
+    for (std::int32_t id : currentTrackIds) {                // :55-58
+        ++nTracks;
+        if (std::binary_search(previous.begin(), previous.end(), id)) ++prevCovisibilities;
+    }
+    const float maxCovis = static_cast<float>(nTracks) * parameters.keyframeDecisionCovisibilityRatio;      // :61
+    return prevCovisibilities <= maxCovis;                   // :62: the int converts to float
+}
+
+// What addKeyframeCommonOuter knows of a frame that carries tracker features only (mapper_helpers.cpp:1196): its KfId and time, poseCW
+// (insertNewKeyframeCandidate's result), the pinhole stand-in of its camera, the tracker features (points[0], id, depth of
+// mapperInput.trackerFeatures), optionally the host's camera.isValidPixel per feature, a DEVICE depth image standing in for frame->getDepth
+// (float32, rows depthStride elements apart) and a DEVICE valid mask (bytes, rows maskStride apart).
+struct TrackerFrameAdmission {
+    std::int32_t id = -1;
+    double t = 0.0;
+    DeviceKeyframePoses::Pose poseCW{};
+    ms_pinhole camera{};
+    std::int32_t focalLength = 0;
+    std::vector<float> x, y, depth;
+    std::vector<std::int32_t> trackIds;
+    std::vector<std::uint8_t> validPixel;                    // empty: every feature passes
+    const float *depthImage = nullptr;
+    std::int32_t depthWidth = 0, depthHeight = 0, depthStride = 0;
+    const std::uint8_t *validMask = nullptr;
+    std::int32_t maskWidth = 0, maskHeight = 0, maskStride = 0;
+};
+
+struct AdmittedTrackerFrame {
+    std::size_t keyPoints = 0, droppedByValidPixel = 0, droppedByMask = 0, depthsFromImage = 0;
+    std::vector<std::int32_t> keyPointTrackIds;              // what matchTrackedFeatures takes next
+    std::vector<std::int32_t> keyPointFeature;               // the tracker feature behind each keypoint
+};
+
+// Keyframe::addTrackerFeatures and processKeyPoints (keyframe.cpp:34-69, :118-133) for one frame into `slot`: ONE device call, no table row
+// uploaded.  Writes M.keyframes (the slot's row = -1), M.keypoints and M.poses; fills the slot's record: id, t, previous / next (the frame
+// follows `previousSlot`, -1 for the first, mapdb.cpp:84-87), cameraCenter, camera, focalLength, descBase = -1 (the frame has no descriptors)
+// and frames = nullptr.  The k-th KEPT feature becomes keypoint k with its own id and depth (the reference keys keyPointToTrackId by the
+// feature index, keyframe.cpp:129).  The refusals of the mirror come before the call as std::invalid_argument; a refusal of
+// the call throws and leaves the tables and the record as they were.
+inline AdmittedTrackerFrame admitTrackerFrame(Context &ctx, MapTables M, std::int32_t slot, std::int32_t previousSlot, const TrackerFrameAdmission &frame) {
+    M.require("admitTrackerFrame", M.KEYPOINTS | M.POSES | M.IDS | M.TIMES | M.LINKS | M.CENTRES | M.CAMERAS | M.FOCALS | M.DESC_BASES | M.FRAMES);
+    const std::size_t nKf = M.keyframes.size(), n = frame.x.size();
+    if (slot < 0 || (std::size_t)slot >= nKf || previousSlot < -1 || (std::size_t)(previousSlot + 1) > nKf || previousSlot == slot)
+        throw std::invalid_argument("admitTrackerFrame: slot " + std::to_string(slot) + " or previous slot " + std::to_string(previousSlot) + " outside the table");
+    KeyframeSlots &S = M.slots;
+    if (S.id[slot] >= 0) throw std::invalid_argument("admitTrackerFrame: slot " + std::to_string(slot) + " holds keyframe " + std::to_string(S.id[slot]));
+    if (previousSlot >= 0 && S.id[previousSlot] < 0) throw std::invalid_argument("admitTrackerFrame: previous slot " + std::to_string(previousSlot) + " is empty");
+    if (frame.id < 0) throw std::invalid_argument("admitTrackerFrame: KfId " + std::to_string(frame.id));
+    if (frame.y.size() != n || frame.depth.size() != n || frame.trackIds.size() != n || (!frame.validPixel.empty() && frame.validPixel.size() != n))
+        throw std::invalid_argument("admitTrackerFrame: one y, depth and id (and validPixel) per tracker feature");
+    ms_frame_admit_args args{};
+    args.slot = slot;
+    std::copy(frame.poseCW.begin(), frame.poseCW.end(), args.pose);
+    args.depth_image = frame.depthImage; args.depth_width = frame.depthWidth; args.depth_height = frame.depthHeight; args.depth_stride = frame.depthStride;
+    args.valid_mask = frame.validMask; args.mask_width = frame.maskWidth; args.mask_height = frame.maskHeight; args.mask_stride = frame.maskStride;
+    AdmittedTrackerFrame out;
+    const std::size_t cap = std::min(n, M.keyframes.stride());
+    out.keyPointTrackIds.resize(cap); out.keyPointFeature.resize(cap);
+    std::int32_t counts[4] = {0, 0, 0, 0};
+    ctx.check(ms_frame_admit(ctx.get(), M.keyframes.mutableTable(), (int)nKf, (int)M.keyframes.stride(), (int)M.keyframes.mapPointCount(), M.keypoints->mutableX(),
+                             M.keypoints->mutableY(), M.keypoints->mutableOctave(), M.keypoints->mutableDepth(), M.poses->pose(), frame.x.data(), frame.y.data(),
+                             frame.trackIds.data(), frame.depth.data(), frame.validPixel.empty() ? nullptr : frame.validPixel.data(), (int)n, &args, out.keyPointTrackIds.data(),
+                             out.keyPointFeature.data(), (int)cap, counts), "ms_frame_admit");
+    out.keyPoints = (std::size_t)counts[0]; out.droppedByValidPixel = (std::size_t)counts[1]; out.droppedByMask = (std::size_t)counts[2];
+    out.depthsFromImage = (std::size_t)counts[3];
+    out.keyPointTrackIds.resize(out.keyPoints); out.keyPointFeature.resize(out.keyPoints);
+    S.id[slot] = frame.id; S.t[slot] = frame.t;
+    S.previous[slot] = previousSlot; S.next[slot] = -1;      // keyframe.cpp:82-83, then mapdb.cpp:84-87
+    if (previousSlot >= 0) S.next[previousSlot] = slot;
+    const auto &P = frame.poseCW;                            // cameraCenter() = -R^T t
+    for (int j = 0; j < 3; ++j) S.cameraCenter[slot][j] = -(P[j] * P[3] + P[4 + j] * P[7] + P[8 + j] * P[11]);
+    S.camera[slot] = frame.camera; S.focalLength[slot] = frame.focalLength;
+    S.descBase[slot] = -1; S.frames[slot] = nullptr;
+    return out;
 }
 
 // ---- a new keyframe from the extractor's output to the device tables (ms_keyframe_admit) ---------------------------------------------------

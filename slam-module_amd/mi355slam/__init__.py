@@ -1581,6 +1581,79 @@ def bow_vector(ctx, word, weight, n, vocab_words):
     return out
 
 
+# ---- a frame of tracker features to the map tables (ms_frame_admit) ----
+class FrameAdmitArgsC(C.Structure):
+    """ms_frame_admit_args"""
+    _fields_ = [("slot", C.c_int32), ("pose", C.c_double * 12), ("depth_image", C.c_void_p), ("depth_width", C.c_int32), ("depth_height", C.c_int32),
+                ("depth_stride", C.c_int32), ("valid_mask", C.c_void_p), ("mask_width", C.c_int32), ("mask_height", C.c_int32), ("mask_stride", C.c_int32)]
+
+
+FRAME_ADMIT_TABLES = ("kf_mp", "kp_x", "kp_y", "kp_octave", "kp_depth", "kf_pose")
+
+
+def _frame_admit_args(args):
+    """dict(slot, pose [12], depth_image (a DevBuf of float32 or None), depth_width, depth_height, depth_stride (the width when absent),
+    valid_mask (a DevBuf of bytes or None), mask_width, mask_height, mask_stride (the width when absent)) -> ms_frame_admit_args"""
+    pose = np.ascontiguousarray(args["pose"], np.float64).reshape(12)
+    dw, mw = int(args.get("depth_width", 0)), int(args.get("mask_width", 0))
+    return FrameAdmitArgsC(int(args["slot"]), (C.c_double * 12)(*pose), _vp(args.get("depth_image")).value, dw, int(args.get("depth_height", 0)),
+                           int(args.get("depth_stride", dw)), _vp(args.get("valid_mask")).value, mw, int(args.get("mask_height", 0)), int(args.get("mask_stride", mw)))
+
+
+def _frame_admit_features(features):
+    """dict(x, y, id, depth, keep (optional); n_tracks, when given, overrides their length; an array that is None goes as NULL) -> the five
+    host arrays and n_tracks"""
+    opt = lambda k, dt: None if features.get(k) is None else np.ascontiguousarray(features[k], dt).reshape(-1)
+    x, y, ids, depth, keep = opt("x", np.float32), opt("y", np.float32), opt("id", np.int32), opt("depth", np.float32), opt("keep", np.uint8)
+    n = int(features["n_tracks"]) if "n_tracks" in features else next((len(a) for a in (x, y, ids, depth) if a is not None), 0)
+    return (x, y, ids, depth, keep), n
+
+
+def frame_admit_validate(tables, n_kf, stride, n_mp, features, args, cap_kp, kp_track=True, kp_feature=True, counts=True):
+    """ms_frame_admit_validate, the host half of ms_frame_admit (no context, no device).  tables: a dict of the names in FRAME_ADMIT_TABLES
+    (numpy arrays, DevBufs, pointers or None: only their presence is looked at); features: _frame_admit_features' dict; args:
+    _frame_admit_args' dict or None.  Returns (rc, message)."""
+    p = lambda k: _vp(tables.get(k))
+    A = _frame_admit_args(args) if args is not None else None
+    arrs, n = _frame_admit_features(features)
+    cap = max(int(cap_kp), 1)
+    why, cnt, trk, feat = C.create_string_buffer(512), np.zeros(4, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    rc = lib().ms_frame_admit_validate(p("kf_mp"), int(n_kf), int(stride), int(n_mp), p("kp_x"), p("kp_y"), p("kp_octave"), p("kp_depth"), p("kf_pose"),
+                                       *[_vp(a) for a in arrs], int(n), C.byref(A) if A is not None else None, _vp(trk if kp_track else None),
+                                       _vp(feat if kp_feature else None), int(cap_kp), _vp(cnt if counts else None), why, C.c_size_t(512))
+    return rc, why.value.decode()
+
+
+def frame_admit_device(ctx, tables, n_kf, stride, n_mp, features, args, cap_kp=None):
+    """ms_frame_admit without raising.  tables: a dict of DevBufs named in FRAME_ADMIT_TABLES, updated in place; features: the HOST tracker
+    features (_frame_admit_features' dict); args: _frame_admit_args' dict; cap_kp: the length of the host outputs (the number of features
+    when absent).  Only the host outputs come down.  Returns (rc, dict(counts [4]; on success kp_track, kp_feature cut to n_kp))."""
+    A = _frame_admit_args(args)
+    arrs, n = _frame_admit_features(features)
+    cap = int(n if cap_kp is None else cap_kp)
+    trk, feat, counts = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(4, np.int32)
+    p = lambda k: _vp(tables[k])
+    rc = lib().ms_frame_admit(ctx._h, p("kf_mp"), int(n_kf), int(stride), int(n_mp), p("kp_x"), p("kp_y"), p("kp_octave"), p("kp_depth"), p("kf_pose"),
+                              *[_vp(a) for a in arrs], int(n), C.byref(A), _vp(trk), _vp(feat), cap, _vp(counts))
+    res = dict(counts=counts)
+    if rc == 0:
+        res.update(kp_track=trk[:counts[0]].copy(), kp_feature=feat[:counts[0]].copy())
+    return rc, res
+
+
+def frame_admit(ctx, kf_table, n_mp, kp, poses, features, args, cap_kp=None):
+    """Keyframe::addTrackerFeatures / processKeyPoints on the device tables (ms_frame_admit): the host's tracker features go into slot
+    args["slot"] of kf_table (a KeyframeTable), kp (a KeypointTable) and poses (a KeyframePoseTable).  Returns frame_admit_device's dict
+    with the touched slot as numpy added, for tests: row, x, y, octave, depth [stride] and pose [12].  Raises MsError."""
+    tables = dict(kf_mp=kf_table.kf_mp, kp_x=kp.x, kp_y=kp.y, kp_octave=kp.octave, kp_depth=kp.depth, kf_pose=poses.pose)
+    rc, res = frame_admit_device(ctx, tables, kf_table.n_kf, kf_table.stride, n_mp, features, args, cap_kp)
+    ctx.check(rc, "ms_frame_admit")
+    slot, shape = int(args["slot"]), (kf_table.n_kf, kf_table.stride)
+    res.update(row=kf_table.download()[slot], x=kp.x.download(np.float32, shape)[slot], y=kp.y.download(np.float32, shape)[slot],
+               octave=kp.octave.download(np.int32, shape)[slot], depth=kp.depth.download(np.float32, shape)[slot], pose=poses.download()[slot])
+    return res
+
+
 class KeyframeTable:
     """Keyframe::mapPoints of every keyframe on the device: kf_mp [n_kf, stride] int32, entry (k, j) = the map-point table row bound to
     keypoint j of the keyframe in slot k, -1 for none.  The queries take n_mp (rows of the map-point table; an entry outside [0, n_mp)
