@@ -2023,6 +2023,87 @@ int ms_frame_admit_validate(const int32_t *kf_mp, int n_kf, int stride, int n_mp
     const ms_frame_admit_args *args,
     const int32_t *kp_track, const int32_t *kp_feature, int cap_kp, const int32_t *counts, char *why, size_t why_bytes);
 
+/* ---- the viewer map and the point-cloud record on the device map tables ------------------------------------------------------
+ * The last two steps of addKeyframeCommonInner, the only ones that hand the map to someone outside the mapper: publishMapForViewer
+ * (mapper_helpers.cpp:814-879, called at :1117 and :1129) and updatePointCloudRecording (:881-909, called at :1125, the recorder behind
+ * pointCloudSavePath).  Both walk every MapPoint once per keyframe; ms_map_publish is that walk as one pass over the rows of the tables of
+ * 9.5 - 9.22, and the record comes down as the CHANGES since the last call.  tests/map_publish_ref.py restates the call and is its
+ * specification.  Row r is PRESENT iff (uint32)r < n_mp and mp_live[r] != 0; an entry is VALID iff (uint32)r < n_mp; bits 0-1 of mp_flags are
+ * 3 = TRIANGULATED, 2 = UNSURE, 0 = NOT_TRIANGULATED.  MapPointStatus::BAD cannot be seen in a map: map_point.cpp:154 sets it on the line
+ * before the erase, so no present row carries it.
+ *
+ * View (:823-839), with MS_PUBLISH_VIEW.  Row r is PUBLISHED iff it is PRESENT and mp_flags[r] & 3 (:830).  The k-th published row in
+ * ascending row order -- row order stands in for the std::map<MpId> walk, as in ms_map_point_union -- gives pub_row[k] = r; pub_pos[3k ..] =
+ * (float)mp_pos[r], round to nearest even (cast<float>()); pub_norm[3k ..] = mp_norm[r] bit for bit; pub_color[3k ..] = (float)c / 255.0f, a
+ * float division per channel (0 with mp_color == NULL); pub_status[k] = int(MapPointStatus): 0 when bit 0 is set, 2 otherwise; pub_bits[k]
+ * bit 0 = localMap: r is among the VALID entries of local_rows (workspaceBA.localMpIds as rows, e.g. the rows of the last
+ * ms_ba_window_lists; any order, repeats allowed, an entry that is not VALID is ignored); bit 1 = nowVisible: r is a VALID entry among all
+ * `stride` entries of current_slot (visibleIds, :823-826).
+ *
+ * Record (:881-909), with MS_PUBLISH_RECORD, on the caller's record state rec_pos (float [3 n_mp]) / rec_state (uint8 [n_mp]: 0 never
+ * recorded, 1 recorded, 2 removed), DEVICE arrays that start as zero bytes and that the caller extends with zeros when n_mp grows.  n_obs are
+ * the whole-map counts of ms_observation_count, which the chain keeps current.  For every row in ascending order, p = (float)mp_pos[r]:
+ *   1. PRESENT, n_obs[r] >= min_record_obs, state 0 or 2: event NEW (1) with p and the normal; state = 1, rec_pos = p.  (State 2 on a present
+ *      row: the table reused the row for a new map point.  The reference never reuses an id; on tables that never reuse rows this is never taken.)
+ *   2. PRESENT, n_obs[r] >= min_record_obs, state 1: if rec_pos differs from p as Eigen's != compares -- by float value per component, so
+ *      -0.0f equals 0.0f and a NaN always differs -- event MOVED (2) with p and the normal, rec_pos = p; otherwise nothing.
+ *   3. PRESENT with fewer observations: nothing, whatever its state (:889).
+ *   4. not PRESENT, state 1: event REMOVED (3) with position 0, 0, 0 (:902-907) and a zero normal; state = 2, rec_pos keeps its bytes.
+ * Events come out in ascending row order as ev_row, ev_kind, ev_pos[3], ev_norm[3]: the reference's two loops write disjoint records, so one
+ * ordered stream carries the same information.
+ *
+ * Keyframes (:854): for i < n_list, pose_wc[16 i ..] = the rigid inverse of kf_pose[kf_list[i]] as a row-major 4 x 4 float matrix: R^T | -R^T t
+ * in float64, -((R0j*t0 + R1j*t1) + R2j*t2) with no contraction, then cast to float; the last row is 0 0 0 1.  The reference takes Eigen's
+ * general 4 x 4 inverse; for rigid poses the float results agree to one unit in the last place.
+ *
+ * counts (HOST [8]) = n_pub, n_ev, the NEW, MOVED and REMOVED events, the published rows with localMap, those with nowVisible, the present
+ * rows skipped as NOT_TRIANGULATED.  Every verdict is taken before any write (the rule of ms_frame_finish and ms_ba_window_apply):
+ * MS_ERR_CAPACITY when n_pub > cap_pub or n_ev > cap_ev; then no output array is written, rec_pos and rec_state keep their bytes, and counts
+ * holds the needed numbers.  Nothing behind n_pub / n_ev is written.  Before any device call (ms_map_publish_validate, the host validation
+ * alone: no context, no device; `why` receives the message): MS_ERR_INVALID for `what` outside 1 .. 3, current_slot outside [-1, n_kf), a
+ * kf_list slot out of range or listed twice, min_record_obs < 0, stride < 1, a negative size or capacity, a missing array for the chosen
+ * `what` (n_obs / rec_* with RECORD, an output array with a non-zero capacity, local_rows with n_local > 0); MS_ERR_CAPACITY beyond the
+ * MS_COVIS_MAX_* caps (n_local: below MS_COVIS_MAX_MP; n_list: MS_COVIS_MAX_KF).  n_mp == 0, n_list == 0, n_local == 0 and current_slot ==
+ * -1 are fine; with n_mp == 0 and n_list == 0 nothing is launched.
+ * FIVE launches whatever the sizes (clear the two mark bitmaps and write pose_wc; mark, the only atomics ORing bits into bitmap words; count
+ * per workgroup; one workgroup's block_offsets over both streams with the verdict and the head; pack, recomputing the predicates), no host
+ * wait between them; at most one upload block (kf_list); TWO downloads through the context's pinned block: the head with pose_wc, then
+ * exactly the bytes that n_pub and n_ev name (none when both are 0).  That is one copy more than ms_frame_finish: the caps are the size of
+ * the map and the answer usually is not, so one download sized by the caps would move the whole map for a handful of events.  Integer
+ * arithmetic decides every position: the same tables give the same bytes on every call, at any capacity.  The workspace only grows;
+ * nothing is allocated after warm-up (ms_debug_host_allocs). */
+#define MS_PUBLISH_VIEW 1
+#define MS_PUBLISH_RECORD 2
+typedef struct {
+    int32_t what;                        /* MS_PUBLISH_VIEW | MS_PUBLISH_RECORD; 0 is invalid */
+    int32_t current_slot;                /* the slot with the largest KfId (mapDB.keyframes.rbegin()), -1 for none */
+    int32_t min_record_obs;              /* the 4 of :889 */
+} ms_map_publish_args;
+int ms_map_publish(ms_ctx *ctx,
+    /* DEVICE tables, read; n_obs may be NULL without MS_PUBLISH_RECORD, mp_color may be NULL */
+    const double *mp_pos, const float *mp_norm, const uint8_t *mp_flags, const uint8_t *mp_live,
+    const int32_t *n_obs, const uint8_t *mp_color, int n_mp,
+    const int32_t *kf_mp, int n_kf, int stride, const double *kf_pose,
+    const int32_t *local_rows, int n_local,
+    /* DEVICE, updated in place: the record state; each may be NULL without MS_PUBLISH_RECORD */
+    float *rec_pos, uint8_t *rec_state,
+    /* HOST */
+    const ms_map_publish_args *args, const int32_t *kf_list, int n_list,
+    /* HOST outputs: pub_* [cap_pub], ev_* [cap_ev], pose_wc [16 n_list], counts [8] */
+    int32_t *pub_row, float *pub_pos, float *pub_norm, float *pub_color, uint8_t *pub_status, uint8_t *pub_bits, int cap_pub,
+    int32_t *ev_row, uint8_t *ev_kind, float *ev_pos, float *ev_norm, int cap_ev,
+    float *pose_wc, int32_t *counts);
+/* the twin is named _validate: the set of ms_*_check functions is closed at 22 (tests/test_map_checks_corpus.py records them) */
+int ms_map_publish_validate(const double *mp_pos, const float *mp_norm, const uint8_t *mp_flags, const uint8_t *mp_live,
+    const int32_t *n_obs, const uint8_t *mp_color, int n_mp,
+    const int32_t *kf_mp, int n_kf, int stride, const double *kf_pose,
+    const int32_t *local_rows, int n_local,
+    const float *rec_pos, const uint8_t *rec_state,
+    const ms_map_publish_args *args, const int32_t *kf_list, int n_list,
+    const int32_t *pub_row, const float *pub_pos, const float *pub_norm, const float *pub_color, const uint8_t *pub_status, const uint8_t *pub_bits, int cap_pub,
+    const int32_t *ev_row, const uint8_t *ev_kind, const float *ev_pos, const float *ev_norm, int cap_ev,
+    const float *pose_wc, const int32_t *counts, char *why, size_t why_bytes);
+
 #ifdef __cplusplus
 }
 #endif

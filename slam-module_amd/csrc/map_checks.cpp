@@ -1,5 +1,5 @@
 // map_checks.cpp -- the host validation of every call on the device map tables: the 22 exported ms_*_check functions, in the order of
-// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate, ms_bow_vector_validate, ms_map_extract_validate and ms_frame_admit_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
+// mi355slam.h, and ms_frame_finish_validate, ms_keyframe_admit_validate, ms_bow_vector_validate, ms_map_extract_validate, ms_frame_admit_validate and ms_map_publish_validate behind them.  Each turns bad arguments away with a code and a message before any device call; its entry point (in the family's .hip file)
 // calls it with the context's error buffer.  Plain C++17, no HIP and no context: the checks read the HOST arguments only and ask of the DEVICE
 // arrays nothing but whether they are there, so this file compiles alone and runs under sanitizers (tests/map_checks_corpus.cpp).  The first
 // failing statement decides the message, so the order of the statements inside a function is part of the interface.
@@ -930,5 +930,40 @@ extern "C" int ms_frame_admit_validate(const int32_t *kf_mp, int n_kf, int strid
     std::sort(ids.begin(), ids.end());
     for (int i = 1; i < n_tracks; ++i)
         if (ids[i - 1] == ids[i]) INVALID("frame admit: track id %d is listed twice", ids[i]);
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ map_publish.hip
+// (named _validate, not _check: the header says why)
+extern "C" int ms_map_publish_validate(const double *mp_pos, const float *mp_norm, const uint8_t *mp_flags, const uint8_t *mp_live, const int32_t *n_obs, const uint8_t *mp_color,
+                                       int n_mp, const int32_t *kf_mp, int n_kf, int stride, const double *kf_pose, const int32_t *local_rows, int n_local, const float *rec_pos,
+                                       const uint8_t *rec_state, const ms_map_publish_args *args, const int32_t *kf_list, int n_list, const int32_t *pub_row, const float *pub_pos,
+                                       const float *pub_norm, const float *pub_color, const uint8_t *pub_status, const uint8_t *pub_bits, int cap_pub, const int32_t *ev_row,
+                                       const uint8_t *ev_kind, const float *ev_pos, const float *ev_norm, int cap_ev, const float *pose_wc, const int32_t *counts, char *why,
+                                       size_t why_bytes) {
+    (void)mp_color;                                          // may be NULL
+    if (n_mp < 0 || n_kf < 0 || n_local < 0 || n_list < 0 || cap_pub < 0 || cap_ev < 0)
+        INVALID("map publish: negative size (%d map points, %d slots, %d local rows, %d listed slots, cap_pub %d, cap_ev %d)", n_mp, n_kf, n_local, n_list, cap_pub, cap_ev);
+    if (stride < 1) return ms_why_stride("map publish", stride, why, why_bytes);
+    if (!args || !counts) INVALID("map publish: missing array (args or counts)");
+    if (args->what < 1 || args->what > (MS_PUBLISH_VIEW | MS_PUBLISH_RECORD)) INVALID("map publish: what %d outside 1 .. 3", args->what);
+    if (args->min_record_obs < 0) INVALID("map publish: min_record_obs %d", args->min_record_obs);
+    const bool view = (args->what & MS_PUBLISH_VIEW) != 0, record = (args->what & MS_PUBLISH_RECORD) != 0;
+    if (n_mp > 0 && (!mp_pos || !mp_norm || !mp_flags || !mp_live)) INVALID("map publish: missing array (mp_pos, mp_norm, mp_flags or mp_live)");
+    if (n_kf > 0 && (!kf_mp || !kf_pose)) INVALID("map publish: missing array (kf_mp or kf_pose)");
+    if (n_local > 0 && !local_rows) INVALID("map publish: missing array (local_rows with %d entries)", n_local);
+    if (n_list > 0 && (!kf_list || !pose_wc)) INVALID("map publish: missing array (kf_list or pose_wc with %d listed slots)", n_list);
+    if (record && n_mp > 0 && (!n_obs || !rec_pos || !rec_state)) INVALID("map publish: missing array (n_obs, rec_pos or rec_state with MS_PUBLISH_RECORD)");
+    if (view && cap_pub > 0 && (!pub_row || !pub_pos || !pub_norm || !pub_color || !pub_status || !pub_bits)) INVALID("map publish: missing array (a pub_ array with cap_pub %d)", cap_pub);
+    if (record && cap_ev > 0 && (!ev_row || !ev_kind || !ev_pos || !ev_norm)) INVALID("map publish: missing array (an ev_ array with cap_ev %d)", cap_ev);
+    if (args->current_slot < -1 || args->current_slot >= n_kf) INVALID("map publish: current slot %d outside [-1, %d)", args->current_slot, n_kf);
+    if (n_local >= MS_COVIS_MAX_MP || n_list > MS_COVIS_MAX_KF || ms_map_over_capacity(n_kf, stride, n_mp, 0))
+        return ms_why(MS_ERR_CAPACITY, why, why_bytes, "map publish: %d slots / stride %d / %d map points / %d local rows / %d listed slots, caps %d / %d / below %d / below %d / %d", n_kf,
+                      stride, n_mp, n_local, n_list, MS_COVIS_MAX_KF, MS_COVIS_MAX_STRIDE, MS_COVIS_MAX_MP, MS_COVIS_MAX_MP, MS_COVIS_MAX_KF);
+    int bad = 0;
+    if (!ms_distinct_in_range(kf_list, n_list, n_kf, &bad)) {
+        if (bad < 0) INVALID("map publish: listed slot %d is listed twice", -1 - bad);
+        INVALID("map publish: listed slot %d outside [0, %d)", kf_list[bad], n_kf);
+    }
     return MS_OK;
 }

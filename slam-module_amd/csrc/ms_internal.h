@@ -35,6 +35,7 @@ enum MsWorkspaceId {
     MS_WS_BOW_VECTOR,       // ms_bow_vector (bow_vector.hip): the device head {n_words, n_bad} that goes down
     MS_WS_MAP_EXTRACT,      // ms_map_extract (map_extract.hip): device list / keypoint counts / pool offsets; entries per row / row maps / block counts; the head that goes down
     MS_WS_FRAME_ADMIT,      // ms_frame_admit (frame_admit.hip): device features (x / y / depth / id / keep); the keypoint index per feature; the block that goes down
+    MS_WS_MAP_PUBLISH,      // ms_map_publish (map_publish.hip): device listed slots; mark bitmaps / block counts / offsets; the head with pose_wc and the packed streams that go down
     MS_WS_COUNT
 };
 

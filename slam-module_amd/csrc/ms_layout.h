@@ -1,5 +1,5 @@
 // ms_layout.h -- byte layout of the staging blocks of the map-side entry points (loop RANSAC, Sim3 optimise, project gate, map refresh /
-// loop correct, covisibility / map point union, triangulate, observation count / map cull, observation lists, match tracked, map fuse, create points, BA window, search bind, loop chain, frame finish, keyframe admit, map extract, frame admit).  Plain C++17, no HIP: tests/ms_layout_check.cpp compiles it alone.
+// loop correct, covisibility / map point union, triangulate, observation count / map cull, observation lists, match tracked, map fuse, create points, BA window, search bind, loop chain, frame finish, keyframe admit, map extract, frame admit, map publish).  Plain C++17, no HIP: tests/ms_layout_check.cpp compiles it alone.
 //
 // A block is a run of arrays, each starting on a 256-byte boundary.  An entry point names every array once, in block order:
 //     MsLayout up;                                          // upload block: rows | flags

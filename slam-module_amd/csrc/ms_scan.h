@@ -1,6 +1,6 @@
 // ms_scan.h -- the stream-compaction skeleton of the map kernels: a lane's rank among the kept lanes of its workgroup, the
 // exclusive sum of one int per lane over the workgroup, and the one-workgroup exclusive scan of per-block totals.  Device code only; it is
-// included by the .hip files that pack something (project_gate, covis, map_cull, obs_lists, map_refresh, match_tracked, map_fuse, create_points, ba_window, search_bind, loop_chain, pose_tables, frame_finish, keyframe_admit, bow_vector, map_extract, frame_admit).
+// included by the .hip files that pack something (project_gate, covis, map_cull, obs_lists, map_refresh, match_tracked, map_fuse, create_points, ba_window, search_bind, loop_chain, pose_tables, frame_finish, keyframe_admit, bow_vector, map_extract, frame_admit, map_publish).
 //
 // BLOCK is the workgroup size, a multiple of 64; s_wave is BLOCK / 64 ints of LDS that the caller declares.  Everything is int32 and
 // bounded by the entry points' capacity checks.  Integer addition is exact and associative, so the order in which a scan adds its terms

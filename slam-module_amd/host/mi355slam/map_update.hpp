@@ -5,14 +5,17 @@
 // bundle adjustment whose window is gathered from the tables and written back into them (localBundleAdjustOnTables), the per-frame pose
 // adjustment (poseBundleAdjustOnTables), the end of a frame (finishFrame, removeKeyframes), the arrival of a frame of tracker features
 // (admitTrackerFrame, with makeKeyframeDecision in front of it), the arrival of a keyframe from the extractor's device output (admitKeyframe)
-// and the map copy for the front end (extractMap, copyMapToFrontend).
-// Results come back through Context::workspace and Context::download; nothing here owns device memory but the two row maps of a MapExtract.
+// and the map copy for the front end (extractMap, copyMapToFrontend), and the map as it leaves the mapper (publishMapForViewer,
+// updatePointCloudRecording).
+// Results come back through Context::workspace and Context::download; nothing here owns device memory but the two row maps of a MapExtract
+// and the record state of a DeviceMapPointRecords.
 #pragma once
 #include <algorithm>
 #include <array>
 #include <cmath>
 #include <functional>
 #include <limits>
+#include <map>
 #include <stdexcept>
 #include "bow_index.hpp"
 #include "bundle_adjuster.hpp"
@@ -1188,6 +1191,153 @@ inline MapExtract copyMapToFrontend(Context &ctx, MapTables backend, std::int32_
         if (s < 0 || (std::size_t)s >= backend.slots.id.size()) throw std::invalid_argument("copyMapToFrontend: slot " + std::to_string(s) + " outside the table");
     std::sort(active.begin(), active.end(), [&](std::int32_t a, std::int32_t b) { return backend.slots.id[a] < backend.slots.id[b]; });      // std::set<KfId>
     return extractMap(ctx, backend, active, frontend, keyPointCounts);
+}
+
+// ---- the viewer map and the point-cloud record on the device tables (ms_map_publish) ------------------------------------------------------
+// The record state of updatePointCloudRecording on the device: the last recorded position and the state (0 never recorded, 1 recorded,
+// 2 removed) of every table row.  It starts empty; grow() keeps what is there and puts zeros behind it, the caller's step when the map-point
+// table grows.  It never shrinks.
+class DeviceMapPointRecords {
+public:
+    explicit DeviceMapPointRecords(Context &ctx) : ctx_(&ctx) {}
+    void grow(std::size_t rows) {
+        if (rows <= n_) return;
+        std::vector<float> pos = pos_.download();
+        std::vector<std::uint8_t> state = state_.download();
+        pos.resize(3 * rows, 0.0f); state.resize(rows, 0);
+        pos_ = DeviceArray<float>(*ctx_, 3 * rows); state_ = DeviceArray<std::uint8_t>(*ctx_, rows);
+        pos_.upload(0, 3 * rows, pos.data()); state_.upload(0, rows, state.data());
+        n_ = rows;
+    }
+    std::size_t size() const { return n_; }
+    float *position() { return pos_.data(); }
+    std::uint8_t *state() { return state_.data(); }
+    std::vector<std::uint8_t> downloadState() const { return state_.download(); }
+private:
+    Context *ctx_;
+    std::size_t n_ = 0;
+    DeviceArray<float> pos_;
+    DeviceArray<std::uint8_t> state_;
+};
+
+// ViewerMapPoint / ViewerKeyframe (viewer_data_publisher.hpp) as the tables can fill them: `row` stands in for the MpId; origPoseWC and the
+// stereo clouds stay with the caller, who holds them.
+struct ViewerMapPoint {
+    std::int32_t row = -1;
+    std::array<float, 3> position{}, normal{}, color{};
+    int status = 0;
+    bool localMap = false, nowVisible = false;
+};
+struct ViewerKeyframe {
+    std::int32_t id = -1;
+    bool localMap = false, current = false;
+    std::array<float, 16> poseWC{};                          // row-major 4 x 4
+    std::vector<int> neighbors;                              // indices into ViewerMap::keyframes
+};
+struct ViewerMap {
+    std::vector<ViewerMapPoint> mapPoints;
+    std::vector<ViewerKeyframe> keyframes;                   // ascending KfId
+};
+// rows that lie on the device, e.g. workspaceBA.localMpIds as the last ms_ba_window_lists left them; any order, repeats allowed
+struct DeviceRows {
+    const std::int32_t *rows = nullptr;
+    std::size_t count = 0;
+};
+
+// publishMapForViewer (mapper_helpers.cpp:814-879) from the tables: ONE ms_map_publish call for the map points and every keyframe's poseWC,
+// ONE getNeighbors call over all keyframes for the neighbour indices (:862-872).  adjacentSlots is mapDB.adjacentKfIds as slots (:848-852).
+// An empty map of keyframes gives an empty result (:820).  Colours are not a table of MapTables: they come out as 0.  Writes nothing.
+inline ViewerMap publishMapForViewer(Context &ctx, MapTables M, const std::vector<std::int32_t> &adjacentSlots, DeviceRows localRows, int minNeighbourCovisibilities) {
+    M.require("publishMapForViewer", M.POINTS | M.FLAGS | M.LIVE | M.POSES | M.IDS | M.LINKS);
+    const std::size_t nKf = M.keyframes.size(), nMp = M.keyframes.mapPointCount();
+    for (std::int32_t k : adjacentSlots)
+        if (k < 0 || (std::size_t)k >= nKf) throw std::invalid_argument("publishMapForViewer: adjacent slot " + std::to_string(k) + " outside the table");
+    if (localRows.count && !localRows.rows) throw std::invalid_argument("publishMapForViewer: local rows without an array");
+    std::vector<std::int32_t> order;                         // mapDB.keyframes: the slots by ascending KfId
+    for (std::size_t k = 0; k < nKf; ++k) if (M.slots.id[k] >= 0) order.push_back((std::int32_t)k);
+    std::sort(order.begin(), order.end(), [&](std::int32_t a, std::int32_t b) { return M.slots.id[a] < M.slots.id[b]; });
+    ViewerMap out;
+    if (order.empty()) return out;
+    const std::int32_t current = order.back();               // mapDB.keyframes.rbegin()
+    const ms_map_publish_args args{MS_PUBLISH_VIEW, current, 0};
+    std::vector<std::int32_t> row(nMp);
+    std::vector<float> pos(3 * nMp), norm(3 * nMp), color(3 * nMp), poseWC(16 * order.size());
+    std::vector<std::uint8_t> status(nMp), bits(nMp);
+    std::int32_t counts[8] = {0};
+    ctx.check(ms_map_publish(ctx.get(), M.points->position(), M.points->norm(), M.flags->flags(), M.live->live(), M.observationCount, nullptr, (int)nMp, M.keyframes.table(),
+                             (int)nKf, (int)M.keyframes.stride(), M.poses->pose(), localRows.rows, (int)localRows.count, nullptr, nullptr, &args, order.data(),
+                             (int)order.size(), row.data(), pos.data(), norm.data(), color.data(), status.data(), bits.data(), (int)nMp, nullptr, nullptr, nullptr, nullptr, 0,
+                             poseWC.data(), counts), "ms_map_publish");
+    out.mapPoints.resize((std::size_t)counts[0]);
+    for (std::size_t k = 0; k < out.mapPoints.size(); ++k) {
+        ViewerMapPoint &p = out.mapPoints[k];
+        p.row = row[k]; p.status = status[k]; p.localMap = (bits[k] & 1) != 0; p.nowVisible = (bits[k] & 2) != 0;
+        for (int a = 0; a < 3; ++a) { p.position[a] = pos[3 * k + a]; p.normal[a] = norm[3 * k + a]; p.color[a] = color[3 * k + a]; }
+    }
+    std::vector<int> inds(nKf, -1);                          // :841-846
+    std::vector<NeighborQuery> queries(order.size());
+    out.keyframes.resize(order.size());
+    for (std::size_t i = 0; i < order.size(); ++i) {
+        const std::int32_t k = order[i];
+        inds[k] = (int)i;
+        ViewerKeyframe &kf = out.keyframes[i];
+        kf.id = M.slots.id[k];
+        kf.localMap = std::find(adjacentSlots.begin(), adjacentSlots.end(), k) != adjacentSlots.end();
+        kf.current = k == current;
+        std::copy(poseWC.begin() + 16 * i, poseWC.begin() + 16 * (i + 1), kf.poseWC.begin());
+        queries[i] = NeighborQuery{k, M.slots.previous[k], M.slots.next[k], minNeighbourCovisibilities, false};
+    }
+    const std::vector<std::vector<std::int32_t>> neighbours = getNeighbors(ctx, M.keyframes, M.flags, queries);
+    for (std::size_t i = 0; i < order.size(); ++i) {
+        for (std::int32_t k : neighbours[i]) out.keyframes[i].neighbors.push_back(inds.at((std::size_t)k));      // inds.at(kfId), :870
+        std::sort(out.keyframes[i].neighbors.begin(), out.keyframes[i].neighbors.end());                          // the std::map walk: ascending KfId
+    }
+    return out;
+}
+
+// MapPointRecord as updatePointCloudRecording fills it (:892-906), keyed by table row.
+struct MapPointRecord {
+    struct Position { float t; std::array<float, 3> p; };
+    std::vector<Position> positions;
+    std::array<float, 3> normal{};
+    bool removed = false;
+};
+
+// updatePointCloudRecording (mapper_helpers.cpp:881-909) from the tables: ONE ms_map_publish call brings down the CHANGES since the last call
+// (new, moved and removed points), and they are applied to hostRecords as :892-906 does.  M.observationCount must be current
+// (observationCountsOnDevice, or the chain that keeps it).  `records` grows to the table's rows.  A NEW event on a row that already has a record
+// -- the table reused a removed row, which the reference's ids never do -- starts that row's record again.  Returns the number of events.
+inline std::size_t updatePointCloudRecording(Context &ctx, MapTables M, DeviceMapPointRecords &records, float t, std::map<std::int32_t, MapPointRecord> &hostRecords,
+                                             int minObservations = 4) {
+    M.require("updatePointCloudRecording", M.POINTS | M.FLAGS | M.LIVE | M.COUNTS);
+    const std::size_t nMp = M.keyframes.mapPointCount();      // the record reads no keyframe table: the call gets none
+    if (minObservations < 0) throw std::invalid_argument("updatePointCloudRecording: minObservations < 0");
+    records.grow(nMp);
+    const ms_map_publish_args args{MS_PUBLISH_RECORD, -1, minObservations};
+    std::vector<std::int32_t> row(nMp);
+    std::vector<std::uint8_t> kind(nMp);
+    std::vector<float> pos(3 * nMp), norm(3 * nMp);
+    std::int32_t counts[8] = {0};
+    ctx.check(ms_map_publish(ctx.get(), M.points->position(), M.points->norm(), M.flags->flags(), M.live->live(), M.observationCount, nullptr, (int)nMp, nullptr, 0,
+                             (int)M.keyframes.stride(), nullptr, nullptr, 0, records.position(), records.state(), &args, nullptr, 0,
+                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, row.data(), kind.data(), pos.data(), norm.data(), (int)nMp, nullptr, counts),
+              "ms_map_publish");
+    for (std::size_t k = 0; k < (std::size_t)counts[1]; ++k) {
+        const std::array<float, 3> p{pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]}, n{norm[3 * k], norm[3 * k + 1], norm[3 * k + 2]};
+        if (kind[k] == 1) {                                  // :892-894
+            MapPointRecord r;
+            r.positions.push_back({t, p}); r.normal = n;
+            hostRecords[row[k]] = r;
+        } else if (kind[k] == 2) {                           // :895-898
+            MapPointRecord &r = hostRecords.at(row[k]);
+            r.positions.push_back({t, p}); r.normal = n;
+        } else {                                             // :902-907
+            MapPointRecord &r = hostRecords.at(row[k]);
+            r.removed = true;
+            r.positions.push_back({t, p});
+        }
+    }
+    return (std::size_t)counts[1];
 }
 
 }  // namespace mi355slam

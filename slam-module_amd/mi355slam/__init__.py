@@ -1654,6 +1654,86 @@ def frame_admit(ctx, kf_table, n_mp, kp, poses, features, args, cap_kp=None):
     return res
 
 
+# ---- the viewer map and the point-cloud record (ms_map_publish) ----
+MS_PUBLISH_VIEW, MS_PUBLISH_RECORD = 1, 2
+
+
+class MapPublishArgsC(C.Structure):
+    """ms_map_publish_args"""
+    _fields_ = [("what", C.c_int32), ("current_slot", C.c_int32), ("min_record_obs", C.c_int32)]
+
+
+MAP_PUBLISH_TABLES = ("mp_pos", "mp_norm", "mp_flags", "mp_live", "n_obs", "mp_color", "kf_mp", "kf_pose", "local_rows", "rec_pos", "rec_state")
+MAP_PUBLISH_PUB = (("pub_row", np.int32, 1), ("pub_pos", np.float32, 3), ("pub_norm", np.float32, 3), ("pub_color", np.float32, 3), ("pub_status", np.uint8, 1),
+                   ("pub_bits", np.uint8, 1))
+MAP_PUBLISH_EV = (("ev_row", np.int32, 1), ("ev_kind", np.uint8, 1), ("ev_pos", np.float32, 3), ("ev_norm", np.float32, 3))
+
+
+def _map_publish_call(fn, head, tables, n_mp, n_kf, stride, n_local, args, kf_list, n_list, out, cap_pub, cap_ev, tail):
+    """the argument list ms_map_publish and ms_map_publish_validate share, in the header's order"""
+    p, o = (lambda k: _vp(tables.get(k))), (lambda k: _vp(out.get(k)))
+    return fn(*head, p("mp_pos"), p("mp_norm"), p("mp_flags"), p("mp_live"), p("n_obs"), p("mp_color"), int(n_mp), p("kf_mp"), int(n_kf), int(stride), p("kf_pose"),
+              p("local_rows"), int(n_local), p("rec_pos"), p("rec_state"), C.byref(args) if args is not None else None, _vp(kf_list), int(n_list),
+              *[o(k) for k, _, _ in MAP_PUBLISH_PUB], int(cap_pub), *[o(k) for k, _, _ in MAP_PUBLISH_EV], int(cap_ev), o("pose_wc"), o("counts"), *tail)
+
+
+def _map_publish_out(cap_pub, cap_ev, n_list):
+    out = {k: np.zeros(max(cap, 1) * w, dt) for spec, cap in ((MAP_PUBLISH_PUB, cap_pub), (MAP_PUBLISH_EV, cap_ev)) for k, dt, w in spec}
+    out.update(pose_wc=np.zeros(16 * max(n_list, 1), np.float32), counts=np.zeros(8, np.int32))
+    return out
+
+
+def map_publish_validate(tables, n_mp, n_kf, stride, n_local, args, kf_list, cap_pub, cap_ev, n_list=None, missing=()):
+    """ms_map_publish_validate, the host half of ms_map_publish (no context, no device).  tables: a dict of the names in MAP_PUBLISH_TABLES
+    (numpy arrays, DevBufs, pointers or None: only their presence is looked at); args: dict(what, current_slot, min_record_obs) or None;
+    kf_list: the listed slots or None; missing: names of output arrays (MAP_PUBLISH_PUB / _EV, pose_wc, counts) passed as NULL.
+    Returns (rc, message)."""
+    A = MapPublishArgsC(int(args["what"]), int(args.get("current_slot", -1)), int(args.get("min_record_obs", 4))) if args is not None else None
+    lst = None if kf_list is None else np.ascontiguousarray(kf_list, np.int32).reshape(-1)
+    n = int(n_list) if n_list is not None else (0 if lst is None else len(lst))
+    out = _map_publish_out(1, 1, 1)                          # only their presence is looked at
+    for k in missing:
+        out[k] = None
+    why = C.create_string_buffer(512)
+    rc = _map_publish_call(lib().ms_map_publish_validate, (), tables, n_mp, n_kf, stride, n_local, A, lst, n, out, cap_pub, cap_ev, (why, C.c_size_t(512)))
+    return rc, why.value.decode()
+
+
+def map_publish_device(ctx, tables, n_mp, n_kf, stride, n_local, args, kf_list=(), cap_pub=None, cap_ev=None):
+    """ms_map_publish without raising.  tables: a dict of DevBufs (or None) named in MAP_PUBLISH_TABLES; rec_pos / rec_state are updated in
+    place.  args: dict(what, current_slot, min_record_obs); kf_list: the slots whose poseWC is wanted; cap_pub / cap_ev: the lengths of the
+    host outputs (n_mp when absent).  Returns (rc, dict(counts [8]; on success pose_wc [n_list, 4, 4] and the MAP_PUBLISH_PUB / _EV arrays
+    cut to n_pub / n_ev))."""
+    A = MapPublishArgsC(int(args["what"]), int(args.get("current_slot", -1)), int(args.get("min_record_obs", 4)))
+    lst = np.ascontiguousarray(kf_list, np.int32).reshape(-1)
+    cp, ce = int(n_mp if cap_pub is None else cap_pub), int(n_mp if cap_ev is None else cap_ev)
+    out = _map_publish_out(cp, ce, len(lst))
+    rc = _map_publish_call(lib().ms_map_publish, (ctx._h,), tables, n_mp, n_kf, stride, n_local, A, lst, len(lst), out, cp, ce, ())
+    res = dict(counts=out["counts"])
+    if rc == 0:
+        n_pub, n_ev = int(out["counts"][0]), int(out["counts"][1])
+        res["pose_wc"] = out["pose_wc"][:16 * len(lst)].reshape(len(lst), 4, 4).copy()
+        for spec, n in ((MAP_PUBLISH_PUB, n_pub), (MAP_PUBLISH_EV, n_ev)):
+            for k, _, w in spec:
+                res[k] = out[k][:n * w].reshape((n, w) if w > 1 else (n,)).copy()
+    return rc, res
+
+
+def map_publish(ctx, table, kf_table, poses, mp_flags, mp_live, n_obs, rec_pos, rec_state, what, current_slot=-1, min_record_obs=4, local_rows=None, kf_list=(),
+                mp_color=None):
+    """publishMapForViewer / updatePointCloudRecording on the device tables (ms_map_publish): table is a MapPointTable (pos, norm), kf_table
+    a KeyframeTable, poses a KeyframePoseTable; mp_flags, mp_live, n_obs, mp_color, rec_pos and rec_state are DevBufs (None where the header
+    allows NULL); local_rows is a DevBuf of int32 (all of it is the list) or None.  rec_pos / rec_state are updated in place.  Returns
+    map_publish_device's dict: numpy arrays cut to the counts.  Raises MsError."""
+    n_mp = table.n
+    tables = dict(mp_pos=table.pos, mp_norm=table.norm, mp_flags=mp_flags, mp_live=mp_live, n_obs=n_obs, mp_color=mp_color, kf_mp=kf_table.kf_mp, kf_pose=poses.pose,
+                  local_rows=local_rows, rec_pos=rec_pos, rec_state=rec_state)
+    n_local = 0 if local_rows is None else local_rows.nbytes // 4
+    rc, res = map_publish_device(ctx, tables, n_mp, kf_table.n_kf, kf_table.stride, n_local, dict(what=what, current_slot=current_slot, min_record_obs=min_record_obs), kf_list)
+    ctx.check(rc, "ms_map_publish")
+    return res
+
+
 class KeyframeTable:
     """Keyframe::mapPoints of every keyframe on the device: kf_mp [n_kf, stride] int32, entry (k, j) = the map-point table row bound to
     keypoint j of the keyframe in slot k, -1 for none.  The queries take n_mp (rows of the map-point table; an entry outside [0, n_mp)
